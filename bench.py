@@ -1,6 +1,6 @@
 """bench.py -- training frames/sec of the sin-inn INN training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,11 +9,18 @@ fused Adam) on a batch drawn by the frame-window sampler kernel from a synthetic
 resident in HBM.  Workload = BASELINE configs[1]: 8 GLOW blocks (-c 4 per level x 2 levels), 256x256x3 frames,
 batch 16 per GPU, fp32 (f32 MFMA).  N>1: weak scaling, one RCCL all-reduce of the flat gradient per step.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused 3x3 coupling conv 256 -> 2*Co channels +
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times K steps and prints the headline (`value` frames/s,
+`ms_per_step`); `roofline`, `cpu_baseline` and `gpu_clocks` are null.  With --full the run also measures them:
+`roofline` is for the dominant kernel (the fused 3x3 coupling conv 256 -> 2*Co channels +
 affine + log-det at level 0): `achieved` / `frac` count the FLOPs the matrix pipe EXECUTES (Winograd F(2x2,3x3) in fp32:
 2.25x fewer than the direct convolution `achieved_algorithmic` credits) over the kernel's execution window (in-kernel
 stamps == the duration a rocprofv3 kernel trace reports; the HIP-event bracket is given beside it); `cpu_baseline` times
 the CPU oracle (torch-CPU restatement, "port") on every host core the process may use.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy: `loss` (the logged training loss,
+float64), `params` (every parameter after the step's Adam update) and `grads` (the step's parameter gradients), float32 in
+model.parameters() order, and with --with-flow `flow_grad` (the gradient w.r.t. the flow field).  Inputs are seeded, so
+two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -170,6 +177,23 @@ def cpu_baseline(args, opt, seconds_budget=30.0):
                       + ('' if b == args.batch else f' (frames/s = batch / step time, per-frame normalised from batch {b}, not the benchmark batch {args.batch})')
                       + f', {args.width}x{args.height}, -c {args.num_coupling}, {getattr(args, "arch", "SRF")}, '
                       f'{torch.get_num_threads()} threads = every core this process may use'}
+
+
+DUMP_MAX_ELEMS = 4 << 20       # per array (16 MiB of float32): the at most four arrays of --dump-outputs stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """One .npy per array, float64 tensors as float64 and everything else as float32.  An array with more than DUMP_MAX_ELEMS
+    elements is written as a fixed sample: the same seeded positions, in ascending order, in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            pick = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t[pick.to(t.device)]
+        t = t.to('cpu', torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(path, name + '.npy'), t.numpy())
 
 
 _JSON_FD = [None]
@@ -365,6 +389,11 @@ def main():
     ap.add_argument('--overlap', choices=['auto', 'full', 'wgrad', 'none'], default='auto',
                     help='full: forward / reverse pass chains on two streams + weight gradients on a third (default below 2 M level-0 '
                          'pixels per batch); wgrad: one chain + the weight-gradient stream; none == --no-overlap')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: the dominant kernel\'s '
+                    'execution window in the timed region, single-stream steps for roofline / roofline.classes, the GPU clocks, the '
+                    'per-step all-reduce time (N>1) and the CPU oracle baseline (unless --no-cpu-baseline)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps write the loss, parameters and '
+                    'gradients of the last step as DIR/<name>.npy (float32 / float64; arrays above 4 M elements as a fixed sample)')
     args = ap.parse_args()
     claim_stdout()
     preset = CONFIGS[args.config]
@@ -434,7 +463,8 @@ def main():
     b, m0 = args.batch, args.batch * lh * lw
     co0 = 24
 
-    timer = KernelTimer(lh, dev)      # forward 3x3 coupling conv (256 -> 2*24 columns) at level-0 resolution
+    # --full: forward 3x3 coupling conv (256 -> 2*24 columns) at level-0 resolution
+    timer = KernelTimer(lh, dev) if args.full else None
 
     # frame indices of every step drawn up front and resident in HBM like the clip itself: a per-step pageable H2D copy is
     # synchronous -- it would make the host wait for the previous step's last kernel before it may enqueue the next step
@@ -495,19 +525,21 @@ def main():
         step()
     barrier()
     print(f'[bench] rank {rank}: warm-up done', file=sys.stderr, flush=True)
-    clocks_before = gpu_clocks(local)
+    clocks_before = gpu_clocks(local) if args.full else None
     ranks = rank_table(local)
     assert len(ranks) == ws == args.gpus, f'--gpus {args.gpus}: {len(ranks)} ranks answered, world size {ws}'
-    sdist.TIMING[0] = [] if ws > 1 else None
-    timer.start()
+    sdist.TIMING[0] = [] if ws > 1 and args.full else None
+    if timer:
+        timer.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     t_issue = time.perf_counter() - t0      # host time to enqueue the steps (GPU still running)
     barrier()
     dt = time.perf_counter() - t0
-    clocks_after = gpu_clocks(local)
-    timer.stop()
+    clocks_after = gpu_clocks(local) if args.full else None
+    if timer:
+        timer.stop()
     allreduce_ms = None
     if sdist.TIMING[0]:
         allreduce_ms = sum(a.elapsed_time(b) for a, b in sdist.TIMING[0]) / len(sdist.TIMING[0])
@@ -516,13 +548,21 @@ def main():
         t = torch.tensor([dt], device=dev if torch.distributed.get_backend() == 'nccl' else 'cpu', dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before the single-stream steps of --full, which train the model further
+        params = list(model.parameters())
+        outs = {'loss': model._logged['train'].double(), 'params': torch.cat([p.detach().reshape(-1) for p in params]),
+                'grads': torch.cat([p.grad.reshape(-1) for p in params if p.grad is not None])}
+        if args.with_flow:
+            outs['flow_grad'] = flow_field.grad
+        dump_outputs(args.dump_outputs, outs)
 
     # The roofline needs kernel durations with the chip to itself: in the timed region above the blocks of a kernel
     # interleave with the other pass chain's and the weight-gradient stream's kernels, and a rocprofv3 trace of this
     # command serialises most of that overlap away.  So the same step is run a few more times on ONE stream (not part of
     # `value`): the dominant kernel is timed there, and so is every kernel class of the block executor (roofline.classes).
     iso, classes, iso_ms = None, None, None
-    if True:                                                # every rank runs them: the optimiser step holds a collective
+    if args.full:                                           # every rank runs them: the optimiser step holds a collective
         _m.USE_SIDE_STREAM[0] = False
         model.overlap_passes = False
         model.opt.hip_graph = False                         # the per-class event brackets live in the executors' launch path
@@ -566,132 +606,133 @@ def main():
     print(f'[bench] timed region {dt:.3f}s for {args.steps} steps (host enqueue time {t_issue:.3f}s)', file=sys.stderr, flush=True)
     ms_per_step = dt / args.steps * 1e3
     value = ws * b * args.steps / dt
-    # roofline of the dominant kernel: algorithmic FLOPs (2 * pixels * 9*256 * 2*Co) per launch
-    # Per-launch duration of the dominant kernel: its EXECUTION WINDOW (first block's entry to last block's exit, stamped from
-    # inside the kernel, sininn_conv_args.stamp) over the single-stream launches -- the quantity a rocprofv3 kernel trace
-    # reports for the same kernel + grid (profiles/*_single_stream_by_grid.csv; the window starts a few us after the
-    # dispatch, so the trace reads ~5 % longer).  The HIP-event bracket on the launch stream is reported next to it: it also
-    # contains the two event packets' dispatch gaps (~12 us), i.e. time in which the GPU is free for other streams' kernels.
-    tm = iso or timer
-    kms_events = tm.mean_event_ms()
-    kms = tm.stamp_ms if tm.stamp_ms is not None else kms_events
-    kms_src = ('in-kernel execution window (s_memrealtime stamps), single-stream steps run right after the timed region'
-               if tm.stamp_ms is not None else 'HIP events on the launch stream (no in-kernel stamps in this kernel), single-stream steps '
-               'run right after the timed region')
-    flops = 2.0 * m0 * 9 * 256 * (2 * co0)
-    roof = None
     bf16 = args.precision == 'bf16'
-    peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_F32_MFMA_TFLOPS
-    traffic, traffic_src = None, None
-    tpath = os.path.join(ROOT, 'profiles', 'traffic_dominant.json')   # PMC pass is a separate rocprofv3 run (committed)
-    if os.path.isfile(tpath) and args.config in (1, 2) and not custom:
-        tj = json.load(open(tpath))
-        traffic, traffic_src = tj.get('hbm_bytes_per_launch'), tj.get('source')
-    # rocprofv3's duration of the same kernels from the committed trace of this build (profiles/roofline_kernels.json, written by
-    # tools/refresh_profiles.sh from profiles/*_single_stream_by_grid.csv with the commit it was measured at): `frac` is computed
-    # from THAT when it is there -- a number the reader can re-derive from profiles/ -- and the live stamp window is kept beside it
-    rk = None
-    rpath = os.path.join(ROOT, 'profiles', 'roofline_kernels.json')
-    if os.path.isfile(rpath) and args.config in (1, 2) and not custom and not bf16 and not irn:
-        rk = json.load(open(rpath))
-    kms_live = kms
-    if rk and rk.get('named'):
-        kms = rk['named']['avg_us'] * 1e-3
-    if kms:
-        ach = flops / (kms * 1e-3) / 1e12
-        hid_bytes = 2.0 if bf16 else 4.0
-        abytes = hid_bytes * m0 * 256 + 4.0 * m0 * 3 * co0 + hid_bytes * 9 * 256 * 2 * co0
-        kernel = ('conv_bf16_kernel<3,32,1,8,true> (fused 3x3 coupling conv 256->48 + affine + log-det, level 0; direct implicit GEMM on '
-                  'v_mfma_f32_32x32x16_bf16, bf16 hidden tensor in, fp32 flow out)') if bf16 else \
-                 ('wino_kernel<2,8,2> (fused 3x3 coupling conv 256->48 + affine + log-det, level 0; Winograd F(2x2,3x3): executes '
-                  '2.25x fewer MFMA FLOPs than the algorithmic direct-conv count used here)')
-        # fp32: the kernel is Winograd F(2x2,3x3) -- the matrix pipe executes 16 multiplies per 2x2 outputs where the direct
-        # convolution the algorithmic count credits needs 36.  A roofline fraction has to be about work the pipe EXECUTES, so
-        # `achieved` / `frac` are the executed rate; the algorithmic (direct-convolution) rate is kept beside it.
-        executed = ach if bf16 else ach / 2.25
-        roof = {'bound': 'mfma', 'achieved': executed, 'peak': peak, 'unit': 'TFLOP/s',
-                'frac': executed / peak, 'traffic': traffic, 'traffic_source': traffic_src,
-                'kernel': kernel,
-                'achieved_algorithmic': ach, 'frac_algorithmic': ach / peak,
-                'launches_timed': tm.count, 'avg_ms': kms,
-                'avg_ms_source': (f"rocprofv3 --kernel-trace of `bench.py --no-overlap` on commit {rk.get('commit')}: {rk['named']['kernel']} "
-                                  f"grid {rk['named']['grid']}, {rk['named']['calls']} calls ({rk.get('source')})") if rk and rk.get('named') else kms_src,
-                'avg_ms_rocprof': rk['named']['avg_us'] * 1e-3 if rk and rk.get('named') else None,
-                'avg_ms_execution_window': kms_live, 'avg_ms_execution_window_source': kms_src,
-                'avg_ms_hip_events': kms_events,
-                'timed_region': {'launches': timer.count, 'avg_ms_execution_window': timer.stamp_ms,
-                                 'avg_ms_hip_events': timer.mean_event_ms(),
-                                 'note': 'three streams in flight: the window contains other kernels\' blocks'},
-                'alg_flops_per_launch': flops, 'executed_flops_per_launch': flops if bf16 else flops / 2.25,
-                'alg_bytes_per_launch': abytes}
-        if not bf16:
-            roof['limiter'] = ('nearest roof is the f32 matrix pipe (168 algorithmic FLOP/B against a ridge of 20), but the pipe is '
-                               f'only {executed / peak:.0%} busy: vector-ALU and LDS instructions do not hide behind an MFMA on this chip '
-                               '(tools/mfma_valu.hip: +2.5 / +4.6 clocks each per 32-clock MFMA), so the per-lane Winograd transforms and '
-                               'the fragment reads cost issue time in the K loop (~0.83 of the pipe there), and the block-level ablation '
-                               '(profiles/r03_wino_fwd_ablation.log) puts the rest in operand staging, the chunk barrier and the epilogue')
-        else:
-            roof['limiter'] = ('nearest roof is the bf16 matrix pipe; the MFMA loop is LDS-bandwidth-bound (one 16-byte fragment read per '
-                               '32x32x16 MFMA and wave = the 128 B/clk of a CU), and phase stamps (DESIGN 6) put two thirds of the block time '
-                               'in operand staging and the epilogue store drain around it')
-        # the same launch against the HBM roof (north_star quotes an HBM fraction): algorithmic bytes / time / 8 TB/s
-        roof['hbm'] = {'achieved': abytes / (kms * 1e-3) / 1e9, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                       'frac': abytes / (kms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                       'note': 'FLOP/B far above the ridge: the kernel is matrix-pipe-bound, this fraction is low by nature'}
-        roof['classes'] = classes
-        roof['single_stream_ms_per_step'] = iso_ms
-        if not bf16:
-            # the kernel that is dominant BY TIME: the grouped Winograd weight gradient of a 3x3 block (four convs, one launch)
-            wg = next((c for c in classes if c['class'].startswith('3x3 weight gradients')), None)
-            wflops = 2.0 * m0 * 9 * (24 * 256 + 256 * 48) * 2          # per block, either level: SURVEY 8d (43.49 GFLOP)
-            wms_live = wg['ms_per_step'] / max(wg['launches_per_step'], 1) if wg else None
-            wms_prof = rk['by_time']['avg_us'] * 1e-3 if rk and rk.get('by_time') else None
-            wms = wms_prof or wms_live
-            if wms:
-                roof['dominant_by_time'] = {
-                    'kernel': 'wgrad_wino_group_kernel<4,2> (the four 3x3 weight gradients of a GLOW block in one launch, Winograd F(2x2,3x3) '
-                              'on v_mfma_f32_16x16x4_f32, + ordered slab reduce)',
-                    'bound': 'mfma', 'peak': peak, 'unit': 'TFLOP/s', 'alg_flops_per_launch': wflops, 'executed_flops_per_launch': wflops / 2.25,
-                    'avg_ms': wms, 'avg_ms_rocprof': wms_prof, 'avg_ms_live_event_bracket_incl_reduce': wms_live,
-                    'avg_ms_source': (f"rocprofv3 --kernel-trace on commit {rk.get('commit')}: grid {rk['by_time']['grid']}, "
-                                      f"{rk['by_time']['calls']} calls, {rk['by_time']['percent']} % of the GPU time of a single-stream step "
-                                      f"({rk.get('source')})") if wms_prof else 'HIP-event bracket of the class (kernel + reduce), single-stream steps',
-                    'achieved': wflops / 2.25 / (wms * 1e-3) / 1e12, 'frac': wflops / 2.25 / (wms * 1e-3) / 1e12 / peak,
-                    'achieved_algorithmic': wflops / (wms * 1e-3) / 1e12}
-        # whole-step algorithmic rate (train step = 6 x forward FLOPs)
-        fwd = 0.0
-        for lvl, (mm, cc) in enumerate(((m0, 48), (m0 // 4, 192))):
-            for blk in range(args.num_coupling):
-                kk = 9 if blk % 2 == 0 else 1
-                fwd += 2.0 * mm * kk * (cc // 2 * 256 + 256 * cc) * 2
-        # executed: the 3x3 subnets (Winograd in fp32: / 2.25), the 1x1 subnets as counted
-        fwd_ex = 0.0
-        for lvl, (mm, cc) in enumerate(((m0, 48), (m0 // 4, 192))):
-            for blk in range(args.num_coupling):
-                kk = 9 if blk % 2 == 0 else 1
-                f = 2.0 * mm * kk * (cc // 2 * 256 + 256 * cc) * 2
-                fwd_ex += f / 2.25 if (kk == 9 and not bf16) else f
-        roof['step'] = {'alg_tflop_per_step': 6 * fwd / 1e12, 'alg_tflops': 6 * fwd / (ms_per_step * 1e-3) / 1e12,
-                        'frac_of_peak_algorithmic': 6 * fwd / (ms_per_step * 1e-3) / 1e12 / peak,
-                        'executed_tflops': 6 * fwd_ex / (ms_per_step * 1e-3) / 1e12,
-                        'frac_of_peak': 6 * fwd_ex / (ms_per_step * 1e-3) / 1e12 / peak}
-    if irn:
-        # dominant kernel class of the IRN step = the one with the largest single-stream time; same accounting as above
-        # (algorithmic direct-convolution FLOPs / HIP-event bracket on the launch stream, f32 matrix-pipe peak)
-        dom = max((c for c in classes if c.get('alg_tflops')), key=lambda c: c['ms_per_step'])
-        fwd = 0.0
-        for mm, ch in ((m0, 48), (m0 // 4, 192)):
-            s1 = min(opt.lr_dims, ch // 2)
-            for cin, cout in ((ch - s1, s1), (s1, ch - s1), (s1, ch - s1)):          # F, G, H (archs.py:135-160)
-                fwd += args.num_coupling * 2.0 * mm * 9 * (32 * (4 * cin + 192) + (cin + 128) * cout)
-        roof = {'bound': 'mfma', 'achieved': dom['executed_tflops'], 'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': dom['frac'], 'achieved_algorithmic': dom['alg_tflops'], 'frac_algorithmic': dom['frac_algorithmic'], 'traffic': None,
-                'kernel': 'IRN: ' + dom['class'] + ' -- average over all its launches of a step (both levels)',
-                'avg_ms': dom['ms_per_step'] / max(dom['launches_per_step'], 1),
-                'avg_ms_source': 'HIP events on the launch stream, single-stream steps run right after the timed region',
-                'classes': classes, 'single_stream_ms_per_step': iso_ms,
-                'step': {'alg_tflop_per_step': 6 * fwd / 1e12, 'alg_tflops': 6 * fwd / (ms_per_step * 1e-3) / 1e12,
-                         'frac_of_peak': 6 * fwd / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS}}
+    roof = None
+    if args.full:
+        # roofline of the dominant kernel: algorithmic FLOPs (2 * pixels * 9*256 * 2*Co) per launch
+        # Per-launch duration of the dominant kernel: its EXECUTION WINDOW (first block's entry to last block's exit, stamped from
+        # inside the kernel, sininn_conv_args.stamp) over the single-stream launches -- the quantity a rocprofv3 kernel trace
+        # reports for the same kernel + grid (profiles/*_single_stream_by_grid.csv; the window starts a few us after the
+        # dispatch, so the trace reads ~5 % longer).  The HIP-event bracket on the launch stream is reported next to it: it also
+        # contains the two event packets' dispatch gaps (~12 us), i.e. time in which the GPU is free for other streams' kernels.
+        tm = iso or timer
+        kms_events = tm.mean_event_ms()
+        kms = tm.stamp_ms if tm.stamp_ms is not None else kms_events
+        kms_src = ('in-kernel execution window (s_memrealtime stamps), single-stream steps run right after the timed region'
+                   if tm.stamp_ms is not None else 'HIP events on the launch stream (no in-kernel stamps in this kernel), single-stream steps '
+                   'run right after the timed region')
+        flops = 2.0 * m0 * 9 * 256 * (2 * co0)
+        peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_F32_MFMA_TFLOPS
+        traffic, traffic_src = None, None
+        tpath = os.path.join(ROOT, 'profiles', 'traffic_dominant.json')   # PMC pass is a separate rocprofv3 run (committed)
+        if os.path.isfile(tpath) and args.config in (1, 2) and not custom:
+            tj = json.load(open(tpath))
+            traffic, traffic_src = tj.get('hbm_bytes_per_launch'), tj.get('source')
+        # rocprofv3's duration of the same kernels from the committed trace of this build (profiles/roofline_kernels.json, written by
+        # tools/refresh_profiles.sh from profiles/*_single_stream_by_grid.csv with the commit it was measured at): `frac` is computed
+        # from THAT when it is there -- a number the reader can re-derive from profiles/ -- and the live stamp window is kept beside it
+        rk = None
+        rpath = os.path.join(ROOT, 'profiles', 'roofline_kernels.json')
+        if os.path.isfile(rpath) and args.config in (1, 2) and not custom and not bf16 and not irn:
+            rk = json.load(open(rpath))
+        kms_live = kms
+        if rk and rk.get('named'):
+            kms = rk['named']['avg_us'] * 1e-3
+        if kms:
+            ach = flops / (kms * 1e-3) / 1e12
+            hid_bytes = 2.0 if bf16 else 4.0
+            abytes = hid_bytes * m0 * 256 + 4.0 * m0 * 3 * co0 + hid_bytes * 9 * 256 * 2 * co0
+            kernel = ('conv_bf16_kernel<3,32,1,8,true> (fused 3x3 coupling conv 256->48 + affine + log-det, level 0; direct implicit GEMM on '
+                      'v_mfma_f32_32x32x16_bf16, bf16 hidden tensor in, fp32 flow out)') if bf16 else \
+                     ('wino_kernel<2,8,2> (fused 3x3 coupling conv 256->48 + affine + log-det, level 0; Winograd F(2x2,3x3): executes '
+                      '2.25x fewer MFMA FLOPs than the algorithmic direct-conv count used here)')
+            # fp32: the kernel is Winograd F(2x2,3x3) -- the matrix pipe executes 16 multiplies per 2x2 outputs where the direct
+            # convolution the algorithmic count credits needs 36.  A roofline fraction has to be about work the pipe EXECUTES, so
+            # `achieved` / `frac` are the executed rate; the algorithmic (direct-convolution) rate is kept beside it.
+            executed = ach if bf16 else ach / 2.25
+            roof = {'bound': 'mfma', 'achieved': executed, 'peak': peak, 'unit': 'TFLOP/s',
+                    'frac': executed / peak, 'traffic': traffic, 'traffic_source': traffic_src,
+                    'kernel': kernel,
+                    'achieved_algorithmic': ach, 'frac_algorithmic': ach / peak,
+                    'launches_timed': tm.count, 'avg_ms': kms,
+                    'avg_ms_source': (f"rocprofv3 --kernel-trace of `bench.py --no-overlap` on commit {rk.get('commit')}: {rk['named']['kernel']} "
+                                      f"grid {rk['named']['grid']}, {rk['named']['calls']} calls ({rk.get('source')})") if rk and rk.get('named') else kms_src,
+                    'avg_ms_rocprof': rk['named']['avg_us'] * 1e-3 if rk and rk.get('named') else None,
+                    'avg_ms_execution_window': kms_live, 'avg_ms_execution_window_source': kms_src,
+                    'avg_ms_hip_events': kms_events,
+                    'timed_region': {'launches': timer.count, 'avg_ms_execution_window': timer.stamp_ms,
+                                     'avg_ms_hip_events': timer.mean_event_ms(),
+                                     'note': 'three streams in flight: the window contains other kernels\' blocks'},
+                    'alg_flops_per_launch': flops, 'executed_flops_per_launch': flops if bf16 else flops / 2.25,
+                    'alg_bytes_per_launch': abytes}
+            if not bf16:
+                roof['limiter'] = ('nearest roof is the f32 matrix pipe (168 algorithmic FLOP/B against a ridge of 20), but the pipe is '
+                                   f'only {executed / peak:.0%} busy: vector-ALU and LDS instructions do not hide behind an MFMA on this chip '
+                                   '(tools/mfma_valu.hip: +2.5 / +4.6 clocks each per 32-clock MFMA), so the per-lane Winograd transforms and '
+                                   'the fragment reads cost issue time in the K loop (~0.83 of the pipe there), and the block-level ablation '
+                                   '(profiles/r03_wino_fwd_ablation.log) puts the rest in operand staging, the chunk barrier and the epilogue')
+            else:
+                roof['limiter'] = ('nearest roof is the bf16 matrix pipe; the MFMA loop is LDS-bandwidth-bound (one 16-byte fragment read per '
+                                   '32x32x16 MFMA and wave = the 128 B/clk of a CU), and phase stamps (DESIGN 6) put two thirds of the block time '
+                                   'in operand staging and the epilogue store drain around it')
+            # the same launch against the HBM roof (north_star quotes an HBM fraction): algorithmic bytes / time / 8 TB/s
+            roof['hbm'] = {'achieved': abytes / (kms * 1e-3) / 1e9, 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                           'frac': abytes / (kms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                           'note': 'FLOP/B far above the ridge: the kernel is matrix-pipe-bound, this fraction is low by nature'}
+            roof['classes'] = classes
+            roof['single_stream_ms_per_step'] = iso_ms
+            if not bf16:
+                # the kernel that is dominant BY TIME: the grouped Winograd weight gradient of a 3x3 block (four convs, one launch)
+                wg = next((c for c in classes if c['class'].startswith('3x3 weight gradients')), None)
+                wflops = 2.0 * m0 * 9 * (24 * 256 + 256 * 48) * 2          # per block, either level: SURVEY 8d (43.49 GFLOP)
+                wms_live = wg['ms_per_step'] / max(wg['launches_per_step'], 1) if wg else None
+                wms_prof = rk['by_time']['avg_us'] * 1e-3 if rk and rk.get('by_time') else None
+                wms = wms_prof or wms_live
+                if wms:
+                    roof['dominant_by_time'] = {
+                        'kernel': 'wgrad_wino_group_kernel<4,2> (the four 3x3 weight gradients of a GLOW block in one launch, Winograd F(2x2,3x3) '
+                                  'on v_mfma_f32_16x16x4_f32, + ordered slab reduce)',
+                        'bound': 'mfma', 'peak': peak, 'unit': 'TFLOP/s', 'alg_flops_per_launch': wflops, 'executed_flops_per_launch': wflops / 2.25,
+                        'avg_ms': wms, 'avg_ms_rocprof': wms_prof, 'avg_ms_live_event_bracket_incl_reduce': wms_live,
+                        'avg_ms_source': (f"rocprofv3 --kernel-trace on commit {rk.get('commit')}: grid {rk['by_time']['grid']}, "
+                                          f"{rk['by_time']['calls']} calls, {rk['by_time']['percent']} % of the GPU time of a single-stream step "
+                                          f"({rk.get('source')})") if wms_prof else 'HIP-event bracket of the class (kernel + reduce), single-stream steps',
+                        'achieved': wflops / 2.25 / (wms * 1e-3) / 1e12, 'frac': wflops / 2.25 / (wms * 1e-3) / 1e12 / peak,
+                        'achieved_algorithmic': wflops / (wms * 1e-3) / 1e12}
+            # whole-step algorithmic rate (train step = 6 x forward FLOPs)
+            fwd = 0.0
+            for lvl, (mm, cc) in enumerate(((m0, 48), (m0 // 4, 192))):
+                for blk in range(args.num_coupling):
+                    kk = 9 if blk % 2 == 0 else 1
+                    fwd += 2.0 * mm * kk * (cc // 2 * 256 + 256 * cc) * 2
+            # executed: the 3x3 subnets (Winograd in fp32: / 2.25), the 1x1 subnets as counted
+            fwd_ex = 0.0
+            for lvl, (mm, cc) in enumerate(((m0, 48), (m0 // 4, 192))):
+                for blk in range(args.num_coupling):
+                    kk = 9 if blk % 2 == 0 else 1
+                    f = 2.0 * mm * kk * (cc // 2 * 256 + 256 * cc) * 2
+                    fwd_ex += f / 2.25 if (kk == 9 and not bf16) else f
+            roof['step'] = {'alg_tflop_per_step': 6 * fwd / 1e12, 'alg_tflops': 6 * fwd / (ms_per_step * 1e-3) / 1e12,
+                            'frac_of_peak_algorithmic': 6 * fwd / (ms_per_step * 1e-3) / 1e12 / peak,
+                            'executed_tflops': 6 * fwd_ex / (ms_per_step * 1e-3) / 1e12,
+                            'frac_of_peak': 6 * fwd_ex / (ms_per_step * 1e-3) / 1e12 / peak}
+        if irn:
+            # dominant kernel class of the IRN step = the one with the largest single-stream time; same accounting as above
+            # (algorithmic direct-convolution FLOPs / HIP-event bracket on the launch stream, f32 matrix-pipe peak)
+            dom = max((c for c in classes if c.get('alg_tflops')), key=lambda c: c['ms_per_step'])
+            fwd = 0.0
+            for mm, ch in ((m0, 48), (m0 // 4, 192)):
+                s1 = min(opt.lr_dims, ch // 2)
+                for cin, cout in ((ch - s1, s1), (s1, ch - s1), (s1, ch - s1)):          # F, G, H (archs.py:135-160)
+                    fwd += args.num_coupling * 2.0 * mm * 9 * (32 * (4 * cin + 192) + (cin + 128) * cout)
+            roof = {'bound': 'mfma', 'achieved': dom['executed_tflops'], 'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': dom['frac'], 'achieved_algorithmic': dom['alg_tflops'], 'frac_algorithmic': dom['frac_algorithmic'], 'traffic': None,
+                    'kernel': 'IRN: ' + dom['class'] + ' -- average over all its launches of a step (both levels)',
+                    'avg_ms': dom['ms_per_step'] / max(dom['launches_per_step'], 1),
+                    'avg_ms_source': 'HIP events on the launch stream, single-stream steps run right after the timed region',
+                    'classes': classes, 'single_stream_ms_per_step': iso_ms,
+                    'step': {'alg_tflop_per_step': 6 * fwd / 1e12, 'alg_tflops': 6 * fwd / (ms_per_step * 1e-3) / 1e12,
+                             'frac_of_peak': 6 * fwd / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS}}
     out = {'metric': 'training frames/sec at 256x256 bs=16', 'value': value, 'unit': 'frames/s', 'n_gpus': ws,
            'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16' if bf16 else 'f32', 'data': 'synthetic',
@@ -706,14 +747,14 @@ def main():
         out['config']['workload'] += f'; + the TCR branch (lambda_bwd_tcr 1, {args.tcr_iters} iteration(s) per step)'
         out['config']['with_tcr'] = args.tcr_iters
     out['gpu_clocks'] = {'before_timed_region': clocks_before, 'after_timed_region': clocks_after,
-                         'source': '/sys/class/drm/card*/device/pp_dpm_{sclk,mclk} (active level), gpu_busy_percent'}
+                         'source': '/sys/class/drm/card*/device/pp_dpm_{sclk,mclk} (active level), gpu_busy_percent'} if args.full else None
     out['config']['hip_graph'] = bool(args.graph == 'on' and any('graph' in v for v in model.__dict__.get('_graphs', {}).values()))
     if args.with_flow:
         out['config']['workload'] += '; preceded in every step by the pair_flow warp + photometric metric + flow gradient on the batch'
         out['config']['with_flow'] = True
     if args.config not in (1, 2) or custom:
         out['metric'] = f'training frames/sec at {args.width}x{args.height} bs={b}' + (' (IRN architecture)' if irn else '')
-    if not args.no_cpu_baseline and ws == 1:
+    if args.full and not args.no_cpu_baseline and ws == 1:
         out['cpu_baseline'] = cpu_baseline(args, opt)
     else:
         out['cpu_baseline'] = None

@@ -246,12 +246,12 @@ def test_pack_miss_after_validation_is_ordered_across_streams():
 
 
 def test_bench_with_flow_line_is_well_formed(tmp_path):
-    """`bench.py --with-flow` (BASELINE configs[3] as named: pair_flow warp + INN) at a toy size: one JSON line with the contract's
-    keys, the roofline / cpu_baseline objects and the two HBM rows of the warp."""
+    """`bench.py --full --with-flow` (BASELINE configs[3] as named: pair_flow warp + INN) at a toy size: one JSON line with the
+    contract's keys, the roofline / cpu_baseline objects and the two HBM rows of the warp."""
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', '3', '--with-flow', '--size', '64', '--batch', '2',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--config', '3', '--with-flow', '--size', '64', '--batch', '2',
                           '--num-coupling', '1', '--frames', '24', '--steps', '2', '--warmup', '1', '--cpu-batch', '1'],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -267,3 +267,31 @@ def test_bench_with_flow_line_is_well_formed(tmp_path):
     warp = [c for c in r['classes'] if c['class'].startswith('flow warp')]
     assert len(warp) == 2 and all(c['bound'] == 'hbm' and c['achieved_gbs'] > 0 for c in warp)
     assert rec['cpu_baseline']['kind'] == 'port' and rec['cpu_baseline']['cores'] >= 1
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the headline keys, `ms_per_step` per timed step, null roofline / cpu_baseline; and
+    --dump-outputs: the last timed step's loss, parameters, gradients and flow gradient as float .npy files that agree between
+    two runs with the same arguments (seeded inputs)."""
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--config', '3', '--with-flow', '--size', '64', '--batch', '2',
+           '--num-coupling', '1', '--frames', '24', '--steps', '3', '--warmup', '1']
+    dumps = []
+    for run in ('a', 'b'):
+        out = subprocess.run(cmd + ['--dump-outputs', str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec['steps'] == 3 and rec['unit'] == 'frames/s' and rec['higher_is_better'] is True and rec['dtype'] == 'bf16'
+        assert rec['value'] > 0 and abs(rec['value'] * rec['ms_per_step'] / 1e3 / 2 - 1) < 1e-6      # batch 2 per step
+        assert rec['roofline'] is None and rec['cpu_baseline'] is None
+        arrays = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert sorted(arrays) == ['flow_grad', 'grads', 'loss', 'params']
+        assert arrays['loss'].dtype == np.float64 and arrays['loss'].shape == (1,)
+        assert all(a.dtype == np.float32 for k, a in arrays.items() if k != 'loss')
+        assert arrays['params'].shape == arrays['grads'].shape and arrays['flow_grad'].size == 2 * 2 * 64 * 64
+        assert all(np.isfinite(a).all() for a in arrays.values()) and np.abs(arrays['grads']).max() > 0
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert relerr(torch.from_numpy(dumps[1][k]), torch.from_numpy(dumps[0][k])) < 1e-4, k

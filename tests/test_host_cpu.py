@@ -191,6 +191,23 @@ def test_bench_self_launches_its_ranks_cpu_rehearsal(n):
     assert d['ms_per_step_max_over_ranks'] > 0 and 'all-reduce' in d['collective']
 
 
+def test_bench_dump_outputs_writes_floats_and_a_fixed_sample_of_large_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, everything else is written as float32; an array above DUMP_MAX_ELEMS is
+    written as the same seeded sample (ascending positions) every time, so that two builds' dumps line up element by element."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_MAX_ELEMS', 1000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), {'big': torch.arange(5000, dtype=torch.float32), 'small': torch.ones(2, 5, dtype=torch.float16),
+                                                 'loss': torch.tensor(2.5, dtype=torch.float64)})
+    big = np.load(tmp_path / 'a' / 'big.npy')
+    assert big.dtype == np.float32 and big.shape == (1000,) and np.array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))
+    assert (np.diff(big) > 0).all() and big[0] >= 0 and big[-1] < 5000
+    small, loss = np.load(tmp_path / 'a' / 'small.npy'), np.load(tmp_path / 'a' / 'loss.npy')
+    assert small.dtype == np.float32 and small.shape == (10,) and (small == 1).all()
+    assert loss.dtype == np.float64 and loss.shape == (1,) and loss[0] == 2.5
+
+
 def test_checkpoint_holds_tensors_and_primitives_only(tmp_path):
     """a checkpoint must load back (torch.load default weights_only=True) and must not carry the clip."""
     import argparse

@@ -1,4 +1,5 @@
-"""Print the headline and the per-class roofline of a bench.py JSON line (file holding the line, or stdin)."""
+"""Print the headline and the per-class roofline of a bench.py JSON line (file holding the line, or stdin).  The roofline and
+the CPU baseline are in lines of `bench.py --full` only."""
 import json
 import sys
 
