@@ -35,7 +35,7 @@ extern "C" {
 int sininn_version(void);
 const char* sininn_last_error(void);
 /* sizeof() of descriptor struct `which` as THIS library was compiled: 0 sininn_conv_args, 1 sininn_wgrad_item,
- * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc; 0 for an unknown index.  A binding written in
+ * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args; 0 for an unknown index.  A binding written in
  * another language (the ctypes mirrors in sin-inn_amd/_lib.py) checks its own layout against it at load time (ABI v4). */
 size_t sininn_sizeof(int which);
 /* A HIP stream at an explicit priority (lower number = higher priority; range from sininn_stream_priority_range: `least` is the
@@ -93,6 +93,11 @@ typedef struct sininn_pack_desc {
 } sininn_pack_desc;
 int sininn_pack_work_items(const sininn_pack_desc* host_desc);
 int sininn_pack_batch(const sininn_pack_desc* descs, int n, int total_work, void* stream);
+/* The same batched refresh for bf16 packs (sininn_pack_conv_weights_bf16 layouts: w_fwd [taps][Np][pad16(Cin)] and
+ * w_dgrad [taps][Cdp][pad16(N)] hold bf16, b_fwd fp32), with src_n / gap_begin / gap_len as above; wino_* must be 0.
+ * work_begin is the prefix sum of sininn_pack_work_items_bf16 (0 for a descriptor this layout cannot serve). */
+int sininn_pack_work_items_bf16(const sininn_pack_desc* host_desc);
+int sininn_pack_batch_bf16(const sininn_pack_desc* descs, int n, int total_work, void* stream);
 
 /* Packed column order used by the coupling epilogue for a subnet with 2*Co outputs (s | t):
  * `tile`-column MFMA tile q = [ s[h*q .. h*q+h-1] | t[h*q .. h*q+h-1] ], h = tile/2, tile in {16, 32}
@@ -322,6 +327,40 @@ typedef struct sininn_dense_args {
 size_t sininn_dense_workspace_bytes(int B, int H, int W, int cin, int cout);
 int sininn_dense_forward(const sininn_dense_args* args, void* stream);
 int sininn_dense_backward(const sininn_dense_args* args, void* stream, void* wgrad_stream);
+
+/* Mixed-precision DenseBlock (the IRN path's --precision bf16): the same launch sequence on the bf16 matrix pipe.
+ * Precision contract: the conv subnets compute in bf16 with fp32 accumulation, the invertible flow stays fp32.
+ *   - stored as bf16 (round to nearest even, once): the feature buffer buf [M][cinp + 128] -- the block input x (pad channels
+ *     [cin, cinp) zero) and conv1-4's outputs after bias + LeakyReLU(0.2) in fp32 -- and the five weight packs;
+ *   - fp32: biases, accumulators, every epilogue, conv5's output with its InvBlockExp tail, dF / dD / dh / dv and the
+ *     parameter gradients.  dD and each finished 32-channel slot of dF are rounded to bf16 while a data-gradient or
+ *     weight-gradient kernel stages them; dF accumulates in fp32.  The LeakyReLU-backward gate is the stored bf16 feature.
+ * Packs (sininn_pack_batch_bf16 / sininn_pack_conv_weights_bf16 layouts) for conv i = 0..4 in the padded channel order:
+ *   w_fwd[i]   [9][Np_i][Kp_i] bf16, Np_i = 32 (i < 4) or pad16(pad8(cout)), Kp_i = pad16(cinp + 32 i)
+ *   b_fwd[i]   [Np_i] fp32
+ *   w_dgrad[i] [9][pad16(cinp + 32 i)][Kd_i] bf16, Kd_i = 32 (i < 4) or pad16(pad8(cout))
+ * Every extent is checked (struct_bytes, element counts, dtype flags) before anything is launched. */
+typedef struct sininn_dense_bf16_args {
+  size_t struct_bytes;                             /* must be sizeof(sininn_dense_bf16_args)                               */
+  int buf_bf16, w_bf16;                            /* dtype flags: must both be 1 (buf and the packs hold bf16)            */
+  int B, H, W, cin, cout, mode;                    /* modes 0-3 as in sininn_dense_args                                     */
+  float clamp;
+  const float* x; int x_stride;
+  const float* aux1; int aux1_stride;
+  const float* aux2;                               /* [M][cout] */
+  void* buf; float* out;                           /* bf16 [M][cinp + 128], fp32 [M][cout] */
+  const void* w_fwd[5]; const float* b_fwd[5]; const void* w_dgrad[5];
+  /* backward only */
+  const float* dout; float* dF; float* dD; float* dh; float* dv;   /* fp32, shapes as sininn_dense_args                 */
+  float* gw[5]; float* gb[5];
+  void* workspace; size_t workspace_bytes;         /* sininn_dense_bf16_workspace_bytes                                   */
+  /* extents in ELEMENTS of each buffer's own type */
+  size_t buf_elems, out_floats, aux2_floats, dout_floats, dF_floats, dD_floats, dh_floats, dv_floats;
+  size_t w_fwd_elems[5], b_fwd_floats[5], w_dgrad_elems[5];
+} sininn_dense_bf16_args;
+size_t sininn_dense_bf16_workspace_bytes(int B, int H, int W, int cin, int cout);
+int sininn_dense_forward_bf16(const sininn_dense_bf16_args* args, void* stream);
+int sininn_dense_backward_bf16(const sininn_dense_bf16_args* args, void* stream, void* wgrad_stream);
 
 /* ------------------------------------------------------------------------------------------------
  * One GLOW coupling block per call (FrEIA GLOWCouplingBlock.forward / its autograd, SURVEY Appendix A;

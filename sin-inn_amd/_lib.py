@@ -86,6 +86,28 @@ class DenseArgs(C.Structure):
         self.struct_bytes = C.sizeof(DenseArgs)
 
 
+class DenseBf16Args(C.Structure):
+    """Mirror of sininn_dense_bf16_args (bf16 buffers as void pointers; extents in elements of each buffer's own type)."""
+    _fields_ = [('struct_bytes', C.c_size_t), ('buf_bf16', C.c_int), ('w_bf16', C.c_int),
+                ('B', C.c_int), ('H', C.c_int), ('W', C.c_int), ('cin', C.c_int), ('cout', C.c_int), ('mode', C.c_int),
+                ('clamp', C.c_float),
+                ('x', c_f), ('x_stride', C.c_int), ('aux1', c_f), ('aux1_stride', C.c_int), ('aux2', c_f),
+                ('buf', C.c_void_p), ('out', c_f),
+                ('w_fwd', C.c_void_p * 5), ('b_fwd', c_f * 5), ('w_dgrad', C.c_void_p * 5),
+                ('dout', c_f), ('dF', c_f), ('dD', c_f), ('dh', c_f), ('dv', c_f),
+                ('gw', c_f * 5), ('gb', c_f * 5),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
+                ('buf_elems', C.c_size_t), ('out_floats', C.c_size_t), ('aux2_floats', C.c_size_t),
+                ('dout_floats', C.c_size_t), ('dF_floats', C.c_size_t), ('dD_floats', C.c_size_t),
+                ('dh_floats', C.c_size_t), ('dv_floats', C.c_size_t),
+                ('w_fwd_elems', C.c_size_t * 5), ('b_fwd_floats', C.c_size_t * 5), ('w_dgrad_elems', C.c_size_t * 5)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(DenseBf16Args)
+        self.buf_bf16 = self.w_bf16 = 1
+
+
 class PackDesc(C.Structure):
     """Mirror of sininn_pack_desc."""
     _fields_ = [('w', c_f), ('bias', c_f), ('N', C.c_int), ('Cin', C.c_int), ('ksize', C.c_int), ('colmap', c_i),
@@ -161,6 +183,11 @@ _SIGS = {
     'sininn_dense_workspace_bytes': (C.c_size_t, [C.c_int] * 5),
     'sininn_dense_forward': (C.c_int, [C.POINTER(DenseArgs), C.c_void_p]),
     'sininn_dense_backward': (C.c_int, [C.POINTER(DenseArgs), C.c_void_p, C.c_void_p]),
+    'sininn_dense_bf16_workspace_bytes': (C.c_size_t, [C.c_int] * 5),
+    'sininn_dense_forward_bf16': (C.c_int, [C.POINTER(DenseBf16Args), C.c_void_p]),
+    'sininn_dense_backward_bf16': (C.c_int, [C.POINTER(DenseBf16Args), C.c_void_p, C.c_void_p]),
+    'sininn_pack_work_items_bf16': (C.c_int, [C.POINTER(PackDesc)]),
+    'sininn_pack_batch_bf16': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'sininn_haar': (C.c_int, [c_f, I64x4, c_f, I64x4, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'sininn_lrelu_bwd': (C.c_int, [c_f, C.c_int, c_f, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p]),
     'sininn_irn_tail': (C.c_int, [c_f, C.c_int, c_f, c_f, C.c_int64, C.c_int, C.c_float, C.c_int, c_f, C.c_int, C.c_void_p]),
@@ -215,7 +242,7 @@ def lib():
             fn.restype, fn.argtypes = res, args
         if handle.sininn_version() != 4:
             raise ImportError('libsininn.so ABI version mismatch')
-        for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc)):
+        for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc, DenseBf16Args)):
             if handle.sininn_sizeof(which) != C.sizeof(mirror):
                 raise ImportError(f'{mirror.__name__}: the ctypes mirror has {C.sizeof(mirror)} bytes, libsininn.so was built '
                                   f'with {handle.sininn_sizeof(which)} (include/sininn.h changed without _lib.py)')

@@ -97,6 +97,11 @@ int frames_to_u8_launch(const float* in, const int64_t is[4], uint8_t* out, int 
 size_t dense_workspace_bytes(int B, int H, int W, int cin, int cout);
 int dense_forward(const sininn_dense_args* a, hipStream_t st);
 int dense_backward(const sininn_dense_args* a, hipStream_t st, hipStream_t wst);
+size_t dense_bf16_workspace_bytes(int B, int H, int W, int cin, int cout);
+int dense_forward_bf16(const sininn_dense_bf16_args* a, hipStream_t st);
+int dense_backward_bf16(const sininn_dense_bf16_args* a, hipStream_t st, hipStream_t wst);
+int pack_work_items_bf16(const sininn_pack_desc* d);
+int pack_batch_bf16_launch(const sininn_pack_desc* descs, int n, int total, hipStream_t st);
 void profile_classes_begin();
 int profile_classes_end(int n, double* ms, double* flops, int* launches);
 int profile_classes_bytes(int n, double* bytes);
@@ -222,6 +227,7 @@ size_t sininn_sizeof(int which) {
     case 3: return sizeof(sininn_glow_args);
     case 4: return sizeof(sininn_subnet);
     case 5: return sizeof(sininn_pack_desc);
+    case 6: return sizeof(sininn_dense_bf16_args);
     default: return 0;
   }
 }
@@ -280,6 +286,10 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
 int sininn_pack_work_items(const sininn_pack_desc* host_desc) { return host_desc ? pack_work_items(host_desc) : 0; }
 int sininn_pack_batch(const sininn_pack_desc* descs, int n, int total_work, void* stream) {
   return pack_batch_launch(descs, n, total_work, ST(stream));
+}
+int sininn_pack_work_items_bf16(const sininn_pack_desc* host_desc) { return pack_work_items_bf16(host_desc); }
+int sininn_pack_batch_bf16(const sininn_pack_desc* descs, int n, int total_work, void* stream) {
+  return pack_batch_bf16_launch(descs, n, total_work, ST(stream));
 }
 int sininn_pack_winograd(const float* w_oihw, int N, int Cin, const int* colmap, int Np, float* u_fwd, int Cdp,
                          float* u_dgrad, void* stream) {
@@ -487,6 +497,13 @@ size_t sininn_dense_workspace_bytes(int B, int H, int W, int cin, int cout) { re
 int sininn_dense_forward(const sininn_dense_args* args, void* stream) { return dense_forward(args, ST(stream)); }
 int sininn_dense_backward(const sininn_dense_args* args, void* stream, void* wgrad_stream) {
   return dense_backward(args, ST(stream), ST(wgrad_stream));
+}
+size_t sininn_dense_bf16_workspace_bytes(int B, int H, int W, int cin, int cout) {
+  return dense_bf16_workspace_bytes(B, H, W, cin, cout);
+}
+int sininn_dense_forward_bf16(const sininn_dense_bf16_args* args, void* stream) { return dense_forward_bf16(args, ST(stream)); }
+int sininn_dense_backward_bf16(const sininn_dense_bf16_args* args, void* stream, void* wgrad_stream) {
+  return dense_backward_bf16(args, ST(stream), ST(wgrad_stream));
 }
 
 int sininn_frames_to_u8(const float* in, const int64_t in_strides[4], uint8_t* out, int B, int C, int H, int W, int wrap,

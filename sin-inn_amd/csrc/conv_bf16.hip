@@ -70,6 +70,9 @@ __device__ __forceinline__ void epilogue_bf16(const ConvDevB& q, const float* T,
         if (p.mode == SININN_CONV_RELU) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) { a[j] = fmaxf(a[j], 0.f); c[j] = fmaxf(c[j], 0.f); }
+        } else if (p.mode == SININN_CONV_LRELU) {          // IRN DenseBlock conv1-4: the feature slot is stored as bf16
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { a[j] = a[j] > 0.f ? a[j] : a[j] * p.clamp; c[j] = c[j] > 0.f ? c[j] : c[j] * p.clamp; }
         }
       } else {                                             // gradient through the ReLU of h
 #pragma unroll
@@ -82,6 +85,53 @@ __device__ __forceinline__ void epilogue_bf16(const ConvDevB& q, const float* T,
 #pragma unroll
       for (int j = 0; j < 4; ++j) { o[j] = (__bf16)a[j]; o[4 + j] = (__bf16)c[j]; }
       *reinterpret_cast<bf16x8*>(q.out_b + pix * p.out_stride + col) = o;
+    }
+  }
+}
+
+// fp32-output epilogue of the IRN DenseBlock data gradients: out = T (+ bias) (+ addend), and on the columns >= Co (the feature
+// slot whose gradient is final) the LeakyReLU backward, its gate read from the STORED bf16 feature value (slope 1 where it is
+// > 0, clamp otherwise).  The shared fp32 epilogue reads an fp32 mask only.  4 columns (16 bytes out, 8 bytes of gate) per item.
+template <int BN, int NPIX>
+__device__ __forceinline__ void epilogue_f32_gate_bf16(const ConvDevB& q, const float* T, int b, int y0, int x0, int n0, int tid) {
+  const ConvDev& p = q.c;
+  constexpr int TS = BN + 4, Q = BN / 4;
+  static_assert(256 % Q == 0, "a thread keeps its column quad over the pixel loop");
+  constexpr int ITERS = (NPIX * Q + 255) / 256;
+  const int q4 = tid % Q;
+  const int col = n0 + q4 * 4;
+  if (col >= p.N) return;                                    // N % 4 == 0 is checked on the host
+  const bool add = p.mode == SININN_CONV_ADD, gated = col >= p.Co;
+  f32x4 bq = {0.f, 0.f, 0.f, 0.f};
+  if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + col);
+  // every side input of the thread (addend, gate) is requested before the first one is used: one global-load latency per block
+  f32x4 ad_all[ITERS];
+  bf16x4 g_all[ITERS];
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int pl = (tid + it * 256) / Q;
+    const int gy = y0 + (pl >> 4), gx = x0 + (pl & 15);
+    const bool in = pl < NPIX && gy < p.H && gx < p.W;
+    const size_t pix = (size_t)(b * p.H + gy) * p.W + gx;
+    ad_all[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    g_all[it] = (bf16x4){0, 0, 0, 0};
+    if (in && add) ad_all[it] = *reinterpret_cast<const f32x4*>(p.addend + pix * p.addend_stride + col);
+    if (in && gated) g_all[it] = *reinterpret_cast<const bf16x4*>(q.mask_b + pix * p.mask_stride + col);
+  }
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int pl = (tid + it * 256) / Q;
+    const int gy = y0 + (pl >> 4), gx = x0 + (pl & 15);
+    if (pl < NPIX && gy < p.H && gx < p.W) {
+      const size_t pix = (size_t)(b * p.H + gy) * p.W + gx;
+      f32x4 val = *reinterpret_cast<const f32x4*>(T + pl * TS + q4 * 4);
+      val += bq;
+      val += ad_all[it];
+      if (gated) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) val[j] = ((float)g_all[it][j] > 0.f) ? val[j] : val[j] * p.clamp;
+      }
+      *reinterpret_cast<f32x4*>(p.out + pix * p.out_stride + col) = val;
     }
   }
 }
@@ -293,6 +343,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(ConvDevB q) {
   __syncthreads();
   if (q.out_bf16) {
     epilogue_bf16<BN, TH * 16>(q, T, b, y0, x0, n0, tid);
+  } else if (!IN_BF16 && KS == 3 && q.gate_b) {
+    if constexpr (!IN_BF16 && KS == 3) epilogue_f32_gate_bf16<BN, TH * 16>(q, T, b, y0, x0, n0, tid);
   } else {
     __shared__ float red[4];
     conv_epilogue_tile<TH, BN, HT, 256>(p, T, b, y0, x0, n0, tid, red);
@@ -333,8 +385,10 @@ static int launch_ht(const ConvDevB& q, hipStream_t st) {
     if (q.in_bf16 && q.c.Np <= 32 && !ht16) return launch_one<KS, CK, 8, true, 32>(q, st);
   }
   if (q.in_bf16) return ht16 ? launch_one<KS, CK, 16, true>(q, st) : launch_one<KS, CK, 8, true>(q, st);
-  // fp32 inputs only feed the bf16-output convs of the path (cond -> h, dr -> dh): the coupling half-width is irrelevant
-  SININN_CHECK(q.out_bf16, "conv_bf16: an fp32-input conv must have a bf16 output");
+  // fp32 inputs feed the bf16-output convs of the SRF path (cond -> h, dr -> dh) and the fp32-output data gradients of the IRN
+  // DenseBlock (dD / a dF slot -> dF); none of them is a coupling conv, so the coupling half-width is irrelevant
+  SININN_CHECK(q.out_bf16 || !(q.c.mode == SININN_CONV_COUPLE_FWD || q.c.mode == SININN_CONV_COUPLE_INV),
+               "conv_bf16: an fp32-input conv cannot carry the coupling epilogue");
   return launch_one<KS, CK, 8, false>(q, st);
 }
 
@@ -365,14 +419,24 @@ int conv_bf16_prepare(const sininn_conv_args* a, ConvDevB& q) {
   const bool couple = a->mode == SININN_CONV_COUPLE_FWD || a->mode == SININN_CONV_COUPLE_INV;
   const bool cbwd = a->mode == SININN_CONV_ADD_CBWD_FWD || a->mode == SININN_CONV_ADD_CBWD_INV;
   if (a->out_bf16) {
-    SININN_CHECK(a->mode == SININN_CONV_RELU || a->mode == SININN_CONV_LINEAR || a->mode == SININN_CONV_MASK,
-                 "conv_bf16: bf16 output supports RELU / LINEAR / MASK only");
+    SININN_CHECK(a->mode == SININN_CONV_RELU || a->mode == SININN_CONV_LINEAR || a->mode == SININN_CONV_MASK ||
+                 a->mode == SININN_CONV_LRELU, "conv_bf16: bf16 output supports RELU / LRELU / LINEAR / MASK only");
     SININN_CHECK(a->N > 0 && a->N % 8 == 0 && a->N <= a->Np && a->out_stride >= a->N && a->out_stride % 8 == 0, "conv_bf16: bad N / out_stride");
     if (a->mode == SININN_CONV_MASK) SININN_CHECK(a->mask && a->mask_bf16 && a->mask_stride % 8 == 0 && aligned16(a->mask), "conv_bf16: MASK needs a bf16 mask");
     if (a->mode == SININN_CONV_RELU) SININN_CHECK(a->bias != nullptr, "conv_bf16: RELU mode needs bias");
+    if (a->mode == SININN_CONV_LRELU) SININN_CHECK(a->bias != nullptr && a->clamp > 0.f, "conv_bf16: LRELU mode needs bias and a slope");
   } else {
-    SININN_CHECK(couple || a->mode == SININN_CONV_ADD || cbwd || a->mode == SININN_CONV_LINEAR || a->mode == SININN_CONV_RELU,
-                 "conv_bf16: fp32 output supports COUPLE / ADD / ADD_CBWD / LINEAR / RELU");
+    const bool irn = a->mode == SININN_CONV_IRN_FWD || a->mode == SININN_CONV_IRN_INV;
+    SININN_CHECK(couple || a->mode == SININN_CONV_ADD || cbwd || a->mode == SININN_CONV_LINEAR || a->mode == SININN_CONV_RELU || irn,
+                 "conv_bf16: fp32 output supports COUPLE / ADD / ADD_CBWD / LINEAR / RELU / IRN_FWD / IRN_INV");
+    if (irn)
+      SININN_CHECK(a->v && a->mask && !a->mask_bf16 && a->clamp > 0.f && a->mask_stride >= a->N && a->v_stride >= a->N,
+                   "conv_bf16: IRN_FWD / IRN_INV need v, an fp32 mask (H's output) and clamp");
+    if ((a->mode == SININN_CONV_LINEAR || a->mode == SININN_CONV_ADD) && a->mask && a->mask_bf16) {
+      SININN_CHECK(a->ksize == 3 && !a->in_bf16 && !a->addend_map, "conv_bf16: the bf16-gated LeakyReLU tail needs an fp32-input 3x3 conv");
+      SININN_CHECK(a->Co >= 0 && a->Co % 4 == 0 && a->clamp > 0.f && a->mask_stride % 4 == 0 && a->mask_stride >= a->N &&
+                   (reinterpret_cast<uintptr_t>(a->mask) & 7u) == 0, "conv_bf16: bad bf16-gated LeakyReLU tail (Co, clamp, mask)");
+    }
     SININN_CHECK(a->out_stride % 4 == 0, "conv_bf16: out_stride %% 4");
     if (couple) {
       SININN_CHECK(a->Co > 0 && a->Co % 8 == 0 && a->Np == 2 * a->Co && a->v && a->v_stride >= a->Co && a->clamp > 0.f && a->out_stride >= a->Co,
@@ -396,7 +460,8 @@ int conv_bf16_prepare(const sininn_conv_args* a, ConvDevB& q) {
   d.out = a->out_bf16 ? nullptr : a->out; d.out_stride = a->out_stride; d.N = a->N; d.out_map = a->out_map;
   d.v = a->v; d.v_stride = a->v_stride; d.out2 = a->out2; d.out2_stride = a->out2_stride;
   d.sbuf = a->sbuf; d.logdet = a->logdet; d.Co = a->Co; d.clamp = a->clamp;
-  d.mask = nullptr; d.mask_stride = a->mask_stride;
+  const bool irn_tail = !a->out_bf16 && (a->mode == SININN_CONV_IRN_FWD || a->mode == SININN_CONV_IRN_INV);
+  d.mask = irn_tail ? a->mask : nullptr; d.mask_stride = a->mask_stride;       // IRN tails: H's output (fp32)
   d.addend = a->addend; d.addend_stride = a->addend_stride; d.addend_map = a->addend_map;
   d.mode = a->mode; d.col_tile = couple ? a->col_tile : 16; d.stamp = a->stamp; d.ablate = 0; d.CK = 0; d.in_chunk = 8; d.out_gs = 0; d.mask_gs = 0;
   const int th = a->ksize == 3 ? 16 : 8;
@@ -406,6 +471,7 @@ int conv_bf16_prepare(const sininn_conv_args* a, ConvDevB& q) {
   q.mask_b = reinterpret_cast<const __bf16*>(a->mask);
   q.Kp = (a->Cin + 15) / 16 * 16;
   q.in_bf16 = a->in_bf16; q.out_bf16 = a->out_bf16;
+  q.gate_b = (!a->out_bf16 && (a->mode == SININN_CONV_LINEAR || a->mode == SININN_CONV_ADD) && a->mask && a->mask_bf16) ? 1 : 0;
   return 0;
 }
 

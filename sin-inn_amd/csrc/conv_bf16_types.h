@@ -16,6 +16,8 @@ struct ConvDevB {
   const __bf16* mask_b;      // bf16 ReLU mask source (MASK mode with out_bf16)
   int Kp;                    // channels of the weight pack (Cin rounded up to a multiple of 16)
   int in_bf16, out_bf16;
+  int gate_b;                // fp32-output LINEAR / ADD whose columns >= c.Co carry the LeakyReLU backward gated by the bf16
+                             // tensor mask_b (IRN DenseBlock data gradients; fp32-input 3x3 convs only)
 };
 
 

@@ -1205,7 +1205,10 @@ static bool g_wgrad_bf16_mfma = true;   // test hook bit 6 clears: bf16-operand 
 void wgrad_set_bf16_mfma(int on) { g_wgrad_bf16_mfma = on != 0; }
 void wgrad_set_wide_c(int on) { g_wgrad_wide_c = on != 0; }
 
-static int plan_group(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, float* ws, WgradGroupPlan& pl) {
+// f32_quads (the IRN bf16 DenseBlock executor only): an fp32 operand needs a channel count % 4, not % 8, on the bf16 matrix pipe --
+// its staging loads 4-channel quads (WgStage / load_d); the bf16 operand keeps % 8.  conv5's N = 84 / 108 / 12 / 180 are such.
+static int plan_group(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, float* ws, WgradGroupPlan& pl,
+                      bool f32_quads = false) {
   SININN_CHECK(items && n >= 1 && n <= WG_MAXP, "wgrad_group: 1..%d problems per group", WG_MAXP);
   SININN_CHECK(ksize == 1 || ksize == 3, "wgrad_group: ksize %d not in {1,3}", ksize);
   SININN_CHECK(B > 0 && H > 0 && W > 0, "wgrad_group: bad shape");
@@ -1223,8 +1226,12 @@ static int plan_group(const sininn_wgrad_item* items, int n, int B, int H, int W
   // a group whose every problem has a bf16 operand runs on the bf16 matrix pipe (one operand is stored as bf16 already,
   // the other is rounded while it is staged); anything else accumulates exact fp32 products on the f32 pipe
   bool all_mixed = g_wgrad_bf16_mfma;
-  for (int i = 0; i < n; ++i)
-    all_mixed = all_mixed && (items[i].in_bf16 || items[i].dout_bf16) && items[i].Cin % 8 == 0 && items[i].N % 8 == 0;
+  for (int i = 0; i < n; ++i) {
+    const sininn_wgrad_item& it = items[i];
+    const bool dims = f32_quads ? (it.Cin % (it.in_bf16 ? 8 : 4) == 0 && it.N % (it.dout_bf16 ? 8 : 4) == 0)
+                                : (it.Cin % 8 == 0 && it.N % 8 == 0);
+    all_mixed = all_mixed && (it.in_bf16 || it.dout_bf16) && dims;
+  }
   pl.mfma_bf16 = all_mixed;
   pl.wino = (ksize == 3) && !pl.mfma_bf16;
   pl.th = pl.mfma_bf16 ? 8 : (pl.wino ? 4 : WG_TH);
@@ -1292,11 +1299,33 @@ size_t wgrad_group_workspace_bytes(const sininn_wgrad_item* items, int n, int B,
   return pl.bytes;
 }
 
+// IRN bf16 DenseBlock: every problem has the bf16 feature buffer as `in` and an fp32 gradient as `dout`
+size_t wgrad_group_mixed_workspace_bytes(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize) {
+  WgradGroupPlan pl;
+  if (plan_group(items, n, B, H, W, ksize, nullptr, pl, true)) return 0;
+  return pl.bytes;
+}
+
+static int wgrad_group_run(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
+                           hipStream_t st, bool f32_quads);
+
 int wgrad_group_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
                        hipStream_t st) {
+  return wgrad_group_run(items, n, B, H, W, ksize, ws, ws_bytes, st, false);
+}
+
+int wgrad_group_mixed_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
+                             hipStream_t st) {
+  return wgrad_group_run(items, n, B, H, W, ksize, ws, ws_bytes, st, true);
+}
+
+static int wgrad_group_run(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
+                           hipStream_t st, bool f32_quads) {
   SININN_CHECK(ws != nullptr && aligned16(ws), "wgrad_group: workspace must be 16-byte aligned");
   WgradGroupPlan pl;
-  if (int rc = plan_group(items, n, B, H, W, ksize, static_cast<float*>(ws), pl)) return rc;
+  if (int rc = plan_group(items, n, B, H, W, ksize, static_cast<float*>(ws), pl, f32_quads)) return rc;
+  SININN_CHECK(!f32_quads || pl.mfma_bf16 || !g_wgrad_bf16_mfma,
+               "wgrad_group: a mixed-precision group must run on the bf16 matrix pipe (bf16 operand with Cin %% 8, fp32 one with %% 4)");
   SININN_CHECK(ws_bytes >= pl.bytes, "wgrad_group: workspace too small (%zu < %zu)", ws_bytes, pl.bytes);
   for (int i = 0; i < n; ++i) {
     const sininn_wgrad_item& it = items[i];

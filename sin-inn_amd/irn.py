@@ -9,6 +9,9 @@ Execution is pixel-major (NHWC) like the SRF path and re-uses the same conv / wg
     IRN_FWD / IRN_INV: y2 = x2*exp(s) + G(y1) and its inverse, s = clamp*(2*sigmoid(H(y1)) - 1)).
   * backward: hand-written chain (irn_coupling_bwd -> wgrad/dgrad of conv5 -> [lrelu_bwd, wgrad, dgrad-accumulate]
     for conv4..conv1) on the same kernels.
+  * precision: 'fp32' (the reference's arithmetic) or 'bf16' (InvRescaleNet.set_precision: the conv subnets compute in bf16
+    with fp32 accumulation, the invertible flow stays fp32 -- the full contract is in set_precision's docstring; executor
+    sininn_dense_forward_bf16 / sininn_dense_backward_bf16, bf16 feature buffer, bf16 weight packs).
 """
 import ctypes
 
@@ -140,7 +143,60 @@ class _DensePacks:
         return self.packs
 
 
+class _DensePacksBf16:
+    """bf16 packs of the five convs (mixed-precision path), same padded channel order and the same keying as _DensePacks
+    (optimiser epoch, parameter versions / storage).  Registered with the model-wide pack registry: the optimiser step
+    refreshes every bf16 DenseBlock pack of the model in ONE batched launch (sininn_pack_batch_bf16)."""
+
+    def __init__(self):
+        self.entries, self.packs, self.sig = None, None, None
+
+    def get(self, block):
+        from .modules import _PACK_REGISTRY, _PackCache, _PackEntry
+        convs = block.convs()
+        sig = (WEIGHTS_EPOCH[0],) + tuple(v for cv in convs for q in (cv._parameters,)
+                                          for v in (q['weight']._version, q['bias']._version, q['weight'].data_ptr()))
+        if sig == self.sig:
+            return self.packs
+        keys = [_PackCache._key(cv, True, False, False, True) for cv in convs]
+        if self.entries is None or any(e.key[0] != k[0] or e.key[4:] != k[4:] for e, k in zip(self.entries, keys)):
+            for e in self.entries or ():
+                _PACK_REGISTRY.discard(e)
+            cin, cinp = block.channel_in, block.cinp
+            self.entries = []
+            for i, cv in enumerate(convs):
+                n = cv.weight.shape[0]
+                pad = (_pad8(n), cinp + GC * i, cin, cinp - cin)
+                e = _PackEntry(cv, None, None, ops.alloc_packs_bf16(pad[0], pad[1], 3, cv.weight.device))
+                e.pad = pad
+                self.entries.append(e)
+                _PACK_REGISTRY.add(e)
+            self.packs = [e.packs for e in self.entries]
+        if any(e.key != k for e, k in zip(self.entries, keys)):
+            descs = [ops.pack_desc_bf16(cv.weight.detach(), cv.bias.detach(), e.packs, e.pad) for e, cv in zip(self.entries, convs)]
+            ops.pack_batch_bf16_run(ops.pack_batch_bf16(descs, convs[0].weight.device))
+            for e, k in zip(self.entries, keys):
+                e.key = k
+        self.sig = sig
+        return self.packs
+
+
 _MODES = {'linear': 0, 'add': 1, 'irn_fwd': 2, 'irn_inv': 3}
+
+
+def _dense_args_bf16(block, packs, b, h, w, mode, clamp):
+    """sininn_dense_bf16_args with the per-block constants filled in (cached like _dense_args)."""
+    key = (b, h, w, mode, float(clamp), 'bf16')
+    cache = block.__dict__.setdefault('_args_tpl', {})
+    hit = cache.get(key)
+    if hit is None or hit[0] is not packs:
+        a = _lib.DenseBf16Args(B=b, H=h, W=w, cin=block.channel_in, cout=block.channel_out, mode=_MODES[mode], clamp=float(clamp))
+        for i, (wf, bf, wd) in enumerate(packs):
+            a.w_fwd[i], a.b_fwd[i], a.w_dgrad[i] = wf.data_ptr(), bf.data_ptr(), wd.data_ptr()
+            a.w_fwd_elems[i], a.b_fwd_floats[i], a.w_dgrad_elems[i] = wf.numel(), bf.numel(), wd.numel()
+        hit = (packs, bytes(a))
+        cache[key] = hit
+    return _lib.DenseBf16Args.from_buffer_copy(hit[1])
 
 
 def _dense_args(block, packs, b, h, w, mode, clamp):
@@ -174,12 +230,18 @@ class _DenseFn(torch.autograd.Function):
         m = b * h * w
         cinp, cout = block.cinp, block.channel_out
         bw = cinp + 4 * GC
-        packs = block._packs.get(block)
-        buf = torch.empty((m, bw), device=dev, dtype=torch.float32)
+        bf16 = block.precision == 'bf16'
+        packs = block._packs_bf16.get(block) if bf16 else block._packs.get(block)
+        buf = torch.empty((m, bw), device=dev, dtype=torch.bfloat16 if bf16 else torch.float32)
         out = torch.empty((b, h, w, cout), device=dev, dtype=torch.float32)
-        a = _dense_args(block, packs, b, h, w, mode, clamp)
+        if bf16:
+            a = _dense_args_bf16(block, packs, b, h, w, mode, clamp)
+            a.buf_elems = buf.numel()
+        else:
+            a = _dense_args(block, packs, b, h, w, mode, clamp)
+            a.buf_floats = buf.numel()
         a.x, a.x_stride, a.buf, a.out = xd.data_ptr(), xs, buf.data_ptr(), out.data_ptr()
-        a.buf_floats, a.out_floats = buf.numel(), out.numel()
+        a.out_floats = out.numel()
         a1 = a2 = None
         if mode != 'linear':
             a1, s1 = _pixel_view(aux1.detach())
@@ -187,9 +249,9 @@ class _DenseFn(torch.autograd.Function):
         if mode in ('irn_fwd', 'irn_inv'):
             a2 = aux2.detach().contiguous()
             a.aux2, a.aux2_floats = a2.data_ptr(), a2.numel()
-        check(_lib.lib().sininn_dense_forward(a, ops._stream()))
+        check((_lib.lib().sininn_dense_forward_bf16 if bf16 else _lib.lib().sininn_dense_forward)(a, ops._stream()))
         if block.__dict__.get('_grad_mode', True) and any(ctx.needs_input_grad):      # the caller's grad mode (autograd is off inside forward)
-            ctx.block, ctx.mode, ctx.clamp, ctx.shape = block, mode, clamp, (b, h, w, cin)
+            ctx.block, ctx.mode, ctx.clamp, ctx.shape, ctx.bf16 = block, mode, clamp, (b, h, w, cin), bf16
             ctx.save_for_backward(buf, out, a1 if a1 is not None else buf, a2 if a2 is not None else buf, xd)
             if GATE_TAP[0] is not None:          # parity tooling: the LeakyReLU gates of conv1-4 (feature slots of buf are > 0)
                 feats = buf.view(b, h, w, bw)[..., cinp:]
@@ -206,16 +268,22 @@ class _DenseFn(torch.autograd.Function):
         dev = buf.device
         cinp, cout = block.cinp, block.channel_out
         bw, coutp = cinp + 4 * GC, _pad8(cout)
-        packs = block._packs.get(block)
+        bf16 = ctx.bf16
+        packs = block._packs_bf16.get(block) if bf16 else block._packs.get(block)
         convs = block.convs()
         dout = dout.contiguous()
         dout.record_stream(torch.cuda.current_stream())     # may have been produced on another chain / helper stream
         lib = _lib.lib()
         irn = mode in ('irn_fwd', 'irn_inv')
-        a = _dense_args(block, packs, b, h, w, mode, clamp)
+        if bf16:
+            a = _dense_args_bf16(block, packs, b, h, w, mode, clamp)
+            a.buf_elems = buf.numel()
+        else:
+            a = _dense_args(block, packs, b, h, w, mode, clamp)
+            a.buf_floats = buf.numel()
         a.x, a.x_stride = xd.data_ptr(), xd.stride(2)
         a.buf, a.out, a.dout = buf.data_ptr(), out.data_ptr(), dout.data_ptr()
-        a.buf_floats, a.out_floats, a.dout_floats = buf.numel(), out.numel(), dout.numel()
+        a.out_floats, a.dout_floats = out.numel(), dout.numel()
         dF = torch.empty((m, bw), device=dev, dtype=torch.float32)        # fully written by conv5's data gradient
         a.dF, a.dF_floats = dF.data_ptr(), dF.numel()
         dD = dh = dv = None
@@ -232,7 +300,7 @@ class _DenseFn(torch.autograd.Function):
         for i, cv in enumerate(convs):
             if cv.weight.requires_grad:
                 a.gw[i], a.gb[i] = _grad_buf(cv.weight).data_ptr(), _grad_buf(cv.bias).data_ptr()
-        nbytes = lib.sininn_dense_workspace_bytes(b, h, w, block.channel_in, cout)
+        nbytes = (lib.sininn_dense_bf16_workspace_bytes if bf16 else lib.sininn_dense_workspace_bytes)(b, h, w, block.channel_in, cout)
         ws = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
         # weight gradients go to the dedicated side stream (like the GLOW executor's): every `+=` into a parameter gradient
@@ -240,7 +308,7 @@ class _DenseFn(torch.autograd.Function):
         main_h = ops._stream_handle()
         side = _side_stream(dev) if USE_SIDE_STREAM[0] else None
         side_h = side.cuda_stream if side is not None else main_h
-        check(lib.sininn_dense_backward(a, ctypes.c_void_p(main_h), ctypes.c_void_p(side_h)))
+        check((lib.sininn_dense_backward_bf16 if bf16 else lib.sininn_dense_backward)(a, ctypes.c_void_p(main_h), ctypes.c_void_p(side_h)))
         if DEBUG_SYNC[0]:
             torch.cuda.synchronize()
         if side is not None and side_h != main_h:
@@ -288,6 +356,8 @@ class DenseBlock(nn.Module):
         self.conv5.weight.data *= 0
         self.conv5.bias.data.zero_()
         self._packs = _DensePacks()
+        self._packs_bf16 = _DensePacksBf16()
+        self.precision = 'fp32'          # InvRescaleNet.set_precision
         self._ar = {}
 
     def convs(self):
@@ -437,15 +507,34 @@ class InvRescaleNet(nn.Module):
             for _ in range(opt.num_coupling):
                 operations.append(InvBlockExp(current, min(channel_out, current // 2)))
         self.operations = nn.ModuleList(operations)
+        self.precision = 'fp32'
+
+    def dense_blocks(self):
+        return [blk for op in self.operations if isinstance(op, InvBlockExp) for blk in (op.F, op.G, op.H)]
+
+    def set_precision(self, precision):
+        """'fp32' (default, the reference's arithmetic) or 'bf16' (mixed precision).  bf16 contract: the conv subnets compute in
+        bf16 with fp32 accumulation, the invertible flow stays fp32.  Per DenseBlock:
+          * stored as bf16 (round to nearest even, once): the block input as copied into the feature buffer (pad channels
+            zero), conv1-4's 32-channel outputs (bias + LeakyReLU(0.2) computed in fp32), the five weight packs -- the feature
+            buffer is bf16 in HBM and is what the backward pass saves;
+          * fp32: biases, accumulators and every epilogue, conv5's output and the InvBlockExp tails fused into it (ADD, IRN_FWD /
+            IRN_INV with s = clamp * (2 sigmoid(H) - 1)), Haar, split / concatenation, the losses, parameters, gradients, Adam;
+          * backward: dD (conv5's output gradient) and each finished 32-channel slot of dF are rounded to bf16 while staged for
+            the data-gradient convs; dF accumulates in fp32; the LeakyReLU-backward gate is the stored bf16 feature (slope 1
+            where > 0, else 0.2); the weight gradients run on bf16 MFMA (fp32 accumulation) from the stored feature buffer and
+            dF / dD rounded while staged, and are added in fp32 to the OIHW gradients."""
+        assert precision in ('fp32', 'bf16')
+        for blk in self.dense_blocks():
+            blk.precision = precision
+        self.precision = precision
 
     def prepare_packs(self):
         """Build every DenseBlock's packed weights on the CURRENT stream (they are keyed on the optimiser epoch, i.e.
         rebuilt once per step): called on the main stream before the two pass chains fork, see
         ReversibleGraphNet.prepare_packs."""
-        for op in self.operations:
-            if isinstance(op, InvBlockExp):
-                for blk in (op.F, op.G, op.H):
-                    blk._packs.get(blk)
+        for blk in self.dense_blocks():
+            (blk._packs_bf16 if blk.precision == 'bf16' else blk._packs).get(blk)
 
     @property
     def concurrent_passes_safe(self):

@@ -140,6 +140,7 @@ class _PackRegistry:
     def __init__(self):
         self.entries = []
         self.table = None
+        self.table_bf16 = None       # (weight + pack addresses, batched bf16 pack table) of the IRN DenseBlock bf16 packs
         self.generation = 0          # bumped whenever a pack buffer is allocated or dropped: whatever baked pack ADDRESSES into
                                      # something replayable (lit_wrapper's hipGraph cache) keys on it
 
@@ -160,6 +161,17 @@ class _PackRegistry:
         live = [(e, c) for e, c in pairs if c is not None and c.weight.is_cuda]
         if len(live) != len(self.entries):
             self.entries, self.table = [e for e, _ in live], None
+        # IRN DenseBlock bf16 packs (padded channel order, `pad` set): every one of them in one batched launch
+        gapped = [(e, c) for e, c in live if e.key[7] and getattr(e, 'pad', None) is not None]
+        if gapped:
+            ptrs = tuple(c.weight.data_ptr() for _, c in gapped) + tuple(e.packs[0].data_ptr() for e, _ in gapped)
+            if self.table_bf16 is None or self.table_bf16[0] != ptrs:
+                descs = [ops.pack_desc_bf16(c.weight.detach(), c.bias.detach(), e.packs, e.pad) for e, c in gapped]
+                self.table_bf16 = (ptrs, ops.pack_batch_bf16(descs, gapped[0][1].weight.device))
+            ops.pack_batch_bf16_run(self.table_bf16[1])
+            for e, c in gapped:
+                e.key = _PackCache._key(c, *e.key[4:])
+            live = [(e, c) for e, c in live if not (e.key[7] and getattr(e, 'pad', None) is not None)]
         # mixed-precision packs: repacked in place, one (tiny) launch pair per conv -- the launches the next pass's cache
         # miss would have issued, moved onto the optimiser's stream
         for e, c in live:

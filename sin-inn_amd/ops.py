@@ -176,6 +176,50 @@ def pack_batch_run(table):
     check(_lib.lib().sininn_pack_batch(C.c_void_p(raw.data_ptr()), n, total, _stream()))
 
 
+def alloc_packs_bf16(n, cin, k, device):
+    """Empty bf16 (w_fwd [taps][pad16(n)][pad16(cin)], b_fwd [pad16(n)] fp32, w_dgrad [taps][pad16(cin)][pad16(n)]) buffers of a
+    conv with n (packed) outputs / cin (packed) inputs: the layouts of pack_conv_bf16."""
+    taps, npk, kp = k * k, pad16(n), pad16(cin)
+    return (torch.empty(taps * npk * kp, device=device, dtype=torch.bfloat16),
+            torch.empty(npk, device=device, dtype=torch.float32),
+            torch.empty(taps * kp * npk, device=device, dtype=torch.bfloat16))
+
+
+def pack_desc_bf16(weight, bias, packs, pad):
+    """sininn_pack_desc refreshing bf16 `packs` (alloc_packs_bf16) from (weight, bias); pad as in pack_desc."""
+    n, cin, k, _ = weight.shape
+    w_fwd, b_fwd, w_dg = packs
+    n_packed, cin_packed, gap_begin, gap_len = pad
+    assert cin_packed - gap_len == cin and n_packed >= n
+    assert w_fwd.dtype == torch.bfloat16 and w_dg.dtype == torch.bfloat16
+    d = _lib.PackDesc()
+    d.src_n, d.gap_begin, d.gap_len = n, gap_begin, gap_len
+    d.w, d.bias, d.N, d.Cin, d.ksize = ptr(weight), ptr(bias), n_packed, cin_packed, k
+    d.colmap, d.Np, d.Cdp = None, pad16(n_packed), pad16(cin_packed)
+    d.w_fwd, d.b_fwd = C.c_void_p(w_fwd.data_ptr()), ptr(b_fwd)
+    d.w_dgrad = C.c_void_p(w_dg.data_ptr())
+    return d
+
+
+def pack_batch_bf16(descs, device):
+    """pack_batch for bf16 descriptors (pack_desc_bf16): (device table, n, total_work) for pack_batch_bf16_run."""
+    lib = _lib.lib()
+    arr = (_lib.PackDesc * len(descs))(*descs)
+    total = 0
+    for d in arr:
+        d.work_begin = total
+        items = lib.sininn_pack_work_items_bf16(C.byref(d))
+        assert items > 0, 'pack_batch_bf16: descriptor the bf16 layout cannot serve'
+        total += items
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return raw, len(descs), total
+
+
+def pack_batch_bf16_run(table):
+    raw, n, total = table
+    check(_lib.lib().sininn_pack_batch_bf16(C.c_void_p(raw.data_ptr()), n, total, _stream()))
+
+
 # ---- conv engine ---------------------------------------------------------------------------------
 def conv(**kw):
     """Launch sininn_conv; keyword names follow sininn_conv_args (tensors given as (tensor, offset) or c_void_p)."""

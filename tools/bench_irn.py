@@ -1,5 +1,6 @@
 """Throughput of the IRN architecture (`-a IRN`) on the same workload as bench.py (256x256x3, batch 16,
-lr_window 10, -c 4): full training step, fp32.  `python tools/bench_irn.py [--steps 10]` on the GPU box."""
+lr_window 10, -c 4): full training step.  `python tools/bench_irn.py [--steps 10] [--precision fp32|bf16] [--height 256 --width 256]
+[--batch 16]` on the GPU box."""
 import argparse
 import os
 import sys
@@ -19,14 +20,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--precision', choices=['fp32', 'bf16'], default='fp32')
+    ap.add_argument('--height', type=int, default=256)
+    ap.add_argument('--width', type=int, default=256)
     a = ap.parse_args()
     dev = torch.device('cuda', 0)
     opt = make_opt(4, 10)
     opt.architecture = 'IRN'
+    opt.precision = a.precision
     torch.manual_seed(0)
-    model = lit_wrapper.SingleVideoINN(3, 256, 256, opt).to(dev)
+    model = lit_wrapper.SingleVideoINN(3, a.height, a.width, opt).to(dev)
     model.attach_optimizer()
-    store = FrameStore.synthetic(64, 256, 256).to(dev)
+    store = FrameStore.synthetic(64, a.height, a.width).to(dev)
     g = torch.Generator().manual_seed(1)
 
     def step():
@@ -43,7 +48,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     n = sum(p.numel() for p in model.parameters())
-    print(f'IRN -c 4 ({n / 1e6:.2f} M parameters): {dt * 1e3:.1f} ms / step = {a.batch / dt:.0f} training frames/s (fp32, batch {a.batch}, 256x256)')
+    print(f'IRN -c 4 ({n / 1e6:.2f} M parameters): {dt * 1e3:.1f} ms / step = {a.batch / dt:.0f} training frames/s ({a.precision}, batch {a.batch}, {a.height}x{a.width})')
 
 
 if __name__ == '__main__':
