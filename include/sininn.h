@@ -215,6 +215,37 @@ size_t sininn_conv_sub1_bwd_workspace_bytes(int cin, int co);
 int sininn_conv_sub1_bwd(const sininn_conv_args* recompute, const sininn_conv_args* d2, const sininn_conv_args* d1, int no_dx,
                          float* gw2, float* gb2, float* gw1, float* gb1, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The mixed-precision backward of the WIDE (level-1) 1x1 subnet, as the block executor runs it: one persistent launch for both data
+ * gradients with the weight gradient of conv1 riding along, then one slab reduce (the same kernels sininn_glow_backward uses; ABI v4):
+ *   dh = (dr W2) . [h > 0] (bf16, stored to d2->out unless it is NULL), dx = dh W1 through d1's epilogue (ADD / ADD_CBWD_*),
+ *   gw1 [256][96] += dh^T x, gb1 [256] += sum dh (OIHW, fp32; x fp32 [pixel][x_stride], dh summed as the bf16 values above).
+ * d2: in = dr fp32 [.. 192], w = bf16 data-gradient pack of conv2, Np = N = 256, mode MASK, mask = h (bf16, the forward's hidden
+ * tensor), mask_bf16 = out_bf16 = 1; d1: in_bf16 = 1, Cin = 256, w = bf16 data-gradient pack of conv1, Np = N = 96, mode ADD or
+ * ADD_CBWD_FWD / _INV with the epilogue fields of sininn_conv_pair_k1 (d1->in is ignored: dh stays on chip).  Shape served:
+ * (Cin of conv1, 2 Co) = (96, 192); an unsupported descriptor pair is refused with an error.  x == NULL: no rider (gw1 / gb1
+ * must then be NULL, the workspace is not used).  sininn_conv_sub1_wide_bwd_workspace_bytes returns 0 for any other shape. */
+size_t sininn_conv_sub1_wide_bwd_workspace_bytes(int cin, int co);
+int sininn_conv_sub1_wide_bwd(const sininn_conv_args* d2, const sininn_conv_args* d1, const float* x, int x_stride, float* gw1, float* gb1,
+                              void* workspace, size_t workspace_bytes, void* stream);
+/* ... and the weight gradient of its conv2, the executor's other rider (a persistent kernel + slab reduce on the weight-gradient
+ * stream): gw2 [192][256] += dr^T h, gb2 [192] += sum dr (OIHW, fp32), dr fp32 [pixel][dr_stride] in conv2's OIHW channel order
+ * (ds | dt), h bf16 [pixel][h_stride].  (cin, co) = (96, 96) only; the workspace size is 0 for any other shape. */
+size_t sininn_conv_sub1_wide_wg2_workspace_bytes(int cin, int co);
+int sininn_conv_sub1_wide_wg2(const float* dr, int dr_stride, const void* h, int h_stride, int B, int H, int W, float* gw2, float* gb2,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* The small-K 3x3 kernel of a level-0 subnet on the mixed-precision path WITH the ReLU-gate bit mask, as the block executor runs it
+ * in training passes (ABI v4).  args: either conv1 (ksize 3, w_bf16, fp32 input with Cin in {8, 16, 24, 32}, bias, mode RELU, Np = N
+ * = 256, out_bf16: h = relu(conv + bias) as bf16) -- it WRITES `bits`; or the masked data gradient of conv2 (fp32 dr with Cin in
+ * {16, 32, 48}, mode MASK, Np = N = 256, out_bf16, mask_bf16 with a valid mask descriptor) -- it READS the gates from `bits`
+ * instead of `mask`.  sininn_conv3_smallk_bits_supported returns 1 when the descriptor qualifies.
+ * Bit layout: [pixel][8] 32-bit words over the image padded to 16 x 16 tiles, B * pad16(H) * pad16(W) * 8 words in all: the
+ * tile (b, ty, tx) (tile = (b * ceil(H/16) + ty) * ceil(W/16) + tx) owns words [tile * 2048, tile * 2048 + 2048); word
+ * (tile * 8 + m) * 256 + c holds, in bit p, the gate [h > 0] of hidden column c at pixel (16 ty + 2 m + p / 16, 16 tx + p % 16).
+ * Bits of pixels outside the image (the padding of the last tile row / column) are unspecified and never read. */
+int sininn_conv3_smallk_bits_supported(const sininn_conv_args* args);
+int sininn_conv3_smallk_bits(const sininn_conv_args* args, unsigned* bits, void* stream);
+
 /* The 3x3 twin for passes that keep nothing for a backward (ABI v4): the WHOLE 3x3 conv subnet (subnet_conv, archs.py:11-13) +
  * affine coupling + log-det of a GLOW half-coupling (archs.py:56-64) in one launch on the mixed-precision path.  `first`:
  * ksize 3, bf16 weights, fp32 input, mode RELU, 256 output channels, out == NULL (the hidden tile lives in LDS only);

@@ -180,6 +180,14 @@ _SIGS = {
     'sininn_conv_sub1_bwd_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'sininn_conv_sub1_bwd': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.POINTER(ConvArgs), C.c_int, c_f, c_f, c_f, c_f,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_conv_sub1_wide_bwd_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'sininn_conv_sub1_wide_bwd': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvArgs), c_f, C.c_int, c_f, c_f, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
+    'sininn_conv_sub1_wide_wg2_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'sininn_conv_sub1_wide_wg2': (C.c_int, [c_f, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_f, c_f, C.c_void_p,
+                                            C.c_size_t, C.c_void_p]),
+    'sininn_conv3_smallk_bits_supported': (C.c_int, [C.POINTER(ConvArgs)]),
+    'sininn_conv3_smallk_bits': (C.c_int, [C.POINTER(ConvArgs), C.c_void_p, C.c_void_p]),
     'sininn_dense_workspace_bytes': (C.c_size_t, [C.c_int] * 5),
     'sininn_dense_forward': (C.c_int, [C.POINTER(DenseArgs), C.c_void_p]),
     'sininn_dense_backward': (C.c_int, [C.POINTER(DenseArgs), C.c_void_p, C.c_void_p]),

@@ -26,6 +26,17 @@ int conv_sub1_bwd_launch(const sininn_conv_args* rc, const sininn_conv_args* d2,
 int conv_sub1_bwd_reduce(int cond_cin, int co, const void* ws, int slabs, float* gw2, float* gb2, float* gw1, float* gb1, hipStream_t st);
 void conv_sub1_bwd_enable(int on);
 void conv3_smallk_enable(int on);
+size_t conv_sub1_bf16_wide_ws_bytes(int ksize, int dtype, int cond_cin, int co);
+int conv_sub1_bf16_wide_bwd_supported(const sininn_conv_args* d2, const sininn_conv_args* d1);
+int conv_sub1_bf16_wide_bwd_launch(const sininn_conv_args* d2, const sininn_conv_args* d1, hipStream_t st);
+int conv_sub1_bf16_wide_bwd_wg1_launch(const sininn_conv_args* d2, const sininn_conv_args* d1, const float* x, int x_stride, void* ws, size_t ws_bytes,
+                                       int* slabs_out, hipStream_t st);
+int conv_sub1_bf16_wide_reduce(const void* ws, int slabs, float* gw1, float* gb1, hipStream_t st);
+size_t conv_sub1_bf16_wide_wg2_ws_bytes(int ksize, int dtype, int cond_cin, int co);
+int conv_sub1_bf16_wide_wg2_launch(const float* dr, int dr_stride, const void* h, int h_stride, int B, int H, int W, void* ws, size_t ws_bytes,
+                                   float* gw2, float* gb2, hipStream_t st);
+int conv3_smallk_bf16_supported(const sininn_conv_args* a);
+int conv3_smallk_bf16_launch_bits(const sininn_conv_args* a, unsigned* bits, hipStream_t st);
 int conv_sub1_fwd_supported(const sininn_conv_args* f, const sininn_conv_args* s);
 int conv_sub1_fwd_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
 int conv_pair_k1_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
@@ -321,6 +332,31 @@ int sininn_conv_sub1_bwd(const sininn_conv_args* recompute, const sininn_conv_ar
   if (int rc = conv_sub1_bwd_launch(recompute, d2, d1, no_dx, workspace, workspace_bytes, &slabs, ST(stream))) return rc;
   if (!gw2 && !gb2 && !gw1 && !gb1) return 0;
   return conv_sub1_bwd_reduce(recompute->Cin, d2->Cin / 2, workspace, slabs, gw2, gb2, gw1, gb1, ST(stream));
+}
+// the block executor's level-1 riders and gate-bit kernels, callable on their own (same internal functions, no other behaviour)
+size_t sininn_conv_sub1_wide_bwd_workspace_bytes(int cin, int co) { return conv_sub1_bf16_wide_ws_bytes(1, 1, cin, co); }
+int sininn_conv_sub1_wide_bwd(const sininn_conv_args* d2, const sininn_conv_args* d1, const float* x, int x_stride, float* gw1, float* gb1,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  SININN_CHECK(conv_sub1_bf16_wide_bwd_supported(d2, d1), "sininn_conv_sub1_wide_bwd: unsupported descriptor pair");
+  if (!x) {
+    SININN_CHECK(!gw1 && !gb1, "sininn_conv_sub1_wide_bwd: gw1 / gb1 need x");
+    return conv_sub1_bf16_wide_bwd_launch(d2, d1, ST(stream));
+  }
+  int slabs = 0;
+  if (int rc = conv_sub1_bf16_wide_bwd_wg1_launch(d2, d1, x, x_stride, workspace, workspace_bytes, &slabs, ST(stream))) return rc;
+  if (!gw1 && !gb1) return 0;
+  return conv_sub1_bf16_wide_reduce(workspace, slabs, gw1, gb1, ST(stream));
+}
+size_t sininn_conv_sub1_wide_wg2_workspace_bytes(int cin, int co) { return conv_sub1_bf16_wide_wg2_ws_bytes(1, 1, cin, co); }
+int sininn_conv_sub1_wide_wg2(const float* dr, int dr_stride, const void* h, int h_stride, int B, int H, int W, float* gw2, float* gb2,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  SININN_CHECK(sininn_conv_sub1_wide_wg2_workspace_bytes(96, 96) > 0, "sininn_conv_sub1_wide_wg2: the wide kernels are switched off");
+  return conv_sub1_bf16_wide_wg2_launch(dr, dr_stride, h, h_stride, B, H, W, workspace, workspace_bytes, gw2, gb2, ST(stream));
+}
+int sininn_conv3_smallk_bits_supported(const sininn_conv_args* args) { return conv3_smallk_bf16_supported(args); }
+int sininn_conv3_smallk_bits(const sininn_conv_args* args, unsigned* bits, void* stream) {
+  SININN_CHECK(bits != nullptr, "sininn_conv3_smallk_bits: bits is NULL");
+  return conv3_smallk_bf16_launch_bits(args, bits, ST(stream));
 }
 // test hook: the block executor's fused 1x1 subnet backward on / off (A/B against the pair + grouped weight-gradient path)
 void sininn_sub1_bwd_test_hook(int on) { conv_sub1_bwd_enable(on); conv3_smallk_enable(on); }   // every round-4 persistent kernel on / off
