@@ -517,9 +517,12 @@ int sininn_sqdiff_bwd(const float* x, const int64_t xs[4], const float* y, const
 #define SININN_MMD_SLOTS 16
 int sininn_mmd_gram(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4],
                     int B, int C, int H, int W, float* g, void* stream);
-/* loss.py:20-36 on the three Grams -> out[0] (mean) and coef[3][B][B] = dLoss/dGram (for backward). */
+/* loss.py:20-36 on the three Grams (the result block of g) -> out[0] (mean) and, when coef is not NULL, coef[4][B][B]:
+ * the matrices AX, BX, AY, BY (in this order, each [B][B] row-major) with dLoss/dx = AX x + BX y, dLoss/dy = AY x + BY y
+ * (rows = samples; the chain rule through the distances and the clamp is folded in). */
 int sininn_mmd_finish(const float* g, int B, int rev, float* out, float* coef, void* stream);
-/* gx[b,:] = scale*( sum_j (coefXX[b][j]+coefXX[j][b]) x[j,:] + coefXY[b][j] y[j,:] ), gy likewise. */
+/* coef = the 4*B*B floats sininn_mmd_finish wrote:  gx[i,:] = scale[0] * sum_j ( AX[i][j] x[j,:] + BX[i][j] y[j,:] ),
+ * gy[i,:] = scale[0] * sum_j ( AY[i][j] x[j,:] + BY[i][j] y[j,:] ).  gx or gy may be NULL (not both). */
 int sininn_mmd_bwd(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4],
                    int B, int C, int H, int W, const float* coef, const float* scale,
                    float* gx, const int64_t gxs[4], float* gy, const int64_t gys[4], void* stream);

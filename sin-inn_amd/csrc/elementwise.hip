@@ -304,6 +304,16 @@ int mmd_gram_launch(const float* x, const int64_t xs[4], const float* y, const i
   const int64_t K = (int64_t)C * H * W;
   const int blocks = (int)((K + MMD_KC - 1) / MMD_KC < 1024 ? (K + MMD_KC - 1) / MMD_KC : 1024);
   const size_t lds = (size_t)2 * B * (MMD_KC + 1) * sizeof(float);
+  if (lds > 64 * 1024) {
+    // only B == 64 (66 048 bytes): legal where the device gives a block more than 64 KiB of LDS, refused elsewhere
+    int dev = 0, limit = 0;
+    SININN_CHECK(hipGetDevice(&dev) == hipSuccess &&
+                 hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess,
+                 "mmd_gram: cannot query the LDS limit of the device");
+    SININN_CHECK(lds <= (size_t)limit, "mmd_gram: batch %d needs %zu bytes of LDS, the device allows %d per block", B, lds, limit);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mmd_gram_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { set_error("mmd_gram: cannot raise the LDS limit to %zu bytes of LDS", lds); return 1; }
+  }
   hipLaunchKernelGGL(mmd_gram_kernel, dim3(blocks), dim3(256), lds, st, x, mk(xs), y, mk(ys), B, C, H, W,
                      xs[3] == 1 ? 1 : 0, g);
   SININN_LAUNCH_CHECK("mmd_gram");

@@ -409,6 +409,21 @@ def test_descriptor_guards_refuse_before_any_launch():
         assert rc != 0 and word in lib.sininn_last_error(), (over, lib.sininn_last_error())
 
 
+def test_mmd_gram_refuses_batches_beyond_its_lds_staging():
+    """mmd_gram stages 2 * B * 129 floats of LDS per block: batches outside 1..64 are refused with the ordinary error return before
+    anything is launched (B == 64 itself, 66 048 bytes, is checked against the device's per-block limit at launch time:
+    tests/test_gpu_elementwise_sizes.py)."""
+    import sin_inn_amd
+    from sin_inn_amd import _lib
+    lib = _lib.lib()
+    fake = 0x7f0000000000                         # never dereferenced on the host
+    st = _lib.I64x4(48, 16, 4, 1)
+    for b in (65, 128, 0, -1):
+        assert lib.sininn_mmd_gram(fake, st, fake, st, b, 3, 4, 4, fake, None) != 0
+        assert b'batch must be in 1..64' in lib.sininn_last_error()
+    assert lib.sininn_mmd_finish(fake, 65, 0, fake, fake, None) != 0
+
+
 def test_32_bit_staging_offsets_are_range_checked_on_the_host():
     """Round 3 moved the staging loops to 32-bit byte offsets (raw buffer loads inside one image, per-tile descriptors in the
     weight gradient): shapes those offsets cannot address are refused before any launch (no GPU needed)."""
