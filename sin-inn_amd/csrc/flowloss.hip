@@ -133,10 +133,14 @@ __global__ void softsplat_bwd_kernel(const float* __restrict__ in, const float* 
   const int64_t r = idx % HW;
   const int y = (int)(r / W), x = (int)(r % W);
   const float ox = (float)x + flow[(b * 2 + 0) * HW + r], oy = (float)y + flow[(b * 2 + 1) * HW + r];
-  const bool nan = !(ox == ox) || !(oy == oy);
-  SplatTaps t = splat_taps(nan ? 0.f : ox, nan ? 0.f : oy, H, W);
-  if (nan) t.vnw = t.vne = t.vsw = t.vse = false;
-  const float fx = ox - (float)t.nwx, fy = oy - (float)t.nwy;   // fractional parts
+  // a pixel the forward skipped (NaN, +-inf or |target| >= 1e9) contributed nothing: both gradients are 0 there.  The guard is
+  // also what keeps the loads in bounds: a target of +inf or >= 2^31 converts to INT_MAX, nwx + 1 wraps, and the compiler (which
+  // may assume it does not) then finds the east taps inside the image and reads gout at o_nw + 1.  Without it a -inf target gives
+  // 0 * inf = NaN in gin / gflow, and a NaN one a NaN gflow (fx = NaN).
+  const bool skip = !(fabsf(ox) < 1e9f) || !(fabsf(oy) < 1e9f);
+  SplatTaps t = splat_taps(skip ? 0.f : ox, skip ? 0.f : oy, H, W);
+  if (skip) t.vnw = t.vne = t.vsw = t.vse = false;
+  const float fx = skip ? 0.f : ox - (float)t.nwx, fy = skip ? 0.f : oy - (float)t.nwy;   // fractional parts
   // d/dx of (nw, ne, sw, se) = (-(1-fy), (1-fy), -fy, fy);  d/dy = (-(1-fx), -fx, (1-fx), fx)
   const int64_t o_nw = (int64_t)t.nwy * W + t.nwx;
   float gfx = 0.f, gfy = 0.f;
