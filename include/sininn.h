@@ -35,7 +35,7 @@ extern "C" {
 int sininn_version(void);
 const char* sininn_last_error(void);
 /* sizeof() of descriptor struct `which` as THIS library was compiled: 0 sininn_conv_args, 1 sininn_wgrad_item,
- * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args; 0 for an unknown index.  A binding written in
+ * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args, 7 sininn_flownet_args; 0 for an unknown index.  A binding written in
  * another language (the ctypes mirrors in sin-inn_amd/_lib.py) checks its own layout against it at load time (ABI v4). */
 size_t sininn_sizeof(int which);
 /* A HIP stream at an explicit priority (lower number = higher priority; range from sininn_stream_priority_range: `least` is the
@@ -643,6 +643,49 @@ int sininn_bilateral_smooth(const float* img, const float* flow, int B, int C, i
                             float edge_constant, float weight, float* acc, float* out, void* stream);
 int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int C, int H, int W, int order, int gauss,
                                 float edge_constant, float weight, const float* gscale, float* gflow, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The flow-field network of the flow trainer: coordinate MLP, forward and backward (csrc/flownet.hip).
+ *   video-interpolation/model.py:490-505 RbfModel (RadialBasisEncoding, model.py:343-366: exp(-sigma_k^2 |x - c_k|^2)),
+ *   model.py:418-433 FFModel / model.py:454-469 UFFModel (FourierFeatures.forward, model.py:230-238: x * 2 pi, x @ frequencies,
+ *   sin / cos interleaved), MLP model.py:31-43, all with the ModelParams defaults (model.py:18-28): 3 -> 512 -> 256 -> 256 -> 256 -> 4.
+ *   forward = FlowTrainer.forward (video-interpolation/trainer.py:37-45): poses = meshgrid(times, linspace(-1,1,H),
+ *   linspace(-1,1,W)); flows[t][c][y][x] = net(poses)[p][c] * scale, flow12 = flows[:, :2], flow21 = flows[:, 2:].
+ * The axis vectors are DEVICE arrays computed by the caller (torch.linspace: bit-identical coordinates); neither the poses nor
+ * the N x 512 encoding are ever stored.  Weights are nn.Linear's own [out][in] layout: there is no packing step.
+ *   forward : writes flows; if saved != NULL (training) also the three post-ReLU hidden layers, [3][Npad][256], Npad = N rounded
+ *             up to 64 (sininn_flownet_saved_bytes(N)); every row is written on every call.
+ *   backward: dflows [T][4][H][W] -> gw[0..3] / gb[0..3] (OVERWRITTEN, nn.Linear layout, scale folded in).  Needs the saved
+ *             buffer of the forward call on the same weights and a workspace of sininn_flownet_workspace_bytes(N) bytes (the three
+ *             hidden gradients, two transposed weights, per-block partial sums); sums over points are added in a fixed order
+ *             (no floating-point atomics): two calls on the same inputs are bitwise equal.  The ReLU gates the forward took are
+ *             saved > 0.
+ * Borrowed pointers, 16-byte aligned (axis vectors and biases: 4), the caller's stream, non-zero return + sininn_last_error.
+ * sininn_flownet_supported: 1 if the sizes are the ones the kernels are built for, else 0 (callers raise, there is no second path).
+ * ---------------------------------------------------------------------------------------------- */
+#define SININN_FLOWNET_RBF 0     /* enc_a = centres [512][3], enc_b = sigma [512]                                  */
+#define SININN_FLOWNET_FOURIER 1 /* enc_a = frequencies [3][256], enc_b unused (FFN and UFF differ in the buffer only) */
+typedef struct sininn_flownet_args {
+  size_t struct_bytes;                    /* must be sizeof(sininn_flownet_args)                                          */
+  int encoding;                           /* SININN_FLOWNET_*                                                             */
+  int enc_dim, hidden, layers, out_dim;   /* 512, 256, 3, 4                                                               */
+  int T, H, W;                            /* N = T H W points, at most 2^22                                               */
+  float scale;
+  const float *times, *ys, *xs;           /* [T], [H], [W]                                                                */
+  const float *enc_a, *enc_b;
+  const float* w[4];                      /* [256][512], [256][256], [256][256], [4][256]                                 */
+  const float* b[4];
+  float* flows;                           /* forward: out [T][4][H][W]                                                    */
+  float* saved; size_t saved_bytes;       /* forward: out or NULL; backward: in                                           */
+  const float* dflows;                    /* backward: in [T][4][H][W]                                                    */
+  float* gw[4]; float* gb[4];             /* backward: out                                                                */
+  void* workspace; size_t workspace_bytes;
+} sininn_flownet_args;
+int sininn_flownet_supported(const sininn_flownet_args* args);
+size_t sininn_flownet_saved_bytes(int64_t n_points);
+size_t sininn_flownet_workspace_bytes(int64_t n_points);
+int sininn_flownet_forward(const sininn_flownet_args* args, void* stream);
+int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
 
 #ifdef __cplusplus
 }

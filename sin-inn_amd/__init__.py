@@ -10,6 +10,7 @@ from .optim import FusedAdam                                                 # n
 from . import irn                                                             # noqa: F401
 from . import functional                                                     # noqa: F401
 from . import flowloss                                                       # noqa: F401
+from . import flownet                                                        # noqa: F401
 
 __all__ = ['GLOWCouplingBlock', 'IRevNetDownsampling', 'PermuteRandom', 'InputNode', 'Node', 'OutputNode',
            'ReversibleGraphNet', 'FusedAdam', 'functional', 'ops']

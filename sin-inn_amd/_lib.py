@@ -108,6 +108,21 @@ class DenseBf16Args(C.Structure):
         self.buf_bf16 = self.w_bf16 = 1
 
 
+class FlowNetArgs(C.Structure):
+    """Mirror of sininn_flownet_args."""
+    _fields_ = [('struct_bytes', C.c_size_t), ('encoding', C.c_int),
+                ('enc_dim', C.c_int), ('hidden', C.c_int), ('layers', C.c_int), ('out_dim', C.c_int),
+                ('T', C.c_int), ('H', C.c_int), ('W', C.c_int), ('scale', C.c_float),
+                ('times', c_f), ('ys', c_f), ('xs', c_f), ('enc_a', c_f), ('enc_b', c_f),
+                ('w', c_f * 4), ('b', c_f * 4), ('flows', c_f), ('saved', c_f), ('saved_bytes', C.c_size_t),
+                ('dflows', c_f), ('gw', c_f * 4), ('gb', c_f * 4),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(FlowNetArgs)
+
+
 class PackDesc(C.Structure):
     """Mirror of sininn_pack_desc."""
     _fields_ = [('w', c_f), ('bias', c_f), ('N', C.c_int), ('Cin', C.c_int), ('ksize', C.c_int), ('colmap', c_i),
@@ -229,6 +244,11 @@ _SIGS = {
     'sininn_bayer_bin': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'sininn_bayer_demosaic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'sininn_frames_to_u8': (C.c_int, [c_f, I64x4, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'sininn_flownet_supported': (C.c_int, [C.POINTER(FlowNetArgs)]),
+    'sininn_flownet_saved_bytes': (C.c_size_t, [C.c_int64]),
+    'sininn_flownet_workspace_bytes': (C.c_size_t, [C.c_int64]),
+    'sininn_flownet_forward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
+    'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, C.c_void_p]),
 }
@@ -250,7 +270,8 @@ def lib():
             fn.restype, fn.argtypes = res, args
         if handle.sininn_version() != 4:
             raise ImportError('libsininn.so ABI version mismatch')
-        for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc, DenseBf16Args)):
+        for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc, DenseBf16Args,
+                                        FlowNetArgs)):
             if handle.sininn_sizeof(which) != C.sizeof(mirror):
                 raise ImportError(f'{mirror.__name__}: the ctypes mirror has {C.sizeof(mirror)} bytes, libsininn.so was built '
                                   f'with {handle.sininn_sizeof(which)} (include/sininn.h changed without _lib.py)')

@@ -118,6 +118,10 @@ int profile_classes_end(int n, double* ms, double* flops, int* launches);
 int profile_classes_bytes(int n, double* bytes);
 void profile_begin(int h, unsigned long long* stamps, int max_launches);
 int profile_end(int* count, float* total_ms);
+size_t flownet_saved_bytes(int64_t n);
+size_t flownet_workspace_bytes(int64_t n);
+int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
+int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -239,6 +243,7 @@ size_t sininn_sizeof(int which) {
     case 4: return sizeof(sininn_subnet);
     case 5: return sizeof(sininn_pack_desc);
     case 6: return sizeof(sininn_dense_bf16_args);
+    case 7: return sizeof(sininn_flownet_args);
     default: return 0;
   }
 }
@@ -551,5 +556,15 @@ int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
                      float eps, float weight_decay, int step, float grad_scale, void* stream) {
   return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ST(stream));
 }
+
+int sininn_flownet_supported(const sininn_flownet_args* a) {
+  return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
+         (a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER) && a->enc_dim == 512 && a->hidden == 256 &&
+         a->layers == 3 && a->out_dim == 4;
+}
+size_t sininn_flownet_saved_bytes(int64_t n_points) { return flownet_saved_bytes(n_points); }
+size_t sininn_flownet_workspace_bytes(int64_t n_points) { return flownet_workspace_bytes(n_points); }
+int sininn_flownet_forward(const sininn_flownet_args* args, void* stream) { return flownet_forward_launch(args, ST(stream)); }
+int sininn_flownet_backward(const sininn_flownet_args* args, void* stream) { return flownet_backward_launch(args, ST(stream)); }
 
 }  // extern "C"

@@ -1,0 +1,539 @@
+// The flow-field network of the flow trainer (reference: video-interpolation/model.py, RbfModel / FFModel / UFFModel with the
+// ModelParams defaults, evaluated by FlowTrainer.forward, video-interpolation/trainer.py:37-45):
+//     poses = meshgrid(times, linspace(-1, 1, h), linspace(-1, 1, w))            N = t h w points of 3 coordinates
+//     enc   = exp(-sigma_k^2 |x - c_k|^2)                       (RBF,  512 centres,      model.py:349-356)
+//           | sin / cos (2 pi x . f_k), interleaved             (FFN / UFF, 256 frequencies, model.py:230-238)
+//     h1 = relu(enc W1^T + b1)   h2 = relu(h1 W2^T + b2)   h3 = relu(h2 W3^T + b3)   out = h3 W4^T + b4        (model.py:36-43)
+//     flows[t][c][y][x] = out[p][c] * scale                                                                    (trainer.py:44)
+// fp32 on v_mfma_f32_16x16x4_f32.  Neither the N x 3 poses nor the N x 512 encoding exist in memory in either pass: a lane
+// computes the four encoded features its A fragment needs from the point's three coordinates (flownet_fwd_kernel) or writes
+// them straight into the LDS operand tile (flownet_wgrad_kernel<.., true>); both call encode4, so the weight gradient of layer 1
+// sees bitwise the encoding the forward pass multiplied.
+//
+// forward   flownet_fwd_kernel: block = 256 threads (4 waves, two blocks per CU), grid-stride over 64-point tiles.  Wave w owns
+//           hidden columns [64 w, 64 w + 64) of all 64 rows: 16 accumulator tiles.  Layer 1's A operand comes from encode4, layers
+//           2 / 3 read the previous hidden tile from LDS ([64][260] floats, ONE buffer: the accumulators hold the next tile until
+//           every wave has finished reading), the weights stream from L2 as 16-byte loads of nn.Linear's own [out][in] layout (no
+//           packing).  Layer 4 (256 -> 4) is 256 dot products on the vector ALU.  Training mode copies each post-ReLU tile to
+//           `saved` ([3][Npad][256]); inference writes the flows only.
+// backward  flownet_bwd_chain_kernel: per tile  dout = dflows * scale;  gW4 / gb4 partials in registers over the block's tiles;
+//           dh3 = (dout W4) . [h3 > 0] on the vector ALU in place over the h3 tile;  dh2 = (dh3 W3) . [h2 > 0],
+//           dh1 = (dh2 W2) . [h1 > 0] with the forward's GEMM loop on transposed weights;  dh1..3 -> workspace.
+//           flownet_wgrad_kernel: gW_l[j][k] = sum_p dh_l[p][j] in_l[p][k] (in_1 = the regenerated encoding), gb_l = sum_p dh_l: a block
+//           owns a 128 x 128 output tile and a fixed set of point tiles (split over points), partial sums go to the workspace and
+//           flownet_reduce_kernel adds them in a fixed order: no floating-point atomics, two runs are bitwise equal.
+// Rows of the last tile beyond N are computed on a clamped point in the forward pass and carry dout = 0 in the backward pass, so
+// saved / workspace rows are always written before they are read and contribute exact zeros to every sum.
+#include "common.h"
+
+namespace sininn {
+
+namespace {
+
+constexpr int FN_P = 64;            // points per tile
+constexpr int FN_HID = 256;
+constexpr int FN_ENC = 512;
+constexpr int FN_OUT = 4;
+constexpr int FN_HS = FN_HID + 4;   // floats per row of the hidden tile in LDS (16-byte reads of 16 rows hit 64 distinct banks)
+constexpr int FN_NTHR = 256;
+constexpr int FN_WT = 128;          // weight-gradient output tile (FN_WT x FN_WT per block)
+constexpr int FN_WS = FN_WT + 16;   // floats per point row of a weight-gradient operand tile (4 rows x 16 lanes -> 64 banks)
+constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunks) x (output tiles) is about 512 blocks
+constexpr int FN_CHAIN_MAX_BLOCKS = 512;
+constexpr size_t FN_LDS = (size_t)(FN_P * FN_HS + FN_P * FN_OUT) * sizeof(float);
+constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
+
+struct FlowNetDev {
+  int T, H, W, N, ntiles;
+  float scale;
+  const float *times, *ys, *xs;
+  const float *enc_a, *enc_b;
+  const float* w[4];
+  const float* b[4];
+  float* flows;
+  float* saved;            // [3][ntiles * 64][256] or nullptr (inference)
+  const float* dflows;
+  float* dh;               // [3][ntiles * 64][256]
+  const float* wt;         // W2^T, W3^T
+  float* part;             // partial sums
+};
+
+struct Coord { float t, y, x; };
+
+__device__ __forceinline__ Coord point_coord(const FlowNetDev& q, int p) {
+  p = p < q.N ? p : q.N - 1;
+  const int hw = q.H * q.W;
+  const int t = p / hw, rem = p - t * hw;
+  const int y = rem / q.W, x = rem - y * q.W;
+  return Coord{q.times[t], q.ys[y], q.xs[x]};
+}
+
+// features f0 .. f0 + 3 (f0 % 4 == 0) of one point
+template <int KIND>
+__device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int f0) {
+  f32x4 o;
+  if constexpr (KIND == SININN_FLOWNET_RBF) {
+    const f32x4* cp = reinterpret_cast<const f32x4*>(q.enc_a + 3 * f0);   // centres [512][3]
+    const f32x4 c0 = cp[0], c1 = cp[1], c2 = cp[2];
+    const f32x4 sg = *reinterpret_cast<const f32x4*>(q.enc_b + f0);
+    const float cc[12] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3], c2[0], c2[1], c2[2], c2[3]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dt = c.t - cc[3 * j], dy = c.y - cc[3 * j + 1], dx = c.x - cc[3 * j + 2];
+      const float d = dt * dt + dy * dy + dx * dx;
+      o[j] = expf(-(d * (sg[j] * sg[j])));
+    }
+  } else {
+    // phase in REVOLUTIONS: each product is split into its rounded value and its exact rounding error, the rounded value is
+    // reduced to [-1/2, 1/2] exactly, so the phase of a 75-cycle frequency is as good as that of a slow one; sincospi does the rest
+    const int f = f0 >> 1;                                                 // frequencies [3][256]
+    const f32x2 fa = *reinterpret_cast<const f32x2*>(q.enc_a + f);
+    const f32x2 fb = *reinterpret_cast<const f32x2*>(q.enc_a + 256 + f);
+    const f32x2 fc = *reinterpret_cast<const f32x2*>(q.enc_a + 512 + f);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const float p0 = c.t * fa[u], p1 = c.y * fb[u], p2 = c.x * fc[u];
+      const float e = fmaf(c.t, fa[u], -p0) + fmaf(c.y, fb[u], -p1) + fmaf(c.x, fc[u], -p2);
+      const float r = ((p0 - rintf(p0)) + (p1 - rintf(p1)) + (p2 - rintf(p2))) + e;
+      float s, co;
+      sincospif(2.f * r, &s, &co);
+      o[2 * u] = s;
+      o[2 * u + 1] = co;
+    }
+  }
+  return o;
+}
+
+// acc[m][n] += A[rows 16 m ..][k] W[cols cw + 16 n ..][k]: A from the LDS tile, W row-major [256][256] from L2
+__device__ __forceinline__ void gemm_lds(const float* hs, const float* w, int cw, int li, int kq, f32x4 (&acc)[4][4]) {
+#pragma unroll 2
+  for (int s = 0; s < FN_HID / 16; ++s) {
+    f32x4 bf[4], af[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const f32x4*>(w + (size_t)(cw + 16 * n + li) * FN_HID + 16 * s + 4 * kq);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) af[m] = *reinterpret_cast<const f32x4*>(hs + (16 * m + li) * FN_HS + 16 * s + 4 * kq);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][j], bf[n][j], acc[m][n], 0, 0, 0);
+  }
+}
+
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// accumulators -> LDS tile; RELU: + bias, max(., 0)
+template <bool RELU>
+__device__ __forceinline__ void store_acc(float* hs, const float* bias, int cw, int li, int kq, const f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const float bq = RELU ? bias[cw + 16 * n + li] : 0.f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = acc[m][n][r] + bq;
+        hs[(16 * m + 4 * kq + r) * FN_HS + cw + 16 * n + li] = RELU ? fmaxf(v, 0.f) : v;
+      }
+  }
+}
+
+// LDS tile -> rows [64 tile, 64 tile + 64) of a [Npad][256] array
+__device__ __forceinline__ void copy_tile_out(const float* hs, float* dst, int tile, int tid) {
+#pragma unroll 4
+  for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
+    const int f = tid + FN_NTHR * u;
+    const int row = f >> 6, c4 = (f & 63) * 4;
+    *reinterpret_cast<f32x4*>(dst + ((size_t)tile * FN_P + row) * FN_HID + c4) = *reinterpret_cast<const f32x4*>(hs + row * FN_HS + c4);
+  }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
+  extern __shared__ __attribute__((aligned(16))) float fn_smem[];
+  float* const hs = fn_smem;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, kq = lane >> 4;
+  const int cw = wave * 64;
+  const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
+  const int hw = q.H * q.W;
+
+  for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
+    Coord pc[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) pc[m] = point_coord(q, tile * FN_P + 16 * m + li);
+
+    f32x4 acc[4][4];
+    zero_acc(acc);
+    // ---- layer 1: the A fragment is generated, never stored ----
+#pragma unroll 1
+    for (int s = 0; s < FN_ENC / 16; ++s) {
+      f32x4 bf[4], af[4];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const f32x4*>(q.w[0] + (size_t)(cw + 16 * n + li) * FN_ENC + 16 * s + 4 * kq);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) af[m] = encode4<KIND>(q, pc[m], 16 * s + 4 * kq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][j], bf[n][j], acc[m][n], 0, 0, 0);
+    }
+    __syncthreads();                       // the previous tile's layer 4 has read hs
+    store_acc<true>(hs, q.b[0], cw, li, kq, acc);
+    __syncthreads();
+    if (q.saved) copy_tile_out(hs, q.saved, tile, tid);
+    // ---- layers 2 and 3 ----
+#pragma unroll 1
+    for (int l = 1; l < 3; ++l) {
+      zero_acc(acc);
+      gemm_lds(hs, q.w[l], cw, li, kq, acc);
+      __syncthreads();                     // every wave has read the whole tile (and copied it out)
+      store_acc<true>(hs, q.b[l], cw, li, kq, acc);
+      __syncthreads();
+      if (q.saved) copy_tile_out(hs, q.saved + l * lstride, tile, tid);
+    }
+    // ---- layer 4 on the vector ALU: thread = (channel tid / 64, point tid % 64) ----
+    {
+      const int c = tid >> 6, pl = tid & 63;
+      const float* w4 = q.w[3] + c * FN_HID;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 8
+      for (int k = 0; k < FN_HID; k += 4) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(hs + pl * FN_HS + k);
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(w4 + k);
+        a0 = fmaf(h[0], wv[0], a0);
+        a1 = fmaf(h[1], wv[1], a1);
+        a2 = fmaf(h[2], wv[2], a2);
+        a3 = fmaf(h[3], wv[3], a3);
+      }
+      const int p = tile * FN_P + pl;
+      if (p < q.N) {
+        const int t = p / hw, rem = p - t * hw;
+        q.flows[((size_t)t * FN_OUT + c) * hw + rem] = (((a0 + a1) + (a2 + a3)) + q.b[3][c]) * q.scale;
+      }
+    }
+  }
+}
+
+// out[k][j] = in[j][k] for W2 and W3 (blockIdx.y): the data-gradient GEMMs then read 16-byte rows like the forward pass does
+__global__ __launch_bounds__(FN_NTHR) void flownet_transpose_kernel(const float* w2, const float* w3, float* wt) {
+  const float* in = blockIdx.y ? w3 : w2;
+  float* out = wt + (size_t)blockIdx.y * FN_HID * FN_HID;
+  const int j = blockIdx.x, k = threadIdx.x;
+  out[k * FN_HID + j] = in[j * FN_HID + k];
+}
+
+__global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDev q) {
+  extern __shared__ __attribute__((aligned(16))) float fn_smem[];
+  float* const hs = fn_smem;
+  float* const dos = fn_smem + FN_P * FN_HS;           // [64][4]: dout of the tile
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, kq = lane >> 4;
+  const int cw = wave * 64;
+  const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
+  const int hw = q.H * q.W;
+
+  float w4k[4], gw4[4] = {0.f, 0.f, 0.f, 0.f}, gb4 = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) w4k[c] = q.w[3][c * FN_HID + tid];
+
+  for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
+    __syncthreads();                                   // the previous tile is done with hs / dos
+    // h3 tile -> LDS, dout = dflows * scale (0 beyond N)
+#pragma unroll 4
+    for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
+      const int f = tid + FN_NTHR * u;
+      const int row = f >> 6, c4 = (f & 63) * 4;
+      *reinterpret_cast<f32x4*>(hs + row * FN_HS + c4) =
+          *reinterpret_cast<const f32x4*>(q.saved + 2 * lstride + ((size_t)tile * FN_P + row) * FN_HID + c4);
+    }
+    {
+      const int c = tid >> 6, pl = tid & 63;
+      const int p = tile * FN_P + pl;
+      float v = 0.f;
+      if (p < q.N) {
+        const int t = p / hw, rem = p - t * hw;
+        v = q.dflows[((size_t)t * FN_OUT + c) * hw + rem] * q.scale;
+      }
+      dos[pl * FN_OUT + c] = v;
+    }
+    __syncthreads();
+    // gW4 += dout^T h3;  dh3 = (dout W4) . [h3 > 0] in place: thread = hidden column tid
+#pragma unroll 4
+    for (int p = 0; p < FN_P; ++p) {
+      const f32x4 d = *reinterpret_cast<const f32x4*>(dos + p * FN_OUT);
+      const float h = hs[p * FN_HS + tid];
+      float v = 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        gw4[c] = fmaf(d[c], h, gw4[c]);
+        v = fmaf(d[c], w4k[c], v);
+      }
+      hs[p * FN_HS + tid] = h > 0.f ? v : 0.f;
+    }
+    if (tid < FN_OUT) {
+      float s = 0.f;
+      for (int p = 0; p < FN_P; ++p) s += dos[p * FN_OUT + tid];
+      gb4 += s;
+    }
+    __syncthreads();
+    copy_tile_out(hs, q.dh + 2 * lstride, tile, tid);
+    // dh2 = (dh3 W3) . [h2 > 0], dh1 = (dh2 W2) . [h1 > 0]
+#pragma unroll 1
+    for (int l = 1; l >= 0; --l) {
+      f32x4 acc[4][4];
+      zero_acc(acc);
+      gemm_lds(hs, q.wt + (size_t)l * FN_HID * FN_HID, cw, li, kq, acc);
+      __syncthreads();
+      store_acc<false>(hs, nullptr, cw, li, kq, acc);
+      __syncthreads();
+#pragma unroll 4
+      for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
+        const int f = tid + FN_NTHR * u;
+        const int row = f >> 6, c4 = (f & 63) * 4;
+        const size_t g = ((size_t)tile * FN_P + row) * FN_HID + c4;
+        const f32x4 h = *reinterpret_cast<const f32x4*>(q.saved + l * lstride + g);
+        f32x4 v = *reinterpret_cast<const f32x4*>(hs + row * FN_HS + c4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = h[j] > 0.f ? v[j] : 0.f;
+        *reinterpret_cast<f32x4*>(q.dh + l * lstride + g) = v;
+        if (l) *reinterpret_cast<f32x4*>(hs + row * FN_HS + c4) = v;
+      }
+      __syncthreads();
+    }
+  }
+  float* const out = q.part + (size_t)blockIdx.x * (FN_OUT * FN_HID + FN_OUT);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) out[c * FN_HID + tid] = gw4[c];
+  if (tid < FN_OUT) out[FN_OUT * FN_HID + tid] = gb4;
+}
+
+// part[chunk][j][k] = sum over the chunk's point tiles of dh[p][j] in[p][k]  (+ [chunk][256 * KF + j] = sum_p dh[p][j]);
+// grid = (2 * KF / 128 output tiles, chunks); ENC: in = the encoding (KF = 512), else a saved hidden layer (KF = 256)
+template <int KIND, bool ENC>
+__global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q, const float* dh, const float* in) {
+  constexpr int KF = ENC ? FN_ENC : FN_HID;
+  constexpr int NU = FN_P * FN_WT / 4 / FN_NTHR;       // 16-byte units per thread and operand tile
+  extern __shared__ __attribute__((aligned(16))) float fn_smem[];
+  float* const as = fn_smem;                           // [64][FN_WS]: dh tile
+  float* const bs = fn_smem + FN_P * FN_WS;            // [64][FN_WS]: input tile
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, kq = lane >> 4;
+  const int j0 = (blockIdx.x & 1) * FN_WT, k0 = (blockIdx.x >> 1) * FN_WT;
+  const int jw = (wave & 1) * 64, kw = (wave >> 1) * 64;
+  const int chunk = blockIdx.y, nchunks = gridDim.y;
+
+  f32x4 acc[4][4];
+  zero_acc(acc);
+  float bsum = 0.f;
+  f32x4 va[NU], vb[NU];
+  auto fetch = [&](int tile) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int f = tid + FN_NTHR * u;
+      const int row = f >> 5, c4 = (f & 31) * 4;
+      const size_t g = ((size_t)tile * FN_P + row) * FN_HID;
+      va[u] = *reinterpret_cast<const f32x4*>(dh + g + j0 + c4);
+      if constexpr (!ENC) vb[u] = *reinterpret_cast<const f32x4*>(in + g + k0 + c4);
+    }
+  };
+  if (chunk < q.ntiles) fetch(chunk);
+  for (int tile = chunk; tile < q.ntiles; tile += nchunks) {
+    __syncthreads();                                   // the previous tile's MFMAs have read as / bs
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int f = tid + FN_NTHR * u;
+      const int row = f >> 5, c4 = (f & 31) * 4;
+      *reinterpret_cast<f32x4*>(as + row * FN_WS + c4) = va[u];
+      if constexpr (ENC) vb[u] = encode4<KIND>(q, point_coord(q, tile * FN_P + row), k0 + c4);
+      *reinterpret_cast<f32x4*>(bs + row * FN_WS + c4) = vb[u];
+    }
+    __syncthreads();
+    if (tile + nchunks < q.ntiles) fetch(tile + nchunks);
+    if (k0 == 0 && tid < FN_WT) {
+      float s = 0.f;
+#pragma unroll 8
+      for (int p = 0; p < FN_P; ++p) s += as[p * FN_WS + tid];
+      bsum += s;
+    }
+#pragma unroll 2
+    for (int ks = 0; ks < FN_P / 4; ++ks) {
+      float a[4], b[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) a[m] = as[(4 * ks + kq) * FN_WS + jw + 16 * m + li];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) b[n] = bs[(4 * ks + kq) * FN_WS + kw + 16 * n + li];
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
+    }
+  }
+  float* const out = q.part + (size_t)chunk * (FN_HID * KF + FN_HID);
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) out[(size_t)(j0 + jw + 16 * m + 4 * kq + r) * KF + k0 + kw + 16 * n + li] = acc[m][n][r];
+  if (k0 == 0 && tid < FN_WT) out[FN_HID * KF + j0 + tid] = bsum;
+}
+
+// gw[i] = sum_c part[c][i] (i < nw), gb[i - nw] = sum_c part[c][i] (nw <= i < nw + nb): chunks in index order, always
+__global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* part, int nparts, int nw, int nb, float* gw, float* gb) {
+  const int i = blockIdx.x * FN_NTHR + threadIdx.x;
+  if (i >= nw + nb) return;
+  const size_t stride = (size_t)nw + nb;
+  float s = 0.f;
+  for (int c = 0; c < nparts; ++c) s += part[c * stride + i];
+  if (i < nw) gw[i] = s;
+  else gb[i - nw] = s;
+}
+
+int wgrad_chunks(int ntiles, int kf) {
+  const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 for layer 1
+  return ntiles < want ? ntiles : want;
+}
+
+int chain_blocks(int ntiles) { return ntiles < FN_CHAIN_MAX_BLOCKS ? ntiles : FN_CHAIN_MAX_BLOCKS; }
+
+size_t part_floats(int ntiles) {
+  size_t a = (size_t)wgrad_chunks(ntiles, FN_HID) * (FN_HID * FN_HID + FN_HID);
+  const size_t b = (size_t)wgrad_chunks(ntiles, FN_ENC) * (FN_HID * FN_ENC + FN_HID);
+  const size_t c = (size_t)chain_blocks(ntiles) * (FN_OUT * FN_HID + FN_OUT);
+  a = a > b ? a : b;
+  return a > c ? a : c;
+}
+
+template <class K>
+int raise_lds(K k, size_t bytes, const char* name) {
+  if (bytes > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) { set_error("%s: cannot raise the LDS limit to %zu", name, bytes); return 1; }
+  }
+  return 0;
+}
+
+int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
+  SININN_CHECK(a != nullptr, "%s: null args", who);
+  SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
+               a->struct_bytes, sizeof(sininn_flownet_args));
+  SININN_CHECK(sininn_flownet_supported(a), "%s: unsupported network (encoding %d, %d -> %d x %d -> %d; built for RBF / Fourier, 512 -> 256 x 3 -> 4)",
+               who, a->encoding, a->enc_dim, a->hidden, a->layers, a->out_dim);
+  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
+               who, a->T, a->H, a->W);
+  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding != SININN_FLOWNET_RBF || a->enc_b), "%s: null axis / encoding pointer", who);
+  SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
+  for (int l = 0; l < 4; ++l) {
+    SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
+    SININN_CHECK(aligned16(a->w[l]), "%s: weight %d must be 16-byte aligned", who, l);
+    q.w[l] = a->w[l];
+    q.b[l] = a->b[l];
+  }
+  q.T = a->T; q.H = a->H; q.W = a->W;
+  q.N = a->T * a->H * a->W;
+  q.ntiles = (q.N + FN_P - 1) / FN_P;
+  q.scale = a->scale;
+  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
+  q.enc_a = a->enc_a; q.enc_b = a->enc_b;
+  q.flows = nullptr; q.saved = nullptr; q.dflows = nullptr; q.dh = nullptr; q.wt = nullptr; q.part = nullptr;
+  return 0;
+}
+
+}  // namespace
+
+size_t flownet_saved_bytes(int64_t n) {
+  if (n <= 0) return 0;
+  return (size_t)3 * (size_t)((n + FN_P - 1) / FN_P) * FN_P * FN_HID * sizeof(float);
+}
+
+size_t flownet_workspace_bytes(int64_t n) {
+  if (n <= 0 || n > ((int64_t)1 << 22)) return 0;
+  const int ntiles = (int)((n + FN_P - 1) / FN_P);
+  return flownet_saved_bytes(n) + ((size_t)2 * FN_HID * FN_HID + part_floats(ntiles)) * sizeof(float);
+}
+
+int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
+  FlowNetDev q;
+  if (int rc = check_args(a, "flownet_forward", q)) return rc;
+  SININN_CHECK(a->flows != nullptr, "flownet_forward: null flows");
+  q.flows = a->flows;
+  if (a->saved) {
+    SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_forward: saved holds %zu bytes, %zu needed", a->saved_bytes,
+                 flownet_saved_bytes(q.N));
+    SININN_CHECK(aligned16(a->saved), "flownet_forward: saved must be 16-byte aligned");
+    q.saved = a->saved;
+  }
+  auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_fwd_kernel<SININN_FLOWNET_RBF> : flownet_fwd_kernel<SININN_FLOWNET_FOURIER>;
+  if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
+  const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS, st, q);
+  SININN_LAUNCH_CHECK("flownet_forward");
+  return 0;
+}
+
+int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) {
+  FlowNetDev q;
+  if (int rc = check_args(a, "flownet_backward", q)) return rc;
+  SININN_CHECK(a->dflows && a->saved && a->workspace, "flownet_backward: null dflows / saved / workspace");
+  SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_backward: saved holds %zu bytes, %zu needed", a->saved_bytes,
+               flownet_saved_bytes(q.N));
+  SININN_CHECK(a->workspace_bytes >= flownet_workspace_bytes(q.N), "flownet_backward: workspace holds %zu bytes, %zu needed",
+               a->workspace_bytes, flownet_workspace_bytes(q.N));
+  SININN_CHECK(aligned16(a->saved) && aligned16(a->workspace), "flownet_backward: saved / workspace must be 16-byte aligned");
+  for (int l = 0; l < 4; ++l) SININN_CHECK(a->gw[l] && a->gb[l], "flownet_backward: null gradient pointer %d", l);
+  const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
+  float* const ws = static_cast<float*>(a->workspace);
+  float* const wt = ws + 3 * lstride;
+  q.saved = a->saved;
+  q.dflows = a->dflows;
+  q.dh = ws;
+  q.wt = wt;
+  q.part = wt + 2 * FN_HID * FN_HID;
+
+  hipLaunchKernelGGL(flownet_transpose_kernel, dim3(FN_HID, 2), dim3(FN_NTHR), 0, st, a->w[1], a->w[2], wt);
+  SININN_LAUNCH_CHECK("flownet_transpose");
+  if (raise_lds(flownet_bwd_chain_kernel, FN_LDS, "flownet_backward")) return 1;
+  const int cb = chain_blocks(q.ntiles);
+  hipLaunchKernelGGL(flownet_bwd_chain_kernel, dim3(cb), dim3(FN_NTHR), FN_LDS, st, q);
+  SININN_LAUNCH_CHECK("flownet_bwd_chain");
+  auto reduce = [&](int nparts, int nw, int nb, float* gw, float* gb) {
+    hipLaunchKernelGGL(flownet_reduce_kernel, dim3((nw + nb + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, q.part, nparts, nw, nb, gw, gb);
+  };
+  reduce(cb, FN_OUT * FN_HID, FN_OUT, a->gw[3], a->gb[3]);
+  SININN_LAUNCH_CHECK("flownet_reduce");
+  for (int l = 2; l >= 1; --l) {                       // gW3 = dh3^T h2, gW2 = dh2^T h1
+    auto k = flownet_wgrad_kernel<SININN_FLOWNET_RBF, false>;
+    if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
+    const int nc = wgrad_chunks(q.ntiles, FN_HID);
+    hipLaunchKernelGGL(k, dim3(2 * FN_HID / FN_WT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)(q.dh + l * lstride),
+                       (const float*)(q.saved + (l - 1) * lstride));
+    SININN_LAUNCH_CHECK("flownet_wgrad");
+    reduce(nc, FN_HID * FN_HID, FN_HID, a->gw[l], a->gb[l]);
+    SININN_LAUNCH_CHECK("flownet_reduce");
+  }
+  {
+    auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true> : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true>;
+    if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
+    const int nc = wgrad_chunks(q.ntiles, FN_ENC);
+    hipLaunchKernelGGL(k, dim3(2 * FN_ENC / FN_WT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)q.dh, (const float*)nullptr);
+    SININN_LAUNCH_CHECK("flownet_wgrad");
+    reduce(nc, FN_HID * FN_ENC, FN_HID, a->gw[0], a->gb[0]);
+    SININN_LAUNCH_CHECK("flownet_reduce");
+  }
+  return 0;
+}
+
+}  // namespace sininn

@@ -1,0 +1,291 @@
+"""The flow-field network of the flow trainer: a coordinate MLP evaluated at every pixel of every frame, forward and
+backward in libsininn.so (csrc/flownet.hip).
+
+    ModelParams / RbfModel / FFModel / UFFModel / model_dict   video-interpolation/model.py:11-28, 490-505, 418-433, 454-469, 681
+    flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
+
+The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
+`encode.frequencies`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
+first, then the four nn.Linear layers), so one `torch.manual_seed` gives the reference's numbers and a reference checkpoint
+loads.  The encodings are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
+(3 -> 512 -> 256 x 3 -> 4); any other size raises, there is no second implementation behind this module, and calling a model
+directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512 encoding never exist here.
+
+Out of scope: `siren`, `RFF` / `PRFF` (learnable frequencies), `RBFG`, the progressive models and their controllers, `PE`
+(the reference's PositionalEncoding.forward raises on any input, model.py:332), LAMB (the reference trains with apex
+FusedLAMB; these modules expose ordinary nn.Parameters and `sin_inn_amd.FusedAdam` drives them), Sintel / .flo IO.
+"""
+import ctypes as C
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as nnf
+
+from . import _lib
+from .ops import _stream, ptr
+
+check = _lib.check
+EPSILON = 1e-4
+RBF, FOURIER = 0, 1
+
+
+class ModelParams:
+    """model.py:11-28."""
+
+    def fill_args(self, **kwargs):
+        for key, item in kwargs.items():
+            if hasattr(self, key):
+                setattr(self, key, item)
+
+    def __init__(self, **kwargs):
+        self.domain_dim = 3
+        self.num_frequencies = 256
+        self.std = 25
+        self.power = 20
+        self.num_layers = 3
+        self.hidden_dim = 256
+        self.output_channels = 4
+        self.num_frequencies_pe = 4
+        self.std_rbf = 12
+        self.fill_args(**kwargs)
+
+
+class MLP(nn.Module):
+    """model.py:31-43: Linear / ReLU chain under `.model` (state_dict keys model.{0,2,4,..})."""
+
+    def __init__(self, layers):
+        super().__init__()
+        seq = []
+        for i in range(len(layers) - 1):
+            seq.append(nn.Linear(layers[i], layers[i + 1]))
+            if i < len(layers) - 2:
+                seq.append(nn.ReLU(True))
+        self.model = nn.Sequential(*seq)
+
+
+class RadialBasisEncoding(nn.Module):
+    """model.py:343-366 (buffers only; evaluated inside the kernels)."""
+    kind = RBF
+
+    def __init__(self, domain_dim, num_frequencies, std):
+        super().__init__()
+        self.domain_dim = domain_dim
+        self.num_frequencies = num_frequencies * 2
+        centres = torch.rand(self.num_frequencies, domain_dim) * 2 - 1
+        sigma = torch.randn(self.num_frequencies).abs() * std + 1
+        self.register_buffer('centres', centres)
+        self.register_buffer('sigma', sigma.sort()[0])
+
+    @property
+    def output_channels(self):
+        return self.num_frequencies
+
+    def kernel_buffers(self):
+        return self.centres, self.sigma
+
+
+class _FourierFeatures(nn.Module):
+    """model.py:224-249."""
+    kind = FOURIER
+
+    def __init__(self, domain_dim, num_frequencies, std):
+        super().__init__()
+        self.domain_dim = domain_dim
+        self.num_frequencies = num_frequencies
+        magnitude = self.init_magnitude(std)
+        magnitude = magnitude[magnitude.abs().argsort(0)]
+        frequencies = torch.randn(domain_dim, num_frequencies)
+        self.register_buffer('frequencies', nnf.normalize(frequencies, p=2, dim=0) * magnitude[None, :])
+
+    @property
+    def output_channels(self):
+        return self.num_frequencies * 2
+
+    def kernel_buffers(self):
+        return self.frequencies, None
+
+
+class GaussianRandomFourierFeatures(_FourierFeatures):
+    """model.py:252-260."""
+
+    def init_magnitude(self, std):
+        return torch.randn(self.num_frequencies) * std
+
+
+class UniformFourierFeatures(_FourierFeatures):
+    """model.py:309-318."""
+
+    def init_magnitude(self, std):
+        std = std / math.sqrt(3)
+        return torch.linspace(-std, std, self.num_frequencies) + EPSILON
+
+
+class _EncodedMlpModel(nn.Module):
+    """model.py:54-103, the part the flow trainer uses."""
+    encoding = None
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        self.encode = self.make_encoding(opt)
+        self.model = MLP([self.encode.output_channels] + opt.num_layers * [opt.hidden_dim] + [opt.output_channels])
+        self._axes = {}
+
+    @property
+    def encoding_dim(self):
+        return self.encode.output_channels
+
+    @property
+    def domain_dim(self):
+        return self.opt.domain_dim
+
+    @property
+    def is_progressive(self):
+        return False
+
+    def update_progress(self):
+        return
+
+    def stash_iteration(self, *args):
+        return
+
+    def linears(self):
+        return [m for m in self.model.model if isinstance(m, nn.Linear)]
+
+    def forward(self, x, *args, **kwargs):
+        raise NotImplementedError('evaluate the network on a (times, h, w) grid with sin_inn_amd.flownet.flow_fields: the pose '
+                                  'list and the encoding are never materialised')
+
+
+class RbfModel(_EncodedMlpModel):
+    """model.py:490-505."""
+
+    @staticmethod
+    def make_encoding(opt):
+        return RadialBasisEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
+
+
+class FFModel(_EncodedMlpModel):
+    """model.py:418-433."""
+
+    @staticmethod
+    def make_encoding(opt):
+        return GaussianRandomFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+
+
+class UFFModel(_EncodedMlpModel):
+    """model.py:454-469."""
+
+    @staticmethod
+    def make_encoding(opt):
+        return UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+
+
+model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel}
+
+
+def _args(net, times, ys, xs, scale):
+    lins = net.linears()
+    a = _lib.FlowNetArgs()
+    a.encoding = net.encode.kind
+    a.enc_dim, a.hidden, a.layers, a.out_dim = net.encode.output_channels, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
+    supported = (net.opt.domain_dim == 3 and len(lins) == 4 and _lib.lib().sininn_flownet_supported(C.byref(a)))
+    if not supported:
+        raise ValueError(f'flownet kernels are built for 3 -> 512 -> 256 x 3 -> 4; got {net.opt.domain_dim} -> {a.enc_dim} -> '
+                         f'{a.hidden} x {a.layers} -> {a.out_dim}')
+    for t in (times, ys, xs):
+        if not t.is_cuda:
+            raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+    a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
+    a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
+    ea, eb = net.encode.kernel_buffers()
+    a.enc_a, a.enc_b = ptr(ea), ptr(eb)
+    for l, lin in enumerate(lins):
+        assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
+        a.w[l], a.b[l] = ptr(lin.weight), ptr(lin.bias)
+    return a
+
+
+def flownet_forward(net, times, ys, xs, scale, train, saved=None):
+    """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
+    (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
+    caller-provided buffer of that shape)."""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _args(net, times, ys, xs, scale)
+    n = a.T * a.H * a.W
+    flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
+    if train:
+        nbytes = _lib.lib().sininn_flownet_saved_bytes(n)
+        if saved is None:
+            saved = torch.empty(3, nbytes // (3 * 256 * 4), 256, device=times.device, dtype=torch.float32)
+        assert saved.is_contiguous() and saved.dtype == torch.float32
+        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    else:
+        saved = None
+    a.flows = ptr(flows)
+    check(_lib.lib().sininn_flownet_forward(C.byref(a), _stream()))
+    return flows, saved
+
+
+def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None):
+    """[gW1, gb1, .., gW4, gb4] for an upstream gradient dflows (t, 4, h, w); `workspace`: optional fp32 tensor of at least
+    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise)."""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _args(net, times, ys, xs, scale)
+    n = a.T * a.H * a.W
+    if not dflows.is_cuda:
+        raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+    dflows = dflows.contiguous()
+    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
+    nbytes = _lib.lib().sininn_flownet_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, device=times.device, dtype=torch.float32)
+    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
+    a.dflows = ptr(dflows)
+    grads = []
+    for l, lin in enumerate(net.linears()):
+        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
+        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
+        grads += [gw, gb]
+    check(_lib.lib().sininn_flownet_backward(C.byref(a), _stream()))
+    return grads
+
+
+class _FlowFields(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, times, ys, xs, scale, train, *params):
+        flows, saved = flownet_forward(net, times, ys, xs, scale, train)
+        ctx.net, ctx.axes, ctx.scale, ctx.saved = net, (times, ys, xs), scale, saved
+        return flows
+
+    @staticmethod
+    def backward(ctx, dflows):
+        if ctx.saved is None:
+            raise RuntimeError('flow_fields: backward through an inference-mode forward')
+        grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved)
+        ctx.saved = None
+        return (None,) * 6 + tuple(grads)
+
+
+def grid_axes(net, times, h, w):
+    """linspace(-1, 1, h) / (w) as trainer.py:40-41 makes them: on the CPU, then moved next to `times` (bit-identical
+    coordinates); cached per size and device."""
+    key = (h, w, times.device)
+    if key not in net._axes:
+        net._axes[key] = (torch.linspace(-1, 1, h).to(times), torch.linspace(-1, 1, w).to(times))
+    return net._axes[key]
+
+
+def flow_fields(net, times, h, w, scale):
+    """FlowTrainer.forward (trainer.py:37-45): (flow12, flow21), each (t, 2, h, w), views of one (t, 4, h, w) tensor.  Under
+    torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved."""
+    if not times.is_cuda:
+        raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+    assert times.dtype == torch.float32 and times.dim() == 1
+    ys, xs = grid_axes(net, times, h, w)
+    params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
+    train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, *params)
+    return flows[:, :2], flows[:, 2:]

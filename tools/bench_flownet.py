@@ -1,0 +1,108 @@
+"""Time the flow-field network (sin_inn_amd.flownet): forward (inference mode) and forward + backward (training mode), with
+device events, after a warm-up, over a window of at least --seconds; one JSON line.
+
+    python tools/bench_flownet.py --net RBF --frames 1 --height 436 --width 1024 [--baseline]
+
+FLOP counts come from the shapes (2 N (512*256 + 2*256*256 + 256*4) forward; backward adds the data gradients of layers 2-4 and
+the weight gradients of all four); `mfma_peak_share` is those executed FLOPs over the event time against the 157.3 TFLOP/s f32
+matrix peak of an MI355X -- the share of the whole call, not of one kernel.  --baseline times the same module composed from
+torch's own GPU ops (tools/fit_flow.composed_flow_fields) in the same process, alternating windows with the fused path.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'tools')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+PEAK_F32_MFMA = 157.3e12
+
+
+def flops(n):
+    fwd = 2 * n * (512 * 256 + 2 * 256 * 256 + 256 * 4)
+    dgrad = 2 * n * (2 * 256 * 256 + 256 * 4)
+    return fwd, fwd + dgrad + fwd
+
+
+def window(fn, seconds, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times, total = [], 0.0
+    while total < seconds * 1e3:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(5):
+            fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) / 5)
+        total += times[-1] * 5
+    times.sort()
+    return dict(median_ms=times[len(times) // 2], min_ms=times[0], max_ms=times[-1], samples=len(times))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF'])
+    ap.add_argument('--frames', type=int, default=1)
+    ap.add_argument('--height', type=int, default=436)
+    ap.add_argument('--width', type=int, default=1024)
+    ap.add_argument('--seconds', type=float, default=1.0)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--rounds', type=int, default=2, help='alternations of the fused and the baseline windows')
+    ap.add_argument('--baseline', action='store_true')
+    a = ap.parse_args()
+    from sin_inn_amd import _lib, flownet
+    from fit_flow import composed_flow_fields
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    net = flownet.model_dict[a.net](flownet.ModelParams()).to(dev)
+    times = torch.linspace(0, 1, a.frames, device=dev) if a.frames > 1 else torch.zeros(1, device=dev)
+    n = a.frames * a.height * a.width
+    up = torch.randn(a.frames, 4, a.height, a.width, device=dev)
+    params = list(net.parameters())
+
+    def paths(fields):
+        def fwd():
+            with torch.no_grad():
+                fields(net, times, a.height, a.width, 2.0)
+
+        def step():
+            for p in params:
+                p.grad = None
+            f12, f21 = fields(net, times, a.height, a.width, 2.0)
+            torch.autograd.backward([f12, f21], [up[:, :2], up[:, 2:]])
+        return fwd, step
+
+    todo = {'fused': paths(flownet.flow_fields)}
+    if a.baseline:
+        todo['torch'] = paths(composed_flow_fields)
+    res = {k: {'forward': [], 'step': []} for k in todo}
+    for _ in range(a.rounds):
+        for k, (fwd, step) in todo.items():
+            res[k]['forward'].append(window(fwd, a.seconds, a.warmup))
+            res[k]['step'].append(window(step, a.seconds, a.warmup))
+    f_fwd, f_step = flops(n)
+    out = dict(net=a.net, frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
+               saved_bytes=_lib.lib().sininn_flownet_saved_bytes(n), workspace_bytes=_lib.lib().sininn_flownet_workspace_bytes(n))
+    for k in res:
+        for what, fl in (('forward', f_fwd), ('step', f_step)):
+            meds = [w['median_ms'] for w in res[k][what]]
+            best = min(meds)
+            out[f'{k}_{what}_ms'] = best
+            out[f'{k}_{what}_ms_windows'] = [round(m, 4) for m in meds]
+            out[f'{k}_{what}_mfma_peak_share'] = round(fl / (best * 1e-3) / PEAK_F32_MFMA, 4)
+    if a.baseline:
+        out['speedup_forward'] = round(out['torch_forward_ms'] / out['fused_forward_ms'], 3)
+        out['speedup_step'] = round(out['torch_step_ms'] / out['fused_step_ms'], 3)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,110 @@
+"""Fit a flow-field network to one synthetic frame pair: flow_fields -> warp / softmax splatting / L1 / census / smoothness
+-> backward -> FusedAdam, the training step of video-interpolation/trainer.py:47-87 on this project's kernels.
+
+    python tools/fit_flow.py --net RBF --height 64 --width 96 --steps 60
+
+The pair is seeded and analytic: frame1 is a smooth texture, frame2 the same texture displaced by a known smooth flow.
+`--composed` evaluates the network with torch's own ops (nn.functional.linear and elementwise ops) instead of the fused
+kernels; everything after the network is the same, which is what tests/test_gpu_flownet.py compares.
+"""
+import argparse
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def texture(x, y, gen_seed):
+    """3-channel sum of 12 low-frequency plane waves per channel, values in about [0, 1]; x, y in pixels (any shape)"""
+    g = torch.Generator().manual_seed(gen_seed)
+    k = (torch.rand(3, 12, 2, generator=g) - 0.5) * 0.6          # radians per pixel
+    ph = torch.rand(3, 12, generator=g) * 2 * math.pi
+    k, ph = k.to(x), ph.to(x)
+    arg = k[:, :, 0, None, None] * x[None, None] + k[:, :, 1, None, None] * y[None, None] + ph[:, :, None, None]
+    return 0.5 + torch.sin(arg).mean(1) * 1.2
+
+
+def make_pair(h, w, seed, device):
+    """frame1, frame2 (1, 3, h, w) and the flow12 (1, 2, h, w) that produced frame2(x) = frame1(x - flow)"""
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing='ij')
+    u = 1.5 * torch.sin(yy / h * math.pi) + 0.5
+    v = 1.0 * torch.cos(xx / w * math.pi)
+    f1 = texture(xx, yy, seed)
+    f2 = texture(xx - u, yy - v, seed)
+    return f1[None].to(device).contiguous(), f2[None].to(device).contiguous(), torch.stack((u, v))[None].to(device)
+
+
+def composed_flow_fields(net, times, h, w, scale):
+    """FlowTrainer.forward (trainer.py:37-45) with torch's own GPU ops on the port's buffers and parameters: what a user of the
+    reference runs, and the baseline of tools/bench_flownet.py"""
+    ys = torch.linspace(-1, 1, h).to(times)
+    xs = torch.linspace(-1, 1, w).to(times)
+    gt, gh, gw = torch.meshgrid(times, ys, xs, indexing='ij')
+    x = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
+    enc = net.encode
+    if hasattr(enc, 'centres'):
+        x = (x[:, None, :] - enc.centres[None, :, :]).pow(2).sum(2)
+        x = torch.exp(-(x * enc.sigma[None, :] ** 2))
+    else:
+        x = torch.matmul(x * 2 * math.pi, enc.frequencies)
+        x = torch.stack((torch.sin(x), torch.cos(x)), dim=2).view(x.shape[0], -1)
+    flows = net.model.model(x).view(times.numel(), h, w, 4).permute(0, 3, 1, 2) * scale
+    return flows[:, :2], flows[:, 2:]
+
+
+def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None):
+    """returns the list of per-step losses (floats)"""
+    from sin_inn_amd import FusedAdam, flowloss as FL, flownet
+    from sin_inn_amd.functional import flow_warp_l1
+    torch.manual_seed(seed)
+    net = flownet.model_dict[net_name](flownet.ModelParams()).to(device)
+    opt = FusedAdam(net.parameters(), lr=lr)
+    frame1, frame2, _ = make_pair(h, w, seed + 1, device)
+    times = torch.zeros(1, device=device)
+    l1, census, smooth = FL.L1Loss(1.0), FL.CensusLoss(0.1, max_distance=3), FL.BilateralSmooth(0.1, 'gauss', 150, 1)
+    fields = composed_flow_fields if composed else flownet.flow_fields
+    losses = []
+    for step in range(steps):
+        opt.zero_grad()
+        flow12, flow21 = fields(net, times, h, w, 1.0)
+        flow12, flow21 = flow12.contiguous(), flow21.contiguous()
+        mask1 = FL.occlusion_wang(flow12, flow21, 0.5)
+        mask2 = FL.occlusion_wang(flow21, flow12, 0.5)
+        _, metric = flow_warp_l1(frame1, flow21, frame2)
+        softmax1 = FL.FunctionSoftsplat(frame2, flow21, -20 * metric, strType='softmax')
+        mask1 = mask1 * (softmax1 != 0)
+        _, metric = flow_warp_l1(frame2, flow12, frame1)
+        softmax2 = FL.FunctionSoftsplat(frame1, flow12, -20 * metric, strType='softmax')
+        mask2 = mask2 * (softmax2 != 0)
+        loss = (l1(softmax1, frame1, mask1) + l1(softmax2, frame2, mask2)
+                + census(softmax1, frame1, mask1) + census(softmax2, frame2, mask2)
+                + smooth(frame1, flow12) + smooth(frame2, flow21))
+        loss.backward()
+        opt.step()
+        losses.append(float(loss))
+        if log:
+            log(f'step {step:3d}  loss {losses[-1]:.6f}')
+    return losses
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF'])
+    ap.add_argument('--height', type=int, default=64)
+    ap.add_argument('--width', type=int, default=96)
+    ap.add_argument('--steps', type=int, default=60)
+    ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--composed', action='store_true')
+    a = ap.parse_args()
+    losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print)
+    print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
+
+
+if __name__ == '__main__':
+    main()
