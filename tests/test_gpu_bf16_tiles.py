@@ -91,54 +91,8 @@ def nhwc_cpu(t, b, h, w, c0=0, c=None):
     return t[:, c0:c0 + c].cpu().reshape(b, h, w, c)
 
 
-# ---- float64 references, one image and one tap at a time ----------------------------------------------------------------------
-def ref_conv(x, w, b=None):
-    """x [B,H,W,C] (any dtype), w [N,C,k,k] -> float64 [B,H,W,N]; zero padding k // 2"""
-    B, H, W, Cn = x.shape
-    n, _, k, _ = w.shape
-    p = k // 2
-    w = w.double()
-    out = torch.zeros(B, H, W, n, dtype=torch.float64)
-    for i in range(B):
-        xp = F.pad(x[i].double(), (0, 0, p, p, p, p))
-        acc = out[i].view(H * W, n)
-        for ky in range(k):
-            for kx in range(k):
-                acc += xp[ky:ky + H, kx:kx + W].reshape(H * W, Cn) @ w[:, :, ky, kx].t()
-    if b is not None:
-        out += b.double()
-    return out
-
-
-def ref_dgrad(g, w):
-    """data gradient of ref_conv: g [B,H,W,N], w [N,C,k,k] -> float64 [B,H,W,C]"""
-    B, H, W, n = g.shape
-    _, Cn, k, _ = w.shape
-    p = k // 2
-    w = w.double()
-    out = torch.zeros(B, H, W, Cn, dtype=torch.float64)
-    for i in range(B):
-        gp = F.pad(g[i].double(), (0, 0, p, p, p, p))
-        acc = out[i].view(H * W, Cn)
-        for ky in range(k):
-            for kx in range(k):
-                acc += gp[2 * p - ky:2 * p - ky + H, 2 * p - kx:2 * p - kx + W].reshape(H * W, n) @ w[:, :, ky, kx]
-    return out
-
-
-def ref_wgrad(x, g, k):
-    """weight gradient of ref_conv: x [B,H,W,C], g [B,H,W,N] -> float64 [N,C,k,k]"""
-    B, H, W, Cn = x.shape
-    n = g.shape[3]
-    p = k // 2
-    gw = torch.zeros(n, Cn, k, k, dtype=torch.float64)
-    for i in range(B):
-        xp = F.pad(x[i].double(), (0, 0, p, p, p, p))
-        gi = g[i].double().reshape(H * W, n).t()
-        for ky in range(k):
-            for kx in range(k):
-                gw[:, :, ky, kx] += gi @ xp[ky:ky + H, kx:kx + W].reshape(H * W, Cn)
-    return gw
+# ---- float64 references, one image and one tap at a time: tests/float64_refs.py --------------------------------------------------
+from float64_refs import ref_conv, ref_dgrad, ref_wgrad  # noqa: E402
 
 
 def args(**kw):
