@@ -660,7 +660,15 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
  *             hidden gradients, two transposed weights, per-block partial sums); sums over points are added in a fixed order
  *             (no floating-point atomics): two calls on the same inputs are bitwise equal.  The ReLU gates the forward took are
  *             saved > 0.
- * Borrowed pointers, 16-byte aligned (axis vectors and biases: 4), the caller's stream, non-zero return + sininn_last_error.
+ * Progressive networks (model.py:526-625 PRBFModel / PFFModel / PUFFModel under the per-feature mask of a controller,
+ *   progressive_controller.py:14-158): progressive = 1, enc_dim = 515, w[0] is [256][515]; the input of layer 1 is
+ *   cat((t, y, x), enc) * mask with mask a DEVICE vector of 515 floats (feature order t, y, x, e0 .. e511).  k_active, from the host, is a
+ *   number of leading features after which every mask entry is zero (515 is always valid): layer 1 and its weight gradient skip the
+ *   features beyond it, which is exact, so any valid k_active gives bitwise the same flows and gradients.  gw[0] is [256][515],
+ *   column k = mask[k] * sum_p dh1[p][j] feature_k[p], an exact 0 where mask[k] is 0.  The forward call folds the mask into a packed
+ *   copy of w[0] and needs a workspace of sininn_flownet_forward_workspace_bytes(args) bytes for it (0 if not progressive); the
+ *   backward call needs no more than sininn_flownet_workspace_bytes(N), and `saved` has the same size.
+ * Borrowed pointers, 16-byte aligned (axis vectors, biases and the mask: 4), the caller's stream, non-zero return + sininn_last_error.
  * sininn_flownet_supported: 1 if the sizes are the ones the kernels are built for, else 0 (callers raise, there is no second path).
  * ---------------------------------------------------------------------------------------------- */
 #define SININN_FLOWNET_RBF 0     /* enc_a = centres [512][3], enc_b = sigma [512]                                  */
@@ -668,22 +676,26 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
 typedef struct sininn_flownet_args {
   size_t struct_bytes;                    /* must be sizeof(sininn_flownet_args)                                          */
   int encoding;                           /* SININN_FLOWNET_*                                                             */
-  int enc_dim, hidden, layers, out_dim;   /* 512, 256, 3, 4                                                               */
+  int enc_dim, hidden, layers, out_dim;   /* 512 (progressive: 515), 256, 3, 4                                            */
   int T, H, W;                            /* N = T H W points, at most 2^22                                               */
   float scale;
   const float *times, *ys, *xs;           /* [T], [H], [W]                                                                */
   const float *enc_a, *enc_b;
-  const float* w[4];                      /* [256][512], [256][256], [256][256], [4][256]                                 */
+  const float* w[4];                      /* [256][512] (progressive: [256][515]), [256][256], [256][256], [4][256]       */
   const float* b[4];
   float* flows;                           /* forward: out [T][4][H][W]                                                    */
   float* saved; size_t saved_bytes;       /* forward: out or NULL; backward: in                                           */
   const float* dflows;                    /* backward: in [T][4][H][W]                                                    */
   float* gw[4]; float* gb[4];             /* backward: out                                                                */
-  void* workspace; size_t workspace_bytes;
+  void* workspace; size_t workspace_bytes;/* backward; progressive forward                                                */
+  int progressive;                        /* 0, or 1: layer 1 reads cat((t, y, x), enc) * mask                            */
+  int k_active;                           /* progressive: 0 .. 515, every mask entry from this index on is zero           */
+  const float* mask;                      /* progressive: device [515]                                                    */
 } sininn_flownet_args;
 int sininn_flownet_supported(const sininn_flownet_args* args);
 size_t sininn_flownet_saved_bytes(int64_t n_points);
 size_t sininn_flownet_workspace_bytes(int64_t n_points);
+size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_forward(const sininn_flownet_args* args, void* stream);
 int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
 

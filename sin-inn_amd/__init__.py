@@ -11,6 +11,7 @@ from . import irn                                                             # 
 from . import functional                                                     # noqa: F401
 from . import flowloss                                                       # noqa: F401
 from . import flownet                                                        # noqa: F401
+from . import progressive                                                    # noqa: F401
 
 __all__ = ['GLOWCouplingBlock', 'IRevNetDownsampling', 'PermuteRandom', 'InputNode', 'Node', 'OutputNode',
            'ReversibleGraphNet', 'FusedAdam', 'functional', 'ops']

@@ -116,7 +116,8 @@ class FlowNetArgs(C.Structure):
                 ('times', c_f), ('ys', c_f), ('xs', c_f), ('enc_a', c_f), ('enc_b', c_f),
                 ('w', c_f * 4), ('b', c_f * 4), ('flows', c_f), ('saved', c_f), ('saved_bytes', C.c_size_t),
                 ('dflows', c_f), ('gw', c_f * 4), ('gb', c_f * 4),
-                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
+                ('progressive', C.c_int), ('k_active', C.c_int), ('mask', c_f)]
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
@@ -247,6 +248,7 @@ _SIGS = {
     'sininn_flownet_supported': (C.c_int, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_flownet_workspace_bytes': (C.c_size_t, [C.c_int64]),
+    'sininn_flownet_forward_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_forward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
     'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,

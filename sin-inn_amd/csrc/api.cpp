@@ -120,6 +120,7 @@ void profile_begin(int h, unsigned long long* stamps, int max_launches);
 int profile_end(int* count, float* total_ms);
 size_t flownet_saved_bytes(int64_t n);
 size_t flownet_workspace_bytes(int64_t n);
+size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a);
 int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
@@ -559,11 +560,13 @@ int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 
 int sininn_flownet_supported(const sininn_flownet_args* a) {
   return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
-         (a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER) && a->enc_dim == 512 && a->hidden == 256 &&
+         (a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER) && (a->progressive == 0 || a->progressive == 1) &&
+         a->enc_dim == (a->progressive ? 515 : 512) && a->hidden == 256 &&
          a->layers == 3 && a->out_dim == 4;
 }
 size_t sininn_flownet_saved_bytes(int64_t n_points) { return flownet_saved_bytes(n_points); }
 size_t sininn_flownet_workspace_bytes(int64_t n_points) { return flownet_workspace_bytes(n_points); }
+size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args) { return flownet_forward_workspace_bytes(args); }
 int sininn_flownet_forward(const sininn_flownet_args* args, void* stream) { return flownet_forward_launch(args, ST(stream)); }
 int sininn_flownet_backward(const sininn_flownet_args* args, void* stream) { return flownet_backward_launch(args, ST(stream)); }
 

@@ -24,6 +24,16 @@
 //           flownet_reduce_kernel adds them in a fixed order: no floating-point atomics, two runs are bitwise equal.
 // Rows of the last tile beyond N are computed on a clamped point in the forward pass and carry dout = 0 in the backward pass, so
 // saved / workspace rows are always written before they are read and contribute exact zeros to every sum.
+//
+// progressive (PRBF / PFF / PUFF of model.py:526-625 under a controller's mask, progressive_controller.py:14-158): the input of layer 1
+//           is cat((t, y, x), enc) * mask, 515 features, W1 [256][515].  flownet_pack_kernel folds the mask into the weights once per
+//           call ((e m) w = e (m w)): W1p = W1[:, 3:] * mask[3:] as an aligned [256][512] matrix and the three coordinate columns as
+//           [256][4] (padded with a zero), so the K loop and encode4 are the ones above; the coordinates are one more K group of four
+//           on the MFMA (16 of 2064 layer-1 MFMAs per wave and tile).  The K loop stops after the last open feature (k_active, from
+//           the host), rounded up to 16: the skipped terms are e * 0, so skipping is exact.  The chain kernel does not see layer 1's
+//           input and is shared.  flownet_wgrad_kernel<.., true, true> adds the three coordinate-weighted column sums of the dh1 tile
+//           next to gb1 and is launched on the open 128-column tiles only; flownet_reduce_prog_kernel scatters the sums into
+//           nn.Linear's [256][515] layout, times the mask, exact zeros where the mask is zero.
 #include "common.h"
 
 namespace sininn {
@@ -42,6 +52,11 @@ constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunk
 constexpr int FN_CHAIN_MAX_BLOCKS = 512;
 constexpr size_t FN_LDS = (size_t)(FN_P * FN_HS + FN_P * FN_OUT) * sizeof(float);
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
+constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features
+constexpr int FN_PENC = FN_ENC + FN_DOM;
+constexpr int FN_CS = 4;            // floats per row of the packed coordinate columns / of the coordinate tile in LDS
+constexpr size_t FN_WG_LDS_PROG = FN_WG_LDS + (size_t)(FN_P * FN_CS) * sizeof(float);
+constexpr size_t FN_PACK_FLOATS = (size_t)FN_HID * (FN_ENC + FN_CS);
 
 struct FlowNetDev {
   int T, H, W, N, ntiles;
@@ -56,6 +71,8 @@ struct FlowNetDev {
   float* dh;               // [3][ntiles * 64][256]
   const float* wt;         // W2^T, W3^T
   float* part;             // partial sums
+  const float* wc;         // progressive: coordinate columns of W1 times their mask, [256][4]
+  int ksteps;              // progressive: 16-feature steps of the layer-1 K loop
 };
 
 struct Coord { float t, y, x; };
@@ -155,7 +172,8 @@ __device__ __forceinline__ void copy_tile_out(const float* hs, float* dst, int t
   }
 }
 
-template <int KIND>
+// PROG: q.w[0] is the packed W1p [256][512], q.wc the coordinate columns, q.ksteps the length of the K loop
+template <int KIND, bool PROG = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;
@@ -173,9 +191,22 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
 
     f32x4 acc[4][4];
     zero_acc(acc);
+    if constexpr (PROG) {
+      // ---- the coordinates: one K group, k = kq: t, y, x, 0 ----
+      float a[4], b[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) a[m] = kq == 0 ? pc[m].t : kq == 1 ? pc[m].y : kq == 2 ? pc[m].x : 0.f;
+#pragma unroll
+      for (int n = 0; n < 4; ++n) b[n] = q.wc[(cw + 16 * n + li) * FN_CS + kq];
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
+    }
     // ---- layer 1: the A fragment is generated, never stored ----
+    const int ksteps = PROG ? q.ksteps : FN_ENC / 16;
 #pragma unroll 1
-    for (int s = 0; s < FN_ENC / 16; ++s) {
+    for (int s = 0; s < ksteps; ++s) {
       f32x4 bf[4], af[4];
 #pragma unroll
       for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const f32x4*>(q.w[0] + (size_t)(cw + 16 * n + li) * FN_ENC + 16 * s + 4 * kq);
@@ -231,6 +262,26 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_transpose_kernel(const float*
   float* out = wt + (size_t)blockIdx.y * FN_HID * FN_HID;
   const int j = blockIdx.x, k = threadIdx.x;
   out[k * FN_HID + j] = in[j * FN_HID + k];
+}
+
+// progressive: w1p[j][k] = w1[j][3 + k] mask[3 + k] (k < 512), wc[j][c] = w1[j][c] mask[c] (c < 3), wc[j][3] = 0; block = row j.
+// A closed feature gets an exact zero whatever the weight holds.
+__global__ __launch_bounds__(FN_NTHR) void flownet_pack_kernel(const float* w1, const float* mask, float* w1p, float* wc) {
+  const int j = blockIdx.x, tid = threadIdx.x;
+  const float* row = w1 + (size_t)j * FN_PENC;
+#pragma unroll
+  for (int k = tid; k < FN_ENC; k += FN_NTHR) {
+    const float m = mask[FN_DOM + k];
+    w1p[(size_t)j * FN_ENC + k] = m == 0.f ? 0.f : row[FN_DOM + k] * m;
+  }
+  if (tid < FN_CS) {
+    float v = 0.f;
+    if (tid < FN_DOM) {
+      const float m = mask[tid];
+      v = m == 0.f ? 0.f : row[tid] * m;
+    }
+    wc[j * FN_CS + tid] = v;
+  }
 }
 
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDev q) {
@@ -320,14 +371,18 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
 }
 
 // part[chunk][j][k] = sum over the chunk's point tiles of dh[p][j] in[p][k]  (+ [chunk][256 * KF + j] = sum_p dh[p][j]);
-// grid = (2 * KF / 128 output tiles, chunks); ENC: in = the encoding (KF = 512), else a saved hidden layer (KF = 256)
-template <int KIND, bool ENC>
+// grid = (2 * KF / 128 output tiles, chunks); ENC: in = the encoding (KF = 512), else a saved hidden layer (KF = 256).
+// PROG (with ENC): + [chunk][256 * KF + 256 + 4 j + c] = sum_p dh[p][j] coordinate_c[p]; the grid may cover the leading k tiles only
+template <int KIND, bool ENC, bool PROG = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q, const float* dh, const float* in) {
+  static_assert(ENC || !PROG, "the progressive weight gradient is layer 1's");
   constexpr int KF = ENC ? FN_ENC : FN_HID;
+  constexpr int PSTRIDE = FN_HID * KF + FN_HID + (PROG ? FN_HID * FN_CS : 0);
   constexpr int NU = FN_P * FN_WT / 4 / FN_NTHR;       // 16-byte units per thread and operand tile
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const as = fn_smem;                           // [64][FN_WS]: dh tile
   float* const bs = fn_smem + FN_P * FN_WS;            // [64][FN_WS]: input tile
+  float* const cs = fn_smem + 2 * FN_P * FN_WS;        // PROG: [64][4]: coordinates of the tile's points
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
@@ -338,6 +393,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
   f32x4 acc[4][4];
   zero_acc(acc);
   float bsum = 0.f;
+  float csum[FN_DOM] = {0.f, 0.f, 0.f};
   f32x4 va[NU], vb[NU];
   auto fetch = [&](int tile) {
 #pragma unroll
@@ -360,12 +416,34 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
       if constexpr (ENC) vb[u] = encode4<KIND>(q, point_coord(q, tile * FN_P + row), k0 + c4);
       *reinterpret_cast<f32x4*>(bs + row * FN_WS + c4) = vb[u];
     }
+    if constexpr (PROG) {
+      if (k0 == 0 && tid < FN_P) {
+        const Coord c = point_coord(q, tile * FN_P + tid);
+        *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
+      }
+    }
     __syncthreads();
     if (tile + nchunks < q.ntiles) fetch(tile + nchunks);
     if (k0 == 0 && tid < FN_WT) {
       float s = 0.f;
+      if constexpr (PROG) {
+        float st = 0.f, sy = 0.f, sx = 0.f;
 #pragma unroll 8
-      for (int p = 0; p < FN_P; ++p) s += as[p * FN_WS + tid];
+        for (int p = 0; p < FN_P; ++p) {
+          const float d = as[p * FN_WS + tid];
+          const f32x4 c = *reinterpret_cast<const f32x4*>(cs + p * FN_CS);
+          s += d;
+          st = fmaf(d, c[0], st);
+          sy = fmaf(d, c[1], sy);
+          sx = fmaf(d, c[2], sx);
+        }
+        csum[0] += st;
+        csum[1] += sy;
+        csum[2] += sx;
+      } else {
+#pragma unroll 8
+        for (int p = 0; p < FN_P; ++p) s += as[p * FN_WS + tid];
+      }
       bsum += s;
     }
 #pragma unroll 2
@@ -381,7 +459,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
         for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
     }
   }
-  float* const out = q.part + (size_t)chunk * (FN_HID * KF + FN_HID);
+  float* const out = q.part + (size_t)chunk * PSTRIDE;
 #pragma unroll
   for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -389,6 +467,10 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
 #pragma unroll
       for (int r = 0; r < 4; ++r) out[(size_t)(j0 + jw + 16 * m + 4 * kq + r) * KF + k0 + kw + 16 * n + li] = acc[m][n][r];
   if (k0 == 0 && tid < FN_WT) out[FN_HID * KF + j0 + tid] = bsum;
+  if constexpr (PROG) {
+    if (k0 == 0 && tid < FN_WT)
+      *reinterpret_cast<f32x4*>(out + FN_HID * KF + FN_HID + (j0 + tid) * FN_CS) = (f32x4){csum[0], csum[1], csum[2], 0.f};
+  }
 }
 
 // gw[i] = sum_c part[c][i] (i < nw), gb[i - nw] = sum_c part[c][i] (nw <= i < nw + nb): chunks in index order, always
@@ -402,6 +484,30 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* pa
   else gb[i - nw] = s;
 }
 
+// progressive layer 1: gw [256][515] = mask[k] * sum_c part[c][..] in chunk order (k < 3: the coordinate sums, else encoded column
+// k - 3), an exact zero where the mask is zero or the column lies beyond the `kcols` encoded columns that were computed; gb as above
+__global__ __launch_bounds__(FN_NTHR) void flownet_reduce_prog_kernel(const float* part, int nparts, const float* mask, int kcols, float* gw,
+                                                                      float* gb) {
+  constexpr int NW = FN_HID * FN_PENC;
+  constexpr size_t STRIDE = (size_t)FN_HID * FN_ENC + FN_HID + FN_HID * FN_CS;
+  const int i = blockIdx.x * FN_NTHR + threadIdx.x;
+  if (i >= NW + FN_HID) return;
+  size_t src;
+  float m = 1.f;
+  if (i < NW) {
+    const int j = i / FN_PENC, k = i - j * FN_PENC;
+    m = mask[k];
+    if (m == 0.f || k - FN_DOM >= kcols) { gw[i] = 0.f; return; }
+    src = k < FN_DOM ? (size_t)FN_HID * FN_ENC + FN_HID + j * FN_CS + k : (size_t)j * FN_ENC + (k - FN_DOM);
+  } else {
+    src = (size_t)FN_HID * FN_ENC + (i - NW);
+  }
+  float s = 0.f;
+  for (int c = 0; c < nparts; ++c) s += part[c * STRIDE + src];
+  if (i < NW) gw[i] = s * m;
+  else gb[i - NW] = s;
+}
+
 int wgrad_chunks(int ntiles, int kf) {
   const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 for layer 1
   return ntiles < want ? ntiles : want;
@@ -411,7 +517,7 @@ int chain_blocks(int ntiles) { return ntiles < FN_CHAIN_MAX_BLOCKS ? ntiles : FN
 
 size_t part_floats(int ntiles) {
   size_t a = (size_t)wgrad_chunks(ntiles, FN_HID) * (FN_HID * FN_HID + FN_HID);
-  const size_t b = (size_t)wgrad_chunks(ntiles, FN_ENC) * (FN_HID * FN_ENC + FN_HID);
+  const size_t b = (size_t)wgrad_chunks(ntiles, FN_ENC) * (FN_HID * FN_ENC + FN_HID + FN_HID * FN_CS);   // progressive layer 1
   const size_t c = (size_t)chain_blocks(ntiles) * (FN_OUT * FN_HID + FN_OUT);
   a = a > b ? a : b;
   return a > c ? a : c;
@@ -430,8 +536,13 @@ int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
   SININN_CHECK(a != nullptr, "%s: null args", who);
   SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
                a->struct_bytes, sizeof(sininn_flownet_args));
-  SININN_CHECK(sininn_flownet_supported(a), "%s: unsupported network (encoding %d, %d -> %d x %d -> %d; built for RBF / Fourier, 512 -> 256 x 3 -> 4)",
-               who, a->encoding, a->enc_dim, a->hidden, a->layers, a->out_dim);
+  SININN_CHECK(sininn_flownet_supported(a),
+               "%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for RBF / Fourier, 512 (progressive: 515) -> 256 x 3 -> 4)",
+               who, a->encoding, a->enc_dim, a->hidden, a->layers, a->out_dim, a->progressive);
+  if (a->progressive) {
+    SININN_CHECK(a->mask != nullptr, "%s: progressive network without a mask", who);
+    SININN_CHECK(a->k_active >= 0 && a->k_active <= FN_PENC, "%s: k_active %d (0 .. %d)", who, a->k_active, FN_PENC);
+  }
   SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
                who, a->T, a->H, a->W);
   SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding != SININN_FLOWNET_RBF || a->enc_b), "%s: null axis / encoding pointer", who);
@@ -449,10 +560,18 @@ int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
   q.times = a->times; q.ys = a->ys; q.xs = a->xs;
   q.enc_a = a->enc_a; q.enc_b = a->enc_b;
   q.flows = nullptr; q.saved = nullptr; q.dflows = nullptr; q.dh = nullptr; q.wt = nullptr; q.part = nullptr;
+  q.wc = nullptr; q.ksteps = 0;
   return 0;
 }
 
+// encoded features in front of the last open one
+int open_encoded(const sininn_flownet_args* a) { return a->k_active > FN_DOM ? a->k_active - FN_DOM : 0; }
+
 }  // namespace
+
+size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a) {
+  return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) && a->progressive ? FN_PACK_FLOATS * sizeof(float) : 0;
+}
 
 size_t flownet_saved_bytes(int64_t n) {
   if (n <= 0) return 0;
@@ -477,6 +596,20 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
     q.saved = a->saved;
   }
   auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_fwd_kernel<SININN_FLOWNET_RBF> : flownet_fwd_kernel<SININN_FLOWNET_FOURIER>;
+  if (a->progressive) {
+    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
+                 "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", flownet_forward_workspace_bytes(a),
+                 a->workspace ? a->workspace_bytes : (size_t)0);
+    SININN_CHECK(aligned16(a->workspace), "flownet_forward: workspace must be 16-byte aligned");
+    float* const w1p = static_cast<float*>(a->workspace);
+    float* const wc = w1p + (size_t)FN_HID * FN_ENC;
+    hipLaunchKernelGGL(flownet_pack_kernel, dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
+    SININN_LAUNCH_CHECK("flownet_pack");
+    q.w[0] = w1p;
+    q.wc = wc;
+    q.ksteps = (open_encoded(a) + 15) / 16;
+    k = a->encoding == SININN_FLOWNET_RBF ? flownet_fwd_kernel<SININN_FLOWNET_RBF, true> : flownet_fwd_kernel<SININN_FLOWNET_FOURIER, true>;
+  }
   if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
   const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
   hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS, st, q);
@@ -524,7 +657,19 @@ int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) {
     reduce(nc, FN_HID * FN_HID, FN_HID, a->gw[l], a->gb[l]);
     SININN_LAUNCH_CHECK("flownet_reduce");
   }
-  {
+  if (a->progressive) {
+    // the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate columns)
+    auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true, true> : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true, true>;
+    if (raise_lds(k, FN_WG_LDS_PROG, "flownet_wgrad")) return 1;
+    const int nc = wgrad_chunks(q.ntiles, FN_ENC);         // not a function of k_active: the order of every sum stays the same
+    const int oe = open_encoded(a);
+    const int ktiles = oe > 0 ? (oe + FN_WT - 1) / FN_WT : 1;
+    hipLaunchKernelGGL(k, dim3(2 * ktiles, nc), dim3(FN_NTHR), FN_WG_LDS_PROG, st, q, (const float*)q.dh, (const float*)nullptr);
+    SININN_LAUNCH_CHECK("flownet_wgrad");
+    hipLaunchKernelGGL(flownet_reduce_prog_kernel, dim3((FN_HID * FN_PENC + FN_HID + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st,
+                       (const float*)q.part, nc, a->mask, ktiles * FN_WT, a->gw[0], a->gb[0]);
+    SININN_LAUNCH_CHECK("flownet_reduce");
+  } else {
     auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true> : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true>;
     if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
     const int nc = wgrad_chunks(q.ntiles, FN_ENC);

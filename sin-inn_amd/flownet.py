@@ -2,6 +2,7 @@
 backward in libsininn.so (csrc/flownet.hip).
 
     ModelParams / RbfModel / FFModel / UFFModel / model_dict   video-interpolation/model.py:11-28, 490-505, 418-433, 454-469, 681
+    ProgressiveModel / PRBFModel / PFFModel / PUFFModel        video-interpolation/model.py:526-598, 621-625 (progressive_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
 
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
@@ -11,9 +12,18 @@ loads.  The encodings are buffers: no gradient flows below layer 1.  The kernels
 (3 -> 512 -> 256 x 3 -> 4); any other size raises, there is no second implementation behind this module, and calling a model
 directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512 encoding never exist here.
 
-Out of scope: `siren`, `RFF` / `PRFF` (learnable frequencies), `RBFG`, the progressive models and their controllers, `PE`
-(the reference's PositionalEncoding.forward raises on any input, model.py:332), LAMB (the reference trains with apex
-FusedLAMB; these modules expose ordinary nn.Parameters and `sin_inn_amd.FusedAdam` drives them), Sintel / .flo IO.
+The progressive models feed `cat((t, y, x), encode(x)) * mask` to layer 1 (515 features, first weight [256][515]); the mask is
+a global vector of 515 values that a controller of `sin_inn_amd.progressive` opens block by block (main.py:136-143).
+`flow_fields` takes a bare progressive model (all-ones mask: the reference applies none) or a controller, and an
+`override_mask` that beats the controller's own (progressive_controller.py:45-53).  The controller's mask comes with the
+number of leading features it has opened so far, and the kernels skip the rest of layer 1; an `override_mask` given as a device
+tensor is not inspected on the host and runs over all 515 features.  Both give bitwise the same result.
+
+Out of scope: `siren`, `RFF` / `PRFF` (learnable frequencies), `RBFG` / `PRBFG`, `PE` / `PPE` (the reference's
+PositionalEncoding.forward raises on any input, model.py:332), `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
+spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
+grid; `FixedSpatialController`; `AdaptiveController`), LAMB (the reference trains with apex FusedLAMB; these modules expose ordinary
+nn.Parameters and `sin_inn_amd.FusedAdam` drives them), Sintel / .flo IO.
 """
 import ctypes as C
 import math
@@ -182,18 +192,80 @@ class UFFModel(_EncodedMlpModel):
         return UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
 
 
+class ProgressiveModel(_EncodedMlpModel):
+    """model.py:526-576: layer 1 reads cat((x, encode(x))) times a mask; `encode` is drawn first, then the MLP on 515 inputs."""
+
+    def __init__(self, opt):
+        nn.Module.__init__(self)
+        self.opt = opt
+        self.encode = self.get_encoding_layer(opt)
+        self.model = MLP([self.encoding_dim] + opt.num_layers * [opt.hidden_dim] + [opt.output_channels])
+        self._axes = {}
+        self._ones = {}
+
+    @property
+    def encoding_dim(self):
+        return self.encode.output_channels + self.domain_dim
+
+    @property
+    def is_progressive(self):
+        return True
+
+    def ones_mask(self, device):
+        """the mask of a network evaluated without a controller, cached per device"""
+        if device not in self._ones:
+            self._ones[device] = torch.ones(self.encoding_dim, device=device)
+        return self._ones[device]
+
+
+class PRBFModel(ProgressiveModel):
+    """model.py:621-625."""
+
+    @staticmethod
+    def get_encoding_layer(opt):
+        return RadialBasisEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
+
+
+class PFFModel(ProgressiveModel):
+    """model.py:579-583."""
+
+    @staticmethod
+    def get_encoding_layer(opt):
+        return GaussianRandomFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+
+
+class PUFFModel(ProgressiveModel):
+    """model.py:593-597."""
+
+    @staticmethod
+    def get_encoding_layer(opt):
+        return UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+
+
 model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel}
+progressive_model_dict = {'PRBF': PRBFModel, 'PFF': PFFModel, 'PUFF': PUFFModel}
 
 
-def _args(net, times, ys, xs, scale):
+def _args(net, times, ys, xs, scale, mask=None, k_active=None):
     lins = net.linears()
     a = _lib.FlowNetArgs()
     a.encoding = net.encode.kind
-    a.enc_dim, a.hidden, a.layers, a.out_dim = net.encode.output_channels, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
+    a.progressive = int(bool(net.is_progressive))
+    a.enc_dim, a.hidden, a.layers, a.out_dim = net.encoding_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
     supported = (net.opt.domain_dim == 3 and len(lins) == 4 and _lib.lib().sininn_flownet_supported(C.byref(a)))
     if not supported:
-        raise ValueError(f'flownet kernels are built for 3 -> 512 -> 256 x 3 -> 4; got {net.opt.domain_dim} -> {a.enc_dim} -> '
-                         f'{a.hidden} x {a.layers} -> {a.out_dim}')
+        raise ValueError(f'flownet kernels are built for 3 -> 512 (progressive: 515) -> 256 x 3 -> 4; got {net.opt.domain_dim} -> '
+                         f'{a.enc_dim} -> {a.hidden} x {a.layers} -> {a.out_dim}')
+    if a.progressive:
+        if mask is None:
+            raise ValueError('a progressive network is evaluated under a mask (flow_fields supplies all ones for a bare model)')
+        if not mask.is_cuda:
+            raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU mask)')
+        assert mask.dtype == torch.float32 and mask.is_contiguous() and tuple(mask.shape) == (a.enc_dim,)
+        a.mask = ptr(mask)
+        a.k_active = a.enc_dim if k_active is None else int(k_active)
+    elif mask is not None:
+        raise ValueError('a mask needs a progressive network')
     for t in (times, ys, xs):
         if not t.is_cuda:
             raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
@@ -207,12 +279,13 @@ def _args(net, times, ys, xs, scale):
     return a
 
 
-def flownet_forward(net, times, ys, xs, scale, train, saved=None):
+def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None):
     """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
     (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
-    caller-provided buffer of that shape)."""
+    caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats and `k_active` a
+    number of leading features after which the mask is all zero (None: 515, nothing is skipped)."""
     times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale)
+    a = _args(net, times, ys, xs, scale, mask, k_active)
     n = a.T * a.H * a.W
     flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
     if train:
@@ -224,15 +297,18 @@ def flownet_forward(net, times, ys, xs, scale, train, saved=None):
     else:
         saved = None
     a.flows = ptr(flows)
+    if a.progressive:                                    # the packed, masked copy of W1
+        pack = torch.empty(_lib.lib().sininn_flownet_forward_workspace_bytes(C.byref(a)) // 4, device=times.device, dtype=torch.float32)
+        a.workspace, a.workspace_bytes = ptr(pack), pack.numel() * 4
     check(_lib.lib().sininn_flownet_forward(C.byref(a), _stream()))
     return flows, saved
 
 
-def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None):
+def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, mask=None, k_active=None):
     """[gW1, gb1, .., gW4, gb4] for an upstream gradient dflows (t, 4, h, w); `workspace`: optional fp32 tensor of at least
-    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise)."""
+    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise); `mask` / `k_active`: those of the forward call."""
     times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale)
+    a = _args(net, times, ys, xs, scale, mask, k_active)
     n = a.T * a.H * a.W
     if not dflows.is_cuda:
         raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
@@ -255,18 +331,19 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None):
 
 class _FlowFields(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, times, ys, xs, scale, train, *params):
-        flows, saved = flownet_forward(net, times, ys, xs, scale, train)
-        ctx.net, ctx.axes, ctx.scale, ctx.saved = net, (times, ys, xs), scale, saved
+    def forward(ctx, net, times, ys, xs, scale, train, mask, *params):
+        mask, k_active = mask
+        flows, saved = flownet_forward(net, times, ys, xs, scale, train, mask=mask, k_active=k_active)
+        ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask = net, (times, ys, xs), scale, saved, (mask, k_active)
         return flows
 
     @staticmethod
     def backward(ctx, dflows):
         if ctx.saved is None:
             raise RuntimeError('flow_fields: backward through an inference-mode forward')
-        grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved)
+        grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, mask=ctx.mask[0], k_active=ctx.mask[1])
         ctx.saved = None
-        return (None,) * 6 + tuple(grads)
+        return (None,) * 7 + tuple(grads)
 
 
 def grid_axes(net, times, h, w):
@@ -278,14 +355,45 @@ def grid_axes(net, times, h, w):
     return net._axes[key]
 
 
-def flow_fields(net, times, h, w, scale):
+def last_open(mask):
+    """k_active of a HOST mask: the number of leading features after which every entry is zero"""
+    nz = torch.nonzero(mask).reshape(-1)
+    return int(nz[-1]) + 1 if nz.numel() else 0
+
+
+def _resolve_mask(net, override_mask, device):
+    """(model, (device mask, k_active)) for a plain model, a bare progressive model or a controller (a module that wraps a
+    progressive model as `.model` and keeps a mask)"""
+    from .progressive import ProgressiveEncoderController
+    controller = net if isinstance(net, ProgressiveEncoderController) else None
+    model = net.model if controller is not None else net
+    if not model.is_progressive:
+        if override_mask is not None:
+            raise ValueError('override_mask needs a progressive network')
+        return model, (None, None)
+    if override_mask is not None:
+        m = override_mask.detach()
+        assert m.dim() == 1 and m.numel() == model.encoding_dim, 'a global mask of encoding_dim values (per-point masks are out of scope)'
+        if m.is_cuda:                                    # not inspected on the host: no synchronisation, nothing skipped
+            return model, (m.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim)
+        m = m.to(torch.float32).contiguous()
+        return model, (m.to(device), last_open(m))
+    if controller is not None:
+        return model, controller.device_mask(device)
+    return model, (model.ones_mask(device), model.encoding_dim)
+
+
+def flow_fields(net, times, h, w, scale, override_mask=None):
     """FlowTrainer.forward (trainer.py:37-45): (flow12, flow21), each (t, 2, h, w), views of one (t, 4, h, w) tensor.  Under
-    torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved."""
+    torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved.  `net` is a
+    model or a controller around a progressive model; `override_mask` (515 values, progressive networks only) replaces the
+    controller's mask."""
     if not times.is_cuda:
         raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
     assert times.dtype == torch.float32 and times.dim() == 1
+    net, mask = _resolve_mask(net, override_mask, times.device)
     ys, xs = grid_axes(net, times, h, w)
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
     train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, *params)
+    flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, mask, *params)
     return flows[:, :2], flows[:, 2:]

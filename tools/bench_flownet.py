@@ -7,6 +7,9 @@ FLOP counts come from the shapes (2 N (512*256 + 2*256*256 + 256*4) forward; bac
 the weight gradients of all four); `mfma_peak_share` is those executed FLOPs over the event time against the 157.3 TFLOP/s f32
 matrix peak of an MI355X -- the share of the whole call, not of one kernel.  --baseline times the same module composed from
 torch's own GPU ops (tools/fit_flow.composed_flow_fields) in the same process, alternating windows with the fused path.
+The progressive nets (PRBF, PFF, PUFF) run under a prefix mask of --k-active leading ones (default 515: all ones), given as a
+host tensor so that the kernels skip the closed features as they do under a controller; the FLOP counts stay those of the full
+network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.
 """
 import argparse
 import json
@@ -49,7 +52,8 @@ def window(fn, seconds, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF'])
+    ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask')
     ap.add_argument('--frames', type=int, default=1)
     ap.add_argument('--height', type=int, default=436)
     ap.add_argument('--width', type=int, default=1024)
@@ -58,25 +62,35 @@ def main():
     ap.add_argument('--rounds', type=int, default=2, help='alternations of the fused and the baseline windows')
     ap.add_argument('--baseline', action='store_true')
     a = ap.parse_args()
-    from sin_inn_amd import _lib, flownet
+    from sin_inn_amd import _lib, flownet, progressive
     from fit_flow import composed_flow_fields
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
-    net = flownet.model_dict[a.net](flownet.ModelParams()).to(dev)
+    prog = a.net in flownet.progressive_model_dict
+    net = (flownet.progressive_model_dict if prog else flownet.model_dict)[a.net](flownet.ModelParams()).to(dev)
+    target = net
+    if prog:
+        assert 0 <= a.k_active <= 515
+        target = progressive.LinearController(net)
+        target.mask = torch.zeros(515)
+        target.mask[:a.k_active] = 1
+        mask_dev = target.mask.to(dev)
     times = torch.linspace(0, 1, a.frames, device=dev) if a.frames > 1 else torch.zeros(1, device=dev)
     n = a.frames * a.height * a.width
     up = torch.randn(a.frames, 4, a.height, a.width, device=dev)
     params = list(net.parameters())
 
     def paths(fields):
+        kw = dict(override_mask=mask_dev) if prog and fields is composed_flow_fields else {}
+
         def fwd():
             with torch.no_grad():
-                fields(net, times, a.height, a.width, 2.0)
+                fields(target, times, a.height, a.width, 2.0, **kw)
 
         def step():
             for p in params:
                 p.grad = None
-            f12, f21 = fields(net, times, a.height, a.width, 2.0)
+            f12, f21 = fields(target, times, a.height, a.width, 2.0, **kw)
             torch.autograd.backward([f12, f21], [up[:, :2], up[:, 2:]])
         return fwd, step
 
@@ -89,7 +103,7 @@ def main():
             res[k]['forward'].append(window(fwd, a.seconds, a.warmup))
             res[k]['step'].append(window(step, a.seconds, a.warmup))
     f_fwd, f_step = flops(n)
-    out = dict(net=a.net, frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
+    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=_lib.lib().sininn_flownet_saved_bytes(n), workspace_bytes=_lib.lib().sininn_flownet_workspace_bytes(n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):

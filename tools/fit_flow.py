@@ -2,6 +2,10 @@
 -> backward -> FusedAdam, the training step of video-interpolation/trainer.py:47-87 on this project's kernels.
 
     python tools/fit_flow.py --net RBF --height 64 --width 96 --steps 60
+    python tools/fit_flow.py --net PRBF --max-iteration 1000
+
+A progressive network (PRBF, PFF, PUFF) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
+video-interpolation/main.py:136-143 does, and the controller sees the loss after every step (trainer.py:75), which opens the mask.
 
 The pair is seeded and analytic: frame1 is a smooth texture, frame2 the same texture displaced by a known smooth flow.
 `--composed` evaluates the network with torch's own ops (nn.functional.linear and elementwise ops) instead of the fused
@@ -39,13 +43,18 @@ def make_pair(h, w, seed, device):
     return f1[None].to(device).contiguous(), f2[None].to(device).contiguous(), torch.stack((u, v))[None].to(device)
 
 
-def composed_flow_fields(net, times, h, w, scale):
+def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     """FlowTrainer.forward (trainer.py:37-45) with torch's own GPU ops on the port's buffers and parameters: what a user of the
-    reference runs, and the baseline of tools/bench_flownet.py"""
+    reference runs, and the baseline of tools/bench_flownet.py.  A progressive network reads cat((poses, encoding)) times the
+    mask of its controller (or `override_mask`; a bare network: no mask), model.py:532-535 and 89-99."""
+    mask = override_mask
+    if hasattr(net, 'mask'):                                      # a controller
+        mask = net.mask if mask is None else mask
+        net = net.model
     ys = torch.linspace(-1, 1, h).to(times)
     xs = torch.linspace(-1, 1, w).to(times)
     gt, gh, gw = torch.meshgrid(times, ys, xs, indexing='ij')
-    x = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
+    x = poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
     enc = net.encode
     if hasattr(enc, 'centres'):
         x = (x[:, None, :] - enc.centres[None, :, :]).pow(2).sum(2)
@@ -53,16 +62,27 @@ def composed_flow_fields(net, times, h, w, scale):
     else:
         x = torch.matmul(x * 2 * math.pi, enc.frequencies)
         x = torch.stack((torch.sin(x), torch.cos(x)), dim=2).view(x.shape[0], -1)
+    if net.is_progressive:
+        x = torch.cat((poses, x), dim=-1)
+        if mask is not None:
+            x = x * mask.to(x)[None, :]
     flows = net.model.model(x).view(times.numel(), h, w, 4).permute(0, 3, 1, 2) * scale
     return flows[:, :2], flows[:, 2:]
 
 
-def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None):
-    """returns the list of per-step losses (floats)"""
-    from sin_inn_amd import FusedAdam, flowloss as FL, flownet
+def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None, max_iteration=1000,
+        info=None):
+    """returns the list of per-step losses (floats); `info`: a dict that receives the network (the controller of a progressive one)"""
+    from sin_inn_amd import FusedAdam, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
-    net = flownet.model_dict[net_name](flownet.ModelParams()).to(device)
+    if net_name in flownet.progressive_model_dict:
+        net = flownet.progressive_model_dict[net_name](flownet.ModelParams()).to(device)
+        net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
+    else:
+        net = flownet.model_dict[net_name](flownet.ModelParams()).to(device)
+    if info is not None:
+        info['net'] = net
     opt = FusedAdam(net.parameters(), lr=lr)
     frame1, frame2, _ = make_pair(h, w, seed + 1, device)
     times = torch.zeros(1, device=device)
@@ -86,15 +106,18 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
                 + smooth(frame1, flow12) + smooth(frame2, flow21))
         loss.backward()
         opt.step()
+        net.stash_iteration(loss.detach())
         losses.append(float(loss))
         if log:
-            log(f'step {step:3d}  loss {losses[-1]:.6f}')
+            extra = f'  open {net.cur_block:3d} / {net.encoding_dim}' if net.is_progressive else ''
+            log(f'step {step:3d}  loss {losses[-1]:.6f}{extra}')
     return losses
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF'])
+    ap.add_argument('--max-iteration', type=int, default=1000, help='progressive nets: the controller opens the mask over 3/4 of it')
     ap.add_argument('--height', type=int, default=64)
     ap.add_argument('--width', type=int, default=96)
     ap.add_argument('--steps', type=int, default=60)
@@ -102,7 +125,7 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--composed', action='store_true')
     a = ap.parse_args()
-    losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print)
+    losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration)
     print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
 
 
