@@ -668,6 +668,18 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
  *   column k = mask[k] * sum_p dh1[p][j] feature_k[p], an exact 0 where mask[k] is 0.  The forward call folds the mask into a packed
  *   copy of w[0] and needs a workspace of sininn_flownet_forward_workspace_bytes(args) bytes for it (0 if not progressive); the
  *   backward call needs no more than sininn_flownet_workspace_bytes(N), and `saved` has the same size.
+ * Learnable frequencies (model.py:263-307 RotatedFourierFeatures, RFFModel model.py:436-451, PRFFModel model.py:586-590): the caller passes
+ *   F_eff = normalize(frequencies, dim 0) * magnitudes as enc_a (768 values, computed with its own ops) and the forward call is the
+ *   Fourier one.  sininn_flownet_backward_encgrad does everything sininn_flownet_backward does (the eight gradients are bitwise the same)
+ *   and also writes g_enc_a [3][256] (OVERWRITTEN), the gradient with respect to the matrix passed as enc_a:
+ *     dE[p][k] = sum_j dh1[p][j] w[0][j][k] (progressive: w[0][j][3 + k] * mask[3 + k]), never stored;
+ *     dphi[p][f] = dE[p][2 f] cos(phi[p][f]) - dE[p][2 f + 1] sin(phi[p][f]), sin / cos as the forward pass computed them;
+ *     g_enc_a[d][f] = 2 pi sum_p coordinate_d[p] dphi[p][f], per-block partial sums added in index order (no floating-point atomics: two
+ *     calls are bitwise equal); progressive: an exact +0 for a frequency whose sin and cos features are both closed, and any valid
+ *     k_active gives bitwise the same g_enc_a.
+ *   It needs a second workspace of sininn_flownet_encgrad_workspace_bytes(args) bytes (a transposed copy of w[0] and the partial sums; 0
+ *   if the encoding is not Fourier), 16-byte aligned, and refuses encoding != SININN_FLOWNET_FOURIER, a null g_enc_a and a short
+ *   enc_workspace before any launch.
  * Borrowed pointers, 16-byte aligned (axis vectors, biases and the mask: 4), the caller's stream, non-zero return + sininn_last_error.
  * sininn_flownet_supported: 1 if the sizes are the ones the kernels are built for, else 0 (callers raise, there is no second path).
  * ---------------------------------------------------------------------------------------------- */
@@ -698,6 +710,9 @@ size_t sininn_flownet_workspace_bytes(int64_t n_points);
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_forward(const sininn_flownet_args* args, void* stream);
 int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
+size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args);
+int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                    void* stream);
 
 #ifdef __cplusplus
 }

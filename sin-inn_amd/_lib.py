@@ -251,6 +251,8 @@ _SIGS = {
     'sininn_flownet_forward_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_forward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
     'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
+    'sininn_flownet_encgrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
+    'sininn_flownet_backward_encgrad': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, C.c_void_p]),
 }

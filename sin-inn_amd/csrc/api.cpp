@@ -123,6 +123,8 @@ size_t flownet_workspace_bytes(int64_t n);
 size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a);
 int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
+size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a);
+int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -569,5 +571,10 @@ size_t sininn_flownet_workspace_bytes(int64_t n_points) { return flownet_workspa
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args) { return flownet_forward_workspace_bytes(args); }
 int sininn_flownet_forward(const sininn_flownet_args* args, void* stream) { return flownet_forward_launch(args, ST(stream)); }
 int sininn_flownet_backward(const sininn_flownet_args* args, void* stream) { return flownet_backward_launch(args, ST(stream)); }
+size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args) { return flownet_encgrad_workspace_bytes(args); }
+int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                    void* stream) {
+  return flownet_backward_encgrad_launch(args, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
+}
 
 }  // extern "C"

@@ -85,6 +85,16 @@ __device__ __forceinline__ Coord point_coord(const FlowNetDev& q, int p) {
   return Coord{q.times[t], q.ys[y], q.xs[x]};
 }
 
+// sin / cos of 2 pi (c . f) for one frequency f = (fa, fb, fc).  The phase is kept in REVOLUTIONS: each product is split into its
+// rounded value and its exact rounding error, the rounded value is reduced to [-1/2, 1/2] exactly, so the phase of a 75-cycle
+// frequency is as good as that of a slow one; sincospi does the rest
+__device__ __forceinline__ void fourier_sincos(const Coord c, float fa, float fb, float fc, float& s, float& co) {
+  const float p0 = c.t * fa, p1 = c.y * fb, p2 = c.x * fc;
+  const float e = fmaf(c.t, fa, -p0) + fmaf(c.y, fb, -p1) + fmaf(c.x, fc, -p2);
+  const float r = ((p0 - rintf(p0)) + (p1 - rintf(p1)) + (p2 - rintf(p2))) + e;
+  sincospif(2.f * r, &s, &co);
+}
+
 // features f0 .. f0 + 3 (f0 % 4 == 0) of one point
 template <int KIND>
 __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int f0) {
@@ -101,19 +111,14 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
       o[j] = expf(-(d * (sg[j] * sg[j])));
     }
   } else {
-    // phase in REVOLUTIONS: each product is split into its rounded value and its exact rounding error, the rounded value is
-    // reduced to [-1/2, 1/2] exactly, so the phase of a 75-cycle frequency is as good as that of a slow one; sincospi does the rest
     const int f = f0 >> 1;                                                 // frequencies [3][256]
     const f32x2 fa = *reinterpret_cast<const f32x2*>(q.enc_a + f);
     const f32x2 fb = *reinterpret_cast<const f32x2*>(q.enc_a + 256 + f);
     const f32x2 fc = *reinterpret_cast<const f32x2*>(q.enc_a + 512 + f);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const float p0 = c.t * fa[u], p1 = c.y * fb[u], p2 = c.x * fc[u];
-      const float e = fmaf(c.t, fa[u], -p0) + fmaf(c.y, fb[u], -p1) + fmaf(c.x, fc[u], -p2);
-      const float r = ((p0 - rintf(p0)) + (p1 - rintf(p1)) + (p2 - rintf(p2))) + e;
       float s, co;
-      sincospif(2.f * r, &s, &co);
+      fourier_sincos(c, fa[u], fb[u], fc[u], s, co);
       o[2 * u] = s;
       o[2 * u + 1] = co;
     }
@@ -508,6 +513,117 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_prog_kernel(const floa
   else gb[i - NW] = s;
 }
 
+// ---- gradient with respect to the Fourier frequencies (the learnable encodings RFF / PRFF) ----
+// dE[p][k] = sum_j dh1[p][j] W1[j][k] is one more data-gradient GEMM through layer 1, contracted over the 256 hidden columns with the
+// forward's LDS loop on a transposed W1; dE lives in the accumulators only.  Row c of that transposed matrix is CHOSEN: pass c / 256,
+// wave (c / 64) % 4, accumulator column block n = (c / 16) % 4, lane c % 16 holds feature 2 f + n / 2 of frequency
+// f = 128 pass + 32 wave + 16 (n % 2) + lane, so a lane's accumulators n and n + 2 are the sin and the cos coefficient of ONE frequency
+// for the same 16 points and dphi = dE_sin cos(phi) - dE_cos sin(phi) needs no lane movement.
+constexpr int FN_NF = FN_ENC / 2;                    // frequencies
+constexpr int FN_EG_PART = FN_DOM * FN_NF;           // floats of one block's partial sums, [3][256]
+constexpr size_t FN_EG_FLOATS = (size_t)FN_ENC * FN_HID + (size_t)FN_CHAIN_MAX_BLOCKS * FN_EG_PART;
+constexpr float FN_TWO_PI = 6.283185307179586f;
+
+// wt[c][j] = w1[j][feature of row c] (progressive: column 3 + feature, times its mask, an exact zero where the mask is zero); block = row c
+__global__ __launch_bounds__(FN_NTHR) void flownet_encgrad_pack_kernel(const float* w1, const float* mask, float* wt) {
+  const int c = blockIdx.x, j = threadIdx.x;
+  const int f = (c >> 8) * 128 + ((c >> 6) & 3) * 32 + ((c >> 4) & 1) * 16 + (c & 15);
+  const int k = 2 * f + ((c >> 5) & 1);
+  float v;
+  if (mask) {
+    const float m = mask[FN_DOM + k];
+    v = m == 0.f ? 0.f : w1[(size_t)j * FN_PENC + FN_DOM + k] * m;
+  } else {
+    v = w1[(size_t)j * FN_ENC + k];
+  }
+  wt[(size_t)c * FN_HID + j] = v;
+}
+
+// part[block][d][f] = sum over the block's point tiles of coordinate_d[p] dphi[p][f]; grid-stride over tiles like the chain kernel.
+// Frequencies from `fopen` on are closed (progressive): a wave whose 32 frequencies are all closed skips its GEMM and leaves zeros
+__global__ __launch_bounds__(FN_NTHR, 2) void flownet_encgrad_kernel(FlowNetDev q, const float* wt, float* part, int fopen) {
+  extern __shared__ __attribute__((aligned(16))) float fn_smem[];
+  float* const hs = fn_smem;                           // [64][FN_HS]: dh1 tile
+  float* const cs = fn_smem + FN_P * FN_HS;            // [64][4]: coordinates of the tile's points
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, kq = lane >> 4;
+  const int cw = wave * 64;
+
+  float g[2][2][FN_DOM];
+#pragma unroll
+  for (int u = 0; u < 4 * FN_DOM; ++u) (&g[0][0][0])[u] = 0.f;
+
+  for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
+    __syncthreads();                                   // the previous tile is done with hs / cs
+#pragma unroll 4
+    for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
+      const int f = tid + FN_NTHR * u;
+      const int row = f >> 6, c4 = (f & 63) * 4;
+      *reinterpret_cast<f32x4*>(hs + row * FN_HS + c4) = *reinterpret_cast<const f32x4*>(q.dh + ((size_t)tile * FN_P + row) * FN_HID + c4);
+    }
+    if (tid < FN_P) {
+      const Coord c = point_coord(q, tile * FN_P + tid);
+      *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const int fw = ps * (FN_NF / 2) + wave * 32;     // this wave's 32 frequencies of the pass
+      if (fw >= fopen) continue;                       // wave-uniform; no barrier below
+      f32x4 acc[4][4];
+      zero_acc(acc);
+      gemm_lds(hs, wt + (size_t)ps * FN_HID * FN_HID, cw, li, kq, acc);
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        const int f = fw + 16 * n + li;
+        const float fa = q.enc_a[f], fb = q.enc_a[FN_NF + f], fc = q.enc_a[2 * FN_NF + f];
+        float st = 0.f, sy = 0.f, sx = 0.f;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const f32x4 c = *reinterpret_cast<const f32x4*>(cs + (16 * m + 4 * kq + r) * FN_CS);
+            float sn, co;
+            fourier_sincos(Coord{c[0], c[1], c[2]}, fa, fb, fc, sn, co);
+            const float d = acc[m][n][r] * co - acc[m][n + 2][r] * sn;
+            st = fmaf(c[0], d, st);
+            sy = fmaf(c[1], d, sy);
+            sx = fmaf(c[2], d, sx);
+          }
+        g[ps][n][0] += st;
+        g[ps][n][1] += sy;
+        g[ps][n][2] += sx;
+      }
+    }
+  }
+  // the four lanes li, li + 16, li + 32, li + 48 hold the four row groups of one frequency: (0 + 1) + (2 + 3)
+  float* const out = part + (size_t)blockIdx.x * FN_EG_PART;
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int d = 0; d < FN_DOM; ++d) {
+        float v = g[ps][n][d];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        if (kq == 0) out[d * FN_NF + ps * (FN_NF / 2) + wave * 32 + 16 * n + li] = v;
+      }
+}
+
+// g[d][f] = 2 pi sum_c part[c][d][f], blocks in index order; an exact +0 for a frequency from `fopen` on or (progressive) one whose two
+// features are both closed by the mask, whatever the partial sums hold
+__global__ __launch_bounds__(FN_NTHR) void flownet_reduce_enc_kernel(const float* part, int nparts, const float* mask, int fopen, float* g) {
+  const int i = blockIdx.x * FN_NTHR + threadIdx.x;
+  if (i >= FN_EG_PART) return;
+  const int f = i % FN_NF;
+  if (f >= fopen || (mask && mask[FN_DOM + 2 * f] == 0.f && mask[FN_DOM + 2 * f + 1] == 0.f)) { g[i] = 0.f; return; }
+  float s = 0.f;
+  for (int c = 0; c < nparts; ++c) s += part[(size_t)c * FN_EG_PART + i];
+  g[i] = s * FN_TWO_PI;
+}
+
 int wgrad_chunks(int ntiles, int kf) {
   const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 for layer 1
   return ntiles < want ? ntiles : want;
@@ -617,7 +733,36 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
   return 0;
 }
 
-int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) {
+size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
+  return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) && a->encoding == SININN_FLOWNET_FOURIER ? FN_EG_FLOATS * sizeof(float) : 0;
+}
+
+namespace {
+int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st);
+}
+
+int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_launch(a, nullptr, nullptr, st); }
+
+int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                    hipStream_t st) {
+  const char* who = "flownet_backward_encgrad";
+  SININN_CHECK(a != nullptr, "%s: null args", who);
+  SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
+               a->struct_bytes, sizeof(sininn_flownet_args));
+  SININN_CHECK(a->encoding == SININN_FLOWNET_FOURIER, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
+               a->encoding);
+  SININN_CHECK(g_enc_a != nullptr, "%s: null g_enc_a", who);
+  SININN_CHECK(enc_workspace != nullptr && enc_workspace_bytes >= flownet_encgrad_workspace_bytes(a),
+               "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
+               flownet_encgrad_workspace_bytes(a));
+  SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
+  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st);
+}
+
+namespace {
+
+// g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
+int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st) {
   FlowNetDev q;
   if (int rc = check_args(a, "flownet_backward", q)) return rc;
   SININN_CHECK(a->dflows && a->saved && a->workspace, "flownet_backward: null dflows / saved / workspace");
@@ -678,7 +823,22 @@ int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) {
     reduce(nc, FN_HID * FN_ENC, FN_HID, a->gw[0], a->gb[0]);
     SININN_LAUNCH_CHECK("flownet_reduce");
   }
+  if (g_enc_a) {
+    float* const epart = enc_ws + (size_t)FN_ENC * FN_HID;
+    const float* const mask = a->progressive ? a->mask : nullptr;
+    const int fopen = a->progressive ? (open_encoded(a) + 1) / 2 : FN_NF;   // a frequency is open if its sin or its cos is
+    hipLaunchKernelGGL(flownet_encgrad_pack_kernel, dim3(FN_ENC), dim3(FN_NTHR), 0, st, a->w[0], mask, enc_ws);
+    SININN_LAUNCH_CHECK("flownet_encgrad_pack");
+    if (raise_lds(flownet_encgrad_kernel, FN_LDS, "flownet_encgrad")) return 1;
+    hipLaunchKernelGGL(flownet_encgrad_kernel, dim3(cb), dim3(FN_NTHR), FN_LDS, st, q, (const float*)enc_ws, epart, fopen);   // not a function of k_active
+    SININN_LAUNCH_CHECK("flownet_encgrad");
+    hipLaunchKernelGGL(flownet_reduce_enc_kernel, dim3((FN_EG_PART + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, (const float*)epart, cb, mask,
+                       fopen, g_enc_a);
+    SININN_LAUNCH_CHECK("flownet_reduce_enc");
+  }
   return 0;
 }
+
+}  // namespace
 
 }  // namespace sininn

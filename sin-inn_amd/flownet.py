@@ -3,12 +3,13 @@ backward in libsininn.so (csrc/flownet.hip).
 
     ModelParams / RbfModel / FFModel / UFFModel / model_dict   video-interpolation/model.py:11-28, 490-505, 418-433, 454-469, 681
     ProgressiveModel / PRBFModel / PFFModel / PUFFModel        video-interpolation/model.py:526-598, 621-625 (progressive_model_dict)
+    RotatedFourierFeatures / RFFModel / PRFFModel              video-interpolation/model.py:263-307, 436-451, 586-590 (learnable_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
 
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
 `encode.frequencies`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
 first, then the four nn.Linear layers), so one `torch.manual_seed` gives the reference's numbers and a reference checkpoint
-loads.  The encodings are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
+loads.  The encodings of `model_dict` / `progressive_model_dict` are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
 (3 -> 512 -> 256 x 3 -> 4); any other size raises, there is no second implementation behind this module, and calling a model
 directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512 encoding never exist here.
 
@@ -19,7 +20,14 @@ a global vector of 515 values that a controller of `sin_inn_amd.progressive` ope
 number of leading features it has opened so far, and the kernels skip the rest of layer 1; an `override_mask` given as a device
 tensor is not inspected on the host and runs over all 515 features.  Both give bitwise the same result.
 
-Out of scope: `siren`, `RFF` / `PRFF` (learnable frequencies), `RBFG` / `PRBFG`, `PE` / `PPE` (the reference's
+`RFF` / `PRFF` train the encoding itself: `encode.frequencies` is an nn.Parameter [3][256] and the network uses
+`F_eff = normalize(frequencies, dim=0) * magnitudes` (`magnitudes` a buffer).  `flow_fields` computes F_eff with torch ops under
+autograd on every call (768 values) and hands it to the kernels as the frequency matrix, so the forward pass is the Fourier one;
+the backward pass (`sininn_flownet_backward_encgrad`) carries the gradient through layer 1 onto F_eff, all in fp32 with a fixed
+summation order, and torch's `normalize` backward takes it to `encode.frequencies.grad`.  With `frequencies.requires_grad` false,
+or grad mode off, the plain backward / inference path runs and nothing extra is computed.
+
+Out of scope: `siren`, `RBFG` / `PRBFG`, `PE` / `PPE` (the reference's
 PositionalEncoding.forward raises on any input, model.py:332), `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
 spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
 grid; `FixedSpatialController`; `AdaptiveController`), LAMB (the reference trains with apex FusedLAMB; these modules expose ordinary
@@ -129,6 +137,43 @@ class UniformFourierFeatures(_FourierFeatures):
     def init_magnitude(self, std):
         std = std / math.sqrt(3)
         return torch.linspace(-std, std, self.num_frequencies) + EPSILON
+
+
+class RotatedFourierFeatures(nn.Module):
+    """model.py:263-297: unit-norm directions are trained, the magnitudes are a buffer.  `init_magnitudes` is drawn first, then the
+    directions; the parameter is registered after the buffer but leads the state dict (parameters come before buffers)."""
+    kind = FOURIER
+
+    def __init__(self, domain_dim, num_frequencies, std):
+        super().__init__()
+        self.domain_dim = domain_dim
+        self.num_frequencies = num_frequencies
+        magnitudes = self.init_magnitudes(std)
+        frequencies = nn.Parameter(nnf.normalize(torch.randn(domain_dim, num_frequencies), p=2, dim=0))
+        self.register_buffer('magnitudes', magnitudes)
+        self.register_parameter('frequencies', frequencies)
+
+    @property
+    def output_channels(self):
+        return self.num_frequencies * 2
+
+    def effective_frequencies(self):
+        """F_eff [3][256] (model.py:274), differentiable with respect to `frequencies`"""
+        return nnf.normalize(self.frequencies, p=2, dim=0) * self.magnitudes[None, :]
+
+    def kernel_buffers(self):
+        return self.effective_frequencies().detach().contiguous(), None
+
+
+class GaussianRotatedFourierFeatures(RotatedFourierFeatures):
+    """model.py:299-307: the sorted magnitudes; the reference then draws a (domain_dim, num_frequencies) normal sample that it does
+    not use, which moves the generator, so it is drawn here too."""
+
+    def init_magnitudes(self, std):
+        magnitude = torch.randn(self.num_frequencies) * std
+        magnitude = magnitude[magnitude.abs().argsort(0)]
+        torch.randn(self.domain_dim, self.num_frequencies)
+        return magnitude
 
 
 class _EncodedMlpModel(nn.Module):
@@ -242,11 +287,28 @@ class PUFFModel(ProgressiveModel):
         return UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
 
 
+class RFFModel(_EncodedMlpModel):
+    """model.py:436-451."""
+
+    @staticmethod
+    def make_encoding(opt):
+        return GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+
+
+class PRFFModel(ProgressiveModel):
+    """model.py:586-590."""
+
+    @staticmethod
+    def get_encoding_layer(opt):
+        return GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+
+
 model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel}
 progressive_model_dict = {'PRBF': PRBFModel, 'PFF': PFFModel, 'PUFF': PUFFModel}
+learnable_model_dict = {'RFF': RFFModel, 'PRFF': PRFFModel}       # the encoding is trained; PRFF is progressive as well
 
 
-def _args(net, times, ys, xs, scale, mask=None, k_active=None):
+def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
     lins = net.linears()
     a = _lib.FlowNetArgs()
     a.encoding = net.encode.kind
@@ -271,21 +333,29 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None):
             raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
     a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
     a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
-    ea, eb = net.encode.kernel_buffers()
+    if enc_a is None:
+        ea, eb = net.encode.kernel_buffers()
+    else:                                                # learnable frequencies: F_eff of this call
+        if not enc_a.is_cuda:
+            raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+        assert net.encode.kind == FOURIER and enc_a.dtype == torch.float32 and enc_a.is_contiguous() and tuple(enc_a.shape) == (3, 256)
+        ea, eb = enc_a, None
     a.enc_a, a.enc_b = ptr(ea), ptr(eb)
+    a._keep = (ea, eb)                                   # kernel_buffers() of a learnable encoding is a temporary
     for l, lin in enumerate(lins):
         assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
         a.w[l], a.b[l] = ptr(lin.weight), ptr(lin.bias)
     return a
 
 
-def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None):
+def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
     """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
     (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
     caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats and `k_active` a
-    number of leading features after which the mask is all zero (None: 515, nothing is skipped)."""
+    number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
+    (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
     times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale, mask, k_active)
+    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
     n = a.T * a.H * a.W
     flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
     if train:
@@ -304,11 +374,15 @@ def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_a
     return flows, saved
 
 
-def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, mask=None, k_active=None):
+def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
+                     enc_workspace=None, g_enc_a=None):
     """[gW1, gb1, .., gW4, gb4] for an upstream gradient dflows (t, 4, h, w); `workspace`: optional fp32 tensor of at least
-    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise); `mask` / `k_active`: those of the forward call."""
+    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise); `mask` / `k_active` / `enc_a`: those of the forward call.
+    `enc_grad=True` (Fourier encodings) returns ([gW1, .., gb4], gF) with gF (3, 256) the gradient with respect to the frequency
+    matrix the kernels read; `enc_workspace`: optional fp32 tensor of sininn_flownet_encgrad_workspace_bytes bytes for it,
+    `g_enc_a`: optional (3, 256) fp32 tensor that receives gF."""
     times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale, mask, k_active)
+    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
     n = a.T * a.H * a.W
     if not dflows.is_cuda:
         raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
@@ -325,25 +399,39 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, m
         gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
         a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
         grads += [gw, gb]
-    check(_lib.lib().sininn_flownet_backward(C.byref(a), _stream()))
-    return grads
+    if not enc_grad:
+        check(_lib.lib().sininn_flownet_backward(C.byref(a), _stream()))
+        return grads
+    if enc_workspace is None:
+        enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=times.device, dtype=torch.float32)
+    g_enc = torch.empty(3, 256, device=times.device, dtype=torch.float32) if g_enc_a is None else g_enc_a
+    assert g_enc.is_cuda and g_enc.is_contiguous() and g_enc.dtype == torch.float32 and tuple(g_enc.shape) == (3, 256)
+    check(_lib.lib().sininn_flownet_backward_encgrad(C.byref(a), ptr(g_enc), ptr(enc_workspace), enc_workspace.numel() * 4, _stream()))
+    return grads, g_enc
 
 
 class _FlowFields(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, net, times, ys, xs, scale, train, mask, *params):
+    def forward(ctx, net, times, ys, xs, scale, train, mask, enc_a, *params):
         mask, k_active = mask
-        flows, saved = flownet_forward(net, times, ys, xs, scale, train, mask=mask, k_active=k_active)
+        if enc_a is not None:
+            enc_a = enc_a.detach().contiguous()
+        flows, saved = flownet_forward(net, times, ys, xs, scale, train, mask=mask, k_active=k_active, enc_a=enc_a)
         ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask = net, (times, ys, xs), scale, saved, (mask, k_active)
+        ctx.enc_a, ctx.enc_grad = enc_a, enc_a is not None and ctx.needs_input_grad[7]
         return flows
 
     @staticmethod
     def backward(ctx, dflows):
         if ctx.saved is None:
             raise RuntimeError('flow_fields: backward through an inference-mode forward')
-        grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, mask=ctx.mask[0], k_active=ctx.mask[1])
+        grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, mask=ctx.mask[0], k_active=ctx.mask[1], enc_a=ctx.enc_a,
+                                 enc_grad=ctx.enc_grad)
+        g_enc = None
+        if ctx.enc_grad:
+            grads, g_enc = grads
         ctx.saved = None
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 7 + (g_enc,) + tuple(grads)
 
 
 def grid_axes(net, times, h, w):
@@ -387,13 +475,15 @@ def flow_fields(net, times, h, w, scale, override_mask=None):
     """FlowTrainer.forward (trainer.py:37-45): (flow12, flow21), each (t, 2, h, w), views of one (t, 4, h, w) tensor.  Under
     torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved.  `net` is a
     model or a controller around a progressive model; `override_mask` (515 values, progressive networks only) replaces the
-    controller's mask."""
+    controller's mask.  A learnable encoding (RFF / PRFF) contributes F_eff, computed here with torch ops; its gradient is computed
+    only if `encode.frequencies` requires one."""
     if not times.is_cuda:
         raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
     assert times.dtype == torch.float32 and times.dim() == 1
     net, mask = _resolve_mask(net, override_mask, times.device)
     ys, xs = grid_axes(net, times, h, w)
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
-    train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, mask, *params)
+    enc_a = net.encode.effective_frequencies() if isinstance(net.encode, RotatedFourierFeatures) else None
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad))
+    flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, mask, enc_a, *params)
     return flows[:, :2], flows[:, 2:]

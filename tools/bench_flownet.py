@@ -10,6 +10,8 @@ torch's own GPU ops (tools/fit_flow.composed_flow_fields) in the same process, a
 The progressive nets (PRBF, PFF, PUFF) run under a prefix mask of --k-active leading ones (default 515: all ones), given as a
 host tensor so that the kernels skip the closed features as they do under a controller; the FLOP counts stay those of the full
 network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.
+RFF / PRFF (learnable frequencies) add the data gradient through layer 1 to the step (2 N 512*256 more FLOPs, counted) and the torch ops
+that make F_eff and carry its gradient to `encode.frequencies`; PRFF runs under the prefix mask like the other progressive nets.
 """
 import argparse
 import json
@@ -26,9 +28,9 @@ for p in (ROOT, os.path.join(ROOT, 'tools')):
 PEAK_F32_MFMA = 157.3e12
 
 
-def flops(n):
+def flops(n, learnable=False):
     fwd = 2 * n * (512 * 256 + 2 * 256 * 256 + 256 * 4)
-    dgrad = 2 * n * (2 * 256 * 256 + 256 * 4)
+    dgrad = 2 * n * (2 * 256 * 256 + 256 * 4 + (512 * 256 if learnable else 0))
     return fwd, fwd + dgrad + fwd
 
 
@@ -52,7 +54,7 @@ def window(fn, seconds, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF'])
     ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask')
     ap.add_argument('--frames', type=int, default=1)
     ap.add_argument('--height', type=int, default=436)
@@ -66,8 +68,9 @@ def main():
     from fit_flow import composed_flow_fields
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
-    prog = a.net in flownet.progressive_model_dict
-    net = (flownet.progressive_model_dict if prog else flownet.model_dict)[a.net](flownet.ModelParams()).to(dev)
+    learnable = a.net in flownet.learnable_model_dict
+    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}[a.net](flownet.ModelParams()).to(dev)
+    prog = net.is_progressive
     target = net
     if prog:
         assert 0 <= a.k_active <= 515
@@ -102,7 +105,7 @@ def main():
         for k, (fwd, step) in todo.items():
             res[k]['forward'].append(window(fwd, a.seconds, a.warmup))
             res[k]['step'].append(window(step, a.seconds, a.warmup))
-    f_fwd, f_step = flops(n)
+    f_fwd, f_step = flops(n, learnable)
     out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=_lib.lib().sininn_flownet_saved_bytes(n), workspace_bytes=_lib.lib().sininn_flownet_workspace_bytes(n))
     for k in res:

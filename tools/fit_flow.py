@@ -3,9 +3,12 @@
 
     python tools/fit_flow.py --net RBF --height 64 --width 96 --steps 60
     python tools/fit_flow.py --net PRBF --max-iteration 1000
+    python tools/fit_flow.py --net RFF
 
-A progressive network (PRBF, PFF, PUFF) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
+A progressive network (PRBF, PFF, PUFF, PRFF) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
 video-interpolation/main.py:136-143 does, and the controller sees the loss after every step (trainer.py:75), which opens the mask.
+
+RFF / PRFF train `encode.frequencies` as well: the optimiser gets net.parameters(), which includes them.
 
 The pair is seeded and analytic: frame1 is a smooth texture, frame2 the same texture displaced by a known smooth flow.
 `--composed` evaluates the network with torch's own ops (nn.functional.linear and elementwise ops) instead of the fused
@@ -46,7 +49,8 @@ def make_pair(h, w, seed, device):
 def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     """FlowTrainer.forward (trainer.py:37-45) with torch's own GPU ops on the port's buffers and parameters: what a user of the
     reference runs, and the baseline of tools/bench_flownet.py.  A progressive network reads cat((poses, encoding)) times the
-    mask of its controller (or `override_mask`; a bare network: no mask), model.py:532-535 and 89-99."""
+    mask of its controller (or `override_mask`; a bare network: no mask), model.py:532-535 and 89-99.  A learnable encoding (RFF /
+    PRFF) normalises its frequencies and scales them by the magnitudes on every call, model.py:274."""
     mask = override_mask
     if hasattr(net, 'mask'):                                      # a controller
         mask = net.mask if mask is None else mask
@@ -60,7 +64,8 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
         x = (x[:, None, :] - enc.centres[None, :, :]).pow(2).sum(2)
         x = torch.exp(-(x * enc.sigma[None, :] ** 2))
     else:
-        x = torch.matmul(x * 2 * math.pi, enc.frequencies)
+        freq = enc.effective_frequencies() if hasattr(enc, 'magnitudes') else enc.frequencies
+        x = torch.matmul(x * 2 * math.pi, freq)
         x = torch.stack((torch.sin(x), torch.cos(x)), dim=2).view(x.shape[0], -1)
     if net.is_progressive:
         x = torch.cat((poses, x), dim=-1)
@@ -76,11 +81,10 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     from sin_inn_amd import FusedAdam, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
-    if net_name in flownet.progressive_model_dict:
-        net = flownet.progressive_model_dict[net_name](flownet.ModelParams()).to(device)
+    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}
+    net = nets[net_name](flownet.ModelParams()).to(device)
+    if net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
-    else:
-        net = flownet.model_dict[net_name](flownet.ModelParams()).to(device)
     if info is not None:
         info['net'] = net
     opt = FusedAdam(net.parameters(), lr=lr)
@@ -116,7 +120,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF'])
     ap.add_argument('--max-iteration', type=int, default=1000, help='progressive nets: the controller opens the mask over 3/4 of it')
     ap.add_argument('--height', type=int, default=64)
     ap.add_argument('--width', type=int, default=96)
