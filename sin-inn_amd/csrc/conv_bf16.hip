@@ -392,7 +392,9 @@ static int launch_ht(const ConvDevB& q, hipStream_t st) {
   return launch_one<KS, CK, 8, false>(q, st);
 }
 
-int g_bf16_force_ck16 = 0;     // diagnostic (SININN_BF16_CK16=1): 16-channel chunks everywhere (3 blocks per CU instead of 2)
+// test hook (sininn_conv_test_hooks(cfg, 16) sets it, any other chunk clears it): 16-channel chunks (3 blocks per CU instead of 2)
+// where launch_ks would take 32.  Unlike the SININN_BF16_CK16 environment diagnostic it does not reach a 1x1 conv with Kp % 128 == 0.
+int g_bf16_force_ck16 = 0;
 
 template <int KS>
 static int launch_ks(const ConvDevB& q, hipStream_t st) {

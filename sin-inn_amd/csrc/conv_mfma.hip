@@ -16,6 +16,7 @@ static int g_force_ck = 0;
 static int g_ablate = 0;     // diagnostic: see ConvDev::ablate (results are wrong when set)    // test hook: override the channel chunk
 
 int conv_bf16_launch(const sininn_conv_args* a, hipStream_t st);
+extern int g_bf16_force_ck16;   // conv_bf16.hip: test hook, 16-channel chunks where launch_ks would take 32
 
 // argument validation + device-side descriptor of one fp32 conv (shared by conv_launch and the fused 1x1 pair)
 int conv_prepare(const sininn_conv_args* a, ConvDev& d) {
@@ -127,6 +128,7 @@ int conv_launch(const sininn_conv_args* a, hipStream_t st) {
 void conv_set_test_hooks(int force_cfg, int force_ck) {
   // force_cfg = ablate*1000 + dma*100 + cfg   (cfg >= 10 pins the 16-wide kernel; dma: 1 on, 2 off, 0 default)
   g_force_cfg = force_cfg % 100; g_force_ck = force_ck; g_ablate = force_cfg / 1000;
+  g_bf16_force_ck16 = force_ck == 16;     // shared with the fp32 chunk override: tools/bench_kernels.py --ck 16 moves the bf16 kernels too
   const int dma = (force_cfg / 100) % 10;
   if (dma) g_conv_dma = (dma == 1);
 }
