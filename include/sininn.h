@@ -35,7 +35,7 @@ extern "C" {
 int sininn_version(void);
 const char* sininn_last_error(void);
 /* sizeof() of descriptor struct `which` as THIS library was compiled: 0 sininn_conv_args, 1 sininn_wgrad_item,
- * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args, 7 sininn_flownet_args; 0 for an unknown index.  A binding written in
+ * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args, 7 sininn_flownet_args, 8 sininn_lamb_args; 0 for an unknown index.  A binding written in
  * another language (the ctypes mirrors in sin-inn_amd/_lib.py) checks its own layout against it at load time (ABI v4). */
 size_t sininn_sizeof(int which);
 /* A HIP stream at an explicit priority (lower number = higher priority; range from sininn_stream_priority_range: `least` is the
@@ -713,6 +713,52 @@ int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
 size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LAMB, the optimiser of the flow trainer (video-interpolation/trainer.py:134-135: apex.optimizers.FusedLAMB(params, lr=lr)),
+ * restated from apex/optimizers/fused_lamb.py and its multi_tensor_lamb stages 1 and 2 (csrc/lamb.hip).  fp32.
+ * One step, t = step (from 1), gs = grad_scale:
+ *   G      = sqrt( sum over ALL tensors of ALL param groups of (gs*g)^2 )        -- one global norm
+ *   clip   = G / max_grad_norm  if G > max_grad_norm  else 1                      -- max_grad_norm <= 0: clip = 1
+ *   bc1,bc2 = 1 - beta1^t, 1 - beta2^t   (both 1 if not bias_correction; computed on the host in double, as 1 - beta1 and 1 - beta2 are)
+ *   beta3  = 1 - beta1 if grad_averaging else 1
+ *   per element:  sg = gs*g / clip
+ *                 m  = beta1*m + beta3*sg ;   v = beta2*v + (1-beta2)*sg*sg
+ *                 adam_w_mode:      u = (m/bc1) / (sqrt(v/bc2) + eps) + wd*p
+ *                 not adam_w_mode:  sg += wd*p before m, v ;  u = (m/bc1) / (sqrt(v/bc2) + eps)
+ *   per tensor:   pn = ||p||_2 (before the step),  un = ||u||_2
+ *                 ratio = lr * pn/un   if (use_nvlamb or wd != 0) and pn != 0 and un != 0   else lr
+ *                 p -= ratio * u
+ * g is read only (apex overwrites it with u; here u has a buffer of its own).
+ * Layout: one param group = flat buffers p, g, m, v, u of n floats (n % 4 == 0); tensor k occupies [tensor_offsets[k],
+ *   tensor_offsets[k] + numel_k), every offset a multiple of 4, tensor_offsets[n_tensors] = n; the padding between tensors belongs to
+ *   no tensor, is never read or written and enters no norm.  `chunks` is a DEVICE table [n_chunks][3] of int64 (tensor, begin, len),
+ *   sorted, begin % 4 == 0, a chunk never crosses a tensor; `tensor_offsets` a DEVICE table of n_tensors + 1 int64.  A chunk that does
+ *   not lie inside its tensor and inside n is skipped by the kernels.
+ * Sums are per-chunk partials in the workspace, added in chunk-index order: no floating-point atomics, results independent of the
+ *   grid size, two calls from the same state bitwise equal.  Nothing is read back: G, clip and the ratios stay on the device.
+ * Several param groups share `norm_slots` (DEVICE, n_groups floats): sininn_lamb_grad_norm writes slot `group` with this group's
+ *   sum of (gs*g)^2 (two launches); sininn_lamb_step reads all n_groups slots, so call grad_norm for EVERY group before step for any.
+ *   sininn_lamb_step is three launches: stage 1 (m, v, u, partials of p^2 and u^2), one block per tensor for the ratio, stage 2.
+ * Workspace: sininn_lamb_workspace_bytes(n_chunks, n_tensors) bytes, 16-byte aligned; its first n_tensors floats are the trust
+ *   ratios of the last step (diagnostic).  Every extent is checked before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sininn_lamb_args {
+  size_t struct_bytes;                       /* must be sizeof(sininn_lamb_args)                                              */
+  float* p; const float* g; float* m; float* v; float* u;   /* n floats each, 16-byte aligned                                */
+  int64_t n;
+  const int64_t* chunks; int64_t n_chunks;
+  const int64_t* tensor_offsets; int n_tensors;
+  double lr, beta1, beta2, eps, weight_decay, max_grad_norm, grad_scale;   /* the kernels compute with their fp32 images; 1 - beta1,
+                                                1 - beta2, the bias corrections and lr * pn/un are formed in double first   */
+  int step;                                  /* >= 1                                                                          */
+  int bias_correction, adam_w_mode, grad_averaging, use_nvlamb;
+  float* norm_slots; int group, n_groups;
+  void* workspace; size_t workspace_bytes;
+} sininn_lamb_args;
+size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
+int sininn_lamb_grad_norm(const sininn_lamb_args* args, void* stream);
+int sininn_lamb_step(const sininn_lamb_args* args, void* stream);
 
 #ifdef __cplusplus
 }

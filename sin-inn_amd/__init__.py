@@ -6,7 +6,7 @@ hyphen).  Everything numerical runs in ``libsininn.so`` (hand-written HIP, C ABI
 from . import _lib, ops                                                     # noqa: F401
 from .modules import GLOWCouplingBlock, IRevNetDownsampling, PermuteRandom   # noqa: F401
 from .framework import InputNode, Node, OutputNode, ReversibleGraphNet      # noqa: F401
-from .optim import FusedAdam                                                 # noqa: F401
+from .optim import FusedAdam, FusedLAMB                                      # noqa: F401
 from . import irn                                                             # noqa: F401
 from . import functional                                                     # noqa: F401
 from . import flowloss                                                       # noqa: F401
@@ -14,4 +14,4 @@ from . import flownet                                                        # n
 from . import progressive                                                    # noqa: F401
 
 __all__ = ['GLOWCouplingBlock', 'IRevNetDownsampling', 'PermuteRandom', 'InputNode', 'Node', 'OutputNode',
-           'ReversibleGraphNet', 'FusedAdam', 'functional', 'ops']
+           'ReversibleGraphNet', 'FusedAdam', 'FusedLAMB', 'functional', 'ops']

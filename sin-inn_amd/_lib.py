@@ -124,6 +124,22 @@ class FlowNetArgs(C.Structure):
         self.struct_bytes = C.sizeof(FlowNetArgs)
 
 
+class LambArgs(C.Structure):
+    """Mirror of sininn_lamb_args."""
+    _fields_ = [('struct_bytes', C.c_size_t),
+                ('p', c_f), ('g', c_f), ('m', c_f), ('v', c_f), ('u', c_f), ('n', C.c_int64),
+                ('chunks', C.c_void_p), ('n_chunks', C.c_int64), ('tensor_offsets', C.c_void_p), ('n_tensors', C.c_int),
+                ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double), ('weight_decay', C.c_double),
+                ('max_grad_norm', C.c_double), ('grad_scale', C.c_double), ('step', C.c_int),
+                ('bias_correction', C.c_int), ('adam_w_mode', C.c_int), ('grad_averaging', C.c_int), ('use_nvlamb', C.c_int),
+                ('norm_slots', c_f), ('group', C.c_int), ('n_groups', C.c_int),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(LambArgs)
+
+
 class PackDesc(C.Structure):
     """Mirror of sininn_pack_desc."""
     _fields_ = [('w', c_f), ('bias', c_f), ('N', C.c_int), ('Cin', C.c_int), ('ksize', C.c_int), ('colmap', c_i),
@@ -255,6 +271,9 @@ _SIGS = {
     'sininn_flownet_backward_encgrad': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, C.c_void_p]),
+    'sininn_lamb_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'sininn_lamb_grad_norm': (C.c_int, [C.POINTER(LambArgs), C.c_void_p]),
+    'sininn_lamb_step': (C.c_int, [C.POINTER(LambArgs), C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)
@@ -275,7 +294,7 @@ def lib():
         if handle.sininn_version() != 4:
             raise ImportError('libsininn.so ABI version mismatch')
         for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc, DenseBf16Args,
-                                        FlowNetArgs)):
+                                        FlowNetArgs, LambArgs)):
             if handle.sininn_sizeof(which) != C.sizeof(mirror):
                 raise ImportError(f'{mirror.__name__}: the ctypes mirror has {C.sizeof(mirror)} bytes, libsininn.so was built '
                                   f'with {handle.sininn_sizeof(which)} (include/sininn.h changed without _lib.py)')

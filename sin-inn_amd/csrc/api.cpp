@@ -125,6 +125,9 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
 size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a);
 int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
+size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
+int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st);
+int lamb_step_launch(const sininn_lamb_args* a, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -247,6 +250,7 @@ size_t sininn_sizeof(int which) {
     case 5: return sizeof(sininn_pack_desc);
     case 6: return sizeof(sininn_dense_bf16_args);
     case 7: return sizeof(sininn_flownet_args);
+    case 8: return sizeof(sininn_lamb_args);
     default: return 0;
   }
 }
@@ -576,5 +580,9 @@ int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_en
                                     void* stream) {
   return flownet_backward_encgrad_launch(args, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
 }
+
+size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors) { return lamb_workspace_bytes(n_chunks, n_tensors); }
+int sininn_lamb_grad_norm(const sininn_lamb_args* args, void* stream) { return lamb_grad_norm_launch(args, ST(stream)); }
+int sininn_lamb_step(const sininn_lamb_args* args, void* stream) { return lamb_step_launch(args, ST(stream)); }
 
 }  // extern "C"

@@ -401,3 +401,16 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=
         assert t.is_contiguous() and t.numel() == p.numel()
     check(_lib.lib().sininn_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay,
                                       step, grad_scale, _stream()))
+
+
+def lamb_workspace_bytes(n_chunks, n_tensors):
+    return _lib.lib().sininn_lamb_workspace_bytes(n_chunks, n_tensors)
+
+
+def lamb_grad_norm(args):
+    """this group's sum of (grad_scale * g)^2 -> its norm slot (args: a filled _lib.LambArgs); every group before any lamb_step"""
+    check(_lib.lib().sininn_lamb_grad_norm(C.byref(args), _stream()))
+
+
+def lamb_step(args):
+    check(_lib.lib().sininn_lamb_step(C.byref(args), _stream()))

@@ -1,9 +1,13 @@
 """Fit a flow-field network to one synthetic frame pair: flow_fields -> warp / softmax splatting / L1 / census / smoothness
--> backward -> FusedAdam, the training step of video-interpolation/trainer.py:47-87 on this project's kernels.
+-> backward -> FusedAdam or FusedLAMB, the training step of video-interpolation/trainer.py:47-87 on this project's kernels.
 
     python tools/fit_flow.py --net RBF --height 64 --width 96 --steps 60
     python tools/fit_flow.py --net PRBF --max-iteration 1000
     python tools/fit_flow.py --net RFF
+    python tools/fit_flow.py --optimizer lamb
+
+`--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
+(trainer.py:134-135); the default stays FusedAdam.
 
 A progressive network (PRBF, PFF, PUFF, PRFF) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
 video-interpolation/main.py:136-143 does, and the controller sees the loss after every step (trainer.py:75), which opens the mask.
@@ -76,9 +80,9 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
 
 
 def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None, max_iteration=1000,
-        info=None):
+        info=None, optimizer='adam'):
     """returns the list of per-step losses (floats); `info`: a dict that receives the network (the controller of a progressive one)"""
-    from sin_inn_amd import FusedAdam, flowloss as FL, flownet, progressive
+    from sin_inn_amd import FusedAdam, FusedLAMB, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
     nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}
@@ -87,7 +91,8 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
     if info is not None:
         info['net'] = net
-    opt = FusedAdam(net.parameters(), lr=lr)
+    assert optimizer in ('adam', 'lamb'), optimizer
+    opt = (FusedLAMB if optimizer == 'lamb' else FusedAdam)(net.parameters(), lr=lr)
     frame1, frame2, _ = make_pair(h, w, seed + 1, device)
     times = torch.zeros(1, device=device)
     l1, census, smooth = FL.L1Loss(1.0), FL.CensusLoss(0.1, max_distance=3), FL.BilateralSmooth(0.1, 'gauss', 150, 1)
@@ -128,8 +133,10 @@ def main():
     ap.add_argument('--lr', type=float, default=1e-3)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--composed', action='store_true')
+    ap.add_argument('--optimizer', default='adam', choices=['adam', 'lamb'])
     a = ap.parse_args()
-    losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration)
+    losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration,
+                 optimizer=a.optimizer)
     print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
 
 
