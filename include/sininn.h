@@ -760,6 +760,39 @@ size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
 int sininn_lamb_grad_norm(const sininn_lamb_args* args, void* stream);
 int sininn_lamb_step(const sininn_lamb_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The flow trainer's step beyond the losses (video-interpolation/trainer.py:47-132; csrc/flowtrain.hip).  fp32 tensors, NCHW.
+ * Every reduction is a per-block partial in a caller-provided buffer, combined by one wave in a fixed order: no floating-point
+ * atomics, two calls bitwise equal, the buffers need no initialisation.  Every extent is checked before anything is launched.
+ *
+ * End-point error (trainer.py:58, 97, 110):  out[0] = mean over (n, y, x) of sqrt((flow[n,0] - gt[n,0])^2 + (flow[n,1] - gt[n,1])^2).
+ *   `flow` is read in place from a larger tensor: sample n starts at flow + n * flow_sample_stride (floats, >= 2 h w), its two channel
+ *   planes are contiguous -- channels 0..1 or 2..3 of the (t, 4, h, w) tensor of the flow network, stride 4 h w.  `gt` is a contiguous
+ *   (n, 2, h, w).  Per pixel fp32, each operation rounded once; the sum is carried in double; the mean is rounded to fp32 once and
+ *   stays on the device.  `partials`: DEVICE doubles, at least the count returned for (n, h, w) by the _partials call.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t sininn_flow_epe_partials(int n, int h, int w);
+int sininn_flow_epe(const float* flow, int64_t flow_sample_stride, const float* gt, int n, int h, int w, double* partials,
+                    int64_t n_partials, float* out, void* stream);
+/* out[n,c,y,x] = mask[n, c % mask_channels, y, x] * (splat[n,c,y,x] != 0)   (trainer.py:64, 68): c = 3, mask_channels 1 or 3; -0.0
+ * counts as zero; the product is formed, so it is bitwise what torch's `mask * (splat != 0)` gives.  Not differentiable, as in the
+ * reference. */
+int sininn_splat_mask(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, void* stream);
+/* flow2img (my_utils/flow_viz.py:6-77) for a batch: flow (n, 2, h, w) fp32 -> img (n, 3, h, w) bytes.  Per frame:
+ *   u, v = clip(flow, -clip, clip), both 0 where |u| or |v| > 1e7 (those pixels come out black)
+ *   maxrad = max(-1, max sqrt(u^2 + v^2))        fp32, as numpy evaluates it on the fp32 array; a NaN anywhere in the frame gives -1
+ *                                                (Python's max(-1, nan))
+ *   u, v = u / maxrad (fp32) + 2.220446049250313e-16 (float64 from here on); NaN pixels -> u = v = 0 and a black pixel
+ *          (this is the whole frame when maxrad == 0)
+ *   rad = sqrt(u^2 + v^2);  fk = (atan2(-v, -u) / pi + 1) / 2 * 54 + 1;  k0 = floor(fk);  k1 = k0 + 1, 56 -> 1;  f = fk - k0
+ *   col = (1 - f) wheel[k0 - 1] / 255 + f wheel[k1 - 1] / 255;  rad <= 1: col = 1 - rad (1 - col), else col *= 0.75
+ *   img = floor(255 col)
+ * `wheel`: DEVICE [55][3] doubles, the Middlebury colour wheel (make_color_wheel), built by the caller.  `workspace`: DEVICE floats,
+ * at least the count returned for (n, h, w) by the _workspace_floats call; n <= 65535. */
+int64_t sininn_flow2img_workspace_floats(int n, int h, int w);
+int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
+                    int64_t workspace_floats, uint8_t* img, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

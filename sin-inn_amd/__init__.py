@@ -12,6 +12,8 @@ from . import functional                                                     # n
 from . import flowloss                                                       # noqa: F401
 from . import flownet                                                        # noqa: F401
 from . import progressive                                                    # noqa: F401
+from . import flowdata                                                       # noqa: F401
+from . import flowtrainer                                                    # noqa: F401
 
 __all__ = ['GLOWCouplingBlock', 'IRevNetDownsampling', 'PermuteRandom', 'InputNode', 'Node', 'OutputNode',
            'ReversibleGraphNet', 'FusedAdam', 'FusedLAMB', 'functional', 'ops']

@@ -274,6 +274,12 @@ _SIGS = {
     'sininn_lamb_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
     'sininn_lamb_grad_norm': (C.c_int, [C.POINTER(LambArgs), C.c_void_p]),
     'sininn_lamb_step': (C.c_int, [C.POINTER(LambArgs), C.c_void_p]),
+    'sininn_flow_epe_partials': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'sininn_flow_epe': (C.c_int, [c_f, C.c_int64, c_f, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, c_f, C.c_void_p]),
+    'sininn_splat_mask': (C.c_int, [c_f, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int, c_f, C.c_void_p]),
+    'sininn_flow2img_workspace_floats': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'sininn_flow2img': (C.c_int, [c_f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, c_f, C.c_int64, C.c_void_p,
+                                  C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -128,6 +128,13 @@ int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a
 size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
 int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st);
 int lamb_step_launch(const sininn_lamb_args* a, hipStream_t st);
+int64_t flow_epe_partials(int n, int h, int w);
+int flow_epe_launch(const float* flow, int64_t flow_sample_stride, const float* gt, int n, int h, int w, double* partials,
+                    int64_t n_partials, float* out, hipStream_t st);
+int splat_mask_launch(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, hipStream_t st);
+int64_t flow2img_workspace_floats(int n, int h, int w);
+int flow2img_launch(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
+                    int64_t workspace_floats, uint8_t* img, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -584,5 +591,19 @@ int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_en
 size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors) { return lamb_workspace_bytes(n_chunks, n_tensors); }
 int sininn_lamb_grad_norm(const sininn_lamb_args* args, void* stream) { return lamb_grad_norm_launch(args, ST(stream)); }
 int sininn_lamb_step(const sininn_lamb_args* args, void* stream) { return lamb_step_launch(args, ST(stream)); }
+
+int64_t sininn_flow_epe_partials(int n, int h, int w) { return flow_epe_partials(n, h, w); }
+int sininn_flow_epe(const float* flow, int64_t flow_sample_stride, const float* gt, int n, int h, int w, double* partials,
+                    int64_t n_partials, float* out, void* stream) {
+  return flow_epe_launch(flow, flow_sample_stride, gt, n, h, w, partials, n_partials, out, ST(stream));
+}
+int sininn_splat_mask(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, void* stream) {
+  return splat_mask_launch(mask, mask_channels, splat, n, c, h, w, out, ST(stream));
+}
+int64_t sininn_flow2img_workspace_floats(int n, int h, int w) { return flow2img_workspace_floats(n, h, w); }
+int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
+                    int64_t workspace_floats, uint8_t* img, void* stream) {
+  return flow2img_launch(flow, n, h, w, clip, wheel, wheel_rows, workspace, workspace_floats, img, ST(stream));
+}
 
 }  // extern "C"

@@ -30,7 +30,8 @@ or grad mode off, the plain backward / inference path runs and nothing extra is 
 Out of scope: `siren`, `RBFG` / `PRBFG`, `PE` / `PPE` (the reference's
 PositionalEncoding.forward raises on any input, model.py:332), `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
 spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
-grid; `FixedSpatialController`; `AdaptiveController`), Sintel / .flo IO.  The optimiser: these modules expose ordinary nn.Parameters;
+grid; `FixedSpatialController`; `AdaptiveController`).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
+`sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
 `sin_inn_amd.FusedLAMB` is the reference's apex FusedLAMB (trainer.py:134-135) restated, `sin_inn_amd.FusedAdam` drives them as well.
 """
 import ctypes as C

@@ -1,0 +1,321 @@
+"""FlowTrainer, the training / validation / test step of the flow path (video-interpolation/trainer.py:15-135), on this project's
+kernels: the flow-field network (`flownet.flow_fields`), the photometric losses (`flowloss`), the Resample2d warp
+(`functional.flow_warp_l1`), FusedLAMB, and three operators of csrc/flowtrain.hip that take the place of chains of small torch
+launches on strided views (the end-point error, `mask * (splat != 0)`) and of a per-frame trip to the host (flow2img).
+
+    flow_epe / splat_mask / flow2img / make_color_wheel   trainer.py:58, 64, 68; my_utils/flow_viz.py:6-127
+    FlowTrainer                                            trainer.py:15-135
+
+The step makes no host round trip of its own.  The two it inherits: `LinearControllerEarly.stash_iteration` reads the loss
+(progressive networks only, as in the reference), and the flow scale of a batch is read once per frame size (it is a constant of
+the data set, `W / 5`) and cached.
+
+Differences from the reference, all on purpose:
+  * `train/PSNR` is not logged.  The reference logs torchmetrics' `PSNR()` with no data range, which infers the range from the
+    targets it has seen so far; torchmetrics is not installed here and that running range cannot be pinned.
+  * `train/loss_epoch` is logged beside `train/loss`: the mean over the epoch so far (what Lightning's `on_epoch=True` records).
+  * `train/ssim` is logged whenever `--loss-ssim` is non-zero; the reference tests the loss VALUE, which reads it back.
+  * wandb is replaced by the FileLogger of `sin_inn_amd.lightning`; the flow and occlusion videos are always written as GIFs under
+    results/ (with PIL; the reference uses imageio, and only when there is no logger), and the test EPE is printed and logged as
+    `test/EPE`.
+  * on resume the controller of a progressive network gets its `iteration`, `cur_block` and `next_block` back (`on_load_checkpoint`);
+    the reference restores the mask alone and restarts the schedule.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, flowloss as FL, flownet
+from .functional import flow_warp_l1
+from .lightning import LightningModule, load_checkpoint
+from .ops import _stream, ptr
+from .optim import FusedLAMB
+
+check = _lib.check
+
+
+def make_color_wheel():
+    """flow_viz.py:80-127: the Middlebury colour wheel, 55 x 3 float64 in 0..255.  Six segments (RY, YG, GC, CB, BM, MR) of 15, 6,
+    4, 11, 13 and 6 colours; within a segment one channel stays at 255 while another ramps up as floor(255 i / len) or down as
+    255 - floor(255 i / len)."""
+    segments = ((15, 0, 1, True), (6, 1, 0, False), (4, 1, 2, True), (11, 2, 1, False), (13, 2, 0, True), (6, 0, 2, False))
+    wheel = np.zeros((sum(s[0] for s in segments), 3))
+    row = 0
+    for length, full, ramp, rising in segments:
+        steps = np.floor(255 * np.arange(length) / length)
+        wheel[row:row + length, full] = 255
+        wheel[row:row + length, ramp] = steps if rising else 255 - steps
+        row += length
+    return wheel
+
+
+_WHEELS = {}
+
+
+def _wheel(device):
+    if device not in _WHEELS:
+        _WHEELS[device] = torch.from_numpy(make_color_wheel()).to(device)
+    return _WHEELS[device]
+
+
+def _gpu32(t):
+    if not t.is_cuda:
+        raise NotImplementedError('sin-inn_amd flow-trainer operators run on the GPU only (got a CPU tensor)')
+    assert t.dtype == torch.float32, 'fp32 tensors expected'
+    return t
+
+
+def flow_epe(flow, gt, partials=None):
+    """mean over (n, y, x) of |flow - gt|_2 (trainer.py:58, 97, 110) as a 0-d device tensor.  `flow` (n, 2, h, w) may be a channel
+    slice of the (n, 4, h, w) tensor `flow_fields` returns: it is read in place through its sample stride.  `partials`: optional
+    float64 device buffer of at least `sininn_flow_epe_partials(n, h, w)` values (allocated here otherwise; needs no
+    initialisation)."""
+    flow, gt = _gpu32(flow.detach()), _gpu32(gt.detach()).contiguous()
+    n, two, h, w = flow.shape
+    assert two == 2 and gt.shape == flow.shape, 'flow_epe expects two (n, 2, h, w) tensors'
+    if flow.stride()[1:] != (h * w, w, 1) or flow.stride(0) < 2 * h * w:
+        flow = flow.contiguous()
+    need = _lib.lib().sininn_flow_epe_partials(n, h, w)
+    if partials is None:
+        partials = torch.empty(max(need, 1), device=flow.device, dtype=torch.float64)
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous()
+    out = torch.empty(1, device=flow.device, dtype=torch.float32)
+    check(_lib.lib().sininn_flow_epe(ptr(flow), flow.stride(0), ptr(gt), n, h, w, C.c_void_p(partials.data_ptr()), partials.numel(),
+                                     ptr(out), _stream()))
+    return out[0]
+
+
+def splat_mask(mask, splat):
+    """mask * (splat != 0) (trainer.py:64, 68): `splat` (n, 3, h, w), `mask` (n, 1, h, w) or (n, 3, h, w), float or bool.  No
+    gradient, as in the reference (the comparison cuts the graph and the occlusion masks carry none)."""
+    splat = _gpu32(splat.detach()).contiguous()
+    mask = _gpu32(mask.detach().to(torch.float32)).contiguous()
+    n, c, h, w = splat.shape
+    assert mask.dim() == 4 and mask.shape[0] == n and tuple(mask.shape[2:]) == (h, w), 'splat_mask: mask and splat disagree'
+    out = torch.empty_like(splat)
+    check(_lib.lib().sininn_splat_mask(ptr(mask), mask.shape[1], ptr(splat), n, c, h, w, ptr(out), _stream()))
+    return out
+
+
+def flow2img(flow, clip=10):
+    """flow_viz.py:6-32 for a batch: (n, 2, h, w) fp32 on the device -> (n, 3, h, w) uint8 on the device; a single (2, h, w) flow
+    gives (3, h, w).  Each frame is normalised by its own maximum radius."""
+    single = flow.dim() == 3
+    flow = _gpu32(flow.detach())
+    flow = (flow[None] if single else flow).contiguous()
+    n, two, h, w = flow.shape
+    assert two == 2, 'flow2img expects (n, 2, h, w)'
+    wheel = _wheel(flow.device)
+    ws = torch.empty(max(_lib.lib().sininn_flow2img_workspace_floats(n, h, w), 1), device=flow.device, dtype=torch.float32)
+    img = torch.empty((n, 3, h, w), device=flow.device, dtype=torch.uint8)
+    check(_lib.lib().sininn_flow2img(ptr(flow), n, h, w, float(clip), C.c_void_p(wheel.data_ptr()), wheel.shape[0], ptr(ws),
+                                     ws.numel(), C.c_void_p(img.data_ptr()), _stream()))
+    return img[0] if single else img
+
+
+def save_gif(filename, frames, fps=4):
+    """(n, h, w, c) uint8, c = 1 or 3 -> an animated GIF (imageio.mimsave(..., format='GIF', fps=4) in the reference)"""
+    from PIL import Image
+    frames = np.asarray(frames)
+    images = [Image.fromarray(f[:, :, 0] if f.shape[2] == 1 else f) for f in frames]
+    images[0].save(filename, format='GIF', save_all=True, append_images=images[1:], duration=int(1000 / fps), loop=0)
+
+
+class FlowTrainer(LightningModule):
+    """trainer.py:15-135.  `args` is the namespace of video-interpolation/main.py with `args.net` the network (a model of
+    `sin_inn_amd.flownet` or a controller of `sin_inn_amd.progressive` around one)."""
+
+    def __init__(self, args, test_tag=None):
+        super().__init__()
+        self.args = args
+        self.net = args.net
+        self.lr = self.args.lr
+
+        self.occlusion = None
+        if args.occl == 'brox':
+            self.occlusion = FL.occlusion_brox
+        elif args.occl == 'wang':
+            self.occlusion = FL.occlusion_wang
+        self.l1 = FL.L1Loss(args.loss_l1)
+        self.census = FL.CensusLoss(args.loss_census, max_distance=args.census_width)
+        self.ssim = FL.SSIMLoss(args.loss_ssim)
+        self.smooth1 = FL.BilateralSmooth(args.loss_smooth1, args.edge_func, args.edge_constant, 1)
+
+        self.test_tag = test_tag
+        self.completed_training = False
+        self.hparams = {k: v for k, v in vars(args).items() if k != 'net'}
+        self._scales = {}
+        self._ones = {}
+        self._epoch_means = {}
+        self.fused = True                    # False: the torch expressions of the three flowtrain operators (tools/bench_flowtrainer.py)
+
+    # ---- the pieces of the step ----
+
+    def _scale(self, scale, frame):
+        """the flow scale of the batch as a Python float (flow_fields bakes it into the kernel's arguments): read from the batch
+        once per frame size -- it is `W / 5` of the data set"""
+        if not torch.is_tensor(scale):
+            return float(scale)
+        key = tuple(frame.shape[-2:])
+        if key not in self._scales:
+            self._scales[key] = float(scale.reshape(-1)[0])
+        return self._scales[key]
+
+    def forward(self, F, T, scale):
+        """trainer.py:37-45: (flow12, flow21), each (t, 2, h, w), at the times T on the pixel grid of the frames F"""
+        _, _, h, w = F.shape
+        return flownet.flow_fields(self.net, T.to(torch.float32), h, w, self._scale(scale, F))
+
+    def _epe(self, flow, gt):
+        if self.fused:
+            return flow_epe(flow, gt)
+        return torch.sum((flow - gt) ** 2, dim=1).sqrt().mean().detach()
+
+    def _splat_mask(self, mask, splat):
+        if self.fused:
+            return splat_mask(mask, splat)
+        return mask * (splat != 0)
+
+    def _no_occlusion(self, frame):
+        """the reference's `torch.ones(2)` placeholders as an all-ones (n, 1, h, w) mask"""
+        key = (frame.shape[0],) + tuple(frame.shape[-2:]) + (frame.device,)
+        if key not in self._ones:
+            self._ones[key] = torch.ones(frame.shape[0], 1, *frame.shape[-2:], device=frame.device)
+        return self._ones[key]
+
+    def log(self, name, value, on_step=True, on_epoch=False, batch_size=1, **_):
+        """on_epoch without on_step (the EPEs): the mean over the epoch so far, weighted by batch size, kept on the device"""
+        if on_epoch and not on_step and torch.is_tensor(value):
+            total, count = self._epoch_means.get(name, (0.0, 0))
+            total, count = total + value.detach() * batch_size, count + batch_size
+            self._epoch_means[name] = (total, count)
+            value = total / count
+        super().log(name, value)
+
+    def _new_epoch(self, prefix):
+        for name in [k for k in self._epoch_means if k.startswith(prefix)]:
+            del self._epoch_means[name]
+
+    def losses(self, frame1, frame2, flow12, flow21):
+        """trainer.py:50-74 after the network: the masks, the two splats and the four loss terms.  Returns
+        (l1, census, ssim, smooth, (mask1, mask2, softmax1, softmax2))."""
+        if self.occlusion:
+            mask1 = self.occlusion(flow12, flow21, self.args.occl_thresh)
+            mask2 = self.occlusion(flow21, flow12, self.args.occl_thresh)
+        else:
+            mask1 = mask2 = self._no_occlusion(frame1)
+        _, metric = flow_warp_l1(frame1, flow21, frame2)
+        softmax1 = FL.FunctionSoftsplat(frame2, flow21, -20 * metric, strType='softmax')
+        mask1 = self._splat_mask(mask1, softmax1)
+        _, metric = flow_warp_l1(frame2, flow12, frame1)
+        softmax2 = FL.FunctionSoftsplat(frame1, flow12, -20 * metric, strType='softmax')
+        mask2 = self._splat_mask(mask2, softmax2)
+
+        l1_loss = self.l1(softmax1, frame1, mask1) + self.l1(softmax2, frame2, mask2)
+        census_loss = self.census(softmax1, frame1, mask1) + self.census(softmax2, frame2, mask2)
+        ssim_loss = self.ssim(softmax1, frame1, mask1) + self.ssim(softmax2, frame2, mask2)
+        smooth_loss = self.smooth1(frame1, flow12) + self.smooth1(frame2, flow21)
+        return l1_loss, census_loss, ssim_loss, smooth_loss, (mask1, mask2, softmax1, softmax2)
+
+    # ---- the LightningModule surface ----
+
+    def training_step(self, batch, batch_idx):
+        """trainer.py:47-87.  `batch`: (frame1, frame2, times, scale) and, with ground truth, the flow from frame1 to frame2."""
+        frame1, frame2, times, scale = batch[:4]
+        if batch_idx == 0:
+            self._new_epoch('train/')
+        flow12, flow21 = self.forward(frame1, times, scale)
+        if len(batch) == 5:
+            self.log('train/EPE', self._epe(flow12, batch[-1]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])
+        flow12, flow21 = flow12.contiguous(), flow21.contiguous()
+        l1_loss, census_loss, ssim_loss, smooth_loss, _ = self.losses(frame1, frame2, flow12, flow21)
+        loss = l1_loss + census_loss + ssim_loss + smooth_loss
+        self.net.stash_iteration(loss.detach())
+
+        self.log('train/loss', loss)
+        self.log('train/loss_epoch', loss, on_step=False, on_epoch=True, batch_size=frame1.shape[0])
+        self.log('train/l1', l1_loss)
+        self.log('train/census', census_loss)
+        if self.ssim.weight != 0:
+            self.log('train/ssim', ssim_loss)
+        self.log('train/smooth', smooth_loss)
+        return loss
+
+    def on_train_end(self):
+        self.completed_training = True
+
+    def validation_step(self, batch, batch_idx):
+        """trainer.py:93-98"""
+        frame1, _, times, scale = batch[:4]
+        if batch_idx == 0:
+            self._new_epoch('val/')
+        flow_fw, _ = self.forward(frame1, times, scale)
+        self.log('val/EPE', self._epe(flow_fw, batch[4]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])
+
+    def test_step(self, batch, batch_idx):
+        """trainer.py:100-112: the colour-coded forward flow (uint8, on the device), the occlusion mask as 0 / 255 bytes (host)
+        and, with ground truth, the batch's EPE"""
+        frame1, _, times, scale = batch[:4]
+        flow_fw, flow_bw = self.forward(frame1, times, scale)
+        out = {'flow': flow2img(flow_fw)}
+        if self.occlusion:
+            out['mask'] = (self.occlusion(flow_fw, flow_bw, self.args.occl_thresh).type(torch.uint8) * 255).cpu()
+        if len(batch) == 5:
+            out['epe'] = self._epe(flow_fw, batch[-1])
+        return out
+
+    def test_epoch_end(self, outputs):
+        """trainer.py:114-132: results/flow_<tag>_epe_<epe:.3f>.gif (and results/occl_<tag>.gif); returns the mean EPE"""
+        epe = torch.stack([seq['epe'] for seq in outputs]).mean().item() if 'epe' in outputs[0] else 0
+        flows = torch.cat([seq['flow'] for seq in outputs], dim=0)
+        os.makedirs('results', exist_ok=True)
+        save_gif(f'results/flow_{self.test_tag}_epe_{epe:.3f}.gif', flows.permute(0, 2, 3, 1).cpu().numpy())
+        if self.occlusion:
+            masks = torch.cat([seq['mask'] for seq in outputs], dim=0)
+            save_gif(f'results/occl_{self.test_tag}.gif', masks.permute(0, 2, 3, 1).numpy())
+        print(f'test/EPE {epe:.6f}')
+        if self.logger:
+            self.logger.log_metrics({'test/EPE': epe, 'epoch': self.current_epoch}, getattr(self.trainer, 'global_step', 0))
+        return epe
+
+    def configure_optimizers(self):
+        return FusedLAMB(self.net.parameters(), lr=self.lr)
+
+    # ---- checkpoints ----
+
+    def load_state_dict(self, state_dict, strict=True):
+        """nn.Module's loader fills `net.mask_stashed` without calling the controller's own load_state_dict: rebuild the mask here"""
+        out = super().load_state_dict(state_dict, strict)
+        if hasattr(self.net, 'load_mask'):
+            with torch.no_grad():
+                self.net.load_mask()
+        return out
+
+    def on_load_checkpoint(self, checkpoint):
+        """Resume the controller's schedule: one `stash_iteration` per step, so `iteration` is the checkpoint's global step; the
+        blocks opened so far are the whole blocks inside floor(mask_stashed), but never ahead of the schedule (a fully ramped
+        block counts as open in the sum half a period before the controller moves on)."""
+        net = self.net
+        if not hasattr(net, 'cur_block'):
+            return
+        net.iteration = int(checkpoint.get('global_step', 0))
+        bs, dim = net.block_size, net.encoding_dim
+        opened = int(torch.floor(net.mask_stashed.reshape(-1)[0]))
+        scheduled = bs * (1 + min(net.iteration, net.progress_iterations) // max(net.block_iterations, 1))
+        cur = dim if opened >= dim else max(bs, min(opened // bs * bs, scheduled))
+        nxt = min(cur + bs, dim)
+        if dim - nxt < bs:
+            nxt = dim
+        net.cur_block, net.next_block = cur, nxt
+        print(f'resumed: iteration {net.iteration}, controller cur_block {net.cur_block} / {dim}')
+
+    @classmethod
+    def load_from_checkpoint(cls, checkpoint_path, args, test_tag=None, map_location=None):
+        """pl.LightningModule.load_from_checkpoint as main.py:88, 117 uses it"""
+        model = cls(args, test_tag=test_tag)
+        ck = load_checkpoint(checkpoint_path, map_location=map_location or 'cpu')
+        model.load_state_dict(ck['state_dict'])
+        model.on_load_checkpoint(ck)
+        return model

@@ -5,6 +5,13 @@ is provided here: ``LightningModule`` (optimizers / manual_backward / log / save
 ``LightningDataModule``, ``Trainer.fit`` (epoch loop, validation every n epochs, checkpoint every ``period``
 epochs, resume), ``ModelCheckpoint`` and a file logger in place of WandbLogger.
 
+The flow trainer (video-interpolation/trainer.py, main.py:52-93) uses three more pieces: automatic optimisation (its
+``training_step`` returns the loss and leaves zero_grad / backward / step to the trainer), ``Trainer.test`` with
+``test_step`` / ``test_epoch_end`` over ``test_dataloader()``, and the ``on_train_end`` / ``on_load_checkpoint`` hooks.  The
+automatic path runs only for a module whose ``automatic_optimization`` is true AND whose ``training_step`` returned a tensor
+that requires grad; the INN wrapper sets ``automatic_optimization = False`` (lit_wrapper.py) and has neither hook, so its
+path through the loop is what it was.
+
 Data parallel: under ``torchrun`` every rank runs the same loop on its shard of each batch; the optimizer proxy
 averages the flat gradient buffer with ONE all-reduce (RCCL) right before ``step()``.
 """
@@ -46,6 +53,14 @@ class LightningModule(nn.Module):
     def device(self):
         return next(self.parameters()).device
 
+    @property
+    def logger(self):
+        return getattr(self.trainer, 'logger', None)
+
+    @property
+    def current_epoch(self):
+        return getattr(self.trainer, 'current_epoch', 0)
+
     def attach_optimizer(self, optimizer=None):
         """Use the module without Trainer.fit (bench.py, tests): builds the optimizer proxy."""
         tr = Trainer.__new__(Trainer)
@@ -60,6 +75,9 @@ class LightningDataModule:
         raise NotImplementedError
 
     def val_dataloader(self):
+        return None
+
+    def test_dataloader(self):
         return None
 
 
@@ -250,7 +268,7 @@ def load_checkpoint(path, map_location=None, trust=False):
 class Trainer:
     def __init__(self, gpus=None, max_epochs=1000, check_val_every_n_epoch=1, default_root_dir='.', logger=None,
                  resume_from_checkpoint=None, callbacks=(), auto_lr_find=False, auto_scale_batch_size=False,
-                 log_every_n_steps=50, trust_checkpoint=False, **_):
+                 log_every_n_steps=50, trust_checkpoint=False, accelerator=None, **_):
         # auto_lr_find / auto_scale_batch_size are inert in the reference as well (trainer.tune() is never
         # called, main.py:108-109)
         self.gpus = list(gpus) if isinstance(gpus, (list, tuple)) else ([gpus] if gpus is not None else [0])
@@ -259,10 +277,13 @@ class Trainer:
         self.ckpt = next((c for c in callbacks if isinstance(c, ModelCheckpoint)), None)
         self.log_every = log_every_n_steps
         self.trust_checkpoint = bool(trust_checkpoint)
+        self.accelerator = accelerator       # 'cpu': run the loop on the host (toy modules in tests); None: a GPU, as before
         self.optimizer = None
         self.current_epoch, self.global_step = 0, 0
 
     def _device(self):
+        if getattr(self, 'accelerator', None) == 'cpu':
+            return torch.device('cpu')
         rank, ws = sdist.init_from_env()
         if ws > 1:
             return torch.device('cuda', sdist.local_device_index())
@@ -303,6 +324,8 @@ class Trainer:
                 self.optimizer.load_state_dict(ck['optimizer_states'][0])
             self.current_epoch = int(ck.get('epoch', -1)) + 1
             self.global_step = int(ck.get('global_step', 0))
+            if hasattr(model, 'on_load_checkpoint'):
+                model.on_load_checkpoint(ck)
         _, ws = sdist.world()
         if ws > 1:   # identical initial weights on every rank
             sdist.broadcast_([p.data for p in model.parameters()])
@@ -310,11 +333,17 @@ class Trainer:
         val_loader = datamodule.val_dataloader()
         ckpt_dir = (self.ckpt.dirpath if self.ckpt and self.ckpt.dirpath else os.path.join(self.root, 'checkpoints'))
         t0 = time.time()
+        # automatic optimisation (the flow trainer): the module is asked once, the returned value on every step
+        automatic = bool(getattr(model, 'automatic_optimization', False))
         for epoch in range(self.current_epoch, self.max_epochs):
             self.current_epoch = epoch
             model.train()
             for i, batch in enumerate(train_loader):
-                model.training_step(_to_device(batch, device), i)
+                out = model.training_step(_to_device(batch, device), i)
+                if automatic and torch.is_tensor(out) and out.requires_grad:
+                    self.optimizer.zero_grad()
+                    out.backward()
+                    self.optimizer.step()
                 self.global_step += 1
                 if self.logger is not None and self.global_step % self.log_every == 0:
                     self._flush(model)
@@ -326,7 +355,22 @@ class Trainer:
                 self._flush(model, extra={'epoch': epoch, 'wall_s': time.time() - t0})
             if self.ckpt is not None and (epoch + 1) % self.ckpt.period == 0:
                 self.save_checkpoint(model, os.path.join(ckpt_dir, f'epoch={epoch}.ckpt'))
+        if hasattr(model, 'on_train_end'):
+            model.on_train_end()
         return model
+
+    def test(self, model, datamodule):
+        """pl.Trainer.test as the flow trainer uses it (main.py:80, 90): test_step over test_dataloader() under no_grad, then
+        test_epoch_end(outputs); returns what test_epoch_end returns"""
+        device = self._device()
+        model.to(device)
+        model.trainer = self
+        model.eval()
+        outputs = []
+        with torch.no_grad():
+            for i, batch in enumerate(datamodule.test_dataloader()):
+                outputs.append(model.test_step(_to_device(batch, device), i))
+            return model.test_epoch_end(outputs)
 
     def _flush(self, model, extra=None):
         if self.logger is None:

@@ -1,0 +1,87 @@
+"""Time one step of the flow trainer: FlowTrainer.training_step + zero_grad / backward / FusedLAMB step, at the reference's
+`--batch 3 --size 436` on SyntheticClip(frames, 436, 1024), with device events, after a warm-up, over windows of at least --seconds
+(the window method of tools/bench_flownet.py); one JSON line.
+
+    python tools/bench_flowtrainer.py [--net RBF] [--batch 3] [--height 436] [--width 1024]
+
+Three paths run in alternating windows in one process:
+    fused     the step as FlowTrainer runs it
+    torch     the same step with the three operators of csrc/flowtrain.hip (end-point error, mask * (splat != 0)) replaced by their
+              torch expressions (FlowTrainer.fused = False); flow2img is not part of a training step
+    network   flow_fields forward + backward alone on the same grid, with a random upstream gradient: the share of the step that is
+              the network
+A progressive net runs under LinearControllerEarly(net, 5000): the controller reads the loss on every step, as in the reference.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'tools')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from bench_flownet import window  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF'])
+    ap.add_argument('--frames', type=int, default=4)
+    ap.add_argument('--batch', type=int, default=3)
+    ap.add_argument('--height', type=int, default=436)
+    ap.add_argument('--width', type=int, default=1024)
+    ap.add_argument('--loss-ssim', type=float, default=0.0)
+    ap.add_argument('--seconds', type=float, default=1.0)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--rounds', type=int, default=2)
+    a = ap.parse_args()
+    from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
+    dev = torch.device('cuda', 0)
+    torch.manual_seed(0)
+    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}[a.net](flownet.ModelParams())
+    if net.is_progressive:
+        net = progressive.LinearControllerEarly(net, 5000, epsilon=1e-3)
+    args = argparse.Namespace(lr=1e-4, loss_l1=1, loss_census=0.1, loss_ssim=a.loss_ssim, census_width=3, loss_smooth1=0.1,
+                              edge_constant=150, edge_func='gauss', occl='wang', occl_thresh=0.7, net=net)
+    model = flowtrainer.FlowTrainer(args).to(dev)
+    opt = model.attach_optimizer()
+    clip = flowdata.SyntheticClip(a.frames, a.height, a.width)
+    assert a.batch <= len(clip)
+    batch = [clip.video[:a.batch].to(dev), clip.video[1:a.batch + 1].to(dev), clip.T[:a.batch].to(dev),
+             torch.tensor([clip.flow_scale] * a.batch, dtype=torch.float64).to(dev), clip.flow[:a.batch].to(dev)]
+    up = torch.randn(a.batch, 4, a.height, a.width, device=dev)
+
+    def step(fused):
+        def run():
+            model.fused = fused
+            opt.zero_grad()
+            model.training_step(batch, 0).backward()
+            opt.step()
+        return run
+
+    def network():
+        opt.zero_grad()
+        f12, f21 = model(batch[0], batch[2], batch[3])
+        torch.autograd.backward([f12, f21], [up[:, :2], up[:, 2:]])
+
+    todo = {'fused': step(True), 'torch': step(False), 'network': network}
+    res = {k: [] for k in todo}
+    for _ in range(a.rounds):
+        for k, fn in todo.items():
+            res[k].append(window(fn, a.seconds, a.warmup))
+    out = dict(net=a.net, batch=a.batch, height=a.height, width=a.width, loss_ssim=a.loss_ssim, points=a.batch * a.height * a.width)
+    for k in res:
+        meds = [w['median_ms'] for w in res[k]]
+        out[f'{k}_ms'] = round(min(meds), 4)
+        out[f'{k}_ms_windows'] = [round(m, 4) for m in meds]
+    out['network_share'] = round(out['network_ms'] / out['fused_ms'], 3)
+    out['fused_over_torch'] = round(out['fused_ms'] / out['torch_ms'], 4)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,223 @@
+"""Command line of the flow path, MI355X build: the operations and flags of the reference's video-interpolation/main.py:17-49,
+driving `sin_inn_amd.flowtrainer.FlowTrainer`.
+
+    python video-interpolation/main.py train --input-video <sintel scene folder> --batch 3 --epochs 5000
+    python video-interpolation/main.py train --synthetic 8 436 1024 --batch 3 --epochs 2
+    python video-interpolation/main.py test | summarize | sintel ...
+
+Differences from the reference, all to make the path runnable here:
+  * the trainer, checkpoint callback and logger come from `sin_inn_amd.lightning` (pytorch_lightning and wandb are not installed):
+    `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
+  * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
+  * `--net` takes the eight networks of `sin_inn_amd.flownet`; `siren`, `RBFG`, `PRBFG`, `PE`, `PPE`, `MPFF` and
+    `--spatially-adaptive` exit with a message (flownet.py lists them as out of scope);
+  * `--ngpus N` is N devices (cuda:0 .. cuda:N-1, the first is used), as in Lightning, not a device index;
+  * a video file as `--input-video` (imageio + RAFT) is refused;
+  * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)`, which is 0 below 112 epochs, and the
+    reference then divides by it; here such a short run opens one block per step;
+  * checkpoints are written every max(epochs // 100, 1) epochs (the reference's `every_n_epochs=0` below 100 epochs writes none)
+    whenever `--wandb` is given, `test` and `sintel` load the newest one, and `train` resumes from it.
+"""
+import argparse
+import os
+import os.path as path
+import sys
+from glob import glob
+
+ROOT = path.dirname(path.dirname(path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF')
+OUT_OF_SCOPE_NETWORKS = ('siren', 'RBFG', 'PRBFG', 'PE', 'PPE', 'MPFF')
+
+
+def get_parser():
+    parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    parser.add_argument('operation', choices=['train', 'test', 'summarize', 'sintel'])
+    parser.add_argument('--ngpus', default=1, type=int)
+    # Data options
+    parser.add_argument('--input-video', default='../datasets/sintel/training/final/alley_1')
+    parser.add_argument('--name', default='temp')
+    parser.add_argument('--end', type=int)
+    parser.add_argument('--step', type=int)
+    parser.add_argument('--size', default=436, type=int)
+    parser.add_argument('--batch', default=1, type=int)
+    parser.add_argument('--test-size', default=436, type=int)
+    parser.add_argument('--test-batch', default=1, type=int)
+    parser.add_argument('--synthetic', nargs=3, type=int, metavar=('T', 'H', 'W'),
+                        help='train / test on a synthetic clip of T frames of H x W instead of --input-video')
+    # Network options
+    parser.add_argument('--net', default='RBF')
+    parser.add_argument('--spatially-adaptive', action='store_true')
+    # Train options
+    parser.add_argument('--epochs', default=1000, type=int)
+    parser.add_argument('--val-iter', type=int)
+    parser.add_argument('--lr', default=1e-4, type=float)
+    parser.add_argument('--loss-l1', default=1, type=float)
+    parser.add_argument('--loss-census', default=0.1, type=float)
+    parser.add_argument('--loss-ssim', default=0, type=float)
+    parser.add_argument('--census-width', default=3, type=int)
+    parser.add_argument('--loss-smooth1', default=0.1, type=float)
+    parser.add_argument('--edge-constant', default=150, type=float)
+    parser.add_argument('--edge-func', default='gauss', choices=['exp', 'gauss'])
+    parser.add_argument('--occl', default='wang', choices=['brox', 'wang', 'None', None],
+                        help="'None' on the command line stands for the reference's None (no occlusion masks)")
+    parser.add_argument('--occl-thresh', default=0.7, type=float)
+    # Logging options
+    parser.add_argument('--wandb', help='any name: selects the JSON-lines FileLogger and checkpointing')
+    parser.add_argument('--log-gt', action='store_true')
+    return parser
+
+
+def get_args(argv=None):
+    """the parsed arguments; exits (status 2, with the limitation named) on a network or controller this project does not have"""
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    if args.occl == 'None':                                    # argparse cannot produce the reference's `None` choice from a string
+        args.occl = None
+    if args.spatially_adaptive:
+        parser.error('--spatially-adaptive is out of scope: StashedSpatialController needs a per-point mask, the fused kernels '
+                     'take one global mask (sin_inn_amd/flownet.py)')
+    if args.net in OUT_OF_SCOPE_NETWORKS:
+        parser.error(f'--net {args.net} is out of scope: the fused kernels are built for {", ".join(NETWORKS)} '
+                     '(sin_inn_amd/flownet.py)')
+    if args.net not in NETWORKS:
+        parser.error(f'--net {args.net}: unknown network; choose from {", ".join(NETWORKS)}')
+    return args
+
+
+def build_net(args):
+    """main.py:136-143: the network, and LinearControllerEarly around a progressive one.  `args.net` is the network's name on the
+    first call; main() replaces it with the module, as the reference does, and keeps the name in `args.net_name`."""
+    from sin_inn_amd import flownet, progressive
+    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}
+    if isinstance(args.net, str):
+        args.net_name = args.net
+    net = nets[args.net_name](flownet.ModelParams())
+    if net.is_progressive:
+        net = progressive.LinearControllerEarly(net, args.epochs, epsilon=1e-3)
+        if net.block_iterations == 0:                          # fewer than 112 epochs: the reference divides by zero here
+            net.block_iterations = 1
+            net.progress_iterations = (net.encoding_dim - net.block_size) // net.block_size
+    return net
+
+
+def _devices(args):
+    return list(range(max(args.ngpus, 1)))
+
+
+def _latest_ckpt(scene, name):
+    """the newest checkpoint of a run (main.py:86-87); raises like the reference if there is none"""
+    return max(glob(path.join('checkpoints', scene, name, '*.ckpt')), key=path.getmtime)
+
+
+def train_model(args):
+    """main.py:52-80"""
+    import torch
+    from sin_inn_amd.flowdata import get_video
+    from sin_inn_amd.flowtrainer import FlowTrainer, flow2img, save_gif
+    from sin_inn_amd.lightning import FileLogger, ModelCheckpoint, Trainer
+    video, scene = get_video(args.input_video, args)
+    dataset = video.testset
+    if not args.val_iter:
+        args.val_iter = args.epochs + 1
+
+    logger, latest_ckpt, clbks = None, None, []
+    if args.wandb:
+        logger = FileLogger(project=args.wandb, name=f'{scene}_{args.name}')
+        logger.log_hyperparams(argparse.Namespace(**{k: v for k, v in vars(args).items() if k != 'net'}))
+        ckpt_dir = path.join('checkpoints', scene, args.name)
+        clbks = [ModelCheckpoint(period=max(args.epochs // 100, 1), dirpath=ckpt_dir)]
+        latest_ckpt = max(glob(path.join(ckpt_dir, '*.ckpt')), default=None, key=path.getmtime)
+    if args.log_gt:                                            # the reference uploads two videos; here they are GIFs
+        os.makedirs('results', exist_ok=True)
+        save_gif(f'results/source_{scene}_{args.name}.gif', (dataset.video * 255).type(torch.uint8).permute(0, 2, 3, 1).numpy())
+        if dataset.gt_available:
+            save_gif(f'results/gt_flow_{scene}_{args.name}.gif', flow2img(dataset.flow.cuda()).permute(0, 2, 3, 1).cpu().numpy())
+
+    model = FlowTrainer(args, test_tag=f'{scene}_{args.name}')
+    steps_per_epoch = max(len(video.train_dataloader()), 1)
+    trainer = Trainer(gpus=_devices(args), logger=logger, max_epochs=args.epochs, callbacks=clbks,
+                      resume_from_checkpoint=latest_ckpt, check_val_every_n_epoch=args.val_iter,
+                      log_every_n_steps=steps_per_epoch)
+    if latest_ckpt:
+        print(f'resuming from {latest_ckpt}')
+    trainer.fit(model, video)
+    if model.completed_training:
+        trainer.test(model, video)
+
+
+def test_model(args):
+    """main.py:83-93"""
+    from sin_inn_amd.flowdata import get_video
+    from sin_inn_amd.flowtrainer import FlowTrainer
+    from sin_inn_amd.lightning import FileLogger, Trainer
+    video, scene = get_video(args.input_video, args)
+    unique_name = f'{scene}_{args.name}'
+    latest_ckpt = _latest_ckpt(scene, args.name)
+    model = FlowTrainer.load_from_checkpoint(latest_ckpt, args=args, test_tag=unique_name)
+    logger = FileLogger(project=args.wandb, name=unique_name) if args.wandb else None
+    trainer = Trainer(gpus=_devices(args), logger=logger)
+    trainer.test(model, video)
+    flow_files = [path.join('results', f) for f in os.listdir('results') if f.startswith(f'flow_{unique_name}_epe')]
+    return flow_files, len(video.testset)
+
+
+def summarize_model(args):
+    """main.py:96-106: the frame-weighted mean EPE over every scene beside --input-video"""
+    root = path.dirname(args.input_video)
+    epe_accum, frame_accum = 0, 0
+    for scene in sorted(os.listdir(root)):
+        args.input_video = path.join(root, scene)
+        args.net = build_net(args)
+        files, num_frames = test_model(args)
+        assert len(files) == 1
+        epe = float(path.splitext(files[0])[0].split('_')[-1])
+        epe_accum += epe * num_frames
+        frame_accum += num_frames
+    print(f'Normalized AEPE: {epe_accum / frame_accum}')
+
+
+def write_scene_flows(model, testset, outdir, device):
+    """main.py:123-130: frame_%04d.flo of the forward flow of every pair, evaluated one pair at a time"""
+    import torch
+    from sin_inn_amd.flowdata import writeFlow
+    os.makedirs(outdir, exist_ok=True)
+    files = []
+    with torch.no_grad():
+        for i in range(len(testset)):
+            f1, _, t, s = testset[i][:4]
+            f1, t = f1.to(device).unsqueeze(0), t.to(device).unsqueeze(0)
+            flow, _ = model(f1, t, s)
+            files.append(path.join(outdir, f'frame_{i + 1:04d}.flo'))
+            writeFlow(files[-1], flow.squeeze(0).permute(1, 2, 0).cpu().numpy())
+    return files
+
+
+def sintel_submission(args):
+    """main.py:109-130: sintel_submission/<clean | final>/<scene>/frame_%04d.flo for every scene beside --input-video; the pass is
+    `clean` if --name ends in it, else `final` (the reference fails on a name that ends in neither).  With --synthetic the one
+    synthetic scene is written."""
+    import torch
+    from sin_inn_amd.flowdata import get_video
+    from sin_inn_amd.flowtrainer import FlowTrainer
+    device = torch.device('cuda', _devices(args)[0])
+    sintel_pass = 'clean' if args.name.endswith('clean') else 'final'
+    scenes = [None] if args.synthetic else sorted(os.listdir(path.dirname(args.input_video)))
+    for entry in scenes:
+        video, scene = get_video(args.input_video if entry is None else path.join(path.dirname(args.input_video), entry), args)
+        args.net = build_net(args)
+        model = FlowTrainer.load_from_checkpoint(_latest_ckpt(scene, args.name), args=args)
+        model.to(device)
+        write_scene_flows(model, video.testset, path.join('sintel_submission', sintel_pass, scene), device)
+
+
+def main(argv=None):
+    args = get_args(argv)
+    args.net = build_net(args)
+    {'train': train_model, 'test': test_model, 'summarize': summarize_model, 'sintel': sintel_submission}[args.operation](args)
+
+
+if __name__ == '__main__':
+    main()
