@@ -107,7 +107,10 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float dt = c.t - cc[3 * j], dy = c.y - cc[3 * j + 1], dx = c.x - cc[3 * j + 2];
-      const float d = dt * dt + dy * dy + dx * dx;
+      // explicit fmaf: left to the compiler, the contraction of this sum differed between the unrolled copies of one call site
+      // (mul, mul, mul, add, add for one point of the forward's four, mul, fma, add for the others), so the same point gave
+      // different bits in different rows of a tile and the weight gradient did not see the forward's encoding
+      const float d = fmaf(dx, dx, fmaf(dy, dy, dt * dt));
       o[j] = expf(-(d * (sg[j] * sg[j])));
     }
   } else {

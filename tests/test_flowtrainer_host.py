@@ -279,3 +279,20 @@ def test_resume_restores_the_controller_schedule():
     dst.load_state_dict(sd)
     dst.on_load_checkpoint({'global_step': 27})
     assert dst.net.cur_block == 18 and dst.net.next_block == 24 and torch.equal(dst.net.mask, args3.net.mask)
+
+
+def test_latest_checkpoint_breaks_equal_times_by_epoch(tmp_path, monkeypatch):
+    """two epochs of a short run can be saved within one tick of the file system's clock; `test`, `sintel` and a resuming `train` must
+    then take the later epoch, whatever order glob lists them in.  A later time still wins over a higher epoch"""
+    m = flow_main()
+    folder = tmp_path / 'checkpoints' / 'scene' / 'run'
+    folder.mkdir(parents=True)
+    for epoch in (10, 9, 6, 7):
+        (folder / f'epoch={epoch}.ckpt').write_bytes(b'')
+        os.utime(folder / f'epoch={epoch}.ckpt', (1000, 1000))
+    monkeypatch.chdir(tmp_path)
+    assert os.path.basename(m._latest_ckpt('scene', 'run')) == 'epoch=10.ckpt'
+    os.utime(folder / 'epoch=6.ckpt', (2000, 2000))
+    assert os.path.basename(m._latest_ckpt('scene', 'run')) == 'epoch=6.ckpt'
+    with pytest.raises(ValueError):
+        m._latest_ckpt('scene', 'none')

@@ -15,8 +15,17 @@ Grids: the fixture's (t = 2, 20 x 28: 17 full tiles and a partial one, fewer til
 controller's first mask (t, y, x, e0, e1, e2 open: the sin of frequency 1 is open and its cos is closed); `mid`, after 100
 iterations (84 leading ones); `ramp`, after 98 iterations (the block in progress stands at 0.5).
 
-Measured on an MI355X (`ratio(...)` lines of a run with -s: error / budget [error, fp32-torch unit]): NOT MEASURED YET -- no run of
-this file on an MI355X has been recorded; DESIGN.md section 14.2 says the same.
+Measured on an MI355X (worst error / budget over nets and masks, from the `ratio(...)` lines of a run with -s: [error, fp32-torch unit]):
+  ragged   flows 0.143 (PRFF ramp) [4.17e-07, 7.28e-07]  gW1 0.0971 (RFF) [4.15e-06, 1.07e-05]  gb1 0.281  gW2 0.0726 [1.62e-06, 5.58e-06]
+           gb2 0.454  gW3 0.0793 [1.53e-06, 4.82e-06]  gb3 0.423  gW4 0.105 [8.21e-07, 1.95e-06]  gb4 0.942 [2.67e-07, 7.07e-08]
+           gF 0.13 (PRFF ones) [3.40e-06, 6.52e-06]  freq.grad 0.232 (RFF) [7.87e-06, 8.50e-06]
+  fixture  flows 0.262 (PRFF init) [3.11e-07, 2.96e-07]  flows vs fixture 0.198  gW1 0.135 (PRFF mid) [4.44e-07, 8.22e-07]  gb1 0.325  gW2 0.113
+           gb2 0.397  gW3 0.0997  gb3 0.575 (PRFF mid) [3.28e-07, 1.43e-07]  gW4 0.168  gb4 0.9 [4.11e-07, 1.14e-07]
+           gF 0.227 (PRFF init) [3.15e-07, 3.46e-07]  freq.grad 0.249 (RFF) [5.33e-06, 5.36e-06]
+  gb4 is the figure of tests/test_gpu_flownet.py: it does not depend on the network.
+  End to end: RFF, the first losses of the fused and the composed loop 0.1364782 / 0.1364782, step 4 within 1.3e-05 relative, final
+  0.0149109 / 0.0165720, frequencies moved by at most 0.0756 / 0.0755; PRFF, the first five losses equal to all printed digits
+  (0.1350149 .. 0.1263025), final 0.0078944 / 0.0079031, frequencies moved by 0.0388 / 0.0384.  20 tests, 5 s.
 """
 import os
 import sys

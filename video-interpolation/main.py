@@ -108,8 +108,12 @@ def _devices(args):
 
 
 def _latest_ckpt(scene, name):
-    """the newest checkpoint of a run (main.py:86-87); raises like the reference if there is none"""
-    return max(glob(path.join('checkpoints', scene, name, '*.ckpt')), key=path.getmtime)
+    """the newest checkpoint of a run (main.py:86-87); raises like the reference if there is none.  Two epochs of a short run can be
+    saved within one tick of the file system's clock: equal times are decided by the epoch in the name, not by the order of glob"""
+    def age(ckpt):
+        epoch = path.basename(ckpt)[len('epoch='):-len('.ckpt')]
+        return path.getmtime(ckpt), int(epoch) if path.basename(ckpt).startswith('epoch=') and epoch.isdigit() else -1
+    return max(glob(path.join('checkpoints', scene, name, '*.ckpt')), key=age)
 
 
 def train_model(args):
