@@ -680,11 +680,17 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
  *   It needs a second workspace of sininn_flownet_encgrad_workspace_bytes(args) bytes (a transposed copy of w[0] and the partial sums; 0
  *   if the encoding is not Fourier), 16-byte aligned, and refuses encoding != SININN_FLOWNET_FOURIER, a null g_enc_a and a short
  *   enc_workspace before any launch.
+ * Radial-basis grid (model.py:369-415 UniformRadialBasisGridEncoding, RbfgModel model.py:508-523, PRBFGModel model.py:614-618): encoding
+ *   SININN_FLOWNET_RBFG, 256 frequencies j with buffers offsets [256][3] (enc_a) and sigma [256] (enc_b), all fp32, p = 2 / sigma_j:
+ *     xa_d = x_d + offsets[j][d], xb_d = xa_d + 1 / sigma_j;  u_d = (v_d mod p) * 2 - p  (v = xa or xb, the remainder in [0, p));
+ *     e(v) = 2 exp(-(sum_d u_d^2) sigma_j^2) - 1;  feature 2 j = e(xa), feature 2 j + 1 = e(xb).
+ *   The buffers are constants: the backward call is sininn_flownet_backward, progressive networks work as above.
  * Borrowed pointers, 16-byte aligned (axis vectors, biases and the mask: 4), the caller's stream, non-zero return + sininn_last_error.
  * sininn_flownet_supported: 1 if the sizes are the ones the kernels are built for, else 0 (callers raise, there is no second path).
  * ---------------------------------------------------------------------------------------------- */
 #define SININN_FLOWNET_RBF 0     /* enc_a = centres [512][3], enc_b = sigma [512]                                  */
 #define SININN_FLOWNET_FOURIER 1 /* enc_a = frequencies [3][256], enc_b unused (FFN and UFF differ in the buffer only) */
+#define SININN_FLOWNET_RBFG 3    /* enc_a = offsets [256][3], enc_b = sigma [256] (2 is not an encoding of this library) */
 typedef struct sininn_flownet_args {
   size_t struct_bytes;                    /* must be sizeof(sininn_flownet_args)                                          */
   int encoding;                           /* SININN_FLOWNET_*                                                             */

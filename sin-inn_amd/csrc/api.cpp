@@ -573,7 +573,7 @@ int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 
 int sininn_flownet_supported(const sininn_flownet_args* a) {
   return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
-         (a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER) && (a->progressive == 0 || a->progressive == 1) &&
+         (a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER || a->encoding == SININN_FLOWNET_RBFG) && (a->progressive == 0 || a->progressive == 1) &&
          a->enc_dim == (a->progressive ? 515 : 512) && a->hidden == 256 &&
          a->layers == 3 && a->out_dim == 4;
 }

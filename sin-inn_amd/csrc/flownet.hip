@@ -3,6 +3,8 @@
 //     poses = meshgrid(times, linspace(-1, 1, h), linspace(-1, 1, w))            N = t h w points of 3 coordinates
 //     enc   = exp(-sigma_k^2 |x - c_k|^2)                       (RBF,  512 centres,      model.py:349-356)
 //           | sin / cos (2 pi x . f_k), interleaved             (FFN / UFF, 256 frequencies, model.py:230-238)
+//           | 2 exp(-sigma_k^2 |((x + o_k [+ 1 / sigma_k]) mod p_k) 2 - p_k|^2) - 1, p_k = 2 / sigma_k, the pair interleaved
+//                                                               (RBFG, 256 frequencies, model.py:375-387)
 //     h1 = relu(enc W1^T + b1)   h2 = relu(h1 W2^T + b2)   h3 = relu(h2 W3^T + b3)   out = h3 W4^T + b4        (model.py:36-43)
 //     flows[t][c][y][x] = out[p][c] * scale                                                                    (trainer.py:44)
 // fp32 on v_mfma_f32_16x16x4_f32.  Neither the N x 3 poses nor the N x 512 encoding exist in memory in either pass: a lane
@@ -112,6 +114,33 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
       // different bits in different rows of a tile and the weight gradient did not see the forward's encoding
       const float d = fmaf(dx, dx, fmaf(dy, dy, dt * dt));
       o[j] = expf(-(d * (sg[j] * sg[j])));
+    }
+  } else if constexpr (KIND == SININN_FLOWNET_RBFG) {
+    const int f = f0 >> 1;                                                 // offsets [256][3], sigma [256]
+    const f32x2* op = reinterpret_cast<const f32x2*>(q.enc_a + 3 * f);
+    const f32x2 o0 = op[0], o1 = op[1], o2 = op[2];
+    const f32x2 sg = *reinterpret_cast<const f32x2*>(q.enc_b + f);
+    const float off[6] = {o0[0], o0[1], o1[0], o1[1], o2[0], o2[1]};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      // one division per frequency: 2 * (1 / sigma) is 2 / sigma to the bit, sigma / 2 is exact
+      const float is = 1.f / sg[u], p = 2.f * is, hp = 0.5f * sg[u], s2 = sg[u] * sg[u];
+      const float xa[3] = {c.t + off[3 * u], c.y + off[3 * u + 1], c.x + off[3 * u + 2]};
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        float w[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const float x = v ? xa[d] + is : xa[d];
+          // Python's remainder, x - floor(x / p) p: the fma rounds once, like fmod's exact result plus p for a negative x.  A
+          // quotient that rounds across an integer leaves r one period off, next to 0 or p, where (2 r - p)^2 is continuous
+          const float r = fmaf(-floorf(x * hp), p, x);
+          w[d] = fmaf(r, 2.f, -p);
+        }
+        // explicit fmaf, as above: the forward and the weight gradient must see the same bits
+        const float d = fmaf(w[2], w[2], fmaf(w[1], w[1], w[0] * w[0]));
+        o[2 * u + v] = fmaf(expf(-(d * s2)), 2.f, -1.f);
+      }
     }
   } else {
     const int f = f0 >> 1;                                                 // frequencies [3][256]
@@ -656,7 +685,7 @@ int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
   SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
                a->struct_bytes, sizeof(sininn_flownet_args));
   SININN_CHECK(sininn_flownet_supported(a),
-               "%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for RBF / Fourier, 512 (progressive: 515) -> 256 x 3 -> 4)",
+               "%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for RBF / Fourier / RBFG, 512 (progressive: 515) -> 256 x 3 -> 4)",
                who, a->encoding, a->enc_dim, a->hidden, a->layers, a->out_dim, a->progressive);
   if (a->progressive) {
     SININN_CHECK(a->mask != nullptr, "%s: progressive network without a mask", who);
@@ -664,7 +693,7 @@ int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
   }
   SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
                who, a->T, a->H, a->W);
-  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding != SININN_FLOWNET_RBF || a->enc_b), "%s: null axis / encoding pointer", who);
+  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding == SININN_FLOWNET_FOURIER || a->enc_b), "%s: null axis / encoding pointer", who);
   SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
   for (int l = 0; l < 4; ++l) {
     SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
@@ -714,7 +743,9 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
     SININN_CHECK(aligned16(a->saved), "flownet_forward: saved must be 16-byte aligned");
     q.saved = a->saved;
   }
-  auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_fwd_kernel<SININN_FLOWNET_RBF> : flownet_fwd_kernel<SININN_FLOWNET_FOURIER>;
+  auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_fwd_kernel<SININN_FLOWNET_RBF>
+           : a->encoding == SININN_FLOWNET_RBFG ? flownet_fwd_kernel<SININN_FLOWNET_RBFG>
+                                                : flownet_fwd_kernel<SININN_FLOWNET_FOURIER>;
   if (a->progressive) {
     SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
                  "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", flownet_forward_workspace_bytes(a),
@@ -727,7 +758,9 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
     q.w[0] = w1p;
     q.wc = wc;
     q.ksteps = (open_encoded(a) + 15) / 16;
-    k = a->encoding == SININN_FLOWNET_RBF ? flownet_fwd_kernel<SININN_FLOWNET_RBF, true> : flownet_fwd_kernel<SININN_FLOWNET_FOURIER, true>;
+    k = a->encoding == SININN_FLOWNET_RBF    ? flownet_fwd_kernel<SININN_FLOWNET_RBF, true>
+        : a->encoding == SININN_FLOWNET_RBFG ? flownet_fwd_kernel<SININN_FLOWNET_RBFG, true>
+                                             : flownet_fwd_kernel<SININN_FLOWNET_FOURIER, true>;
   }
   if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
   const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
@@ -807,7 +840,9 @@ int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws,
   }
   if (a->progressive) {
     // the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate columns)
-    auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true, true> : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true, true>;
+    auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true, true>
+             : a->encoding == SININN_FLOWNET_RBFG ? flownet_wgrad_kernel<SININN_FLOWNET_RBFG, true, true>
+                                                  : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true, true>;
     if (raise_lds(k, FN_WG_LDS_PROG, "flownet_wgrad")) return 1;
     const int nc = wgrad_chunks(q.ntiles, FN_ENC);         // not a function of k_active: the order of every sum stays the same
     const int oe = open_encoded(a);
@@ -818,7 +853,9 @@ int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws,
                        (const float*)q.part, nc, a->mask, ktiles * FN_WT, a->gw[0], a->gb[0]);
     SININN_LAUNCH_CHECK("flownet_reduce");
   } else {
-    auto k = a->encoding == SININN_FLOWNET_RBF ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true> : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true>;
+    auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true>
+             : a->encoding == SININN_FLOWNET_RBFG ? flownet_wgrad_kernel<SININN_FLOWNET_RBFG, true>
+                                                  : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true>;
     if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
     const int nc = wgrad_chunks(q.ntiles, FN_ENC);
     hipLaunchKernelGGL(k, dim3(2 * FN_ENC / FN_WT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)q.dh, (const float*)nullptr);

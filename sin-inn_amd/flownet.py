@@ -4,12 +4,13 @@ backward in libsininn.so (csrc/flownet.hip).
     ModelParams / RbfModel / FFModel / UFFModel / model_dict   video-interpolation/model.py:11-28, 490-505, 418-433, 454-469, 681
     ProgressiveModel / PRBFModel / PFFModel / PUFFModel        video-interpolation/model.py:526-598, 621-625 (progressive_model_dict)
     RotatedFourierFeatures / RFFModel / PRFFModel              video-interpolation/model.py:263-307, 436-451, 586-590 (learnable_model_dict)
+    UniformRadialBasisGridEncoding / RbfgModel / PRBFGModel    video-interpolation/model.py:369-415, 508-523, 614-618 (grid_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
 
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
-`encode.frequencies`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
+`encode.frequencies` / `encode.offsets`, `encode.sigma`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
 first, then the four nn.Linear layers), so one `torch.manual_seed` gives the reference's numbers and a reference checkpoint
-loads.  The encodings of `model_dict` / `progressive_model_dict` are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
+loads.  The encodings of `model_dict` / `progressive_model_dict` / `grid_model_dict` are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
 (3 -> 512 -> 256 x 3 -> 4); any other size raises, there is no second implementation behind this module, and calling a model
 directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512 encoding never exist here.
 
@@ -27,7 +28,13 @@ the backward pass (`sininn_flownet_backward_encgrad`) carries the gradient throu
 summation order, and torch's `normalize` backward takes it to `encode.frequencies.grad`.  With `frequencies.requires_grad` false,
 or grad mode off, the plain backward / inference path runs and nothing extra is computed.
 
-Out of scope: `siren`, `RBFG` / `PRBFG`, `PE` / `PPE` (the reference's
+`RBFG` / `PRBFG` use a periodic grid of Gaussian bumps: 256 frequencies j with buffers `encode.offsets` [256][3] and `encode.sigma`
+[256] (`linspace(0, 12 sqrt(3), 256)` plus half a step), period p = 2 / sigma_j.  Feature 2 j is
+`2 exp(-sigma_j^2 |((x + offsets_j) mod p) 2 - p|^2) - 1`, feature 2 j + 1 the same half a period further
+(`+ 1 / sigma_j`).  Both are buffers, the kernels evaluate them as a third encoding kind and the rest (masks, `k_active`, the
+backward pass) is the path of `RBF` / `PRBF`.
+
+Out of scope: `siren`, `PE` / `PPE` (the reference's
 PositionalEncoding.forward raises on any input, model.py:332), `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
 spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
 grid; `FixedSpatialController`; `AdaptiveController`).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
@@ -46,7 +53,7 @@ from .ops import _stream, ptr
 
 check = _lib.check
 EPSILON = 1e-4
-RBF, FOURIER = 0, 1
+RBF, FOURIER, RBFG = 0, 1, 3
 
 
 class ModelParams:
@@ -177,6 +184,29 @@ class GaussianRotatedFourierFeatures(RotatedFourierFeatures):
         return magnitude
 
 
+class UniformRadialBasisGridEncoding(nn.Module):
+    """model.py:369-415 (buffers only; evaluated inside the kernels).  The one RNG draw is the `rand` of the offsets; `sigma` is
+    ascending as built, the reference's sort leaves it as it is."""
+    kind = RBFG
+
+    def __init__(self, domain_dim, num_frequencies, std):
+        super().__init__()
+        self.domain_dim = domain_dim
+        self.num_frequencies = num_frequencies
+        sigma = torch.linspace(0, std * math.sqrt(3), num_frequencies)
+        sigma = sigma + sigma[1] / 2
+        offsets = (torch.rand(num_frequencies, domain_dim) * 2 - 1) % (2 / sigma[:, None])
+        self.register_buffer('offsets', offsets)
+        self.register_buffer('sigma', sigma.sort()[0])
+
+    @property
+    def output_channels(self):
+        return 2 * self.num_frequencies
+
+    def kernel_buffers(self):
+        return self.offsets, self.sigma
+
+
 class _EncodedMlpModel(nn.Module):
     """model.py:54-103, the part the flow trainer uses."""
     encoding = None
@@ -304,9 +334,26 @@ class PRFFModel(ProgressiveModel):
         return GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
 
 
+class RbfgModel(_EncodedMlpModel):
+    """model.py:508-523."""
+
+    @staticmethod
+    def make_encoding(opt):
+        return UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
+
+
+class PRBFGModel(ProgressiveModel):
+    """model.py:614-618."""
+
+    @staticmethod
+    def get_encoding_layer(opt):
+        return UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
+
+
 model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel}
 progressive_model_dict = {'PRBF': PRBFModel, 'PFF': PFFModel, 'PUFF': PUFFModel}
 learnable_model_dict = {'RFF': RFFModel, 'PRFF': PRFFModel}       # the encoding is trained; PRFF is progressive as well
+grid_model_dict = {'RBFG': RbfgModel, 'PRBFG': PRBFGModel}        # the radial-basis grid; PRBFG is progressive
 
 
 def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):

@@ -7,7 +7,7 @@ FLOP counts come from the shapes (2 N (512*256 + 2*256*256 + 256*4) forward; bac
 the weight gradients of all four); `mfma_peak_share` is those executed FLOPs over the event time against the 157.3 TFLOP/s f32
 matrix peak of an MI355X -- the share of the whole call, not of one kernel.  --baseline times the same module composed from
 torch's own GPU ops (tools/fit_flow.composed_flow_fields) in the same process, alternating windows with the fused path.
-The progressive nets (PRBF, PFF, PUFF) run under a prefix mask of --k-active leading ones (default 515: all ones), given as a
+The progressive nets (PRBF, PFF, PUFF, PRBFG) run under a prefix mask of --k-active leading ones (default 515: all ones), given as a
 host tensor so that the kernels skip the closed features as they do under a controller; the FLOP counts stay those of the full
 network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.
 RFF / PRFF (learnable frequencies) add the data gradient through layer 1 to the step (2 N 512*256 more FLOPs, counted) and the torch ops
@@ -54,7 +54,7 @@ def window(fn, seconds, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG'])
     ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask')
     ap.add_argument('--frames', type=int, default=1)
     ap.add_argument('--height', type=int, default=436)
@@ -69,7 +69,7 @@ def main():
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
-    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}[a.net](flownet.ModelParams()).to(dev)
+    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict}[a.net](flownet.ModelParams()).to(dev)
     prog = net.is_progressive
     target = net
     if prog:

@@ -9,8 +9,8 @@ Differences from the reference, all to make the path runnable here:
   * the trainer, checkpoint callback and logger come from `sin_inn_amd.lightning` (pytorch_lightning and wandb are not installed):
     `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
   * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
-  * `--net` takes the eight networks of `sin_inn_amd.flownet`; `siren`, `RBFG`, `PRBFG`, `PE`, `PPE`, `MPFF` and
-    `--spatially-adaptive` exit with a message (flownet.py lists them as out of scope);
+  * `--net` takes the ten networks of `sin_inn_amd.flownet`; `siren`, `PE`, `PPE`, `MPFF` and `--spatially-adaptive` exit with a
+    message (flownet.py lists them as out of scope);
   * `--ngpus N` is N devices (cuda:0 .. cuda:N-1, the first is used), as in Lightning, not a device index;
   * a video file as `--input-video` (imageio + RAFT) is refused;
   * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)`, which is 0 below 112 epochs, and the
@@ -28,8 +28,8 @@ ROOT = path.dirname(path.dirname(path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF')
-OUT_OF_SCOPE_NETWORKS = ('siren', 'RBFG', 'PRBFG', 'PE', 'PPE', 'MPFF')
+NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG')
+OUT_OF_SCOPE_NETWORKS = ('siren', 'PE', 'PPE', 'MPFF')
 
 
 def get_parser():
@@ -91,7 +91,7 @@ def build_net(args):
     """main.py:136-143: the network, and LinearControllerEarly around a progressive one.  `args.net` is the network's name on the
     first call; main() replaces it with the module, as the reference does, and keeps the name in `args.net_name`."""
     from sin_inn_amd import flownet, progressive
-    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict}
+    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict}
     if isinstance(args.net, str):
         args.net_name = args.net
     net = nets[args.net_name](flownet.ModelParams())
