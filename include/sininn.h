@@ -685,16 +685,27 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
  *     xa_d = x_d + offsets[j][d], xb_d = xa_d + 1 / sigma_j;  u_d = (v_d mod p) * 2 - p  (v = xa or xb, the remainder in [0, p));
  *     e(v) = 2 exp(-(sum_d u_d^2) sigma_j^2) - 1;  feature 2 j = e(xa), feature 2 j + 1 = e(xb).
  *   The buffers are constants: the backward call is sininn_flownet_backward, progressive networks work as above.
+ * Positional encoding (model.py:321-340 PositionalEncoding, PEModel model.py:472-487, PPEModel model.py:607-611): encoding
+ *   SININN_FLOWNET_PE, enc_a = freqs [4] (2^i pi in fp32), enc_b unused, enc_dim = 24 (progressive: 27), w[0] is [256][24] ([256][27]):
+ *     feature 6 f + d = cos(freqs[f] * x_d), feature 6 f + 3 + d = sin(freqs[f] * x_d), f = 0 .. 3, d = 0 .. 2 (t, y, x); the argument is
+ *     one fp32 product, sine and cosine the accurate full-range fp32 functions.
+ *   The reference's forward reshapes through view(-1, 21) and raises unless N is a multiple of 7; where it runs it is this formula, which
+ *   the library evaluates for every N.  Plain PE reads w[0] in place (96-byte rows) and sininn_flownet_forward_workspace_bytes is 0 for it;
+ *   the progressive forward packs mask * w[0] into [256][32] + [256][4] (36864 bytes).  mask has 27 entries, k_active is 0 .. 27; gw[0]
+ *   is [256][24] / [256][27], progressive: an exact +0 where mask[k] is 0 and in an encoded column k >= 3 with k >= k_active; the three
+ *   coordinate columns k < 3 are governed by the mask alone, whatever k_active is (as in the 515-wide networks).  The order of every sum is
+ *   independent of k_active; the backward call is sininn_flownet_backward, workspace and `saved` have the sizes above.
  * Borrowed pointers, 16-byte aligned (axis vectors, biases and the mask: 4), the caller's stream, non-zero return + sininn_last_error.
  * sininn_flownet_supported: 1 if the sizes are the ones the kernels are built for, else 0 (callers raise, there is no second path).
  * ---------------------------------------------------------------------------------------------- */
 #define SININN_FLOWNET_RBF 0     /* enc_a = centres [512][3], enc_b = sigma [512]                                  */
 #define SININN_FLOWNET_FOURIER 1 /* enc_a = frequencies [3][256], enc_b unused (FFN and UFF differ in the buffer only) */
 #define SININN_FLOWNET_RBFG 3    /* enc_a = offsets [256][3], enc_b = sigma [256] (2 is not an encoding of this library) */
+#define SININN_FLOWNET_PE 4      /* enc_a = freqs [4], enc_b unused; enc_dim 24 (progressive: 27)                   */
 typedef struct sininn_flownet_args {
   size_t struct_bytes;                    /* must be sizeof(sininn_flownet_args)                                          */
   int encoding;                           /* SININN_FLOWNET_*                                                             */
-  int enc_dim, hidden, layers, out_dim;   /* 512 (progressive: 515), 256, 3, 4                                            */
+  int enc_dim, hidden, layers, out_dim;   /* 512 (progressive: 515; PE: 24 / 27), 256, 3, 4                               */
   int T, H, W;                            /* N = T H W points, at most 2^22                                               */
   float scale;
   const float *times, *ys, *xs;           /* [T], [H], [W]                                                                */
@@ -707,8 +718,8 @@ typedef struct sininn_flownet_args {
   float* gw[4]; float* gb[4];             /* backward: out                                                                */
   void* workspace; size_t workspace_bytes;/* backward; progressive forward                                                */
   int progressive;                        /* 0, or 1: layer 1 reads cat((t, y, x), enc) * mask                            */
-  int k_active;                           /* progressive: 0 .. 515, every mask entry from this index on is zero           */
-  const float* mask;                      /* progressive: device [515]                                                    */
+  int k_active;                           /* progressive: 0 .. enc_dim, every mask entry from this index on is zero       */
+  const float* mask;                      /* progressive: device [enc_dim]                                                */
 } sininn_flownet_args;
 int sininn_flownet_supported(const sininn_flownet_args* args);
 size_t sininn_flownet_saved_bytes(int64_t n_points);

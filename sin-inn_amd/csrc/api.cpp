@@ -573,8 +573,11 @@ int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 
 int sininn_flownet_supported(const sininn_flownet_args* a) {
   return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
-         (a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER || a->encoding == SININN_FLOWNET_RBFG) && (a->progressive == 0 || a->progressive == 1) &&
-         a->enc_dim == (a->progressive ? 515 : 512) && a->hidden == 256 &&
+         (a->progressive == 0 || a->progressive == 1) &&
+         (((a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER || a->encoding == SININN_FLOWNET_RBFG) &&
+           a->enc_dim == (a->progressive ? 515 : 512)) ||
+          (a->encoding == SININN_FLOWNET_PE && a->enc_dim == (a->progressive ? 27 : 24))) &&
+         a->hidden == 256 &&
          a->layers == 3 && a->out_dim == 4;
 }
 size_t sininn_flownet_saved_bytes(int64_t n_points) { return flownet_saved_bytes(n_points); }

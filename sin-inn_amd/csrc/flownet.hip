@@ -5,6 +5,8 @@
 //           | sin / cos (2 pi x . f_k), interleaved             (FFN / UFF, 256 frequencies, model.py:230-238)
 //           | 2 exp(-sigma_k^2 |((x + o_k [+ 1 / sigma_k]) mod p_k) 2 - p_k|^2) - 1, p_k = 2 / sigma_k, the pair interleaved
 //                                                               (RBFG, 256 frequencies, model.py:375-387)
+//           | cos / sin (freqs_f x_d), feature 6 f + d the cosine, 6 f + 3 + d the sine   (PE, 4 frequencies x 3 coordinates: 24
+//                                                               features, model.py:321-340)
 //     h1 = relu(enc W1^T + b1)   h2 = relu(h1 W2^T + b2)   h3 = relu(h2 W3^T + b3)   out = h3 W4^T + b4        (model.py:36-43)
 //     flows[t][c][y][x] = out[p][c] * scale                                                                    (trainer.py:44)
 // fp32 on v_mfma_f32_16x16x4_f32.  Neither the N x 3 poses nor the N x 512 encoding exist in memory in either pass: a lane
@@ -34,8 +36,16 @@
 //           on the MFMA (16 of 2064 layer-1 MFMAs per wave and tile).  The K loop stops after the last open feature (k_active, from
 //           the host), rounded up to 16: the skipped terms are e * 0, so skipping is exact.  The chain kernel does not see layer 1's
 //           input and is shared.  flownet_wgrad_kernel<.., true, true> adds the three coordinate-weighted column sums of the dh1 tile
-//           next to gb1 and is launched on the open 128-column tiles only; flownet_reduce_prog_kernel scatters the sums into
+//           next to gb1 and is launched on the open 128-column tiles only; flownet_reduce_l1_kernel scatters the sums into
 //           nn.Linear's [256][515] layout, times the mask, exact zeros where the mask is zero.
+//
+// positional encoding (PE / PPE, PEModel model.py:472-487, PPEModel model.py:607-611): layer 1 has 24 (27) inputs.  The K range is padded
+//           to 32, features 24 .. 31 are exact zeros from encode4.  Plain PE reads W1 [256][24] in place (96-byte rows, the 16-byte loads
+//           of columns 24 .. 31 are replaced by zeros), two K steps; PPE packs mask * W1 into [256][32] + [256][4] like the other
+//           progressive networks and runs ceil(open / 16) K steps.  The layer-1 weight gradient is a narrower instantiation of
+//           flownet_wgrad_kernel: a block owns 128 hidden columns x the 32 padded features (a wave 32 x 32), always all of them, so
+//           nothing in it depends on k_active; flownet_reduce_l1_kernel writes nn.Linear's [256][24] / [256][27] layout, for PPE
+//           an exact +0 where the mask is zero or the column lies beyond k_active.
 #include "common.h"
 
 namespace sininn {
@@ -59,6 +69,9 @@ constexpr int FN_PENC = FN_ENC + FN_DOM;
 constexpr int FN_CS = 4;            // floats per row of the packed coordinate columns / of the coordinate tile in LDS
 constexpr size_t FN_WG_LDS_PROG = FN_WG_LDS + (size_t)(FN_P * FN_CS) * sizeof(float);
 constexpr size_t FN_PACK_FLOATS = (size_t)FN_HID * (FN_ENC + FN_CS);
+constexpr int FN_PE_LIVE = 24;      // positional encoding: 4 frequencies x 3 coordinates x (cos, sin)
+constexpr int FN_PE_W = 32;         // ... padded to two 16-feature K steps; features 24 .. 31 are exact zeros
+constexpr size_t FN_PE_PACK_FLOATS = (size_t)FN_HID * (FN_PE_W + FN_CS);
 
 struct FlowNetDev {
   int T, H, W, N, ntiles;
@@ -142,6 +155,21 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
         o[2 * u + v] = fmaf(expf(-(d * s2)), 2.f, -1.f);
       }
     }
+  } else if constexpr (KIND == SININN_FLOWNET_PE) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = f0 + j;                                                // freqs [4]; 6 f + d: cos, 6 f + 3 + d: sin
+      float v = 0.f;
+      if (k < FN_PE_LIVE) {
+        const int f = k / 6, r = k - 6 * f, d = r < 3 ? r : r - 3;
+        const float xd = d == 0 ? c.t : d == 1 ? c.y : c.x;
+        // one rounded product, as torch's einsum makes it, never contracted; the accurate full-range sine and cosine
+        float sn, co;
+        sincosf(__fmul_rn(q.enc_a[f], xd), &sn, &co);
+        v = r < 3 ? co : sn;
+      }
+      o[j] = v;
+    }
   } else {
     const int f = f0 >> 1;                                                 // frequencies [3][256]
     const f32x2 fa = *reinterpret_cast<const f32x2*>(q.enc_a + f);
@@ -176,11 +204,12 @@ __device__ __forceinline__ void gemm_lds(const float* hs, const float* w, int cw
   }
 }
 
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[4][4]) {
+template <int M, int N>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[M][N]) {
 #pragma unroll
-  for (int m = 0; m < 4; ++m)
+  for (int m = 0; m < M; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < N; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
 }
 
 // accumulators -> LDS tile; RELU: + bias, max(., 0)
@@ -209,9 +238,12 @@ __device__ __forceinline__ void copy_tile_out(const float* hs, float* dst, int t
   }
 }
 
-// PROG: q.w[0] is the packed W1p [256][512], q.wc the coordinate columns, q.ksteps the length of the K loop
+// PROG: q.w[0] is the packed W1p [256][512] (PE: [256][32]), q.wc the coordinate columns, q.ksteps the length of the K loop
 template <int KIND, bool PROG = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
+  constexpr bool PE = KIND == SININN_FLOWNET_PE;
+  constexpr int EW = PE ? (PROG ? FN_PE_W : FN_PE_LIVE) : FN_ENC;   // floats per row of q.w[0]
+  constexpr int KSTEPS = (PE ? FN_PE_W : FN_ENC) / 16;
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;
   const int tid = threadIdx.x;
@@ -241,12 +273,15 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
         for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
     }
     // ---- layer 1: the A fragment is generated, never stored ----
-    const int ksteps = PROG ? q.ksteps : FN_ENC / 16;
+    const int ksteps = PROG ? q.ksteps : KSTEPS;
 #pragma unroll 1
     for (int s = 0; s < ksteps; ++s) {
       f32x4 bf[4], af[4];
 #pragma unroll
-      for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const f32x4*>(q.w[0] + (size_t)(cw + 16 * n + li) * FN_ENC + 16 * s + 4 * kq);
+      for (int n = 0; n < 4; ++n) {
+        if (PE && !PROG && 16 * s + 4 * kq >= FN_PE_LIVE) bf[n] = (f32x4){0.f, 0.f, 0.f, 0.f};   // W1 [256][24] has no such columns
+        else bf[n] = *reinterpret_cast<const f32x4*>(q.w[0] + (size_t)(cw + 16 * n + li) * EW + 16 * s + 4 * kq);
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m) af[m] = encode4<KIND>(q, pc[m], 16 * s + 4 * kq);
 #pragma unroll
@@ -302,14 +337,19 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_transpose_kernel(const float*
 }
 
 // progressive: w1p[j][k] = w1[j][3 + k] mask[3 + k] (k < 512), wc[j][c] = w1[j][c] mask[c] (c < 3), wc[j][3] = 0; block = row j.
-// A closed feature gets an exact zero whatever the weight holds.
+// A closed feature gets an exact zero whatever the weight holds.  EW > LIVE (PE: w1 is [256][3 + 24], w1p [256][32]): zeros from LIVE on.
+template <int EW = FN_ENC, int LIVE = FN_ENC>
 __global__ __launch_bounds__(FN_NTHR) void flownet_pack_kernel(const float* w1, const float* mask, float* w1p, float* wc) {
   const int j = blockIdx.x, tid = threadIdx.x;
-  const float* row = w1 + (size_t)j * FN_PENC;
+  const float* row = w1 + (size_t)j * (FN_DOM + LIVE);
 #pragma unroll
-  for (int k = tid; k < FN_ENC; k += FN_NTHR) {
-    const float m = mask[FN_DOM + k];
-    w1p[(size_t)j * FN_ENC + k] = m == 0.f ? 0.f : row[FN_DOM + k] * m;
+  for (int k = tid; k < EW; k += FN_NTHR) {
+    float v = 0.f;
+    if (k < LIVE) {
+      const float m = mask[FN_DOM + k];
+      v = m == 0.f ? 0.f : row[FN_DOM + k] * m;
+    }
+    w1p[(size_t)j * EW + k] = v;
   }
   if (tid < FN_CS) {
     float v = 0.f;
@@ -409,13 +449,18 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
 
 // part[chunk][j][k] = sum over the chunk's point tiles of dh[p][j] in[p][k]  (+ [chunk][256 * KF + j] = sum_p dh[p][j]);
 // grid = (2 * KF / 128 output tiles, chunks); ENC: in = the encoding (KF = 512), else a saved hidden layer (KF = 256).
-// PROG (with ENC): + [chunk][256 * KF + 256 + 4 j + c] = sum_p dh[p][j] coordinate_c[p]; the grid may cover the leading k tiles only
+// PROG (with ENC): + [chunk][256 * KF + 256 + 4 j + c] = sum_p dh[p][j] coordinate_c[p]; the grid may cover the leading k tiles only.
+// NARROW (ENC of the positional encoding): KF = 32, grid = (2, chunks), a block owns 128 x 32 and a wave 32 x 32 of it
 template <int KIND, bool ENC, bool PROG = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q, const float* dh, const float* in) {
   static_assert(ENC || !PROG, "the progressive weight gradient is layer 1's");
-  constexpr int KF = ENC ? FN_ENC : FN_HID;
+  constexpr bool NARROW = ENC && KIND == SININN_FLOWNET_PE;
+  constexpr int KF = ENC ? (NARROW ? FN_PE_W : FN_ENC) : FN_HID;
+  constexpr int KT = NARROW ? FN_PE_W : FN_WT;         // input columns of a block
+  constexpr int MT = NARROW ? 2 : 4, NT = NARROW ? 2 : 4;   // 16 x 16 accumulator tiles of a wave
   constexpr int PSTRIDE = FN_HID * KF + FN_HID + (PROG ? FN_HID * FN_CS : 0);
   constexpr int NU = FN_P * FN_WT / 4 / FN_NTHR;       // 16-byte units per thread and operand tile
+  constexpr int NUB = FN_P * KT / 4 / FN_NTHR;         // ... of the input tile
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const as = fn_smem;                           // [64][FN_WS]: dh tile
   float* const bs = fn_smem + FN_P * FN_WS;            // [64][FN_WS]: input tile
@@ -423,11 +468,11 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
-  const int j0 = (blockIdx.x & 1) * FN_WT, k0 = (blockIdx.x >> 1) * FN_WT;
-  const int jw = (wave & 1) * 64, kw = (wave >> 1) * 64;
+  const int j0 = (blockIdx.x & 1) * FN_WT, k0 = (blockIdx.x >> 1) * KT;
+  const int jw = NARROW ? wave * 32 : (wave & 1) * 64, kw = NARROW ? 0 : (wave >> 1) * 64;
   const int chunk = blockIdx.y, nchunks = gridDim.y;
 
-  f32x4 acc[4][4];
+  f32x4 acc[MT][NT];
   zero_acc(acc);
   float bsum = 0.f;
   float csum[FN_DOM] = {0.f, 0.f, 0.f};
@@ -450,8 +495,11 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
       const int f = tid + FN_NTHR * u;
       const int row = f >> 5, c4 = (f & 31) * 4;
       *reinterpret_cast<f32x4*>(as + row * FN_WS + c4) = va[u];
-      if constexpr (ENC) vb[u] = encode4<KIND>(q, point_coord(q, tile * FN_P + row), k0 + c4);
-      *reinterpret_cast<f32x4*>(bs + row * FN_WS + c4) = vb[u];
+      if (u < NUB) {
+        const int rb = NARROW ? f / (KT / 4) : row, cb = NARROW ? (f % (KT / 4)) * 4 : c4;
+        if constexpr (ENC) vb[u] = encode4<KIND>(q, point_coord(q, tile * FN_P + rb), k0 + cb);
+        *reinterpret_cast<f32x4*>(bs + rb * FN_WS + cb) = vb[u];
+      }
     }
     if constexpr (PROG) {
       if (k0 == 0 && tid < FN_P) {
@@ -485,22 +533,22 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
     }
 #pragma unroll 2
     for (int ks = 0; ks < FN_P / 4; ++ks) {
-      float a[4], b[4];
+      float a[MT], b[NT];
 #pragma unroll
-      for (int m = 0; m < 4; ++m) a[m] = as[(4 * ks + kq) * FN_WS + jw + 16 * m + li];
+      for (int m = 0; m < MT; ++m) a[m] = as[(4 * ks + kq) * FN_WS + jw + 16 * m + li];
 #pragma unroll
-      for (int n = 0; n < 4; ++n) b[n] = bs[(4 * ks + kq) * FN_WS + kw + 16 * n + li];
+      for (int n = 0; n < NT; ++n) b[n] = bs[(4 * ks + kq) * FN_WS + kw + 16 * n + li];
 #pragma unroll
-      for (int m = 0; m < 4; ++m)
+      for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
+        for (int n = 0; n < NT; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
     }
   }
   float* const out = q.part + (size_t)chunk * PSTRIDE;
 #pragma unroll
-  for (int m = 0; m < 4; ++m)
+  for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int n = 0; n < 4; ++n)
+    for (int n = 0; n < NT; ++n)
 #pragma unroll
       for (int r = 0; r < 4; ++r) out[(size_t)(j0 + jw + 16 * m + 4 * kq + r) * KF + k0 + kw + 16 * n + li] = acc[m][n][r];
   if (k0 == 0 && tid < FN_WT) out[FN_HID * KF + j0 + tid] = bsum;
@@ -522,22 +570,28 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* pa
 }
 
 // progressive layer 1: gw [256][515] = mask[k] * sum_c part[c][..] in chunk order (k < 3: the coordinate sums, else encoded column
-// k - 3), an exact zero where the mask is zero or the column lies beyond the `kcols` encoded columns that were computed; gb as above
-__global__ __launch_bounds__(FN_NTHR) void flownet_reduce_prog_kernel(const float* part, int nparts, const float* mask, int kcols, float* gw,
-                                                                      float* gb) {
-  constexpr int NW = FN_HID * FN_PENC;
-  constexpr size_t STRIDE = (size_t)FN_HID * FN_ENC + FN_HID + FN_HID * FN_CS;
+// k - 3), an exact zero where the mask is zero or the column lies beyond the `kcols` encoded columns that were computed; gb as above.
+// EW: columns of a row of the partial sums, LIVE: encoded columns of gw (PE: 32 and 24).  !PROG (PE): gw [256][LIVE], no mask
+template <int EW = FN_ENC, int LIVE = FN_ENC, bool PROG = true>
+__global__ __launch_bounds__(FN_NTHR) void flownet_reduce_l1_kernel(const float* part, int nparts, const float* mask, int kcols, float* gw,
+                                                                    float* gb) {
+  constexpr int DOM = PROG ? FN_DOM : 0;
+  constexpr int WIDTH = DOM + LIVE;
+  constexpr int NW = FN_HID * WIDTH;
+  constexpr size_t STRIDE = (size_t)FN_HID * EW + FN_HID + (PROG ? FN_HID * FN_CS : 0);
   const int i = blockIdx.x * FN_NTHR + threadIdx.x;
   if (i >= NW + FN_HID) return;
   size_t src;
   float m = 1.f;
   if (i < NW) {
-    const int j = i / FN_PENC, k = i - j * FN_PENC;
-    m = mask[k];
-    if (m == 0.f || k - FN_DOM >= kcols) { gw[i] = 0.f; return; }
-    src = k < FN_DOM ? (size_t)FN_HID * FN_ENC + FN_HID + j * FN_CS + k : (size_t)j * FN_ENC + (k - FN_DOM);
+    const int j = i / WIDTH, k = i - j * WIDTH;
+    if constexpr (PROG) {
+      m = mask[k];
+      if (m == 0.f || k - DOM >= kcols) { gw[i] = 0.f; return; }
+    }
+    src = k < DOM ? (size_t)FN_HID * EW + FN_HID + j * FN_CS + k : (size_t)j * EW + (k - DOM);
   } else {
-    src = (size_t)FN_HID * FN_ENC + (i - NW);
+    src = (size_t)FN_HID * EW + (i - NW);
   }
   float s = 0.f;
   for (int c = 0; c < nparts; ++c) s += part[c * STRIDE + src];
@@ -656,6 +710,8 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_enc_kernel(const float
   g[i] = s * FN_TWO_PI;
 }
 
+constexpr int FN_PE_CHUNK_KF = 128;   // wgrad_chunks' width for the narrow layer 1: 2 output tiles x 256 chunks = 512 blocks
+
 int wgrad_chunks(int ntiles, int kf) {
   const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 for layer 1
   return ntiles < want ? ntiles : want;
@@ -666,6 +722,7 @@ int chain_blocks(int ntiles) { return ntiles < FN_CHAIN_MAX_BLOCKS ? ntiles : FN
 size_t part_floats(int ntiles) {
   size_t a = (size_t)wgrad_chunks(ntiles, FN_HID) * (FN_HID * FN_HID + FN_HID);
   const size_t b = (size_t)wgrad_chunks(ntiles, FN_ENC) * (FN_HID * FN_ENC + FN_HID + FN_HID * FN_CS);   // progressive layer 1
+  // the positional encoding's layer 1 (FN_PE_CHUNK_KF: up to 256 chunks of 256 * 32 + 256 + 1024 floats) is below `a` for every ntiles
   const size_t c = (size_t)chain_blocks(ntiles) * (FN_OUT * FN_HID + FN_OUT);
   a = a > b ? a : b;
   return a > c ? a : c;
@@ -685,15 +742,15 @@ int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
   SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
                a->struct_bytes, sizeof(sininn_flownet_args));
   SININN_CHECK(sininn_flownet_supported(a),
-               "%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for RBF / Fourier / RBFG, 512 (progressive: 515) -> 256 x 3 -> 4)",
+               "%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for RBF / Fourier / RBFG, 512 (progressive: 515), or PE, 24 (progressive: 27), -> 256 x 3 -> 4)",
                who, a->encoding, a->enc_dim, a->hidden, a->layers, a->out_dim, a->progressive);
   if (a->progressive) {
     SININN_CHECK(a->mask != nullptr, "%s: progressive network without a mask", who);
-    SININN_CHECK(a->k_active >= 0 && a->k_active <= FN_PENC, "%s: k_active %d (0 .. %d)", who, a->k_active, FN_PENC);
+    SININN_CHECK(a->k_active >= 0 && a->k_active <= a->enc_dim, "%s: k_active %d (0 .. %d)", who, a->k_active, a->enc_dim);
   }
   SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
                who, a->T, a->H, a->W);
-  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding == SININN_FLOWNET_FOURIER || a->enc_b), "%s: null axis / encoding pointer", who);
+  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding == SININN_FLOWNET_FOURIER || a->encoding == SININN_FLOWNET_PE || a->enc_b), "%s: null axis / encoding pointer", who);
   SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
   for (int l = 0; l < 4; ++l) {
     SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
@@ -718,7 +775,8 @@ int open_encoded(const sininn_flownet_args* a) { return a->k_active > FN_DOM ? a
 }  // namespace
 
 size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a) {
-  return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) && a->progressive ? FN_PACK_FLOATS * sizeof(float) : 0;
+  if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args) || !a->progressive) return 0;   // plain PE reads W1 in place
+  return (a->encoding == SININN_FLOWNET_PE ? FN_PE_PACK_FLOATS : FN_PACK_FLOATS) * sizeof(float);
 }
 
 size_t flownet_saved_bytes(int64_t n) {
@@ -743,8 +801,10 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
     SININN_CHECK(aligned16(a->saved), "flownet_forward: saved must be 16-byte aligned");
     q.saved = a->saved;
   }
+  const bool pe = a->encoding == SININN_FLOWNET_PE;
   auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_fwd_kernel<SININN_FLOWNET_RBF>
            : a->encoding == SININN_FLOWNET_RBFG ? flownet_fwd_kernel<SININN_FLOWNET_RBFG>
+           : pe                                 ? flownet_fwd_kernel<SININN_FLOWNET_PE>
                                                 : flownet_fwd_kernel<SININN_FLOWNET_FOURIER>;
   if (a->progressive) {
     SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
@@ -752,14 +812,16 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
                  a->workspace ? a->workspace_bytes : (size_t)0);
     SININN_CHECK(aligned16(a->workspace), "flownet_forward: workspace must be 16-byte aligned");
     float* const w1p = static_cast<float*>(a->workspace);
-    float* const wc = w1p + (size_t)FN_HID * FN_ENC;
-    hipLaunchKernelGGL(flownet_pack_kernel, dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
+    float* const wc = w1p + (size_t)FN_HID * (pe ? FN_PE_W : FN_ENC);
+    if (pe) hipLaunchKernelGGL((flownet_pack_kernel<FN_PE_W, FN_PE_LIVE>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
+    else hipLaunchKernelGGL((flownet_pack_kernel<>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
     SININN_LAUNCH_CHECK("flownet_pack");
     q.w[0] = w1p;
     q.wc = wc;
     q.ksteps = (open_encoded(a) + 15) / 16;
     k = a->encoding == SININN_FLOWNET_RBF    ? flownet_fwd_kernel<SININN_FLOWNET_RBF, true>
         : a->encoding == SININN_FLOWNET_RBFG ? flownet_fwd_kernel<SININN_FLOWNET_RBFG, true>
+        : pe                                 ? flownet_fwd_kernel<SININN_FLOWNET_PE, true>
                                              : flownet_fwd_kernel<SININN_FLOWNET_FOURIER, true>;
   }
   if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
@@ -838,7 +900,26 @@ int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws,
     reduce(nc, FN_HID * FN_HID, FN_HID, a->gw[l], a->gb[l]);
     SININN_LAUNCH_CHECK("flownet_reduce");
   }
-  if (a->progressive) {
+  if (a->encoding == SININN_FLOWNET_PE) {
+    // one narrow column tile, always whole; the chunks are not a function of k_active either
+    const int nc = wgrad_chunks(q.ntiles, FN_PE_CHUNK_KF);
+    if (a->progressive) {
+      auto k = flownet_wgrad_kernel<SININN_FLOWNET_PE, true, true>;
+      if (raise_lds(k, FN_WG_LDS_PROG, "flownet_wgrad")) return 1;
+      hipLaunchKernelGGL(k, dim3(2, nc), dim3(FN_NTHR), FN_WG_LDS_PROG, st, q, (const float*)q.dh, (const float*)nullptr);
+      SININN_LAUNCH_CHECK("flownet_wgrad");
+      hipLaunchKernelGGL((flownet_reduce_l1_kernel<FN_PE_W, FN_PE_LIVE, true>), dim3((FN_HID * (FN_DOM + FN_PE_LIVE) + FN_HID + FN_NTHR - 1) / FN_NTHR),
+                         dim3(FN_NTHR), 0, st, (const float*)q.part, nc, a->mask, open_encoded(a), a->gw[0], a->gb[0]);
+    } else {
+      auto k = flownet_wgrad_kernel<SININN_FLOWNET_PE, true>;
+      if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
+      hipLaunchKernelGGL(k, dim3(2, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)q.dh, (const float*)nullptr);
+      SININN_LAUNCH_CHECK("flownet_wgrad");
+      hipLaunchKernelGGL((flownet_reduce_l1_kernel<FN_PE_W, FN_PE_LIVE, false>), dim3((FN_HID * FN_PE_LIVE + FN_HID + FN_NTHR - 1) / FN_NTHR),
+                         dim3(FN_NTHR), 0, st, (const float*)q.part, nc, (const float*)nullptr, FN_PE_LIVE, a->gw[0], a->gb[0]);
+    }
+    SININN_LAUNCH_CHECK("flownet_reduce");
+  } else if (a->progressive) {
     // the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate columns)
     auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true, true>
              : a->encoding == SININN_FLOWNET_RBFG ? flownet_wgrad_kernel<SININN_FLOWNET_RBFG, true, true>
@@ -849,7 +930,7 @@ int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws,
     const int ktiles = oe > 0 ? (oe + FN_WT - 1) / FN_WT : 1;
     hipLaunchKernelGGL(k, dim3(2 * ktiles, nc), dim3(FN_NTHR), FN_WG_LDS_PROG, st, q, (const float*)q.dh, (const float*)nullptr);
     SININN_LAUNCH_CHECK("flownet_wgrad");
-    hipLaunchKernelGGL(flownet_reduce_prog_kernel, dim3((FN_HID * FN_PENC + FN_HID + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st,
+    hipLaunchKernelGGL((flownet_reduce_l1_kernel<>), dim3((FN_HID * FN_PENC + FN_HID + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st,
                        (const float*)q.part, nc, a->mask, ktiles * FN_WT, a->gw[0], a->gb[0]);
     SININN_LAUNCH_CHECK("flownet_reduce");
   } else {

@@ -5,13 +5,14 @@ backward in libsininn.so (csrc/flownet.hip).
     ProgressiveModel / PRBFModel / PFFModel / PUFFModel        video-interpolation/model.py:526-598, 621-625 (progressive_model_dict)
     RotatedFourierFeatures / RFFModel / PRFFModel              video-interpolation/model.py:263-307, 436-451, 586-590 (learnable_model_dict)
     UniformRadialBasisGridEncoding / RbfgModel / PRBFGModel    video-interpolation/model.py:369-415, 508-523, 614-618 (grid_model_dict)
+    PositionalEncoding / PEModel / PPEModel                    video-interpolation/model.py:321-340, 472-487, 607-611 (positional_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
 
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
-`encode.frequencies` / `encode.offsets`, `encode.sigma`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
+`encode.frequencies` / `encode.offsets`, `encode.sigma` / `encode.freqs`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
 first, then the four nn.Linear layers), so one `torch.manual_seed` gives the reference's numbers and a reference checkpoint
 loads.  The encodings of `model_dict` / `progressive_model_dict` / `grid_model_dict` are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
-(3 -> 512 -> 256 x 3 -> 4); any other size raises, there is no second implementation behind this module, and calling a model
+(3 -> 512 -> 256 x 3 -> 4, and 3 -> 24 -> 256 x 3 -> 4 for the positional encoding); any other size raises, there is no second implementation behind this module, and calling a model
 directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512 encoding never exist here.
 
 The progressive models feed `cat((t, y, x), encode(x)) * mask` to layer 1 (515 features, first weight [256][515]); the mask is
@@ -34,8 +35,14 @@ or grad mode off, the plain backward / inference path runs and nothing extra is 
 (`+ 1 / sigma_j`).  Both are buffers, the kernels evaluate them as a third encoding kind and the rest (masks, `k_active`, the
 backward pass) is the path of `RBF` / `PRBF`.
 
-Out of scope: `siren`, `PE` / `PPE` (the reference's
-PositionalEncoding.forward raises on any input, model.py:332), `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
+`PE` / `PPE` use the axis-aligned positional encoding of NeRF: the buffer `encode.freqs` = 2^i pi (i = 0 .. 3, fp32), feature
+`6 f + d` is `cos(freqs[f] x_d)` and feature `6 f + 3 + d` is `sin(freqs[f] x_d)`: 24 features, the cosines of a frequency before
+its sines.  Layer 1 is [256][24] (PPE: [256][27], mask of 27 values, blocks of 6 that cut through a frequency).  The reference's
+`PositionalEncoding.forward` reshapes through `.view(-1, 21)` (model.py:332), which raises unless the number of points is a
+multiple of 7 and is the formula above where it runs; the kernels evaluate the formula for every N.  The kernels are a fourth
+encoding kind with a narrow layer 1 (two 16-feature K steps instead of 32, a 32-column weight-gradient tile).
+
+Out of scope: `siren`, `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
 spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
 grid; `FixedSpatialController`; `AdaptiveController`).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
 `sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
@@ -53,7 +60,7 @@ from .ops import _stream, ptr
 
 check = _lib.check
 EPSILON = 1e-4
-RBF, FOURIER, RBFG = 0, 1, 3
+RBF, FOURIER, RBFG, PE = 0, 1, 3, 4
 
 
 class ModelParams:
@@ -207,6 +214,26 @@ class UniformRadialBasisGridEncoding(nn.Module):
         return self.offsets, self.sigma
 
 
+class PositionalEncoding(nn.Module):
+    """model.py:321-340 (one buffer, no RNG draw; evaluated inside the kernels).  Feature 6 f + d = cos(freqs[f] x_d), feature
+    6 f + 3 + d = sin(freqs[f] x_d).  The reference's forward runs only where the number of points is a multiple of 7 (its
+    `.view(-1, 21)`), and is this formula there; the kernels evaluate it for every N."""
+    kind = PE
+
+    def __init__(self, domain_dim, num_frequencies):
+        super().__init__()
+        self.domain_dim = domain_dim
+        self.num_frequencies = num_frequencies
+        self.register_buffer('freqs', torch.tensor([2. ** i * math.pi for i in range(num_frequencies)]))
+
+    @property
+    def output_channels(self):
+        return self.num_frequencies * self.domain_dim * 2
+
+    def kernel_buffers(self):
+        return self.freqs, None
+
+
 class _EncodedMlpModel(nn.Module):
     """model.py:54-103, the part the flow trainer uses."""
     encoding = None
@@ -350,10 +377,27 @@ class PRBFGModel(ProgressiveModel):
         return UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
 
 
+class PEModel(_EncodedMlpModel):
+    """model.py:472-487."""
+
+    @staticmethod
+    def make_encoding(opt):
+        return PositionalEncoding(opt.domain_dim, opt.num_frequencies_pe)
+
+
+class PPEModel(ProgressiveModel):
+    """model.py:607-611."""
+
+    @staticmethod
+    def get_encoding_layer(opt):
+        return PositionalEncoding(opt.domain_dim, opt.num_frequencies_pe)
+
+
 model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel}
 progressive_model_dict = {'PRBF': PRBFModel, 'PFF': PFFModel, 'PUFF': PUFFModel}
 learnable_model_dict = {'RFF': RFFModel, 'PRFF': PRFFModel}       # the encoding is trained; PRFF is progressive as well
 grid_model_dict = {'RBFG': RbfgModel, 'PRBFG': PRBFGModel}        # the radial-basis grid; PRBFG is progressive
+positional_model_dict = {'PE': PEModel, 'PPE': PPEModel}          # 24 features; PPE is progressive
 
 
 def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
@@ -364,7 +408,7 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
     a.enc_dim, a.hidden, a.layers, a.out_dim = net.encoding_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
     supported = (net.opt.domain_dim == 3 and len(lins) == 4 and _lib.lib().sininn_flownet_supported(C.byref(a)))
     if not supported:
-        raise ValueError(f'flownet kernels are built for 3 -> 512 (progressive: 515) -> 256 x 3 -> 4; got {net.opt.domain_dim} -> '
+        raise ValueError(f'flownet kernels are built for 3 -> 512 (progressive: 515; PE: 24, PPE: 27) -> 256 x 3 -> 4; got {net.opt.domain_dim} -> '
                          f'{a.enc_dim} -> {a.hidden} x {a.layers} -> {a.out_dim}')
     if a.progressive:
         if mask is None:
@@ -399,7 +443,7 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
 def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
     """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
     (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
-    caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats and `k_active` a
+    caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats (PPE: 27) and `k_active` a
     number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
     (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
     times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
@@ -522,7 +566,7 @@ def _resolve_mask(net, override_mask, device):
 def flow_fields(net, times, h, w, scale, override_mask=None):
     """FlowTrainer.forward (trainer.py:37-45): (flow12, flow21), each (t, 2, h, w), views of one (t, 4, h, w) tensor.  Under
     torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved.  `net` is a
-    model or a controller around a progressive model; `override_mask` (515 values, progressive networks only) replaces the
+    model or a controller around a progressive model; `override_mask` (515 values, PPE: 27; progressive networks only) replaces the
     controller's mask.  A learnable encoding (RFF / PRFF) contributes F_eff, computed here with torch ops; its gradient is computed
     only if `encode.frequencies` requires one."""
     if not times.is_cuda:

@@ -3,11 +3,12 @@ device events, after a warm-up, over a window of at least --seconds; one JSON li
 
     python tools/bench_flownet.py --net RBF --frames 1 --height 436 --width 1024 [--baseline]
 
-FLOP counts come from the shapes (2 N (512*256 + 2*256*256 + 256*4) forward; backward adds the data gradients of layers 2-4 and
+FLOP counts come from the shapes (2 N (E*256 + 2*256*256 + 256*4) forward, E = 512, for PE / PPE the network's own 24 / 27; backward adds the data gradients of layers 2-4 and
 the weight gradients of all four); `mfma_peak_share` is those executed FLOPs over the event time against the 157.3 TFLOP/s f32
 matrix peak of an MI355X -- the share of the whole call, not of one kernel.  --baseline times the same module composed from
 torch's own GPU ops (tools/fit_flow.composed_flow_fields) in the same process, alternating windows with the fused path.
-The progressive nets (PRBF, PFF, PUFF, PRBFG) run under a prefix mask of --k-active leading ones (default 515: all ones), given as a
+The progressive nets (PRBF, PFF, PUFF, PRBFG, PPE) run under a prefix mask of --k-active leading ones (default 515: all ones; clamped to
+the network's width, 27 for PPE), given as a
 host tensor so that the kernels skip the closed features as they do under a controller; the FLOP counts stay those of the full
 network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.
 RFF / PRFF (learnable frequencies) add the data gradient through layer 1 to the step (2 N 512*256 more FLOPs, counted) and the torch ops
@@ -28,9 +29,9 @@ for p in (ROOT, os.path.join(ROOT, 'tools')):
 PEAK_F32_MFMA = 157.3e12
 
 
-def flops(n, learnable=False):
-    fwd = 2 * n * (512 * 256 + 2 * 256 * 256 + 256 * 4)
-    dgrad = 2 * n * (2 * 256 * 256 + 256 * 4 + (512 * 256 if learnable else 0))
+def flops(n, learnable=False, enc_dim=512):
+    fwd = 2 * n * (enc_dim * 256 + 2 * 256 * 256 + 256 * 4)
+    dgrad = 2 * n * (2 * 256 * 256 + 256 * 4 + (enc_dim * 256 if learnable else 0))
     return fwd, fwd + dgrad + fwd
 
 
@@ -54,8 +55,8 @@ def window(fn, seconds, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG'])
-    ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask')
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE'])
+    ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask (0 .. 515, clamped to the network\'s width: 27 for PPE)')
     ap.add_argument('--frames', type=int, default=1)
     ap.add_argument('--height', type=int, default=436)
     ap.add_argument('--width', type=int, default=1024)
@@ -69,13 +70,14 @@ def main():
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
-    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict}[a.net](flownet.ModelParams()).to(dev)
+    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}[a.net](flownet.ModelParams()).to(dev)
     prog = net.is_progressive
     target = net
     if prog:
         assert 0 <= a.k_active <= 515
+        a.k_active = min(a.k_active, net.encoding_dim)
         target = progressive.LinearController(net)
-        target.mask = torch.zeros(515)
+        target.mask = torch.zeros(net.encoding_dim)
         target.mask[:a.k_active] = 1
         mask_dev = target.mask.to(dev)
     times = torch.linspace(0, 1, a.frames, device=dev) if a.frames > 1 else torch.zeros(1, device=dev)
@@ -105,7 +107,7 @@ def main():
         for k, (fwd, step) in todo.items():
             res[k]['forward'].append(window(fwd, a.seconds, a.warmup))
             res[k]['step'].append(window(step, a.seconds, a.warmup))
-    f_fwd, f_step = flops(n, learnable)
+    f_fwd, f_step = flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
     out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=_lib.lib().sininn_flownet_saved_bytes(n), workspace_bytes=_lib.lib().sininn_flownet_workspace_bytes(n))
     for k in res:

@@ -29,7 +29,7 @@ from bench_flownet import window  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE'])
     ap.add_argument('--frames', type=int, default=4)
     ap.add_argument('--batch', type=int, default=3)
     ap.add_argument('--height', type=int, default=436)
@@ -42,7 +42,7 @@ def main():
     from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
-    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict}[a.net](flownet.ModelParams())
+    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}[a.net](flownet.ModelParams())
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, 5000, epsilon=1e-3)
     args = argparse.Namespace(lr=1e-4, loss_l1=1, loss_census=0.1, loss_ssim=a.loss_ssim, census_width=3, loss_smooth1=0.1,

@@ -5,12 +5,13 @@
     python tools/fit_flow.py --net PRBF --max-iteration 1000
     python tools/fit_flow.py --net RFF
     python tools/fit_flow.py --net RBFG
+    python tools/fit_flow.py --net PPE
     python tools/fit_flow.py --optimizer lamb
 
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
 
-A progressive network (PRBF, PFF, PUFF, PRFF, PRBFG) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
+A progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, PPE) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
 video-interpolation/main.py:136-143 does, and the controller sees the loss after every step (trainer.py:75), which opens the mask.
 
 RFF / PRFF train `encode.frequencies` as well: the optimiser gets net.parameters(), which includes them.
@@ -56,7 +57,8 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     reference runs, and the baseline of tools/bench_flownet.py.  A progressive network reads cat((poses, encoding)) times the
     mask of its controller (or `override_mask`; a bare network: no mask), model.py:532-535 and 89-99.  A learnable encoding (RFF /
     PRFF) normalises its frequencies and scales them by the magnitudes on every call, model.py:274.  The radial-basis grid (RBFG / PRBFG)
-    is model.py:375-387 line by line, with its N x 256 x 2 x 3 intermediate."""
+    is model.py:375-387 line by line, with its N x 256 x 2 x 3 intermediate; the positional encoding (PE / PPE) is the einsum / cat of
+    model.py:331-332, without the `.view(-1, 21)` that raises unless N is a multiple of 7 (the cat is already (N, 4, 6))."""
     mask = override_mask
     if hasattr(net, 'mask'):                                      # a controller
         mask = net.mask if mask is None else mask
@@ -69,6 +71,9 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     if hasattr(enc, 'centres'):
         x = (x[:, None, :] - enc.centres[None, :, :]).pow(2).sum(2)
         x = torch.exp(-(x * enc.sigma[None, :] ** 2))
+    elif hasattr(enc, 'freqs'):
+        x = torch.einsum('f,nd->nfd', enc.freqs, x)
+        x = torch.cat((torch.cos(x), torch.sin(x)), dim=2).view(x.shape[0], -1)
     elif hasattr(enc, 'offsets'):
         x_a = x[:, None, :] + enc.offsets[None, :]
         x_b = x_a + (1 / enc.sigma[None, :, None])
@@ -94,7 +99,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     from sin_inn_amd import FusedAdam, FusedLAMB, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
-    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict}
+    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}
     net = nets[net_name](flownet.ModelParams()).to(device)
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
@@ -134,7 +139,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE'])
     ap.add_argument('--max-iteration', type=int, default=1000, help='progressive nets: the controller opens the mask over 3/4 of it')
     ap.add_argument('--height', type=int, default=64)
     ap.add_argument('--width', type=int, default=96)

@@ -9,11 +9,11 @@ Differences from the reference, all to make the path runnable here:
   * the trainer, checkpoint callback and logger come from `sin_inn_amd.lightning` (pytorch_lightning and wandb are not installed):
     `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
   * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
-  * `--net` takes the ten networks of `sin_inn_amd.flownet`; `siren`, `PE`, `PPE`, `MPFF` and `--spatially-adaptive` exit with a
+  * `--net` takes the twelve networks of `sin_inn_amd.flownet`; `siren`, `MPFF` and `--spatially-adaptive` exit with a
     message (flownet.py lists them as out of scope);
   * `--ngpus N` is N devices (cuda:0 .. cuda:N-1, the first is used), as in Lightning, not a device index;
   * a video file as `--input-video` (imageio + RAFT) is refused;
-  * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)`, which is 0 below 112 epochs, and the
+  * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)` (PPE: `// 12`), which is 0 below 112 (4) epochs, and the
     reference then divides by it; here such a short run opens one block per step;
   * checkpoints are written every max(epochs // 100, 1) epochs (the reference's `every_n_epochs=0` below 100 epochs writes none)
     whenever `--wandb` is given, `test` and `sintel` load the newest one, and `train` resumes from it.
@@ -28,8 +28,8 @@ ROOT = path.dirname(path.dirname(path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG')
-OUT_OF_SCOPE_NETWORKS = ('siren', 'PE', 'PPE', 'MPFF')
+NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE')
+OUT_OF_SCOPE_NETWORKS = ('siren', 'MPFF')
 
 
 def get_parser():
@@ -91,13 +91,13 @@ def build_net(args):
     """main.py:136-143: the network, and LinearControllerEarly around a progressive one.  `args.net` is the network's name on the
     first call; main() replaces it with the module, as the reference does, and keeps the name in `args.net_name`."""
     from sin_inn_amd import flownet, progressive
-    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict}
+    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}
     if isinstance(args.net, str):
         args.net_name = args.net
     net = nets[args.net_name](flownet.ModelParams())
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, args.epochs, epsilon=1e-3)
-        if net.block_iterations == 0:                          # fewer than 112 epochs: the reference divides by zero here
+        if net.block_iterations == 0:                          # fewer than 112 epochs (PPE: 4): the reference divides by zero here
             net.block_iterations = 1
             net.progress_iterations = (net.encoding_dim - net.block_size) // net.block_size
     return net
