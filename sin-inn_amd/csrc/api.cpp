@@ -118,6 +118,7 @@ int profile_classes_end(int n, double* ms, double* flops, int* launches);
 int profile_classes_bytes(int n, double* bytes);
 void profile_begin(int h, unsigned long long* stamps, int max_launches);
 int profile_end(int* count, float* total_ms);
+int flownet_supported(const sininn_flownet_args* a, const char* who);
 size_t flownet_saved_bytes(int64_t n);
 size_t flownet_workspace_bytes(int64_t n);
 size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a);
@@ -571,15 +572,7 @@ int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
   return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ST(stream));
 }
 
-int sininn_flownet_supported(const sininn_flownet_args* a) {
-  return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
-         (a->progressive == 0 || a->progressive == 1) &&
-         (((a->encoding == SININN_FLOWNET_RBF || a->encoding == SININN_FLOWNET_FOURIER || a->encoding == SININN_FLOWNET_RBFG) &&
-           a->enc_dim == (a->progressive ? 515 : 512)) ||
-          (a->encoding == SININN_FLOWNET_PE && a->enc_dim == (a->progressive ? 27 : 24))) &&
-         a->hidden == 256 &&
-         a->layers == 3 && a->out_dim == 4;
-}
+int sininn_flownet_supported(const sininn_flownet_args* args) { return flownet_supported(args, "sininn_flownet_supported"); }
 size_t sininn_flownet_saved_bytes(int64_t n_points) { return flownet_saved_bytes(n_points); }
 size_t sininn_flownet_workspace_bytes(int64_t n_points) { return flownet_workspace_bytes(n_points); }
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args) { return flownet_forward_workspace_bytes(args); }

@@ -14,6 +14,12 @@
 // them straight into the LDS operand tile (flownet_wgrad_kernel<.., true>); both call encode4, so the weight gradient of layer 1
 // sees bitwise the encoding the forward pass multiplied.
 //
+// structure: Enc<KIND> is the one description of an encoding (live features, padded K width, whether enc_b is read, whether enc_a has a
+//           gradient); the row strides of W1, the pack size, the K steps, the weight-gradient tile and its partial sums are derived from
+//           it there and nowhere else.  for_kind turns the run-time `encoding` into that compile-time kind for every launch, for
+//           flownet_supported and for the text of its refusal.  A new encoding is one Enc<> row, one case in for_kind and one branch
+//           of encode4.
+//
 // forward   flownet_fwd_kernel: block = 256 threads (4 waves, two blocks per CU), grid-stride over 64-point tiles.  Wave w owns
 //           hidden columns [64 w, 64 w + 64) of all 64 rows: 16 accumulator tiles.  Layer 1's A operand comes from encode4, layers
 //           2 / 3 read the previous hidden tile from LDS ([64][260] floats, ONE buffer: the accumulators hold the next tile until
@@ -39,13 +45,13 @@
 //           next to gb1 and is launched on the open 128-column tiles only; flownet_reduce_l1_kernel scatters the sums into
 //           nn.Linear's [256][515] layout, times the mask, exact zeros where the mask is zero.
 //
-// positional encoding (PE / PPE, PEModel model.py:472-487, PPEModel model.py:607-611): layer 1 has 24 (27) inputs.  The K range is padded
-//           to 32, features 24 .. 31 are exact zeros from encode4.  Plain PE reads W1 [256][24] in place (96-byte rows, the 16-byte loads
-//           of columns 24 .. 31 are replaced by zeros), two K steps; PPE packs mask * W1 into [256][32] + [256][4] like the other
-//           progressive networks and runs ceil(open / 16) K steps.  The layer-1 weight gradient is a narrower instantiation of
-//           flownet_wgrad_kernel: a block owns 128 hidden columns x the 32 padded features (a wave 32 x 32), always all of them, so
-//           nothing in it depends on k_active; flownet_reduce_l1_kernel writes nn.Linear's [256][24] / [256][27] layout, for PPE
-//           an exact +0 where the mask is zero or the column lies beyond k_active.
+// positional encoding (PE / PPE, PEModel model.py:472-487, PPEModel model.py:607-611): layer 1 has LIVE (LIVE + 3) inputs, fewer than
+//           its padded K width KW; features LIVE .. KW - 1 are exact zeros from encode4.  Plain PE reads W1 [256][LIVE] in place (96-byte
+//           rows, the 16-byte loads of columns LIVE .. KW - 1 are replaced by zeros), two K steps; PPE packs mask * W1 into [256][KW] +
+//           [256][4] like the other progressive networks and runs ceil(open / 16) K steps.  The layer-1 weight gradient is the NARROW
+//           instantiation of flownet_wgrad_kernel: a block owns 128 hidden columns x the KW padded features (a wave 32 x 32), always all of
+//           them, so nothing in it depends on k_active; flownet_reduce_l1_kernel writes nn.Linear's [256][LIVE] / [256][LIVE + 3] layout,
+//           for PPE an exact +0 where the mask is zero or the column lies beyond k_active.
 #include "common.h"
 
 namespace sininn {
@@ -54,7 +60,6 @@ namespace {
 
 constexpr int FN_P = 64;            // points per tile
 constexpr int FN_HID = 256;
-constexpr int FN_ENC = 512;
 constexpr int FN_OUT = 4;
 constexpr int FN_HS = FN_HID + 4;   // floats per row of the hidden tile in LDS (16-byte reads of 16 rows hit 64 distinct banks)
 constexpr int FN_NTHR = 256;
@@ -65,13 +70,48 @@ constexpr int FN_CHAIN_MAX_BLOCKS = 512;
 constexpr size_t FN_LDS = (size_t)(FN_P * FN_HS + FN_P * FN_OUT) * sizeof(float);
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
 constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features
-constexpr int FN_PENC = FN_ENC + FN_DOM;
 constexpr int FN_CS = 4;            // floats per row of the packed coordinate columns / of the coordinate tile in LDS
 constexpr size_t FN_WG_LDS_PROG = FN_WG_LDS + (size_t)(FN_P * FN_CS) * sizeof(float);
-constexpr size_t FN_PACK_FLOATS = (size_t)FN_HID * (FN_ENC + FN_CS);
-constexpr int FN_PE_LIVE = 24;      // positional encoding: 4 frequencies x 3 coordinates x (cos, sin)
-constexpr int FN_PE_W = 32;         // ... padded to two 16-feature K steps; features 24 .. 31 are exact zeros
-constexpr size_t FN_PE_PACK_FLOATS = (size_t)FN_HID * (FN_PE_W + FN_CS);
+
+// ---- the input of a layer as the kernels see it: LIVE features in a K range of KW.  Everything that depends on the encoding is here ----
+template <int LIVE_, int KW_, bool ENC_B_ = false, bool FREQ_GRAD_ = false>
+struct LayerInput {
+  static constexpr int LIVE = LIVE_;                   // features that exist
+  static constexpr int KW = KW_;                       // ... padded to whole 16-feature K steps: encode4 gives exact zeros from LIVE on
+  static constexpr bool ENC_B = ENC_B_;                // the encoding reads enc_b
+  static constexpr bool FREQ_GRAD = FREQ_GRAD_;        // the gradient with respect to enc_a exists
+  static constexpr int KSTEPS = KW / 16;
+  static constexpr int width(bool prog) { return LIVE + (prog ? FN_DOM : 0); }   // enc_dim: a row of nn.Linear's W1
+  static constexpr int w1_stride(bool prog) { return prog ? KW : LIVE; }         // a row of the W1 the forward reads: packed / in place
+  static constexpr size_t PACK_FLOATS = (size_t)FN_HID * (KW + FN_CS);           // progressive: W1p [256][KW] and wc [256][4]
+  // the weight gradient: a block owns 128 x KT outputs, a wave AT x AT accumulator tiles (wide: 64 x 64, narrow: 32 x 32)
+  static constexpr bool NARROW = KW < FN_WT;
+  static constexpr int KT = NARROW ? KW : FN_WT;
+  static constexpr int AT = NARROW ? 2 : 4;
+  static constexpr int CHUNK_KF = FN_WT * (KW / KT);   // wgrad_chunks' width: (chunks) x (2 KW / KT output tiles) is about 512 blocks
+  static constexpr int part_stride(bool prog) { return FN_HID * KW + FN_HID + (prog ? FN_HID * FN_CS : 0); }   // one chunk's partial sums
+};
+
+template <int KIND> struct Enc;
+template <> struct Enc<SININN_FLOWNET_RBF> : LayerInput<512, 512, true> { static constexpr const char* NAME = "RBF"; };
+template <> struct Enc<SININN_FLOWNET_FOURIER> : LayerInput<512, 512, false, true> { static constexpr const char* NAME = "Fourier"; };
+template <> struct Enc<SININN_FLOWNET_RBFG> : LayerInput<512, 512, true> { static constexpr const char* NAME = "RBFG"; };
+// 4 frequencies x 3 coordinates x (cos, sin), padded to two K steps
+template <> struct Enc<SININN_FLOWNET_PE> : LayerInput<24, 32> { static constexpr const char* NAME = "PE"; };
+using Hidden = LayerInput<FN_HID, FN_HID>;             // layers 2 and 3, for their weight gradient
+constexpr int FN_KINDS[] = {SININN_FLOWNET_RBF, SININN_FLOWNET_FOURIER, SININN_FLOWNET_RBFG, SININN_FLOWNET_PE};
+
+// f(std::integral_constant<int, KIND>) for the run-time `encoding`; `otherwise` for a value that is no encoding of this library
+template <class R, class F>
+R for_kind(int encoding, R otherwise, F&& f) {
+  switch (encoding) {
+    case SININN_FLOWNET_RBF: return f(std::integral_constant<int, SININN_FLOWNET_RBF>{});
+    case SININN_FLOWNET_FOURIER: return f(std::integral_constant<int, SININN_FLOWNET_FOURIER>{});
+    case SININN_FLOWNET_RBFG: return f(std::integral_constant<int, SININN_FLOWNET_RBFG>{});
+    case SININN_FLOWNET_PE: return f(std::integral_constant<int, SININN_FLOWNET_PE>{});
+    default: return otherwise;
+  }
+}
 
 struct FlowNetDev {
   int T, H, W, N, ntiles;
@@ -160,7 +200,7 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
     for (int j = 0; j < 4; ++j) {
       const int k = f0 + j;                                                // freqs [4]; 6 f + d: cos, 6 f + 3 + d: sin
       float v = 0.f;
-      if (k < FN_PE_LIVE) {
+      if (k < Enc<KIND>::LIVE) {
         const int f = k / 6, r = k - 6 * f, d = r < 3 ? r : r - 3;
         const float xd = d == 0 ? c.t : d == 1 ? c.y : c.x;
         // one rounded product, as torch's einsum makes it, never contracted; the accurate full-range sine and cosine
@@ -238,12 +278,11 @@ __device__ __forceinline__ void copy_tile_out(const float* hs, float* dst, int t
   }
 }
 
-// PROG: q.w[0] is the packed W1p [256][512] (PE: [256][32]), q.wc the coordinate columns, q.ksteps the length of the K loop
+// PROG: q.w[0] is the packed W1p [256][KW], q.wc the coordinate columns, q.ksteps the length of the K loop
 template <int KIND, bool PROG = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
-  constexpr bool PE = KIND == SININN_FLOWNET_PE;
-  constexpr int EW = PE ? (PROG ? FN_PE_W : FN_PE_LIVE) : FN_ENC;   // floats per row of q.w[0]
-  constexpr int KSTEPS = (PE ? FN_PE_W : FN_ENC) / 16;
+  using E = Enc<KIND>;
+  constexpr int EW = E::w1_stride(PROG);               // floats per row of q.w[0]
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;
   const int tid = threadIdx.x;
@@ -273,13 +312,13 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
         for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
     }
     // ---- layer 1: the A fragment is generated, never stored ----
-    const int ksteps = PROG ? q.ksteps : KSTEPS;
+    const int ksteps = PROG ? q.ksteps : E::KSTEPS;
 #pragma unroll 1
     for (int s = 0; s < ksteps; ++s) {
       f32x4 bf[4], af[4];
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        if (PE && !PROG && 16 * s + 4 * kq >= FN_PE_LIVE) bf[n] = (f32x4){0.f, 0.f, 0.f, 0.f};   // W1 [256][24] has no such columns
+        if (!PROG && E::LIVE < E::KW && 16 * s + 4 * kq >= E::LIVE) bf[n] = (f32x4){0.f, 0.f, 0.f, 0.f};   // W1 [256][LIVE] has no such columns
         else bf[n] = *reinterpret_cast<const f32x4*>(q.w[0] + (size_t)(cw + 16 * n + li) * EW + 16 * s + 4 * kq);
       }
 #pragma unroll
@@ -337,8 +376,9 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_transpose_kernel(const float*
 }
 
 // progressive: w1p[j][k] = w1[j][3 + k] mask[3 + k] (k < 512), wc[j][c] = w1[j][c] mask[c] (c < 3), wc[j][3] = 0; block = row j.
-// A closed feature gets an exact zero whatever the weight holds.  EW > LIVE (PE: w1 is [256][3 + 24], w1p [256][32]): zeros from LIVE on.
-template <int EW = FN_ENC, int LIVE = FN_ENC>
+// A closed feature gets an exact zero whatever the weight holds.  EW > LIVE (PE: w1 is [256][3 + LIVE], w1p [256][KW]): zeros from LIVE on.
+// Instantiated as <E::KW, E::LIVE>: encodings of one shape share one kernel
+template <int EW, int LIVE>
 __global__ __launch_bounds__(FN_NTHR) void flownet_pack_kernel(const float* w1, const float* mask, float* w1p, float* wc) {
   const int j = blockIdx.x, tid = threadIdx.x;
   const float* row = w1 + (size_t)j * (FN_DOM + LIVE);
@@ -448,17 +488,18 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
 }
 
 // part[chunk][j][k] = sum over the chunk's point tiles of dh[p][j] in[p][k]  (+ [chunk][256 * KF + j] = sum_p dh[p][j]);
-// grid = (2 * KF / 128 output tiles, chunks); ENC: in = the encoding (KF = 512), else a saved hidden layer (KF = 256).
+// grid = (2 * KF / KT output tiles, chunks); ENC: in = the encoding (KF = Enc<KIND>::KW), else a saved hidden layer (KF = 256, KIND unused).
 // PROG (with ENC): + [chunk][256 * KF + 256 + 4 j + c] = sum_p dh[p][j] coordinate_c[p]; the grid may cover the leading k tiles only.
-// NARROW (ENC of the positional encoding): KF = 32, grid = (2, chunks), a block owns 128 x 32 and a wave 32 x 32 of it
+// NARROW (an encoding of fewer than 128 padded features): grid = (2, chunks), a block owns 128 x KF and a wave 32 x 32 of it
 template <int KIND, bool ENC, bool PROG = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q, const float* dh, const float* in) {
   static_assert(ENC || !PROG, "the progressive weight gradient is layer 1's");
-  constexpr bool NARROW = ENC && KIND == SININN_FLOWNET_PE;
-  constexpr int KF = ENC ? (NARROW ? FN_PE_W : FN_ENC) : FN_HID;
-  constexpr int KT = NARROW ? FN_PE_W : FN_WT;         // input columns of a block
-  constexpr int MT = NARROW ? 2 : 4, NT = NARROW ? 2 : 4;   // 16 x 16 accumulator tiles of a wave
-  constexpr int PSTRIDE = FN_HID * KF + FN_HID + (PROG ? FN_HID * FN_CS : 0);
+  using L = std::conditional_t<ENC, Enc<KIND>, Hidden>;
+  constexpr bool NARROW = L::NARROW;
+  constexpr int KF = L::KW;
+  constexpr int KT = L::KT;                            // input columns of a block
+  constexpr int MT = L::AT, NT = L::AT;                // 16 x 16 accumulator tiles of a wave
+  constexpr int PSTRIDE = L::part_stride(PROG);
   constexpr int NU = FN_P * FN_WT / 4 / FN_NTHR;       // 16-byte units per thread and operand tile
   constexpr int NUB = FN_P * KT / 4 / FN_NTHR;         // ... of the input tile
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
@@ -571,14 +612,14 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* pa
 
 // progressive layer 1: gw [256][515] = mask[k] * sum_c part[c][..] in chunk order (k < 3: the coordinate sums, else encoded column
 // k - 3), an exact zero where the mask is zero or the column lies beyond the `kcols` encoded columns that were computed; gb as above.
-// EW: columns of a row of the partial sums, LIVE: encoded columns of gw (PE: 32 and 24).  !PROG (PE): gw [256][LIVE], no mask
-template <int EW = FN_ENC, int LIVE = FN_ENC, bool PROG = true>
+// EW: columns of a row of the partial sums, LIVE: encoded columns of gw (<E::KW, E::LIVE>).  !PROG (PE): gw [256][LIVE], no mask
+template <int EW, int LIVE, bool PROG>
 __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_l1_kernel(const float* part, int nparts, const float* mask, int kcols, float* gw,
                                                                     float* gb) {
   constexpr int DOM = PROG ? FN_DOM : 0;
   constexpr int WIDTH = DOM + LIVE;
   constexpr int NW = FN_HID * WIDTH;
-  constexpr size_t STRIDE = (size_t)FN_HID * EW + FN_HID + (PROG ? FN_HID * FN_CS : 0);
+  constexpr size_t STRIDE = LayerInput<LIVE, EW>::part_stride(PROG);
   const int i = blockIdx.x * FN_NTHR + threadIdx.x;
   if (i >= NW + FN_HID) return;
   size_t src;
@@ -605,9 +646,10 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_l1_kernel(const float*
 // wave (c / 64) % 4, accumulator column block n = (c / 16) % 4, lane c % 16 holds feature 2 f + n / 2 of frequency
 // f = 128 pass + 32 wave + 16 (n % 2) + lane, so a lane's accumulators n and n + 2 are the sin and the cos coefficient of ONE frequency
 // for the same 16 points and dphi = dE_sin cos(phi) - dE_cos sin(phi) needs no lane movement.
-constexpr int FN_NF = FN_ENC / 2;                    // frequencies
+using Fourier = Enc<SININN_FLOWNET_FOURIER>;
+constexpr int FN_NF = Fourier::LIVE / 2;             // frequencies
 constexpr int FN_EG_PART = FN_DOM * FN_NF;           // floats of one block's partial sums, [3][256]
-constexpr size_t FN_EG_FLOATS = (size_t)FN_ENC * FN_HID + (size_t)FN_CHAIN_MAX_BLOCKS * FN_EG_PART;
+constexpr size_t FN_EG_FLOATS = (size_t)Fourier::LIVE * FN_HID + (size_t)FN_CHAIN_MAX_BLOCKS * FN_EG_PART;
 constexpr float FN_TWO_PI = 6.283185307179586f;
 
 // wt[c][j] = w1[j][feature of row c] (progressive: column 3 + feature, times its mask, an exact zero where the mask is zero); block = row c
@@ -618,9 +660,9 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_encgrad_pack_kernel(const flo
   float v;
   if (mask) {
     const float m = mask[FN_DOM + k];
-    v = m == 0.f ? 0.f : w1[(size_t)j * FN_PENC + FN_DOM + k] * m;
+    v = m == 0.f ? 0.f : w1[(size_t)j * Fourier::width(true) + FN_DOM + k] * m;
   } else {
-    v = w1[(size_t)j * FN_ENC + k];
+    v = w1[(size_t)j * Fourier::width(false) + k];
   }
   wt[(size_t)c * FN_HID + j] = v;
 }
@@ -710,22 +752,26 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_enc_kernel(const float
   g[i] = s * FN_TWO_PI;
 }
 
-constexpr int FN_PE_CHUNK_KF = 128;   // wgrad_chunks' width for the narrow layer 1: 2 output tiles x 256 chunks = 512 blocks
-
 int wgrad_chunks(int ntiles, int kf) {
-  const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 for layer 1
+  const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 (narrow: 256 x 2) for layer 1
   return ntiles < want ? ntiles : want;
 }
 
 int chain_blocks(int ntiles) { return ntiles < FN_CHAIN_MAX_BLOCKS ? ntiles : FN_CHAIN_MAX_BLOCKS; }
 
+// the largest set of partial sums of a backward call: a hidden layer's, any encoding's progressive layer 1, the chain kernel's
 size_t part_floats(int ntiles) {
-  size_t a = (size_t)wgrad_chunks(ntiles, FN_HID) * (FN_HID * FN_HID + FN_HID);
-  const size_t b = (size_t)wgrad_chunks(ntiles, FN_ENC) * (FN_HID * FN_ENC + FN_HID + FN_HID * FN_CS);   // progressive layer 1
-  // the positional encoding's layer 1 (FN_PE_CHUNK_KF: up to 256 chunks of 256 * 32 + 256 + 1024 floats) is below `a` for every ntiles
+  size_t n = (size_t)wgrad_chunks(ntiles, Hidden::CHUNK_KF) * Hidden::part_stride(false);
   const size_t c = (size_t)chain_blocks(ntiles) * (FN_OUT * FN_HID + FN_OUT);
-  a = a > b ? a : b;
-  return a > c ? a : c;
+  n = n > c ? n : c;
+  for (int kind : FN_KINDS) {
+    const size_t b = for_kind(kind, (size_t)0, [&](auto k) {
+      using E = Enc<decltype(k)::value>;
+      return (size_t)wgrad_chunks(ntiles, E::CHUNK_KF) * E::part_stride(true);
+    });
+    n = n > b ? n : b;
+  }
+  return n;
 }
 
 template <class K>
@@ -737,20 +783,76 @@ int raise_lds(K k, size_t bytes, const char* name) {
   return 0;
 }
 
-int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
+// encoded features in front of the last open one
+int open_encoded(const sininn_flownet_args* a) { return a->k_active > FN_DOM ? a->k_active - FN_DOM : 0; }
+
+void reduce_launch(const FlowNetDev& q, int nparts, int nw, int nb, float* gw, float* gb, hipStream_t st) {
+  hipLaunchKernelGGL(flownet_reduce_kernel, dim3((nw + nb + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, (const float*)q.part, nparts, nw, nb, gw, gb);
+}
+
+}  // namespace
+
+// the support table; a refusal leaves its reason, with the table, as the library's last error
+int flownet_supported(const sininn_flownet_args* a, const char* who) {
+  if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
+  const bool prog = a->progressive == 1;
+  const bool ok = (a->progressive == 0 || prog) && a->hidden == FN_HID && a->layers == 3 && a->out_dim == FN_OUT &&
+                  for_kind(a->encoding, false, [&](auto k) { return a->enc_dim == Enc<decltype(k)::value>::width(prog); });
+  if (!ok) {
+    std::string table;
+    for (int kind : FN_KINDS)
+      for_kind(kind, 0, [&](auto k) {
+        using E = Enc<decltype(k)::value>;
+        table += std::string(table.empty() ? "" : ", ") + E::NAME + " " + std::to_string(E::width(false)) + " (progressive: " +
+                 std::to_string(E::width(true)) + ")";
+        return 0;
+      });
+    set_error("%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for %s -> %d x 3 -> %d)", who, a->encoding,
+              a->enc_dim, a->hidden, a->layers, a->out_dim, a->progressive, table.c_str(), FN_HID, FN_OUT);
+  }
+  return ok;
+}
+
+size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a) {
+  if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args) || !a->progressive) return 0;   // plain PE reads W1 in place
+  return for_kind(a->encoding, (size_t)0, [](auto k) { return Enc<decltype(k)::value>::PACK_FLOATS * sizeof(float); });
+}
+
+size_t flownet_saved_bytes(int64_t n) {
+  if (n <= 0) return 0;
+  return (size_t)3 * (size_t)((n + FN_P - 1) / FN_P) * FN_P * FN_HID * sizeof(float);
+}
+
+size_t flownet_workspace_bytes(int64_t n) {
+  if (n <= 0 || n > ((int64_t)1 << 22)) return 0;
+  const int ntiles = (int)((n + FN_P - 1) / FN_P);
+  return flownet_saved_bytes(n) + ((size_t)2 * FN_HID * FN_HID + part_floats(ntiles)) * sizeof(float);
+}
+
+size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
+  const bool has = a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
+                   for_kind(a->encoding, false, [](auto k) { return Enc<decltype(k)::value>::FREQ_GRAD; });
+  return has ? FN_EG_FLOATS * sizeof(float) : 0;
+}
+
+// the head of every entry point: a struct of this library's size that describes a network the kernels are built for
+static int check_network(const sininn_flownet_args* a, const char* who) {
   SININN_CHECK(a != nullptr, "%s: null args", who);
   SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
                a->struct_bytes, sizeof(sininn_flownet_args));
-  SININN_CHECK(sininn_flownet_supported(a),
-               "%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for RBF / Fourier / RBFG, 512 (progressive: 515), or PE, 24 (progressive: 27), -> 256 x 3 -> 4)",
-               who, a->encoding, a->enc_dim, a->hidden, a->layers, a->out_dim, a->progressive);
+  return flownet_supported(a, who) ? 0 : 1;
+}
+
+static int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
+  if (int rc = check_network(a, who)) return rc;
   if (a->progressive) {
     SININN_CHECK(a->mask != nullptr, "%s: progressive network without a mask", who);
     SININN_CHECK(a->k_active >= 0 && a->k_active <= a->enc_dim, "%s: k_active %d (0 .. %d)", who, a->k_active, a->enc_dim);
   }
   SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
                who, a->T, a->H, a->W);
-  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->encoding == SININN_FLOWNET_FOURIER || a->encoding == SININN_FLOWNET_PE || a->enc_b), "%s: null axis / encoding pointer", who);
+  const bool enc_b = for_kind(a->encoding, false, [](auto k) { return Enc<decltype(k)::value>::ENC_B; });
+  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->enc_b || !enc_b), "%s: null axis / encoding pointer", who);
   SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
   for (int l = 0; l < 4; ++l) {
     SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
@@ -769,98 +871,33 @@ int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
   return 0;
 }
 
-// encoded features in front of the last open one
-int open_encoded(const sininn_flownet_args* a) { return a->k_active > FN_DOM ? a->k_active - FN_DOM : 0; }
-
-}  // namespace
-
-size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a) {
-  if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args) || !a->progressive) return 0;   // plain PE reads W1 in place
-  return (a->encoding == SININN_FLOWNET_PE ? FN_PE_PACK_FLOATS : FN_PACK_FLOATS) * sizeof(float);
-}
-
-size_t flownet_saved_bytes(int64_t n) {
-  if (n <= 0) return 0;
-  return (size_t)3 * (size_t)((n + FN_P - 1) / FN_P) * FN_P * FN_HID * sizeof(float);
-}
-
-size_t flownet_workspace_bytes(int64_t n) {
-  if (n <= 0 || n > ((int64_t)1 << 22)) return 0;
-  const int ntiles = (int)((n + FN_P - 1) / FN_P);
-  return flownet_saved_bytes(n) + ((size_t)2 * FN_HID * FN_HID + part_floats(ntiles)) * sizeof(float);
-}
-
-int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
-  FlowNetDev q;
-  if (int rc = check_args(a, "flownet_forward", q)) return rc;
-  SININN_CHECK(a->flows != nullptr, "flownet_forward: null flows");
-  q.flows = a->flows;
-  if (a->saved) {
-    SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_forward: saved holds %zu bytes, %zu needed", a->saved_bytes,
-                 flownet_saved_bytes(q.N));
-    SININN_CHECK(aligned16(a->saved), "flownet_forward: saved must be 16-byte aligned");
-    q.saved = a->saved;
+// layer 1: gW1 = dh1^T (regenerated input), gb1, and their reduction into nn.Linear's layout
+template <int KIND, bool PROG>
+static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hipStream_t st) {
+  using E = Enc<KIND>;
+  constexpr size_t lds = PROG ? FN_WG_LDS_PROG : FN_WG_LDS;
+  auto k = flownet_wgrad_kernel<KIND, true, PROG>;
+  if (raise_lds(k, lds, "flownet_wgrad")) return 1;
+  const int nc = wgrad_chunks(q.ntiles, E::CHUNK_KF);  // not a function of k_active: the order of every sum stays the same
+  // progressive, wide: the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate
+  // columns); narrow: the one column tile, always whole
+  const int oe = open_encoded(a);
+  const int ktiles = PROG && !E::NARROW ? (oe > 0 ? (oe + FN_WT - 1) / FN_WT : 1) : E::KW / E::KT;
+  hipLaunchKernelGGL(k, dim3(2 * ktiles, nc), dim3(FN_NTHR), lds, st, q, (const float*)q.dh, (const float*)nullptr);
+  SININN_LAUNCH_CHECK("flownet_wgrad");
+  if constexpr (!PROG && E::LIVE == E::KW) {           // the partial sums are in nn.Linear's layout already
+    reduce_launch(q, nc, FN_HID * E::LIVE, FN_HID, a->gw[0], a->gb[0], st);
+  } else {
+    const int kcols = !PROG ? E::LIVE : E::NARROW ? oe : ktiles * FN_WT;
+    hipLaunchKernelGGL((flownet_reduce_l1_kernel<E::KW, E::LIVE, PROG>), dim3((FN_HID * E::width(PROG) + FN_HID + FN_NTHR - 1) / FN_NTHR),
+                       dim3(FN_NTHR), 0, st, (const float*)q.part, nc, PROG ? a->mask : (const float*)nullptr, kcols, a->gw[0], a->gb[0]);
   }
-  const bool pe = a->encoding == SININN_FLOWNET_PE;
-  auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_fwd_kernel<SININN_FLOWNET_RBF>
-           : a->encoding == SININN_FLOWNET_RBFG ? flownet_fwd_kernel<SININN_FLOWNET_RBFG>
-           : pe                                 ? flownet_fwd_kernel<SININN_FLOWNET_PE>
-                                                : flownet_fwd_kernel<SININN_FLOWNET_FOURIER>;
-  if (a->progressive) {
-    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
-                 "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", flownet_forward_workspace_bytes(a),
-                 a->workspace ? a->workspace_bytes : (size_t)0);
-    SININN_CHECK(aligned16(a->workspace), "flownet_forward: workspace must be 16-byte aligned");
-    float* const w1p = static_cast<float*>(a->workspace);
-    float* const wc = w1p + (size_t)FN_HID * (pe ? FN_PE_W : FN_ENC);
-    if (pe) hipLaunchKernelGGL((flownet_pack_kernel<FN_PE_W, FN_PE_LIVE>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
-    else hipLaunchKernelGGL((flownet_pack_kernel<>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
-    SININN_LAUNCH_CHECK("flownet_pack");
-    q.w[0] = w1p;
-    q.wc = wc;
-    q.ksteps = (open_encoded(a) + 15) / 16;
-    k = a->encoding == SININN_FLOWNET_RBF    ? flownet_fwd_kernel<SININN_FLOWNET_RBF, true>
-        : a->encoding == SININN_FLOWNET_RBFG ? flownet_fwd_kernel<SININN_FLOWNET_RBFG, true>
-        : pe                                 ? flownet_fwd_kernel<SININN_FLOWNET_PE, true>
-                                             : flownet_fwd_kernel<SININN_FLOWNET_FOURIER, true>;
-  }
-  if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
-  const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS, st, q);
-  SININN_LAUNCH_CHECK("flownet_forward");
+  SININN_LAUNCH_CHECK("flownet_reduce");
   return 0;
 }
 
-size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
-  return a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) && a->encoding == SININN_FLOWNET_FOURIER ? FN_EG_FLOATS * sizeof(float) : 0;
-}
-
-namespace {
-int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st);
-}
-
-int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_launch(a, nullptr, nullptr, st); }
-
-int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                    hipStream_t st) {
-  const char* who = "flownet_backward_encgrad";
-  SININN_CHECK(a != nullptr, "%s: null args", who);
-  SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
-               a->struct_bytes, sizeof(sininn_flownet_args));
-  SININN_CHECK(a->encoding == SININN_FLOWNET_FOURIER, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
-               a->encoding);
-  SININN_CHECK(g_enc_a != nullptr, "%s: null g_enc_a", who);
-  SININN_CHECK(enc_workspace != nullptr && enc_workspace_bytes >= flownet_encgrad_workspace_bytes(a),
-               "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
-               flownet_encgrad_workspace_bytes(a));
-  SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
-  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st);
-}
-
-namespace {
-
 // g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
-int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st) {
+static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st) {
   FlowNetDev q;
   if (int rc = check_args(a, "flownet_backward", q)) return rc;
   SININN_CHECK(a->dflows && a->saved && a->workspace, "flownet_backward: null dflows / saved / workspace");
@@ -885,70 +922,27 @@ int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws,
   const int cb = chain_blocks(q.ntiles);
   hipLaunchKernelGGL(flownet_bwd_chain_kernel, dim3(cb), dim3(FN_NTHR), FN_LDS, st, q);
   SININN_LAUNCH_CHECK("flownet_bwd_chain");
-  auto reduce = [&](int nparts, int nw, int nb, float* gw, float* gb) {
-    hipLaunchKernelGGL(flownet_reduce_kernel, dim3((nw + nb + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, q.part, nparts, nw, nb, gw, gb);
-  };
-  reduce(cb, FN_OUT * FN_HID, FN_OUT, a->gw[3], a->gb[3]);
+  reduce_launch(q, cb, FN_OUT * FN_HID, FN_OUT, a->gw[3], a->gb[3], st);
   SININN_LAUNCH_CHECK("flownet_reduce");
   for (int l = 2; l >= 1; --l) {                       // gW3 = dh3^T h2, gW2 = dh2^T h1
     auto k = flownet_wgrad_kernel<SININN_FLOWNET_RBF, false>;
     if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
-    const int nc = wgrad_chunks(q.ntiles, FN_HID);
-    hipLaunchKernelGGL(k, dim3(2 * FN_HID / FN_WT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)(q.dh + l * lstride),
+    const int nc = wgrad_chunks(q.ntiles, Hidden::CHUNK_KF);
+    hipLaunchKernelGGL(k, dim3(2 * Hidden::KW / Hidden::KT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)(q.dh + l * lstride),
                        (const float*)(q.saved + (l - 1) * lstride));
     SININN_LAUNCH_CHECK("flownet_wgrad");
-    reduce(nc, FN_HID * FN_HID, FN_HID, a->gw[l], a->gb[l]);
+    reduce_launch(q, nc, FN_HID * FN_HID, FN_HID, a->gw[l], a->gb[l], st);
     SININN_LAUNCH_CHECK("flownet_reduce");
   }
-  if (a->encoding == SININN_FLOWNET_PE) {
-    // one narrow column tile, always whole; the chunks are not a function of k_active either
-    const int nc = wgrad_chunks(q.ntiles, FN_PE_CHUNK_KF);
-    if (a->progressive) {
-      auto k = flownet_wgrad_kernel<SININN_FLOWNET_PE, true, true>;
-      if (raise_lds(k, FN_WG_LDS_PROG, "flownet_wgrad")) return 1;
-      hipLaunchKernelGGL(k, dim3(2, nc), dim3(FN_NTHR), FN_WG_LDS_PROG, st, q, (const float*)q.dh, (const float*)nullptr);
-      SININN_LAUNCH_CHECK("flownet_wgrad");
-      hipLaunchKernelGGL((flownet_reduce_l1_kernel<FN_PE_W, FN_PE_LIVE, true>), dim3((FN_HID * (FN_DOM + FN_PE_LIVE) + FN_HID + FN_NTHR - 1) / FN_NTHR),
-                         dim3(FN_NTHR), 0, st, (const float*)q.part, nc, a->mask, open_encoded(a), a->gw[0], a->gb[0]);
-    } else {
-      auto k = flownet_wgrad_kernel<SININN_FLOWNET_PE, true>;
-      if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
-      hipLaunchKernelGGL(k, dim3(2, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)q.dh, (const float*)nullptr);
-      SININN_LAUNCH_CHECK("flownet_wgrad");
-      hipLaunchKernelGGL((flownet_reduce_l1_kernel<FN_PE_W, FN_PE_LIVE, false>), dim3((FN_HID * FN_PE_LIVE + FN_HID + FN_NTHR - 1) / FN_NTHR),
-                         dim3(FN_NTHR), 0, st, (const float*)q.part, nc, (const float*)nullptr, FN_PE_LIVE, a->gw[0], a->gb[0]);
-    }
-    SININN_LAUNCH_CHECK("flownet_reduce");
-  } else if (a->progressive) {
-    // the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate columns)
-    auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true, true>
-             : a->encoding == SININN_FLOWNET_RBFG ? flownet_wgrad_kernel<SININN_FLOWNET_RBFG, true, true>
-                                                  : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true, true>;
-    if (raise_lds(k, FN_WG_LDS_PROG, "flownet_wgrad")) return 1;
-    const int nc = wgrad_chunks(q.ntiles, FN_ENC);         // not a function of k_active: the order of every sum stays the same
-    const int oe = open_encoded(a);
-    const int ktiles = oe > 0 ? (oe + FN_WT - 1) / FN_WT : 1;
-    hipLaunchKernelGGL(k, dim3(2 * ktiles, nc), dim3(FN_NTHR), FN_WG_LDS_PROG, st, q, (const float*)q.dh, (const float*)nullptr);
-    SININN_LAUNCH_CHECK("flownet_wgrad");
-    hipLaunchKernelGGL((flownet_reduce_l1_kernel<>), dim3((FN_HID * FN_PENC + FN_HID + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st,
-                       (const float*)q.part, nc, a->mask, ktiles * FN_WT, a->gw[0], a->gb[0]);
-    SININN_LAUNCH_CHECK("flownet_reduce");
-  } else {
-    auto k = a->encoding == SININN_FLOWNET_RBF    ? flownet_wgrad_kernel<SININN_FLOWNET_RBF, true>
-             : a->encoding == SININN_FLOWNET_RBFG ? flownet_wgrad_kernel<SININN_FLOWNET_RBFG, true>
-                                                  : flownet_wgrad_kernel<SININN_FLOWNET_FOURIER, true>;
-    if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
-    const int nc = wgrad_chunks(q.ntiles, FN_ENC);
-    hipLaunchKernelGGL(k, dim3(2 * FN_ENC / FN_WT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)q.dh, (const float*)nullptr);
-    SININN_LAUNCH_CHECK("flownet_wgrad");
-    reduce(nc, FN_HID * FN_ENC, FN_HID, a->gw[0], a->gb[0]);
-    SININN_LAUNCH_CHECK("flownet_reduce");
-  }
+  if (int rc = for_kind(a->encoding, 1, [&](auto k) {
+        return a->progressive ? wgrad_l1_launch<decltype(k)::value, true>(a, q, st) : wgrad_l1_launch<decltype(k)::value, false>(a, q, st);
+      }))
+    return rc;
   if (g_enc_a) {
-    float* const epart = enc_ws + (size_t)FN_ENC * FN_HID;
+    float* const epart = enc_ws + (size_t)Fourier::LIVE * FN_HID;
     const float* const mask = a->progressive ? a->mask : nullptr;
     const int fopen = a->progressive ? (open_encoded(a) + 1) / 2 : FN_NF;   // a frequency is open if its sin or its cos is
-    hipLaunchKernelGGL(flownet_encgrad_pack_kernel, dim3(FN_ENC), dim3(FN_NTHR), 0, st, a->w[0], mask, enc_ws);
+    hipLaunchKernelGGL(flownet_encgrad_pack_kernel, dim3(Fourier::LIVE), dim3(FN_NTHR), 0, st, a->w[0], mask, enc_ws);
     SININN_LAUNCH_CHECK("flownet_encgrad_pack");
     if (raise_lds(flownet_encgrad_kernel, FN_LDS, "flownet_encgrad")) return 1;
     hipLaunchKernelGGL(flownet_encgrad_kernel, dim3(cb), dim3(FN_NTHR), FN_LDS, st, q, (const float*)enc_ws, epart, fopen);   // not a function of k_active
@@ -960,6 +954,60 @@ int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws,
   return 0;
 }
 
-}  // namespace
+template <int KIND, bool PROG>
+static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipStream_t st) {
+  using E = Enc<KIND>;
+  if constexpr (PROG) {
+    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
+                 "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", flownet_forward_workspace_bytes(a),
+                 a->workspace ? a->workspace_bytes : (size_t)0);
+    SININN_CHECK(aligned16(a->workspace), "flownet_forward: workspace must be 16-byte aligned");
+    float* const w1p = static_cast<float*>(a->workspace);
+    float* const wc = w1p + (size_t)FN_HID * E::KW;
+    hipLaunchKernelGGL((flownet_pack_kernel<E::KW, E::LIVE>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
+    SININN_LAUNCH_CHECK("flownet_pack");
+    q.w[0] = w1p;
+    q.wc = wc;
+    q.ksteps = (open_encoded(a) + 15) / 16;
+  }
+  auto k = flownet_fwd_kernel<KIND, PROG>;
+  if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
+  const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS, st, q);
+  SININN_LAUNCH_CHECK("flownet_forward");
+  return 0;
+}
+
+int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
+  FlowNetDev q;
+  if (int rc = check_args(a, "flownet_forward", q)) return rc;
+  SININN_CHECK(a->flows != nullptr, "flownet_forward: null flows");
+  q.flows = a->flows;
+  if (a->saved) {
+    SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_forward: saved holds %zu bytes, %zu needed", a->saved_bytes,
+                 flownet_saved_bytes(q.N));
+    SININN_CHECK(aligned16(a->saved), "flownet_forward: saved must be 16-byte aligned");
+    q.saved = a->saved;
+  }
+  return for_kind(a->encoding, 1, [&](auto k) {
+    return a->progressive ? forward_kind_launch<decltype(k)::value, true>(a, q, st) : forward_kind_launch<decltype(k)::value, false>(a, q, st);
+  });
+}
+
+int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_launch(a, nullptr, nullptr, st); }
+
+int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                    hipStream_t st) {
+  const char* who = "flownet_backward_encgrad";
+  if (int rc = check_network(a, who)) return rc;
+  SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
+               a->encoding);
+  SININN_CHECK(g_enc_a != nullptr, "%s: null g_enc_a", who);
+  SININN_CHECK(enc_workspace != nullptr && enc_workspace_bytes >= flownet_encgrad_workspace_bytes(a),
+               "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
+               flownet_encgrad_workspace_bytes(a));
+  SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
+  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st);
+}
 
 }  // namespace sininn

@@ -11,9 +11,12 @@ backward in libsininn.so (csrc/flownet.hip).
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
 `encode.frequencies` / `encode.offsets`, `encode.sigma` / `encode.freqs`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
 first, then the four nn.Linear layers), so one `torch.manual_seed` gives the reference's numbers and a reference checkpoint
-loads.  The encodings of `model_dict` / `progressive_model_dict` / `grid_model_dict` are buffers: no gradient flows below layer 1.  The kernels are built for the ModelParams defaults
-(3 -> 512 -> 256 x 3 -> 4, and 3 -> 24 -> 256 x 3 -> 4 for the positional encoding); any other size raises, there is no second implementation behind this module, and calling a model
-directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512 encoding never exist here.
+loads.  One table describes them: `ENCODINGS` holds each encoding's constructor call once, a model class names its row and is plain or
+progressive, and `all_model_dict` maps the twelve network names to the classes; the reference's five dicts are views of it.  The
+encodings of `model_dict` / `progressive_model_dict` / `grid_model_dict` are buffers: no gradient flows below layer 1.  The kernels are
+built for the ModelParams defaults; any other size raises with the library's own list of the sizes it supports, there is no second
+implementation behind this module, and calling a model directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512
+encoding never exist here.
 
 The progressive models feed `cat((t, y, x), encode(x)) * mask` to layer 1 (515 features, first weight [256][515]); the mask is
 a global vector of 515 values that a controller of `sin_inn_amd.progressive` opens block by block (main.py:136-143).
@@ -32,15 +35,15 @@ or grad mode off, the plain backward / inference path runs and nothing extra is 
 `RBFG` / `PRBFG` use a periodic grid of Gaussian bumps: 256 frequencies j with buffers `encode.offsets` [256][3] and `encode.sigma`
 [256] (`linspace(0, 12 sqrt(3), 256)` plus half a step), period p = 2 / sigma_j.  Feature 2 j is
 `2 exp(-sigma_j^2 |((x + offsets_j) mod p) 2 - p|^2) - 1`, feature 2 j + 1 the same half a period further
-(`+ 1 / sigma_j`).  Both are buffers, the kernels evaluate them as a third encoding kind and the rest (masks, `k_active`, the
+(`+ 1 / sigma_j`).  Both are buffers, the kernels evaluate them as an encoding of their own (`RBFG = 3`) and the rest (masks, `k_active`, the
 backward pass) is the path of `RBF` / `PRBF`.
 
 `PE` / `PPE` use the axis-aligned positional encoding of NeRF: the buffer `encode.freqs` = 2^i pi (i = 0 .. 3, fp32), feature
 `6 f + d` is `cos(freqs[f] x_d)` and feature `6 f + 3 + d` is `sin(freqs[f] x_d)`: 24 features, the cosines of a frequency before
 its sines.  Layer 1 is [256][24] (PPE: [256][27], mask of 27 values, blocks of 6 that cut through a frequency).  The reference's
 `PositionalEncoding.forward` reshapes through `.view(-1, 21)` (model.py:332), which raises unless the number of points is a
-multiple of 7 and is the formula above where it runs; the kernels evaluate the formula for every N.  The kernels are a fourth
-encoding kind with a narrow layer 1 (two 16-feature K steps instead of 32, a 32-column weight-gradient tile).
+multiple of 7 and is the formula above where it runs; the kernels evaluate the formula for every N.  In the kernels it is the one
+encoding with a narrow layer 1 (two 16-feature K steps instead of 32, a 32-column weight-gradient tile).
 
 Out of scope: `siren`, `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
 spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
@@ -234,16 +237,30 @@ class PositionalEncoding(nn.Module):
         return self.freqs, None
 
 
+# encoding name -> its one constructor call; the plain and the progressive model of an encoding share it
+ENCODINGS = {
+    'RBF': lambda opt: RadialBasisEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf),
+    'FFN': lambda opt: GaussianRandomFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std),
+    'UFF': lambda opt: UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std),
+    'RFF': lambda opt: GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std),
+    'RBFG': lambda opt: UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf),
+    'PE': lambda opt: PositionalEncoding(opt.domain_dim, opt.num_frequencies_pe),
+}
+
+
 class _EncodedMlpModel(nn.Module):
-    """model.py:54-103, the part the flow trainer uses."""
+    """model.py:54-103, the part the flow trainer uses: `encode` is drawn first, then the MLP on `encoding_dim` inputs.  A model
+    class names its row of ENCODINGS."""
     encoding = None
+    is_progressive = False
 
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
-        self.encode = self.make_encoding(opt)
-        self.model = MLP([self.encode.output_channels] + opt.num_layers * [opt.hidden_dim] + [opt.output_channels])
+        self.encode = ENCODINGS[self.encoding](opt)
+        self.model = MLP([self.encoding_dim] + opt.num_layers * [opt.hidden_dim] + [opt.output_channels])
         self._axes = {}
+        self._ones = {}
 
     @property
     def encoding_dim(self):
@@ -252,10 +269,6 @@ class _EncodedMlpModel(nn.Module):
     @property
     def domain_dim(self):
         return self.opt.domain_dim
-
-    @property
-    def is_progressive(self):
-        return False
 
     def update_progress(self):
         return
@@ -271,48 +284,13 @@ class _EncodedMlpModel(nn.Module):
                                   'list and the encoding are never materialised')
 
 
-class RbfModel(_EncodedMlpModel):
-    """model.py:490-505."""
-
-    @staticmethod
-    def make_encoding(opt):
-        return RadialBasisEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
-
-
-class FFModel(_EncodedMlpModel):
-    """model.py:418-433."""
-
-    @staticmethod
-    def make_encoding(opt):
-        return GaussianRandomFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
-
-
-class UFFModel(_EncodedMlpModel):
-    """model.py:454-469."""
-
-    @staticmethod
-    def make_encoding(opt):
-        return UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
-
-
 class ProgressiveModel(_EncodedMlpModel):
-    """model.py:526-576: layer 1 reads cat((x, encode(x))) times a mask; `encode` is drawn first, then the MLP on 515 inputs."""
-
-    def __init__(self, opt):
-        nn.Module.__init__(self)
-        self.opt = opt
-        self.encode = self.get_encoding_layer(opt)
-        self.model = MLP([self.encoding_dim] + opt.num_layers * [opt.hidden_dim] + [opt.output_channels])
-        self._axes = {}
-        self._ones = {}
+    """model.py:526-576: layer 1 reads cat((x, encode(x))) times a mask: the MLP has 515 inputs (PPE: 27)."""
+    is_progressive = True
 
     @property
     def encoding_dim(self):
         return self.encode.output_channels + self.domain_dim
-
-    @property
-    def is_progressive(self):
-        return True
 
     def ones_mask(self, device):
         """the mask of a network evaluated without a controller, cached per device"""
@@ -321,83 +299,42 @@ class ProgressiveModel(_EncodedMlpModel):
         return self._ones[device]
 
 
-class PRBFModel(ProgressiveModel):
-    """model.py:621-625."""
-
-    @staticmethod
-    def get_encoding_layer(opt):
-        return RadialBasisEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
+def _model(name, base, encoding, doc):
+    return type(name, (base,), {'encoding': encoding, '__doc__': doc, '__module__': __name__})
 
 
-class PFFModel(ProgressiveModel):
-    """model.py:579-583."""
-
-    @staticmethod
-    def get_encoding_layer(opt):
-        return GaussianRandomFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
-
-
-class PUFFModel(ProgressiveModel):
-    """model.py:593-597."""
-
-    @staticmethod
-    def get_encoding_layer(opt):
-        return UniformFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
-
-
-class RFFModel(_EncodedMlpModel):
-    """model.py:436-451."""
-
-    @staticmethod
-    def make_encoding(opt):
-        return GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+# the registry: network name -> model class = (row of ENCODINGS, progressive?)
+RbfModel = _model('RbfModel', _EncodedMlpModel, 'RBF', 'model.py:490-505.')
+FFModel = _model('FFModel', _EncodedMlpModel, 'FFN', 'model.py:418-433.')
+UFFModel = _model('UFFModel', _EncodedMlpModel, 'UFF', 'model.py:454-469.')
+PRBFModel = _model('PRBFModel', ProgressiveModel, 'RBF', 'model.py:621-625.')
+PFFModel = _model('PFFModel', ProgressiveModel, 'FFN', 'model.py:579-583.')
+PUFFModel = _model('PUFFModel', ProgressiveModel, 'UFF', 'model.py:593-597.')
+RFFModel = _model('RFFModel', _EncodedMlpModel, 'RFF', 'model.py:436-451.')
+PRFFModel = _model('PRFFModel', ProgressiveModel, 'RFF', 'model.py:586-590.')
+RbfgModel = _model('RbfgModel', _EncodedMlpModel, 'RBFG', 'model.py:508-523.')
+PRBFGModel = _model('PRBFGModel', ProgressiveModel, 'RBFG', 'model.py:614-618.')
+PEModel = _model('PEModel', _EncodedMlpModel, 'PE', 'model.py:472-487.')
+PPEModel = _model('PPEModel', ProgressiveModel, 'PE', 'model.py:607-611.')
+all_model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel, 'PRBF': PRBFModel, 'PFF': PFFModel, 'PUFF': PUFFModel,
+                  'RFF': RFFModel, 'PRFF': PRFFModel, 'RBFG': RbfgModel, 'PRBFG': PRBFGModel, 'PE': PEModel, 'PPE': PPEModel}
 
 
-class PRFFModel(ProgressiveModel):
-    """model.py:586-590."""
-
-    @staticmethod
-    def get_encoding_layer(opt):
-        return GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std)
+def _view(*names):
+    return {name: all_model_dict[name] for name in names}
 
 
-class RbfgModel(_EncodedMlpModel):
-    """model.py:508-523."""
-
-    @staticmethod
-    def make_encoding(opt):
-        return UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
-
-
-class PRBFGModel(ProgressiveModel):
-    """model.py:614-618."""
-
-    @staticmethod
-    def get_encoding_layer(opt):
-        return UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf)
+# the reference's five dicts, as views of the registry
+model_dict = _view('RBF', 'FFN', 'UFF')
+progressive_model_dict = _view('PRBF', 'PFF', 'PUFF')
+learnable_model_dict = _view('RFF', 'PRFF')                       # the encoding is trained; PRFF is progressive as well
+grid_model_dict = _view('RBFG', 'PRBFG')                          # the radial-basis grid; PRBFG is progressive
+positional_model_dict = _view('PE', 'PPE')                        # 24 features; PPE is progressive
 
 
-class PEModel(_EncodedMlpModel):
-    """model.py:472-487."""
-
-    @staticmethod
-    def make_encoding(opt):
-        return PositionalEncoding(opt.domain_dim, opt.num_frequencies_pe)
-
-
-class PPEModel(ProgressiveModel):
-    """model.py:607-611."""
-
-    @staticmethod
-    def get_encoding_layer(opt):
-        return PositionalEncoding(opt.domain_dim, opt.num_frequencies_pe)
-
-
-model_dict = {'RBF': RbfModel, 'FFN': FFModel, 'UFF': UFFModel}
-progressive_model_dict = {'PRBF': PRBFModel, 'PFF': PFFModel, 'PUFF': PUFFModel}
-learnable_model_dict = {'RFF': RFFModel, 'PRFF': PRFFModel}       # the encoding is trained; PRFF is progressive as well
-grid_model_dict = {'RBFG': RbfgModel, 'PRBFG': PRBFGModel}        # the radial-basis grid; PRBFG is progressive
-positional_model_dict = {'PE': PEModel, 'PPE': PPEModel}          # 24 features; PPE is progressive
+def _on_gpu(t, what='tensor'):
+    if not t.is_cuda:
+        raise NotImplementedError(f'sin-inn_amd flownet runs on the GPU only (got a CPU {what})')
 
 
 def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
@@ -406,30 +343,27 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
     a.encoding = net.encode.kind
     a.progressive = int(bool(net.is_progressive))
     a.enc_dim, a.hidden, a.layers, a.out_dim = net.encoding_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
-    supported = (net.opt.domain_dim == 3 and len(lins) == 4 and _lib.lib().sininn_flownet_supported(C.byref(a)))
-    if not supported:
-        raise ValueError(f'flownet kernels are built for 3 -> 512 (progressive: 515; PE: 24, PPE: 27) -> 256 x 3 -> 4; got {net.opt.domain_dim} -> '
-                         f'{a.enc_dim} -> {a.hidden} x {a.layers} -> {a.out_dim}')
+    if not _lib.lib().sininn_flownet_supported(C.byref(a)):      # the library's refusal names the sizes it is built for
+        raise ValueError(_lib.lib().sininn_last_error().decode())
+    if net.opt.domain_dim != 3 or len(lins) != 4:
+        raise ValueError(f'flownet kernels take 3 coordinates and 4 linear layers; got {net.opt.domain_dim} and {len(lins)}')
     if a.progressive:
         if mask is None:
             raise ValueError('a progressive network is evaluated under a mask (flow_fields supplies all ones for a bare model)')
-        if not mask.is_cuda:
-            raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU mask)')
+        _on_gpu(mask, 'mask')
         assert mask.dtype == torch.float32 and mask.is_contiguous() and tuple(mask.shape) == (a.enc_dim,)
         a.mask = ptr(mask)
         a.k_active = a.enc_dim if k_active is None else int(k_active)
     elif mask is not None:
         raise ValueError('a mask needs a progressive network')
     for t in (times, ys, xs):
-        if not t.is_cuda:
-            raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+        _on_gpu(t)
     a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
     a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
     if enc_a is None:
         ea, eb = net.encode.kernel_buffers()
     else:                                                # learnable frequencies: F_eff of this call
-        if not enc_a.is_cuda:
-            raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+        _on_gpu(enc_a)
         assert net.encode.kind == FOURIER and enc_a.dtype == torch.float32 and enc_a.is_contiguous() and tuple(enc_a.shape) == (3, 256)
         ea, eb = enc_a, None
     a.enc_a, a.enc_b = ptr(ea), ptr(eb)
@@ -476,8 +410,7 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, m
     times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
     a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
     n = a.T * a.H * a.W
-    if not dflows.is_cuda:
-        raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+    _on_gpu(dflows)
     dflows = dflows.contiguous()
     assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
     nbytes = _lib.lib().sininn_flownet_workspace_bytes(n)
@@ -569,8 +502,7 @@ def flow_fields(net, times, h, w, scale, override_mask=None):
     model or a controller around a progressive model; `override_mask` (515 values, PPE: 27; progressive networks only) replaces the
     controller's mask.  A learnable encoding (RFF / PRFF) contributes F_eff, computed here with torch ops; its gradient is computed
     only if `encode.frequencies` requires one."""
-    if not times.is_cuda:
-        raise NotImplementedError('sin-inn_amd flownet runs on the GPU only (got a CPU tensor)')
+    _on_gpu(times)
     assert times.dtype == torch.float32 and times.dim() == 1
     net, mask = _resolve_mask(net, override_mask, times.device)
     ys, xs = grid_axes(net, times, h, w)

@@ -1,16 +1,20 @@
 """CPU: the flow-field network port (sin_inn_amd/flownet.py) against fixtures written by the reference's own model.py
 (tests/golden/make_golden_flownet.py), and the float64 restatement of the network that tests/test_gpu_flownet.py measures the
-kernels with.  The restatement lives here because oracle/ is not to change; `restate` is imported by the GPU test.
+kernels with (tests/flownet_refs.py: oracle/ is not to change).
 """
 import ctypes as C
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from flownet_refs import net_tensors, own_gates, restate  # noqa: E402
+
 NETS = ('RBF', 'FFN', 'UFF')
 SEED = {'RBF': 101, 'FFN': 202, 'UFF': 303}
 TIMES, GH, GW, SCALE, STRIDE = (0.0, 0.5), 20, 28, 3.0, 97
@@ -25,39 +29,6 @@ def build(name):
     from sin_inn_amd import flownet
     torch.manual_seed(SEED[name])
     return flownet.model_dict[name](flownet.ModelParams())
-
-
-def encode(name, bufs, poses):
-    """model.py:349-356 (RBF) / model.py:230-238 (FFN, UFF), in the dtype of `poses`"""
-    if name == 'RBF':
-        centres, sigma = bufs['encode.centres'].to(poses), bufs['encode.sigma'].to(poses)
-        out = (poses[:, None, :] - centres[None, :, :]).pow(2).sum(2)
-        return torch.exp(-(out * sigma[None, :] ** 2))
-    freq = bufs['encode.frequencies'].to(poses)
-    out = torch.matmul(poses * 2 * np.pi, freq)
-    return torch.stack((torch.sin(out), torch.cos(out)), dim=2).view(poses.shape[0], -1)
-
-
-def restate(name, bufs, weights, times, ys, xs, scale, dtype, gates=None):
-    """FlowTrainer.forward (trainer.py:37-45) in plain torch in `dtype`, from fp32 axis vectors / buffers / weights (widened).
-    weights: [W1, b1, .., W4, b4] (autograd leaves of `dtype` if gradients are wanted); gates: None (ReLU) or three bool
-    (N, 256) tensors that REPLACE the ReLU decision: h = pre * gate.  Returns flows (t, 4, h, w)."""
-    t, h, w = times.numel(), ys.numel(), xs.numel()
-    weights = [p.to(dtype) for p in weights]
-    gt, gh, gw = torch.meshgrid(times.to(dtype), ys.to(dtype), xs.to(dtype), indexing='ij')
-    poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-    x = encode(name, bufs, poses)
-    for l in range(3):
-        pre = torch.nn.functional.linear(x, weights[2 * l], weights[2 * l + 1])
-        x = torch.relu(pre) if gates is None else pre * gates[l].to(dtype)
-    out = torch.nn.functional.linear(x, weights[6], weights[7])
-    return out.view(t, h, w, 4).permute(0, 3, 1, 2) * scale
-
-
-def net_tensors(net, device='cpu'):
-    bufs = {k: v.detach().to(device) for k, v in net.state_dict().items() if k.startswith('encode.')}
-    weights = [p.detach().to(device) for lin in net.linears() for p in (lin.weight, lin.bias)]
-    return bufs, weights
 
 
 @pytest.mark.parametrize('name', NETS)
@@ -93,16 +64,7 @@ def test_restatement_reproduces_the_reference_in_float64(gold, name):
     ref32 = torch.from_numpy(gold[f'{name}_out32'])
     assert float((f32 - ref32).abs().max() / ref32.abs().max()) < 1e-4      # two fp32 evaluations (thread count, BLAS blocking)
     # forced gates equal to the ReLU's own decision change nothing
-    with torch.no_grad():
-        x = None
-        gates = []
-        t, h, w = len(TIMES), GH, GW
-        gt, gh, gw = torch.meshgrid(times.double(), ys.double(), xs.double(), indexing='ij')
-        x = encode(name, bufs, torch.stack((gt, gh, gw), dim=-1).view(-1, 3))
-        for l in range(3):
-            x = torch.relu(torch.nn.functional.linear(x, w64[2 * l], w64[2 * l + 1]))
-            gates.append(x > 0)
-    forced = restate(name, bufs, w64, times, ys, xs, SCALE, torch.float64, gates)
+    forced = restate(name, bufs, w64, times, ys, xs, SCALE, torch.float64, gates=own_gates(name, bufs, w64, times, ys, xs))
     assert float((forced.detach() - ref).abs().max() / ref.abs().max()) < 1e-12
     up = torch.from_numpy(gold['up']).double()
     grads = torch.autograd.grad((forced * up).sum(), w64)
@@ -162,3 +124,29 @@ def test_other_sizes_raise_instead_of_falling_back():
     fake = torch.zeros(2)
     with pytest.raises(ValueError):
         flownet._args(net, fake, fake, fake, 1.0)
+
+
+def test_registry_is_the_union_of_the_five_dicts_and_agrees_with_the_library():
+    """the twelve names of `all_model_dict` are the disjoint union of the five dicts; the library supports each model's own
+    (encoding, progressive, enc_dim) and refuses it one feature off either way or as encoding 2, which is none of the library's"""
+    from sin_inn_amd import _lib, flownet
+    views = (flownet.model_dict, flownet.progressive_model_dict, flownet.learnable_model_dict, flownet.grid_model_dict,
+             flownet.positional_model_dict)
+    union = {}
+    for view in views:
+        union.update(view)
+    assert sum(len(view) for view in views) == len(union) == len(flownet.all_model_dict) == 12
+    assert union == flownet.all_model_dict
+    lib = _lib.lib()
+    for name, cls in flownet.all_model_dict.items():
+        net = cls(flownet.ModelParams())
+        assert net.is_progressive == (name in ('PRBF', 'PFF', 'PUFF', 'PRFF', 'PRBFG', 'PPE')), name
+        a = _lib.FlowNetArgs()
+        a.hidden, a.layers, a.out_dim = 256, 3, 4
+        a.encoding, a.progressive, a.enc_dim = net.encode.kind, int(net.is_progressive), net.encoding_dim
+        assert lib.sininn_flownet_supported(C.byref(a)) == 1, name
+        for off in (-1, 1):
+            a.enc_dim = net.encoding_dim + off
+            assert lib.sininn_flownet_supported(C.byref(a)) == 0, (name, off)
+        a.enc_dim, a.encoding = net.encoding_dim, 2
+        assert lib.sininn_flownet_supported(C.byref(a)) == 0, name

@@ -1,16 +1,20 @@
 """CPU: the radial-basis-grid flow-field networks RBFG / PRBFG (sin_inn_amd/flownet.py) against a fixture written by the reference's
 own model.py and progressive_controller.py (tests/golden/make_golden_flownet_grid.py), and the float64 restatement of the encoding
-and the network that tests/test_gpu_flownet_grid.py measures the kernels with (`encode_grid`, `restate`, imported there).
+and the network that tests/test_gpu_flownet_grid.py measures the kernels with (`encode_grid`, `restate` of tests/flownet_refs.py).
 """
 import ctypes as C
 import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from flownet_refs import net_tensors, own_gates, restate  # noqa: E402
+
 NETS = ('RBFG', 'PRBFG')
 SEED = {'RBFG': 707, 'PRBFG': 808}
 TIMES, GH, GW, SCALE, STRIDE = (0.0, 0.5), 20, 28, 3.0, 97
@@ -39,62 +43,6 @@ def flow_main():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def encode_grid(bufs, poses):
-    """model.py:375-387 in the dtype of `poses`, from the fp32 buffers (widened): (N, 512), feature 2 j = e(xa), 2 j + 1 = e(xb)"""
-    offsets, sigma = bufs['encode.offsets'].to(poses), bufs['encode.sigma'].to(poses)
-    x_a = poses[:, None, :] + offsets[None, :]
-    x_b = x_a + (1 / sigma[None, :, None])
-    out = torch.stack((x_a, x_b), dim=2)
-    out = (out % (2 / sigma[None, :, None, None])) * 2 - (2 / sigma[None, :, None, None])
-    out = out.pow(2).sum(3)
-    out = out * sigma[None, :, None] ** 2
-    out = out.view(-1, 2 * sigma.numel())
-    return torch.exp(-out) * 2 - 1
-
-
-def poses_of(times, ys, xs, dtype):
-    gt, gh, gw = torch.meshgrid(times.to(dtype), ys.to(dtype), xs.to(dtype), indexing='ij')
-    return torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-
-
-def restate(name, bufs, weights, times, ys, xs, scale, dtype, mask=None, gates=None):
-    """FlowTrainer.forward (trainer.py:37-45) on RBFG (mask None) or PRBFG (layer 1 reads cat((poses, encode(poses))) * mask,
-    model.py:532-535) in plain torch in `dtype`; arguments as `restate` of tests/test_flownet_progressive_golden.py."""
-    t, h, w = times.numel(), ys.numel(), xs.numel()
-    weights = [p.to(dtype) for p in weights]
-    poses = poses_of(times, ys, xs, dtype)
-    x = encode_grid(bufs, poses)
-    if name == 'PRBFG':
-        x = torch.cat((poses, x), dim=-1) * mask.to(poses)[None, :]
-    else:
-        assert mask is None
-    for l in range(3):
-        pre = torch.nn.functional.linear(x, weights[2 * l], weights[2 * l + 1])
-        x = torch.relu(pre) if gates is None else pre * gates[l].to(dtype)
-    out = torch.nn.functional.linear(x, weights[6], weights[7])
-    return out.view(t, h, w, 4).permute(0, 3, 1, 2) * scale
-
-
-def net_tensors(net, device='cpu'):
-    bufs = {k: v.detach().to(device) for k, v in net.state_dict().items() if k.startswith('encode.')}
-    weights = [p.detach().to(device) for lin in net.linears() for p in (lin.weight, lin.bias)]
-    return bufs, weights
-
-
-def own_gates(name, bufs, w64, times, ys, xs, mask):
-    """the ReLU decisions of the float64 network itself"""
-    with torch.no_grad():
-        poses = poses_of(times, ys, xs, torch.float64)
-        x = encode_grid(bufs, poses)
-        if name == 'PRBFG':
-            x = torch.cat((poses, x), dim=-1) * mask.double()[None, :]
-        gates = []
-        for l in range(3):
-            x = torch.relu(torch.nn.functional.linear(x, w64[2 * l], w64[2 * l + 1]))
-            gates.append(x > 0)
-    return gates
 
 
 @pytest.mark.parametrize('name', NETS)

@@ -5,12 +5,16 @@ restatement that tests/test_gpu_flownet_learnable.py measures the kernels with, 
 import ctypes as C
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from flownet_refs import net_tensors, own_gates, restate  # noqa: E402
+
 NETS = ('RFF', 'PRFF')
 SEED = {'RFF': 707, 'PRFF': 808}
 CASES = {'RFF': ('plain',), 'PRFF': ('ones', 'init', 'ramp')}
@@ -38,34 +42,6 @@ def f_eff(frequencies, magnitudes):
 
 def host_mask(gold, case):
     return None if case in ('plain', 'ones') else torch.from_numpy(gold[f'mask_{case}'])
-
-
-def restate(name, feff, weights, times, ys, xs, scale, dtype, mask=None, gates=None):
-    """FlowTrainer.forward (trainer.py:37-45) on RFFModel / PRFFModel in plain torch in `dtype`, from the frequency matrix `feff`
-    (3, 256) the network uses (model.py:273-278), fp32 axis vectors and weights [W1, b1, .., W4, b4] (autograd leaves of `dtype` if
-    gradients are wanted).  PRFF: layer 1 reads cat((poses, encoding)) * mask (mask: 515 values or None for the bare network).
-    gates: None (ReLU) or three bool (N, 256) tensors that REPLACE the ReLU decision.  Returns flows (t, 4, h, w)."""
-    t, h, w = times.numel(), ys.numel(), xs.numel()
-    weights = [p.to(dtype) for p in weights]
-    gt, gh, gw = torch.meshgrid(times.to(dtype), ys.to(dtype), xs.to(dtype), indexing='ij')
-    poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-    out = torch.matmul(poses * 2 * np.pi, feff.to(dtype))
-    x = torch.stack((torch.sin(out), torch.cos(out)), dim=2).view(poses.shape[0], -1)
-    if name == 'PRFF':
-        x = torch.cat((poses, x), dim=-1)
-        if mask is not None:
-            x = x * mask.to(x)[None, :]
-    for l in range(3):
-        pre = torch.nn.functional.linear(x, weights[2 * l], weights[2 * l + 1])
-        x = torch.relu(pre) if gates is None else pre * gates[l].to(dtype)
-    out = torch.nn.functional.linear(x, weights[6], weights[7])
-    return out.view(t, h, w, 4).permute(0, 3, 1, 2) * scale
-
-
-def net_tensors(net, device='cpu'):
-    """(frequencies, magnitudes, [W1, b1, .., W4, b4]) detached on `device`"""
-    weights = [p.detach().to(device) for lin in net.linears() for p in (lin.weight, lin.bias)]
-    return net.encode.frequencies.detach().to(device), net.encode.magnitudes.detach().to(device), weights
 
 
 @pytest.mark.parametrize('name', NETS)
@@ -111,7 +87,8 @@ def test_controller_masks_of_the_port(gold):
 @pytest.mark.parametrize('name', NETS)
 def test_restatement_reproduces_the_reference_in_float64(gold, name):
     net = build(name)
-    freq, mag, weights = net_tensors(net)
+    bufs, weights = net_tensors(net)
+    freq, mag = bufs['encode.frequencies'], bufs['encode.magnitudes']
     times, ys, xs = torch.tensor(TIMES), torch.linspace(-1, 1, GH), torch.linspace(-1, 1, GW)
     up = torch.from_numpy(gold['up']).double()
     for case in CASES[name]:
@@ -126,19 +103,7 @@ def test_restatement_reproduces_the_reference_in_float64(gold, name):
         ref32 = torch.from_numpy(gold[f'{name}_out32_{case}'])
         assert float((f32 - ref32).abs().max() / ref32.abs().max()) < 1e-4, case     # two fp32 evaluations (thread count, BLAS blocking)
         # forced gates equal to the ReLU's own decision change nothing
-        with torch.no_grad():
-            gt, gh, gw = torch.meshgrid(times.double(), ys.double(), xs.double(), indexing='ij')
-            poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-            ph = torch.matmul(poses * 2 * np.pi, f_eff(f64, mag))
-            x = torch.stack((torch.sin(ph), torch.cos(ph)), dim=2).view(poses.shape[0], -1)
-            if name == 'PRFF':
-                x = torch.cat((poses, x), dim=-1)
-                if mask is not None:
-                    x = x * mask.double()[None, :]
-            gates = []
-            for l in range(3):
-                x = torch.relu(torch.nn.functional.linear(x, w64[2 * l], w64[2 * l + 1]))
-                gates.append(x > 0)
+        gates = own_gates(name, f_eff(f64, mag), w64, times, ys, xs, mask)
         forced = restate(name, f_eff(f64, mag), w64, times, ys, xs, SCALE, torch.float64, mask, gates)
         assert float((forced.detach() - ref).abs().max() / ref.abs().max()) < 1e-12, case
         grads = torch.autograd.grad((forced * up).sum(), [f64] + w64)

@@ -1,6 +1,6 @@
 """CPU: the positional-encoding flow-field networks PE / PPE (sin_inn_amd/flownet.py) against a fixture written by the reference's own
 model.py and progressive_controller.py (tests/golden/make_golden_flownet_pe.py), and the float64 restatement of the encoding and the
-network that tests/test_gpu_flownet_pe.py measures the kernels with (`encode_pe`, `restate`, imported there).
+network that tests/test_gpu_flownet_pe.py measures the kernels with (`encode_pe`, `restate` of tests/flownet_refs.py).
 
 The reference's PositionalEncoding.forward reshapes through `.view(-1, 21)` and raises unless the number of points is a multiple of
 7; the fixture's grid has 1176 = 7 * 168 points.  `encode_pe` is the formula itself and runs for every N.
@@ -8,12 +8,16 @@ The reference's PositionalEncoding.forward reshapes through `.view(-1, 21)` and 
 import ctypes as C
 import importlib.util
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from flownet_refs import encode_pe, net_tensors, own_gates, poses_of, restate  # noqa: E402
+
 NETS = ('PE', 'PPE')
 SEED = {'PE': 909, 'PPE': 1010}
 TIMES, GH, GW, SCALE, STRIDE = (0.0, 0.5), 21, 28, 3.0, 97
@@ -43,57 +47,6 @@ def flow_main():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def encode_pe(bufs, poses):
-    """model.py:331-332 as a formula, in the dtype of `poses`, from the fp32 buffer (widened): (N, 24), feature 6 f + d =
-    cos(freqs[f] x_d), 6 f + 3 + d = sin(freqs[f] x_d).  No einsum: one product per element, for every N."""
-    freqs = bufs['encode.freqs'].to(poses)
-    arg = freqs[None, :, None] * poses[:, None, :]
-    return torch.cat((torch.cos(arg), torch.sin(arg)), dim=2).reshape(poses.shape[0], -1)
-
-
-def poses_of(times, ys, xs, dtype):
-    gt, gh, gw = torch.meshgrid(times.to(dtype), ys.to(dtype), xs.to(dtype), indexing='ij')
-    return torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-
-
-def restate(name, bufs, weights, times, ys, xs, scale, dtype, mask=None, gates=None):
-    """FlowTrainer.forward (trainer.py:37-45) on PE (mask None) or PPE (layer 1 reads cat((poses, encode(poses))) * mask,
-    model.py:532-535) in plain torch in `dtype`; arguments as `restate` of tests/test_flownet_grid_golden.py."""
-    t, h, w = times.numel(), ys.numel(), xs.numel()
-    weights = [p.to(dtype) for p in weights]
-    poses = poses_of(times, ys, xs, dtype)
-    x = encode_pe(bufs, poses)
-    if name == 'PPE':
-        x = torch.cat((poses, x), dim=-1) * mask.to(poses)[None, :]
-    else:
-        assert mask is None
-    for l in range(3):
-        pre = torch.nn.functional.linear(x, weights[2 * l], weights[2 * l + 1])
-        x = torch.relu(pre) if gates is None else pre * gates[l].to(dtype)
-    out = torch.nn.functional.linear(x, weights[6], weights[7])
-    return out.view(t, h, w, 4).permute(0, 3, 1, 2) * scale
-
-
-def net_tensors(net, device='cpu'):
-    bufs = {k: v.detach().to(device) for k, v in net.state_dict().items() if k.startswith('encode.')}
-    weights = [p.detach().to(device) for lin in net.linears() for p in (lin.weight, lin.bias)]
-    return bufs, weights
-
-
-def own_gates(name, bufs, w64, times, ys, xs, mask):
-    """the ReLU decisions of the float64 network itself"""
-    with torch.no_grad():
-        poses = poses_of(times, ys, xs, torch.float64)
-        x = encode_pe(bufs, poses)
-        if name == 'PPE':
-            x = torch.cat((poses, x), dim=-1) * mask.double()[None, :]
-        gates = []
-        for l in range(3):
-            x = torch.relu(torch.nn.functional.linear(x, w64[2 * l], w64[2 * l + 1]))
-            gates.append(x > 0)
-    return gates
 
 
 def fixture_axes():

@@ -12,7 +12,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_flownet_golden import encode  # noqa: E402
+from flownet_refs import net_tensors, own_gates, restate  # noqa: E402
 
 NETS = ('PRBF', 'PFF', 'PUFF')
 SEED = {'PRBF': 404, 'PFF': 505, 'PUFF': 606}
@@ -42,27 +42,6 @@ def controller(kind, net):
 
 def scripted_loss(i):
     return torch.tensor(0.5 if i < 300 else 5e-4)
-
-
-def restate(name, bufs, weights, times, ys, xs, scale, dtype, mask, gates=None):
-    """FlowTrainer.forward (trainer.py:37-45) on a progressive network (model.py:532-535, 89-99) in plain torch in `dtype`:
-    layer 1 reads cat((poses, encode(poses))) * mask.  Arguments as `restate` of tests/test_flownet_golden.py; mask: 515 values."""
-    t, h, w = times.numel(), ys.numel(), xs.numel()
-    weights = [p.to(dtype) for p in weights]
-    gt, gh, gw = torch.meshgrid(times.to(dtype), ys.to(dtype), xs.to(dtype), indexing='ij')
-    poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-    x = torch.cat((poses, encode('RBF' if name == 'PRBF' else 'FFN', bufs, poses)), dim=-1) * mask.to(poses)[None, :]
-    for l in range(3):
-        pre = torch.nn.functional.linear(x, weights[2 * l], weights[2 * l + 1])
-        x = torch.relu(pre) if gates is None else pre * gates[l].to(dtype)
-    out = torch.nn.functional.linear(x, weights[6], weights[7])
-    return out.view(t, h, w, 4).permute(0, 3, 1, 2) * scale
-
-
-def net_tensors(net, device='cpu'):
-    bufs = {k: v.detach().to(device) for k, v in net.state_dict().items() if k.startswith('encode.')}
-    weights = [p.detach().to(device) for lin in net.linears() for p in (lin.weight, lin.bias)]
-    return bufs, weights
 
 
 @pytest.mark.parametrize('name', NETS)
@@ -161,15 +140,7 @@ def test_restatement_reproduces_the_reference_in_float64(gold, name):
             assert float((f32 - ref32).abs().max() / ref32.abs().max()) < 1e-4, k   # two fp32 evaluations (thread count, BLAS blocking)
     # gradients under the ramping mask, with forced gates equal to the ReLU's own decision
     mask = masks['ramp']
-    with torch.no_grad():
-        gt, gh, gw = torch.meshgrid(times.double(), ys.double(), xs.double(), indexing='ij')
-        poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-        x = torch.cat((poses, encode('RBF' if name == 'PRBF' else 'FFN', bufs, poses)), dim=-1) * mask.double()[None, :]
-        gates = []
-        for l in range(3):
-            x = torch.relu(torch.nn.functional.linear(x, w64[2 * l], w64[2 * l + 1]))
-            gates.append(x > 0)
-    forced = restate(name, bufs, w64, times, ys, xs, SCALE, torch.float64, mask, gates)
+    forced = restate(name, bufs, w64, times, ys, xs, SCALE, torch.float64, mask, own_gates(name, bufs, w64, times, ys, xs, mask))
     ref = torch.from_numpy(gold[f'{name}_out64_ramp'])
     assert float((forced.detach() - ref).abs().max() / ref.abs().max()) < 1e-12
     up = torch.from_numpy(gold['up']).double()

@@ -3,7 +3,7 @@
 (t = 1, 436 x 1024).
 
 Method (that of tests/test_gpu_flowloss_sizes.py):
-  * the reference is `restate` of tests/test_flownet_golden.py in float64 on the GPU, from the fp32 weights, buffers and axis vectors
+  * the reference is `restate` of tests/flownet_refs.py in float64 on the GPU, from the fp32 weights, buffers and axis vectors
     the kernel received, widened; test_flownet_golden.py ties it to the reference's own model.py through the fixture, and on the fixture
     grid the kernel is also compared with the fixture's stored outputs directly;
   * the unit of error is the deviation of the same formula evaluated in fp32 torch from float64 on the same inputs, measured in the
@@ -37,7 +37,8 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_flownet_golden import NETS, SCALE, TIMES, GH, GW, build, net_tensors, restate  # noqa: E402
+from flownet_refs import net_tensors, restate  # noqa: E402
+from test_flownet_golden import NETS, SCALE, TIMES, GH, GW, build  # noqa: E402
 
 F64 = torch.float64
 MULT, CEIL = 4.0, 1e-4
@@ -107,7 +108,7 @@ def test_forward_and_backward_against_float64(dev, name, grid):
     grads_ref = {}
     for dtype in (F64, torch.float32):
         w = [p.to(dtype).requires_grad_(True) for p in weights]
-        flows = restate(name, bufs, w, times, ys, xs, SCALE, dtype, gates)
+        flows = restate(name, bufs, w, times, ys, xs, SCALE, dtype, gates=gates)
         grads_ref[dtype] = torch.autograd.grad((flows * up.to(dtype)).sum(), w)
         del flows
     wbytes = _lib.lib().sininn_flownet_workspace_bytes(n)

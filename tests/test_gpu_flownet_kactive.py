@@ -45,14 +45,15 @@ Measured on an MI355X (worst error / budget over all cases, from the `ratio(...)
 import os
 import sys
 
-import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import flownet_refs as R  # noqa: E402
 import test_flownet_learnable_golden as L  # noqa: E402
 import test_flownet_progressive_golden as P  # noqa: E402
+from flownet_refs import closed_frequencies, is_plus_zero, nan_buffers, restate  # noqa: E402
 from test_gpu_flownet import CEIL, F64, MULT, axes, check  # noqa: E402
 
 assert (MULT, CEIL) == (4.0, 1e-4)                     # the standing budget; this file does not choose one
@@ -96,23 +97,12 @@ def holes_mask():
     return mask
 
 
-def closed_frequencies(hmask):
-    return (hmask[3::2] == 0) & (hmask[4::2] == 0)
-
-
 def restate_h1(name, enc, weights, times, ys, xs, scale, dtype, mask, gates=None):
-    """`restate` of the two golden files (enc: the buffers of PRBF / PFF / PUFF, or F_eff (3, 256) of PRFF) that also returns h1, the
-    output of layer 1; run_case ties its flows to theirs"""
+    """`restate` of tests/flownet_refs.py (enc: the buffers of PRBF / PFF / PUFF, or F_eff (3, 256) of PRFF) that also returns h1, the
+    output of layer 1; run_case ties its flows to that one's"""
     t, h, w = times.numel(), ys.numel(), xs.numel()
     weights = [p.to(dtype) for p in weights]
-    gt, gh, gw = torch.meshgrid(times.to(dtype), ys.to(dtype), xs.to(dtype), indexing='ij')
-    poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
-    if name == 'PRFF':
-        ph = torch.matmul(poses * 2 * np.pi, enc.to(dtype))
-        e = torch.stack((torch.sin(ph), torch.cos(ph)), dim=2).view(poses.shape[0], -1)
-    else:
-        e = P.encode('RBF' if name == 'PRBF' else 'FFN', enc, poses)
-    x = torch.cat((poses, e), dim=-1) * mask.to(poses)[None, :]
+    x = R.layer1_input(name, enc, R.poses_of(times, ys, xs, dtype), mask)
     h1 = None
     for l in range(3):
         pre = torch.nn.functional.linear(x, weights[2 * l], weights[2 * l + 1])
@@ -120,14 +110,6 @@ def restate_h1(name, enc, weights, times, ys, xs, scale, dtype, mask, gates=None
         h1 = x if l == 0 else h1
     out = torch.nn.functional.linear(x, weights[6], weights[7])
     return out.view(t, h, w, 4).permute(0, 3, 1, 2) * scale, h1
-
-
-def restate(name, enc, *rest):
-    return (L if name == 'PRFF' else P).restate(name, enc, *rest)
-
-
-def is_plus_zero(x):
-    return bool((x == 0.0).all()) and not bool(torch.signbit(x).any())
 
 
 def check_or_zero(tag, got, r64, r32, signed=True):
@@ -151,11 +133,12 @@ class Net:
         self.name, self.prff = name, name == 'PRFF'
         self.net = (L if self.prff else P).build(name).to(dev)
         if self.prff:
-            self.freq, self.mag, self.weights = L.net_tensors(self.net, dev)
+            bufs, self.weights = R.net_tensors(self.net, dev)
+            self.freq, self.mag = bufs['encode.frequencies'], bufs['encode.magnitudes']
             self.enc = L.f_eff(self.freq, self.mag).contiguous()              # the fp32 matrix the kernels receive
             self.ekw = dict(enc_a=self.enc)
         else:
-            self.enc, self.weights = P.net_tensors(self.net, dev)
+            self.enc, self.weights = R.net_tensors(self.net, dev)
             self.ekw = {}
         self.weights = [w.clone() for w in self.weights]                    # the reference keeps the clean weights
 
@@ -165,24 +148,12 @@ def live_features(nt, times, ys, xs):
     narrow width gives exp(-x) below FLT_MIN at every point; fp32 rounds or flushes that to zero, and the gradient column of such a
     feature is honestly all zero although its mask is open (float64 holds 1e-60 there; the comparison with float64 covers it).  The
     factor 2 is far above the 1e-5 that the fp32 rounding of an exponent of 87 moves the value by.  Fourier features are all live"""
-    gt, gh, gw = torch.meshgrid(times.to(F64), ys.to(F64), xs.to(F64), indexing='ij')
-    poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
+    poses = R.poses_of(times, ys, xs, F64)
     live = torch.ones(515, dtype=torch.bool, device=poses.device)
     if nt.name == 'PRBF':
-        live[3:] = P.encode('RBF', nt.enc, poses).abs().amax(dim=0) >= 2 * torch.finfo(F32).tiny
+        live[3:] = R.encode_rbf(nt.enc, poses).abs().amax(dim=0) >= 2 * torch.finfo(F32).tiny
     live[:3] = poses.abs().amax(dim=0) > 0
     return live
-
-
-def nan_buffers(n, dev):
-    from sin_inn_amd import _lib
-    lib = _lib.lib()
-    saved = torch.full((3, lib.sininn_flownet_saved_bytes(n) // (3 * 256 * 4), 256), NAN, device=dev)
-    ws = torch.full((lib.sininn_flownet_workspace_bytes(n) // 4,), NAN, device=dev)
-    a = _lib.FlowNetArgs()
-    a.encoding = 1
-    ews = torch.full((lib.sininn_flownet_encgrad_workspace_bytes(a) // 4,), NAN, device=dev)
-    return saved, ws, ews
 
 
 def run_kernels(nt, grid, hmask, k, dev):
@@ -255,7 +226,7 @@ def run_case(dev, name, grid, hmask, k, tag):
         for dtype in (F64, F32):
             ref[dtype] = restate_h1(name, nt.enc, nt.weights, times, ys, xs, SCALE, dtype, mask)
             theirs = restate(name, nt.enc, nt.weights, times, ys, xs, SCALE, dtype, mask)
-            assert torch.equal(ref[dtype][0], theirs), f'restate_h1 is not the restatement of the golden file ({dtype})'
+            assert torch.equal(ref[dtype][0], theirs), f'restate_h1 is not the shared restatement ({dtype})'
             del theirs
     check(f'{tag} flows', out['flows'], ref[F64][0], ref[F32][0])
     check_or_zero(f'{tag} h1', saved[0, :n], ref[F64][1], ref[F32][1])

@@ -37,7 +37,8 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_flownet_learnable_golden import EPSILON, MAX_ITERATION, NETS, SCALE, build, f_eff, net_tensors, restate  # noqa: E402
+from flownet_refs import closed_frequencies, nan_buffers, net_tensors, restate  # noqa: E402
+from test_flownet_learnable_golden import EPSILON, MAX_ITERATION, NETS, SCALE, build, f_eff  # noqa: E402
 from test_gpu_flownet import CEIL, F64, GRIDS, axes, check  # noqa: E402
 
 SMALL = ('fixture', 'ragged')
@@ -69,27 +70,12 @@ def host_mask(kind):
     return ctl.mask.clone()
 
 
-def closed_frequencies(hmask):
-    return (hmask[3::2] == 0) & (hmask[4::2] == 0)
-
-
-def nan_buffers(n, dev):
-    from sin_inn_amd import _lib
-    lib = _lib.lib()
-    saved = torch.full((3, lib.sininn_flownet_saved_bytes(n) // (3 * 256 * 4), 256), float('nan'), device=dev)
-    ws = torch.full((lib.sininn_flownet_workspace_bytes(n) // 4,), float('nan'), device=dev)
-    a = _lib.FlowNetArgs()
-    a.encoding = 1
-    ews = torch.full((lib.sininn_flownet_encgrad_workspace_bytes(a) // 4,), float('nan'), device=dev)
-    assert ews.numel() >= 512 * 256 + 512 * 768
-    return saved, ws, ews
-
-
 def run_case(dev, gold, name, grid, kind):
     """everything of cases 1 and 3 for one network, grid and mask; returns nothing, asserts"""
     from sin_inn_amd import flownet
     net = build(name).to(dev)
-    freq, mag, weights = net_tensors(net, dev)
+    bufs, weights = net_tensors(net, dev)
+    freq, mag = bufs['encode.frequencies'], bufs['encode.magnitudes']
     feff = f_eff(freq, mag).contiguous()                           # the fp32 matrix the kernels receive
     times, ys, xs = axes(GRIDS[grid], dev)
     n = times.numel() * ys.numel() * xs.numel()

@@ -36,8 +36,8 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_flownet_pe_golden import (N_MID, N_RAMP, SCALE, TIMES, GH, GW, build, controller, encode_pe, net_tensors, poses_of,  # noqa: E402
-                                    restate)
+from flownet_refs import encode_pe, is_plus_zero, nan_saved, nan_workspace, net_tensors, poses_of, reference_grads, restate  # noqa: E402
+from test_flownet_pe_golden import N_MID, N_RAMP, SCALE, TIMES, GH, GW, build, controller  # noqa: E402
 from test_gpu_flownet import CEIL, F64, MULT, axes, check  # noqa: E402
 
 GRIDS = {'fixture': (TIMES, GH, GW), 'ragged': ((0.0, 0.25, 1.0), 37, 53)}
@@ -55,30 +55,6 @@ def dev():
 @pytest.fixture(scope='module')
 def gold():
     return np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_flownet_pe.npz'))
-
-
-def nan_saved(n, dev):
-    from sin_inn_amd import _lib
-    nbytes = _lib.lib().sininn_flownet_saved_bytes(n)
-    return torch.full((3, nbytes // (3 * 256 * 4), 256), NAN, device=dev)
-
-
-def nan_workspace(n, dev):
-    from sin_inn_amd import _lib
-    return torch.full((_lib.lib().sininn_flownet_workspace_bytes(n) // 4,), NAN, device=dev)
-
-
-def is_plus_zero(t):
-    return bool((t == 0.0).all()) and not bool(torch.signbit(t).any())
-
-
-def reference_grads(name, bufs, weights, times, ys, xs, up, mask, gates):
-    out = {}
-    for dtype in (F64, torch.float32):
-        w = [p.to(dtype).requires_grad_(True) for p in weights]
-        flows = restate(name, bufs, w, times, ys, xs, SCALE, dtype, mask, gates)
-        out[dtype] = torch.autograd.grad((flows * up.to(dtype)).sum(), w)
-    return out
 
 
 def masks_of(gold, kind, net=None):
@@ -149,7 +125,7 @@ def test_forward_and_backward_against_float64(dev, gold, grid):
 
     gates = [saved[l, :n] > 0 for l in range(3)]
     up = torch.randn(infer.shape, generator=torch.Generator().manual_seed(11)).to(dev)
-    grads_ref = reference_grads(name, bufs, weights, times, ys, xs, up, None, gates)
+    grads_ref = reference_grads(name, bufs, weights, times, ys, xs, SCALE, up, None, gates)
     got = flownet.flownet_backward(net, times, ys, xs, SCALE, up, saved, nan_workspace(n, dev))
     again = flownet.flownet_backward(net, times, ys, xs, SCALE, up, saved, nan_workspace(n, dev))
     assert tuple(got[0].shape) == (256, 24)
@@ -189,7 +165,7 @@ def test_masks(dev, gold, kind, grid):
 
     gates = [saved[l, :n] > 0 for l in range(3)]
     up = torch.randn(infer.shape, generator=torch.Generator().manual_seed(11)).to(dev)
-    grads_ref = reference_grads(name, bufs, weights, times, ys, xs, up, mask, gates)
+    grads_ref = reference_grads(name, bufs, weights, times, ys, xs, SCALE, up, mask, gates)
     got = flownet.flownet_backward(net, times, ys, xs, SCALE, up, saved, nan_workspace(n, dev), mask=mask, k_active=ka)
     assert tuple(got[0].shape) == (256, 27)
     closed = mask == 0

@@ -1,8 +1,8 @@
 """GPU: the progressive mode of the flow-field network kernels (csrc/flownet.hip) for PRBF, PFF and PUFF against float64, with the
 method, the budget and the three grids of tests/test_gpu_flownet.py, unchanged: error against float64 <= min(4 x the deviation of
 the same formula in fp32 torch, measured here, 1e-4), max-norm relative to max |ref|, gradients with the kernel's own gates forced,
-no element excluded.  The reference is `restate` of tests/test_flownet_progressive_golden.py (concatenation and mask), which that
-file ties to the reference's own model.py / progressive_controller.py through the fixture.
+no element excluded.  The reference is `restate` of tests/flownet_refs.py (concatenation and mask), which
+tests/test_flownet_progressive_golden.py ties to the reference's own model.py / progressive_controller.py through the fixture.
 
 Masks: all ones; `mid`, the controller's mask after 100 iterations (84 leading ones); `init`, the controller's first mask (6 open
 features: the three coordinates and three encoded ones); and `ramp`, the mask after 98 iterations, whose block in progress stands at
@@ -28,7 +28,8 @@ import torch
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_flownet_progressive_golden import NETS, SCALE, build, controller, net_tensors, restate  # noqa: E402
+from flownet_refs import net_tensors, restate  # noqa: E402
+from test_flownet_progressive_golden import NETS, SCALE, build, controller  # noqa: E402
 from test_gpu_flownet import CEIL, F64, GRIDS, axes, check  # noqa: E402
 
 MASKS = ('ones', 'mid', 'init', 'ramp')

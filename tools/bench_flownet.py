@@ -70,7 +70,7 @@ def main():
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
-    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}[a.net](flownet.ModelParams()).to(dev)
+    net = flownet.all_model_dict[a.net](flownet.ModelParams()).to(dev)
     prog = net.is_progressive
     target = net
     if prog:

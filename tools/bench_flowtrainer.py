@@ -42,7 +42,7 @@ def main():
     from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
-    net = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}[a.net](flownet.ModelParams())
+    net = flownet.all_model_dict[a.net](flownet.ModelParams())
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, 5000, epsilon=1e-3)
     args = argparse.Namespace(lr=1e-4, loss_l1=1, loss_census=0.1, loss_ssim=a.loss_ssim, census_width=3, loss_smooth1=0.1,

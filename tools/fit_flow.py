@@ -99,8 +99,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     from sin_inn_amd import FusedAdam, FusedLAMB, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
-    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}
-    net = nets[net_name](flownet.ModelParams()).to(device)
+    net = flownet.all_model_dict[net_name](flownet.ModelParams()).to(device)
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
     if info is not None:

@@ -91,10 +91,9 @@ def build_net(args):
     """main.py:136-143: the network, and LinearControllerEarly around a progressive one.  `args.net` is the network's name on the
     first call; main() replaces it with the module, as the reference does, and keeps the name in `args.net_name`."""
     from sin_inn_amd import flownet, progressive
-    nets = {**flownet.model_dict, **flownet.progressive_model_dict, **flownet.learnable_model_dict, **flownet.grid_model_dict, **flownet.positional_model_dict}
     if isinstance(args.net, str):
         args.net_name = args.net
-    net = nets[args.net_name](flownet.ModelParams())
+    net = flownet.all_model_dict[args.net_name](flownet.ModelParams())
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, args.epochs, epsilon=1e-3)
         if net.block_iterations == 0:                          # fewer than 112 epochs (PPE: 4): the reference divides by zero here
