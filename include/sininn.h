@@ -35,7 +35,7 @@ extern "C" {
 int sininn_version(void);
 const char* sininn_last_error(void);
 /* sizeof() of descriptor struct `which` as THIS library was compiled: 0 sininn_conv_args, 1 sininn_wgrad_item,
- * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args, 7 sininn_flownet_args, 8 sininn_lamb_args; 0 for an unknown index.  A binding written in
+ * 2 sininn_dense_args, 3 sininn_glow_args, 4 sininn_subnet, 5 sininn_pack_desc, 6 sininn_dense_bf16_args, 7 sininn_flownet_args, 8 sininn_lamb_args, 9 sininn_siren_args; 0 for an unknown index.  A binding written in
  * another language (the ctypes mirrors in sin-inn_amd/_lib.py) checks its own layout against it at load time (ABI v4). */
 size_t sininn_sizeof(int which);
 /* A HIP stream at an explicit priority (lower number = higher priority; range from sininn_stream_priority_range: `least` is the
@@ -730,6 +730,52 @@ int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
 size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).
+ *   video-interpolation/model.py:123-146 SineLayer (sin(omega_0 * linear(x)), omega_0 = 30), model.py:149-171 SirenModel with the
+ *   ModelParams defaults (model.py:18-28): 3 -> 256 -> 256 -> 256 -> 256 -> 4, four sine layers and a plain last nn.Linear; evaluated on the
+ *   grid of FlowTrainer.forward (trainer.py:37-45) like the networks above: h_0 = (t, y, x) of meshgrid(times, ys, xs), N = T H W points,
+ *     u_l = omega (W_l h_{l-1} + b_l),  h_l = sin(u_l)    l = 1 .. 4     w[0] [256][3], w[1..3] [256][256]
+ *     out = W_5 h_4 + b_5                                                 w[4] [4][256]
+ *     flows[t][c][y][x] = out[p][c] * scale
+ *   The sine is the accurate full-range fp32 function (phases are tens of radians).  omega is read on every call.
+ *   forward : writes flows; if saved != NULL (training) also what the backward call needs, sininn_siren_saved_bytes(N) bytes whose content is
+ *             this library's business (today the phases u_1 .. u_4, [4][Npad][256], Npad = N rounded up to 64); every byte is written on
+ *             every call.  Training and inference flows are bitwise equal.  No N x 3 pose list and (inference) no N x 256 activation is
+ *             ever stored.
+ *   backward: dflows [T][4][H][W] -> gw[0..4] / gb[0..4] (OVERWRITTEN, nn.Linear layout, scale folded in), dout = dflows * scale:
+ *               gW5 = dout^T h_4        gb5 = sum_p dout
+ *               dh_4 = dout W_5         dz_l = omega dh_l cos(u_l)
+ *               gW_l = dz_l^T h_{l-1}   gb_l = sum_p dz_l     dh_{l-1} = dz_l W_l
+ *             Needs the saved buffer of the forward call on the same weights and omega, and a workspace of
+ *             sininn_siren_workspace_bytes(N) bytes; sums over points are added in a fixed order (no floating-point atomics): two calls on
+ *             the same inputs are bitwise equal.
+ * Borrowed pointers, 16-byte aligned (axis vectors and biases: 4), the caller's stream, non-zero return + sininn_last_error, N <= 2^22.
+ * Refused before any launch: a wrong struct_bytes; sizes other than in_dim 3, hidden 256, layers 3, out_dim 4 and an omega that is not
+ * finite and positive (the message lists what is supported); null or short buffers.  sininn_siren_supported: 1 if the sizes and omega are
+ * supported, else 0 (callers raise, there is no second path).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sininn_siren_args {
+  size_t struct_bytes;                    /* must be sizeof(sininn_siren_args)                                            */
+  int in_dim, hidden, layers, out_dim;    /* 3, 256, 3 (hidden sine layers after the first), 4                            */
+  float omega;                            /* omega_0 of every sine layer, finite and > 0 (the reference: 30)              */
+  int T, H, W;                            /* N = T H W points, at most 2^22                                               */
+  float scale;
+  const float *times, *ys, *xs;           /* [T], [H], [W]                                                                */
+  const float* w[5];                      /* [256][3], [256][256] x 3, [4][256]                                           */
+  const float* b[5];
+  float* flows;                           /* forward: out [T][4][H][W]                                                    */
+  float* saved; size_t saved_bytes;       /* forward: out or NULL; backward: in                                           */
+  const float* dflows;                    /* backward: in [T][4][H][W]                                                    */
+  float* gw[5]; float* gb[5];             /* backward: out                                                                */
+  void* workspace; size_t workspace_bytes;/* backward                                                                     */
+} sininn_siren_args;
+int sininn_siren_supported(const sininn_siren_args* args);
+size_t sininn_siren_saved_bytes(int64_t n_points);
+size_t sininn_siren_workspace_bytes(int64_t n_points);
+int sininn_siren_forward(const sininn_siren_args* args, void* stream);
+int sininn_siren_backward(const sininn_siren_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LAMB, the optimiser of the flow trainer (video-interpolation/trainer.py:134-135: apex.optimizers.FusedLAMB(params, lr=lr)),

@@ -124,6 +124,21 @@ class FlowNetArgs(C.Structure):
         self.struct_bytes = C.sizeof(FlowNetArgs)
 
 
+class SirenArgs(C.Structure):
+    """Mirror of sininn_siren_args."""
+    _fields_ = [('struct_bytes', C.c_size_t),
+                ('in_dim', C.c_int), ('hidden', C.c_int), ('layers', C.c_int), ('out_dim', C.c_int), ('omega', C.c_float),
+                ('T', C.c_int), ('H', C.c_int), ('W', C.c_int), ('scale', C.c_float),
+                ('times', c_f), ('ys', c_f), ('xs', c_f),
+                ('w', c_f * 5), ('b', c_f * 5), ('flows', c_f), ('saved', c_f), ('saved_bytes', C.c_size_t),
+                ('dflows', c_f), ('gw', c_f * 5), ('gb', c_f * 5),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(SirenArgs)
+
+
 class LambArgs(C.Structure):
     """Mirror of sininn_lamb_args."""
     _fields_ = [('struct_bytes', C.c_size_t),
@@ -269,6 +284,11 @@ _SIGS = {
     'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
     'sininn_flownet_encgrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_backward_encgrad': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
+    'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),
+    'sininn_siren_workspace_bytes': (C.c_size_t, [C.c_int64]),
+    'sininn_siren_forward': (C.c_int, [C.POINTER(SirenArgs), C.c_void_p]),
+    'sininn_siren_backward': (C.c_int, [C.POINTER(SirenArgs), C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, C.c_void_p]),
     'sininn_lamb_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
@@ -300,7 +320,7 @@ def lib():
         if handle.sininn_version() != 4:
             raise ImportError('libsininn.so ABI version mismatch')
         for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc, DenseBf16Args,
-                                        FlowNetArgs, LambArgs)):
+                                        FlowNetArgs, LambArgs, SirenArgs)):
             if handle.sininn_sizeof(which) != C.sizeof(mirror):
                 raise ImportError(f'{mirror.__name__}: the ctypes mirror has {C.sizeof(mirror)} bytes, libsininn.so was built '
                                   f'with {handle.sininn_sizeof(which)} (include/sininn.h changed without _lib.py)')

@@ -126,6 +126,11 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
 size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a);
 int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
+int siren_supported(const sininn_siren_args* a, const char* who);
+size_t siren_saved_bytes(int64_t n);
+size_t siren_workspace_bytes(int64_t n);
+int siren_forward_launch(const sininn_siren_args* a, hipStream_t st);
+int siren_backward_launch(const sininn_siren_args* a, hipStream_t st);
 size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
 int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st);
 int lamb_step_launch(const sininn_lamb_args* a, hipStream_t st);
@@ -259,6 +264,7 @@ size_t sininn_sizeof(int which) {
     case 6: return sizeof(sininn_dense_bf16_args);
     case 7: return sizeof(sininn_flownet_args);
     case 8: return sizeof(sininn_lamb_args);
+    case 9: return sizeof(sininn_siren_args);
     default: return 0;
   }
 }
@@ -583,6 +589,11 @@ int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_en
                                     void* stream) {
   return flownet_backward_encgrad_launch(args, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
 }
+int sininn_siren_supported(const sininn_siren_args* args) { return siren_supported(args, "sininn_siren_supported"); }
+size_t sininn_siren_saved_bytes(int64_t n_points) { return siren_saved_bytes(n_points); }
+size_t sininn_siren_workspace_bytes(int64_t n_points) { return siren_workspace_bytes(n_points); }
+int sininn_siren_forward(const sininn_siren_args* args, void* stream) { return siren_forward_launch(args, ST(stream)); }
+int sininn_siren_backward(const sininn_siren_args* args, void* stream) { return siren_backward_launch(args, ST(stream)); }
 
 size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors) { return lamb_workspace_bytes(n_chunks, n_tensors); }
 int sininn_lamb_grad_norm(const sininn_lamb_args* args, void* stream) { return lamb_grad_norm_launch(args, ST(stream)); }

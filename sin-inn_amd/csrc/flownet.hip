@@ -52,25 +52,17 @@
 //           instantiation of flownet_wgrad_kernel: a block owns 128 hidden columns x the KW padded features (a wave 32 x 32), always all of
 //           them, so nothing in it depends on k_active; flownet_reduce_l1_kernel writes nn.Linear's [256][LIVE] / [256][LIVE + 3] layout,
 //           for PPE an exact +0 where the mask is zero or the column lies beyond k_active.
-#include "common.h"
+#include "flownet_tile.h"
 
 namespace sininn {
 
 namespace {
 
-constexpr int FN_P = 64;            // points per tile
-constexpr int FN_HID = 256;
-constexpr int FN_OUT = 4;
-constexpr int FN_HS = FN_HID + 4;   // floats per row of the hidden tile in LDS (16-byte reads of 16 rows hit 64 distinct banks)
-constexpr int FN_NTHR = 256;
 constexpr int FN_WT = 128;          // weight-gradient output tile (FN_WT x FN_WT per block)
 constexpr int FN_WS = FN_WT + 16;   // floats per point row of a weight-gradient operand tile (4 rows x 16 lanes -> 64 banks)
 constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunks) x (output tiles) is about 512 blocks
-constexpr int FN_CHAIN_MAX_BLOCKS = 512;
-constexpr size_t FN_LDS = (size_t)(FN_P * FN_HS + FN_P * FN_OUT) * sizeof(float);
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
 constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features
-constexpr int FN_CS = 4;            // floats per row of the packed coordinate columns / of the coordinate tile in LDS
 constexpr size_t FN_WG_LDS_PROG = FN_WG_LDS + (size_t)(FN_P * FN_CS) * sizeof(float);
 
 // ---- the input of a layer as the kernels see it: LIVE features in a K range of KW.  Everything that depends on the encoding is here ----
@@ -130,15 +122,7 @@ struct FlowNetDev {
   int ksteps;              // progressive: 16-feature steps of the layer-1 K loop
 };
 
-struct Coord { float t, y, x; };
 
-__device__ __forceinline__ Coord point_coord(const FlowNetDev& q, int p) {
-  p = p < q.N ? p : q.N - 1;
-  const int hw = q.H * q.W;
-  const int t = p / hw, rem = p - t * hw;
-  const int y = rem / q.W, x = rem - y * q.W;
-  return Coord{q.times[t], q.ys[y], q.xs[x]};
-}
 
 // sin / cos of 2 pi (c . f) for one frequency f = (fa, fb, fc).  The phase is kept in REVOLUTIONS: each product is split into its
 // rounded value and its exact rounding error, the rounded value is reduced to [-1/2, 1/2] exactly, so the phase of a 75-cycle
@@ -226,31 +210,7 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
   return o;
 }
 
-// acc[m][n] += A[rows 16 m ..][k] W[cols cw + 16 n ..][k]: A from the LDS tile, W row-major [256][256] from L2
-__device__ __forceinline__ void gemm_lds(const float* hs, const float* w, int cw, int li, int kq, f32x4 (&acc)[4][4]) {
-#pragma unroll 2
-  for (int s = 0; s < FN_HID / 16; ++s) {
-    f32x4 bf[4], af[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) bf[n] = *reinterpret_cast<const f32x4*>(w + (size_t)(cw + 16 * n + li) * FN_HID + 16 * s + 4 * kq);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) af[m] = *reinterpret_cast<const f32x4*>(hs + (16 * m + li) * FN_HS + 16 * s + 4 * kq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][j], bf[n][j], acc[m][n], 0, 0, 0);
-  }
-}
 
-template <int M, int N>
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[M][N]) {
-#pragma unroll
-  for (int m = 0; m < M; ++m)
-#pragma unroll
-    for (int n = 0; n < N; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-}
 
 // accumulators -> LDS tile; RELU: + bias, max(., 0)
 template <bool RELU>
@@ -268,15 +228,6 @@ __device__ __forceinline__ void store_acc(float* hs, const float* bias, int cw, 
   }
 }
 
-// LDS tile -> rows [64 tile, 64 tile + 64) of a [Npad][256] array
-__device__ __forceinline__ void copy_tile_out(const float* hs, float* dst, int tile, int tid) {
-#pragma unroll 4
-  for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
-    const int f = tid + FN_NTHR * u;
-    const int row = f >> 6, c4 = (f & 63) * 4;
-    *reinterpret_cast<f32x4*>(dst + ((size_t)tile * FN_P + row) * FN_HID + c4) = *reinterpret_cast<const f32x4*>(hs + row * FN_HS + c4);
-  }
-}
 
 // PROG: q.w[0] is the packed W1p [256][KW], q.wc the coordinate columns, q.ksteps the length of the K loop
 template <int KIND, bool PROG = false>
@@ -757,7 +708,6 @@ int wgrad_chunks(int ntiles, int kf) {
   return ntiles < want ? ntiles : want;
 }
 
-int chain_blocks(int ntiles) { return ntiles < FN_CHAIN_MAX_BLOCKS ? ntiles : FN_CHAIN_MAX_BLOCKS; }
 
 // the largest set of partial sums of a backward call: a hidden layer's, any encoding's progressive layer 1, the chain kernel's
 size_t part_floats(int ntiles) {
@@ -774,15 +724,6 @@ size_t part_floats(int ntiles) {
   return n;
 }
 
-template <class K>
-int raise_lds(K k, size_t bytes, const char* name) {
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error("%s: cannot raise the LDS limit to %zu", name, bytes); return 1; }
-  }
-  return 0;
-}
-
 // encoded features in front of the last open one
 int open_encoded(const sininn_flownet_args* a) { return a->k_active > FN_DOM ? a->k_active - FN_DOM : 0; }
 
@@ -791,6 +732,24 @@ void reduce_launch(const FlowNetDev& q, int nparts, int nw, int nb, float* gw, f
 }
 
 }  // namespace
+
+// gW [256][256] = dh^T in, gb [256] = sum_p dh for one hidden layer, from two [64 ntiles][256] arrays: the split-over-points kernel, then
+// its partial sums in chunk order.  `part`: hidden_wgrad_part_floats(ntiles) floats.  Shared with siren.hip
+size_t hidden_wgrad_part_floats(int ntiles) { return (size_t)wgrad_chunks(ntiles, Hidden::CHUNK_KF) * Hidden::part_stride(false); }
+
+int hidden_wgrad_launch(int ntiles, const float* dh, const float* in, float* part, float* gw, float* gb, hipStream_t st) {
+  FlowNetDev q = {};
+  q.ntiles = ntiles;
+  q.part = part;
+  auto k = flownet_wgrad_kernel<SININN_FLOWNET_RBF, false>;
+  if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
+  const int nc = wgrad_chunks(ntiles, Hidden::CHUNK_KF);
+  hipLaunchKernelGGL(k, dim3(2 * Hidden::KW / Hidden::KT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, dh, in);
+  SININN_LAUNCH_CHECK("flownet_wgrad");
+  reduce_launch(q, nc, FN_HID * FN_HID, FN_HID, gw, gb, st);
+  SININN_LAUNCH_CHECK("flownet_reduce");
+  return 0;
+}
 
 // the support table; a refusal leaves its reason, with the table, as the library's last error
 int flownet_supported(const sininn_flownet_args* a, const char* who) {
@@ -924,16 +883,8 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
   SININN_LAUNCH_CHECK("flownet_bwd_chain");
   reduce_launch(q, cb, FN_OUT * FN_HID, FN_OUT, a->gw[3], a->gb[3], st);
   SININN_LAUNCH_CHECK("flownet_reduce");
-  for (int l = 2; l >= 1; --l) {                       // gW3 = dh3^T h2, gW2 = dh2^T h1
-    auto k = flownet_wgrad_kernel<SININN_FLOWNET_RBF, false>;
-    if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
-    const int nc = wgrad_chunks(q.ntiles, Hidden::CHUNK_KF);
-    hipLaunchKernelGGL(k, dim3(2 * Hidden::KW / Hidden::KT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, (const float*)(q.dh + l * lstride),
-                       (const float*)(q.saved + (l - 1) * lstride));
-    SININN_LAUNCH_CHECK("flownet_wgrad");
-    reduce_launch(q, nc, FN_HID * FN_HID, FN_HID, a->gw[l], a->gb[l], st);
-    SININN_LAUNCH_CHECK("flownet_reduce");
-  }
+  for (int l = 2; l >= 1; --l)                         // gW3 = dh3^T h2, gW2 = dh2^T h1
+    if (int rc = hidden_wgrad_launch(q.ntiles, q.dh + l * lstride, q.saved + (l - 1) * lstride, q.part, a->gw[l], a->gb[l], st)) return rc;
   if (int rc = for_kind(a->encoding, 1, [&](auto k) {
         return a->progressive ? wgrad_l1_launch<decltype(k)::value, true>(a, q, st) : wgrad_l1_launch<decltype(k)::value, false>(a, q, st);
       }))

@@ -6,6 +6,7 @@ backward in libsininn.so (csrc/flownet.hip).
     RotatedFourierFeatures / RFFModel / PRFFModel              video-interpolation/model.py:263-307, 436-451, 586-590 (learnable_model_dict)
     UniformRadialBasisGridEncoding / RbfgModel / PRBFGModel    video-interpolation/model.py:369-415, 508-523, 614-618 (grid_model_dict)
     PositionalEncoding / PEModel / PPEModel                    video-interpolation/model.py:321-340, 472-487, 607-611 (positional_model_dict)
+    SineLayer / SirenModel                                     video-interpolation/model.py:123-146, 149-171 (siren_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
 
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
@@ -45,9 +46,16 @@ its sines.  Layer 1 is [256][24] (PPE: [256][27], mask of 27 values, blocks of 6
 multiple of 7 and is the formula above where it runs; the kernels evaluate the formula for every N.  In the kernels it is the one
 encoding with a narrow layer 1 (two 16-feature K steps instead of 32, a 32-column weight-gradient tile).
 
-Out of scope: `siren`, `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
+`siren` (`SirenModel`) has no encoding: four `SineLayer`s, `sin(30 (W h + b))`, the first on the three raw coordinates, and a plain
+last nn.Linear (`state_dict` keys `model.{0..3}.linear.{weight,bias}`, `model.4.{weight,bias}`; every nn.Linear draws its own init first,
+then `weight.uniform_`).  It runs in kernels of its own (csrc/siren.hip, `siren_forward` / `siren_backward`) behind the same
+`flow_fields`; the sine is the accurate full-range fp32 function and omega is passed on every call.  It is registered in
+`siren_model_dict`, beside `all_model_dict`, not in it.
+
+Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
 spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
-grid; `FixedSpatialController`; `AdaptiveController`).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
+grid; `FixedSpatialController`; `AdaptiveController`).  Of `siren` only the `--net siren` switch of the command line remains
+closed (video-interpolation/main.py still refuses it).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
 `sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
 `sin_inn_amd.FusedLAMB` is the reference's apex FusedLAMB (trainer.py:134-135) restated, `sin_inn_amd.FusedAdam` drives them as well.
 """
@@ -332,6 +340,79 @@ grid_model_dict = _view('RBFG', 'PRBFG')                          # the radial-b
 positional_model_dict = _view('PE', 'PPE')                        # 24 features; PPE is progressive
 
 
+class SineLayer(nn.Module):
+    """model.py:123-146: sin(omega_0 * linear(x)); nn.Linear's own init draws first, then `weight.uniform_`.  Evaluated inside the
+    kernels."""
+
+    def __init__(self, in_features, out_features, bias=True, is_first=False, omega_0=30):
+        super().__init__()
+        self.omega_0 = omega_0
+        self.is_first = is_first
+        self.in_features = in_features
+        self.linear = nn.Linear(in_features, out_features, bias=bias)
+        self.init_weights()
+
+    def init_weights(self):
+        with torch.no_grad():
+            if self.is_first:
+                self.linear.weight.uniform_(-1 / self.in_features, 1 / self.in_features)
+            else:
+                bound = math.sqrt(6 / self.in_features) / self.omega_0
+                self.linear.weight.uniform_(-bound, bound)
+
+
+class SirenModel(nn.Module):
+    """model.py:149-171: SineLayer(3, 256, first), 3 x SineLayer(256, 256), nn.Linear(256, 4) with `weight.uniform_` after its own
+    init; `model` is the nn.Sequential of the five."""
+    is_progressive = False
+
+    def __init__(self, opt):
+        super().__init__()
+        self.opt = opt
+        layers = [SineLayer(opt.domain_dim, opt.hidden_dim, is_first=True, omega_0=30)]
+        for _ in range(opt.num_layers):
+            layers.append(SineLayer(opt.hidden_dim, opt.hidden_dim, is_first=False, omega_0=30))
+        final_linear = nn.Linear(opt.hidden_dim, opt.output_channels)
+        with torch.no_grad():
+            bound = math.sqrt(6 / opt.hidden_dim) / 30
+            final_linear.weight.uniform_(-bound, bound)
+        layers.append(final_linear)
+        self.model = nn.Sequential(*layers)
+        self._axes = {}
+
+    @property
+    def encoding_dim(self):
+        return self.opt.domain_dim
+
+    @property
+    def domain_dim(self):
+        return self.opt.domain_dim
+
+    @property
+    def omega(self):
+        """omega_0 of the sine layers: one value, the kernels take it as an argument"""
+        omegas = {m.omega_0 for m in self.model if isinstance(m, SineLayer)}
+        if len(omegas) != 1:
+            raise ValueError(f'siren kernels take one omega for every sine layer; got {sorted(omegas)}')
+        return float(omegas.pop())
+
+    def update_progress(self):
+        return
+
+    def stash_iteration(self, *args):
+        return
+
+    def linears(self):
+        return [m.linear if isinstance(m, SineLayer) else m for m in self.model]
+
+    def forward(self, x, *args, **kwargs):
+        raise NotImplementedError('evaluate the network on a (times, h, w) grid with sin_inn_amd.flownet.flow_fields: the pose '
+                                  'list and the activations are never materialised')
+
+
+siren_model_dict = {'siren': SirenModel}                          # beside all_model_dict: the command line does not open it yet
+
+
 def _on_gpu(t, what='tensor'):
     if not t.is_cuda:
         raise NotImplementedError(f'sin-inn_amd flownet runs on the GPU only (got a CPU {what})')
@@ -435,6 +516,86 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, m
     return grads, g_enc
 
 
+def _siren_args(net, times, ys, xs, scale, omega=None):
+    lins = net.linears()
+    a = _lib.SirenArgs()
+    a.in_dim, a.hidden, a.layers, a.out_dim = net.opt.domain_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
+    a.omega = net.omega if omega is None else float(omega)
+    if not _lib.lib().sininn_siren_supported(C.byref(a)):        # the library's refusal names the sizes it is built for
+        raise ValueError(_lib.lib().sininn_last_error().decode())
+    if len(lins) != 5:
+        raise ValueError(f'siren kernels take 5 linear layers; got {len(lins)}')
+    for t in (times, ys, xs):
+        _on_gpu(t)
+    a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
+    a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
+    for l, lin in enumerate(lins):
+        _on_gpu(lin.weight, 'parameter')
+        assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
+        a.w[l], a.b[l] = ptr(lin.weight), ptr(lin.bias)
+    return a
+
+
+def siren_forward(net, times, ys, xs, scale, train, saved=None, omega=None):
+    """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale for a SirenModel, and (train) what the backward call needs as one
+    opaque fp32 tensor of sininn_siren_saved_bytes(N) bytes (`saved`: optional caller-provided buffer of that size).  `omega`:
+    instead of the network's own omega_0 (None)."""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _siren_args(net, times, ys, xs, scale, omega)
+    n = a.T * a.H * a.W
+    flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
+    if train:
+        nbytes = _lib.lib().sininn_siren_saved_bytes(n)
+        if saved is None:
+            saved = torch.empty(nbytes // 4, device=times.device, dtype=torch.float32)
+        assert saved.is_cuda and saved.is_contiguous() and saved.dtype == torch.float32
+        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    else:
+        saved = None
+    a.flows = ptr(flows)
+    check(_lib.lib().sininn_siren_forward(C.byref(a), _stream()))
+    return flows, saved
+
+
+def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, omega=None):
+    """[gW1, gb1, .., gW5, gb5] for an upstream gradient dflows (t, 4, h, w); `saved`: that of the forward call on the same weights
+    and omega; `workspace`: optional fp32 tensor of at least sininn_siren_workspace_bytes(N) bytes (allocated here otherwise)."""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _siren_args(net, times, ys, xs, scale, omega)
+    n = a.T * a.H * a.W
+    _on_gpu(dflows)
+    dflows = dflows.contiguous()
+    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
+    if workspace is None:
+        workspace = torch.empty(_lib.lib().sininn_siren_workspace_bytes(n) // 4, device=times.device, dtype=torch.float32)
+    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
+    a.dflows = ptr(dflows)
+    grads = []
+    for l, lin in enumerate(net.linears()):
+        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
+        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
+        grads += [gw, gb]
+    check(_lib.lib().sininn_siren_backward(C.byref(a), _stream()))
+    return grads
+
+
+class _SirenFields(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, times, ys, xs, scale, train, *params):
+        flows, saved = siren_forward(net, times, ys, xs, scale, train)
+        ctx.net, ctx.axes, ctx.scale, ctx.saved = net, (times, ys, xs), scale, saved
+        return flows
+
+    @staticmethod
+    def backward(ctx, dflows):
+        if ctx.saved is None:
+            raise RuntimeError('flow_fields: backward through an inference-mode forward')
+        grads = siren_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved)
+        ctx.saved = None
+        return (None,) * 6 + tuple(grads)
+
+
 class _FlowFields(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, times, ys, xs, scale, train, mask, enc_a, *params):
@@ -501,12 +662,16 @@ def flow_fields(net, times, h, w, scale, override_mask=None):
     torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved.  `net` is a
     model or a controller around a progressive model; `override_mask` (515 values, PPE: 27; progressive networks only) replaces the
     controller's mask.  A learnable encoding (RFF / PRFF) contributes F_eff, computed here with torch ops; its gradient is computed
-    only if `encode.frequencies` requires one."""
+    only if `encode.frequencies` requires one.  A SirenModel runs in its own kernels under the same contract."""
     _on_gpu(times)
     assert times.dtype == torch.float32 and times.dim() == 1
     net, mask = _resolve_mask(net, override_mask, times.device)
     ys, xs = grid_axes(net, times, h, w)
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
+    if isinstance(net, SirenModel):
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        flows = _SirenFields.apply(net, times, ys, xs, float(scale), train, *params)
+        return flows[:, :2], flows[:, 2:]
     enc_a = net.encode.effective_frequencies() if isinstance(net.encode, RotatedFourierFeatures) else None
     train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad))
     flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, mask, enc_a, *params)

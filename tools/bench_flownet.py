@@ -13,6 +13,8 @@ host tensor so that the kernels skip the closed features as they do under a cont
 network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.
 RFF / PRFF (learnable frequencies) add the data gradient through layer 1 to the step (2 N 512*256 more FLOPs, counted) and the torch ops
 that make F_eff and carry its gradient to `encode.frequencies`; PRFF runs under the prefix mask like the other progressive nets.
+`siren` is 3-256-256-256-256-4: 2 N (3*256 + 3*256*256 + 256*4) FLOPs forward; backward adds the data gradients of layers 2-5 and the
+weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines in the backward pass) are not counted.
 """
 import argparse
 import json
@@ -32,6 +34,12 @@ PEAK_F32_MFMA = 157.3e12
 def flops(n, learnable=False, enc_dim=512):
     fwd = 2 * n * (enc_dim * 256 + 2 * 256 * 256 + 256 * 4)
     dgrad = 2 * n * (2 * 256 * 256 + 256 * 4 + (enc_dim * 256 if learnable else 0))
+    return fwd, fwd + dgrad + fwd
+
+
+def flops_siren(n):
+    fwd = 2 * n * (3 * 256 + 3 * 256 * 256 + 256 * 4)
+    dgrad = 2 * n * (3 * 256 * 256 + 256 * 4)
     return fwd, fwd + dgrad + fwd
 
 
@@ -55,7 +63,7 @@ def window(fn, seconds, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE'])
+    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE', 'siren'])
     ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask (0 .. 515, clamped to the network\'s width: 27 for PPE)')
     ap.add_argument('--frames', type=int, default=1)
     ap.add_argument('--height', type=int, default=436)
@@ -70,7 +78,8 @@ def main():
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
-    net = flownet.all_model_dict[a.net](flownet.ModelParams()).to(dev)
+    siren = a.net in flownet.siren_model_dict
+    net = {**flownet.all_model_dict, **flownet.siren_model_dict}[a.net](flownet.ModelParams()).to(dev)
     prog = net.is_progressive
     target = net
     if prog:
@@ -107,9 +116,11 @@ def main():
         for k, (fwd, step) in todo.items():
             res[k]['forward'].append(window(fwd, a.seconds, a.warmup))
             res[k]['step'].append(window(step, a.seconds, a.warmup))
-    f_fwd, f_step = flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
+    f_fwd, f_step = flops_siren(n) if siren else flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
+    sizes = (_lib.lib().sininn_siren_saved_bytes, _lib.lib().sininn_siren_workspace_bytes) if siren else \
+        (_lib.lib().sininn_flownet_saved_bytes, _lib.lib().sininn_flownet_workspace_bytes)
     out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
-               saved_bytes=_lib.lib().sininn_flownet_saved_bytes(n), workspace_bytes=_lib.lib().sininn_flownet_workspace_bytes(n))
+               saved_bytes=sizes[0](n), workspace_bytes=sizes[1](n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):
             meds = [w['median_ms'] for w in res[k][what]]
