@@ -731,6 +731,34 @@ size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
                                     void* stream);
 
+/* Spatially adaptive progression (progressive_controller.py:461-710 StashedSpatialController, what --spatially-adaptive builds): every
+ * point has its own 515 mask values, interpolated trilinearly from a DEVICE grid G [res^3][515] (fp32, row-major, features contiguous:
+ * the controller's blurred mask).  The descriptor is the one above with progressive = 1; its `mask` is ignored and may be NULL.
+ *   centre_scale: HOST array of 6 floats, read during the call: centre (t, y, x), then scale (t, y, x), the reference's center_scale;
+ *   identity is 0, 0, 0, 1, 1, 1.  For the point with coordinates x_d, d = 0 .. 2 = (t, y, x), as interpolate_ does
+ *   (progressive_controller.py:655-664), every operation a rounded fp32 one, nothing contracted:
+ *     u_d = ((x_d - centre_d) * scale_d + 1) / 2 * max(res - 2, 1) + 0.5;   i0 = floor(u_d), i1 = ceil(u_d + 1e-6);
+ *     a0 = i1 - u_d, a1 = u_d - i0 (their sum is 2 where u_d lies within 1e-6 below an integer, as in the reference);
+ *     corner c = 0 .. 7 takes i / a number (c >> 2) & 1 of t, (c >> 1) & 1 of y, c & 1 of x: row = i_t + i_y res + i_x res^2 (t has
+ *     stride 1), weight = (a_t a_y) a_x;   m_k(p) = sum over c in that order of weight_c * G[row_c][k].
+ *   Corner indices are clamped to [0, res - 1] before the load: where the reference would raise an index error the edge cell is read.
+ *   Nothing is validated on the device and nothing is read back.
+ * Layer 1 reads cat((t, y, x), enc)_k * m_k(p): the mask multiplies the generated operand in registers, w[0] [256][515] is read in place;
+ * there is no pack step and no forward workspace.  gw[0][j][k] = sum_p dh1[p][j] feature_k[p] m_k(p), and for the Fourier encoding
+ * dE[p][k] = m_{3 + k}(p) sum_j dh1[p][j] w[0][j][3 + k] feeds g_enc_a as above.  k_active keeps its meaning: every entry of G in a
+ * column from k_active on must be zero (515 is always valid); any valid value gives bitwise the same flows and gradients (finite
+ * weights), every sum over points keeps its fixed order, two calls are bitwise equal, and a column of gw[0] whose grid column is all
+ * zero is an exact +0.  Workspaces and `saved` have the sizes of the calls above.
+ *   sininn_flownet_sample_mask writes m_k(p) for the descriptor's grid of points, out [N][515] (device): what the kernels multiply by.
+ * Refused before any launch: a null grid or centre_scale, res < 3, res^3 * 515 beyond 2^31 - 1 (32-bit indexing in the kernels), a
+ * descriptor that is not progressive, and PPE (27 features and a packed narrow layer 1 of its own: out of scope for this mode). */
+int sininn_flownet_forward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream);
+int sininn_flownet_backward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream);
+int sininn_flownet_backward_encgrad_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                            float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, void* stream);
+int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, float* out,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).
  *   video-interpolation/model.py:123-146 SineLayer (sin(omega_0 * linear(x)), omega_0 = 30), model.py:149-171 SirenModel with the

@@ -284,6 +284,11 @@ _SIGS = {
     'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
     'sininn_flownet_encgrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_backward_encgrad': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_flownet_forward_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, C.c_void_p]),
+    'sininn_flownet_backward_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, C.c_void_p]),
+    'sininn_flownet_backward_encgrad_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_void_p, C.c_size_t,
+                                                          C.c_void_p]),
+    'sininn_flownet_sample_mask': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_void_p]),
     'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
     'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_siren_workspace_bytes': (C.c_size_t, [C.c_int64]),

@@ -126,6 +126,11 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
 size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a);
 int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
+int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st);
+int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st);
+int flownet_backward_encgrad_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* g_enc_a,
+                                            void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
+int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st);
 int siren_supported(const sininn_siren_args* a, const char* who);
 size_t siren_saved_bytes(int64_t n);
 size_t siren_workspace_bytes(int64_t n);
@@ -588,6 +593,20 @@ size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args) {
 int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
                                     void* stream) {
   return flownet_backward_encgrad_launch(args, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
+}
+int sininn_flownet_forward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream) {
+  return flownet_forward_spatial_launch(args, grid, res, centre_scale, ST(stream));
+}
+int sininn_flownet_backward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream) {
+  return flownet_backward_spatial_launch(args, grid, res, centre_scale, ST(stream));
+}
+int sininn_flownet_backward_encgrad_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                            float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, void* stream) {
+  return flownet_backward_encgrad_spatial_launch(args, grid, res, centre_scale, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
+}
+int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, float* out,
+                               void* stream) {
+  return flownet_sample_mask_launch(args, grid, res, centre_scale, out, ST(stream));
 }
 int sininn_siren_supported(const sininn_siren_args* args) { return siren_supported(args, "sininn_siren_supported"); }
 size_t sininn_siren_saved_bytes(int64_t n_points) { return siren_saved_bytes(n_points); }

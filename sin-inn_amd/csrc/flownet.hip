@@ -52,6 +52,16 @@
 //           instantiation of flownet_wgrad_kernel: a block owns 128 hidden columns x the KW padded features (a wave 32 x 32), always all of
 //           them, so nothing in it depends on k_active; flownet_reduce_l1_kernel writes nn.Linear's [256][LIVE] / [256][LIVE + 3] layout,
 //           for PPE an exact +0 where the mask is zero or the column lies beyond k_active.
+//
+// spatially adaptive (StashedSpatialController, progressive_controller.py:461-710): the mask is a per-point one, m_k(p) = the trilinear
+//           interpolation of a device grid G [res^3][515] at the point's coordinates (Spatial, corners_of, sample_cols).  It cannot be
+//           folded into W1, so the SPATIAL instantiations multiply the generated operand instead: encode4 * m in the forward pass and in
+//           the layer-1 weight gradient (the same function on the same inputs: the same bits), dE * m in the frequency gradient.  W1
+//           [256][515] is read in place with dword-aligned 16-byte loads (rows of 2060 bytes), and so are the eight grid rows of a
+//           point: a 64-point tile of one image row spans a few grid cells, a few dozen distinct rows of 2060 bytes that L2 serves
+//           again and again; they are NOT staged in LDS, which two blocks per CU leave no room for.  What is staged
+//           per tile is the 64 x (8 corner weights, 8 row offsets), 4 KiB, computed once per point by the first 64 threads.  k_active
+//           cuts the K loop and the weight-gradient tiles as above: the grid is zero from there on, the operand e * 0.
 #include "flownet_tile.h"
 
 namespace sininn {
@@ -64,6 +74,9 @@ constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunk
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
 constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features
 constexpr size_t FN_WG_LDS_PROG = FN_WG_LDS + (size_t)(FN_P * FN_CS) * sizeof(float);
+constexpr int FN_GW = 512 + FN_DOM;  // spatial: floats per row of the mask grid and of the W1 it goes with
+constexpr int FN_CN = 16;           // spatial: floats per point of the corner tile in LDS: 8 weights, 8 row offsets
+constexpr size_t FN_CN_LDS = (size_t)(FN_P * FN_CN) * sizeof(float);
 
 // ---- the input of a layer as the kernels see it: LIVE features in a K range of KW.  Everything that depends on the encoding is here ----
 template <int LIVE_, int KW_, bool ENC_B_ = false, bool FREQ_GRAD_ = false>
@@ -105,6 +118,14 @@ R for_kind(int encoding, R otherwise, F&& f) {
   }
 }
 
+// spatial: the mask grid and the map from a coordinate to its cell
+struct Spatial {
+  const float* grid;       // [res^3][FN_GW]
+  int res;
+  float span;              // max(res - 2, 1)
+  float centre[3], scale[3];
+};
+
 struct FlowNetDev {
   int T, H, W, N, ntiles;
   float scale;
@@ -120,7 +141,104 @@ struct FlowNetDev {
   float* part;             // partial sums
   const float* wc;         // progressive: coordinate columns of W1 times their mask, [256][4]
   int ksteps;              // progressive: 16-feature steps of the layer-1 K loop
+  Spatial sp;
 };
+
+// ---- spatial: the per-point mask ----
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at a dword-aligned address: rows of FN_GW floats
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+struct Corners {
+  float w[8];              // (a_t a_y) a_x of corner c: bit 2 of c chooses t's upper index, bit 1 y's, bit 0 x's
+  int row[8];              // FN_GW * (i_t + i_y res + i_x res^2), indices clamped to the grid
+};
+
+// interpolate_ of the reference in fp32, one rounding per operation as torch makes them: floor and ceil decide as they do there
+__device__ __forceinline__ Corners corners_of(const Spatial& sp, const Coord c) {
+#pragma clang fp contract(off)
+  const float x[3] = {c.t, c.y, c.x};
+  float a[3][2];
+  int i[3][2];
+  const float top = (float)(sp.res - 1);
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const float xs = (x[d] - sp.centre[d]) * sp.scale[d];
+    const float u = ((xs + 1.f) * 0.5f) * sp.span + 0.5f;
+    const float f0 = floorf(u), f1 = ceilf(u + 1e-6f);
+    a[d][0] = f1 - u;
+    a[d][1] = u - f0;
+    i[d][0] = (int)fminf(fmaxf(f0, 0.f), top);         // a NaN goes to cell 0
+    i[d][1] = (int)fminf(fmaxf(f1, 0.f), top);
+  }
+  Corners o;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int st = (k >> 2) & 1, sy = (k >> 1) & 1, sx = k & 1;
+    o.w[k] = (a[0][st] * a[1][sy]) * a[2][sx];
+    o.row[k] = (i[0][st] + (i[1][sy] + i[2][sx] * sp.res) * sp.res) * FN_GW;
+  }
+  return o;
+}
+
+__device__ __forceinline__ void store_corners(float* cn, const Corners& o) {
+  *reinterpret_cast<f32x4*>(cn) = (f32x4){o.w[0], o.w[1], o.w[2], o.w[3]};
+  *reinterpret_cast<f32x4*>(cn + 4) = (f32x4){o.w[4], o.w[5], o.w[6], o.w[7]};
+  *reinterpret_cast<i32x4*>(cn + 8) = (i32x4){o.row[0], o.row[1], o.row[2], o.row[3]};
+  *reinterpret_cast<i32x4*>(cn + 12) = (i32x4){o.row[4], o.row[5], o.row[6], o.row[7]};
+}
+
+__device__ __forceinline__ Corners load_corners(const float* cn) {
+  const f32x4 w0 = *reinterpret_cast<const f32x4*>(cn), w1 = *reinterpret_cast<const f32x4*>(cn + 4);
+  const i32x4 r0 = *reinterpret_cast<const i32x4*>(cn + 8), r1 = *reinterpret_cast<const i32x4*>(cn + 12);
+  return Corners{{w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]}, {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]}};
+}
+
+// m[j] = sum_c w_c G[row_c][col + j], corners in index order, a rounded product and a rounded sum each: the one place the mask is
+// computed, so the forward pass, both gradients and sample_mask see the same bits
+template <int NC>
+__device__ __forceinline__ void sample_cols(const float* grid, const Corners& cn, int col, float (&m)[NC]) {
+#pragma clang fp contract(off)
+  static_assert(NC == 1 || NC == 2 || NC == 4, "one, two or four columns");
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const float* g = grid + cn.row[c] + col;
+    float v[NC];
+    if constexpr (NC == 4) {
+      const f32x4u t = *reinterpret_cast<const f32x4u*>(g);
+      v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else if constexpr (NC == 2) {
+      const f32x2u t = *reinterpret_cast<const f32x2u*>(g);
+      v[0] = t[0]; v[1] = t[1];
+    } else {
+      v[0] = g[0];
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const float t = cn.w[c] * v[j];
+      m[j] = c ? m[j] + t : t;
+    }
+  }
+}
+
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// the first 64 threads: the corners of the tile's points -> LDS
+__device__ __forceinline__ void stage_corners(const FlowNetDev& q, int tile, int tid, float* cns) {
+  if (tid < FN_P) store_corners(cns + tid * FN_CN, corners_of(q.sp, point_coord(q, tile * FN_P + tid)));
+}
+
+// the three masked coordinates of a point, as layer 1 reads them
+__device__ __forceinline__ f32x4 masked_coord(const FlowNetDev& q, const Coord c, const Corners& cn) {
+  float m0[1], m1[1], m2[1];
+  sample_cols<1>(q.sp.grid, cn, 0, m0);
+  sample_cols<1>(q.sp.grid, cn, 1, m1);
+  sample_cols<1>(q.sp.grid, cn, 2, m2);
+  return (f32x4){mul_rn(c.t, m0[0]), mul_rn(c.y, m1[0]), mul_rn(c.x, m2[0]), 0.f};
+}
 
 
 
@@ -230,12 +348,15 @@ __device__ __forceinline__ void store_acc(float* hs, const float* bias, int cw, 
 
 
 // PROG: q.w[0] is the packed W1p [256][KW], q.wc the coordinate columns, q.ksteps the length of the K loop
-template <int KIND, bool PROG = false>
+// SPATIAL (with PROG): q.w[0] is nn.Linear's own W1 [256][FN_GW], the operand is multiplied by the point's mask, q.ksteps as above
+template <int KIND, bool PROG = false, bool SPATIAL = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
+  static_assert(PROG || !SPATIAL, "a spatial mask is a progressive network's");
   using E = Enc<KIND>;
-  constexpr int EW = E::w1_stride(PROG);               // floats per row of q.w[0]
+  constexpr int EW = SPATIAL ? FN_GW : E::w1_stride(PROG);   // floats per row of q.w[0]
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;
+  float* const cns = fn_smem + FN_P * FN_HS + FN_P * FN_OUT;   // SPATIAL: [64][FN_CN]
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
@@ -250,13 +371,28 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
 
     f32x4 acc[4][4];
     zero_acc(acc);
+    if constexpr (SPATIAL) {
+      stage_corners(q, tile, tid, cns);                // the last reads of the previous tile's lie before its barriers
+      __syncthreads();
+    }
     if constexpr (PROG) {
       // ---- the coordinates: one K group, k = kq: t, y, x, 0 ----
       float a[4], b[4];
 #pragma unroll
       for (int m = 0; m < 4; ++m) a[m] = kq == 0 ? pc[m].t : kq == 1 ? pc[m].y : kq == 2 ? pc[m].x : 0.f;
+      if constexpr (SPATIAL) {
 #pragma unroll
-      for (int n = 0; n < 4; ++n) b[n] = q.wc[(cw + 16 * n + li) * FN_CS + kq];
+        for (int m = 0; m < 4; ++m) {
+          float mk[1];
+          sample_cols<1>(q.sp.grid, load_corners(cns + (16 * m + li) * FN_CN), kq < FN_DOM ? kq : 0, mk);
+          a[m] = kq < FN_DOM ? mul_rn(a[m], mk[0]) : 0.f;
+        }
+#pragma unroll
+        for (int n = 0; n < 4; ++n) b[n] = kq < FN_DOM ? q.w[0][(size_t)(cw + 16 * n + li) * FN_GW + kq] : 0.f;
+      } else {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) b[n] = q.wc[(cw + 16 * n + li) * FN_CS + kq];
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -270,10 +406,20 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
         if (!PROG && E::LIVE < E::KW && 16 * s + 4 * kq >= E::LIVE) bf[n] = (f32x4){0.f, 0.f, 0.f, 0.f};   // W1 [256][LIVE] has no such columns
+        else if constexpr (SPATIAL) bf[n] = *reinterpret_cast<const f32x4u*>(q.w[0] + (size_t)(cw + 16 * n + li) * EW + FN_DOM + 16 * s + 4 * kq);
         else bf[n] = *reinterpret_cast<const f32x4*>(q.w[0] + (size_t)(cw + 16 * n + li) * EW + 16 * s + 4 * kq);
       }
 #pragma unroll
-      for (int m = 0; m < 4; ++m) af[m] = encode4<KIND>(q, pc[m], 16 * s + 4 * kq);
+      for (int m = 0; m < 4; ++m) {
+        af[m] = encode4<KIND>(q, pc[m], 16 * s + 4 * kq);
+        if constexpr (SPATIAL) {
+          float mk[4];
+          sample_cols<4>(q.sp.grid, load_corners(cns + (16 * m + li) * FN_CN), FN_DOM + 16 * s + 4 * kq, mk);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) af[m][j] = mul_rn(af[m][j], mk[j]);
+          __builtin_amdgcn_sched_barrier(0);           // one point's eight grid rows in flight at a time: 32 registers, not 128
+        }
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -442,9 +588,11 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
 // grid = (2 * KF / KT output tiles, chunks); ENC: in = the encoding (KF = Enc<KIND>::KW), else a saved hidden layer (KF = 256, KIND unused).
 // PROG (with ENC): + [chunk][256 * KF + 256 + 4 j + c] = sum_p dh[p][j] coordinate_c[p]; the grid may cover the leading k tiles only.
 // NARROW (an encoding of fewer than 128 padded features): grid = (2, chunks), a block owns 128 x KF and a wave 32 x 32 of it
-template <int KIND, bool ENC, bool PROG = false>
+// SPATIAL (with PROG): the input is times the point's mask, as the forward pass made it, the coordinates included
+template <int KIND, bool ENC, bool PROG = false, bool SPATIAL = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q, const float* dh, const float* in) {
   static_assert(ENC || !PROG, "the progressive weight gradient is layer 1's");
+  static_assert(PROG || !SPATIAL, "a spatial mask is a progressive network's");
   using L = std::conditional_t<ENC, Enc<KIND>, Hidden>;
   constexpr bool NARROW = L::NARROW;
   constexpr int KF = L::KW;
@@ -457,6 +605,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
   float* const as = fn_smem;                           // [64][FN_WS]: dh tile
   float* const bs = fn_smem + FN_P * FN_WS;            // [64][FN_WS]: input tile
   float* const cs = fn_smem + 2 * FN_P * FN_WS;        // PROG: [64][4]: coordinates of the tile's points
+  float* const cns = cs + FN_P * FN_CS;                // SPATIAL: [64][FN_CN]: their corners
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
@@ -482,6 +631,15 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
   if (chunk < q.ntiles) fetch(chunk);
   for (int tile = chunk; tile < q.ntiles; tile += nchunks) {
     __syncthreads();                                   // the previous tile's MFMAs have read as / bs
+    if constexpr (SPATIAL) {
+      if (tid < FN_P) {
+        const Coord c = point_coord(q, tile * FN_P + tid);
+        const Corners cn = corners_of(q.sp, c);
+        store_corners(cns + tid * FN_CN, cn);
+        if (k0 == 0) *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = masked_coord(q, c, cn);
+      }
+      __syncthreads();
+    }
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       const int f = tid + FN_NTHR * u;
@@ -490,10 +648,16 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
       if (u < NUB) {
         const int rb = NARROW ? f / (KT / 4) : row, cb = NARROW ? (f % (KT / 4)) * 4 : c4;
         if constexpr (ENC) vb[u] = encode4<KIND>(q, point_coord(q, tile * FN_P + rb), k0 + cb);
+        if constexpr (SPATIAL) {
+          float mk[4];
+          sample_cols<4>(q.sp.grid, load_corners(cns + rb * FN_CN), FN_DOM + k0 + cb, mk);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) vb[u][j] = mul_rn(vb[u][j], mk[j]);
+        }
         *reinterpret_cast<f32x4*>(bs + rb * FN_WS + cb) = vb[u];
       }
     }
-    if constexpr (PROG) {
+    if constexpr (PROG && !SPATIAL) {
       if (k0 == 0 && tid < FN_P) {
         const Coord c = point_coord(q, tile * FN_P + tid);
         *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
@@ -563,6 +727,7 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* pa
 
 // progressive layer 1: gw [256][515] = mask[k] * sum_c part[c][..] in chunk order (k < 3: the coordinate sums, else encoded column
 // k - 3), an exact zero where the mask is zero or the column lies beyond the `kcols` encoded columns that were computed; gb as above.
+// mask == nullptr (spatial: the mask is in the partial sums already): the sums as they are, zeros beyond `kcols`.
 // EW: columns of a row of the partial sums, LIVE: encoded columns of gw (<E::KW, E::LIVE>).  !PROG (PE): gw [256][LIVE], no mask
 template <int EW, int LIVE, bool PROG>
 __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_l1_kernel(const float* part, int nparts, const float* mask, int kcols, float* gw,
@@ -578,7 +743,7 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_l1_kernel(const float*
   if (i < NW) {
     const int j = i / WIDTH, k = i - j * WIDTH;
     if constexpr (PROG) {
-      m = mask[k];
+      if (mask) m = mask[k];
       if (m == 0.f || k - DOM >= kcols) { gw[i] = 0.f; return; }
     }
     src = k < DOM ? (size_t)FN_HID * EW + FN_HID + j * FN_CS + k : (size_t)j * EW + (k - DOM);
@@ -603,13 +768,16 @@ constexpr int FN_EG_PART = FN_DOM * FN_NF;           // floats of one block's pa
 constexpr size_t FN_EG_FLOATS = (size_t)Fourier::LIVE * FN_HID + (size_t)FN_CHAIN_MAX_BLOCKS * FN_EG_PART;
 constexpr float FN_TWO_PI = 6.283185307179586f;
 
-// wt[c][j] = w1[j][feature of row c] (progressive: column 3 + feature, times its mask, an exact zero where the mask is zero); block = row c
-__global__ __launch_bounds__(FN_NTHR) void flownet_encgrad_pack_kernel(const float* w1, const float* mask, float* wt) {
+// wt[c][j] = w1[j][feature of row c] (progressive: column 3 + feature, times its mask, an exact zero where the mask is zero; spatial:
+// column 3 + feature as it is, the kernel applies the mask to dE); block = row c
+__global__ __launch_bounds__(FN_NTHR) void flownet_encgrad_pack_kernel(const float* w1, const float* mask, float* wt, int spatial) {
   const int c = blockIdx.x, j = threadIdx.x;
   const int f = (c >> 8) * 128 + ((c >> 6) & 3) * 32 + ((c >> 4) & 1) * 16 + (c & 15);
   const int k = 2 * f + ((c >> 5) & 1);
   float v;
-  if (mask) {
+  if (spatial) {
+    v = w1[(size_t)j * Fourier::width(true) + FN_DOM + k];
+  } else if (mask) {
     const float m = mask[FN_DOM + k];
     v = m == 0.f ? 0.f : w1[(size_t)j * Fourier::width(true) + FN_DOM + k] * m;
   } else {
@@ -619,11 +787,14 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_encgrad_pack_kernel(const flo
 }
 
 // part[block][d][f] = sum over the block's point tiles of coordinate_d[p] dphi[p][f]; grid-stride over tiles like the chain kernel.
-// Frequencies from `fopen` on are closed (progressive): a wave whose 32 frequencies are all closed skips its GEMM and leaves zeros
+// Frequencies from `fopen` on are closed (progressive): a wave whose 32 frequencies are all closed skips its GEMM and leaves zeros.
+// SPATIAL: wt is unmasked and dE[p][k] is multiplied by the point's mask of feature k
+template <bool SPATIAL>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_encgrad_kernel(FlowNetDev q, const float* wt, float* part, int fopen) {
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;                           // [64][FN_HS]: dh1 tile
   float* const cs = fn_smem + FN_P * FN_HS;            // [64][4]: coordinates of the tile's points
+  float* const cns = cs + FN_P * FN_CS;                // SPATIAL: [64][FN_CN]: their corners
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
@@ -644,6 +815,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_encgrad_kernel(FlowNetDev 
     if (tid < FN_P) {
       const Coord c = point_coord(q, tile * FN_P + tid);
       *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
+      if constexpr (SPATIAL) store_corners(cns + tid * FN_CN, corners_of(q.sp, c));
     }
     __syncthreads();
 #pragma unroll
@@ -653,6 +825,41 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_encgrad_kernel(FlowNetDev 
       f32x4 acc[4][4];
       zero_acc(acc);
       gemm_lds(hs, wt + (size_t)ps * FN_HID * FN_HID, cw, li, kq, acc);
+      if constexpr (SPATIAL) {
+        // point by point, both frequencies of the lane inside: a point's coordinates and corners are read once per pass and dropped
+        // (features 2 f, the sine, and 2 f + 1, the cosine, are adjacent grid columns: one 8-byte load per corner); dE * m, then the
+        // sums below in the same order over the points.  The accumulators leave no room to keep 16 points' worth of anything
+        asm volatile("" ::: "memory");
+        float fq[2][3], sm[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+          const int f = fw + 16 * n + li;
+          fq[n][0] = q.enc_a[f]; fq[n][1] = q.enc_a[FN_NF + f]; fq[n][2] = q.enc_a[2 * FN_NF + f];
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int pr = 16 * m + 4 * kq + r;
+            const f32x4 c = *reinterpret_cast<const f32x4*>(cs + pr * FN_CS);
+            const Corners cn = load_corners(cns + pr * FN_CN);
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+              float mk[2], sn, co;
+              sample_cols<2>(q.sp.grid, cn, FN_DOM + 2 * (fw + 16 * n + li), mk);
+              fourier_sincos(Coord{c[0], c[1], c[2]}, fq[n][0], fq[n][1], fq[n][2], sn, co);
+              const float d = mul_rn(acc[m][n][r], mk[0]) * co - mul_rn(acc[m][n + 2][r], mk[1]) * sn;
+              sm[n][0] = fmaf(c[0], d, sm[n][0]);
+              sm[n][1] = fmaf(c[1], d, sm[n][1]);
+              sm[n][2] = fmaf(c[2], d, sm[n][2]);
+            }
+          }
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int d = 0; d < FN_DOM; ++d) g[ps][n][d] += sm[n][d];
+        continue;
+      }
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         const int f = fw + 16 * n + li;
@@ -701,6 +908,31 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_enc_kernel(const float
   float s = 0.f;
   for (int c = 0; c < nparts; ++c) s += part[(size_t)c * FN_EG_PART + i];
   g[i] = s * FN_TWO_PI;
+}
+
+// out[p][k] = m_k(p): thread = (point, group g of 129: g == 0 the three coordinate columns, else encoded features 4 (g - 1) ..)
+constexpr int FN_GROUPS = 1 + (FN_GW - FN_DOM) / 4;
+__global__ __launch_bounds__(FN_NTHR) void flownet_sample_mask_kernel(FlowNetDev q, float* out) {
+  const size_t total = (size_t)q.N * FN_GROUPS;
+  for (size_t i = (size_t)blockIdx.x * FN_NTHR + threadIdx.x; i < total; i += (size_t)gridDim.x * FN_NTHR) {
+    const int p = (int)(i / FN_GROUPS), g = (int)(i - (size_t)p * FN_GROUPS);
+    const Corners cn = corners_of(q.sp, point_coord(q, p));
+    float* const o = out + (size_t)p * FN_GW;
+    if (g == 0) {
+#pragma unroll
+      for (int k = 0; k < FN_DOM; ++k) {
+        float mk[1];
+        sample_cols<1>(q.sp.grid, cn, k, mk);
+        o[k] = mk[0];
+      }
+    } else {
+      const int k = FN_DOM + 4 * (g - 1);
+      float mk[4];
+      sample_cols<4>(q.sp.grid, cn, k, mk);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[k + j] = mk[j];
+    }
+  }
 }
 
 int wgrad_chunks(int ntiles, int kf) {
@@ -802,10 +1034,44 @@ static int check_network(const sininn_flownet_args* a, const char* who) {
   return flownet_supported(a, who) ? 0 : 1;
 }
 
-static int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q) {
+// what the spatial entry points take beside the descriptor
+struct SpatialArgs {
+  const float* grid;
+  int res;
+  const float* centre_scale;   // host [6]
+};
+
+// the spatial mode: a 515-wide progressive network, a grid the kernels can index; everything a launch would trip over, before any launch
+static int check_spatial(const sininn_flownet_args* a, const char* who, const SpatialArgs& s, FlowNetDev& q) {
   if (int rc = check_network(a, who)) return rc;
+  SININN_CHECK(a->progressive == 1, "%s: a spatial mask needs a progressive network (progressive = 1)", who);
+  SININN_CHECK(a->enc_dim == FN_GW,
+               "%s: spatial masks are built for the %d-wide progressive encodings (PRBF, PFF / PUFF / PRFF, PRBFG); PPE (enc_dim %d, a packed "
+               "narrow layer 1 of its own) is out of scope for this mode", who, FN_GW, a->enc_dim);
+  SININN_CHECK(s.grid != nullptr && s.centre_scale != nullptr, "%s: null grid / centre_scale", who);
+  SININN_CHECK(s.res >= 3, "%s: res %d (at least 3)", who, s.res);
+  SININN_CHECK((int64_t)s.res * s.res * s.res * FN_GW <= (int64_t)INT32_MAX, "%s: res %d: res^3 * %d exceeds the kernels' 32-bit indexing", who,
+               s.res, FN_GW);
+  q.sp.grid = s.grid;
+  q.sp.res = s.res;
+  q.sp.span = (float)(s.res - 2 > 1 ? s.res - 2 : 1);
+  for (int d = 0; d < 3; ++d) {
+    q.sp.centre[d] = s.centre_scale[d];
+    q.sp.scale[d] = s.centre_scale[3 + d];
+  }
+  return 0;
+}
+
+// spatial != nullptr: the descriptor's mask is ignored, the grid is checked and goes to q.sp
+static int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial = nullptr) {
+  q.sp = Spatial{};
+  if (spatial) {
+    if (int rc = check_spatial(a, who, *spatial, q)) return rc;
+  } else if (int rc = check_network(a, who)) {
+    return rc;
+  }
   if (a->progressive) {
-    SININN_CHECK(a->mask != nullptr, "%s: progressive network without a mask", who);
+    SININN_CHECK(spatial || a->mask != nullptr, "%s: progressive network without a mask", who);
     SININN_CHECK(a->k_active >= 0 && a->k_active <= a->enc_dim, "%s: k_active %d (0 .. %d)", who, a->k_active, a->enc_dim);
   }
   SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
@@ -831,11 +1097,11 @@ static int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev&
 }
 
 // layer 1: gW1 = dh1^T (regenerated input), gb1, and their reduction into nn.Linear's layout
-template <int KIND, bool PROG>
+template <int KIND, bool PROG, bool SPATIAL = false>
 static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hipStream_t st) {
   using E = Enc<KIND>;
-  constexpr size_t lds = PROG ? FN_WG_LDS_PROG : FN_WG_LDS;
-  auto k = flownet_wgrad_kernel<KIND, true, PROG>;
+  constexpr size_t lds = SPATIAL ? FN_WG_LDS_PROG + FN_CN_LDS : PROG ? FN_WG_LDS_PROG : FN_WG_LDS;
+  auto k = flownet_wgrad_kernel<KIND, true, PROG, SPATIAL>;
   if (raise_lds(k, lds, "flownet_wgrad")) return 1;
   const int nc = wgrad_chunks(q.ntiles, E::CHUNK_KF);  // not a function of k_active: the order of every sum stays the same
   // progressive, wide: the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate
@@ -849,16 +1115,17 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
   } else {
     const int kcols = !PROG ? E::LIVE : E::NARROW ? oe : ktiles * FN_WT;
     hipLaunchKernelGGL((flownet_reduce_l1_kernel<E::KW, E::LIVE, PROG>), dim3((FN_HID * E::width(PROG) + FN_HID + FN_NTHR - 1) / FN_NTHR),
-                       dim3(FN_NTHR), 0, st, (const float*)q.part, nc, PROG ? a->mask : (const float*)nullptr, kcols, a->gw[0], a->gb[0]);
+                       dim3(FN_NTHR), 0, st, (const float*)q.part, nc, PROG && !SPATIAL ? a->mask : (const float*)nullptr, kcols, a->gw[0], a->gb[0]);
   }
   SININN_LAUNCH_CHECK("flownet_reduce");
   return 0;
 }
 
 // g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
-static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st) {
+// spatial != nullptr: layer 1 under the per-point mask of that grid
+static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial = nullptr) {
   FlowNetDev q;
-  if (int rc = check_args(a, "flownet_backward", q)) return rc;
+  if (int rc = check_args(a, spatial ? "flownet_backward_spatial" : "flownet_backward", q, spatial)) return rc;
   SININN_CHECK(a->dflows && a->saved && a->workspace, "flownet_backward: null dflows / saved / workspace");
   SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_backward: saved holds %zu bytes, %zu needed", a->saved_bytes,
                flownet_saved_bytes(q.N));
@@ -886,17 +1153,23 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
   for (int l = 2; l >= 1; --l)                         // gW3 = dh3^T h2, gW2 = dh2^T h1
     if (int rc = hidden_wgrad_launch(q.ntiles, q.dh + l * lstride, q.saved + (l - 1) * lstride, q.part, a->gw[l], a->gb[l], st)) return rc;
   if (int rc = for_kind(a->encoding, 1, [&](auto k) {
-        return a->progressive ? wgrad_l1_launch<decltype(k)::value, true>(a, q, st) : wgrad_l1_launch<decltype(k)::value, false>(a, q, st);
+        constexpr int KIND = decltype(k)::value;
+        if constexpr (Enc<KIND>::width(true) == FN_GW) {
+          if (spatial) return wgrad_l1_launch<KIND, true, true>(a, q, st);
+        }
+        return a->progressive ? wgrad_l1_launch<KIND, true>(a, q, st) : wgrad_l1_launch<KIND, false>(a, q, st);
       }))
     return rc;
   if (g_enc_a) {
     float* const epart = enc_ws + (size_t)Fourier::LIVE * FN_HID;
-    const float* const mask = a->progressive ? a->mask : nullptr;
+    const float* const mask = a->progressive && !spatial ? a->mask : nullptr;
     const int fopen = a->progressive ? (open_encoded(a) + 1) / 2 : FN_NF;   // a frequency is open if its sin or its cos is
-    hipLaunchKernelGGL(flownet_encgrad_pack_kernel, dim3(Fourier::LIVE), dim3(FN_NTHR), 0, st, a->w[0], mask, enc_ws);
+    hipLaunchKernelGGL(flownet_encgrad_pack_kernel, dim3(Fourier::LIVE), dim3(FN_NTHR), 0, st, a->w[0], mask, enc_ws, spatial ? 1 : 0);
     SININN_LAUNCH_CHECK("flownet_encgrad_pack");
-    if (raise_lds(flownet_encgrad_kernel, FN_LDS, "flownet_encgrad")) return 1;
-    hipLaunchKernelGGL(flownet_encgrad_kernel, dim3(cb), dim3(FN_NTHR), FN_LDS, st, q, (const float*)enc_ws, epart, fopen);   // not a function of k_active
+    const size_t elds = spatial ? FN_LDS + FN_CN_LDS : FN_LDS;
+    auto ek = spatial ? flownet_encgrad_kernel<true> : flownet_encgrad_kernel<false>;
+    if (raise_lds(ek, elds, "flownet_encgrad")) return 1;
+    hipLaunchKernelGGL(ek, dim3(cb), dim3(FN_NTHR), elds, st, q, (const float*)enc_ws, epart, fopen);   // not a function of k_active
     SININN_LAUNCH_CHECK("flownet_encgrad");
     hipLaunchKernelGGL(flownet_reduce_enc_kernel, dim3((FN_EG_PART + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, (const float*)epart, cb, mask,
                        fopen, g_enc_a);
@@ -929,9 +1202,21 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
   return 0;
 }
 
-int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
+// the spatial forward: W1 in place, no pack kernel, no workspace
+template <int KIND>
+static int forward_spatial_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipStream_t st) {
+  q.ksteps = (open_encoded(a) + 15) / 16;
+  auto k = flownet_fwd_kernel<KIND, true, true>;
+  if (raise_lds(k, FN_LDS + FN_CN_LDS, "flownet_forward_spatial")) return 1;
+  const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS + FN_CN_LDS, st, q);
+  SININN_LAUNCH_CHECK("flownet_forward_spatial");
+  return 0;
+}
+
+static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial) {
   FlowNetDev q;
-  if (int rc = check_args(a, "flownet_forward", q)) return rc;
+  if (int rc = check_args(a, spatial ? "flownet_forward_spatial" : "flownet_forward", q, spatial)) return rc;
   SININN_CHECK(a->flows != nullptr, "flownet_forward: null flows");
   q.flows = a->flows;
   if (a->saved) {
@@ -941,16 +1226,56 @@ int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) {
     q.saved = a->saved;
   }
   return for_kind(a->encoding, 1, [&](auto k) {
-    return a->progressive ? forward_kind_launch<decltype(k)::value, true>(a, q, st) : forward_kind_launch<decltype(k)::value, false>(a, q, st);
+    constexpr int KIND = decltype(k)::value;
+    if constexpr (Enc<KIND>::width(true) == FN_GW) {
+      if (spatial) return forward_spatial_kind_launch<KIND>(a, q, st);
+    }
+    return a->progressive ? forward_kind_launch<KIND, true>(a, q, st) : forward_kind_launch<KIND, false>(a, q, st);
   });
+}
+
+int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) { return forward_launch(a, st, nullptr); }
+
+int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  return forward_launch(a, st, &s);
+}
+
+int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  return backward_launch(a, nullptr, nullptr, st, &s);
+}
+
+int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  FlowNetDev q{};
+  if (int rc = check_spatial(a, "flownet_sample_mask", s, q)) return rc;
+  SININN_CHECK(out != nullptr, "flownet_sample_mask: null out");
+  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "flownet_sample_mask: grid %d x %d x %d (1 .. 2^22 points)",
+               a->T, a->H, a->W);
+  SININN_CHECK(a->times && a->ys && a->xs, "flownet_sample_mask: null axis pointer");
+  q.T = a->T; q.H = a->H; q.W = a->W;
+  q.N = a->T * a->H * a->W;
+  q.ntiles = (q.N + FN_P - 1) / FN_P;
+  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
+  const size_t units = ((size_t)q.N * FN_GROUPS + FN_NTHR - 1) / FN_NTHR;
+  hipLaunchKernelGGL(flownet_sample_mask_kernel, dim3((unsigned)(units < 8192 ? units : 8192)), dim3(FN_NTHR), 0, st, q, out);
+  SININN_LAUNCH_CHECK("flownet_sample_mask");
+  return 0;
 }
 
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_launch(a, nullptr, nullptr, st); }
 
-int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                    hipStream_t st) {
-  const char* who = "flownet_backward_encgrad";
+static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st,
+                                   const SpatialArgs* spatial) {
+  const char* who = spatial ? "flownet_backward_encgrad_spatial" : "flownet_backward_encgrad";
   if (int rc = check_network(a, who)) return rc;
+  if (spatial) {
+    // checked again by backward_launch (check_args), which fills its own descriptor; here only so that a refusal of the mode (PPE, a
+    // null grid, res) is reported under this entry point's name and before the Fourier-only refusal below, which would hide it
+    FlowNetDev unused{};
+    if (int rc = check_spatial(a, who, *spatial, unused)) return rc;
+  }
   SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
                a->encoding);
   SININN_CHECK(g_enc_a != nullptr, "%s: null g_enc_a", who);
@@ -958,7 +1283,18 @@ int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a
                "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
                flownet_encgrad_workspace_bytes(a));
   SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
-  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st);
+  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st, spatial);
+}
+
+int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                    hipStream_t st) {
+  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, nullptr);
+}
+
+int flownet_backward_encgrad_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* g_enc_a,
+                                            void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, &s);
 }
 
 }  // namespace sininn

@@ -52,9 +52,15 @@ then `weight.uniform_`).  It runs in kernels of its own (csrc/siren.hip, `siren_
 `flow_fields`; the sine is the accurate full-range fp32 function and omega is passed on every call.  It is registered in
 `siren_model_dict`, beside `all_model_dict`, not in it.
 
-Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, the
-spatially adaptive controllers (`StashedSpatialController` of `--spatially-adaptive`: a per-point mask interpolated from a 50^3
-grid; `FixedSpatialController`; `AdaptiveController`).  Of `siren` only the `--net siren` switch of the command line remains
+Spatially adaptive progression (`sin_inn_amd.progressive.StashedSpatialController`, the reference's `--spatially-adaptive`): every
+point has its own 515 mask values, interpolated trilinearly from the controller's blurred grid [res^3][515] on the device.  The
+per-point mask never exists in memory either: the kernels sample the grid while they generate the operand of layer 1
+(`flownet_forward_spatial` / `flownet_backward_spatial`, `sininn_flownet_*_spatial`), W1 is read in place and there is no pack step.
+`flow_fields` takes that controller (`k_active` = its `next_block`), or a raw grid as a 2-D `override_mask`; `flownet_sample_mask`
+returns the interpolated mask itself (the reference's `get_mask=` keyword).  All 515-wide progressive networks; `PPE` is refused.
+
+Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
+`--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
 closed (video-interpolation/main.py still refuses it).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
 `sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
 `sin_inn_amd.FusedLAMB` is the reference's apex FusedLAMB (trainer.py:134-135) restated, `sin_inn_amd.FusedAdam` drives them as well.
@@ -418,7 +424,7 @@ def _on_gpu(t, what='tensor'):
         raise NotImplementedError(f'sin-inn_amd flownet runs on the GPU only (got a CPU {what})')
 
 
-def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
+def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spatial=False):
     lins = net.linears()
     a = _lib.FlowNetArgs()
     a.encoding = net.encode.kind
@@ -428,7 +434,11 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None):
         raise ValueError(_lib.lib().sininn_last_error().decode())
     if net.opt.domain_dim != 3 or len(lins) != 4:
         raise ValueError(f'flownet kernels take 3 coordinates and 4 linear layers; got {net.opt.domain_dim} and {len(lins)}')
-    if a.progressive:
+    if spatial:                                          # the grid goes beside the descriptor, its `mask` is ignored
+        if not a.progressive:
+            raise ValueError('a spatial mask needs a progressive network')
+        a.k_active = a.enc_dim if k_active is None else int(k_active)
+    elif a.progressive:
         if mask is None:
             raise ValueError('a progressive network is evaluated under a mask (flow_fields supplies all ones for a bare model)')
         _on_gpu(mask, 'mask')
@@ -516,6 +526,83 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, m
     return grads, g_enc
 
 
+IDENTITY_SCALE = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0)
+
+
+def _spatial(a, grid, res, centre_scale):
+    """(device grid, res, the six host floats) as the spatial entry points take them, checked against the descriptor"""
+    _on_gpu(grid, 'mask grid')
+    res = int(res)
+    assert grid.dtype == torch.float32 and grid.is_contiguous() and tuple(grid.shape) == (res ** 3, a.enc_dim), \
+        f'a mask grid of shape (res^3, {a.enc_dim}), contiguous fp32'
+    cs = (C.c_float * 6)(*[float(v) for v in (IDENTITY_SCALE if centre_scale is None else centre_scale)])
+    return ptr(grid), res, C.cast(cs, C.c_void_p), cs
+
+
+def flownet_forward_spatial(net, times, ys, xs, scale, train, grid, res, centre_scale=None, k_active=None, saved=None, enc_a=None):
+    """flownet_forward under a per-point mask: `grid` (res^3, 515) on the device, the controller's blurred mask; `centre_scale`: six
+    host floats, centre (t, y, x) then scale (t, y, x), None: identity; `k_active`: every grid column from there on is zero (None:
+    515).  No workspace: W1 is read in place."""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
+    g, res, cs, keep = _spatial(a, grid, res, centre_scale)
+    n = a.T * a.H * a.W
+    flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
+    if train:
+        nbytes = _lib.lib().sininn_flownet_saved_bytes(n)
+        if saved is None:
+            saved = torch.empty(3, nbytes // (3 * 256 * 4), 256, device=times.device, dtype=torch.float32)
+        assert saved.is_contiguous() and saved.dtype == torch.float32
+        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    else:
+        saved = None
+    a.flows = ptr(flows)
+    check(_lib.lib().sininn_flownet_forward_spatial(C.byref(a), g, res, cs, _stream()))
+    return flows, saved
+
+
+def flownet_backward_spatial(net, times, ys, xs, scale, dflows, saved, grid, res, centre_scale=None, k_active=None, workspace=None,
+                             enc_a=None, enc_grad=False, enc_workspace=None, g_enc_a=None):
+    """flownet_backward under the per-point mask of the forward call; the arguments of flownet_backward and flownet_forward_spatial"""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
+    g, res, cs, keep = _spatial(a, grid, res, centre_scale)
+    n = a.T * a.H * a.W
+    _on_gpu(dflows)
+    dflows = dflows.contiguous()
+    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
+    if workspace is None:
+        workspace = torch.empty(_lib.lib().sininn_flownet_workspace_bytes(n) // 4, device=times.device, dtype=torch.float32)
+    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
+    a.dflows = ptr(dflows)
+    grads = []
+    for l, lin in enumerate(net.linears()):
+        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
+        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
+        grads += [gw, gb]
+    if not enc_grad:
+        check(_lib.lib().sininn_flownet_backward_spatial(C.byref(a), g, res, cs, _stream()))
+        return grads
+    if enc_workspace is None:
+        enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=times.device, dtype=torch.float32)
+    g_enc = torch.empty(3, 256, device=times.device, dtype=torch.float32) if g_enc_a is None else g_enc_a
+    assert g_enc.is_cuda and g_enc.is_contiguous() and g_enc.dtype == torch.float32 and tuple(g_enc.shape) == (3, 256)
+    check(_lib.lib().sininn_flownet_backward_encgrad_spatial(C.byref(a), g, res, cs, ptr(g_enc), ptr(enc_workspace),
+                                                             enc_workspace.numel() * 4, _stream()))
+    return grads, g_enc
+
+
+def flownet_sample_mask(net, times, ys, xs, grid, res, centre_scale=None):
+    """the interpolated mask (N, 515) of the grid of points, bitwise what the spatial kernels multiply layer 1's input by"""
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a = _args(net, times, ys, xs, 1.0, spatial=True)
+    g, res, cs, keep = _spatial(a, grid, res, centre_scale)
+    out = torch.empty(a.T * a.H * a.W, a.enc_dim, device=times.device, dtype=torch.float32)
+    check(_lib.lib().sininn_flownet_sample_mask(C.byref(a), g, res, cs, ptr(out), _stream()))
+    return out
+
+
 def _siren_args(net, times, ys, xs, scale, omega=None):
     lins = net.linears()
     a = _lib.SirenArgs()
@@ -599,11 +686,15 @@ class _SirenFields(torch.autograd.Function):
 class _FlowFields(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, times, ys, xs, scale, train, mask, enc_a, *params):
-        mask, k_active = mask
+        mask, k_active, *spatial = mask                  # spatial: (res, centre_scale) after a grid (res^3, enc_dim)
         if enc_a is not None:
             enc_a = enc_a.detach().contiguous()
-        flows, saved = flownet_forward(net, times, ys, xs, scale, train, mask=mask, k_active=k_active, enc_a=enc_a)
-        ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask = net, (times, ys, xs), scale, saved, (mask, k_active)
+        if spatial:
+            flows, saved = flownet_forward_spatial(net, times, ys, xs, scale, train, mask, *spatial, k_active=k_active, enc_a=enc_a)
+            ctx.grid_version = mask._version             # the controller updates its grid in place
+        else:
+            flows, saved = flownet_forward(net, times, ys, xs, scale, train, mask=mask, k_active=k_active, enc_a=enc_a)
+        ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask, ctx.spatial = net, (times, ys, xs), scale, saved, (mask, k_active), spatial
         ctx.enc_a, ctx.enc_grad = enc_a, enc_a is not None and ctx.needs_input_grad[7]
         return flows
 
@@ -611,8 +702,15 @@ class _FlowFields(torch.autograd.Function):
     def backward(ctx, dflows):
         if ctx.saved is None:
             raise RuntimeError('flow_fields: backward through an inference-mode forward')
-        grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, mask=ctx.mask[0], k_active=ctx.mask[1], enc_a=ctx.enc_a,
-                                 enc_grad=ctx.enc_grad)
+        if ctx.spatial:
+            if ctx.mask[0]._version != ctx.grid_version:
+                raise RuntimeError('flow_fields: the mask grid changed between the forward and the backward pass (run backward before '
+                                   'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
+            grads = flownet_backward_spatial(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, ctx.mask[0], *ctx.spatial,
+                                             k_active=ctx.mask[1], enc_a=ctx.enc_a, enc_grad=ctx.enc_grad)
+        else:
+            grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, mask=ctx.mask[0], k_active=ctx.mask[1],
+                                     enc_a=ctx.enc_a, enc_grad=ctx.enc_grad)
         g_enc = None
         if ctx.enc_grad:
             grads, g_enc = grads
@@ -637,36 +735,61 @@ def last_open(mask):
 
 def _resolve_mask(net, override_mask, device):
     """(model, (device mask, k_active)) for a plain model, a bare progressive model or a controller (a module that wraps a
-    progressive model as `.model` and keeps a mask)"""
-    from .progressive import ProgressiveEncoderController
+    progressive model as `.model` and keeps a mask); (model, (device grid, k_active, res, centre_scale)) under a spatial controller
+    or a raw 2-D grid"""
+    from .progressive import ProgressiveEncoderController, StashedSpatialController
     controller = net if isinstance(net, ProgressiveEncoderController) else None
+    spatial = controller if isinstance(controller, StashedSpatialController) else None
     model = net.model if controller is not None else net
     if not model.is_progressive:
         if override_mask is not None:
             raise ValueError('override_mask needs a progressive network')
         return model, (None, None)
+    if override_mask is not None and override_mask.dim() == 2:
+        # a raw grid (res^3, enc_dim) on the device: not inspected, nothing skipped; the cell map is the spatial controller's, else identity
+        g = override_mask.detach()
+        _on_gpu(g, 'mask grid')
+        res = round(g.shape[0] ** (1.0 / 3.0))
+        if res ** 3 != g.shape[0] or g.shape[1] != model.encoding_dim:
+            raise ValueError(f'a mask grid has shape (res^3, {model.encoding_dim}); got {tuple(g.shape)}')
+        cs = spatial.centre_scale_host() if spatial is not None else IDENTITY_SCALE
+        return model, (g.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim, res, cs)
     if override_mask is not None:
         m = override_mask.detach()
-        assert m.dim() == 1 and m.numel() == model.encoding_dim, 'a global mask of encoding_dim values (per-point masks are out of scope)'
+        assert m.dim() == 1 and m.numel() == model.encoding_dim, 'a global mask of encoding_dim values, or a grid (res^3, encoding_dim)'
         if m.is_cuda:                                    # not inspected on the host: no synchronisation, nothing skipped
             return model, (m.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim)
         m = m.to(torch.float32).contiguous()
         return model, (m.to(device), last_open(m))
+    if spatial is not None:
+        return model, spatial.device_grid(device)
     if controller is not None:
         return model, controller.device_mask(device)
     return model, (model.ones_mask(device), model.encoding_dim)
 
 
-def flow_fields(net, times, h, w, scale, override_mask=None):
+def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
     """FlowTrainer.forward (trainer.py:37-45): (flow12, flow21), each (t, 2, h, w), views of one (t, 4, h, w) tensor.  Under
     torch.no_grad() (or with no trainable parameter) the inference mode of the kernel runs and nothing is saved.  `net` is a
     model or a controller around a progressive model; `override_mask` (515 values, PPE: 27; progressive networks only) replaces the
     controller's mask.  A learnable encoding (RFF / PRFF) contributes F_eff, computed here with torch ops; its gradient is computed
-    only if `encode.frequencies` requires one.  A SirenModel runs in its own kernels under the same contract."""
+    only if `encode.frequencies` requires one.  A SirenModel runs in its own kernels under the same contract.
+    A StashedSpatialController, or an `override_mask` of shape (res^3, 515) on the device, evaluates the network under the per-point
+    mask interpolated from that grid.  `get_mask=True` (the reference's keyword) returns (flow12, flow21, mask): the mask in use, (515,)
+    or, spatial, the interpolated (t h w, 515)."""
     _on_gpu(times)
     assert times.dtype == torch.float32 and times.dim() == 1
+    controller = net
     net, mask = _resolve_mask(net, override_mask, times.device)
     ys, xs = grid_axes(net, times, h, w)
+    if len(mask) == 4 and hasattr(controller, 'note_grid'):
+        controller.note_grid(times, ys, xs)              # stash_iteration finds the cells of these points
+    if get_mask:
+        if not net.is_progressive:
+            raise ValueError('get_mask needs a progressive network')
+        with torch.no_grad():
+            used = flownet_sample_mask(net, times, ys, xs, mask[0], *mask[2:]) if len(mask) == 4 else mask[0]
+        return (*flow_fields(controller, times, h, w, scale, override_mask), used)
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
     if isinstance(net, SirenModel):
         train = torch.is_grad_enabled() and any(p.requires_grad for p in params)

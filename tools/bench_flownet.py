@@ -13,6 +13,10 @@ host tensor so that the kernels skip the closed features as they do under a cont
 network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.
 RFF / PRFF (learnable frequencies) add the data gradient through layer 1 to the step (2 N 512*256 more FLOPs, counted) and the torch ops
 that make F_eff and carry its gradient to `encode.frequencies`; PRFF runs under the prefix mask like the other progressive nets.
+--spatial R (515-wide progressive nets) puts the network under a StashedSpatialController(net, R) whose every cell has the prefix mask of
+--k-active ones: the fused path samples the grid [R^3][515] in the kernels (sininn_flownet_*_spatial, k_active = --k-active), the
+--baseline is composed_flow_fields with the reference's own gather + einsum, `get_mask()[inds]` (N, 8, 515) times the weights, on every
+call.  The FLOP counts stay those of the network; the interpolation is not counted.
 `siren` is 3-256-256-256-256-4: 2 N (3*256 + 3*256*256 + 256*4) FLOPs forward; backward adds the data gradients of layers 2-5 and the
 weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines in the backward pass) are not counted.
 """
@@ -72,6 +76,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--rounds', type=int, default=2, help='alternations of the fused and the baseline windows')
     ap.add_argument('--baseline', action='store_true')
+    ap.add_argument('--spatial', type=int, default=0, metavar='R', help='progressive nets: a per-point mask from an R^3 grid (0: the global mask)')
     a = ap.parse_args()
     from sin_inn_amd import _lib, flownet, progressive
     from fit_flow import composed_flow_fields
@@ -82,7 +87,16 @@ def main():
     net = {**flownet.all_model_dict, **flownet.siren_model_dict}[a.net](flownet.ModelParams()).to(dev)
     prog = net.is_progressive
     target = net
-    if prog:
+    if a.spatial:
+        assert prog and net.encoding_dim == 515, '--spatial needs a 515-wide progressive network'
+        assert 6 <= a.k_active <= 515
+        target = progressive.StashedSpatialController(net, a.spatial)
+        target.mask.zero_()
+        target.mask[:, :a.k_active] = 1
+        target.mask_ = None
+        target.cur_block = target.next_block = a.k_active          # k_active of the kernels
+        assert target.device_grid(dev)[1] == a.k_active
+    elif prog:
         assert 0 <= a.k_active <= 515
         a.k_active = min(a.k_active, net.encoding_dim)
         target = progressive.LinearController(net)
@@ -95,7 +109,7 @@ def main():
     params = list(net.parameters())
 
     def paths(fields):
-        kw = dict(override_mask=mask_dev) if prog and fields is composed_flow_fields else {}
+        kw = dict(override_mask=mask_dev) if prog and not a.spatial and fields is composed_flow_fields else {}
 
         def fwd():
             with torch.no_grad():
@@ -119,7 +133,7 @@ def main():
     f_fwd, f_step = flops_siren(n) if siren else flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
     sizes = (_lib.lib().sininn_siren_saved_bytes, _lib.lib().sininn_siren_workspace_bytes) if siren else \
         (_lib.lib().sininn_flownet_saved_bytes, _lib.lib().sininn_flownet_workspace_bytes)
-    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
+    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=sizes[0](n), workspace_bytes=sizes[1](n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):

@@ -8,12 +8,17 @@
     python tools/fit_flow.py --net PPE
     python tools/fit_flow.py --net siren
     python tools/fit_flow.py --optimizer lamb
+    python tools/fit_flow.py --net PRBF --controller spatial --res 7
 
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
 
 A progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, PPE) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
 video-interpolation/main.py:136-143 does, and the controller sees the loss after every step (trainer.py:75), which opens the mask.
+
+`--controller spatial [--res R]` wraps a 515-wide progressive network in StashedSpatialController(net, R) instead (the reference's
+--spatially-adaptive): after every step the controller stashes the per-pixel squared error of flow12 against the pair's known flow,
+and every `block_iterations` (20) steps `update_progress()` closes the cells that are fitted and opens the next block in the others.
 
 RFF / PRFF train `encode.frequencies` as well: the optimiser gets net.parameters(), which includes them.
 
@@ -65,13 +70,19 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     model.py:331-332, without the `.view(-1, 21)` that raises unless N is a multiple of 7 (the cat is already (N, 4, 6)).  A SirenModel has
     no encoding: sin(omega_0 * linear(x)) four times and the last nn.Linear, model.py:145-146, 163-171."""
     mask = override_mask
+    spatial = None
     if hasattr(net, 'mask'):                                      # a controller
-        mask = net.mask if mask is None else mask
+        if hasattr(net, 'interpolate'):                           # spatially adaptive: the reference's gather + einsum, (N, 8, 515)
+            spatial = net
+        else:
+            mask = net.mask if mask is None else mask
         net = net.model
     ys = torch.linspace(-1, 1, h).to(times)
     xs = torch.linspace(-1, 1, w).to(times)
     gt, gh, gw = torch.meshgrid(times, ys, xs, indexing='ij')
     x = poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
+    if spatial is not None and mask is None:
+        mask = spatial.interpolate(poses)                         # (N, 515), one row per point
     if not hasattr(net, 'encode'):                                # siren
         for layer in net.model:
             x = torch.sin(layer.omega_0 * layer.linear(x)) if hasattr(layer, 'omega_0') else layer(x)
@@ -98,25 +109,34 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     if net.is_progressive:
         x = torch.cat((poses, x), dim=-1)
         if mask is not None:
-            x = x * mask.to(x)[None, :]
+            x = x * (mask.to(x) if mask.dim() == 2 else mask.to(x)[None, :])
     flows = net.model.model(x).view(times.numel(), h, w, 4).permute(0, 3, 1, 2) * scale
     return flows[:, :2], flows[:, 2:]
 
 
 def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None, max_iteration=1000,
-        info=None, optimizer='adam'):
-    """returns the list of per-step losses (floats); `info`: a dict that receives the network (the controller of a progressive one)"""
+        info=None, optimizer='adam', controller='early', res=7):
+    """returns the list of per-step losses (floats); `info`: a dict that receives the network (the controller of a progressive one,
+    and under `controller='spatial'` the number of update_progress calls as info['progress'])"""
     from sin_inn_amd import FusedAdam, FusedLAMB, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
     net = {**flownet.all_model_dict, **flownet.siren_model_dict}[net_name](flownet.ModelParams()).to(device)
-    if net.is_progressive:
+    assert controller in ('early', 'spatial'), controller
+    spatial = controller == 'spatial'
+    if spatial:
+        if not net.is_progressive or net.encoding_dim != 515:
+            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG); got {net_name}')
+        net = progressive.StashedSpatialController(net, res)
+    elif net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
     if info is not None:
         info['net'] = net
     assert optimizer in ('adam', 'lamb'), optimizer
     opt = (FusedLAMB if optimizer == 'lamb' else FusedAdam)(net.parameters(), lr=lr)
-    frame1, frame2, _ = make_pair(h, w, seed + 1, device)
+    frame1, frame2, true_flow = make_pair(h, w, seed + 1, device)
+    if info is not None:
+        info['progress'] = 0
     times = torch.zeros(1, device=device)
     l1, census, smooth = FL.L1Loss(1.0), FL.CensusLoss(0.1, max_distance=3), FL.BilateralSmooth(0.1, 'gauss', 150, 1)
     fields = composed_flow_fields if composed else flownet.flow_fields
@@ -138,7 +158,14 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
                 + smooth(frame1, flow12) + smooth(frame2, flow21))
         loss.backward()
         opt.step()
-        net.stash_iteration(loss.detach())
+        if spatial:
+            net.stash_iteration((flow12.detach() - true_flow).pow(2).sum(1).flatten())
+            if (step + 1) % net.block_iterations == 0:
+                net.update_progress()
+                if info is not None:
+                    info['progress'] += 1
+        else:
+            net.stash_iteration(loss.detach())
         losses.append(float(loss))
         if log:
             extra = f'  open {net.cur_block:3d} / {net.encoding_dim}' if net.is_progressive else ''
@@ -157,9 +184,11 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--composed', action='store_true')
     ap.add_argument('--optimizer', default='adam', choices=['adam', 'lamb'])
+    ap.add_argument('--controller', default='early', choices=['early', 'spatial'], help='progressive nets: the mask is global / per grid cell')
+    ap.add_argument('--res', type=int, default=7, help='--controller spatial: cells per axis of the mask grid')
     a = ap.parse_args()
     losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration,
-                 optimizer=a.optimizer)
+                 optimizer=a.optimizer, controller=a.controller, res=a.res)
     print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
 
 

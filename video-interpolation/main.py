@@ -10,7 +10,7 @@ Differences from the reference, all to make the path runnable here:
     `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
   * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
   * `--net` takes the twelve networks of `sin_inn_amd.flownet`; `siren`, `MPFF` and `--spatially-adaptive` exit with a
-    message (flownet.py lists them as out of scope);
+    message (flownet.py lists them as out of scope; the spatial controller itself is ported, the switch stays closed);
   * `--ngpus N` is N devices (cuda:0 .. cuda:N-1, the first is used), as in Lightning, not a device index;
   * a video file as `--input-video` (imageio + RAFT) is refused;
   * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)` (PPE: `// 12`), which is 0 below 112 (4) epochs, and the
@@ -77,8 +77,9 @@ def get_args(argv=None):
     if args.occl == 'None':                                    # argparse cannot produce the reference's `None` choice from a string
         args.occl = None
     if args.spatially_adaptive:
-        parser.error('--spatially-adaptive is out of scope: StashedSpatialController needs a per-point mask, the fused kernels '
-                     'take one global mask (sin_inn_amd/flownet.py)')
+        parser.error('--spatially-adaptive is out of scope here: sin_inn_amd.progressive.StashedSpatialController and the spatial '
+                     'kernels exist (tools/fit_flow.py --controller spatial drives them), but the controller needs a per-point loss '
+                     'and this trainer, like the reference\'s, hands its controller a scalar')
     if args.net in OUT_OF_SCOPE_NETWORKS:
         parser.error(f'--net {args.net} is out of scope: the fused kernels are built for {", ".join(NETWORKS)} '
                      '(sin_inn_amd/flownet.py)')
