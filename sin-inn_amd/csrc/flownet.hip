@@ -18,7 +18,15 @@
 //           gradient); the row strides of W1, the pack size, the K steps, the weight-gradient tile and its partial sums are derived from
 //           it there and nowhere else.  for_kind turns the run-time `encoding` into that compile-time kind for every launch, for
 //           flownet_supported and for the text of its refusal.  A new encoding is one Enc<> row, one case in for_kind and one branch
-//           of encode4.
+//           of encode4.  The mode of a call is described once as well: for_mode turns (encoding, progressive, spatial) into the three
+//           template arguments for the forward and the backward dispatch, forward_kind_launch<KIND, PROG, SPATIAL> is the one forward
+//           launch, tile_lds / wgrad_lds are the LDS size of every launch of a kernel mode, check_head is the head of every entry point
+//           (the struct, the support table and, spatial, the refusals of that mode, made once under the entry point's own name).
+//           Shared with siren.hip through flownet_tile.h: the tile, gemm_lds, mfma_k4 (the coordinate K group), store_acc and its
+//           epilogues, copy_tile_out, stage_coord, and on the host the point-grid part of a descriptor
+//           (check_points), check_layers, check_saved and the buffer checks of a forward and a backward call.  siren.hip also calls
+//           hidden_wgrad_launch below.  The output layer, dout, the tile load, the column sums and the transpose kernel are spelled out
+//           here and there: as helpers they changed the instructions, or the placement, of the kernels that use them.
 //
 // forward   flownet_fwd_kernel: block = 256 threads (4 waves, two blocks per CU), grid-stride over 64-point tiles.  Wave w owns
 //           hidden columns [64 w, 64 w + 64) of all 64 rows: 16 accumulator tiles.  Layer 1's A operand comes from encode4, layers
@@ -73,10 +81,15 @@ constexpr int FN_WS = FN_WT + 16;   // floats per point row of a weight-gradient
 constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunks) x (output tiles) is about 512 blocks
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
 constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features
-constexpr size_t FN_WG_LDS_PROG = FN_WG_LDS + (size_t)(FN_P * FN_CS) * sizeof(float);
 constexpr int FN_GW = 512 + FN_DOM;  // spatial: floats per row of the mask grid and of the W1 it goes with
 constexpr int FN_CN = 16;           // spatial: floats per point of the corner tile in LDS: 8 weights, 8 row offsets
 constexpr size_t FN_CN_LDS = (size_t)(FN_P * FN_CN) * sizeof(float);
+// the dynamic LDS of each kernel mode, for every launch of it: the forward, chain and frequency-gradient kernels hold the hidden tile and
+// a [64][4] tile, the weight gradient its two operand tiles and (PROG) the coordinate tile; SPATIAL adds the corner tile
+constexpr size_t tile_lds(bool spatial) { return FN_LDS + (spatial ? FN_CN_LDS : 0); }
+constexpr size_t wgrad_lds(bool prog, bool spatial) {
+  return FN_WG_LDS + (prog ? (size_t)(FN_P * FN_CS) * sizeof(float) : 0) + (spatial ? FN_CN_LDS : 0);
+}
 
 // ---- the input of a layer as the kernels see it: LIVE features in a K range of KW.  Everything that depends on the encoding is here ----
 template <int LIVE_, int KW_, bool ENC_B_ = false, bool FREQ_GRAD_ = false>
@@ -330,22 +343,12 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
 
 
 
-// accumulators -> LDS tile; RELU: + bias, max(., 0)
-template <bool RELU>
-__device__ __forceinline__ void store_acc(float* hs, const float* bias, int cw, int li, int kq, const f32x4 (&acc)[4][4]) {
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const float bq = RELU ? bias[cw + 16 * n + li] : 0.f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = acc[m][n][r] + bq;
-        hs[(16 * m + 4 * kq + r) * FN_HS + cw + 16 * n + li] = RELU ? fmaxf(v, 0.f) : v;
-      }
-  }
-}
-
+// the chain kernel's plain store: acc + 0.f, which turns a -0 into +0.  flownet_tile.h's Plain stores the accumulator as it is; this kernel
+// keeps the sum it has always made, its instructions and its bits
+struct PlainAddZero {
+  __device__ __forceinline__ float col(int) const { return 0.f; }
+  __device__ __forceinline__ float operator()(float v, float bq) const { return v + bq; }
+};
 
 // PROG: q.w[0] is the packed W1p [256][KW], q.wc the coordinate columns, q.ksteps the length of the K loop
 // SPATIAL (with PROG): q.w[0] is nn.Linear's own W1 [256][FN_GW], the operand is multiplied by the point's mask, q.ksteps as above
@@ -393,10 +396,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) b[n] = q.wc[(cw + 16 * n + li) * FN_CS + kq];
       }
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
+      mfma_k4(a, b, acc);
     }
     // ---- layer 1: the A fragment is generated, never stored ----
     const int ksteps = PROG ? q.ksteps : E::KSTEPS;
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
           for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][j], bf[n][j], acc[m][n], 0, 0, 0);
     }
     __syncthreads();                       // the previous tile's layer 4 has read hs
-    store_acc<true>(hs, q.b[0], cw, li, kq, acc);
+    store_acc(hs, cw, li, kq, acc, BiasRelu{q.b[0]});
     __syncthreads();
     if (q.saved) copy_tile_out(hs, q.saved, tile, tid);
     // ---- layers 2 and 3 ----
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
       zero_acc(acc);
       gemm_lds(hs, q.w[l], cw, li, kq, acc);
       __syncthreads();                     // every wave has read the whole tile (and copied it out)
-      store_acc<true>(hs, q.b[l], cw, li, kq, acc);
+      store_acc(hs, cw, li, kq, acc, BiasRelu{q.b[l]});
       __syncthreads();
       if (q.saved) copy_tile_out(hs, q.saved + l * lstride, tile, tid);
     }
@@ -515,7 +515,6 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
 
   for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
     __syncthreads();                                   // the previous tile is done with hs / dos
-    // h3 tile -> LDS, dout = dflows * scale (0 beyond N)
 #pragma unroll 4
     for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
       const int f = tid + FN_NTHR * u;
@@ -561,7 +560,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
       zero_acc(acc);
       gemm_lds(hs, q.wt + (size_t)l * FN_HID * FN_HID, cw, li, kq, acc);
       __syncthreads();
-      store_acc<false>(hs, nullptr, cw, li, kq, acc);
+      store_acc(hs, cw, li, kq, acc, PlainAddZero{});
       __syncthreads();
 #pragma unroll 4
       for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
@@ -658,10 +657,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
       }
     }
     if constexpr (PROG && !SPATIAL) {
-      if (k0 == 0 && tid < FN_P) {
-        const Coord c = point_coord(q, tile * FN_P + tid);
-        *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
-      }
+      if (k0 == 0 && tid < FN_P) stage_coord(q, cs, tile, tid);
     }
     __syncthreads();
     if (tile + nchunks < q.ntiles) fetch(tile + nchunks);
@@ -974,9 +970,9 @@ int hidden_wgrad_launch(int ntiles, const float* dh, const float* in, float* par
   q.ntiles = ntiles;
   q.part = part;
   auto k = flownet_wgrad_kernel<SININN_FLOWNET_RBF, false>;
-  if (raise_lds(k, FN_WG_LDS, "flownet_wgrad")) return 1;
+  if (raise_lds(k, wgrad_lds(false, false), "flownet_wgrad")) return 1;
   const int nc = wgrad_chunks(ntiles, Hidden::CHUNK_KF);
-  hipLaunchKernelGGL(k, dim3(2 * Hidden::KW / Hidden::KT, nc), dim3(FN_NTHR), FN_WG_LDS, st, q, dh, in);
+  hipLaunchKernelGGL(k, dim3(2 * Hidden::KW / Hidden::KT, nc), dim3(FN_NTHR), wgrad_lds(false, false), st, q, dh, in);
   SININN_LAUNCH_CHECK("flownet_wgrad");
   reduce_launch(q, nc, FN_HID * FN_HID, FN_HID, gw, gb, st);
   SININN_LAUNCH_CHECK("flownet_reduce");
@@ -1026,14 +1022,6 @@ size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
   return has ? FN_EG_FLOATS * sizeof(float) : 0;
 }
 
-// the head of every entry point: a struct of this library's size that describes a network the kernels are built for
-static int check_network(const sininn_flownet_args* a, const char* who) {
-  SININN_CHECK(a != nullptr, "%s: null args", who);
-  SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
-               a->struct_bytes, sizeof(sininn_flownet_args));
-  return flownet_supported(a, who) ? 0 : 1;
-}
-
 // what the spatial entry points take beside the descriptor
 struct SpatialArgs {
   const float* grid;
@@ -1041,66 +1029,76 @@ struct SpatialArgs {
   const float* centre_scale;   // host [6]
 };
 
-// the spatial mode: a 515-wide progressive network, a grid the kernels can index; everything a launch would trip over, before any launch
-static int check_spatial(const sininn_flownet_args* a, const char* who, const SpatialArgs& s, FlowNetDev& q) {
-  if (int rc = check_network(a, who)) return rc;
+// the head of every entry point: a struct of this library's size that describes a network the kernels are built for; spatial != nullptr:
+// and the spatial mode, a 515-wide progressive network and a grid the kernels can index.  Everything a launch would trip over, before any
+// launch
+static int check_head(const sininn_flownet_args* a, const char* who, const SpatialArgs* spatial) {
+  SININN_CHECK(a != nullptr, "%s: null args", who);
+  SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
+               a->struct_bytes, sizeof(sininn_flownet_args));
+  if (!flownet_supported(a, who)) return 1;
+  if (!spatial) return 0;
   SININN_CHECK(a->progressive == 1, "%s: a spatial mask needs a progressive network (progressive = 1)", who);
   SININN_CHECK(a->enc_dim == FN_GW,
                "%s: spatial masks are built for the %d-wide progressive encodings (PRBF, PFF / PUFF / PRFF, PRBFG); PPE (enc_dim %d, a packed "
                "narrow layer 1 of its own) is out of scope for this mode", who, FN_GW, a->enc_dim);
-  SININN_CHECK(s.grid != nullptr && s.centre_scale != nullptr, "%s: null grid / centre_scale", who);
-  SININN_CHECK(s.res >= 3, "%s: res %d (at least 3)", who, s.res);
-  SININN_CHECK((int64_t)s.res * s.res * s.res * FN_GW <= (int64_t)INT32_MAX, "%s: res %d: res^3 * %d exceeds the kernels' 32-bit indexing", who,
-               s.res, FN_GW);
-  q.sp.grid = s.grid;
-  q.sp.res = s.res;
-  q.sp.span = (float)(s.res - 2 > 1 ? s.res - 2 : 1);
-  for (int d = 0; d < 3; ++d) {
-    q.sp.centre[d] = s.centre_scale[d];
-    q.sp.scale[d] = s.centre_scale[3 + d];
-  }
+  SININN_CHECK(spatial->grid != nullptr && spatial->centre_scale != nullptr, "%s: null grid / centre_scale", who);
+  SININN_CHECK(spatial->res >= 3, "%s: res %d (at least 3)", who, spatial->res);
+  SININN_CHECK((int64_t)spatial->res * spatial->res * spatial->res * FN_GW <= (int64_t)INT32_MAX,
+               "%s: res %d: res^3 * %d exceeds the kernels' 32-bit indexing", who, spatial->res, FN_GW);
   return 0;
 }
 
-// spatial != nullptr: the descriptor's mask is ignored, the grid is checked and goes to q.sp
-static int check_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial = nullptr) {
-  q.sp = Spatial{};
-  if (spatial) {
-    if (int rc = check_spatial(a, who, *spatial, q)) return rc;
-  } else if (int rc = check_network(a, who)) {
-    return rc;
+// the kernels' view of a grid that check_head has accepted; nullptr: none
+static Spatial spatial_of(const SpatialArgs* s) {
+  Spatial sp{};
+  if (s) {
+    sp.grid = s->grid;
+    sp.res = s->res;
+    sp.span = (float)(s->res - 2 > 1 ? s->res - 2 : 1);
+    for (int d = 0; d < 3; ++d) {
+      sp.centre[d] = s->centre_scale[d];
+      sp.scale[d] = s->centre_scale[3 + d];
+    }
   }
+  return sp;
+}
+
+// the descriptor of a call whose entry point has called check_head, checked and copied into q.  spatial != nullptr: the descriptor's mask
+// is ignored, the grid goes to q.sp
+static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial) {
+  q = FlowNetDev{};
+  q.sp = spatial_of(spatial);
   if (a->progressive) {
     SININN_CHECK(spatial || a->mask != nullptr, "%s: progressive network without a mask", who);
     SININN_CHECK(a->k_active >= 0 && a->k_active <= a->enc_dim, "%s: k_active %d (0 .. %d)", who, a->k_active, a->enc_dim);
   }
-  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
-               who, a->T, a->H, a->W);
   const bool enc_b = for_kind(a->encoding, false, [](auto k) { return Enc<decltype(k)::value>::ENC_B; });
-  SININN_CHECK(a->times && a->ys && a->xs && a->enc_a && (a->enc_b || !enc_b), "%s: null axis / encoding pointer", who);
+  if (int rc = check_points(a, who, q, a->enc_a && (a->enc_b || !enc_b), "axis / encoding")) return rc;
   SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
-  for (int l = 0; l < 4; ++l) {
-    SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
-    SININN_CHECK(aligned16(a->w[l]), "%s: weight %d must be 16-byte aligned", who, l);
-    q.w[l] = a->w[l];
-    q.b[l] = a->b[l];
-  }
-  q.T = a->T; q.H = a->H; q.W = a->W;
-  q.N = a->T * a->H * a->W;
-  q.ntiles = (q.N + FN_P - 1) / FN_P;
+  if (int rc = check_layers<4>(a, who, q)) return rc;
   q.scale = a->scale;
-  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
   q.enc_a = a->enc_a; q.enc_b = a->enc_b;
-  q.flows = nullptr; q.saved = nullptr; q.dflows = nullptr; q.dh = nullptr; q.wt = nullptr; q.part = nullptr;
-  q.wc = nullptr; q.ksteps = 0;
   return 0;
 }
 
+// f(KIND, PROG, SPATIAL) as integral constants for the run-time mode of a call, next to for_kind.  The spatial instantiations exist for
+// the FN_GW-wide progressive networks, the only ones check_head lets into that mode
+template <class F>
+static int for_mode(const sininn_flownet_args* a, bool spatial, F&& f) {
+  return for_kind(a->encoding, 1, [&](auto k) {
+    if constexpr (Enc<decltype(k)::value>::width(true) == FN_GW) {
+      if (spatial) return f(k, std::true_type{}, std::true_type{});
+    }
+    return a->progressive ? f(k, std::true_type{}, std::false_type{}) : f(k, std::false_type{}, std::false_type{});
+  });
+}
+
 // layer 1: gW1 = dh1^T (regenerated input), gb1, and their reduction into nn.Linear's layout
-template <int KIND, bool PROG, bool SPATIAL = false>
+template <int KIND, bool PROG, bool SPATIAL>
 static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hipStream_t st) {
   using E = Enc<KIND>;
-  constexpr size_t lds = SPATIAL ? FN_WG_LDS_PROG + FN_CN_LDS : PROG ? FN_WG_LDS_PROG : FN_WG_LDS;
+  constexpr size_t lds = wgrad_lds(PROG, SPATIAL);
   auto k = flownet_wgrad_kernel<KIND, true, PROG, SPATIAL>;
   if (raise_lds(k, lds, "flownet_wgrad")) return 1;
   const int nc = wgrad_chunks(q.ntiles, E::CHUNK_KF);  // not a function of k_active: the order of every sum stays the same
@@ -1122,42 +1120,30 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
 }
 
 // g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
-// spatial != nullptr: layer 1 under the per-point mask of that grid
-static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial = nullptr) {
+// spatial != nullptr: layer 1 under the per-point mask of that grid.  The entry point has called check_head
+static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial) {
   FlowNetDev q;
-  if (int rc = check_args(a, spatial ? "flownet_backward_spatial" : "flownet_backward", q, spatial)) return rc;
-  SININN_CHECK(a->dflows && a->saved && a->workspace, "flownet_backward: null dflows / saved / workspace");
-  SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_backward: saved holds %zu bytes, %zu needed", a->saved_bytes,
-               flownet_saved_bytes(q.N));
-  SININN_CHECK(a->workspace_bytes >= flownet_workspace_bytes(q.N), "flownet_backward: workspace holds %zu bytes, %zu needed",
-               a->workspace_bytes, flownet_workspace_bytes(q.N));
-  SININN_CHECK(aligned16(a->saved) && aligned16(a->workspace), "flownet_backward: saved / workspace must be 16-byte aligned");
-  for (int l = 0; l < 4; ++l) SININN_CHECK(a->gw[l] && a->gb[l], "flownet_backward: null gradient pointer %d", l);
+  if (int rc = fill_args(a, spatial ? "flownet_backward_spatial" : "flownet_backward", q, spatial)) return rc;
+  if (int rc = check_backward_buffers<4>(a, "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
   float* const wt = ws + 3 * lstride;
-  q.saved = a->saved;
-  q.dflows = a->dflows;
   q.dh = ws;
   q.wt = wt;
   q.part = wt + 2 * FN_HID * FN_HID;
 
   hipLaunchKernelGGL(flownet_transpose_kernel, dim3(FN_HID, 2), dim3(FN_NTHR), 0, st, a->w[1], a->w[2], wt);
   SININN_LAUNCH_CHECK("flownet_transpose");
-  if (raise_lds(flownet_bwd_chain_kernel, FN_LDS, "flownet_backward")) return 1;
+  if (raise_lds(flownet_bwd_chain_kernel, tile_lds(false), "flownet_backward")) return 1;
   const int cb = chain_blocks(q.ntiles);
-  hipLaunchKernelGGL(flownet_bwd_chain_kernel, dim3(cb), dim3(FN_NTHR), FN_LDS, st, q);
+  hipLaunchKernelGGL(flownet_bwd_chain_kernel, dim3(cb), dim3(FN_NTHR), tile_lds(false), st, q);
   SININN_LAUNCH_CHECK("flownet_bwd_chain");
   reduce_launch(q, cb, FN_OUT * FN_HID, FN_OUT, a->gw[3], a->gb[3], st);
   SININN_LAUNCH_CHECK("flownet_reduce");
   for (int l = 2; l >= 1; --l)                         // gW3 = dh3^T h2, gW2 = dh2^T h1
     if (int rc = hidden_wgrad_launch(q.ntiles, q.dh + l * lstride, q.saved + (l - 1) * lstride, q.part, a->gw[l], a->gb[l], st)) return rc;
-  if (int rc = for_kind(a->encoding, 1, [&](auto k) {
-        constexpr int KIND = decltype(k)::value;
-        if constexpr (Enc<KIND>::width(true) == FN_GW) {
-          if (spatial) return wgrad_l1_launch<KIND, true, true>(a, q, st);
-        }
-        return a->progressive ? wgrad_l1_launch<KIND, true>(a, q, st) : wgrad_l1_launch<KIND, false>(a, q, st);
+  if (int rc = for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
+        return wgrad_l1_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, st);
       }))
     return rc;
   if (g_enc_a) {
@@ -1166,7 +1152,7 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
     const int fopen = a->progressive ? (open_encoded(a) + 1) / 2 : FN_NF;   // a frequency is open if its sin or its cos is
     hipLaunchKernelGGL(flownet_encgrad_pack_kernel, dim3(Fourier::LIVE), dim3(FN_NTHR), 0, st, a->w[0], mask, enc_ws, spatial ? 1 : 0);
     SININN_LAUNCH_CHECK("flownet_encgrad_pack");
-    const size_t elds = spatial ? FN_LDS + FN_CN_LDS : FN_LDS;
+    const size_t elds = tile_lds(spatial != nullptr);
     auto ek = spatial ? flownet_encgrad_kernel<true> : flownet_encgrad_kernel<false>;
     if (raise_lds(ek, elds, "flownet_encgrad")) return 1;
     hipLaunchKernelGGL(ek, dim3(cb), dim3(FN_NTHR), elds, st, q, (const float*)enc_ws, epart, fopen);   // not a function of k_active
@@ -1178,10 +1164,12 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
   return 0;
 }
 
-template <int KIND, bool PROG>
+// PROG without SPATIAL: the pack step, W1 times the global mask into the workspace; SPATIAL: W1 in place, no pack kernel, no workspace
+template <int KIND, bool PROG, bool SPATIAL>
 static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipStream_t st) {
   using E = Enc<KIND>;
-  if constexpr (PROG) {
+  constexpr const char* who = SPATIAL ? "flownet_forward_spatial" : "flownet_forward";
+  if constexpr (PROG && !SPATIAL) {
     SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
                  "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", flownet_forward_workspace_bytes(a),
                  a->workspace ? a->workspace_bytes : (size_t)0);
@@ -1192,45 +1180,24 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
     SININN_LAUNCH_CHECK("flownet_pack");
     q.w[0] = w1p;
     q.wc = wc;
-    q.ksteps = (open_encoded(a) + 15) / 16;
   }
-  auto k = flownet_fwd_kernel<KIND, PROG>;
-  if (raise_lds(k, FN_LDS, "flownet_forward")) return 1;
+  if constexpr (PROG) q.ksteps = (open_encoded(a) + 15) / 16;
+  auto k = flownet_fwd_kernel<KIND, PROG, SPATIAL>;
+  if (raise_lds(k, tile_lds(SPATIAL), who)) return 1;
   const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS, st, q);
-  SININN_LAUNCH_CHECK("flownet_forward");
-  return 0;
-}
-
-// the spatial forward: W1 in place, no pack kernel, no workspace
-template <int KIND>
-static int forward_spatial_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipStream_t st) {
-  q.ksteps = (open_encoded(a) + 15) / 16;
-  auto k = flownet_fwd_kernel<KIND, true, true>;
-  if (raise_lds(k, FN_LDS + FN_CN_LDS, "flownet_forward_spatial")) return 1;
-  const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), FN_LDS + FN_CN_LDS, st, q);
-  SININN_LAUNCH_CHECK("flownet_forward_spatial");
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), tile_lds(SPATIAL), st, q);
+  SININN_LAUNCH_CHECK(who);
   return 0;
 }
 
 static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial) {
+  const char* who = spatial ? "flownet_forward_spatial" : "flownet_forward";
   FlowNetDev q;
-  if (int rc = check_args(a, spatial ? "flownet_forward_spatial" : "flownet_forward", q, spatial)) return rc;
-  SININN_CHECK(a->flows != nullptr, "flownet_forward: null flows");
-  q.flows = a->flows;
-  if (a->saved) {
-    SININN_CHECK(a->saved_bytes >= flownet_saved_bytes(q.N), "flownet_forward: saved holds %zu bytes, %zu needed", a->saved_bytes,
-                 flownet_saved_bytes(q.N));
-    SININN_CHECK(aligned16(a->saved), "flownet_forward: saved must be 16-byte aligned");
-    q.saved = a->saved;
-  }
-  return for_kind(a->encoding, 1, [&](auto k) {
-    constexpr int KIND = decltype(k)::value;
-    if constexpr (Enc<KIND>::width(true) == FN_GW) {
-      if (spatial) return forward_spatial_kind_launch<KIND>(a, q, st);
-    }
-    return a->progressive ? forward_kind_launch<KIND, true>(a, q, st) : forward_kind_launch<KIND, false>(a, q, st);
+  if (int rc = check_head(a, who, spatial)) return rc;
+  if (int rc = fill_args(a, who, q, spatial)) return rc;
+  if (int rc = check_forward_buffers(a, "flownet_forward", flownet_saved_bytes(q.N), q)) return rc;
+  return for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
+    return forward_kind_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, st);
   });
 }
 
@@ -1241,41 +1208,37 @@ int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* gr
   return forward_launch(a, st, &s);
 }
 
+static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial) {
+  if (int rc = check_head(a, spatial ? "flownet_backward_spatial" : "flownet_backward", spatial)) return rc;
+  return backward_launch(a, nullptr, nullptr, st, spatial);
+}
+
+int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_plain_launch(a, st, nullptr); }
+
 int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st) {
   const SpatialArgs s{grid, res, centre_scale};
-  return backward_launch(a, nullptr, nullptr, st, &s);
+  return backward_plain_launch(a, st, &s);
 }
 
 int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st) {
   const SpatialArgs s{grid, res, centre_scale};
-  FlowNetDev q{};
-  if (int rc = check_spatial(a, "flownet_sample_mask", s, q)) return rc;
+  if (int rc = check_head(a, "flownet_sample_mask", &s)) return rc;
   SININN_CHECK(out != nullptr, "flownet_sample_mask: null out");
-  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "flownet_sample_mask: grid %d x %d x %d (1 .. 2^22 points)",
-               a->T, a->H, a->W);
-  SININN_CHECK(a->times && a->ys && a->xs, "flownet_sample_mask: null axis pointer");
-  q.T = a->T; q.H = a->H; q.W = a->W;
-  q.N = a->T * a->H * a->W;
-  q.ntiles = (q.N + FN_P - 1) / FN_P;
-  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
+  FlowNetDev q{};
+  if (int rc = check_points(a, "flownet_sample_mask", q)) return rc;
+  q.sp = spatial_of(&s);
   const size_t units = ((size_t)q.N * FN_GROUPS + FN_NTHR - 1) / FN_NTHR;
   hipLaunchKernelGGL(flownet_sample_mask_kernel, dim3((unsigned)(units < 8192 ? units : 8192)), dim3(FN_NTHR), 0, st, q, out);
   SININN_LAUNCH_CHECK("flownet_sample_mask");
   return 0;
 }
 
-int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_launch(a, nullptr, nullptr, st); }
-
+// the head under this entry point's own name, so that a refusal of the spatial mode (PPE, a null grid, res) comes before the Fourier-only
+// refusal, which would hide it
 static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st,
                                    const SpatialArgs* spatial) {
   const char* who = spatial ? "flownet_backward_encgrad_spatial" : "flownet_backward_encgrad";
-  if (int rc = check_network(a, who)) return rc;
-  if (spatial) {
-    // checked again by backward_launch (check_args), which fills its own descriptor; here only so that a refusal of the mode (PPE, a
-    // null grid, res) is reported under this entry point's name and before the Fourier-only refusal below, which would hide it
-    FlowNetDev unused{};
-    if (int rc = check_spatial(a, who, *spatial, unused)) return rc;
-  }
+  if (int rc = check_head(a, who, spatial)) return rc;
   SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
                a->encoding);
   SININN_CHECK(g_enc_a != nullptr, "%s: null g_enc_a", who);

@@ -1,5 +1,10 @@
-// What the fused coordinate-network kernels share (flownet.hip, siren.hip): the 64-point tile, its hidden tile in LDS, the grid of
-// points, the LDS-tile GEMM on v_mfma_f32_16x16x4_f32 and the launch helpers.  Internal linkage: each file compiles its own copy.
+// What the fused coordinate-network kernels share (flownet.hip, siren.hip).  Internal linkage: each file compiles its own copy.
+//   device  the 64-point tile and its hidden tile in LDS; point_coord; the LDS-tile GEMM (gemm_lds) and one K group of four (mfma_k4) on
+//           v_mfma_f32_16x16x4_f32; store_acc with its epilogue (Plain, BiasRelu, Phase); copy_tile_out; stage_coord.
+//           The output layer, dout, the tile load, the column sums and the coordinate selection stay spelled out in each kernel: moved
+//           into a helper, each of them changed the instructions of a hot kernel.  The two transpose kernels stay where they are too
+//   host    check_points / check_layers / check_saved / check_forward_buffers / check_backward_buffers: the parts of a descriptor and
+//           their refusals that do not depend on the network; chain_blocks, raise_lds
 #pragma once
 #include "common.h"
 
@@ -62,6 +67,108 @@ __device__ __forceinline__ void copy_tile_out(const float* hs, float* dst, int t
     const int row = f >> 6, c4 = (f & 63) * 4;
     *reinterpret_cast<f32x4*>(dst + ((size_t)tile * FN_P + row) * FN_HID + c4) = *reinterpret_cast<const f32x4*>(hs + row * FN_HS + c4);
   }
+}
+
+// what store_acc does to an accumulator on its way to the LDS tile; col(c): the per-column operand, read once per column
+struct Plain {                                         // as it is.  Not flownet.hip's chain kernel: its PlainAddZero stores acc + 0.f (-0 -> +0)
+  __device__ __forceinline__ float col(int) const { return 0.f; }
+  __device__ __forceinline__ float operator()(float v, float) const { return v; }
+};
+struct BiasRelu {                                      // max(acc + bias, 0)
+  const float* bias;
+  __device__ __forceinline__ float col(int c) const { return bias[c]; }
+  __device__ __forceinline__ float operator()(float v, float bq) const { return fmaxf(v + bq, 0.f); }
+};
+struct Phase {                                         // omega (acc + bias), as torch rounds it: the linear layer's sum, then the product
+  const float* bias;
+  float omega;
+  __device__ __forceinline__ float col(int c) const { return bias[c]; }
+  __device__ __forceinline__ float operator()(float v, float bq) const { return __fmul_rn(omega, v + bq); }
+};
+
+// accumulators -> LDS tile through an epilogue
+template <class EPI>
+__device__ __forceinline__ void store_acc(float* hs, int cw, int li, int kq, const f32x4 (&acc)[4][4], const EPI epi) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const float bq = epi.col(cw + 16 * n + li);
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) hs[(16 * m + 4 * kq + r) * FN_HS + cw + 16 * n + li] = epi(acc[m][n][r], bq);
+  }
+}
+
+// one K group of four on the MFMA (the coordinates: lane group kq holds t, y, x, 0)
+__device__ __forceinline__ void mfma_k4(const float (&a)[4], const float (&b)[4], f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
+}
+
+// cs [64][4]: row tid = (t, y, x, 0) of point tid of the tile (tid < 64)
+template <class Q>
+__device__ __forceinline__ void stage_coord(const Q& q, float* cs, int tile, int tid) {
+  const Coord c = point_coord(q, tile * FN_P + tid);
+  *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
+}
+
+// ---- host: the parts of a descriptor that do not depend on the network.  A: the C struct of a call, Q: the kernels' descriptor ----
+// the grid of points: T H W in 1 .. 2^22 and the axis vectors (`more` / `what`: further pointers refused in the same sentence)
+template <class A, class Q>
+int check_points(const A* a, const char* who, Q& q, bool more = true, const char* what = "axis") {
+  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
+               who, a->T, a->H, a->W);
+  SININN_CHECK(a->times && a->ys && a->xs && more, "%s: null %s pointer", who, what);
+  q.T = a->T; q.H = a->H; q.W = a->W;
+  q.N = a->T * a->H * a->W;
+  q.ntiles = (q.N + FN_P - 1) / FN_P;
+  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
+  return 0;
+}
+
+template <int NL, class A, class Q>
+int check_layers(const A* a, const char* who, Q& q) {
+  for (int l = 0; l < NL; ++l) {
+    SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
+    SININN_CHECK(aligned16(a->w[l]), "%s: weight %d must be 16-byte aligned", who, l);
+    q.w[l] = a->w[l];
+    q.b[l] = a->b[l];
+  }
+  return 0;
+}
+
+template <class A>
+int check_saved(const A* a, const char* who, size_t need) {
+  SININN_CHECK(a->saved_bytes >= need, "%s: saved holds %zu bytes, %zu needed", who, a->saved_bytes, need);
+  return 0;
+}
+
+// a forward call: flows, and `saved` where the caller wants the training mode
+template <class A, class Q>
+int check_forward_buffers(const A* a, const char* who, size_t saved_need, Q& q) {
+  SININN_CHECK(a->flows != nullptr, "%s: null flows", who);
+  q.flows = a->flows;
+  if (a->saved) {
+    if (int rc = check_saved(a, who, saved_need)) return rc;
+    SININN_CHECK(aligned16(a->saved), "%s: saved must be 16-byte aligned", who);
+    q.saved = a->saved;
+  }
+  return 0;
+}
+
+// a backward call: dflows, saved, the workspace and NL pairs of gradient pointers
+template <int NL, class A, class Q>
+int check_backward_buffers(const A* a, const char* who, size_t saved_need, size_t workspace_need, Q& q) {
+  SININN_CHECK(a->dflows && a->saved && a->workspace, "%s: null dflows / saved / workspace", who);
+  if (int rc = check_saved(a, who, saved_need)) return rc;
+  SININN_CHECK(a->workspace_bytes >= workspace_need, "%s: workspace holds %zu bytes, %zu needed", who, a->workspace_bytes, workspace_need);
+  SININN_CHECK(aligned16(a->saved) && aligned16(a->workspace), "%s: saved / workspace must be 16-byte aligned", who);
+  for (int l = 0; l < NL; ++l) SININN_CHECK(a->gw[l] && a->gb[l], "%s: null gradient pointer %d", who, l);
+  q.saved = a->saved;
+  q.dflows = a->dflows;
+  return 0;
 }
 
 int chain_blocks(int ntiles) { return ntiles < FN_CHAIN_MAX_BLOCKS ? ntiles : FN_CHAIN_MAX_BLOCKS; }

@@ -18,6 +18,12 @@
 //           the dz_1 tile and the tile's coordinates.  gW_l = dz_l^T h_{l-1}, gb_l (l = 2 .. 4) are flownet.hip's split-over-points kernel and
 //           reduce; siren_reduce_kernel adds the chain kernel's per-block partial sums in block order.  No floating-point atomics: two
 //           calls are bitwise equal.
+// structure: what this file has of its own is the sine (sine_tile, the sincosf steps of the chain kernel), its descriptor and its partial
+//           sums.  From flownet_tile.h come the tile, gemm_lds, mfma_k4 for layer 1, store_acc with the Phase / Plain epilogues, copy_tile_out,
+//           stage_coord and the host checks of the point grid, the layers, `saved` and the
+//           buffers of a forward / backward call; from flownet.hip the hidden layers' weight gradient (hidden_wgrad_launch).  The output
+//           layer, dout, the tile load, the column sums and the transpose kernel match flownet.hip's text but stay spelled out: as helpers
+//           they changed the instructions, or the placement, of these kernels.
 // Rows of the last tile beyond N are computed on a clamped point in the forward pass and carry dout = 0 in the backward pass, so every
 // saved / workspace row is written before it is read and contributes exact zeros to every sum.
 #include "flownet_tile.h"
@@ -62,24 +68,7 @@ __device__ __forceinline__ void layer1(const SirenDev& q, int tile, int cw, int 
 #pragma unroll
   for (int n = 0; n < 4; ++n) b[n] = kq < SR_IN ? q.w[0][(cw + 16 * n + li) * SR_IN + kq] : 0.f;
   zero_acc(acc);
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[n], acc[m][n], 0, 0, 0);
-}
-
-// accumulators -> LDS tile; PHASE: omega (acc + bias), as torch rounds it: the linear layer's sum, then the product
-template <bool PHASE>
-__device__ __forceinline__ void store_tile(float* hs, const float* bias, float omega, int cw, int li, int kq, const f32x4 (&acc)[4][4]) {
-#pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const float bq = PHASE ? bias[cw + 16 * n + li] : 0.f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        hs[(16 * m + 4 * kq + r) * FN_HS + cw + 16 * n + li] = PHASE ? __fmul_rn(omega, acc[m][n][r] + bq) : acc[m][n][r];
-  }
+  mfma_k4(a, b, acc);
 }
 
 // the LDS tile holds phases: (dst != nullptr) copy them to rows [64 tile, 64 tile + 64) of a [Npad][256] array; their sines in place
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_fwd_kernel(SirenDev q) {
     f32x4 acc[4][4];
     layer1(q, tile, cw, li, kq, acc);
     __syncthreads();                       // the previous tile's layer 5 has read hs
-    store_tile<true>(hs, q.b[0], q.omega, cw, li, kq, acc);
+    store_acc(hs, cw, li, kq, acc, Phase{q.b[0], q.omega});
     __syncthreads();
     sine_tile(hs, q.saved, tile, tid);
     __syncthreads();
@@ -120,7 +109,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_fwd_kernel(SirenDev q) {
       zero_acc(acc);
       gemm_lds(hs, q.w[l], cw, li, kq, acc);
       __syncthreads();                     // every wave has read the whole tile
-      store_tile<true>(hs, q.b[l], q.omega, cw, li, kq, acc);
+      store_acc(hs, cw, li, kq, acc, Phase{q.b[l], q.omega});
       __syncthreads();
       sine_tile(hs, q.saved ? q.saved + l * lstride : nullptr, tile, tid);
       __syncthreads();
@@ -174,7 +163,6 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(SirenDev q)
 
   for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
     __syncthreads();                                   // the previous tile is done with hs / dos / cs
-    // u4 tile -> LDS, dout = dflows * scale (0 beyond N), the coordinates
 #pragma unroll 4
     for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
       const int f = tid + FN_NTHR * u;
@@ -192,10 +180,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(SirenDev q)
       }
       dos[pl * FN_OUT + c] = v;
     }
-    if (tid < FN_P) {
-      const Coord c = point_coord(q, tile * FN_P + tid);
-      *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
-    }
+    if (tid < FN_P) stage_coord(q, cs, tile, tid);
     __syncthreads();
     // gW5 += dout^T sin(u4);  dz4 = omega (dout W5) cos(u4) in place: thread = hidden column tid
 #pragma unroll 2
@@ -225,7 +210,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(SirenDev q)
       zero_acc(acc);
       gemm_lds(hs, q.wt + (size_t)l * FN_HID * FN_HID, cw, li, kq, acc);
       __syncthreads();
-      store_tile<false>(hs, nullptr, 1.f, cw, li, kq, acc);
+      store_acc(hs, cw, li, kq, acc, Plain{});
       __syncthreads();
 #pragma unroll 2
       for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
@@ -321,36 +306,18 @@ static int check_args(const sininn_siren_args* a, const char* who, SirenDev& q) 
   SININN_CHECK(a->struct_bytes == sizeof(sininn_siren_args), "%s: struct_bytes is %zu, this library was built with %zu", who, a->struct_bytes,
                sizeof(sininn_siren_args));
   if (!siren_supported(a, who)) return 1;
-  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
-               who, a->T, a->H, a->W);
-  SININN_CHECK(a->times && a->ys && a->xs, "%s: null axis pointer", who);
-  for (int l = 0; l <= SR_SINES; ++l) {
-    SININN_CHECK(a->w[l] && a->b[l], "%s: null weight / bias %d", who, l);
-    SININN_CHECK(aligned16(a->w[l]), "%s: weight %d must be 16-byte aligned", who, l);
-    q.w[l] = a->w[l];
-    q.b[l] = a->b[l];
-  }
-  q.T = a->T; q.H = a->H; q.W = a->W;
-  q.N = a->T * a->H * a->W;
-  q.ntiles = (q.N + FN_P - 1) / FN_P;
+  q = SirenDev{};
+  if (int rc = check_points(a, who, q)) return rc;
+  if (int rc = check_layers<SR_SINES + 1>(a, who, q)) return rc;
   q.scale = a->scale;
   q.omega = a->omega;
-  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
-  q.flows = nullptr; q.saved = nullptr; q.dflows = nullptr; q.dz = nullptr; q.hin = nullptr; q.wt = nullptr; q.part = nullptr;
   return 0;
 }
 
 int siren_forward_launch(const sininn_siren_args* a, hipStream_t st) {
   SirenDev q;
   if (int rc = check_args(a, "siren_forward", q)) return rc;
-  SININN_CHECK(a->flows != nullptr, "siren_forward: null flows");
-  q.flows = a->flows;
-  if (a->saved) {
-    SININN_CHECK(a->saved_bytes >= siren_saved_bytes(q.N), "siren_forward: saved holds %zu bytes, %zu needed", a->saved_bytes,
-                 siren_saved_bytes(q.N));
-    SININN_CHECK(aligned16(a->saved), "siren_forward: saved must be 16-byte aligned");
-    q.saved = a->saved;
-  }
+  if (int rc = check_forward_buffers(a, "siren_forward", siren_saved_bytes(q.N), q)) return rc;
   if (raise_lds(siren_fwd_kernel, SR_LDS, "siren_forward")) return 1;
   hipLaunchKernelGGL(siren_fwd_kernel, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), SR_LDS, st, q);   // two resident blocks per CU
   SININN_LAUNCH_CHECK("siren_forward");
@@ -360,18 +327,10 @@ int siren_forward_launch(const sininn_siren_args* a, hipStream_t st) {
 int siren_backward_launch(const sininn_siren_args* a, hipStream_t st) {
   SirenDev q;
   if (int rc = check_args(a, "siren_backward", q)) return rc;
-  SININN_CHECK(a->dflows && a->saved && a->workspace, "siren_backward: null dflows / saved / workspace");
-  SININN_CHECK(a->saved_bytes >= siren_saved_bytes(q.N), "siren_backward: saved holds %zu bytes, %zu needed", a->saved_bytes,
-               siren_saved_bytes(q.N));
-  SININN_CHECK(a->workspace_bytes >= siren_workspace_bytes(q.N), "siren_backward: workspace holds %zu bytes, %zu needed", a->workspace_bytes,
-               siren_workspace_bytes(q.N));
-  SININN_CHECK(aligned16(a->saved) && aligned16(a->workspace), "siren_backward: saved / workspace must be 16-byte aligned");
-  for (int l = 0; l <= SR_SINES; ++l) SININN_CHECK(a->gw[l] && a->gb[l], "siren_backward: null gradient pointer %d", l);
+  if (int rc = check_backward_buffers<SR_SINES + 1>(a, "siren_backward", siren_saved_bytes(q.N), siren_workspace_bytes(q.N), q)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
   float* const wt = ws + 2 * (SR_SINES - 1) * lstride;
-  q.saved = a->saved;
-  q.dflows = a->dflows;
   q.dz = ws;
   q.hin = ws + (SR_SINES - 1) * lstride;
   q.wt = wt;

@@ -59,6 +59,14 @@ per-point mask never exists in memory either: the kernels sample the grid while 
 `flow_fields` takes that controller (`k_active` = its `next_block`), or a raw grid as a 2-D `override_mask`; `flownet_sample_mask`
 returns the interpolated mask itself (the reference's `get_mask=` keyword).  All 515-wide progressive networks; `PPE` is refused.
 
+One call path serves the three modes (global mask or none, per-point mask, SIREN).  `Mask` is the mask of a call: the device tensor,
+`k_active` and, for a grid, `res` and `centre_scale`; `.spatial` is the one way to ask which it is, and `_resolve_mask`, the controllers'
+`device_mask` / `device_grid`, `_FlowFields` and `flow_fields` pass it around.  A descriptor is built by `_args` / `_siren_args`, which share
+the grid of points and the layers (`_points_and_layers`); `_forward` allocates `flows` / `saved` and calls, `_backward` checks `dflows`, allocates
+the workspace and the gradients, calls, and carries the optional frequency gradient.  The six public forward / backward functions name their
+descriptor builder, their size queries and their library call and nothing else; `_FlowFields` is the one autograd function, `_mode` picks
+the pair of functions and their keyword arguments for it (`_SirenFields.apply` is its SIREN call under the earlier name).
+
 Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
 `--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
 closed (video-interpolation/main.py still refuses it).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
@@ -67,6 +75,7 @@ closed (video-interpolation/main.py still refuses it).  Sintel / .flo IO and the
 """
 import ctypes as C
 import math
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -417,11 +426,45 @@ class SirenModel(nn.Module):
 
 
 siren_model_dict = {'siren': SirenModel}                          # beside all_model_dict: the command line does not open it yet
+flow_model_dict = {**all_model_dict, **siren_model_dict}          # every network flow_fields evaluates: what the tools offer
 
 
 def _on_gpu(t, what='tensor'):
     if not t.is_cuda:
         raise NotImplementedError(f'sin-inn_amd flownet runs on the GPU only (got a CPU {what})')
+
+
+IDENTITY_SCALE = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0)
+
+
+class Mask(NamedTuple):
+    """The mask of one call.  `tensor`: None (a plain network), the global mask (enc_dim,) or the grid (res^3, enc_dim), on the device;
+    `k_active`: the number of leading features after which it is all zero (None: nothing is skipped); a grid comes with its `res` and
+    `centre_scale`, six host floats, centre (t, y, x) then scale (t, y, x)."""
+    tensor: Optional[torch.Tensor] = None
+    k_active: Optional[int] = None
+    res: Optional[int] = None
+    centre_scale: Optional[tuple] = None
+
+    @property
+    def spatial(self):
+        return self.res is not None
+
+
+# ---- the descriptors: what is particular to a kind of network, then the part they share ----
+def _points_and_layers(a, lins, times, ys, xs, scale):
+    """the grid of points (axes on the GPU, T H W, scale, pointers) and the nn.Linear layers of a descriptor"""
+    for t in (times, ys, xs):
+        _on_gpu(t)
+    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+    a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
+    a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
+    a._axes, a._device = (times, ys, xs), times.device           # the contiguous copies live as long as the descriptor
+    for l, lin in enumerate(lins):
+        _on_gpu(lin.weight, 'parameter')
+        assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
+        a.w[l], a.b[l] = ptr(lin.weight), ptr(lin.bias)
+    return a
 
 
 def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spatial=False):
@@ -447,10 +490,7 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spati
         a.k_active = a.enc_dim if k_active is None else int(k_active)
     elif mask is not None:
         raise ValueError('a mask needs a progressive network')
-    for t in (times, ys, xs):
-        _on_gpu(t)
-    a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
-    a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
+    _points_and_layers(a, lins, times, ys, xs, scale)
     if enc_a is None:
         ea, eb = net.encode.kernel_buffers()
     else:                                                # learnable frequencies: F_eff of this call
@@ -459,148 +499,7 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spati
         ea, eb = enc_a, None
     a.enc_a, a.enc_b = ptr(ea), ptr(eb)
     a._keep = (ea, eb)                                   # kernel_buffers() of a learnable encoding is a temporary
-    for l, lin in enumerate(lins):
-        assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
-        a.w[l], a.b[l] = ptr(lin.weight), ptr(lin.bias)
     return a
-
-
-def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
-    """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
-    (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
-    caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats (PPE: 27) and `k_active` a
-    number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
-    (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
-    n = a.T * a.H * a.W
-    flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
-    if train:
-        nbytes = _lib.lib().sininn_flownet_saved_bytes(n)
-        if saved is None:
-            saved = torch.empty(3, nbytes // (3 * 256 * 4), 256, device=times.device, dtype=torch.float32)
-        assert saved.is_contiguous() and saved.dtype == torch.float32
-        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
-    else:
-        saved = None
-    a.flows = ptr(flows)
-    if a.progressive:                                    # the packed, masked copy of W1
-        pack = torch.empty(_lib.lib().sininn_flownet_forward_workspace_bytes(C.byref(a)) // 4, device=times.device, dtype=torch.float32)
-        a.workspace, a.workspace_bytes = ptr(pack), pack.numel() * 4
-    check(_lib.lib().sininn_flownet_forward(C.byref(a), _stream()))
-    return flows, saved
-
-
-def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
-                     enc_workspace=None, g_enc_a=None):
-    """[gW1, gb1, .., gW4, gb4] for an upstream gradient dflows (t, 4, h, w); `workspace`: optional fp32 tensor of at least
-    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise); `mask` / `k_active` / `enc_a`: those of the forward call.
-    `enc_grad=True` (Fourier encodings) returns ([gW1, .., gb4], gF) with gF (3, 256) the gradient with respect to the frequency
-    matrix the kernels read; `enc_workspace`: optional fp32 tensor of sininn_flownet_encgrad_workspace_bytes bytes for it,
-    `g_enc_a`: optional (3, 256) fp32 tensor that receives gF."""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
-    n = a.T * a.H * a.W
-    _on_gpu(dflows)
-    dflows = dflows.contiguous()
-    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
-    nbytes = _lib.lib().sininn_flownet_workspace_bytes(n)
-    if workspace is None:
-        workspace = torch.empty(nbytes // 4, device=times.device, dtype=torch.float32)
-    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
-    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
-    a.dflows = ptr(dflows)
-    grads = []
-    for l, lin in enumerate(net.linears()):
-        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
-        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
-        grads += [gw, gb]
-    if not enc_grad:
-        check(_lib.lib().sininn_flownet_backward(C.byref(a), _stream()))
-        return grads
-    if enc_workspace is None:
-        enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=times.device, dtype=torch.float32)
-    g_enc = torch.empty(3, 256, device=times.device, dtype=torch.float32) if g_enc_a is None else g_enc_a
-    assert g_enc.is_cuda and g_enc.is_contiguous() and g_enc.dtype == torch.float32 and tuple(g_enc.shape) == (3, 256)
-    check(_lib.lib().sininn_flownet_backward_encgrad(C.byref(a), ptr(g_enc), ptr(enc_workspace), enc_workspace.numel() * 4, _stream()))
-    return grads, g_enc
-
-
-IDENTITY_SCALE = (0.0, 0.0, 0.0, 1.0, 1.0, 1.0)
-
-
-def _spatial(a, grid, res, centre_scale):
-    """(device grid, res, the six host floats) as the spatial entry points take them, checked against the descriptor"""
-    _on_gpu(grid, 'mask grid')
-    res = int(res)
-    assert grid.dtype == torch.float32 and grid.is_contiguous() and tuple(grid.shape) == (res ** 3, a.enc_dim), \
-        f'a mask grid of shape (res^3, {a.enc_dim}), contiguous fp32'
-    cs = (C.c_float * 6)(*[float(v) for v in (IDENTITY_SCALE if centre_scale is None else centre_scale)])
-    return ptr(grid), res, C.cast(cs, C.c_void_p), cs
-
-
-def flownet_forward_spatial(net, times, ys, xs, scale, train, grid, res, centre_scale=None, k_active=None, saved=None, enc_a=None):
-    """flownet_forward under a per-point mask: `grid` (res^3, 515) on the device, the controller's blurred mask; `centre_scale`: six
-    host floats, centre (t, y, x) then scale (t, y, x), None: identity; `k_active`: every grid column from there on is zero (None:
-    515).  No workspace: W1 is read in place."""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
-    g, res, cs, keep = _spatial(a, grid, res, centre_scale)
-    n = a.T * a.H * a.W
-    flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
-    if train:
-        nbytes = _lib.lib().sininn_flownet_saved_bytes(n)
-        if saved is None:
-            saved = torch.empty(3, nbytes // (3 * 256 * 4), 256, device=times.device, dtype=torch.float32)
-        assert saved.is_contiguous() and saved.dtype == torch.float32
-        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
-    else:
-        saved = None
-    a.flows = ptr(flows)
-    check(_lib.lib().sininn_flownet_forward_spatial(C.byref(a), g, res, cs, _stream()))
-    return flows, saved
-
-
-def flownet_backward_spatial(net, times, ys, xs, scale, dflows, saved, grid, res, centre_scale=None, k_active=None, workspace=None,
-                             enc_a=None, enc_grad=False, enc_workspace=None, g_enc_a=None):
-    """flownet_backward under the per-point mask of the forward call; the arguments of flownet_backward and flownet_forward_spatial"""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
-    g, res, cs, keep = _spatial(a, grid, res, centre_scale)
-    n = a.T * a.H * a.W
-    _on_gpu(dflows)
-    dflows = dflows.contiguous()
-    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
-    if workspace is None:
-        workspace = torch.empty(_lib.lib().sininn_flownet_workspace_bytes(n) // 4, device=times.device, dtype=torch.float32)
-    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
-    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
-    a.dflows = ptr(dflows)
-    grads = []
-    for l, lin in enumerate(net.linears()):
-        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
-        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
-        grads += [gw, gb]
-    if not enc_grad:
-        check(_lib.lib().sininn_flownet_backward_spatial(C.byref(a), g, res, cs, _stream()))
-        return grads
-    if enc_workspace is None:
-        enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=times.device, dtype=torch.float32)
-    g_enc = torch.empty(3, 256, device=times.device, dtype=torch.float32) if g_enc_a is None else g_enc_a
-    assert g_enc.is_cuda and g_enc.is_contiguous() and g_enc.dtype == torch.float32 and tuple(g_enc.shape) == (3, 256)
-    check(_lib.lib().sininn_flownet_backward_encgrad_spatial(C.byref(a), g, res, cs, ptr(g_enc), ptr(enc_workspace),
-                                                             enc_workspace.numel() * 4, _stream()))
-    return grads, g_enc
-
-
-def flownet_sample_mask(net, times, ys, xs, grid, res, centre_scale=None):
-    """the interpolated mask (N, 515) of the grid of points, bitwise what the spatial kernels multiply layer 1's input by"""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _args(net, times, ys, xs, 1.0, spatial=True)
-    g, res, cs, keep = _spatial(a, grid, res, centre_scale)
-    out = torch.empty(a.T * a.H * a.W, a.enc_dim, device=times.device, dtype=torch.float32)
-    check(_lib.lib().sininn_flownet_sample_mask(C.byref(a), g, res, cs, ptr(out), _stream()))
-    return out
 
 
 def _siren_args(net, times, ys, xs, scale, omega=None):
@@ -612,49 +511,43 @@ def _siren_args(net, times, ys, xs, scale, omega=None):
         raise ValueError(_lib.lib().sininn_last_error().decode())
     if len(lins) != 5:
         raise ValueError(f'siren kernels take 5 linear layers; got {len(lins)}')
-    for t in (times, ys, xs):
-        _on_gpu(t)
-    a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
-    a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
-    for l, lin in enumerate(lins):
-        _on_gpu(lin.weight, 'parameter')
-        assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
-        a.w[l], a.b[l] = ptr(lin.weight), ptr(lin.bias)
-    return a
+    return _points_and_layers(a, lins, times, ys, xs, scale)
 
 
-def siren_forward(net, times, ys, xs, scale, train, saved=None, omega=None):
-    """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale for a SirenModel, and (train) what the backward call needs as one
-    opaque fp32 tensor of sininn_siren_saved_bytes(N) bytes (`saved`: optional caller-provided buffer of that size).  `omega`:
-    instead of the network's own omega_0 (None)."""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _siren_args(net, times, ys, xs, scale, omega)
-    n = a.T * a.H * a.W
-    flows = torch.empty(a.T, 4, a.H, a.W, device=times.device, dtype=torch.float32)
+def _spatial(a, grid, res, centre_scale):
+    """(device grid, res, the six host floats) as the spatial entry points take them, checked against the descriptor"""
+    _on_gpu(grid, 'mask grid')
+    res = int(res)
+    assert grid.dtype == torch.float32 and grid.is_contiguous() and tuple(grid.shape) == (res ** 3, a.enc_dim), \
+        f'a mask grid of shape (res^3, {a.enc_dim}), contiguous fp32'
+    a._cs = (C.c_float * 6)(*[float(v) for v in (IDENTITY_SCALE if centre_scale is None else centre_scale)])
+    return ptr(grid), res, C.cast(a._cs, C.c_void_p)
+
+
+# ---- the two halves every call shares: a = a finished descriptor, `call` its library entry point, `extra` what that takes beside it ----
+def _forward(a, train, saved, saved_shape, call, *extra):
+    """allocate flows and (train) `saved` of `saved_shape()`, call, return (flows, saved)"""
+    flows = torch.empty(a.T, 4, a.H, a.W, device=a._device, dtype=torch.float32)
+    a.flows = ptr(flows)
     if train:
-        nbytes = _lib.lib().sininn_siren_saved_bytes(n)
         if saved is None:
-            saved = torch.empty(nbytes // 4, device=times.device, dtype=torch.float32)
+            saved = torch.empty(saved_shape(), device=a._device, dtype=torch.float32)
         assert saved.is_cuda and saved.is_contiguous() and saved.dtype == torch.float32
         a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
     else:
         saved = None
-    a.flows = ptr(flows)
-    check(_lib.lib().sininn_siren_forward(C.byref(a), _stream()))
+    check(call(C.byref(a), *extra, _stream()))
     return flows, saved
 
 
-def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, omega=None):
-    """[gW1, gb1, .., gW5, gb5] for an upstream gradient dflows (t, 4, h, w); `saved`: that of the forward call on the same weights
-    and omega; `workspace`: optional fp32 tensor of at least sininn_siren_workspace_bytes(N) bytes (allocated here otherwise)."""
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a = _siren_args(net, times, ys, xs, scale, omega)
-    n = a.T * a.H * a.W
+def _backward(a, net, dflows, saved, workspace, workspace_bytes, call, *extra, enc_call=None, enc_workspace=None, g_enc_a=None):
+    """check dflows, allocate the workspace (`workspace_bytes(N)`) and the gradients, call; `enc_call`: the entry point that also
+    returns the frequency gradient, ([gW1, ..], gF) then"""
     _on_gpu(dflows)
     dflows = dflows.contiguous()
     assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
     if workspace is None:
-        workspace = torch.empty(_lib.lib().sininn_siren_workspace_bytes(n) // 4, device=times.device, dtype=torch.float32)
+        workspace = torch.empty(workspace_bytes(a.T * a.H * a.W) // 4, device=a._device, dtype=torch.float32)
     a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
     a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
     a.dflows = ptr(dflows)
@@ -663,59 +556,131 @@ def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, ome
         gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
         a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
         grads += [gw, gb]
-    check(_lib.lib().sininn_siren_backward(C.byref(a), _stream()))
-    return grads
+    if enc_call is None:
+        check(call(C.byref(a), *extra, _stream()))
+        return grads
+    if enc_workspace is None:
+        enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
+    g_enc = torch.empty(3, 256, device=a._device, dtype=torch.float32) if g_enc_a is None else g_enc_a
+    assert g_enc.is_cuda and g_enc.is_contiguous() and g_enc.dtype == torch.float32 and tuple(g_enc.shape) == (3, 256)
+    check(enc_call(C.byref(a), *extra, ptr(g_enc), ptr(enc_workspace), enc_workspace.numel() * 4, _stream()))
+    return grads, g_enc
 
 
-class _SirenFields(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, times, ys, xs, scale, train, *params):
-        flows, saved = siren_forward(net, times, ys, xs, scale, train)
-        ctx.net, ctx.axes, ctx.scale, ctx.saved = net, (times, ys, xs), scale, saved
-        return flows
+def _flownet_saved_shape(a):
+    return lambda: (3, _lib.lib().sininn_flownet_saved_bytes(a.T * a.H * a.W) // (3 * 256 * 4), 256)
 
-    @staticmethod
-    def backward(ctx, dflows):
-        if ctx.saved is None:
-            raise RuntimeError('flow_fields: backward through an inference-mode forward')
-        grads = siren_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved)
-        ctx.saved = None
-        return (None,) * 6 + tuple(grads)
+
+def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
+    """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
+    (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
+    caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats (PPE: 27) and `k_active` a
+    number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
+    (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
+    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
+    if a.progressive:                                    # the packed, masked copy of W1
+        a._pack = torch.empty(_lib.lib().sininn_flownet_forward_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
+        a.workspace, a.workspace_bytes = ptr(a._pack), a._pack.numel() * 4
+    return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward)
+
+
+def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
+                     enc_workspace=None, g_enc_a=None):
+    """[gW1, gb1, .., gW4, gb4] for an upstream gradient dflows (t, 4, h, w); `workspace`: optional fp32 tensor of at least
+    sininn_flownet_workspace_bytes(N) bytes (allocated here otherwise); `mask` / `k_active` / `enc_a`: those of the forward call.
+    `enc_grad=True` (Fourier encodings) returns ([gW1, .., gb4], gF) with gF (3, 256) the gradient with respect to the frequency
+    matrix the kernels read; `enc_workspace`: optional fp32 tensor of sininn_flownet_encgrad_workspace_bytes bytes for it,
+    `g_enc_a`: optional (3, 256) fp32 tensor that receives gF."""
+    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
+    return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward,
+                     enc_call=_lib.lib().sininn_flownet_backward_encgrad if enc_grad else None, enc_workspace=enc_workspace, g_enc_a=g_enc_a)
+
+
+def flownet_forward_spatial(net, times, ys, xs, scale, train, grid, res, centre_scale=None, k_active=None, saved=None, enc_a=None):
+    """flownet_forward under a per-point mask: `grid` (res^3, 515) on the device, the controller's blurred mask; `centre_scale`: six
+    host floats, centre (t, y, x) then scale (t, y, x), None: identity; `k_active`: every grid column from there on is zero (None:
+    515).  No workspace: W1 is read in place."""
+    a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
+    return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_spatial, *_spatial(a, grid, res, centre_scale))
+
+
+def flownet_backward_spatial(net, times, ys, xs, scale, dflows, saved, grid, res, centre_scale=None, k_active=None, workspace=None,
+                             enc_a=None, enc_grad=False, enc_workspace=None, g_enc_a=None):
+    """flownet_backward under the per-point mask of the forward call; the arguments of flownet_backward and flownet_forward_spatial"""
+    a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
+    return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward_spatial,
+                     *_spatial(a, grid, res, centre_scale), enc_call=_lib.lib().sininn_flownet_backward_encgrad_spatial if enc_grad else None,
+                     enc_workspace=enc_workspace, g_enc_a=g_enc_a)
+
+
+def flownet_sample_mask(net, times, ys, xs, grid, res, centre_scale=None):
+    """the interpolated mask (N, 515) of the grid of points, bitwise what the spatial kernels multiply layer 1's input by"""
+    a = _args(net, times, ys, xs, 1.0, spatial=True)
+    extra = _spatial(a, grid, res, centre_scale)
+    out = torch.empty(a.T * a.H * a.W, a.enc_dim, device=a._device, dtype=torch.float32)
+    check(_lib.lib().sininn_flownet_sample_mask(C.byref(a), *extra, ptr(out), _stream()))
+    return out
+
+
+def siren_forward(net, times, ys, xs, scale, train, saved=None, omega=None):
+    """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale for a SirenModel, and (train) what the backward call needs as one
+    opaque fp32 tensor of sininn_siren_saved_bytes(N) bytes (`saved`: optional caller-provided buffer of that size).  `omega`:
+    instead of the network's own omega_0 (None)."""
+    a = _siren_args(net, times, ys, xs, scale, omega)
+    return _forward(a, train, saved, lambda: _lib.lib().sininn_siren_saved_bytes(a.T * a.H * a.W) // 4, _lib.lib().sininn_siren_forward)
+
+
+def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, omega=None):
+    """[gW1, gb1, .., gW5, gb5] for an upstream gradient dflows (t, 4, h, w); `saved`: that of the forward call on the same weights
+    and omega; `workspace`: optional fp32 tensor of at least sininn_siren_workspace_bytes(N) bytes (allocated here otherwise)."""
+    a = _siren_args(net, times, ys, xs, scale, omega)
+    return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_siren_workspace_bytes, _lib.lib().sininn_siren_backward)
+
+
+def _mode(net, mask, enc_a):
+    """(forward, backward, the keyword arguments both take) of a call: a SirenModel, a per-point mask, or a global mask / none"""
+    if isinstance(net, SirenModel):
+        return siren_forward, siren_backward, {}
+    if mask.spatial:
+        return flownet_forward_spatial, flownet_backward_spatial, dict(grid=mask.tensor, res=mask.res, centre_scale=mask.centre_scale,
+                                                                       k_active=mask.k_active, enc_a=enc_a)
+    return flownet_forward, flownet_backward, dict(mask=mask.tensor, k_active=mask.k_active, enc_a=enc_a)
 
 
 class _FlowFields(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, times, ys, xs, scale, train, mask, enc_a, *params):
-        mask, k_active, *spatial = mask                  # spatial: (res, centre_scale) after a grid (res^3, enc_dim)
         if enc_a is not None:
             enc_a = enc_a.detach().contiguous()
-        if spatial:
-            flows, saved = flownet_forward_spatial(net, times, ys, xs, scale, train, mask, *spatial, k_active=k_active, enc_a=enc_a)
-            ctx.grid_version = mask._version             # the controller updates its grid in place
-        else:
-            flows, saved = flownet_forward(net, times, ys, xs, scale, train, mask=mask, k_active=k_active, enc_a=enc_a)
-        ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask, ctx.spatial = net, (times, ys, xs), scale, saved, (mask, k_active), spatial
-        ctx.enc_a, ctx.enc_grad = enc_a, enc_a is not None and ctx.needs_input_grad[7]
+        forward, ctx.backward_fn, ctx.kw = _mode(net, mask, enc_a)
+        flows, saved = forward(net, times, ys, xs, scale, train, **ctx.kw)
+        ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask = net, (times, ys, xs), scale, saved, mask
+        if mask.spatial:
+            ctx.grid_version = mask.tensor._version      # the controller updates its grid in place
+        if enc_a is not None and ctx.needs_input_grad[7]:
+            ctx.kw['enc_grad'] = True
         return flows
 
     @staticmethod
     def backward(ctx, dflows):
         if ctx.saved is None:
             raise RuntimeError('flow_fields: backward through an inference-mode forward')
-        if ctx.spatial:
-            if ctx.mask[0]._version != ctx.grid_version:
-                raise RuntimeError('flow_fields: the mask grid changed between the forward and the backward pass (run backward before '
-                                   'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
-            grads = flownet_backward_spatial(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, ctx.mask[0], *ctx.spatial,
-                                             k_active=ctx.mask[1], enc_a=ctx.enc_a, enc_grad=ctx.enc_grad)
-        else:
-            grads = flownet_backward(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, mask=ctx.mask[0], k_active=ctx.mask[1],
-                                     enc_a=ctx.enc_a, enc_grad=ctx.enc_grad)
-        g_enc = None
-        if ctx.enc_grad:
+        if ctx.mask.spatial and ctx.mask.tensor._version != ctx.grid_version:
+            raise RuntimeError('flow_fields: the mask grid changed between the forward and the backward pass (run backward before '
+                               'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
+        grads, g_enc = ctx.backward_fn(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, **ctx.kw), None
+        if ctx.kw.get('enc_grad'):
             grads, g_enc = grads
         ctx.saved = None
         return (None,) * 7 + (g_enc,) + tuple(grads)
+
+
+class _SirenFields:
+    """the call `_FlowFields` had for a SirenModel before the two were one function: no mask, no frequency matrix"""
+
+    @staticmethod
+    def apply(net, times, ys, xs, scale, train, *params):
+        return _FlowFields.apply(net, times, ys, xs, scale, train, Mask(), None, *params)
 
 
 def grid_axes(net, times, h, w):
@@ -734,9 +699,8 @@ def last_open(mask):
 
 
 def _resolve_mask(net, override_mask, device):
-    """(model, (device mask, k_active)) for a plain model, a bare progressive model or a controller (a module that wraps a
-    progressive model as `.model` and keeps a mask); (model, (device grid, k_active, res, centre_scale)) under a spatial controller
-    or a raw 2-D grid"""
+    """(model, Mask) for a plain model (no mask), a bare progressive model (all ones) or a controller (a module that wraps a
+    progressive model as `.model` and keeps a mask); a grid under a spatial controller or a raw 2-D `override_mask`"""
     from .progressive import ProgressiveEncoderController, StashedSpatialController
     controller = net if isinstance(net, ProgressiveEncoderController) else None
     spatial = controller if isinstance(controller, StashedSpatialController) else None
@@ -744,7 +708,7 @@ def _resolve_mask(net, override_mask, device):
     if not model.is_progressive:
         if override_mask is not None:
             raise ValueError('override_mask needs a progressive network')
-        return model, (None, None)
+        return model, Mask()
     if override_mask is not None and override_mask.dim() == 2:
         # a raw grid (res^3, enc_dim) on the device: not inspected, nothing skipped; the cell map is the spatial controller's, else identity
         g = override_mask.detach()
@@ -753,19 +717,19 @@ def _resolve_mask(net, override_mask, device):
         if res ** 3 != g.shape[0] or g.shape[1] != model.encoding_dim:
             raise ValueError(f'a mask grid has shape (res^3, {model.encoding_dim}); got {tuple(g.shape)}')
         cs = spatial.centre_scale_host() if spatial is not None else IDENTITY_SCALE
-        return model, (g.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim, res, cs)
+        return model, Mask(g.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim, res, cs)
     if override_mask is not None:
         m = override_mask.detach()
         assert m.dim() == 1 and m.numel() == model.encoding_dim, 'a global mask of encoding_dim values, or a grid (res^3, encoding_dim)'
         if m.is_cuda:                                    # not inspected on the host: no synchronisation, nothing skipped
-            return model, (m.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim)
+            return model, Mask(m.to(device=device, dtype=torch.float32).contiguous(), model.encoding_dim)
         m = m.to(torch.float32).contiguous()
-        return model, (m.to(device), last_open(m))
+        return model, Mask(m.to(device), last_open(m))
     if spatial is not None:
         return model, spatial.device_grid(device)
     if controller is not None:
         return model, controller.device_mask(device)
-    return model, (model.ones_mask(device), model.encoding_dim)
+    return model, Mask(model.ones_mask(device), model.encoding_dim)
 
 
 def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
@@ -782,20 +746,18 @@ def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
     controller = net
     net, mask = _resolve_mask(net, override_mask, times.device)
     ys, xs = grid_axes(net, times, h, w)
-    if len(mask) == 4 and hasattr(controller, 'note_grid'):
+    if mask.spatial and hasattr(controller, 'note_grid'):
         controller.note_grid(times, ys, xs)              # stash_iteration finds the cells of these points
     if get_mask:
         if not net.is_progressive:
             raise ValueError('get_mask needs a progressive network')
-        with torch.no_grad():
-            used = flownet_sample_mask(net, times, ys, xs, mask[0], *mask[2:]) if len(mask) == 4 else mask[0]
+        used = mask.tensor
+        if mask.spatial:
+            with torch.no_grad():
+                used = flownet_sample_mask(net, times, ys, xs, mask.tensor, mask.res, mask.centre_scale)
         return (*flow_fields(controller, times, h, w, scale, override_mask), used)
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
-    if isinstance(net, SirenModel):
-        train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        flows = _SirenFields.apply(net, times, ys, xs, float(scale), train, *params)
-        return flows[:, :2], flows[:, 2:]
-    enc_a = net.encode.effective_frequencies() if isinstance(net.encode, RotatedFourierFeatures) else None
+    enc_a = net.encode.effective_frequencies() if isinstance(getattr(net, 'encode', None), RotatedFourierFeatures) else None
     train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad))
     flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, mask, enc_a, *params)
     return flows[:, :2], flows[:, 2:]

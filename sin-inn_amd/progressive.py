@@ -36,7 +36,7 @@ Out of scope: FixedSpatialController, AdaptiveController, the `--spatially-adapt
 import torch
 import torch.nn as nn
 
-from .flownet import last_open
+from .flownet import Mask, last_open
 
 
 class ProgressiveEncoderController(nn.Module):
@@ -111,7 +111,7 @@ class ProgressiveEncoderController(nn.Module):
         return self.model.linears()
 
     def device_mask(self, device):
-        """(mask on `device`, k_active); uploads only if the host mask changed since the last call for this device"""
+        """Mask(mask on `device`, k_active); uploads only if the host mask changed since the last call for this device"""
         device = torch.device(device)
         hit = self._device_masks.get(device)
         if hit is None or not torch.equal(hit[0], self.mask):
@@ -121,7 +121,7 @@ class ProgressiveEncoderController(nn.Module):
             hit = (snapshot, snapshot.pin_memory().to(device, non_blocking=True), last_open(snapshot))
             self._device_masks[device] = hit
             self.uploads += 1
-        return hit[1], hit[2]
+        return Mask(hit[1], hit[2])
 
     def __init__(self, model):
         super().__init__()
@@ -365,11 +365,11 @@ class StashedSpatialController(ProgressiveEncoderController):
         return max(self.next_block, self._loaded_open)
 
     def device_grid(self, device):
-        """(blurred grid on the device, k_active, res, centre_scale): what the spatial kernels take"""
+        """Mask(blurred grid on the device, k_active, res, centre_scale): what the spatial kernels take"""
         device = torch.device(device)
         if self.mask.device.type != device.type or (device.index is not None and self.mask.device.index != device.index):
             raise ValueError(f'the controller is on {self.mask.device}, the grid of points on {device}: move it with .to()')
-        return self.get_mask(), self.k_active, self.res, self.centre_scale_host()
+        return Mask(self.get_mask(), self.k_active, self.res, self.centre_scale_host())
 
     # ---- cells of points ----
     def flat_inds(self, indices, alphas):

@@ -66,8 +66,9 @@ def window(fn, seconds, warmup):
 
 
 def main():
+    from sin_inn_amd import _lib, flownet, progressive
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE', 'siren'])
+    ap.add_argument('--net', default='RBF', choices=list(flownet.flow_model_dict))
     ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask (0 .. 515, clamped to the network\'s width: 27 for PPE)')
     ap.add_argument('--frames', type=int, default=1)
     ap.add_argument('--height', type=int, default=436)
@@ -78,13 +79,12 @@ def main():
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--spatial', type=int, default=0, metavar='R', help='progressive nets: a per-point mask from an R^3 grid (0: the global mask)')
     a = ap.parse_args()
-    from sin_inn_amd import _lib, flownet, progressive
     from fit_flow import composed_flow_fields
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
     siren = a.net in flownet.siren_model_dict
-    net = {**flownet.all_model_dict, **flownet.siren_model_dict}[a.net](flownet.ModelParams()).to(dev)
+    net = flownet.flow_model_dict[a.net](flownet.ModelParams()).to(dev)
     prog = net.is_progressive
     target = net
     if a.spatial:
@@ -95,7 +95,7 @@ def main():
         target.mask[:, :a.k_active] = 1
         target.mask_ = None
         target.cur_block = target.next_block = a.k_active          # k_active of the kernels
-        assert target.device_grid(dev)[1] == a.k_active
+        assert target.device_grid(dev).k_active == a.k_active
     elif prog:
         assert 0 <= a.k_active <= 515
         a.k_active = min(a.k_active, net.encoding_dim)

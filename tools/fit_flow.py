@@ -121,7 +121,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     from sin_inn_amd import FusedAdam, FusedLAMB, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
-    net = {**flownet.all_model_dict, **flownet.siren_model_dict}[net_name](flownet.ModelParams()).to(device)
+    net = flownet.flow_model_dict[net_name](flownet.ModelParams()).to(device)
     assert controller in ('early', 'spatial'), controller
     spatial = controller == 'spatial'
     if spatial:
@@ -174,8 +174,9 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
 
 
 def main():
+    from sin_inn_amd import flownet
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE', 'siren'])
+    ap.add_argument('--net', default='RBF', choices=list(flownet.flow_model_dict))
     ap.add_argument('--max-iteration', type=int, default=1000, help='progressive nets: the controller opens the mask over 3/4 of it')
     ap.add_argument('--height', type=int, default=64)
     ap.add_argument('--width', type=int, default=96)
