@@ -43,23 +43,29 @@ def test_lamb_layout_tiles_every_tensor_once_and_never_touches_padding():
         assert per_tensor == [-(-k // c) for k in sizes]
 
 
-def _numpy_lamb(p, g, m, v, offsets, lr, b1, b2, eps, wd, mgn, step, gs):
+def _numpy_lamb(p, g, m, v, offsets, lr, b1, b2, eps, wd, mgn, step, gs, bias_correction=True, adam_w_mode=True,
+                grad_averaging=True, use_nvlamb=False):
     """the formula block of include/sininn.h, one element at a time, in Python floats (float64)"""
     p, m, v = p.copy(), m.copy(), v.copy()
     G = math.sqrt(sum((gs * g[i]) ** 2 for b, k in offsets for i in range(b, b + k)))
     clip = G / mgn if (mgn > 0 and G > mgn) else 1.0
-    bc1, bc2, beta3 = 1 - b1 ** step, 1 - b2 ** step, 1 - b1
+    bc1, bc2 = (1 - b1 ** step, 1 - b2 ** step) if bias_correction else (1.0, 1.0)
+    beta3 = 1 - b1 if grad_averaging else 1.0
     ratios = []
     for b, k in offsets:
         u = np.zeros(k)
         for j, i in enumerate(range(b, b + k)):
             sg = gs * g[i] / clip
+            if not adam_w_mode:
+                sg += wd * p[i]
             m[i] = b1 * m[i] + beta3 * sg
             v[i] = b2 * v[i] + (1 - b2) * sg * sg
-            u[j] = (m[i] / bc1) / (math.sqrt(v[i] / bc2) + eps) + wd * p[i]
+            u[j] = (m[i] / bc1) / (math.sqrt(v[i] / bc2) + eps)
+            if adam_w_mode:
+                u[j] += wd * p[i]
         pn = math.sqrt(sum(p[i] ** 2 for i in range(b, b + k)))
         un = math.sqrt(sum(x * x for x in u))
-        ratio = lr * pn / un if (wd != 0 and pn != 0 and un != 0) else lr
+        ratio = lr * pn / un if ((use_nvlamb or wd != 0) and pn != 0 and un != 0) else lr
         for j, i in enumerate(range(b, b + k)):
             p[i] -= ratio * u[j]
         ratios.append(ratio)
@@ -86,6 +92,56 @@ def test_restatement_matches_an_element_by_element_loop(gmul, clipped):
         assert abs(float(got['G']) - want[4]) <= 1e-13 * want[4]
         for a in (got['p'], got['m'], got['v']):                  # padding stays what it was
             assert float(a[5:8].abs().max()) == 0 and float(a[11]) == 0
+
+
+# every switch of the formula block away from its default: alone, max_grad_norm = 0, and all four together.  use_nvlamb only shows
+# where wd = 0 (with wd != 0 the ratio is adapted anyway), so its own case runs without weight decay.
+MODE_CASES = {'l2': dict(adam_w_mode=False),
+              'no_grad_averaging': dict(grad_averaging=False),
+              'no_bias_correction': dict(bias_correction=False),
+              'nvlamb_nowd': dict(use_nvlamb=True, weight_decay=0.0),
+              'no_clip': dict(max_grad_norm=0.0),
+              'all': dict(adam_w_mode=False, grad_averaging=False, bias_correction=False, use_nvlamb=True)}
+MODE_DEFAULTS = dict(adam_w_mode=True, grad_averaging=True, bias_correction=True, use_nvlamb=False, max_grad_norm=1.0)
+
+
+@pytest.mark.parametrize('case', list(MODE_CASES))
+def test_restatement_modes_match_an_element_by_element_loop(case):
+    """the restatement's branches against the loop's, and each flipped switch visible in p: the float64 p moves by more than 1e-6 of
+    max |p| (four orders above the rtol) when the switch goes back to its default, so no mode is compared on inputs that hide it"""
+    rng = np.random.default_rng(7)
+    offsets = [(0, 5), (8, 3)]
+    p, g, m, v = (np.zeros(12) for _ in range(4))
+    for b, k in offsets:
+        p[b:b + k] = rng.standard_normal(k)
+        g[b:b + k] = rng.standard_normal(k) * 4.0                # G > max_grad_norm = 1: the clip is live wherever it is enabled
+        m[b:b + k] = rng.standard_normal(k) * 0.1
+        v[b:b + k] = rng.random(k) * 0.01
+    flipped = MODE_CASES[case]
+    hyper = dict(lr=2e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, **MODE_DEFAULTS)
+    hyper.update(flipped)
+    tensors = [torch.from_numpy(a) for a in (p, g, m, v)]
+    for step, gs in ((1, 1.0), (3, 0.5)):
+        flags = {k: hyper[k] for k in ('bias_correction', 'adam_w_mode', 'grad_averaging', 'use_nvlamb')}
+        want = _numpy_lamb(p, g, m, v, offsets, 2e-3, 0.9, 0.999, 1e-6, hyper['weight_decay'], hyper['max_grad_norm'], step, gs,
+                           **flags)
+        assert want[4] > 1.0
+        got = lamb_step_ref(*tensors, offsets, hyper, step, gs, torch.float64)
+        for name, w in zip(('p', 'm', 'v', 'ratios'), want):
+            np.testing.assert_allclose(got[name].numpy(), w, rtol=1e-13, atol=0, err_msg=name)
+        assert abs(float(got['G']) - want[4]) <= 1e-13 * want[4]
+        for a in (got['p'], got['m'], got['v']):
+            assert float(a[5:8].abs().max()) == 0 and float(a[11]) == 0
+        # the flipped switches back at their defaults, all at once and one at a time.  Two of 'all' cannot show alone, by the
+        # formulas: with wd != 0 the ratio is adapted whatever use_nvlamb says, and without the decoupled wd * p term the adapted
+        # ratio divides out the scale sqrt(bc2) / bc1 that bias_correction puts on u (up to eps)
+        switches = [k for k in flipped if k != 'weight_decay']
+        alone = [[k] for k in switches if len(switches) > 1 and k in ('adam_w_mode', 'grad_averaging')]
+        for keys in [switches] + alone:
+            back = lamb_step_ref(*tensors, offsets, dict(hyper, **{k: MODE_DEFAULTS[k] for k in keys}), step, gs, torch.float64)
+            moved = float((back['p'] - got['p']).abs().max() / got['p'].abs().max())
+            print(f'{case} step {step}: {", ".join(keys)} back at the default moves p by {moved:.3g} of max |p|')
+            assert moved > 1e-6, (case, keys, moved)
 
 
 def test_lamb_descriptor_guards_refuse_before_any_launch():
