@@ -759,6 +759,22 @@ int sininn_flownet_backward_encgrad_spatial(const sininn_flownet_args* args, con
 int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, float* out,
                                void* stream);
 
+/* Arbitrary points (net(poses), trainer.py:43-44, pair_flow.py:58-59, progressive_controller.py:45-53): the same kernels at a caller's pose
+ * list instead of a grid.  poses: DEVICE [n][3] fp32, row-major, row p = (t, y, x) of point p: a contiguous torch (n, 3) tensor; 4-byte
+ * alignment.  It is read in place where the grid calls read the axis vectors; no pose list is copied and no encoding is stored.
+ *     flows[c][p] = net(poses[p])[c] * scale              flows / dflows are [4][n] (the grid layout with T = H = 1, W = n)
+ *   The descriptor is the one above; its T, H, W, times, ys, xs are ignored and may be 0 / NULL.  Every other field means what it means in
+ *   the grid calls: encoding, progressive / mask / k_active, enc_a, scale; `saved` and the workspaces have the sizes of
+ *   sininn_flownet_saved_bytes(n), sininn_flownet_workspace_bytes(n), sininn_flownet_forward_workspace_bytes(args) and
+ *   sininn_flownet_encgrad_workspace_bytes(args).  Tiles, partial sums and the order of every sum depend on n alone: a pose list that
+ *   spells out meshgrid(times, ys, xs) gives bitwise the flows and gradients of the grid call, two calls are bitwise equal and any valid
+ *   k_active gives the same bits.  There is no gradient with respect to the coordinates.
+ * Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse.  Not available under a spatial mask. */
+int sininn_flownet_forward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
+int sininn_flownet_backward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
+int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a,
+                                           void* enc_workspace, size_t enc_workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).
  *   video-interpolation/model.py:123-146 SineLayer (sin(omega_0 * linear(x)), omega_0 = 30), model.py:149-171 SirenModel with the
@@ -804,6 +820,12 @@ size_t sininn_siren_saved_bytes(int64_t n_points);
 size_t sininn_siren_workspace_bytes(int64_t n_points);
 int sininn_siren_forward(const sininn_siren_args* args, void* stream);
 int sininn_siren_backward(const sininn_siren_args* args, void* stream);
+/* Arbitrary points: h_0 = poses[p], DEVICE [n][3] fp32 row-major (4-byte alignment), read in place; flows / dflows are [4][n],
+ * flows[c][p] = out[p][c] * scale.  T, H, W, times, ys, xs of the descriptor are ignored (0 / NULL); saved and workspace have the sizes of
+ * sininn_siren_saved_bytes(n) / sininn_siren_workspace_bytes(n).  The same kernels: a pose list that spells out the grid gives bitwise the
+ * grid call's flows and gradients.  Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse. */
+int sininn_siren_forward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream);
+int sininn_siren_backward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LAMB, the optimiser of the flow trainer (video-interpolation/trainer.py:134-135: apex.optimizers.FusedLAMB(params, lr=lr)),

@@ -289,11 +289,16 @@ _SIGS = {
     'sininn_flownet_backward_encgrad_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_void_p, C.c_size_t,
                                                           C.c_void_p]),
     'sininn_flownet_sample_mask': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_void_p]),
+    'sininn_flownet_forward_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, C.c_void_p]),
+    'sininn_flownet_backward_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, C.c_void_p]),
+    'sininn_flownet_backward_encgrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
     'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_siren_workspace_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_siren_forward': (C.c_int, [C.POINTER(SirenArgs), C.c_void_p]),
     'sininn_siren_backward': (C.c_int, [C.POINTER(SirenArgs), C.c_void_p]),
+    'sininn_siren_forward_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, C.c_void_p]),
+    'sininn_siren_backward_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, C.c_void_p]),
     'sininn_lamb_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),

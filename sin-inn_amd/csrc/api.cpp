@@ -131,11 +131,17 @@ int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* g
 int flownet_backward_encgrad_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* g_enc_a,
                                             void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
 int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st);
+int flownet_forward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st);
+int flownet_backward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st);
+int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
+                                           size_t enc_workspace_bytes, hipStream_t st);
 int siren_supported(const sininn_siren_args* a, const char* who);
 size_t siren_saved_bytes(int64_t n);
 size_t siren_workspace_bytes(int64_t n);
 int siren_forward_launch(const sininn_siren_args* a, hipStream_t st);
 int siren_backward_launch(const sininn_siren_args* a, hipStream_t st);
+int siren_forward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st);
+int siren_backward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st);
 size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
 int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st);
 int lamb_step_launch(const sininn_lamb_args* a, hipStream_t st);
@@ -608,11 +614,27 @@ int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* gri
                                void* stream) {
   return flownet_sample_mask_launch(args, grid, res, centre_scale, out, ST(stream));
 }
+int sininn_flownet_forward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream) {
+  return flownet_forward_points_launch(args, poses, n, ST(stream));
+}
+int sininn_flownet_backward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream) {
+  return flownet_backward_points_launch(args, poses, n, ST(stream));
+}
+int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
+                                           size_t enc_workspace_bytes, void* stream) {
+  return flownet_backward_encgrad_points_launch(args, poses, n, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
+}
 int sininn_siren_supported(const sininn_siren_args* args) { return siren_supported(args, "sininn_siren_supported"); }
 size_t sininn_siren_saved_bytes(int64_t n_points) { return siren_saved_bytes(n_points); }
 size_t sininn_siren_workspace_bytes(int64_t n_points) { return siren_workspace_bytes(n_points); }
 int sininn_siren_forward(const sininn_siren_args* args, void* stream) { return siren_forward_launch(args, ST(stream)); }
 int sininn_siren_backward(const sininn_siren_args* args, void* stream) { return siren_backward_launch(args, ST(stream)); }
+int sininn_siren_forward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream) {
+  return siren_forward_points_launch(args, poses, n, ST(stream));
+}
+int sininn_siren_backward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream) {
+  return siren_backward_points_launch(args, poses, n, ST(stream));
+}
 
 size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors) { return lamb_workspace_bytes(n_chunks, n_tensors); }
 int sininn_lamb_grad_norm(const sininn_lamb_args* args, void* stream) { return lamb_grad_norm_launch(args, ST(stream)); }

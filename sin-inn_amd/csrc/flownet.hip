@@ -53,6 +53,12 @@
 //           next to gb1 and is launched on the open 128-column tiles only; flownet_reduce_l1_kernel scatters the sums into
 //           nn.Linear's [256][515] layout, times the mask, exact zeros where the mask is zero.
 //
+// points    (sininn_flownet_*_points) the coordinates of point p are row p of a caller's pose list [N][3] instead of an entry of each axis
+//           vector: point_coord (flownet_tile.h) branches on q.poses, a kernel argument, and the host sets T = H = 1, W = N, which makes
+//           the [T][4][H][W] indexing of flows / dflows the planar [4][N].  No kernel is instantiated for it and nothing else differs:
+//           tiles, `saved`, workspaces and the order of every sum depend on N alone, so a pose list that spells out a grid gives the grid
+//           call's bits.  Not combined with the spatial mode.
+//
 // positional encoding (PE / PPE, PEModel model.py:472-487, PPEModel model.py:607-611): layer 1 has LIVE (LIVE + 3) inputs, fewer than
 //           its padded K width KW; features LIVE .. KW - 1 are exact zeros from encode4.  Plain PE reads W1 [256][LIVE] in place (96-byte
 //           rows, the 16-byte loads of columns LIVE .. KW - 1 are replaced by zeros), two K steps; PPE packs mask * W1 into [256][KW] +
@@ -143,6 +149,7 @@ struct FlowNetDev {
   int T, H, W, N, ntiles;
   float scale;
   const float *times, *ys, *xs;
+  const float* poses;      // points mode: [N][3], the coordinates of point p; nullptr: the grid above
   const float *enc_a, *enc_b;
   const float* w[4];
   const float* b[4];
@@ -1065,8 +1072,8 @@ static Spatial spatial_of(const SpatialArgs* s) {
 }
 
 // the descriptor of a call whose entry point has called check_head, checked and copied into q.  spatial != nullptr: the descriptor's mask
-// is ignored, the grid goes to q.sp
-static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial) {
+// is ignored, the grid goes to q.sp.  pl != nullptr: the points are that pose list, not the descriptor's grid (never with spatial)
+static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
   q = FlowNetDev{};
   q.sp = spatial_of(spatial);
   if (a->progressive) {
@@ -1074,7 +1081,7 @@ static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& 
     SININN_CHECK(a->k_active >= 0 && a->k_active <= a->enc_dim, "%s: k_active %d (0 .. %d)", who, a->k_active, a->enc_dim);
   }
   const bool enc_b = for_kind(a->encoding, false, [](auto k) { return Enc<decltype(k)::value>::ENC_B; });
-  if (int rc = check_points(a, who, q, a->enc_a && (a->enc_b || !enc_b), "axis / encoding")) return rc;
+  if (int rc = check_points(a, who, q, pl, a->enc_a && (a->enc_b || !enc_b), pl ? "encoding" : "axis / encoding")) return rc;
   SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
   if (int rc = check_layers<4>(a, who, q)) return rc;
   q.scale = a->scale;
@@ -1120,11 +1127,13 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
 }
 
 // g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
-// spatial != nullptr: layer 1 under the per-point mask of that grid.  The entry point has called check_head
-static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial) {
+// spatial != nullptr: layer 1 under the per-point mask of that grid.  pl != nullptr: at that pose list.  The entry point has called check_head
+static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial,
+                           const PoseList* pl = nullptr) {
   FlowNetDev q;
-  if (int rc = fill_args(a, spatial ? "flownet_backward_spatial" : "flownet_backward", q, spatial)) return rc;
-  if (int rc = check_backward_buffers<4>(a, "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q)) return rc;
+  if (int rc = fill_args(a, spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl)) return rc;
+  if (int rc = check_backward_buffers<4>(a, pl ? "flownet_backward_points" : "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q))
+    return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
   float* const wt = ws + 3 * lstride;
@@ -1190,12 +1199,12 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
   return 0;
 }
 
-static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial) {
-  const char* who = spatial ? "flownet_forward_spatial" : "flownet_forward";
+static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
+  const char* who = spatial ? "flownet_forward_spatial" : pl ? "flownet_forward_points" : "flownet_forward";
   FlowNetDev q;
   if (int rc = check_head(a, who, spatial)) return rc;
-  if (int rc = fill_args(a, who, q, spatial)) return rc;
-  if (int rc = check_forward_buffers(a, "flownet_forward", flownet_saved_bytes(q.N), q)) return rc;
+  if (int rc = fill_args(a, who, q, spatial, pl)) return rc;
+  if (int rc = check_forward_buffers(a, pl ? who : "flownet_forward", flownet_saved_bytes(q.N), q)) return rc;
   return for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
     return forward_kind_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, st);
   });
@@ -1208,9 +1217,9 @@ int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* gr
   return forward_launch(a, st, &s);
 }
 
-static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial) {
-  if (int rc = check_head(a, spatial ? "flownet_backward_spatial" : "flownet_backward", spatial)) return rc;
-  return backward_launch(a, nullptr, nullptr, st, spatial);
+static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
+  if (int rc = check_head(a, spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", spatial)) return rc;
+  return backward_launch(a, nullptr, nullptr, st, spatial, pl);
 }
 
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_plain_launch(a, st, nullptr); }
@@ -1236,8 +1245,8 @@ int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, 
 // the head under this entry point's own name, so that a refusal of the spatial mode (PPE, a null grid, res) comes before the Fourier-only
 // refusal, which would hide it
 static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st,
-                                   const SpatialArgs* spatial) {
-  const char* who = spatial ? "flownet_backward_encgrad_spatial" : "flownet_backward_encgrad";
+                                   const SpatialArgs* spatial, const PoseList* pl = nullptr) {
+  const char* who = spatial ? "flownet_backward_encgrad_spatial" : pl ? "flownet_backward_encgrad_points" : "flownet_backward_encgrad";
   if (int rc = check_head(a, who, spatial)) return rc;
   SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
                a->encoding);
@@ -1246,7 +1255,7 @@ static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a,
                "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
                flownet_encgrad_workspace_bytes(a));
   SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
-  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st, spatial);
+  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st, spatial, pl);
 }
 
 int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
@@ -1258,6 +1267,23 @@ int flownet_backward_encgrad_spatial_launch(const sininn_flownet_args* a, const 
                                             void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st) {
   const SpatialArgs s{grid, res, centre_scale};
   return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, &s);
+}
+
+// ---- points mode: the same launches at a pose list [n][3]; the descriptor's grid is not read, flows / dflows are [4][n] ----
+int flownet_forward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return forward_launch(a, st, nullptr, &pl);
+}
+
+int flownet_backward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return backward_plain_launch(a, st, nullptr, &pl);
+}
+
+int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
+                                           size_t enc_workspace_bytes, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, nullptr, &pl);
 }
 
 }  // namespace sininn

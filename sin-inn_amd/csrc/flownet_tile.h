@@ -4,7 +4,8 @@
 //           The output layer, dout, the tile load, the column sums and the coordinate selection stay spelled out in each kernel: moved
 //           into a helper, each of them changed the instructions of a hot kernel.  The two transpose kernels stay where they are too
 //   host    check_points / check_layers / check_saved / check_forward_buffers / check_backward_buffers: the parts of a descriptor and
-//           their refusals that do not depend on the network; chain_blocks, raise_lds
+//           their refusals that do not depend on the network (check_points: the grid of a call, or, poses != nullptr, its pose list);
+//           chain_blocks, raise_lds
 #pragma once
 #include "common.h"
 
@@ -23,10 +24,15 @@ constexpr int FN_CS = 4;            // floats per row of the packed coordinate c
 
 struct Coord { float t, y, x; };
 
-// the coordinates of point p of the (times, ys, xs) grid; Q: a kernel descriptor with T, H, W, N and the axis vectors
+// the coordinates of point p: row p of the pose list [N][3] (q.poses, points mode: a wave-uniform branch on a kernel argument), else point
+// p of the (times, ys, xs) grid; Q: a kernel descriptor with T, H, W, N, the axis vectors and poses
 template <class Q>
 __device__ __forceinline__ Coord point_coord(const Q& q, int p) {
   p = p < q.N ? p : q.N - 1;
+  if (q.poses) {
+    const float* const r = q.poses + 3 * p;            // N <= 2^22: 3 p fits an int
+    return Coord{r[0], r[1], r[2]};
+  }
   const int hw = q.H * q.W;
   const int t = p / hw, rem = p - t * hw;
   const int y = rem / q.W, x = rem - y * q.W;
@@ -115,16 +121,31 @@ __device__ __forceinline__ void stage_coord(const Q& q, float* cs, int tile, int
 }
 
 // ---- host: the parts of a descriptor that do not depend on the network.  A: the C struct of a call, Q: the kernels' descriptor ----
-// the grid of points: T H W in 1 .. 2^22 and the axis vectors (`more` / `what`: further pointers refused in the same sentence)
+// the points of a call (`more` / `what`: further pointers refused in the same sentence)
+struct PoseList {
+  const float* poses;      // device [n][3]
+  int64_t n;
+};
+
+// pl == nullptr: the grid of the descriptor, T H W in 1 .. 2^22 and the axis vectors.  Else the pose list, n in 1 .. 2^22: the descriptor's
+// grid is not read, the kernels see T = H = 1, W = n, which makes [T][4][H][W] the planar [4][n]
 template <class A, class Q>
-int check_points(const A* a, const char* who, Q& q, bool more = true, const char* what = "axis") {
-  SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
-               who, a->T, a->H, a->W);
-  SININN_CHECK(a->times && a->ys && a->xs && more, "%s: null %s pointer", who, what);
-  q.T = a->T; q.H = a->H; q.W = a->W;
-  q.N = a->T * a->H * a->W;
+int check_points(const A* a, const char* who, Q& q, const PoseList* pl = nullptr, bool more = true, const char* what = "axis") {
+  if (pl) {
+    SININN_CHECK(pl->n >= 1 && pl->n <= (int64_t)1 << 22, "%s: %lld points (1 .. 2^22)", who, (long long)pl->n);
+    SININN_CHECK(pl->poses != nullptr, "%s: null poses pointer", who);
+    SININN_CHECK(more, "%s: null %s pointer", who, what);
+    q.T = 1; q.H = 1; q.W = (int)pl->n;
+    q.poses = pl->poses;
+  } else {
+    SININN_CHECK(a->T > 0 && a->H > 0 && a->W > 0 && (int64_t)a->T * a->H * a->W <= (int64_t)1 << 22, "%s: grid %d x %d x %d (1 .. 2^22 points)",
+                 who, a->T, a->H, a->W);
+    SININN_CHECK(a->times && a->ys && a->xs && more, "%s: null %s pointer", who, what);
+    q.T = a->T; q.H = a->H; q.W = a->W;
+    q.times = a->times; q.ys = a->ys; q.xs = a->xs;
+  }
+  q.N = q.T * q.H * q.W;
   q.ntiles = (q.N + FN_P - 1) / FN_P;
-  q.times = a->times; q.ys = a->ys; q.xs = a->xs;
   return 0;
 }
 

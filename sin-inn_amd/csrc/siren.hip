@@ -24,6 +24,8 @@
 //           buffers of a forward / backward call; from flownet.hip the hidden layers' weight gradient (hidden_wgrad_launch).  The output
 //           layer, dout, the tile load, the column sums and the transpose kernel match flownet.hip's text but stay spelled out: as helpers
 //           they changed the instructions, or the placement, of these kernels.
+// points    (sininn_siren_*_points) point_coord reads row p of a caller's pose list [N][3] instead of the axis vectors; T = H = 1, W = N makes
+//           flows / dflows the planar [4][N].  The same kernels, nothing else differs (see flownet.hip)
 // Rows of the last tile beyond N are computed on a clamped point in the forward pass and carry dout = 0 in the backward pass, so every
 // saved / workspace row is written before it is read and contributes exact zeros to every sum.
 #include "flownet_tile.h"
@@ -46,6 +48,7 @@ struct SirenDev {
   int T, H, W, N, ntiles;
   float scale, omega;
   const float *times, *ys, *xs;
+  const float* poses;      // points mode: [N][3], the coordinates of point p; nullptr: the grid above
   const float* w[SR_SINES + 1];
   const float* b[SR_SINES + 1];
   float* flows;
@@ -301,33 +304,36 @@ size_t siren_workspace_bytes(int64_t n) {
   return ((size_t)2 * (SR_SINES - 1) * lstride + (size_t)(SR_SINES - 1) * FN_HID * FN_HID + part_floats(ntiles)) * sizeof(float);
 }
 
-static int check_args(const sininn_siren_args* a, const char* who, SirenDev& q) {
+// pl != nullptr: the points are that pose list, not the descriptor's grid
+static int check_args(const sininn_siren_args* a, const char* who, SirenDev& q, const PoseList* pl) {
   SININN_CHECK(a != nullptr, "%s: null args", who);
   SININN_CHECK(a->struct_bytes == sizeof(sininn_siren_args), "%s: struct_bytes is %zu, this library was built with %zu", who, a->struct_bytes,
                sizeof(sininn_siren_args));
   if (!siren_supported(a, who)) return 1;
   q = SirenDev{};
-  if (int rc = check_points(a, who, q)) return rc;
+  if (int rc = check_points(a, who, q, pl)) return rc;
   if (int rc = check_layers<SR_SINES + 1>(a, who, q)) return rc;
   q.scale = a->scale;
   q.omega = a->omega;
   return 0;
 }
 
-int siren_forward_launch(const sininn_siren_args* a, hipStream_t st) {
+static int forward_launch(const sininn_siren_args* a, hipStream_t st, const PoseList* pl) {
   SirenDev q;
-  if (int rc = check_args(a, "siren_forward", q)) return rc;
-  if (int rc = check_forward_buffers(a, "siren_forward", siren_saved_bytes(q.N), q)) return rc;
+  const char* who = pl ? "siren_forward_points" : "siren_forward";
+  if (int rc = check_args(a, who, q, pl)) return rc;
+  if (int rc = check_forward_buffers(a, who, siren_saved_bytes(q.N), q)) return rc;
   if (raise_lds(siren_fwd_kernel, SR_LDS, "siren_forward")) return 1;
   hipLaunchKernelGGL(siren_fwd_kernel, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), SR_LDS, st, q);   // two resident blocks per CU
   SININN_LAUNCH_CHECK("siren_forward");
   return 0;
 }
 
-int siren_backward_launch(const sininn_siren_args* a, hipStream_t st) {
+static int backward_launch(const sininn_siren_args* a, hipStream_t st, const PoseList* pl) {
   SirenDev q;
-  if (int rc = check_args(a, "siren_backward", q)) return rc;
-  if (int rc = check_backward_buffers<SR_SINES + 1>(a, "siren_backward", siren_saved_bytes(q.N), siren_workspace_bytes(q.N), q)) return rc;
+  const char* who = pl ? "siren_backward_points" : "siren_backward";
+  if (int rc = check_args(a, who, q, pl)) return rc;
+  if (int rc = check_backward_buffers<SR_SINES + 1>(a, who, siren_saved_bytes(q.N), siren_workspace_bytes(q.N), q)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
   float* const wt = ws + 2 * (SR_SINES - 1) * lstride;
@@ -348,6 +354,20 @@ int siren_backward_launch(const sininn_siren_args* a, hipStream_t st) {
   for (int l = SR_SINES - 1; l >= 1; --l)                // gW_{l+1} = dz_{l+1}^T h_l
     if (int rc = hidden_wgrad_launch(q.ntiles, q.dz + (l - 1) * lstride, q.hin + (l - 1) * lstride, q.part, a->gw[l], a->gb[l], st)) return rc;
   return 0;
+}
+
+int siren_forward_launch(const sininn_siren_args* a, hipStream_t st) { return forward_launch(a, st, nullptr); }
+int siren_backward_launch(const sininn_siren_args* a, hipStream_t st) { return backward_launch(a, st, nullptr); }
+
+// points mode: the same launches at a pose list [n][3]; the descriptor's grid is not read, flows / dflows are [4][n]
+int siren_forward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return forward_launch(a, st, &pl);
+}
+
+int siren_backward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return backward_launch(a, st, &pl);
 }
 
 }  // namespace sininn

@@ -8,6 +8,7 @@ backward in libsininn.so (csrc/flownet.hip).
     PositionalEncoding / PEModel / PPEModel                    video-interpolation/model.py:321-340, 472-487, 607-611 (positional_model_dict)
     SineLayer / SirenModel                                     video-interpolation/model.py:123-146, 149-171 (siren_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
+    flow_at / net(poses)                                       net(poses) of trainer.py:43-44, pair_flow.py:58-59
 
 The modules have the reference's constructor signatures, its `state_dict` keys (`encode.centres`, `encode.sigma` /
 `encode.frequencies` / `encode.offsets`, `encode.sigma` / `encode.freqs`, `model.model.{0,2,4,6}.{weight,bias}`) and its order of RNG draws at construction (encoding buffers
@@ -16,8 +17,8 @@ loads.  One table describes them: `ENCODINGS` holds each encoding's constructor 
 progressive, and `all_model_dict` maps the twelve network names to the classes; the reference's five dicts are views of it.  The
 encodings of `model_dict` / `progressive_model_dict` / `grid_model_dict` are buffers: no gradient flows below layer 1.  The kernels are
 built for the ModelParams defaults; any other size raises with the library's own list of the sizes it supports, there is no second
-implementation behind this module, and calling a model directly (`net(poses)`) is not provided: the N x 3 pose list and the N x 512
-encoding never exist here.
+implementation behind this module.  On a grid the N x 3 pose list never exists; on a pose list (`flow_at`, below) it is the caller's
+tensor, read in place; the N x 512 encoding never exists in either.
 
 The progressive models feed `cat((t, y, x), encode(x)) * mask` to layer 1 (515 features, first weight [256][515]); the mask is
 a global vector of 515 values that a controller of `sin_inn_amd.progressive` opens block by block (main.py:136-143).
@@ -66,6 +67,14 @@ the grid of points and the layers (`_points_and_layers`); `_forward` allocates `
 the workspace and the gradients, calls, and carries the optional frequency gradient.  The six public forward / backward functions name their
 descriptor builder, their size queries and their library call and nothing else; `_FlowFields` is the one autograd function, `_mode` picks
 the pair of functions and their keyword arguments for it (`_SirenFields.apply` is its SIREN call under the earlier name).
+
+Arbitrary points: `flow_at(net, poses, scale)` and, through it, `net(poses)` and `controller(poses, override_mask=, get_mask=)`
+evaluate the same kernels at a caller's pose list (..., 3) -> (..., 4) (`sininn_flownet_*_points` / `sininn_siren_*_points`): the kernels
+read point p's coordinates from row p of the list where the grid mode reads the three axis vectors, and nothing else differs, so the
+flows and gradients of a list that spells out a grid are bitwise those of the grid call.  The kernels write the planar (4, N) layout
+(`planar=True` returns it); the transpose to the reference's (N, 4) is a torch op.  Differentiable with respect to the parameters
+(`_FlowAt`, next to `_FlowFields`), learnable frequencies included; there is no gradient with respect to the coordinates.  Per-point
+masks (a `StashedSpatialController`, a grid as `override_mask`) are not evaluated at pose lists.
 
 Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
 `--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
@@ -303,8 +312,8 @@ class _EncodedMlpModel(nn.Module):
         return [m for m in self.model.model if isinstance(m, nn.Linear)]
 
     def forward(self, x, *args, **kwargs):
-        raise NotImplementedError('evaluate the network on a (times, h, w) grid with sin_inn_amd.flownet.flow_fields: the pose '
-                                  'list and the encoding are never materialised')
+        """net(poses), model.py:97-103: (..., 3) -> (..., 4) in the fused kernels (`flow_at`)"""
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'))
 
 
 class ProgressiveModel(_EncodedMlpModel):
@@ -421,8 +430,8 @@ class SirenModel(nn.Module):
         return [m.linear if isinstance(m, SineLayer) else m for m in self.model]
 
     def forward(self, x, *args, **kwargs):
-        raise NotImplementedError('evaluate the network on a (times, h, w) grid with sin_inn_amd.flownet.flow_fields: the pose '
-                                  'list and the activations are never materialised')
+        """net(poses), model.py:167-171: (..., 3) -> (..., 4) in the fused kernels (`flow_at`)"""
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'))
 
 
 siren_model_dict = {'siren': SirenModel}                          # beside all_model_dict: the command line does not open it yet
@@ -453,13 +462,24 @@ class Mask(NamedTuple):
 
 # ---- the descriptors: what is particular to a kind of network, then the part they share ----
 def _points_and_layers(a, lins, times, ys, xs, scale):
-    """the grid of points (axes on the GPU, T H W, scale, pointers) and the nn.Linear layers of a descriptor"""
-    for t in (times, ys, xs):
-        _on_gpu(t)
-    times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
-    a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
-    a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
-    a._axes, a._device = (times, ys, xs), times.device           # the contiguous copies live as long as the descriptor
+    """the grid of points (axes on the GPU, T H W, scale, pointers) and the nn.Linear layers of a descriptor.  `ys is None`: `times`
+    is a pose list (N, 3); the descriptor gets the planar shape T = H = 1, W = N that `flows` / `dflows` have then and no axis
+    pointers, and `a._poses` is what the points entry points take beside it"""
+    if ys is None:
+        poses = times
+        _on_gpu(poses, 'pose list')
+        assert poses.dtype == torch.float32 and poses.dim() == 2 and poses.shape[1] == 3, 'a pose list (N, 3), fp32'
+        poses = poses.contiguous()
+        a.T, a.H, a.W, a.scale = 1, 1, poses.shape[0], float(scale)
+        a._axes, a._device = (poses,), poses.device
+        a._poses = (ptr(poses) if poses.numel() else None, poses.shape[0])
+    else:
+        for t in (times, ys, xs):
+            _on_gpu(t)
+        times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
+        a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
+        a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
+        a._axes, a._device = (times, ys, xs), times.device       # the contiguous copies live as long as the descriptor
     for l, lin in enumerate(lins):
         _on_gpu(lin.weight, 'parameter')
         assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
@@ -571,16 +591,21 @@ def _flownet_saved_shape(a):
     return lambda: (3, _lib.lib().sininn_flownet_saved_bytes(a.T * a.H * a.W) // (3 * 256 * 4), 256)
 
 
+def _pack_workspace(a):
+    """a progressive forward call: the workspace of the packed, masked copy of W1"""
+    if a.progressive:
+        a._pack = torch.empty(_lib.lib().sininn_flownet_forward_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
+        a.workspace, a.workspace_bytes = ptr(a._pack), a._pack.numel() * 4
+    return a
+
+
 def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
     """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
     (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
     caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats (PPE: 27) and `k_active` a
     number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
     (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
-    a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
-    if a.progressive:                                    # the packed, masked copy of W1
-        a._pack = torch.empty(_lib.lib().sininn_flownet_forward_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
-        a.workspace, a.workspace_bytes = ptr(a._pack), a._pack.numel() * 4
+    a = _pack_workspace(_args(net, times, ys, xs, scale, mask, k_active, enc_a))
     return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward)
 
 
@@ -637,6 +662,39 @@ def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, ome
     return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_siren_workspace_bytes, _lib.lib().sininn_siren_backward)
 
 
+# ---- the same four calls at a pose list (N, 3): flows and dflows are planar, (4, N) ----
+def flownet_forward_points(net, poses, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
+    """flownet_forward at a pose list (N, 3) on the device: flows (4, N) = net(poses)^T * scale; `saved` as there, for N points"""
+    a = _pack_workspace(_args(net, poses, None, None, scale, mask, k_active, enc_a))
+    flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_points, *a._poses)
+    return flows.view(4, -1), saved
+
+
+def flownet_backward_points(net, poses, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
+                            enc_workspace=None, g_enc_a=None):
+    """flownet_backward at the pose list of the forward call, dflows (4, N); everything else as there"""
+    a = _args(net, poses, None, None, scale, mask, k_active, enc_a)
+    return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
+                     _lib.lib().sininn_flownet_backward_points, *a._poses,
+                     enc_call=_lib.lib().sininn_flownet_backward_encgrad_points if enc_grad else None, enc_workspace=enc_workspace,
+                     g_enc_a=g_enc_a)
+
+
+def siren_forward_points(net, poses, scale, train, saved=None, omega=None):
+    """siren_forward at a pose list (N, 3) on the device: flows (4, N)"""
+    a = _siren_args(net, poses, None, None, scale, omega)
+    flows, saved = _forward(a, train, saved, lambda: _lib.lib().sininn_siren_saved_bytes(a.W) // 4, _lib.lib().sininn_siren_forward_points,
+                            *a._poses)
+    return flows.view(4, -1), saved
+
+
+def siren_backward_points(net, poses, scale, dflows, saved, workspace=None, omega=None):
+    """siren_backward at the pose list of the forward call, dflows (4, N)"""
+    a = _siren_args(net, poses, None, None, scale, omega)
+    return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_siren_workspace_bytes,
+                     _lib.lib().sininn_siren_backward_points, *a._poses)
+
+
 def _mode(net, mask, enc_a):
     """(forward, backward, the keyword arguments both take) of a call: a SirenModel, a per-point mask, or a global mask / none"""
     if isinstance(net, SirenModel):
@@ -681,6 +739,35 @@ class _SirenFields:
     @staticmethod
     def apply(net, times, ys, xs, scale, train, *params):
         return _FlowFields.apply(net, times, ys, xs, scale, train, Mask(), None, *params)
+
+
+class _FlowAt(torch.autograd.Function):
+    """`_FlowFields` at a pose list: flows (4, N).  The poses get no gradient"""
+
+    @staticmethod
+    def forward(ctx, net, poses, scale, train, mask, enc_a, *params):
+        if enc_a is not None:
+            enc_a = enc_a.detach().contiguous()
+        if isinstance(net, SirenModel):
+            forward, ctx.backward_fn, ctx.kw = siren_forward_points, siren_backward_points, {}
+        else:
+            forward, ctx.backward_fn = flownet_forward_points, flownet_backward_points
+            ctx.kw = dict(mask=mask.tensor, k_active=mask.k_active, enc_a=enc_a)
+        flows, saved = forward(net, poses, scale, train, **ctx.kw)
+        ctx.net, ctx.poses, ctx.scale, ctx.saved = net, poses, scale, saved
+        if enc_a is not None and ctx.needs_input_grad[5]:
+            ctx.kw['enc_grad'] = True
+        return flows
+
+    @staticmethod
+    def backward(ctx, dflows):
+        if ctx.saved is None:
+            raise RuntimeError('flow_at: backward through an inference-mode forward')
+        grads, g_enc = ctx.backward_fn(ctx.net, ctx.poses, ctx.scale, dflows, ctx.saved, **ctx.kw), None
+        if ctx.kw.get('enc_grad'):
+            grads, g_enc = grads
+        ctx.saved = None
+        return (None,) * 5 + (g_enc,) + tuple(grads)
 
 
 def grid_axes(net, times, h, w):
@@ -761,3 +848,36 @@ def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
     train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad))
     flows = _FlowFields.apply(net, times, ys, xs, float(scale), train, mask, enc_a, *params)
     return flows[:, :2], flows[:, 2:]
+
+
+def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=False):
+    """net(poses) * scale (trainer.py:43-44, progressive_controller.py:45-53) at arbitrary points: `poses` (..., 3) fp32 on the GPU,
+    columns (t, y, x) -> (..., 4), contiguous.  `net`: what flow_fields takes, a model or a LinearController / LinearControllerEarly
+    around a progressive one; `override_mask` (515 values, PPE: 27) replaces the controller's mask.  The kernels read the list in place
+    and write the planar (4, N) layout; `planar=True` returns that tensor, without the transpose to the reference's layout.
+    Differentiable with respect to the parameters (and `encode.frequencies` of RFF / PRFF); under torch.no_grad() (or with no trainable
+    parameter) the inference mode runs and nothing is saved.  `get_mask=True` returns (out, the mask in use on the device).
+    There is no gradient with respect to the coordinates: poses that require one are refused."""
+    if not torch.is_tensor(poses) or poses.dim() < 1 or poses.shape[-1] != 3:
+        raise ValueError(f'flow_at: poses of shape (..., 3), columns (t, y, x); got {tuple(poses.shape) if torch.is_tensor(poses) else type(poses)}')
+    if poses.dtype != torch.float32:
+        raise ValueError(f'flow_at: fp32 poses; got {poses.dtype}')
+    if poses.requires_grad:
+        raise NotImplementedError('flow_at: there is no gradient with respect to the coordinates (the kernels differentiate the '
+                                  'parameters only); pass poses.detach()')
+    _on_gpu(poses, 'pose list')
+    lead = poses.shape[:-1]
+    flat = poses.reshape(-1, 3).contiguous()
+    net, mask = _resolve_mask(net, override_mask, poses.device)
+    if mask.spatial:
+        raise NotImplementedError('flow_at: per-point masks (StashedSpatialController, a mask grid) are evaluated on a (times, h, w) '
+                                  'grid only, with flow_fields')
+    if get_mask and not net.is_progressive:
+        raise ValueError('get_mask needs a progressive network')
+    params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
+    enc_a = net.encode.effective_frequencies() if isinstance(getattr(net, 'encode', None), RotatedFourierFeatures) else None
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad))
+    out = _FlowAt.apply(net, flat, float(scale), train, mask, enc_a, *params)
+    if not planar:
+        out = out.t().contiguous().view(*lead, 4)
+    return (out, mask.tensor) if get_mask else out

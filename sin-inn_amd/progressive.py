@@ -18,7 +18,8 @@ checkpoints and training curves depend on:
   * LinearControllerEarly.stash_iteration calls `super(LinearController, self)`: it skips LinearController in the MRO;
   * a checkpoint keeps `mask_stashed`, the SUM of the mask, and load_mask rebuilds `floor(sum)` ones followed by the fraction:
     a block of six entries ramping at 0.5 comes back as three ones.
-Calling a controller on a pose list raises like the models do (`flow_fields` evaluates a controller on a grid).
+Calling a linear controller on a pose list, `controller(poses, override_mask=, get_mask=)`, is progressive_controller.py:45-53 on
+`flownet.flow_at`; `flow_fields` evaluates a controller on a grid.  StashedSpatialController evaluates grids only.
 
 StashedSpatialController keeps a mask PER GRID CELL, [res^3][515], and every point reads the trilinear interpolation of its box
 blur.  At res = 50 that is 257 MB, so unlike the linear controllers its state lives on the DEVICE, next to the model (`.to()` /
@@ -36,7 +37,7 @@ Out of scope: FixedSpatialController, AdaptiveController, the `--spatially-adapt
 import torch
 import torch.nn as nn
 
-from .flownet import Mask, last_open
+from .flownet import Mask, flow_at, last_open
 
 
 class ProgressiveEncoderController(nn.Module):
@@ -70,13 +71,12 @@ class ProgressiveEncoderController(nn.Module):
         raise NotImplementedError
 
     def __call__(self, x, **kwargs):
-        if 'override_mask' in kwargs and kwargs['override_mask'] is not None:
-            override_mask = kwargs['override_mask']
-        else:
-            override_mask = self.mask
-        out = self.model(x, override_mask=override_mask)
+        """progressive_controller.py:45-53 on flow_at: the controller's own mask goes through `device_mask` (uploaded when it changed,
+        with its k_active), an `override_mask` as flow_at takes it; `get_mask` among the keywords returns (out, that mask)"""
+        override_mask = kwargs.get('override_mask')
+        out = flow_at(self, x, 1.0, override_mask=override_mask)
         if 'get_mask' in kwargs:
-            return out, override_mask
+            return out, self.mask if override_mask is None else override_mask
         return out
 
     def init_mask(self):

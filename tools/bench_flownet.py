@@ -19,6 +19,8 @@ that make F_eff and carry its gradient to `encode.frequencies`; PRFF runs under 
 call.  The FLOP counts stay those of the network; the interpolation is not counted.
 `siren` is 3-256-256-256-256-4: 2 N (3*256 + 3*256*256 + 256*4) FLOPs forward; backward adds the data gradients of layers 2-5 and the
 weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines in the backward pass) are not counted.
+--points N times the network at a pose list of N uniform random points of [-1, 1]^3 (flownet.flow_at, planar output: the kernels' own
+layout) instead of a grid; the --baseline is tools/fit_flow.composed_flow_at on the same list.  The FLOP counts are those of N points.
 """
 import argparse
 import json
@@ -77,9 +79,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--rounds', type=int, default=2, help='alternations of the fused and the baseline windows')
     ap.add_argument('--baseline', action='store_true')
+    ap.add_argument('--points', type=int, default=0, metavar='N', help='a pose list of N random points instead of the frames x height x width grid')
     ap.add_argument('--spatial', type=int, default=0, metavar='R', help='progressive nets: a per-point mask from an R^3 grid (0: the global mask)')
     a = ap.parse_args()
-    from fit_flow import composed_flow_fields
+    from fit_flow import composed_flow_at, composed_flow_fields
+    assert not (a.points and a.spatial), '--points: per-point masks are evaluated on grids only'
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
@@ -104,9 +108,25 @@ def main():
         target.mask[:a.k_active] = 1
         mask_dev = target.mask.to(dev)
     times = torch.linspace(0, 1, a.frames, device=dev) if a.frames > 1 else torch.zeros(1, device=dev)
-    n = a.frames * a.height * a.width
-    up = torch.randn(a.frames, 4, a.height, a.width, device=dev)
+    n = a.points if a.points else a.frames * a.height * a.width
+    up = torch.randn(a.frames, 4, a.height, a.width, device=dev) if not a.points else None
     params = list(net.parameters())
+
+    def point_paths(at, **fixed):
+        poses = (torch.rand(n, 3, generator=torch.Generator().manual_seed(1)) * 2 - 1).to(dev)
+        kw = dict(override_mask=mask_dev) if prog and at is composed_flow_at else {}
+        up_p = torch.randn(4, n, device=dev)
+        up_p = up_p if fixed else up_p.t().contiguous()          # the composed network returns (N, 4)
+
+        def fwd():
+            with torch.no_grad():
+                at(target, poses, 2.0, **kw, **fixed)
+
+        def step():
+            for p in params:
+                p.grad = None
+            at(target, poses, 2.0, **kw, **fixed).backward(up_p)
+        return fwd, step
 
     def paths(fields):
         kw = dict(override_mask=mask_dev) if prog and not a.spatial and fields is composed_flow_fields else {}
@@ -122,9 +142,14 @@ def main():
             torch.autograd.backward([f12, f21], [up[:, :2], up[:, 2:]])
         return fwd, step
 
-    todo = {'fused': paths(flownet.flow_fields)}
-    if a.baseline:
-        todo['torch'] = paths(composed_flow_fields)
+    if a.points:
+        todo = {'fused': point_paths(flownet.flow_at, planar=True)}
+        if a.baseline:
+            todo['torch'] = point_paths(composed_flow_at)
+    else:
+        todo = {'fused': paths(flownet.flow_fields)}
+        if a.baseline:
+            todo['torch'] = paths(composed_flow_fields)
     res = {k: {'forward': [], 'step': []} for k in todo}
     for _ in range(a.rounds):
         for k, (fwd, step) in todo.items():
@@ -133,7 +158,7 @@ def main():
     f_fwd, f_step = flops_siren(n) if siren else flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
     sizes = (_lib.lib().sininn_siren_saved_bytes, _lib.lib().sininn_siren_workspace_bytes) if siren else \
         (_lib.lib().sininn_flownet_saved_bytes, _lib.lib().sininn_flownet_workspace_bytes)
-    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), frames=a.frames, height=a.height, width=a.width, points=n, flop_forward=f_fwd, flop_step=f_step,
+    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(mode='points') if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=sizes[0](n), workspace_bytes=sizes[1](n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):

@@ -9,6 +9,7 @@
     python tools/fit_flow.py --net siren
     python tools/fit_flow.py --optimizer lamb
     python tools/fit_flow.py --net PRBF --controller spatial --res 7
+    python tools/fit_flow.py --net RBF --points 4096
 
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
@@ -24,6 +25,10 @@ RFF / PRFF train `encode.frequencies` as well: the optimiser gets net.parameters
 
 `siren` (flownet.siren_model_dict) is the sine network on the raw coordinates; composed, it is its five nn.Linears with
 torch.sin(30 * .) between them, model.py:145-146.
+
+`--points N` (fit_points) is the other way such a network is trained: every step draws N uniform points in [-1, 1]^3 from a seeded
+generator and fits net(poses) (flownet.flow_at, or the composed network) to the analytic flow of flowdata.SyntheticClip at those points,
+MSE and FusedAdam; no warping, no images.
 
 The pair is seeded and analytic: frame1 is a smooth texture, frame2 the same texture displaced by a known smooth flow.
 `--composed` evaluates the network with torch's own ops (nn.functional.linear and elementwise ops) instead of the fused
@@ -114,6 +119,101 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     return flows[:, :2], flows[:, 2:]
 
 
+def composed_flow_at(net, poses, scale=1.0, override_mask=None):
+    """net(poses) * scale, (N, 3) -> (N, 4), with torch's own GPU ops: composed_flow_fields on a pose list (one frame of N x 1 points
+    whose coordinates are the list), the baseline of `bench_flownet.py --points`"""
+    mask = override_mask
+    if hasattr(net, 'mask'):                                      # a linear controller
+        mask = net.mask if mask is None else mask
+        net = net.model
+    x = poses
+    if not hasattr(net, 'encode'):                                # siren
+        for layer in net.model:
+            x = torch.sin(layer.omega_0 * layer.linear(x)) if hasattr(layer, 'omega_0') else layer(x)
+        return x * scale
+    enc = net.encode
+    if hasattr(enc, 'centres'):
+        x = (x[:, None, :] - enc.centres[None, :, :]).pow(2).sum(2)
+        x = torch.exp(-(x * enc.sigma[None, :] ** 2))
+    elif hasattr(enc, 'freqs'):
+        x = torch.einsum('f,nd->nfd', enc.freqs, x)
+        x = torch.cat((torch.cos(x), torch.sin(x)), dim=2).view(x.shape[0], -1)
+    elif hasattr(enc, 'offsets'):
+        x_a = x[:, None, :] + enc.offsets[None, :]
+        x_b = x_a + (1 / enc.sigma[None, :, None])
+        x = torch.stack((x_a, x_b), dim=2)
+        x = (x % (2 / enc.sigma[None, :, None, None])) * 2 - (2 / enc.sigma[None, :, None, None])
+        x = x.pow(2).sum(3) * enc.sigma[None, :, None] ** 2
+        x = torch.exp(-x.view(-1, enc.output_channels)) * 2 - 1
+    else:
+        freq = enc.effective_frequencies() if hasattr(enc, 'magnitudes') else enc.frequencies
+        x = torch.matmul(x * 2 * math.pi, freq)
+        x = torch.stack((torch.sin(x), torch.cos(x)), dim=2).view(x.shape[0], -1)
+    if net.is_progressive:
+        x = torch.cat((poses, x), dim=-1)
+        if mask is not None:
+            x = x * mask.to(x)[None, :]
+    return net.model.model(x) * scale
+
+
+def analytic_flow(poses, h=64, w=96, frames=3):
+    """(N, 4) fp32: the ground-truth flow of flowdata.SyntheticClip(frames, h, w) as a function of continuous (t, y, x) in [-1, 1]^3,
+    in pixels: columns 0:2 the flow that carries the frame at time t onto the frame one step later (SyntheticClip.flow between its
+    frames), columns 2:4 the flow back.  s = (t + 1) / 2 is the clip's displacement factor, one step is 1 / (frames - 1).  Evaluated in
+    float64 with the clip's own fixed-point iteration."""
+    p = poses.to(torch.float64)
+    s0 = (p[:, 0] + 1) / 2
+    yy, xx = (p[:, 1] + 1) / 2 * (h - 1), (p[:, 2] + 1) / 2 * (w - 1)
+    s1 = s0 + 1.0 / (frames - 1)
+
+    def disp(x, y):
+        return 1.5 * torch.sin(y / h * math.pi) + 0.5, 1.0 * torch.cos(x / w * math.pi)
+
+    def carry(sa, sb):                                            # the frame at factor sa -> the frame at factor sb
+        u, v = disp(xx, yy)
+        px, py = xx - sa * u, yy - sa * v
+        x1, y1 = xx.clone(), yy.clone()
+        for _ in range(60):                                       # a contraction of ratio < 0.15: far below 1e-13 after 60
+            du, dv = disp(x1, y1)
+            x1, y1 = px + sb * du, py + sb * dv
+        return x1 - xx, y1 - yy
+
+    return torch.stack((*carry(s0, s1), *carry(s1, s0)), dim=1).to(torch.float32)
+
+
+def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, lr=1e-3, seed=0, device='cuda', log=None,
+               max_iteration=1000):
+    """fit net(poses) to analytic_flow at `n_points` fresh uniform points of [-1, 1]^3 per step (a seeded generator): MSE, FusedAdam.
+    Returns the list of per-step losses (floats).  `info`: a dict that receives the network (the controller of a progressive one)
+    as info['net'] and, as info['first'], the first step's `poses`, `target` and the network's `state` before that step"""
+    from sin_inn_amd import FusedAdam, flownet, progressive
+    torch.manual_seed(seed)
+    net = flownet.flow_model_dict[name](flownet.ModelParams()).to(device)
+    if net.is_progressive:
+        net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
+    opt = FusedAdam(net.parameters(), lr=lr)
+    gen = torch.Generator().manual_seed(seed + 1)
+    at = composed_flow_at if composed else flownet.flow_at
+    if info is not None:
+        info['net'] = net
+    losses = []
+    for step in range(steps):
+        poses = (torch.rand(n_points, 3, generator=gen) * 2 - 1).to(device)
+        target = analytic_flow(poses)
+        if info is not None and step == 0:
+            info['first'] = dict(poses=poses, target=target, state={k: v.detach().clone() for k, v in net.state_dict().items()})
+        opt.zero_grad()
+        loss = torch.nn.functional.mse_loss(at(net, poses, 1.0), target)
+        loss.backward()
+        opt.step()
+        net.stash_iteration(loss.detach())
+        losses.append(float(loss.detach()))
+        if log:
+            extra = f'  open {net.cur_block:3d} / {net.encoding_dim}' if net.is_progressive else ''
+            log(f'step {step:3d}  loss {losses[-1]:.6f}{extra}')
+    return losses
+
+
 def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None, max_iteration=1000,
         info=None, optimizer='adam', controller='early', res=7):
     """returns the list of per-step losses (floats); `info`: a dict that receives the network (the controller of a progressive one,
@@ -187,7 +287,12 @@ def main():
     ap.add_argument('--optimizer', default='adam', choices=['adam', 'lamb'])
     ap.add_argument('--controller', default='early', choices=['early', 'spatial'], help='progressive nets: the mask is global / per grid cell')
     ap.add_argument('--res', type=int, default=7, help='--controller spatial: cells per axis of the mask grid')
+    ap.add_argument('--points', type=int, default=0, metavar='N', help='fit net(poses) at N random points per step (fit_points) instead of a frame pair')
     a = ap.parse_args()
+    if a.points:
+        losses = fit_points(a.net, a.points, a.steps, a.composed, lr=a.lr, seed=a.seed, log=print, max_iteration=a.max_iteration)
+        print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
+        return
     losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration,
                  optimizer=a.optimizer, controller=a.controller, res=a.res)
     print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
