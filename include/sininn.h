@@ -768,12 +768,38 @@ int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* gri
  *   sininn_flownet_saved_bytes(n), sininn_flownet_workspace_bytes(n), sininn_flownet_forward_workspace_bytes(args) and
  *   sininn_flownet_encgrad_workspace_bytes(args).  Tiles, partial sums and the order of every sum depend on n alone: a pose list that
  *   spells out meshgrid(times, ys, xs) gives bitwise the flows and gradients of the grid call, two calls are bitwise equal and any valid
- *   k_active gives the same bits.  There is no gradient with respect to the coordinates.
+ *   k_active gives the same bits.  The gradient with respect to the coordinates is a call of its own, below.
  * Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse.  Not available under a spatial mask. */
 int sininn_flownet_forward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
 int sininn_flownet_backward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
 int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a,
                                            void* enc_workspace, size_t enc_workspace_bytes, void* stream);
+
+/* Gradient with respect to the coordinates (points mode, global masks): sininn_flownet_backward_posegrad_points does everything
+ * sininn_flownet_backward_points does, and with g_enc_a != NULL everything sininn_flownet_backward_encgrad_points does (the eight gradients and
+ * g_enc_a are bitwise those calls'), and also writes g_poses [n][3] fp32 (DEVICE, the layout of poses, OVERWRITTEN: it needs no
+ * initialisation), the gradient of sum(dflows * flows) with respect to poses, `scale` included:
+ *     dE[p][k]    = sum_j dh1[p][j] w[0][j][k]           (progressive: w[0][j][3 + k] * mask[3 + k], an exact zero for a closed feature)
+ *     g_poses[p][d] = sum_k dE[p][k] * d feature_k / d x_d (p)   (progressive: + mask[d] * sum_j dh1[p][j] w[0][j][d])
+ *   with the derivative of each encoding evaluated from the forward pass's own inputs, x = poses[p], d = 0 .. 2 = (t, y, x):
+ *     RBF      feature k = e_k = exp(-sigma_k^2 |x - c_k|^2):                  -2 sigma_k^2 (x_d - c_kd) e_k
+ *     Fourier  features 2 f / 2 f + 1 = sin / cos(phi), phi = 2 pi x . F[:, f]:  2 pi F[d][f] (dE_sin cos(phi) - dE_cos sin(phi)) for the pair
+ *              (fixed and learnable enc_a alike: enc_a is the matrix the call was given)
+ *     RBFG     feature e = 2 exp(-sigma^2 |u|^2) - 1, u_d the wrapped, doubled offset of the forward pass:  -4 sigma^2 u_d (e + 1); the
+ *              remainder's derivative with respect to its dividend is 1, so the gradient jumps where a coordinate wraps although e is continuous
+ *     PE       feature 6 f + d = cos(w_f x_d): -w_f sin(w_f x_d);  feature 6 f + 3 + d = sin(w_f x_d): w_f cos(w_f x_d);  its own coordinate only
+ *     ReLU gates are those the forward pass took (saved > 0).
+ *   The order of every sum is fixed and depends on nothing but the encoding: the four features of a lane in index order, the 16 lanes of a
+ *   feature group by an xor butterfly, the groups of 64 features in index order, then the coordinate column.  No atomics, nothing crosses a
+ *   tile: two calls are bitwise equal, a point's gradient does not depend on n or on its place in the list, and any valid k_active gives
+ *   the same bits.  There is no second derivative.
+ *   extra_workspace: sininn_flownet_posegrad_workspace_bytes(args, with_enc_grad) bytes, 16-byte aligned (a packed, mask-folded copy of
+ *   w[0], plus, with_enc_grad != 0, what the encgrad call needs); g_enc_a may be NULL (no frequency gradient).
+ * Refused before any launch: a null g_poses, a non-null g_enc_a for an encoding other than SININN_FLOWNET_FOURIER, a null or short
+ * extra_workspace, and everything the points calls refuse, each with a sentence under this entry point's name.  Not available under a spatial mask. */
+size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad);
+int sininn_flownet_backward_posegrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
+                                            void* extra_workspace, size_t extra_workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).
@@ -826,6 +852,10 @@ int sininn_siren_backward(const sininn_siren_args* args, void* stream);
  * grid call's flows and gradients.  Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse. */
 int sininn_siren_forward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream);
 int sininn_siren_backward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream);
+/* sininn_siren_backward_points, and also g_poses [n][3] (DEVICE, OVERWRITTEN, the layout of poses): g_poses[p][d] = sum_j dz_1[p][j] w[0][j][d],
+ * dz_1 = omega dh_1 cos(u_1), `scale` included; 256 terms in a fixed order, no atomics; the ten gradients are bitwise those of
+ * sininn_siren_backward_points.  Refused before any launch: a null g_poses and everything that call refuses. */
+int sininn_siren_backward_posegrad_points(const sininn_siren_args* args, const float* poses, int64_t n, float* g_poses, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LAMB, the optimiser of the flow trainer (video-interpolation/trainer.py:134-135: apex.optimizers.FusedLAMB(params, lr=lr)),

@@ -292,6 +292,9 @@ _SIGS = {
     'sininn_flownet_forward_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, C.c_void_p]),
     'sininn_flownet_backward_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, C.c_void_p]),
     'sininn_flownet_backward_encgrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_flownet_posegrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs), C.c_int]),
+    'sininn_flownet_backward_posegrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_siren_backward_posegrad_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, c_f, C.c_void_p]),
     'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
     'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_siren_workspace_bytes': (C.c_size_t, [C.c_int64]),

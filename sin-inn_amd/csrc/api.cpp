@@ -135,6 +135,10 @@ int flownet_forward_points_launch(const sininn_flownet_args* a, const float* pos
 int flownet_backward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st);
 int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
                                            size_t enc_workspace_bytes, hipStream_t st);
+size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad);
+int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
+                                            void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st);
+int siren_backward_posegrad_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, float* g_poses, hipStream_t st);
 int siren_supported(const sininn_siren_args* a, const char* who);
 size_t siren_saved_bytes(int64_t n);
 size_t siren_workspace_bytes(int64_t n);
@@ -623,6 +627,16 @@ int sininn_flownet_backward_points(const sininn_flownet_args* args, const float*
 int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
                                            size_t enc_workspace_bytes, void* stream) {
   return flownet_backward_encgrad_points_launch(args, poses, n, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
+}
+size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad) {
+  return flownet_posegrad_workspace_bytes(args, with_enc_grad);
+}
+int sininn_flownet_backward_posegrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
+                                            void* extra_workspace, size_t extra_workspace_bytes, void* stream) {
+  return flownet_backward_posegrad_points_launch(args, poses, n, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, ST(stream));
+}
+int sininn_siren_backward_posegrad_points(const sininn_siren_args* args, const float* poses, int64_t n, float* g_poses, void* stream) {
+  return siren_backward_posegrad_points_launch(args, poses, n, g_poses, ST(stream));
 }
 int sininn_siren_supported(const sininn_siren_args* args) { return siren_supported(args, "sininn_siren_supported"); }
 size_t sininn_siren_saved_bytes(int64_t n_points) { return siren_saved_bytes(n_points); }

@@ -59,6 +59,10 @@
 //           tiles, `saved`, workspaces and the order of every sum depend on N alone, so a pose list that spells out a grid gives the grid
 //           call's bits.  Not combined with the spatial mode.
 //
+// pose gradient (sininn_flownet_backward_posegrad_points) after the whole backward of a points call: flownet_posegrad_kernel contracts
+//           dE = dh1 W1 (the GEMM of the frequency gradient, for every encoding) with the analytic derivative of the encoding over the
+//           FEATURES of each point: g_poses [N][3].  A tile owns its points: no partial sums in memory, no atomics, a fixed order.  DESIGN 14.8
+//
 // positional encoding (PE / PPE, PEModel model.py:472-487, PPEModel model.py:607-611): layer 1 has LIVE (LIVE + 3) inputs, fewer than
 //           its padded K width KW; features LIVE .. KW - 1 are exact zeros from encode4.  Plain PE reads W1 [256][LIVE] in place (96-byte
 //           rows, the 16-byte loads of columns LIVE .. KW - 1 are replaced by zeros), two K steps; PPE packs mask * W1 into [256][KW] +
@@ -938,6 +942,240 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_sample_mask_kernel(FlowNetDev
   }
 }
 
+// ---- gradient with respect to the coordinates (points mode): g_poses[p][d] = sum_k dE[p][k] m_k dz_k / dx_d (p) ----
+// dE = dh1 W1 is the data-gradient GEMM of flownet_encgrad_kernel, for every encoding, in passes of 256 feature columns; what differs is
+// the contraction: over the FEATURES of a point, not over the points of a feature.  A tile owns its points, so nothing crosses blocks.
+// Column c of a pass is CHOSEN so that a lane owns four consecutive features, the unit of encode4: wave c / 64, accumulator column block
+// n = (c / 16) % 4, lane li = c % 16 holds feature 256 pass + 64 wave + 4 li + n.
+constexpr int FN_PG_ROW = 4;        // floats per point of a slot of partial sums in LDS: d = 0 .. 2 and a pad
+template <int KIND> constexpr int posegrad_passes() { return (Enc<KIND>::KW + FN_HID - 1) / FN_HID; }
+template <int KIND> constexpr size_t posegrad_pack_floats() { return (size_t)(posegrad_passes<KIND>() * FN_HID + FN_CS) * FN_HID; }
+template <int KIND> constexpr size_t posegrad_lds() { return FN_LDS + (size_t)(posegrad_passes<KIND>() * 4 * FN_P * FN_PG_ROW) * sizeof(float); }
+
+// wt[c][j] = w1[j][feature of row c] for the rows of every pass (progressive: column 3 + feature, times its mask, an exact zero where the
+// mask is zero; a feature from LIVE on: zero), then four rows of the coordinate columns, wt[NP 256 + d][j] = w1[j][d] (progressive, d < 3;
+// else zero): their mask multiplies the finished sum.  block = row c; <E::LIVE, E::KW>: encodings of one shape share one kernel
+template <int LIVE, int KW>
+__global__ __launch_bounds__(FN_NTHR) void flownet_posegrad_pack_kernel(const float* w1, const float* mask, float* wt, int prog) {
+  constexpr int ROWS = (KW + FN_HID - 1) / FN_HID * FN_HID;
+  const int c = blockIdx.x, j = threadIdx.x;
+  const float* row = w1 + (size_t)j * (LIVE + (prog ? FN_DOM : 0));
+  float v = 0.f;
+  if (c >= ROWS) {
+    if (prog && c - ROWS < FN_DOM) v = row[c - ROWS];
+  } else {
+    const int k = (c & ~63) + 4 * (c & 15) + ((c >> 4) & 3);
+    if (k < LIVE) {
+      if (prog) {
+        const float m = mask[FN_DOM + k];
+        v = m == 0.f ? 0.f : row[FN_DOM + k] * m;
+      } else {
+        v = row[k];
+      }
+    }
+  }
+  wt[(size_t)c * FN_HID + j] = v;
+}
+
+// the constants of features f0 .. f0 + 3 (f0 % 4 == 0), loaded once per pass, and the derivative of encode4 at one point:
+// grad(c, dz, g): g[d] += sum_j dz[j] d feature_{f0 + j} / d x_d, j in index order.  The inputs and the operations up to the feature are
+// encode4's; every sum is an explicit fmaf, so each unrolled copy (each row of a tile) rounds the same way
+template <int KIND>
+struct FeatureGrad4 {
+  float par[16];
+  int f0;
+  __device__ __forceinline__ FeatureGrad4(const FlowNetDev& q, int f0_) : f0(f0_) {
+    if constexpr (KIND == SININN_FLOWNET_RBF) {          // centres [4][3], sigma^2 [4]
+      const f32x4* cp = reinterpret_cast<const f32x4*>(q.enc_a + 3 * f0);
+      const f32x4 c0 = cp[0], c1 = cp[1], c2 = cp[2];
+      const f32x4 sg = *reinterpret_cast<const f32x4*>(q.enc_b + f0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        par[i] = c0[i]; par[4 + i] = c1[i]; par[8 + i] = c2[i];
+        par[12 + i] = sg[i] * sg[i];
+      }
+    } else if constexpr (KIND == SININN_FLOWNET_RBFG) {  // offsets [2][3], sigma [2]
+      const int f = f0 >> 1;
+      const f32x2* op = reinterpret_cast<const f32x2*>(q.enc_a + 3 * f);
+      const f32x2 o0 = op[0], o1 = op[1], o2 = op[2];
+      const f32x2 sg = *reinterpret_cast<const f32x2*>(q.enc_b + f);
+      par[0] = o0[0]; par[1] = o0[1]; par[2] = o1[0]; par[3] = o1[1]; par[4] = o2[0]; par[5] = o2[1];
+      par[6] = sg[0]; par[7] = sg[1];
+    } else if constexpr (KIND == SININN_FLOWNET_PE) {    // the frequency of each of the four features
+#pragma unroll
+      for (int j = 0; j < 4; ++j) par[j] = f0 + j < Enc<KIND>::LIVE ? q.enc_a[(f0 + j) / 6] : 0.f;
+    } else {                                             // frequencies [3][2]
+      const int f = f0 >> 1;
+      const f32x2 fa = *reinterpret_cast<const f32x2*>(q.enc_a + f);
+      const f32x2 fb = *reinterpret_cast<const f32x2*>(q.enc_a + 256 + f);
+      const f32x2 fc = *reinterpret_cast<const f32x2*>(q.enc_a + 512 + f);
+      par[0] = fa[0]; par[1] = fb[0]; par[2] = fc[0]; par[3] = fa[1]; par[4] = fb[1]; par[5] = fc[1];
+    }
+  }
+
+  __device__ __forceinline__ void grad(const Coord c, const float (&dz)[4], float (&g)[FN_DOM]) const {
+#pragma clang fp contract(off)
+    if constexpr (KIND == SININN_FLOWNET_RBF) {          // d e / d x_d = -2 sigma^2 (x_d - c_d) e
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float dt = c.t - par[3 * j], dy = c.y - par[3 * j + 1], dx = c.x - par[3 * j + 2];
+        const float d = fmaf(dx, dx, fmaf(dy, dy, dt * dt));
+        const float t = dz[j] * ((-2.f * par[12 + j]) * expf(-(d * par[12 + j])));
+        g[0] = fmaf(t, dt, g[0]);
+        g[1] = fmaf(t, dy, g[1]);
+        g[2] = fmaf(t, dx, g[2]);
+      }
+    } else if constexpr (KIND == SININN_FLOWNET_RBFG) {  // d e / d x_d = -4 sigma^2 u_d (e + 1): d u_d / d x_d = 2, the remainder's slope is 1
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float sg = par[6 + u];
+        const float is = 1.f / sg, p = 2.f * is, hp = 0.5f * sg, s2 = sg * sg;
+        const float xa[3] = {c.t + par[3 * u], c.y + par[3 * u + 1], c.x + par[3 * u + 2]};
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+          float w[3];
+#pragma unroll
+          for (int d = 0; d < 3; ++d) {
+            const float x = v ? xa[d] + is : xa[d];
+            const float r = fmaf(-floorf(x * hp), p, x);
+            w[d] = fmaf(r, 2.f, -p);
+          }
+          const float d = fmaf(w[2], w[2], fmaf(w[1], w[1], w[0] * w[0]));
+          const float t = dz[2 * u + v] * ((-4.f * s2) * (expf(-(d * s2)) * 2.f));
+          g[0] = fmaf(t, w[0], g[0]);
+          g[1] = fmaf(t, w[1], g[1]);
+          g[2] = fmaf(t, w[2], g[2]);
+        }
+      }
+    } else if constexpr (KIND == SININN_FLOWNET_PE) {    // feature 6 f + d: -w sin(w x_d), 6 f + 3 + d: w cos(w x_d); its own coordinate only
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = f0 + j;
+        const int r = k % 6, d = r < 3 ? r : r - 3;
+        const float xd = d == 0 ? c.t : d == 1 ? c.y : c.x;
+        float sn, co;
+        sincosf(__fmul_rn(par[j], xd), &sn, &co);
+        const float t = dz[j] * (r < 3 ? -(par[j] * sn) : par[j] * co);   // par = 0 beyond LIVE: an exact zero
+        g[0] = d == 0 ? g[0] + t : g[0];
+        g[1] = d == 1 ? g[1] + t : g[1];
+        g[2] = d == 2 ? g[2] + t : g[2];
+      }
+    } else {                                             // 2 pi F[d][f] (dz_sin cos(phi) - dz_cos sin(phi))
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        float s, co;
+        fourier_sincos(c, par[3 * u], par[3 * u + 1], par[3 * u + 2], s, co);
+        const float t = FN_TWO_PI * fmaf(dz[2 * u], co, -(dz[2 * u + 1] * s));
+        g[0] = fmaf(t, par[3 * u], g[0]);
+        g[1] = fmaf(t, par[3 * u + 1], g[1]);
+        g[2] = fmaf(t, par[3 * u + 2], g[2]);
+      }
+    }
+  }
+};
+
+// one step of the xor butterfly over the 16 column lanes: the lanes of a pair split the N values, each keeps one half and adds the
+// partner's share of it; after the steps 1, 2, 4, 8 a lane holds the three sums of ONE point
+template <int N, int B>
+__device__ __forceinline__ void butterfly_step(float (&v)[16 * FN_DOM], int li) {
+  const bool up = (li & B) != 0;
+#pragma unroll
+  for (int i = 0; i < N / 2; ++i) {
+    const float send = up ? v[i] : v[i + N / 2], keep = up ? v[i + N / 2] : v[i];
+    v[i] = keep + __shfl_xor(send, B);
+  }
+}
+
+// wt: flownet_posegrad_pack_kernel's matrix; mask: the global mask (PROG) for the coordinate columns; kopen: encoded features in front of
+// the last open one (not PROG: all), a wave whose 64 columns lie beyond it skips its GEMM and contributes exact zeros.
+// The order of every sum is fixed: a lane's four columns in index order (fmaf), the 16 lanes by the butterfly, then the slots
+// (pass, wave) in index order, then (PROG) m_d times the coordinate column's sum.  Rows p >= N are not written
+template <int KIND, bool PROG>
+__global__ __launch_bounds__(FN_NTHR, 2) void flownet_posegrad_kernel(FlowNetDev q, const float* wt, const float* mask, float* g_poses,
+                                                                     int kopen) {
+  constexpr int NP = posegrad_passes<KIND>();
+  extern __shared__ __attribute__((aligned(16))) float fn_smem[];
+  float* const hs = fn_smem;                           // [64][FN_HS]: dh1 tile
+  float* const cs = fn_smem + FN_P * FN_HS;            // [64][4]: coordinates of the tile's points
+  float* const red = cs + FN_P * FN_CS;                // [NP * 4][64][FN_PG_ROW]: a wave's sums of a pass
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, kq = lane >> 4;
+  const int cw = wave * 64;
+  // the point whose sums this lane holds after the butterfly: bit b of li chose the upper half at step b
+  const int pt = ((li & 1) << 3) | ((li & 2) << 1) | ((li & 4) >> 1) | ((li & 8) >> 3);
+  const int prow = 16 * (pt >> 2) + 4 * kq + (pt & 3);
+
+  for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
+    __syncthreads();                                   // the previous tile is done with hs / cs / red
+#pragma unroll 4
+    for (int u = 0; u < FN_P * FN_HID / 4 / FN_NTHR; ++u) {
+      const int f = tid + FN_NTHR * u;
+      const int row = f >> 6, c4 = (f & 63) * 4;
+      *reinterpret_cast<f32x4*>(hs + row * FN_HS + c4) = *reinterpret_cast<const f32x4*>(q.dh + ((size_t)tile * FN_P + row) * FN_HID + c4);
+    }
+    if (tid < FN_P) stage_coord(q, cs, tile, tid);
+    __syncthreads();
+    // ---- the coordinate columns on the vector ALU: thread = (coordinate tid / 64, point tid % 64) ----
+    float csum = 0.f;
+    if constexpr (PROG) {
+      if (wave < FN_DOM) {
+        const float* wc = wt + (size_t)(NP * FN_HID + wave) * FN_HID;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < FN_HID; k += 4) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hs + lane * FN_HS + k);
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(wc + k);
+          a0 = fmaf(h[0], wv[0], a0);
+          a1 = fmaf(h[1], wv[1], a1);
+          a2 = fmaf(h[2], wv[2], a2);
+          a3 = fmaf(h[3], wv[3], a3);
+        }
+        csum = (a0 + a1) + (a2 + a3);
+      }
+    }
+    // ---- the encoded features: 256 columns per pass, 64 per wave ----
+#pragma unroll
+    for (int ps = 0; ps < NP; ++ps) {
+      const int k0 = ps * FN_HID + cw;
+      float v[16 * FN_DOM];
+#pragma unroll
+      for (int i = 0; i < 16 * FN_DOM; ++i) v[i] = 0.f;
+      if (k0 < kopen) {                                // wave-uniform; no barrier inside
+        f32x4 acc[4][4];
+        zero_acc(acc);
+        gemm_lds(hs, wt + (size_t)ps * FN_HID * FN_HID, cw, li, kq, acc);
+        const FeatureGrad4<KIND> fg(q, k0 + 4 * li);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const f32x4 c = *reinterpret_cast<const f32x4*>(cs + (16 * m + 4 * kq + r) * FN_CS);
+            const float dz[4] = {acc[m][0][r], acc[m][1][r], acc[m][2][r], acc[m][3][r]};
+            float g[FN_DOM] = {0.f, 0.f, 0.f};
+            fg.grad(Coord{c[0], c[1], c[2]}, dz, g);
+#pragma unroll
+            for (int d = 0; d < FN_DOM; ++d) v[(4 * m + r) * FN_DOM + d] = g[d];
+          }
+        butterfly_step<48, 1>(v, li);
+        butterfly_step<24, 2>(v, li);
+        butterfly_step<12, 4>(v, li);
+        butterfly_step<6, 8>(v, li);
+      }
+      *reinterpret_cast<f32x4*>(red + ((size_t)(ps * 4 + wave) * FN_P + prow) * FN_PG_ROW) = (f32x4){v[0], v[1], v[2], 0.f};
+    }
+    __syncthreads();
+    const int p = tile * FN_P + lane;
+    if (wave < FN_DOM && p < q.N) {
+      float s = 0.f;
+#pragma unroll
+      for (int u = 0; u < NP * 4; ++u) s += red[(u * FN_P + lane) * FN_PG_ROW + wave];
+      if constexpr (PROG) s += mul_rn(mask[wave], csum);
+      g_poses[(size_t)p * FN_DOM + wave] = s;
+    }
+  }
+}
+
 int wgrad_chunks(int ntiles, int kf) {
   const int want = FN_CHUNK_ELEMS / kf;                // 128 chunks x 4 output tiles, 64 x 8 (narrow: 256 x 2) for layer 1
   return ntiles < want ? ntiles : want;
@@ -1128,11 +1366,13 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
 
 // g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
 // spatial != nullptr: layer 1 under the per-point mask of that grid.  pl != nullptr: at that pose list.  The entry point has called check_head
+// who != nullptr: the name every refusal is made under (the posegrad call), else the names the backward calls have always used.
+// out_q != nullptr: receives the kernels' descriptor of the call (dh1 is slot 0 of q.dh) for a kernel the caller launches after these
 static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial,
-                           const PoseList* pl = nullptr) {
+                           const PoseList* pl = nullptr, const char* who = nullptr, FlowNetDev* out_q = nullptr) {
   FlowNetDev q;
-  if (int rc = fill_args(a, spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl)) return rc;
-  if (int rc = check_backward_buffers<4>(a, pl ? "flownet_backward_points" : "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q))
+  if (int rc = fill_args(a, who ? who : spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl)) return rc;
+  if (int rc = check_backward_buffers<4>(a, who ? who : pl ? "flownet_backward_points" : "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q))
     return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
@@ -1170,6 +1410,7 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
                        fopen, g_enc_a);
     SININN_LAUNCH_CHECK("flownet_reduce_enc");
   }
+  if (out_q) *out_q = q;
   return 0;
 }
 
@@ -1284,6 +1525,53 @@ int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const f
                                            size_t enc_workspace_bytes, hipStream_t st) {
   const PoseList pl{poses, n};
   return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, nullptr, &pl);
+}
+
+// ---- points mode with the gradient of the coordinates.  extra workspace: the packed W1 of flownet_posegrad_pack_kernel, then (with the
+// frequency gradient) the workspace of the encgrad call ----
+static size_t posegrad_pack_bytes(const sininn_flownet_args* a) {
+  return for_kind(a->encoding, (size_t)0, [](auto k) { return posegrad_pack_floats<decltype(k)::value>() * sizeof(float); });
+}
+
+size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad) {
+  if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
+  const size_t pack = posegrad_pack_bytes(a);
+  return pack ? pack + (with_enc_grad ? flownet_encgrad_workspace_bytes(a) : 0) : 0;
+}
+
+template <int KIND, bool PROG>
+static int posegrad_kind_launch(const sininn_flownet_args* a, const FlowNetDev& q, float* wt, float* g_poses, hipStream_t st) {
+  using E = Enc<KIND>;
+  constexpr int NP = posegrad_passes<KIND>();
+  constexpr size_t lds = posegrad_lds<KIND>();
+  hipLaunchKernelGGL((flownet_posegrad_pack_kernel<E::LIVE, E::KW>), dim3(NP * FN_HID + FN_CS), dim3(FN_NTHR), 0, st, a->w[0],
+                     PROG ? a->mask : (const float*)nullptr, wt, PROG ? 1 : 0);
+  SININN_LAUNCH_CHECK("flownet_posegrad_pack");
+  auto k = flownet_posegrad_kernel<KIND, PROG>;
+  if (raise_lds(k, lds, "flownet_posegrad")) return 1;
+  hipLaunchKernelGGL(k, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), lds, st, q, (const float*)wt, PROG ? a->mask : (const float*)nullptr, g_poses,
+                     PROG ? open_encoded(a) : E::KW);
+  SININN_LAUNCH_CHECK("flownet_posegrad");
+  return 0;
+}
+
+int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
+                                            void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st) {
+  const char* who = "flownet_backward_posegrad_points";
+  const PoseList pl{poses, n};
+  if (int rc = check_head(a, who, nullptr)) return rc;
+  SININN_CHECK(g_poses != nullptr, "%s: null g_poses", who);
+  SININN_CHECK(g_enc_a == nullptr || flownet_encgrad_workspace_bytes(a) != 0,
+               "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only (pass a null g_enc_a)", who, a->encoding);
+  const size_t need = flownet_posegrad_workspace_bytes(a, g_enc_a != nullptr);
+  SININN_CHECK(extra_workspace != nullptr && extra_workspace_bytes >= need, "%s: extra_workspace holds %zu bytes, %zu needed", who,
+               extra_workspace ? extra_workspace_bytes : (size_t)0, need);
+  SININN_CHECK(aligned16(extra_workspace), "%s: extra_workspace must be 16-byte aligned", who);
+  float* const wt = static_cast<float*>(extra_workspace);
+  float* const enc_ws = g_enc_a ? wt + posegrad_pack_bytes(a) / sizeof(float) : nullptr;
+  FlowNetDev q;                                        // every check is backward_launch's, made before its first launch
+  if (int rc = backward_launch(a, g_enc_a, enc_ws, st, nullptr, &pl, who, &q)) return rc;
+  return for_mode(a, false, [&](auto k, auto prog, auto) { return posegrad_kind_launch<decltype(k)::value, decltype(prog)::value>(a, q, wt, g_poses, st); });
 }
 
 }  // namespace sininn

@@ -26,6 +26,8 @@
 //           they changed the instructions, or the placement, of these kernels.
 // points    (sininn_siren_*_points) point_coord reads row p of a caller's pose list [N][3] instead of the axis vectors; T = H = 1, W = N makes
 //           flows / dflows the planar [4][N].  The same kernels, nothing else differs (see flownet.hip)
+// pose gradient (sininn_siren_backward_posegrad_points) siren_bwd_chain_kernel<true> also writes g_poses[p][d] = sum_j dz_1[p][j] W1[j][d] from the
+//           dz_1 tile it holds at the end of a tile; <false> is the kernel as it was, instruction for instruction
 // Rows of the last tile beyond N are computed on a clamped point in the forward pass and carry dout = 0 in the backward pass, so every
 // saved / workspace row is written before it is read and contributes exact zeros to every sum.
 #include "flownet_tile.h"
@@ -58,6 +60,11 @@ struct SirenDev {
   float* hin;              // [3][ntiles * 64][256]: h_1 .. h_3
   const float* wt;         // W2^T, W3^T, W4^T
   float* part;
+};
+
+// the descriptor of the chain kernel that also writes the gradient of the coordinates
+struct SirenPoseDev : SirenDev {
+  float* g_poses;          // [N][3]
 };
 
 // acc = W1 (t, y, x) for the tile's points: one K group, k = kq: t, y, x, 0
@@ -148,7 +155,11 @@ __global__ __launch_bounds__(FN_NTHR) void siren_transpose_kernel(const float* w
   out[k * FN_HID + j] = in[j * FN_HID + k];
 }
 
-__global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(SirenDev q) {
+// POSEGRAD: also g_poses[p][d] = sum_j dz_1[p][j] W1[j][d] from the dz_1 tile (dz_1 = omega v, v the gradient of the layer-1 phase):
+// thread = (coordinate tid / 64, point tid % 64), four strided partial sums of 64 terms each, (a0 + a1) + (a2 + a3); rows p >= N are
+// not written.  Not POSEGRAD: the kernel as it has always been
+template <bool POSEGRAD>
+__global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(std::conditional_t<POSEGRAD, SirenPoseDev, SirenDev> q) {
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;
   float* const dos = fn_smem + FN_P * FN_HS;           // [64][4]: dout of the tile
@@ -252,6 +263,22 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(SirenDev q)
       gw1[1] += sy;
       gw1[2] += sx;
     }
+    if constexpr (POSEGRAD) {
+      const int d = tid >> 6, pl = tid & 63;
+      const int p = tile * FN_P + pl;
+      if (d < SR_IN && p < q.N) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 8
+        for (int k = 0; k < FN_HID; k += 4) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hs + pl * FN_HS + k);
+          a0 = fmaf(h[0], q.w[0][k * SR_IN + d], a0);
+          a1 = fmaf(h[1], q.w[0][(k + 1) * SR_IN + d], a1);
+          a2 = fmaf(h[2], q.w[0][(k + 2) * SR_IN + d], a2);
+          a3 = fmaf(h[3], q.w[0][(k + 3) * SR_IN + d], a3);
+        }
+        q.g_poses[(size_t)p * SR_IN + d] = (a0 + a1) + (a2 + a3);
+      }
+    }
   }
   float* const out = q.part + (size_t)blockIdx.x * SR_PART;
 #pragma unroll
@@ -329,10 +356,12 @@ static int forward_launch(const sininn_siren_args* a, hipStream_t st, const Pose
   return 0;
 }
 
-static int backward_launch(const sininn_siren_args* a, hipStream_t st, const PoseList* pl) {
-  SirenDev q;
-  const char* who = pl ? "siren_backward_points" : "siren_backward";
+// g_poses != nullptr (with a pose list): the chain kernel that also writes the gradient of the coordinates; everything else is the same
+static int backward_launch(const sininn_siren_args* a, hipStream_t st, const PoseList* pl, float* g_poses = nullptr) {
+  SirenPoseDev q;
+  const char* who = g_poses ? "siren_backward_posegrad_points" : pl ? "siren_backward_points" : "siren_backward";
   if (int rc = check_args(a, who, q, pl)) return rc;
+  q.g_poses = g_poses;
   if (int rc = check_backward_buffers<SR_SINES + 1>(a, who, siren_saved_bytes(q.N), siren_workspace_bytes(q.N), q)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
@@ -344,9 +373,14 @@ static int backward_launch(const sininn_siren_args* a, hipStream_t st, const Pos
 
   hipLaunchKernelGGL(siren_transpose_kernel, dim3(FN_HID, SR_SINES - 1), dim3(FN_NTHR), 0, st, a->w[1], a->w[2], a->w[3], wt);
   SININN_LAUNCH_CHECK("siren_transpose");
-  if (raise_lds(siren_bwd_chain_kernel, SR_LDS, "siren_backward")) return 1;
   const int cb = chain_blocks(q.ntiles);
-  hipLaunchKernelGGL(siren_bwd_chain_kernel, dim3(cb), dim3(FN_NTHR), SR_LDS, st, q);
+  if (g_poses) {
+    if (raise_lds(siren_bwd_chain_kernel<true>, SR_LDS, "siren_backward")) return 1;
+    hipLaunchKernelGGL(siren_bwd_chain_kernel<true>, dim3(cb), dim3(FN_NTHR), SR_LDS, st, q);
+  } else {
+    if (raise_lds(siren_bwd_chain_kernel<false>, SR_LDS, "siren_backward")) return 1;
+    hipLaunchKernelGGL(siren_bwd_chain_kernel<false>, dim3(cb), dim3(FN_NTHR), SR_LDS, st, static_cast<const SirenDev&>(q));
+  }
   SININN_LAUNCH_CHECK("siren_bwd_chain");
   hipLaunchKernelGGL(siren_reduce_kernel, dim3((SR_PART + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, (const float*)q.part, cb, a->gw[0], a->gb[0],
                      a->gw[SR_SINES], a->gb[SR_SINES]);
@@ -368,6 +402,12 @@ int siren_forward_points_launch(const sininn_siren_args* a, const float* poses, 
 int siren_backward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st) {
   const PoseList pl{poses, n};
   return backward_launch(a, st, &pl);
+}
+
+int siren_backward_posegrad_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, float* g_poses, hipStream_t st) {
+  SININN_CHECK(g_poses != nullptr, "siren_backward_posegrad_points: null g_poses");
+  const PoseList pl{poses, n};
+  return backward_launch(a, st, &pl, g_poses);
 }
 
 }  // namespace sininn

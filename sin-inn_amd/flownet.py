@@ -73,7 +73,9 @@ evaluate the same kernels at a caller's pose list (..., 3) -> (..., 4) (`sininn_
 read point p's coordinates from row p of the list where the grid mode reads the three axis vectors, and nothing else differs, so the
 flows and gradients of a list that spells out a grid are bitwise those of the grid call.  The kernels write the planar (4, N) layout
 (`planar=True` returns it); the transpose to the reference's (N, 4) is a torch op.  Differentiable with respect to the parameters
-(`_FlowAt`, next to `_FlowFields`), learnable frequencies included; there is no gradient with respect to the coordinates.  Per-point
+(`_FlowAt`, next to `_FlowFields`), learnable frequencies included, and, with `pose_grad=True`, with respect to the coordinates: the
+backward pass then is `sininn_flownet_backward_posegrad_points` / `sininn_siren_backward_posegrad_points`, which contract dh1 W1 with the
+analytic derivative of the encoding over the features of each point (csrc/flownet.hip, flownet_posegrad_kernel).  Per-point
 masks (a `StashedSpatialController`, a grid as `override_mask`) are not evaluated at pose lists.
 
 Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
@@ -313,7 +315,7 @@ class _EncodedMlpModel(nn.Module):
 
     def forward(self, x, *args, **kwargs):
         """net(poses), model.py:97-103: (..., 3) -> (..., 4) in the fused kernels (`flow_at`)"""
-        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'))
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False))
 
 
 class ProgressiveModel(_EncodedMlpModel):
@@ -431,7 +433,7 @@ class SirenModel(nn.Module):
 
     def forward(self, x, *args, **kwargs):
         """net(poses), model.py:167-171: (..., 3) -> (..., 4) in the fused kernels (`flow_at`)"""
-        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'))
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False))
 
 
 siren_model_dict = {'siren': SirenModel}                          # beside all_model_dict: the command line does not open it yet
@@ -560,9 +562,10 @@ def _forward(a, train, saved, saved_shape, call, *extra):
     return flows, saved
 
 
-def _backward(a, net, dflows, saved, workspace, workspace_bytes, call, *extra, enc_call=None, enc_workspace=None, g_enc_a=None):
-    """check dflows, allocate the workspace (`workspace_bytes(N)`) and the gradients, call; `enc_call`: the entry point that also
-    returns the frequency gradient, ([gW1, ..], gF) then"""
+def _backward_buffers(a, net, dflows, saved, workspace, workspace_bytes):
+    """check dflows, allocate the workspace (`workspace_bytes(N)`) and the gradients into the descriptor.  Returns ([gW1, gb1, ..], keep):
+    `keep` holds the tensors the descriptor points into (the contiguous dflows, the workspace); the caller keeps it until the library call
+    has been made, so that nothing it allocates in between lands in their memory"""
     _on_gpu(dflows)
     dflows = dflows.contiguous()
     assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
@@ -576,13 +579,26 @@ def _backward(a, net, dflows, saved, workspace, workspace_bytes, call, *extra, e
         gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
         a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
         grads += [gw, gb]
+    return grads, (dflows, workspace)
+
+
+def _out_tensor(given, shape, device):
+    """a caller's output tensor of that shape (contiguous fp32 on the GPU), or a new one"""
+    t = torch.empty(shape, device=device, dtype=torch.float32) if given is None else given
+    assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == tuple(shape)
+    return t
+
+
+def _backward(a, net, dflows, saved, workspace, workspace_bytes, call, *extra, enc_call=None, enc_workspace=None, g_enc_a=None):
+    """the backward half: `_backward_buffers`, then `call`; `enc_call`: the entry point that also returns the frequency gradient,
+    ([gW1, ..], gF) then"""
+    grads, keep = _backward_buffers(a, net, dflows, saved, workspace, workspace_bytes)  # noqa: F841 (keep: alive until the call is made)
     if enc_call is None:
         check(call(C.byref(a), *extra, _stream()))
         return grads
     if enc_workspace is None:
         enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
-    g_enc = torch.empty(3, 256, device=a._device, dtype=torch.float32) if g_enc_a is None else g_enc_a
-    assert g_enc.is_cuda and g_enc.is_contiguous() and g_enc.dtype == torch.float32 and tuple(g_enc.shape) == (3, 256)
+    g_enc = _out_tensor(g_enc_a, (3, 256), a._device)
     check(enc_call(C.byref(a), *extra, ptr(g_enc), ptr(enc_workspace), enc_workspace.numel() * 4, _stream()))
     return grads, g_enc
 
@@ -671,9 +687,25 @@ def flownet_forward_points(net, poses, scale, train, saved=None, mask=None, k_ac
 
 
 def flownet_backward_points(net, poses, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
-                            enc_workspace=None, g_enc_a=None):
-    """flownet_backward at the pose list of the forward call, dflows (4, N); everything else as there"""
+                            enc_workspace=None, g_enc_a=None, pose_grad=False, pose_workspace=None, g_poses=None):
+    """flownet_backward at the pose list of the forward call, dflows (4, N); everything else as there.  `pose_grad=True` returns
+    (what the call returns without it, g_poses): g_poses (N, 3), the gradient with respect to the coordinates, from
+    sininn_flownet_backward_posegrad_points, which computes everything else as well (bitwise the same); `pose_workspace`: optional fp32
+    tensor of sininn_flownet_posegrad_workspace_bytes bytes (it holds the frequency gradient's workspace too: `enc_workspace` is refused),
+    `g_poses`: optional (N, 3) fp32 tensor that receives the gradient"""
     a = _args(net, poses, None, None, scale, mask, k_active, enc_a)
+    if pose_grad:
+        assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
+        lib = _lib.lib()
+        grads, keep = _backward_buffers(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, lib.sininn_flownet_workspace_bytes)  # noqa: F841
+        g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
+        g_enc = _out_tensor(g_enc_a, (3, 256), a._device) if enc_grad else None
+        if pose_workspace is None:
+            nbytes = lib.sininn_flownet_posegrad_workspace_bytes(C.byref(a), int(enc_grad))
+            pose_workspace = torch.empty(nbytes // 4, device=a._device, dtype=torch.float32)
+        check(lib.sininn_flownet_backward_posegrad_points(C.byref(a), *a._poses, ptr(g_poses), ptr(g_enc), ptr(pose_workspace),
+                                                          pose_workspace.numel() * 4, _stream()))
+        return ((grads, g_enc) if enc_grad else grads), g_poses
     return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
                      _lib.lib().sininn_flownet_backward_points, *a._poses,
                      enc_call=_lib.lib().sininn_flownet_backward_encgrad_points if enc_grad else None, enc_workspace=enc_workspace,
@@ -688,9 +720,16 @@ def siren_forward_points(net, poses, scale, train, saved=None, omega=None):
     return flows.view(4, -1), saved
 
 
-def siren_backward_points(net, poses, scale, dflows, saved, workspace=None, omega=None):
-    """siren_backward at the pose list of the forward call, dflows (4, N)"""
+def siren_backward_points(net, poses, scale, dflows, saved, workspace=None, omega=None, pose_grad=False, g_poses=None):
+    """siren_backward at the pose list of the forward call, dflows (4, N).  `pose_grad=True` returns (the gradients, g_poses (N, 3)),
+    from sininn_siren_backward_posegrad_points"""
     a = _siren_args(net, poses, None, None, scale, omega)
+    if pose_grad:
+        lib = _lib.lib()
+        grads, keep = _backward_buffers(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, lib.sininn_siren_workspace_bytes)  # noqa: F841
+        g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
+        check(lib.sininn_siren_backward_posegrad_points(C.byref(a), *a._poses, ptr(g_poses), _stream()))
+        return grads, g_poses
     return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_siren_workspace_bytes,
                      _lib.lib().sininn_siren_backward_points, *a._poses)
 
@@ -742,10 +781,11 @@ class _SirenFields:
 
 
 class _FlowAt(torch.autograd.Function):
-    """`_FlowFields` at a pose list: flows (4, N).  The poses get no gradient"""
+    """`_FlowFields` at a pose list: flows (4, N).  `pose_grad` and poses that require it: the backward pass is the posegrad call and
+    returns the gradient of the coordinates as well.  Once differentiable: the gradients come from kernels, a double backward raises"""
 
     @staticmethod
-    def forward(ctx, net, poses, scale, train, mask, enc_a, *params):
+    def forward(ctx, net, poses, scale, train, mask, enc_a, pose_grad, *params):
         if enc_a is not None:
             enc_a = enc_a.detach().contiguous()
         if isinstance(net, SirenModel):
@@ -757,17 +797,22 @@ class _FlowAt(torch.autograd.Function):
         ctx.net, ctx.poses, ctx.scale, ctx.saved = net, poses, scale, saved
         if enc_a is not None and ctx.needs_input_grad[5]:
             ctx.kw['enc_grad'] = True
+        if pose_grad and ctx.needs_input_grad[1]:
+            ctx.kw['pose_grad'] = True
         return flows
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, dflows):
         if ctx.saved is None:
             raise RuntimeError('flow_at: backward through an inference-mode forward')
-        grads, g_enc = ctx.backward_fn(ctx.net, ctx.poses, ctx.scale, dflows, ctx.saved, **ctx.kw), None
+        grads, g_enc, g_poses = ctx.backward_fn(ctx.net, ctx.poses, ctx.scale, dflows, ctx.saved, **ctx.kw), None, None
+        if ctx.kw.get('pose_grad'):
+            grads, g_poses = grads
         if ctx.kw.get('enc_grad'):
             grads, g_enc = grads
         ctx.saved = None
-        return (None,) * 5 + (g_enc,) + tuple(grads)
+        return (None, g_poses, None, None, None, g_enc, None) + tuple(grads)
 
 
 def grid_axes(net, times, h, w):
@@ -850,21 +895,24 @@ def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
     return flows[:, :2], flows[:, 2:]
 
 
-def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=False):
+def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=False, pose_grad=False):
     """net(poses) * scale (trainer.py:43-44, progressive_controller.py:45-53) at arbitrary points: `poses` (..., 3) fp32 on the GPU,
     columns (t, y, x) -> (..., 4), contiguous.  `net`: what flow_fields takes, a model or a LinearController / LinearControllerEarly
     around a progressive one; `override_mask` (515 values, PPE: 27) replaces the controller's mask.  The kernels read the list in place
     and write the planar (4, N) layout; `planar=True` returns that tensor, without the transpose to the reference's layout.
     Differentiable with respect to the parameters (and `encode.frequencies` of RFF / PRFF); under torch.no_grad() (or with no trainable
     parameter) the inference mode runs and nothing is saved.  `get_mask=True` returns (out, the mask in use on the device).
-    There is no gradient with respect to the coordinates: poses that require one are refused."""
+    `pose_grad=True`: poses that require a gradient get one (d flow / d pose against the upstream gradient, `scale` included, computed
+    by the fused kernels: sininn_flownet_backward_posegrad_points / sininn_siren_backward_posegrad_points), which chains queries:
+    flow_at(net, p + pad(flow_at(net, p, pose_grad=True)[..., :2]), pose_grad=True).  Once differentiable.  Without the keyword there is no
+    gradient with respect to the coordinates: poses that require one are refused."""
     if not torch.is_tensor(poses) or poses.dim() < 1 or poses.shape[-1] != 3:
         raise ValueError(f'flow_at: poses of shape (..., 3), columns (t, y, x); got {tuple(poses.shape) if torch.is_tensor(poses) else type(poses)}')
     if poses.dtype != torch.float32:
         raise ValueError(f'flow_at: fp32 poses; got {poses.dtype}')
-    if poses.requires_grad:
-        raise NotImplementedError('flow_at: there is no gradient with respect to the coordinates (the kernels differentiate the '
-                                  'parameters only); pass poses.detach()')
+    if poses.requires_grad and not pose_grad:
+        raise NotImplementedError('flow_at: there is no gradient with respect to the coordinates unless asked for: pass pose_grad=True, '
+                                  'or poses.detach()')
     _on_gpu(poses, 'pose list')
     lead = poses.shape[:-1]
     flat = poses.reshape(-1, 3).contiguous()
@@ -876,8 +924,9 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
         raise ValueError('get_mask needs a progressive network')
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
     enc_a = net.encode.effective_frequencies() if isinstance(getattr(net, 'encode', None), RotatedFourierFeatures) else None
-    train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad))
-    out = _FlowAt.apply(net, flat, float(scale), train, mask, enc_a, *params)
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad) or
+                                         (pose_grad and poses.requires_grad))
+    out = _FlowAt.apply(net, flat, float(scale), train, mask, enc_a, bool(pose_grad), *params)
     if not planar:
         out = out.t().contiguous().view(*lead, 4)
     return (out, mask.tensor) if get_mask else out

@@ -72,9 +72,9 @@ class ProgressiveEncoderController(nn.Module):
 
     def __call__(self, x, **kwargs):
         """progressive_controller.py:45-53 on flow_at: the controller's own mask goes through `device_mask` (uploaded when it changed,
-        with its k_active), an `override_mask` as flow_at takes it; `get_mask` among the keywords returns (out, that mask)"""
+        with its k_active), an `override_mask` as flow_at takes it; `get_mask` among the keywords returns (out, that mask); `pose_grad=True` is flow_at's"""
         override_mask = kwargs.get('override_mask')
-        out = flow_at(self, x, 1.0, override_mask=override_mask)
+        out = flow_at(self, x, 1.0, override_mask=override_mask, pose_grad=kwargs.get('pose_grad', False))
         if 'get_mask' in kwargs:
             return out, self.mask if override_mask is None else override_mask
         return out

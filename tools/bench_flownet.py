@@ -81,7 +81,10 @@ def main():
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--points', type=int, default=0, metavar='N', help='a pose list of N random points instead of the frames x height x width grid')
     ap.add_argument('--spatial', type=int, default=0, metavar='R', help='progressive nets: a per-point mask from an R^3 grid (0: the global mask)')
+    ap.add_argument('--pose-grad', action='store_true', help='--points: the step also differentiates the poses (flow_at(.., pose_grad=True); the '
+                    'baseline: the composed network with the poses as a leaf); adds no_pose_grad_step_ms, the same step without it, and pose_grad_cost_ms / pose_grad_cost_ratio')
     a = ap.parse_args()
+    assert a.points or not a.pose_grad, '--pose-grad: the coordinate gradient exists at pose lists (--points)'
     from fit_flow import composed_flow_at, composed_flow_fields
     assert not (a.points and a.spatial), '--points: per-point masks are evaluated on grids only'
     dev = torch.device('cuda', 0)
@@ -112,8 +115,11 @@ def main():
     up = torch.randn(a.frames, 4, a.height, a.width, device=dev) if not a.points else None
     params = list(net.parameters())
 
-    def point_paths(at, **fixed):
+    def point_paths(at, pose_grad=False, **fixed):
         poses = (torch.rand(n, 3, generator=torch.Generator().manual_seed(1)) * 2 - 1).to(dev)
+        if pose_grad:
+            poses.requires_grad_(True)
+            fixed = dict(fixed, pose_grad=True) if at is flownet.flow_at else fixed
         kw = dict(override_mask=mask_dev) if prog and at is composed_flow_at else {}
         up_p = torch.randn(4, n, device=dev)
         up_p = up_p if fixed else up_p.t().contiguous()          # the composed network returns (N, 4)
@@ -125,6 +131,7 @@ def main():
         def step():
             for p in params:
                 p.grad = None
+            poses.grad = None
             at(target, poses, 2.0, **kw, **fixed).backward(up_p)
         return fwd, step
 
@@ -143,9 +150,11 @@ def main():
         return fwd, step
 
     if a.points:
-        todo = {'fused': point_paths(flownet.flow_at, planar=True)}
+        todo = {'fused': point_paths(flownet.flow_at, a.pose_grad, planar=True)}
+        if a.pose_grad:
+            todo['no_pose_grad'] = point_paths(flownet.flow_at, planar=True)
         if a.baseline:
-            todo['torch'] = point_paths(composed_flow_at)
+            todo['torch'] = point_paths(composed_flow_at, a.pose_grad)
     else:
         todo = {'fused': paths(flownet.flow_fields)}
         if a.baseline:
@@ -158,7 +167,7 @@ def main():
     f_fwd, f_step = flops_siren(n) if siren else flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
     sizes = (_lib.lib().sininn_siren_saved_bytes, _lib.lib().sininn_siren_workspace_bytes) if siren else \
         (_lib.lib().sininn_flownet_saved_bytes, _lib.lib().sininn_flownet_workspace_bytes)
-    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(mode='points') if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
+    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(mode='points', pose_grad=a.pose_grad) if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=sizes[0](n), workspace_bytes=sizes[1](n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):
@@ -166,10 +175,14 @@ def main():
             best = min(meds)
             out[f'{k}_{what}_ms'] = best
             out[f'{k}_{what}_ms_windows'] = [round(m, 4) for m in meds]
-            out[f'{k}_{what}_mfma_peak_share'] = round(fl / (best * 1e-3) / PEAK_F32_MFMA, 4)
+            if not (a.pose_grad and what == 'step' and k != 'no_pose_grad'):      # flop_step counts no pose gradient: no share for such a step
+                out[f'{k}_{what}_mfma_peak_share'] = round(fl / (best * 1e-3) / PEAK_F32_MFMA, 4)
     if a.baseline:
         out['speedup_forward'] = round(out['torch_forward_ms'] / out['fused_forward_ms'], 3)
         out['speedup_step'] = round(out['torch_step_ms'] / out['fused_step_ms'], 3)
+    if a.pose_grad:
+        out['pose_grad_cost_ms'] = round(out['fused_step_ms'] - out['no_pose_grad_step_ms'], 4)
+        out['pose_grad_cost_ratio'] = round(out['fused_step_ms'] / out['no_pose_grad_step_ms'], 3)
     print(json.dumps(out))
 
 

@@ -10,6 +10,7 @@
     python tools/fit_flow.py --optimizer lamb
     python tools/fit_flow.py --net PRBF --controller spatial --res 7
     python tools/fit_flow.py --net RBF --points 4096
+    python tools/fit_flow.py --net RBF --points 4096 --cycle
 
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
@@ -28,7 +29,10 @@ torch.sin(30 * .) between them, model.py:145-146.
 
 `--points N` (fit_points) is the other way such a network is trained: every step draws N uniform points in [-1, 1]^3 from a seeded
 generator and fits net(poses) (flownet.flow_at, or the composed network) to the analytic flow of flowdata.SyntheticClip at those points,
-MSE and FusedAdam; no warping, no images.
+MSE and FusedAdam; no warping, no images.  `--cycle` adds a forward-backward consistency term at those continuous points: p' = p moved by
+flow12(p) (pixels turned into the pose units of the clip, the time unchanged: the clip's flow21 at a pose is the flow back onto that pose's
+frame), and flow21(p') + flow12(p) should vanish.  The second query is a chained one: its gradient reaches the parameters through p' as
+well (flow_at(.., pose_grad=True); composed: torch's autograd).  It runs the fused and the composed loop and prints the losses of both.
 
 The pair is seeded and analytic: frame1 is a smooth texture, frame2 the same texture displaced by a known smooth flow.
 `--composed` evaluates the network with torch's own ops (nn.functional.linear and elementwise ops) instead of the fused
@@ -181,9 +185,22 @@ def analytic_flow(poses, h=64, w=96, frames=3):
     return torch.stack((*carry(s0, s1), *carry(s1, s0)), dim=1).to(torch.float32)
 
 
+def follow(poses, out, h=64, w=96):
+    """p' (N, 3): `poses` moved by flow12 = out[:, :2] (x then y displacement, in pixels of the h x w clip) in pose units, the time unchanged"""
+    zero = torch.zeros_like(out[:, 0])
+    return poses + torch.stack((zero, out[:, 1] * (2.0 / (h - 1)), out[:, 0] * (2.0 / (w - 1))), dim=1)
+
+
+def cycle_term(query, poses, out):
+    """mean |flow21(p') + flow12(p)|^2 with p' = follow(poses, out), out = query(poses) already evaluated"""
+    back = query(follow(poses, out))
+    return (back[:, 2:] + out[:, :2]).pow(2).mean()
+
+
 def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, lr=1e-3, seed=0, device='cuda', log=None,
-               max_iteration=1000):
+               max_iteration=1000, cycle=False, cycle_weight=1.0):
     """fit net(poses) to analytic_flow at `n_points` fresh uniform points of [-1, 1]^3 per step (a seeded generator): MSE, FusedAdam.
+    `cycle`: plus cycle_weight x cycle_term, the forward-backward consistency at p' (a chained query).
     Returns the list of per-step losses (floats).  `info`: a dict that receives the network (the controller of a progressive one)
     as info['net'] and, as info['first'], the first step's `poses`, `target` and the network's `state` before that step"""
     from sin_inn_amd import FusedAdam, flownet, progressive
@@ -194,6 +211,7 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
     opt = FusedAdam(net.parameters(), lr=lr)
     gen = torch.Generator().manual_seed(seed + 1)
     at = composed_flow_at if composed else flownet.flow_at
+    query = (lambda x: composed_flow_at(net, x, 1.0)) if composed else (lambda x: flownet.flow_at(net, x, 1.0, pose_grad=True))
     if info is not None:
         info['net'] = net
     losses = []
@@ -203,7 +221,10 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
         if info is not None and step == 0:
             info['first'] = dict(poses=poses, target=target, state={k: v.detach().clone() for k, v in net.state_dict().items()})
         opt.zero_grad()
-        loss = torch.nn.functional.mse_loss(at(net, poses, 1.0), target)
+        out = at(net, poses, 1.0)
+        loss = torch.nn.functional.mse_loss(out, target)
+        if cycle:
+            loss = loss + cycle_weight * cycle_term(query, poses, out)
         loss.backward()
         opt.step()
         net.stash_iteration(loss.detach())
@@ -288,7 +309,16 @@ def main():
     ap.add_argument('--controller', default='early', choices=['early', 'spatial'], help='progressive nets: the mask is global / per grid cell')
     ap.add_argument('--res', type=int, default=7, help='--controller spatial: cells per axis of the mask grid')
     ap.add_argument('--points', type=int, default=0, metavar='N', help='fit net(poses) at N random points per step (fit_points) instead of a frame pair')
+    ap.add_argument('--cycle', action='store_true', help='--points: add the forward-backward consistency term at p + flow12(p); runs the '
+                    'fused and the composed loop and prints both')
     a = ap.parse_args()
+    assert a.points or not a.cycle, '--cycle is a term of the --points loop'
+    if a.cycle:
+        for what, comp in (('fused', False), ('composed', True)):
+            losses = fit_points(a.net, a.points, a.steps, comp, lr=a.lr, seed=a.seed, log=lambda m, w=what: print(w, m),
+                                max_iteration=a.max_iteration, cycle=True)
+            print(f'{what}: first {losses[0]:.6f}  last {losses[-1]:.6f}')
+        return
     if a.points:
         losses = fit_points(a.net, a.points, a.steps, a.composed, lr=a.lr, seed=a.seed, log=print, max_iteration=a.max_iteration)
         print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
