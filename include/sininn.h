@@ -769,7 +769,8 @@ int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* gri
  *   sininn_flownet_encgrad_workspace_bytes(args).  Tiles, partial sums and the order of every sum depend on n alone: a pose list that
  *   spells out meshgrid(times, ys, xs) gives bitwise the flows and gradients of the grid call, two calls are bitwise equal and any valid
  *   k_active gives the same bits.  The gradient with respect to the coordinates is a call of its own, below.
- * Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse.  Not available under a spatial mask. */
+ * Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse.  Under a spatial mask: the
+ * sininn_flownet_*_spatial_points calls below. */
 int sininn_flownet_forward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
 int sininn_flownet_backward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
 int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a,
@@ -796,10 +797,39 @@ int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, cons
  *   extra_workspace: sininn_flownet_posegrad_workspace_bytes(args, with_enc_grad) bytes, 16-byte aligned (a packed, mask-folded copy of
  *   w[0], plus, with_enc_grad != 0, what the encgrad call needs); g_enc_a may be NULL (no frequency gradient).
  * Refused before any launch: a null g_poses, a non-null g_enc_a for an encoding other than SININN_FLOWNET_FOURIER, a null or short
- * extra_workspace, and everything the points calls refuse, each with a sentence under this entry point's name.  Not available under a spatial mask. */
+ * extra_workspace, and everything the points calls refuse, each with a sentence under this entry point's name.  Under a spatial mask:
+ * sininn_flownet_backward_posegrad_spatial_points below. */
 size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad);
 int sininn_flownet_backward_posegrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
                                             void* extra_workspace, size_t extra_workspace_bytes, void* stream);
+
+/* Per-point masks at pose lists (controller(poses) of a StashedSpatialController, progressive_controller.py:655-680: the reference's own way to
+ * evaluate one): the spatial calls at a caller's pose list, and the points calls under the mask grid.  Every argument means what it means in
+ * its two twins above: (grid, res, centre_scale) as in sininn_flownet_*_spatial, (poses, n) and the planar flows / dflows [4][n] as in
+ * sininn_flownet_*_points, the trailing arguments those of the points call of the same name.  The descriptor's grid of points and its `mask`
+ * are ignored.  The kernels are the spatial ones (a point's coordinates come from row p of the list): a pose list that spells out
+ * meshgrid(times, ys, xs) gives bitwise the flows, the eight gradients, g_enc_a and the sampled mask of the spatial grid calls; two calls are
+ * bitwise equal; any valid k_active gives the same bits.  Workspaces and `saved` have the sizes of the points calls for n
+ * (sininn_flownet_posegrad_workspace_bytes for the posegrad call: the packed copy of w[0] is unmasked here).
+ *   sininn_flownet_backward_posegrad_spatial_points: g_poses[p][d] = sum_k (m_{3 + k}(p) dE[p][k]) * d feature_k / d x_d (p)
+ *     + m_d(p) * sum_j dh1[p][j] w[0][j][d], dE[p][k] = sum_j dh1[p][j] w[0][j][3 + k], each product with the mask a rounded fp32 one, the
+ *     order of every sum that of sininn_flownet_backward_posegrad_points.  The mask is a CONSTANT of the point: the reference interpolates it
+ *     under no_grad, so there is no d mask / d pose term, although m_k(p) is piecewise trilinear in the pose.
+ *   sininn_flownet_sample_mask_points: out [n][515] = m_k(p) at the pose list.
+ * Refused before any launch, each under its own name: everything the spatial twin refuses (a null grid or centre_scale, res, a descriptor that
+ * is not progressive, PPE), everything the points twin refuses (null poses, n < 1, n > 2^22, ...). */
+int sininn_flownet_forward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                          const float* poses, int64_t n, void* stream);
+int sininn_flownet_backward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                           const float* poses, int64_t n, void* stream);
+int sininn_flownet_backward_encgrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
+                                                   size_t enc_workspace_bytes, void* stream);
+int sininn_flownet_backward_posegrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
+                                                    size_t extra_workspace_bytes, void* stream);
+int sininn_flownet_sample_mask_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                      const float* poses, int64_t n, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).

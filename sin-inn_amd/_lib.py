@@ -294,6 +294,13 @@ _SIGS = {
     'sininn_flownet_backward_encgrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     'sininn_flownet_posegrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs), C.c_int]),
     'sininn_flownet_backward_posegrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_flownet_forward_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, C.c_void_p]),
+    'sininn_flownet_backward_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, C.c_void_p]),
+    'sininn_flownet_backward_encgrad_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, c_f, C.c_void_p,
+                                                                 C.c_size_t, C.c_void_p]),
+    'sininn_flownet_backward_posegrad_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, c_f, c_f,
+                                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    'sininn_flownet_sample_mask_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, c_f, C.c_void_p]),
     'sininn_siren_backward_posegrad_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, c_f, C.c_void_p]),
     'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
     'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),

@@ -138,6 +138,18 @@ int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const f
 size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad);
 int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
                                             void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st);
+int flownet_forward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
+                                          int64_t n, hipStream_t st);
+int flownet_backward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
+                                           int64_t n, hipStream_t st);
+int flownet_backward_encgrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
+                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                                   hipStream_t st);
+int flownet_backward_posegrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
+                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
+                                                    size_t extra_workspace_bytes, hipStream_t st);
+int flownet_sample_mask_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
+                                      int64_t n, float* out, hipStream_t st);
 int siren_backward_posegrad_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, float* g_poses, hipStream_t st);
 int siren_supported(const sininn_siren_args* a, const char* who);
 size_t siren_saved_bytes(int64_t n);
@@ -634,6 +646,30 @@ size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, 
 int sininn_flownet_backward_posegrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
                                             void* extra_workspace, size_t extra_workspace_bytes, void* stream) {
   return flownet_backward_posegrad_points_launch(args, poses, n, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, ST(stream));
+}
+int sininn_flownet_forward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                          const float* poses, int64_t n, void* stream) {
+  return flownet_forward_spatial_points_launch(args, grid, res, centre_scale, poses, n, ST(stream));
+}
+int sininn_flownet_backward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                           const float* poses, int64_t n, void* stream) {
+  return flownet_backward_spatial_points_launch(args, grid, res, centre_scale, poses, n, ST(stream));
+}
+int sininn_flownet_backward_encgrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
+                                                   size_t enc_workspace_bytes, void* stream) {
+  return flownet_backward_encgrad_spatial_points_launch(args, grid, res, centre_scale, poses, n, g_enc_a, enc_workspace, enc_workspace_bytes,
+                                                        ST(stream));
+}
+int sininn_flownet_backward_posegrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
+                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
+                                                    size_t extra_workspace_bytes, void* stream) {
+  return flownet_backward_posegrad_spatial_points_launch(args, grid, res, centre_scale, poses, n, g_poses, g_enc_a, extra_workspace,
+                                                         extra_workspace_bytes, ST(stream));
+}
+int sininn_flownet_sample_mask_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, const float* poses,
+                                      int64_t n, float* out, void* stream) {
+  return flownet_sample_mask_points_launch(args, grid, res, centre_scale, poses, n, out, ST(stream));
 }
 int sininn_siren_backward_posegrad_points(const sininn_siren_args* args, const float* poses, int64_t n, float* g_poses, void* stream) {
   return siren_backward_posegrad_points_launch(args, poses, n, g_poses, ST(stream));

@@ -57,11 +57,16 @@
 //           vector: point_coord (flownet_tile.h) branches on q.poses, a kernel argument, and the host sets T = H = 1, W = N, which makes
 //           the [T][4][H][W] indexing of flows / dflows the planar [4][N].  No kernel is instantiated for it and nothing else differs:
 //           tiles, `saved`, workspaces and the order of every sum depend on N alone, so a pose list that spells out a grid gives the grid
-//           call's bits.  Not combined with the spatial mode.
+//           call's bits.  Combined with the spatial mode (sininn_flownet_*_spatial_points) it is PoseList plus Spatial in one FlowNetDev:
+//           the SPATIAL instantiations below take a point's coordinates through point_coord as well, so they serve a pose list as they are.
 //
 // pose gradient (sininn_flownet_backward_posegrad_points) after the whole backward of a points call: flownet_posegrad_kernel contracts
 //           dE = dh1 W1 (the GEMM of the frequency gradient, for every encoding) with the analytic derivative of the encoding over the
 //           FEATURES of each point: g_poses [N][3].  A tile owns its points: no partial sums in memory, no atomics, a fixed order.  DESIGN 14.8
+//           SPATIAL (sininn_flownet_backward_posegrad_spatial_points): a per-point mask cannot be folded into the packed W1, so the pack is
+//           unmasked and the kernel multiplies dE[p][k] by m_k(p) after the GEMM, and the coordinate column's sum by m_d(p), from the corner
+//           tile staged once per tile.  The mask is a CONSTANT of the point: the reference interpolates it under no_grad
+//           (progressive_controller.py:655-680), so there is no d mask / d pose term.  DESIGN 14.9
 //
 // positional encoding (PE / PPE, PEModel model.py:472-487, PPEModel model.py:607-611): layer 1 has LIVE (LIVE + 3) inputs, fewer than
 //           its padded K width KW; features LIVE .. KW - 1 are exact zeros from encode4.  Plain PE reads W1 [256][LIVE] in place (96-byte
@@ -954,9 +959,10 @@ template <int KIND> constexpr size_t posegrad_lds() { return FN_LDS + (size_t)(p
 
 // wt[c][j] = w1[j][feature of row c] for the rows of every pass (progressive: column 3 + feature, times its mask, an exact zero where the
 // mask is zero; a feature from LIVE on: zero), then four rows of the coordinate columns, wt[NP 256 + d][j] = w1[j][d] (progressive, d < 3;
-// else zero): their mask multiplies the finished sum.  block = row c; <E::LIVE, E::KW>: encodings of one shape share one kernel
+// else zero): their mask multiplies the finished sum.  spatial (with prog): column 3 + feature as it is, the kernel applies the point's
+// mask to dE.  block = row c; <E::LIVE, E::KW>: encodings of one shape share one kernel
 template <int LIVE, int KW>
-__global__ __launch_bounds__(FN_NTHR) void flownet_posegrad_pack_kernel(const float* w1, const float* mask, float* wt, int prog) {
+__global__ __launch_bounds__(FN_NTHR) void flownet_posegrad_pack_kernel(const float* w1, const float* mask, float* wt, int prog, int spatial) {
   constexpr int ROWS = (KW + FN_HID - 1) / FN_HID * FN_HID;
   const int c = blockIdx.x, j = threadIdx.x;
   const float* row = w1 + (size_t)j * (LIVE + (prog ? FN_DOM : 0));
@@ -966,7 +972,9 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_posegrad_pack_kernel(const fl
   } else {
     const int k = (c & ~63) + 4 * (c & 15) + ((c >> 4) & 3);
     if (k < LIVE) {
-      if (prog) {
+      if (spatial) {
+        v = row[FN_DOM + k];
+      } else if (prog) {
         const float m = mask[FN_DOM + k];
         v = m == 0.f ? 0.f : row[FN_DOM + k] * m;
       } else {
@@ -1090,14 +1098,19 @@ __device__ __forceinline__ void butterfly_step(float (&v)[16 * FN_DOM], int li) 
 // the last open one (not PROG: all), a wave whose 64 columns lie beyond it skips its GEMM and contributes exact zeros.
 // The order of every sum is fixed: a lane's four columns in index order (fmaf), the 16 lanes by the butterfly, then the slots
 // (pass, wave) in index order, then (PROG) m_d times the coordinate column's sum.  Rows p >= N are not written
-template <int KIND, bool PROG>
+// SPATIAL (with PROG): wt is unmasked, `mask` unused; a lane's four features of a point are multiplied by the point's mask of those features
+// (sample_cols on the corner tile, one rounded product each) before FeatureGrad4::grad, the coordinate column's sum by m_d(p).  Grid columns
+// from k_active on are zero, so the skipped waves would have added dE * 0: kopen skips exactly, as above
+template <int KIND, bool PROG, bool SPATIAL = false>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_posegrad_kernel(FlowNetDev q, const float* wt, const float* mask, float* g_poses,
                                                                      int kopen) {
+  static_assert(PROG || !SPATIAL, "a spatial mask is a progressive network's");
   constexpr int NP = posegrad_passes<KIND>();
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
   float* const hs = fn_smem;                           // [64][FN_HS]: dh1 tile
   float* const cs = fn_smem + FN_P * FN_HS;            // [64][4]: coordinates of the tile's points
   float* const red = cs + FN_P * FN_CS;                // [NP * 4][64][FN_PG_ROW]: a wave's sums of a pass
+  float* const cns = red + NP * 4 * FN_P * FN_PG_ROW;  // SPATIAL: [64][FN_CN]: the corners of the tile's points
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kq = lane >> 4;
@@ -1114,7 +1127,15 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_posegrad_kernel(FlowNetDev
       const int row = f >> 6, c4 = (f & 63) * 4;
       *reinterpret_cast<f32x4*>(hs + row * FN_HS + c4) = *reinterpret_cast<const f32x4*>(q.dh + ((size_t)tile * FN_P + row) * FN_HID + c4);
     }
-    if (tid < FN_P) stage_coord(q, cs, tile, tid);
+    if constexpr (SPATIAL) {
+      if (tid < FN_P) {
+        const Coord c = point_coord(q, tile * FN_P + tid);
+        *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
+        store_corners(cns + tid * FN_CN, corners_of(q.sp, c));
+      }
+    } else {
+      if (tid < FN_P) stage_coord(q, cs, tile, tid);
+    }
     __syncthreads();
     // ---- the coordinate columns on the vector ALU: thread = (coordinate tid / 64, point tid % 64) ----
     float csum = 0.f;
@@ -1151,11 +1172,18 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_posegrad_kernel(FlowNetDev
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const f32x4 c = *reinterpret_cast<const f32x4*>(cs + (16 * m + 4 * kq + r) * FN_CS);
-            const float dz[4] = {acc[m][0][r], acc[m][1][r], acc[m][2][r], acc[m][3][r]};
+            float dz[4] = {acc[m][0][r], acc[m][1][r], acc[m][2][r], acc[m][3][r]};
+            if constexpr (SPATIAL) {
+              float mk[4];
+              sample_cols<4>(q.sp.grid, load_corners(cns + (16 * m + 4 * kq + r) * FN_CN), FN_DOM + k0 + 4 * li, mk);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) dz[j] = mul_rn(dz[j], mk[j]);
+            }
             float g[FN_DOM] = {0.f, 0.f, 0.f};
             fg.grad(Coord{c[0], c[1], c[2]}, dz, g);
 #pragma unroll
             for (int d = 0; d < FN_DOM; ++d) v[(4 * m + r) * FN_DOM + d] = g[d];
+            if constexpr (SPATIAL) __builtin_amdgcn_sched_barrier(0);   // one point's eight grid rows in flight at a time, as in the forward kernel
           }
         butterfly_step<48, 1>(v, li);
         butterfly_step<24, 2>(v, li);
@@ -1170,7 +1198,13 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_posegrad_kernel(FlowNetDev
       float s = 0.f;
 #pragma unroll
       for (int u = 0; u < NP * 4; ++u) s += red[(u * FN_P + lane) * FN_PG_ROW + wave];
-      if constexpr (PROG) s += mul_rn(mask[wave], csum);
+      if constexpr (SPATIAL) {
+        float md[1];
+        sample_cols<1>(q.sp.grid, load_corners(cns + lane * FN_CN), wave, md);
+        s += mul_rn(md[0], csum);
+      } else if constexpr (PROG) {
+        s += mul_rn(mask[wave], csum);
+      }
       g_poses[(size_t)p * FN_DOM + wave] = s;
     }
   }
@@ -1310,7 +1344,7 @@ static Spatial spatial_of(const SpatialArgs* s) {
 }
 
 // the descriptor of a call whose entry point has called check_head, checked and copied into q.  spatial != nullptr: the descriptor's mask
-// is ignored, the grid goes to q.sp.  pl != nullptr: the points are that pose list, not the descriptor's grid (never with spatial)
+// is ignored, the grid goes to q.sp.  pl != nullptr: the points are that pose list, not the descriptor's grid (with or without spatial)
 static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
   q = FlowNetDev{};
   q.sp = spatial_of(spatial);
@@ -1337,6 +1371,12 @@ static int for_mode(const sininn_flownet_args* a, bool spatial, F&& f) {
     }
     return a->progressive ? f(k, std::true_type{}, std::false_type{}) : f(k, std::false_type{}, std::false_type{});
   });
+}
+
+// the name an entry point refuses under: <stem>[_spatial][_points]
+static const char* call_name(const char* plain, const char* spatial_name, const char* points_name, const char* both, const SpatialArgs* spatial,
+                             const PoseList* pl) {
+  return spatial ? (pl ? both : spatial_name) : (pl ? points_name : plain);
 }
 
 // layer 1: gW1 = dh1^T (regenerated input), gb1, and their reduction into nn.Linear's layout
@@ -1441,7 +1481,7 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
 }
 
 static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
-  const char* who = spatial ? "flownet_forward_spatial" : pl ? "flownet_forward_points" : "flownet_forward";
+  const char* who = call_name("flownet_forward", "flownet_forward_spatial", "flownet_forward_points", "flownet_forward_spatial_points", spatial, pl);
   FlowNetDev q;
   if (int rc = check_head(a, who, spatial)) return rc;
   if (int rc = fill_args(a, who, q, spatial, pl)) return rc;
@@ -1459,8 +1499,9 @@ int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* gr
 }
 
 static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
-  if (int rc = check_head(a, spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", spatial)) return rc;
-  return backward_launch(a, nullptr, nullptr, st, spatial, pl);
+  const char* who = call_name("flownet_backward", "flownet_backward_spatial", "flownet_backward_points", "flownet_backward_spatial_points", spatial, pl);
+  if (int rc = check_head(a, who, spatial)) return rc;
+  return backward_launch(a, nullptr, nullptr, st, spatial, pl, spatial && pl ? who : nullptr);   // the earlier calls keep their sentences
 }
 
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_plain_launch(a, st, nullptr); }
@@ -1470,12 +1511,12 @@ int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* g
   return backward_plain_launch(a, st, &s);
 }
 
-int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  if (int rc = check_head(a, "flownet_sample_mask", &s)) return rc;
-  SININN_CHECK(out != nullptr, "flownet_sample_mask: null out");
+static int sample_mask_launch(const sininn_flownet_args* a, const SpatialArgs& s, const PoseList* pl, float* out, hipStream_t st) {
+  const char* who = pl ? "flownet_sample_mask_points" : "flownet_sample_mask";
+  if (int rc = check_head(a, who, &s)) return rc;
+  SININN_CHECK(out != nullptr, "%s: null out", who);
   FlowNetDev q{};
-  if (int rc = check_points(a, "flownet_sample_mask", q)) return rc;
+  if (int rc = check_points(a, who, q, pl)) return rc;
   q.sp = spatial_of(&s);
   const size_t units = ((size_t)q.N * FN_GROUPS + FN_NTHR - 1) / FN_NTHR;
   hipLaunchKernelGGL(flownet_sample_mask_kernel, dim3((unsigned)(units < 8192 ? units : 8192)), dim3(FN_NTHR), 0, st, q, out);
@@ -1483,11 +1524,16 @@ int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, 
   return 0;
 }
 
+int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st) {
+  return sample_mask_launch(a, SpatialArgs{grid, res, centre_scale}, nullptr, out, st);
+}
+
 // the head under this entry point's own name, so that a refusal of the spatial mode (PPE, a null grid, res) comes before the Fourier-only
 // refusal, which would hide it
 static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st,
                                    const SpatialArgs* spatial, const PoseList* pl = nullptr) {
-  const char* who = spatial ? "flownet_backward_encgrad_spatial" : pl ? "flownet_backward_encgrad_points" : "flownet_backward_encgrad";
+  const char* who = call_name("flownet_backward_encgrad", "flownet_backward_encgrad_spatial", "flownet_backward_encgrad_points",
+                              "flownet_backward_encgrad_spatial_points", spatial, pl);
   if (int rc = check_head(a, who, spatial)) return rc;
   SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
                a->encoding);
@@ -1496,7 +1542,7 @@ static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a,
                "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
                flownet_encgrad_workspace_bytes(a));
   SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
-  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st, spatial, pl);
+  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st, spatial, pl, spatial && pl ? who : nullptr);
 }
 
 int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
@@ -1539,27 +1585,28 @@ size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_e
   return pack ? pack + (with_enc_grad ? flownet_encgrad_workspace_bytes(a) : 0) : 0;
 }
 
-template <int KIND, bool PROG>
+// SPATIAL: the pack is unmasked and no global mask is read; the corner tile comes on top of posegrad_lds
+template <int KIND, bool PROG, bool SPATIAL>
 static int posegrad_kind_launch(const sininn_flownet_args* a, const FlowNetDev& q, float* wt, float* g_poses, hipStream_t st) {
   using E = Enc<KIND>;
   constexpr int NP = posegrad_passes<KIND>();
-  constexpr size_t lds = posegrad_lds<KIND>();
-  hipLaunchKernelGGL((flownet_posegrad_pack_kernel<E::LIVE, E::KW>), dim3(NP * FN_HID + FN_CS), dim3(FN_NTHR), 0, st, a->w[0],
-                     PROG ? a->mask : (const float*)nullptr, wt, PROG ? 1 : 0);
+  constexpr size_t lds = posegrad_lds<KIND>() + (SPATIAL ? FN_CN_LDS : 0);
+  const float* const mask = PROG && !SPATIAL ? a->mask : (const float*)nullptr;
+  hipLaunchKernelGGL((flownet_posegrad_pack_kernel<E::LIVE, E::KW>), dim3(NP * FN_HID + FN_CS), dim3(FN_NTHR), 0, st, a->w[0], mask, wt,
+                     PROG ? 1 : 0, SPATIAL ? 1 : 0);
   SININN_LAUNCH_CHECK("flownet_posegrad_pack");
-  auto k = flownet_posegrad_kernel<KIND, PROG>;
+  auto k = flownet_posegrad_kernel<KIND, PROG, SPATIAL>;
   if (raise_lds(k, lds, "flownet_posegrad")) return 1;
-  hipLaunchKernelGGL(k, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), lds, st, q, (const float*)wt, PROG ? a->mask : (const float*)nullptr, g_poses,
+  hipLaunchKernelGGL(k, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), lds, st, q, (const float*)wt, mask, g_poses,
                      PROG ? open_encoded(a) : E::KW);
   SININN_LAUNCH_CHECK("flownet_posegrad");
   return 0;
 }
 
-int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
-                                            void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st) {
-  const char* who = "flownet_backward_posegrad_points";
-  const PoseList pl{poses, n};
-  if (int rc = check_head(a, who, nullptr)) return rc;
+static int backward_posegrad_launch(const sininn_flownet_args* a, const SpatialArgs* spatial, const PoseList& pl, float* g_poses, float* g_enc_a,
+                                    void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st) {
+  const char* who = spatial ? "flownet_backward_posegrad_spatial_points" : "flownet_backward_posegrad_points";
+  if (int rc = check_head(a, who, spatial)) return rc;
   SININN_CHECK(g_poses != nullptr, "%s: null g_poses", who);
   SININN_CHECK(g_enc_a == nullptr || flownet_encgrad_workspace_bytes(a) != 0,
                "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only (pass a null g_enc_a)", who, a->encoding);
@@ -1570,8 +1617,51 @@ int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const 
   float* const wt = static_cast<float*>(extra_workspace);
   float* const enc_ws = g_enc_a ? wt + posegrad_pack_bytes(a) / sizeof(float) : nullptr;
   FlowNetDev q;                                        // every check is backward_launch's, made before its first launch
-  if (int rc = backward_launch(a, g_enc_a, enc_ws, st, nullptr, &pl, who, &q)) return rc;
-  return for_mode(a, false, [&](auto k, auto prog, auto) { return posegrad_kind_launch<decltype(k)::value, decltype(prog)::value>(a, q, wt, g_poses, st); });
+  if (int rc = backward_launch(a, g_enc_a, enc_ws, st, spatial, &pl, who, &q)) return rc;
+  return for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
+    return posegrad_kind_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, wt, g_poses, st);
+  });
+}
+
+int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
+                                            void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st) {
+  return backward_posegrad_launch(a, nullptr, PoseList{poses, n}, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, st);
+}
+
+// ---- points mode under a per-point mask: PoseList plus Spatial in one call; the kernels are the SPATIAL instantiations ----
+int flownet_forward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
+                                          int64_t n, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  const PoseList pl{poses, n};
+  return forward_launch(a, st, &s, &pl);
+}
+
+int flownet_backward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
+                                           int64_t n, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  const PoseList pl{poses, n};
+  return backward_plain_launch(a, st, &s, &pl);
+}
+
+int flownet_backward_encgrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
+                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
+                                                   hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  const PoseList pl{poses, n};
+  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, &s, &pl);
+}
+
+int flownet_backward_posegrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
+                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
+                                                    size_t extra_workspace_bytes, hipStream_t st) {
+  const SpatialArgs s{grid, res, centre_scale};
+  return backward_posegrad_launch(a, &s, PoseList{poses, n}, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, st);
+}
+
+int flownet_sample_mask_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
+                                      int64_t n, float* out, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return sample_mask_launch(a, SpatialArgs{grid, res, centre_scale}, &pl, out, st);
 }
 
 }  // namespace sininn

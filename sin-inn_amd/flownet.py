@@ -75,8 +75,15 @@ flows and gradients of a list that spells out a grid are bitwise those of the gr
 (`planar=True` returns it); the transpose to the reference's (N, 4) is a torch op.  Differentiable with respect to the parameters
 (`_FlowAt`, next to `_FlowFields`), learnable frequencies included, and, with `pose_grad=True`, with respect to the coordinates: the
 backward pass then is `sininn_flownet_backward_posegrad_points` / `sininn_siren_backward_posegrad_points`, which contract dh1 W1 with the
-analytic derivative of the encoding over the features of each point (csrc/flownet.hip, flownet_posegrad_kernel).  Per-point
-masks (a `StashedSpatialController`, a grid as `override_mask`) are not evaluated at pose lists.
+analytic derivative of the encoding over the features of each point (csrc/flownet.hip, flownet_posegrad_kernel).
+
+Per-point masks at pose lists: `controller(poses)` of a `StashedSpatialController` is the reference's own way to evaluate one
+(progressive_controller.py:670-680), and `flow_at` takes that controller, or any controller with a grid (res^3, 515) on the device as a 2-D
+`override_mask`.  The calls are `flownet_forward_spatial_points` / `flownet_backward_spatial_points` / `flownet_sample_mask_points`
+(`sininn_flownet_*_spatial_points`): the spatial kernels at a pose list, bitwise the spatial grid call where the list spells out a grid;
+`pose_grad=True` runs the SPATIAL form of flownet_posegrad_kernel.  The mask is a constant of the point there, as in the reference, which
+interpolates it under no_grad: the pose gradient has no d mask / d pose term.  A bare progressive model with a grid is still refused at a
+pose list: the interpolation is a controller's.
 
 Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
 `--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
@@ -696,20 +703,60 @@ def flownet_backward_points(net, poses, scale, dflows, saved, workspace=None, ma
     a = _args(net, poses, None, None, scale, mask, k_active, enc_a)
     if pose_grad:
         assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
-        lib = _lib.lib()
-        grads, keep = _backward_buffers(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, lib.sininn_flownet_workspace_bytes)  # noqa: F841
-        g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
-        g_enc = _out_tensor(g_enc_a, (3, 256), a._device) if enc_grad else None
-        if pose_workspace is None:
-            nbytes = lib.sininn_flownet_posegrad_workspace_bytes(C.byref(a), int(enc_grad))
-            pose_workspace = torch.empty(nbytes // 4, device=a._device, dtype=torch.float32)
-        check(lib.sininn_flownet_backward_posegrad_points(C.byref(a), *a._poses, ptr(g_poses), ptr(g_enc), ptr(pose_workspace),
-                                                          pose_workspace.numel() * 4, _stream()))
-        return ((grads, g_enc) if enc_grad else grads), g_poses
+        return _backward_posegrad(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_backward_posegrad_points, a._poses, enc_grad,
+                                  g_enc_a, pose_workspace, g_poses)
     return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
                      _lib.lib().sininn_flownet_backward_points, *a._poses,
                      enc_call=_lib.lib().sininn_flownet_backward_encgrad_points if enc_grad else None, enc_workspace=enc_workspace,
                      g_enc_a=g_enc_a)
+
+
+def _backward_posegrad(a, net, dflows, saved, workspace, call, extra, enc_grad, g_enc_a, pose_workspace, g_poses):
+    """the posegrad call of a points descriptor: `_backward_buffers`, g_poses (N, 3), the optional frequency gradient and the extra workspace,
+    then `call(a, *extra, ..)`: ((grads[, gF]), g_poses)"""
+    lib = _lib.lib()
+    grads, keep = _backward_buffers(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, lib.sininn_flownet_workspace_bytes)  # noqa: F841
+    g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
+    g_enc = _out_tensor(g_enc_a, (3, 256), a._device) if enc_grad else None
+    if pose_workspace is None:
+        nbytes = lib.sininn_flownet_posegrad_workspace_bytes(C.byref(a), int(enc_grad))
+        pose_workspace = torch.empty(nbytes // 4, device=a._device, dtype=torch.float32)
+    check(call(C.byref(a), *extra, ptr(g_poses), ptr(g_enc), ptr(pose_workspace), pose_workspace.numel() * 4, _stream()))
+    return ((grads, g_enc) if enc_grad else grads), g_poses
+
+
+# ---- and under a per-point mask: the spatial calls at a pose list ----
+def flownet_forward_spatial_points(net, poses, scale, train, grid, res, centre_scale=None, k_active=None, saved=None, enc_a=None):
+    """flownet_forward_points under the per-point mask of flownet_forward_spatial: flows (4, N)"""
+    a = _args(net, poses, None, None, scale, None, k_active, enc_a, spatial=True)
+    flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_spatial_points,
+                            *_spatial(a, grid, res, centre_scale), *a._poses)
+    return flows.view(4, -1), saved
+
+
+def flownet_backward_spatial_points(net, poses, scale, dflows, saved, grid, res, centre_scale=None, k_active=None, workspace=None, enc_a=None,
+                                    enc_grad=False, enc_workspace=None, g_enc_a=None, pose_grad=False, pose_workspace=None, g_poses=None):
+    """flownet_backward_points under the per-point mask of the forward call, dflows (4, N); `pose_grad=True` as there, from
+    sininn_flownet_backward_posegrad_spatial_points: the mask is a constant of the point, there is no d mask / d pose term"""
+    a = _args(net, poses, None, None, scale, None, k_active, enc_a, spatial=True)
+    extra = (*_spatial(a, grid, res, centre_scale), *a._poses)
+    if pose_grad:
+        assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
+        return _backward_posegrad(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_backward_posegrad_spatial_points, extra, enc_grad,
+                                  g_enc_a, pose_workspace, g_poses)
+    return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
+                     _lib.lib().sininn_flownet_backward_spatial_points, *extra,
+                     enc_call=_lib.lib().sininn_flownet_backward_encgrad_spatial_points if enc_grad else None, enc_workspace=enc_workspace,
+                     g_enc_a=g_enc_a)
+
+
+def flownet_sample_mask_points(net, poses, grid, res, centre_scale=None):
+    """the interpolated mask (N, 515) at a pose list (N, 3), bitwise what the spatial kernels multiply layer 1's input by"""
+    a = _args(net, poses, None, None, 1.0, spatial=True)
+    extra = _spatial(a, grid, res, centre_scale)
+    out = torch.empty(a.W, a.enc_dim, device=a._device, dtype=torch.float32)
+    check(_lib.lib().sininn_flownet_sample_mask_points(C.byref(a), *extra, *a._poses, ptr(out), _stream()))
+    return out
 
 
 def siren_forward_points(net, poses, scale, train, saved=None, omega=None):
@@ -790,11 +837,16 @@ class _FlowAt(torch.autograd.Function):
             enc_a = enc_a.detach().contiguous()
         if isinstance(net, SirenModel):
             forward, ctx.backward_fn, ctx.kw = siren_forward_points, siren_backward_points, {}
+        elif mask.spatial:
+            forward, ctx.backward_fn = flownet_forward_spatial_points, flownet_backward_spatial_points
+            ctx.kw = dict(grid=mask.tensor, res=mask.res, centre_scale=mask.centre_scale, k_active=mask.k_active, enc_a=enc_a)
         else:
             forward, ctx.backward_fn = flownet_forward_points, flownet_backward_points
             ctx.kw = dict(mask=mask.tensor, k_active=mask.k_active, enc_a=enc_a)
         flows, saved = forward(net, poses, scale, train, **ctx.kw)
-        ctx.net, ctx.poses, ctx.scale, ctx.saved = net, poses, scale, saved
+        ctx.net, ctx.poses, ctx.scale, ctx.saved, ctx.mask = net, poses, scale, saved, mask
+        if mask.spatial:
+            ctx.grid_version = mask.tensor._version      # the controller updates its grid in place
         if enc_a is not None and ctx.needs_input_grad[5]:
             ctx.kw['enc_grad'] = True
         if pose_grad and ctx.needs_input_grad[1]:
@@ -806,6 +858,9 @@ class _FlowAt(torch.autograd.Function):
     def backward(ctx, dflows):
         if ctx.saved is None:
             raise RuntimeError('flow_at: backward through an inference-mode forward')
+        if ctx.mask.spatial and ctx.mask.tensor._version != ctx.grid_version:
+            raise RuntimeError('flow_at: the mask grid changed between the forward and the backward pass (run backward before '
+                               'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
         grads, g_enc, g_poses = ctx.backward_fn(ctx.net, ctx.poses, ctx.scale, dflows, ctx.saved, **ctx.kw), None, None
         if ctx.kw.get('pose_grad'):
             grads, g_poses = grads
@@ -898,7 +953,10 @@ def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
 def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=False, pose_grad=False):
     """net(poses) * scale (trainer.py:43-44, progressive_controller.py:45-53) at arbitrary points: `poses` (..., 3) fp32 on the GPU,
     columns (t, y, x) -> (..., 4), contiguous.  `net`: what flow_fields takes, a model or a LinearController / LinearControllerEarly
-    around a progressive one; `override_mask` (515 values, PPE: 27) replaces the controller's mask.  The kernels read the list in place
+    around a progressive one; `override_mask` (515 values, PPE: 27) replaces the controller's mask.  A StashedSpatialController, or a
+    controller with an `override_mask` of shape (res^3, 515) on the device, evaluates the network under the per-point mask interpolated from
+    that grid (the mask is a constant of the point: `pose_grad` has no d mask / d pose term), and `get_mask=True` returns the interpolated
+    mask (..., 515) then.  The kernels read the list in place
     and write the planar (4, N) layout; `planar=True` returns that tensor, without the transpose to the reference's layout.
     Differentiable with respect to the parameters (and `encode.frequencies` of RFF / PRFF); under torch.no_grad() (or with no trainable
     parameter) the inference mode runs and nothing is saved.  `get_mask=True` returns (out, the mask in use on the device).
@@ -916,12 +974,16 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     _on_gpu(poses, 'pose list')
     lead = poses.shape[:-1]
     flat = poses.reshape(-1, 3).contiguous()
+    controller = net
     net, mask = _resolve_mask(net, override_mask, poses.device)
-    if mask.spatial:
-        raise NotImplementedError('flow_at: per-point masks (StashedSpatialController, a mask grid) are evaluated on a (times, h, w) '
-                                  'grid only, with flow_fields')
+    if mask.spatial and controller is net:
+        raise NotImplementedError('flow_at: a mask grid at a pose list is a controller\'s (StashedSpatialController, or a linear controller '
+                                  'with the grid as override_mask): the interpolation of the grid is the controller\'s in the reference; a '
+                                  'bare model takes a grid on a (times, h, w) grid only, with flow_fields')
     if get_mask and not net.is_progressive:
         raise ValueError('get_mask needs a progressive network')
+    if mask.spatial and hasattr(controller, 'note_poses'):
+        controller.note_poses(flat)                      # stash_iteration finds the cells of these points
     params = [p for lin in net.linears() for p in (lin.weight, lin.bias)]
     enc_a = net.encode.effective_frequencies() if isinstance(getattr(net, 'encode', None), RotatedFourierFeatures) else None
     train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad) or
@@ -929,4 +991,8 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     out = _FlowAt.apply(net, flat, float(scale), train, mask, enc_a, bool(pose_grad), *params)
     if not planar:
         out = out.t().contiguous().view(*lead, 4)
+    if get_mask and mask.spatial:
+        with torch.no_grad():
+            used = flownet_sample_mask_points(net, flat.detach(), mask.tensor, mask.res, mask.centre_scale)
+        return out, used.view(*lead, used.shape[-1])
     return (out, mask.tensor) if get_mask else out

@@ -19,7 +19,8 @@ checkpoints and training curves depend on:
   * a checkpoint keeps `mask_stashed`, the SUM of the mask, and load_mask rebuilds `floor(sum)` ones followed by the fraction:
     a block of six entries ramping at 0.5 comes back as three ones.
 Calling a linear controller on a pose list, `controller(poses, override_mask=, get_mask=)`, is progressive_controller.py:45-53 on
-`flownet.flow_at`; `flow_fields` evaluates a controller on a grid.  StashedSpatialController evaluates grids only.
+`flownet.flow_at`; `flow_fields` evaluates a controller on a grid.  StashedSpatialController does both: `controller(poses)` is its
+reference form (progressive_controller.py:670-680), the interpolation inside the kernels; `mask_by` / `expand_by` stay out.
 
 StashedSpatialController keeps a mask PER GRID CELL, [res^3][515], and every point reads the trilinear interpolation of its box
 blur.  At res = 50 that is 257 MB, so unlike the linear controllers its state lives on the DEVICE, next to the model (`.to()` /
@@ -74,6 +75,8 @@ class ProgressiveEncoderController(nn.Module):
         """progressive_controller.py:45-53 on flow_at: the controller's own mask goes through `device_mask` (uploaded when it changed,
         with its k_active), an `override_mask` as flow_at takes it; `get_mask` among the keywords returns (out, that mask); `pose_grad=True` is flow_at's"""
         override_mask = kwargs.get('override_mask')
+        if override_mask is not None and override_mask.dim() == 2:    # a grid (res^3, 515): the per-point mask, interpolated by the kernels
+            return flow_at(self, x, 1.0, override_mask=override_mask, get_mask='get_mask' in kwargs, pose_grad=kwargs.get('pose_grad', False))
         out = flow_at(self, x, 1.0, override_mask=override_mask, pose_grad=kwargs.get('pose_grad', False))
         if 'get_mask' in kwargs:
             return out, self.mask if override_mask is None else override_mask
@@ -402,17 +405,32 @@ class StashedSpatialController(ProgressiveEncoderController):
 
     def note_grid(self, times, ys, xs):
         """flow_fields: the grid of points just evaluated; stash_iteration computes its cells when it needs them"""
-        self._last_grid = (times, ys, xs)
+        self._last_grid, self._last_list = (times, ys, xs), None
+        self.stash = (None, None)
+
+    def note_poses(self, x):
+        """flow_at: the pose list (N, 3) just evaluated, as note_grid"""
+        self._last_grid, self._last_list = None, x.detach().reshape(-1, 3)
         self.stash = (None, None)
 
     def _last_poses(self):
+        if self._last_list is not None:
+            return self._last_list
         if self._last_grid is None:
             raise RuntimeError('stash_iteration before any evaluation: no points to attribute the loss to')
         gt, gh, gw = torch.meshgrid(*self._last_grid, indexing='ij')
         return torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
 
     def __call__(self, x, **kwargs):
-        raise NotImplementedError('evaluate the controller on a (times, h, w) grid with sin_inn_amd.flownet.flow_fields')
+        """progressive_controller.py:670-680 on flow_at: the per-point mask is interpolated inside the kernels from this controller's blurred
+        grid, or from an `override_mask` grid (res^3, 515); `get_mask` among the keywords returns (out, the interpolated mask (..., 515));
+        `pose_grad=True` is flow_at's.  `mask_by` (a mask taken at other points) and `expand_by` (a function of the mask) are not built"""
+        for key in ('mask_by', 'expand_by'):
+            if key in kwargs:
+                raise NotImplementedError(f'StashedSpatialController: the `{key}` keyword is not supported: the mask is interpolated inside '
+                                          f'the kernels at the poses themselves')
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), get_mask='get_mask' in kwargs,
+                       pose_grad=kwargs.get('pose_grad', False))
 
     # ---- checkpoints ----
     def load_mask(self):
@@ -443,7 +461,7 @@ class StashedSpatialController(ProgressiveEncoderController):
         self._dirty = None
         self._in_progress_any = True
         self._loaded_open = 0
-        self._last_grid = None
+        self._last_grid = self._last_list = None
         self.cur_block = self.block_size
         self.next_block = self.block_size * 2
         self.block_iterations = block_iterations

@@ -21,6 +21,8 @@ call.  The FLOP counts stay those of the network; the interpolation is not count
 weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines in the backward pass) are not counted.
 --points N times the network at a pose list of N uniform random points of [-1, 1]^3 (flownet.flow_at, planar output: the kernels' own
 layout) instead of a grid; the --baseline is tools/fit_flow.composed_flow_at on the same list.  The FLOP counts are those of N points.
+--points N --spatial R [--pose-grad] calls the StashedSpatialController on the pose list (sininn_flownet_*_spatial_points); the --baseline is
+composed_flow_at under the controller's `interpolate` (gather + einsum, (N, 8, 515)) on every call.
 """
 import argparse
 import json
@@ -86,7 +88,6 @@ def main():
     a = ap.parse_args()
     assert a.points or not a.pose_grad, '--pose-grad: the coordinate gradient exists at pose lists (--points)'
     from fit_flow import composed_flow_at, composed_flow_fields
-    assert not (a.points and a.spatial), '--points: per-point masks are evaluated on grids only'
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
@@ -120,7 +121,7 @@ def main():
         if pose_grad:
             poses.requires_grad_(True)
             fixed = dict(fixed, pose_grad=True) if at is flownet.flow_at else fixed
-        kw = dict(override_mask=mask_dev) if prog and at is composed_flow_at else {}
+        kw = dict(override_mask=mask_dev) if prog and not a.spatial and at is composed_flow_at else {}
         up_p = torch.randn(4, n, device=dev)
         up_p = up_p if fixed else up_p.t().contiguous()          # the composed network returns (N, 4)
 

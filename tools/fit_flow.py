@@ -11,6 +11,7 @@
     python tools/fit_flow.py --net PRBF --controller spatial --res 7
     python tools/fit_flow.py --net RBF --points 4096
     python tools/fit_flow.py --net RBF --points 4096 --cycle
+    python tools/fit_flow.py --net PRBF --points 4096 --controller spatial --res 7 [--cycle]
 
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
@@ -33,6 +34,10 @@ MSE and FusedAdam; no warping, no images.  `--cycle` adds a forward-backward con
 flow12(p) (pixels turned into the pose units of the clip, the time unchanged: the clip's flow21 at a pose is the flow back onto that pose's
 frame), and flow21(p') + flow12(p) should vanish.  The second query is a chained one: its gradient reaches the parameters through p' as
 well (flow_at(.., pose_grad=True); composed: torch's autograd).  It runs the fused and the composed loop and prints the losses of both.
+`--points N --controller spatial --res R` puts a 515-wide progressive network under StashedSpatialController(net, R) and calls it the
+reference's way, controller(poses): fresh random points every step, the per-point squared error of flow12 stashed after the step (with
+`--cycle` the controller attributes it to the cells of the list it evaluated last, p', as the reference's stash does), `update_progress()`
+every `block_iterations` steps as on a grid.  Composed, the mask is the controller's `interpolate` (gather + einsum), (N, 515).
 
 The pair is seeded and analytic: frame1 is a smooth texture, frame2 the same texture displaced by a known smooth flow.
 `--composed` evaluates the network with torch's own ops (nn.functional.linear and elementwise ops) instead of the fused
@@ -127,8 +132,11 @@ def composed_flow_at(net, poses, scale=1.0, override_mask=None):
     """net(poses) * scale, (N, 3) -> (N, 4), with torch's own GPU ops: composed_flow_fields on a pose list (one frame of N x 1 points
     whose coordinates are the list), the baseline of `bench_flownet.py --points`"""
     mask = override_mask
-    if hasattr(net, 'mask'):                                      # a linear controller
-        mask = net.mask if mask is None else mask
+    if hasattr(net, 'mask'):                                      # a controller
+        if hasattr(net, 'interpolate'):                           # spatially adaptive: the reference's gather + einsum, (N, 515)
+            mask = net.interpolate(poses) if mask is None else mask
+        else:
+            mask = net.mask if mask is None else mask
         net = net.model
     x = poses
     if not hasattr(net, 'encode'):                                # siren
@@ -156,7 +164,7 @@ def composed_flow_at(net, poses, scale=1.0, override_mask=None):
     if net.is_progressive:
         x = torch.cat((poses, x), dim=-1)
         if mask is not None:
-            x = x * mask.to(x)[None, :]
+            x = x * (mask.to(x) if mask.dim() == 2 else mask.to(x)[None, :])
     return net.model.model(x) * scale
 
 
@@ -198,22 +206,30 @@ def cycle_term(query, poses, out):
 
 
 def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, lr=1e-3, seed=0, device='cuda', log=None,
-               max_iteration=1000, cycle=False, cycle_weight=1.0):
+               max_iteration=1000, cycle=False, cycle_weight=1.0, controller='early', res=7):
     """fit net(poses) to analytic_flow at `n_points` fresh uniform points of [-1, 1]^3 per step (a seeded generator): MSE, FusedAdam.
     `cycle`: plus cycle_weight x cycle_term, the forward-backward consistency at p' (a chained query).
     Returns the list of per-step losses (floats).  `info`: a dict that receives the network (the controller of a progressive one)
-    as info['net'] and, as info['first'], the first step's `poses`, `target` and the network's `state` before that step"""
+    as info['net'] and, as info['first'], the first step's `poses`, `target` and the network's `state` before that step.
+    `controller='spatial'`: a StashedSpatialController(net, res) called on the pose list; it stashes the per-point squared error of flow12
+    and runs update_progress every block_iterations steps (their number: info['progress'])"""
     from sin_inn_amd import FusedAdam, flownet, progressive
     torch.manual_seed(seed)
     net = flownet.flow_model_dict[name](flownet.ModelParams()).to(device)
-    if net.is_progressive:
+    assert controller in ('early', 'spatial'), controller
+    spatial = controller == 'spatial'
+    if spatial:
+        if not net.is_progressive or net.encoding_dim != 515:
+            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG); got {name}')
+        net = progressive.StashedSpatialController(net, res)
+    elif net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
     opt = FusedAdam(net.parameters(), lr=lr)
     gen = torch.Generator().manual_seed(seed + 1)
     at = composed_flow_at if composed else flownet.flow_at
     query = (lambda x: composed_flow_at(net, x, 1.0)) if composed else (lambda x: flownet.flow_at(net, x, 1.0, pose_grad=True))
     if info is not None:
-        info['net'] = net
+        info['net'], info['progress'] = net, 0
     losses = []
     for step in range(steps):
         poses = (torch.rand(n_points, 3, generator=gen) * 2 - 1).to(device)
@@ -227,7 +243,14 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
             loss = loss + cycle_weight * cycle_term(query, poses, out)
         loss.backward()
         opt.step()
-        net.stash_iteration(loss.detach())
+        if spatial:
+            net.stash_iteration((out.detach()[:, :2] - target[:, :2]).pow(2).sum(1))
+            if (step + 1) % net.block_iterations == 0:
+                net.update_progress()
+                if info is not None:
+                    info['progress'] += 1
+        else:
+            net.stash_iteration(loss.detach())
         losses.append(float(loss.detach()))
         if log:
             extra = f'  open {net.cur_block:3d} / {net.encoding_dim}' if net.is_progressive else ''
@@ -316,11 +339,12 @@ def main():
     if a.cycle:
         for what, comp in (('fused', False), ('composed', True)):
             losses = fit_points(a.net, a.points, a.steps, comp, lr=a.lr, seed=a.seed, log=lambda m, w=what: print(w, m),
-                                max_iteration=a.max_iteration, cycle=True)
+                                max_iteration=a.max_iteration, cycle=True, controller=a.controller, res=a.res)
             print(f'{what}: first {losses[0]:.6f}  last {losses[-1]:.6f}')
         return
     if a.points:
-        losses = fit_points(a.net, a.points, a.steps, a.composed, lr=a.lr, seed=a.seed, log=print, max_iteration=a.max_iteration)
+        losses = fit_points(a.net, a.points, a.steps, a.composed, lr=a.lr, seed=a.seed, log=print, max_iteration=a.max_iteration,
+                            controller=a.controller, res=a.res)
         print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
         return
     losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration,
