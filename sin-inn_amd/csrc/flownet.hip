@@ -34,7 +34,7 @@
 //           every wave has finished reading), the weights stream from L2 as 16-byte loads of nn.Linear's own [out][in] layout (no
 //           packing).  Layer 4 (256 -> 4) is 256 dot products on the vector ALU.  Training mode copies each post-ReLU tile to
 //           `saved` ([3][Npad][256]); inference writes the flows only.
-// backward  flownet_bwd_chain_kernel: per tile  dout = dflows * scale;  gW4 / gb4 partials in registers over the block's tiles;
+// backward  flownet_bwd_chain_kernel: per tile  dout = dflows * scale;  gW4 / gb4 partials in registers over the block's tiles (gb4 in double);
 //           dh3 = (dout W4) . [h3 > 0] on the vector ALU in place over the h3 tile;  dh2 = (dh3 W3) . [h2 > 0],
 //           dh1 = (dh2 W2) . [h1 > 0] with the forward's GEMM loop on transposed weights;  dh1..3 -> workspace.
 //           flownet_wgrad_kernel: gW_l[j][k] = sum_p dh_l[p][j] in_l[p][k] (in_1 = the regenerated encoding), gb_l = sum_p dh_l: a block
@@ -525,7 +525,8 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   const int hw = q.H * q.W;
 
-  float w4k[4], gw4[4] = {0.f, 0.f, 0.f, 0.f}, gb4 = 0.f;
+  float w4k[4], gw4[4] = {0.f, 0.f, 0.f, 0.f};
+  double gb4 = 0.0;                                    // four lanes, 64 terms per tile: a long sum of signed terms, kept in double
 #pragma unroll
   for (int c = 0; c < 4; ++c) w4k[c] = q.w[3][c * FN_HID + tid];
 
@@ -563,8 +564,8 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
       hs[p * FN_HS + tid] = h > 0.f ? v : 0.f;
     }
     if (tid < FN_OUT) {
-      float s = 0.f;
-      for (int p = 0; p < FN_P; ++p) s += dos[p * FN_OUT + tid];
+      double s = 0.0;
+      for (int p = 0; p < FN_P; ++p) s += (double)dos[p * FN_OUT + tid];
       gb4 += s;
     }
     __syncthreads();
@@ -596,7 +597,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
   float* const out = q.part + (size_t)blockIdx.x * (FN_OUT * FN_HID + FN_OUT);
 #pragma unroll
   for (int c = 0; c < 4; ++c) out[c * FN_HID + tid] = gw4[c];
-  if (tid < FN_OUT) out[FN_OUT * FN_HID + tid] = gb4;
+  if (tid < FN_OUT) out[FN_OUT * FN_HID + tid] = (float)gb4;
 }
 
 // part[chunk][j][k] = sum over the chunk's point tiles of dh[p][j] in[p][k]  (+ [chunk][256 * KF + j] = sum_p dh[p][j]);
@@ -726,15 +727,21 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
   }
 }
 
-// gw[i] = sum_c part[c][i] (i < nw), gb[i - nw] = sum_c part[c][i] (nw <= i < nw + nb): chunks in index order, always
+// gw[i] = sum_c part[c][i] (i < nw), gb[i - nw] = sum_c part[c][i] (nw <= i < nw + nb): chunks in index order, always.  The bias
+// sums (nb entries, up to 512 signed terms that largely cancel) are added in double and rounded once; the weights stay in fp32
 __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* part, int nparts, int nw, int nb, float* gw, float* gb) {
   const int i = blockIdx.x * FN_NTHR + threadIdx.x;
   if (i >= nw + nb) return;
   const size_t stride = (size_t)nw + nb;
-  float s = 0.f;
-  for (int c = 0; c < nparts; ++c) s += part[c * stride + i];
-  if (i < nw) gw[i] = s;
-  else gb[i - nw] = s;
+  if (i < nw) {
+    float s = 0.f;
+    for (int c = 0; c < nparts; ++c) s += part[c * stride + i];
+    gw[i] = s;
+  } else {
+    double s = 0.0;
+    for (int c = 0; c < nparts; ++c) s += (double)part[c * stride + i];
+    gb[i - nw] = (float)s;
+  }
 }
 
 // progressive layer 1: gw [256][515] = mask[k] * sum_c part[c][..] in chunk order (k < 3: the coordinate sums, else encoded column
@@ -959,8 +966,9 @@ template <int KIND> constexpr size_t posegrad_lds() { return FN_LDS + (size_t)(p
 
 // wt[c][j] = w1[j][feature of row c] for the rows of every pass (progressive: column 3 + feature, times its mask, an exact zero where the
 // mask is zero; a feature from LIVE on: zero), then four rows of the coordinate columns, wt[NP 256 + d][j] = w1[j][d] (progressive, d < 3;
-// else zero): their mask multiplies the finished sum.  spatial (with prog): column 3 + feature as it is, the kernel applies the point's
-// mask to dE.  block = row c; <E::LIVE, E::KW>: encodings of one shape share one kernel
+// else zero): their mask multiplies the finished sum, so the value is not scaled here, but a closed coordinate (m_d == 0) is an exact zero
+// as well: 0 x (a sum over a W1 column that holds NaN) would be NaN.  spatial (with prog): column 3 + feature and the coordinate columns
+// as they are, the kernel applies the point's mask to dE.  block = row c; <E::LIVE, E::KW>: encodings of one shape share one kernel
 template <int LIVE, int KW>
 __global__ __launch_bounds__(FN_NTHR) void flownet_posegrad_pack_kernel(const float* w1, const float* mask, float* wt, int prog, int spatial) {
   constexpr int ROWS = (KW + FN_HID - 1) / FN_HID * FN_HID;
@@ -968,7 +976,7 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_posegrad_pack_kernel(const fl
   const float* row = w1 + (size_t)j * (LIVE + (prog ? FN_DOM : 0));
   float v = 0.f;
   if (c >= ROWS) {
-    if (prog && c - ROWS < FN_DOM) v = row[c - ROWS];
+    if (prog && c - ROWS < FN_DOM) v = !spatial && mask[c - ROWS] == 0.f ? 0.f : row[c - ROWS];
   } else {
     const int k = (c & ~63) + 4 * (c & 15) + ((c >> 4) & 3);
     if (k < LIVE) {

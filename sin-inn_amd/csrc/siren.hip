@@ -171,9 +171,10 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(std::condit
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   const int hw = q.H * q.W;
 
-  float w5k[4], gw5[4] = {0.f, 0.f, 0.f, 0.f}, gb5 = 0.f, gw1[SR_IN] = {0.f, 0.f, 0.f}, gb1 = 0.f;
+  float w5k[4], gw5[4] = {0.f, 0.f, 0.f, 0.f}, gw1[SR_IN] = {0.f, 0.f, 0.f}, gb1 = 0.f;
 #pragma unroll
   for (int c = 0; c < 4; ++c) w5k[c] = q.w[SR_SINES][c * FN_HID + tid];
+  double gb5 = 0.0;                                    // as gb4 of flownet_bwd_chain_kernel: in double
 
   for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
     __syncthreads();                                   // the previous tile is done with hs / dos / cs
@@ -211,8 +212,8 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(std::condit
       hs[p * FN_HS + tid] = q.omega * v * co;
     }
     if (tid < FN_OUT) {
-      float s = 0.f;
-      for (int p = 0; p < FN_P; ++p) s += dos[p * FN_OUT + tid];
+      double s = 0.0;
+      for (int p = 0; p < FN_P; ++p) s += (double)dos[p * FN_OUT + tid];
       gb5 += s;
     }
     __syncthreads();
@@ -286,19 +287,24 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(std::condit
   out[SR_PART_GB1 + tid] = gb1;
 #pragma unroll
   for (int c = 0; c < 4; ++c) out[SR_PART_GW5 + c * FN_HID + tid] = gw5[c];
-  if (tid < FN_OUT) out[SR_PART_GB5 + tid] = gb5;
+  if (tid < FN_OUT) out[SR_PART_GB5 + tid] = (float)gb5;
 }
 
 // the chain kernel's partial sums, blocks in index order, into gW1 [256][3], gb1 [256], gW5 [4][256], gb5 [4]
 __global__ __launch_bounds__(FN_NTHR) void siren_reduce_kernel(const float* part, int nparts, float* gw1, float* gb1, float* gw5, float* gb5) {
   const int i = blockIdx.x * FN_NTHR + threadIdx.x;
   if (i >= SR_PART) return;
+  if (i >= SR_PART_GB5) {                              // the output bias: block sums that largely cancel, added in double, rounded once
+    double d = 0.0;
+    for (int c = 0; c < nparts; ++c) d += (double)part[(size_t)c * SR_PART + i];
+    gb5[i - SR_PART_GB5] = (float)d;
+    return;
+  }
   float s = 0.f;
   for (int c = 0; c < nparts; ++c) s += part[(size_t)c * SR_PART + i];
   if (i < SR_PART_GB1) gw1[i] = s;
   else if (i < SR_PART_GW5) gb1[i - SR_PART_GB1] = s;
-  else if (i < SR_PART_GB5) gw5[i - SR_PART_GW5] = s;
-  else gb5[i - SR_PART_GB5] = s;
+  else gw5[i - SR_PART_GW5] = s;
 }
 
 size_t part_floats(int ntiles) {
