@@ -290,8 +290,11 @@ def test_fused_3x3_subnet_matches_the_two_launch_path(rev, channels, hw):
     not the default dispatch: measured slower than the two launches it replaces).  Against the same block
     through the two-launch path (bf16 hidden tensor in HBM): the hidden values are rounded to bf16 once in both, from fp32 sums
     accumulated in another order -> a value next to a rounding boundary lands one bf16 ulp apart in a few channels (budget
-    8e-3 of the max-norm, 1.5e-3 L2); ragged image sizes (tiles cut by the border in x and y), both coupling
-    widths (24 | 24: 16-column interleave, 96 | 96: 32-column), both directions; and against the oracle's bf16 emulation."""
+    8e-3 of the max-norm, 1.5e-3 L2); ragged image sizes (tiles cut by the border in x and y), both directions; and against the
+    oracle's bf16 emulation.  Channels 48, 96 and 192 reach three of the kernel's instantiations: conv_sub3_bf16_kernel<48, 8>
+    (24 | 24, 16-column interleave), <96, 16> and <192, 16> (48 | 48 and 96 | 96, 32-column), each from Cin = 24, 48 or 96.  The
+    other seven supported (Np, HT) pairs, Cin = 8, 40 and 192, and every element against float64 (the hidden halo, cut tiles,
+    the padded K step): tests/test_gpu_conv_sub3_sizes.py."""
     import archs
     import sin_inn_amd as S
     from sin_inn_amd import _lib

@@ -356,6 +356,14 @@ def _carry_couple(v, t_ref, e_ref, bs, bt, inverse):
     return v.abs() * e_ref * grow + bt
 
 
+def logdet_budget(ppt, co, tiles_img, unit_l, labs, acc_s=None):
+    """Budget of the log-det added per image by a coupling epilogue: a block sums the L of at most ppt pixels x co channels in fp32 and
+    adds ONE atomic per image tile, each L is within 4 unit_l of float64 (unit_l: the relative unit of L's formula in fp32 torch);
+    labs = sum |L| per image.  acc_s [pixels][co] (optional): what the conv's own error in s carries over, |L'| <= 0.636."""
+    budget = ((ppt * co + tiles_img) * U + 4 * unit_l) * labs
+    return budget if acc_s is None else budget + 0.636 * acc_s.reshape(labs.shape[0], -1).sum(1)
+
+
 def _tails(ksize, shape, regime):
     import sin_inn_amd  # noqa: F401
     from sin_inn_amd import _lib, ops
@@ -403,7 +411,7 @@ def _tails(ksize, shape, regime):
         unit_y, unit_l = rel_unit(y32, y_ref, scale), rel_unit(L32, L_ref, L_ref.abs())
         ld_ref = (-1 if inverse else 1) * L_ref.reshape(b, -1).sum(1)
         labs = L_ref.abs().reshape(b, -1).sum(1)
-        ld_budget = ((ppt * co + grid['tiles_img']) * U + 4 * unit_l) * labs + 0.636 * acc[:, :co].reshape(b, -1).sum(1)
+        ld_budget = logdet_budget(ppt, co, grid['tiles_img'], unit_l, labs, acc[:, :co])
         lds = []
         for _ in range(2):                                 # float atomics: two runs agree within the budget, not bitwise
             out, y2 = fresh_out(m, w, co), fresh_out(m, w, co)
