@@ -695,6 +695,16 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
  *   is [256][24] / [256][27], progressive: an exact +0 where mask[k] is 0 and in an encoded column k >= 3 with k >= k_active; the three
  *   coordinate columns k < 3 are governed by the mask alone, whatever k_active is (as in the 515-wide networks).  The order of every sum is
  *   independent of k_active; the backward call is sininn_flownet_backward, workspace and `saved` have the sizes above.
+ * Piecewise-linear encoding (model.py:628-678 PieceWiseEncoding, MPFFModel model.py:600-604): encoding SININN_FLOWNET_PIECEWISE, enc_a =
+ *   frequencies [3][256] (the layout of the Fourier kind), enc_b unused, progressive = 1 and enc_dim = 515 only: the reference has no plain
+ *   network of this encoding, (5, 512, progressive 0) is refused.  For frequency f and a point x:
+ *     u = (x_t + 1) F[0][f] + (x_y + 1) F[1][f] + (x_x + 1) F[2][f] (each x_d + 1 one fp32 sum, then fused multiply-adds from t to x);
+ *     tri(w) = 2 r + 1 if r < 0 else 1 - 2 r,  r = fmod(w, 2) - 1, fmod TRUNCATING as C's and torch.fmod (the sign of w);
+ *     feature 2 f = tri(u), feature 2 f + 1 = tri(u + 1).
+ *   For w >= 0 that is a triangle wave of period 2 in [-1, 1]; for w < 0 the reference's values lie in (-5, -1] and jump at the negative
+ *   integers, and the kernels give those values.  The frequencies are constants: the backward call is sininn_flownet_backward, the
+ *   encgrad calls refuse this kind; masks, k_active, the spatial and the points calls are those of the other 515-wide networks.  The
+ *   coordinate gradient is piecewise constant, d feature / d x_d = -+2 F[d][f] with the sign of the branch the forward pass took.
  * Borrowed pointers, 16-byte aligned (axis vectors, biases and the mask: 4), the caller's stream, non-zero return + sininn_last_error.
  * sininn_flownet_supported: 1 if the sizes are the ones the kernels are built for, else 0 (callers raise, there is no second path).
  * ---------------------------------------------------------------------------------------------- */
@@ -702,6 +712,7 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
 #define SININN_FLOWNET_FOURIER 1 /* enc_a = frequencies [3][256], enc_b unused (FFN and UFF differ in the buffer only) */
 #define SININN_FLOWNET_RBFG 3    /* enc_a = offsets [256][3], enc_b = sigma [256] (2 is not an encoding of this library) */
 #define SININN_FLOWNET_PE 4      /* enc_a = freqs [4], enc_b unused; enc_dim 24 (progressive: 27)                   */
+#define SININN_FLOWNET_PIECEWISE 5 /* enc_a = frequencies [3][256], enc_b unused; progressive only, enc_dim 515  */
 typedef struct sininn_flownet_args {
   size_t struct_bytes;                    /* must be sizeof(sininn_flownet_args)                                          */
   int encoding;                           /* SININN_FLOWNET_*                                                             */

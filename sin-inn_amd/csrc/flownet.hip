@@ -7,6 +7,8 @@
 //                                                               (RBFG, 256 frequencies, model.py:375-387)
 //           | cos / sin (freqs_f x_d), feature 6 f + d the cosine, 6 f + 3 + d the sine   (PE, 4 frequencies x 3 coordinates: 24
 //                                                               features, model.py:321-340)
+//           | tri(u), tri(u + 1), u = (x + 1) . f_k, interleaved; tri(w) = 2 r + 1 if r < 0 else 1 - 2 r, r = fmod(w, 2) - 1 with
+//             torch.fmod's truncation          (MPFF, 256 frequencies, model.py:634-646; progressive only)
 //     h1 = relu(enc W1^T + b1)   h2 = relu(h1 W2^T + b2)   h3 = relu(h2 W3^T + b3)   out = h3 W4^T + b4        (model.py:36-43)
 //     flows[t][c][y][x] = out[p][c] * scale                                                                    (trainer.py:44)
 // fp32 on v_mfma_f32_16x16x4_f32.  Neither the N x 3 poses nor the N x 512 encoding exist in memory in either pass: a lane
@@ -113,6 +115,7 @@ struct LayerInput {
   static constexpr int KW = KW_;                       // ... padded to whole 16-feature K steps: encode4 gives exact zeros from LIVE on
   static constexpr bool ENC_B = ENC_B_;                // the encoding reads enc_b
   static constexpr bool FREQ_GRAD = FREQ_GRAD_;        // the gradient with respect to enc_a exists
+  static constexpr bool PLAIN = true;                  // the network without the coordinates and the mask exists (a row may say no)
   static constexpr int KSTEPS = KW / 16;
   static constexpr int width(bool prog) { return LIVE + (prog ? FN_DOM : 0); }   // enc_dim: a row of nn.Linear's W1
   static constexpr int w1_stride(bool prog) { return prog ? KW : LIVE; }         // a row of the W1 the forward reads: packed / in place
@@ -131,8 +134,14 @@ template <> struct Enc<SININN_FLOWNET_FOURIER> : LayerInput<512, 512, false, tru
 template <> struct Enc<SININN_FLOWNET_RBFG> : LayerInput<512, 512, true> { static constexpr const char* NAME = "RBFG"; };
 // 4 frequencies x 3 coordinates x (cos, sin), padded to two K steps
 template <> struct Enc<SININN_FLOWNET_PE> : LayerInput<24, 32> { static constexpr const char* NAME = "PE"; };
+// the triangle wave of MPFF: the shape of the Fourier kind, no frequency gradient; the reference has the progressive network only, so the
+// plain 512-wide form is refused and its kernels are not instantiated
+template <> struct Enc<SININN_FLOWNET_PIECEWISE> : LayerInput<512, 512> {
+  static constexpr const char* NAME = "PieceWise";
+  static constexpr bool PLAIN = false;
+};
 using Hidden = LayerInput<FN_HID, FN_HID>;             // layers 2 and 3, for their weight gradient
-constexpr int FN_KINDS[] = {SININN_FLOWNET_RBF, SININN_FLOWNET_FOURIER, SININN_FLOWNET_RBFG, SININN_FLOWNET_PE};
+constexpr int FN_KINDS[] = {SININN_FLOWNET_RBF, SININN_FLOWNET_FOURIER, SININN_FLOWNET_RBFG, SININN_FLOWNET_PE, SININN_FLOWNET_PIECEWISE};
 
 // f(std::integral_constant<int, KIND>) for the run-time `encoding`; `otherwise` for a value that is no encoding of this library
 template <class R, class F>
@@ -142,6 +151,7 @@ R for_kind(int encoding, R otherwise, F&& f) {
     case SININN_FLOWNET_FOURIER: return f(std::integral_constant<int, SININN_FLOWNET_FOURIER>{});
     case SININN_FLOWNET_RBFG: return f(std::integral_constant<int, SININN_FLOWNET_RBFG>{});
     case SININN_FLOWNET_PE: return f(std::integral_constant<int, SININN_FLOWNET_PE>{});
+    case SININN_FLOWNET_PIECEWISE: return f(std::integral_constant<int, SININN_FLOWNET_PIECEWISE>{});
     default: return otherwise;
   }
 }
@@ -281,6 +291,24 @@ __device__ __forceinline__ void fourier_sincos(const Coord c, float fa, float fb
   sincospif(2.f * r, &s, &co);
 }
 
+// the piecewise-linear kind (model.py:638-644).  piecewise_arg: u = (c + 1) . f for one frequency f = (fa, fb, fc), each c_d + 1 rounded
+// as the reference rounds it before its matmul; explicit fmaf, for the reason recorded at the RBF branch below.  piecewise_rem:
+// r = fmod(w, 2) - 1 with torch.fmod's truncation (the sign follows the dividend, NOT the floor-mod of the RBFG branch):
+// w - 2 trunc(w / 2) is exact in fp32, the quotient's integer part is exact and the difference lies on w's own grid.  The feature is
+// 2 r + 1 where r < 0, else 1 - 2 r; for w < 0 that is the reference's value in (-5, -1], jumps at the negative integers included.
+// encode4 and FeatureGrad4 call these and take the same branch on the same r
+__device__ __forceinline__ float piecewise_arg(const Coord c, float fa, float fb, float fc) {
+  const float xt = c.t + 1.f, xy = c.y + 1.f, xx = c.x + 1.f;
+  return fmaf(xx, fc, fmaf(xy, fb, xt * fa));
+}
+
+__device__ __forceinline__ float piecewise_rem(float w) { return fmaf(-2.f, truncf(0.5f * w), w) - 1.f; }
+
+__device__ __forceinline__ float piecewise_tri(float w) {
+  const float r = piecewise_rem(w);
+  return r < 0.f ? fmaf(2.f, r, 1.f) : fmaf(-2.f, r, 1.f);
+}
+
 // features f0 .. f0 + 3 (f0 % 4 == 0) of one point
 template <int KIND>
 __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int f0) {
@@ -340,6 +368,17 @@ __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int
         v = r < 3 ? co : sn;
       }
       o[j] = v;
+    }
+  } else if constexpr (KIND == SININN_FLOWNET_PIECEWISE) {
+    const int f = f0 >> 1;                                                 // frequencies [3][256]
+    const f32x2 fa = *reinterpret_cast<const f32x2*>(q.enc_a + f);
+    const f32x2 fb = *reinterpret_cast<const f32x2*>(q.enc_a + 256 + f);
+    const f32x2 fc = *reinterpret_cast<const f32x2*>(q.enc_a + 512 + f);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const float w = piecewise_arg(c, fa[u], fb[u], fc[u]);
+      o[2 * u] = piecewise_tri(w);
+      o[2 * u + 1] = piecewise_tri(w + 1.f);
     }
   } else {
     const int f = f0 >> 1;                                                 // frequencies [3][256]
@@ -1076,6 +1115,16 @@ struct FeatureGrad4 {
         g[1] = d == 1 ? g[1] + t : g[1];
         g[2] = d == 2 ? g[2] + t : g[2];
       }
+    } else if constexpr (KIND == SININN_FLOWNET_PIECEWISE) {   // d e / d x_d = s F[d][f], s = +2 where the forward's own r < 0, else -2
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const float w = piecewise_arg(c, par[3 * u], par[3 * u + 1], par[3 * u + 2]);
+        const float s0 = piecewise_rem(w) < 0.f ? 2.f : -2.f, s1 = piecewise_rem(w + 1.f) < 0.f ? 2.f : -2.f;
+        const float t = fmaf(dz[2 * u + 1], s1, dz[2 * u] * s0);             // both products are exact
+        g[0] = fmaf(t, par[3 * u], g[0]);
+        g[1] = fmaf(t, par[3 * u + 1], g[1]);
+        g[2] = fmaf(t, par[3 * u + 2], g[2]);
+      }
     } else {                                             // 2 pi F[d][f] (dz_sin cos(phi) - dz_cos sin(phi))
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -1271,14 +1320,18 @@ int flownet_supported(const sininn_flownet_args* a, const char* who) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
   const bool prog = a->progressive == 1;
   const bool ok = (a->progressive == 0 || prog) && a->hidden == FN_HID && a->layers == 3 && a->out_dim == FN_OUT &&
-                  for_kind(a->encoding, false, [&](auto k) { return a->enc_dim == Enc<decltype(k)::value>::width(prog); });
+                  for_kind(a->encoding, false, [&](auto k) {
+                    using E = Enc<decltype(k)::value>;
+                    return a->enc_dim == E::width(prog) && (prog || E::PLAIN);
+                  });
   if (!ok) {
     std::string table;
     for (int kind : FN_KINDS)
       for_kind(kind, 0, [&](auto k) {
         using E = Enc<decltype(k)::value>;
-        table += std::string(table.empty() ? "" : ", ") + E::NAME + " " + std::to_string(E::width(false)) + " (progressive: " +
-                 std::to_string(E::width(true)) + ")";
+        table += std::string(table.empty() ? "" : ", ") + E::NAME + " " +
+                 (E::PLAIN ? std::to_string(E::width(false)) + " (progressive: " + std::to_string(E::width(true)) + ")"
+                           : "progressive only: " + std::to_string(E::width(true)));
         return 0;
       });
     set_error("%s: unsupported network (encoding %d, %d -> %d x %d -> %d, progressive %d; built for %s -> %d x 3 -> %d)", who, a->encoding,
@@ -1327,7 +1380,7 @@ static int check_head(const sininn_flownet_args* a, const char* who, const Spati
   if (!spatial) return 0;
   SININN_CHECK(a->progressive == 1, "%s: a spatial mask needs a progressive network (progressive = 1)", who);
   SININN_CHECK(a->enc_dim == FN_GW,
-               "%s: spatial masks are built for the %d-wide progressive encodings (PRBF, PFF / PUFF / PRFF, PRBFG); PPE (enc_dim %d, a packed "
+               "%s: spatial masks are built for the %d-wide progressive encodings (PRBF, PFF / PUFF / PRFF, PRBFG, MPFF); PPE (enc_dim %d, a packed "
                "narrow layer 1 of its own) is out of scope for this mode", who, FN_GW, a->enc_dim);
   SININN_CHECK(spatial->grid != nullptr && spatial->centre_scale != nullptr, "%s: null grid / centre_scale", who);
   SININN_CHECK(spatial->res >= 3, "%s: res %d (at least 3)", who, spatial->res);
@@ -1374,10 +1427,12 @@ static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& 
 template <class F>
 static int for_mode(const sininn_flownet_args* a, bool spatial, F&& f) {
   return for_kind(a->encoding, 1, [&](auto k) {
-    if constexpr (Enc<decltype(k)::value>::width(true) == FN_GW) {
+    using E = Enc<decltype(k)::value>;
+    if constexpr (E::width(true) == FN_GW) {
       if (spatial) return f(k, std::true_type{}, std::true_type{});
     }
-    return a->progressive ? f(k, std::true_type{}, std::false_type{}) : f(k, std::false_type{}, std::false_type{});
+    if constexpr (!E::PLAIN) return f(k, std::true_type{}, std::false_type{});   // flownet_supported has refused the plain form
+    else return a->progressive ? f(k, std::true_type{}, std::false_type{}) : f(k, std::false_type{}, std::false_type{});
   });
 }
 

@@ -7,6 +7,7 @@ backward in libsininn.so (csrc/flownet.hip).
     UniformRadialBasisGridEncoding / RbfgModel / PRBFGModel    video-interpolation/model.py:369-415, 508-523, 614-618 (grid_model_dict)
     PositionalEncoding / PEModel / PPEModel                    video-interpolation/model.py:321-340, 472-487, 607-611 (positional_model_dict)
     SineLayer / SirenModel                                     video-interpolation/model.py:123-146, 149-171 (siren_model_dict)
+    PieceWiseEncoding / MPFFModel                              video-interpolation/model.py:628-678, 600-604 (piecewise_model_dict)
     flow_fields                                                FlowTrainer.forward, video-interpolation/trainer.py:37-45
     flow_at / net(poses)                                       net(poses) of trainer.py:43-44, pair_flow.py:58-59
 
@@ -47,6 +48,14 @@ its sines.  Layer 1 is [256][24] (PPE: [256][27], mask of 27 values, blocks of 6
 multiple of 7 and is the formula above where it runs; the kernels evaluate the formula for every N.  In the kernels it is the one
 encoding with a narrow layer 1 (two 16-feature K steps instead of 32, a 32-column weight-gradient tile).
 
+`MPFF` (`MPFFModel`, progressive only) uses the piecewise-linear encoding: the buffer `encode.frequencies` [3][256] (non-negative, columns
+of ascending magnitude), u = (x + 1) @ frequencies, feature 2 f = tri(u_f), feature 2 f + 1 = tri(u_f + 1) with
+`tri(w) = 2 r + 1 if r < 0 else 1 - 2 r`, `r = fmod(w, 2) - 1` and torch.fmod's truncation: a triangle wave of period 2 for w >= 0, and for
+w < 0 (points outside [-1, 1]^3) the reference's own values in (-5, -1], reproduced as they are.  An encoding of its own in the kernels
+(`PIECEWISE = 5`), the rest is the path of `PFF`: global masks and `k_active`, the spatial controller, pose lists, and a coordinate gradient
+that is piecewise constant (-+2 F[d][f], the sign of the branch the forward pass took).  The reference's `model_dict` does not hold it and
+neither does `all_model_dict`: it is registered in `piecewise_model_dict`, beside it, and the command line stays closed.
+
 `siren` (`SirenModel`) has no encoding: four `SineLayer`s, `sin(30 (W h + b))`, the first on the three raw coordinates, and a plain
 last nn.Linear (`state_dict` keys `model.{0..3}.linear.{weight,bias}`, `model.4.{weight,bias}`; every nn.Linear draws its own init first,
 then `weight.uniform_`).  It runs in kernels of its own (csrc/siren.hip, `siren_forward` / `siren_backward`) behind the same
@@ -85,9 +94,9 @@ Per-point masks at pose lists: `controller(poses)` of a `StashedSpatialControlle
 interpolates it under no_grad: the pose gradient has no d mask / d pose term.  A bare progressive model with a grid is still refused at a
 pose list: the interpolation is a controller's.
 
-Out of scope: `MPFF`, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
+Out of scope: a plain (non-progressive) piecewise network and a frequency gradient for that encoding, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
 `--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
-closed (video-interpolation/main.py still refuses it).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
+closed, and of `MPFF` its `--net MPFF` (video-interpolation/main.py still refuses both).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
 `sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
 `sin_inn_amd.FusedLAMB` is the reference's apex FusedLAMB (trainer.py:134-135) restated, `sin_inn_amd.FusedAdam` drives them as well.
 """
@@ -104,7 +113,7 @@ from .ops import _stream, ptr
 
 check = _lib.check
 EPSILON = 1e-4
-RBF, FOURIER, RBFG, PE = 0, 1, 3, 4
+RBF, FOURIER, RBFG, PE, PIECEWISE = 0, 1, 3, 4, 5
 
 
 class ModelParams:
@@ -278,6 +287,47 @@ class PositionalEncoding(nn.Module):
         return self.freqs, None
 
 
+class PieceWiseEncoding(nn.Module):
+    """model.py:628-657 (one buffer; evaluated inside the kernels): u = (x + 1) @ frequencies, features tri(u), tri(u + 1) interleaved,
+    tri(w) = 2 r + 1 if r < 0 else 1 - 2 r with r = fmod(w, 2) - 1 (torch.fmod: the sign of w)."""
+    kind = PIECEWISE
+
+    def __init__(self, domain_dim, num_frequencies, std):
+        super().__init__()
+        self.domain_dim = domain_dim
+        self.num_frequencies = num_frequencies
+        self.register_buffer('frequencies', self.init_frequencies(std))
+
+    @property
+    def output_channels(self):
+        return 2 * self.num_frequencies
+
+    def kernel_buffers(self):
+        return self.frequencies, None
+
+
+class GaussianRandomPieceWiseEncoding(PieceWiseEncoding):
+    """model.py:660-667: |N(0, std / 2 pi)| per entry, the columns sorted by their norm."""
+
+    def init_frequencies(self, std):
+        frequencies = torch.randn(self.domain_dim, self.num_frequencies) * std / (2 * math.pi)
+        frequencies = frequencies.abs()
+        order = frequencies.norm(2, 0).argsort()
+        return frequencies[:, order]
+
+
+class UniformPieceWiseEncoding(PieceWiseEncoding):
+    """model.py:670-678: magnitudes linspace(0, std sqrt(12) / 2 pi) plus half a step, along the absolute values of one normal draw
+    (domain_dim, num_frequencies), normalised per column.  The bound is a float64 scalar, as the reference's numpy expression is."""
+
+    def init_frequencies(self, std):
+        b = std * math.sqrt(12) / (2 * math.pi)
+        magnitude = torch.linspace(0, b, self.num_frequencies)
+        magnitude = magnitude + magnitude[1] / 2
+        frequencies = torch.randn(self.domain_dim, self.num_frequencies).abs()
+        return nnf.normalize(frequencies, p=2, dim=0) * magnitude[None, :]
+
+
 # encoding name -> its one constructor call; the plain and the progressive model of an encoding share it
 ENCODINGS = {
     'RBF': lambda opt: RadialBasisEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf),
@@ -286,6 +336,8 @@ ENCODINGS = {
     'RFF': lambda opt: GaussianRotatedFourierFeatures(opt.domain_dim, opt.num_frequencies, opt.std),
     'RBFG': lambda opt: UniformRadialBasisGridEncoding(opt.domain_dim, opt.num_frequencies, opt.std_rbf),
     'PE': lambda opt: PositionalEncoding(opt.domain_dim, opt.num_frequencies_pe),
+    'MPFF': lambda opt: UniformPieceWiseEncoding(opt.domain_dim, opt.num_frequencies, opt.std),
+    'GMPFF': lambda opt: GaussianRandomPieceWiseEncoding(opt.domain_dim, opt.num_frequencies, opt.std),   # no reference network names it
 }
 
 
@@ -443,8 +495,11 @@ class SirenModel(nn.Module):
         return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False))
 
 
+# the piecewise-linear progressive network (model.py:600-604): beside all_model_dict, like siren; the reference's model_dict lacks it too
+MPFFModel = _model('MPFFModel', ProgressiveModel, 'MPFF', 'model.py:600-604.')
+piecewise_model_dict = {'MPFF': MPFFModel}
 siren_model_dict = {'siren': SirenModel}                          # beside all_model_dict: the command line does not open it yet
-flow_model_dict = {**all_model_dict, **siren_model_dict}          # every network flow_fields evaluates: what the tools offer
+flow_model_dict = {**all_model_dict, **piecewise_model_dict, **siren_model_dict}          # every network flow_fields evaluates: what the tools offer
 
 
 def _on_gpu(t, what='tensor'):

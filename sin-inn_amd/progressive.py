@@ -1,5 +1,5 @@
 """The controllers of the progressive encoding (video-interpolation/progressive_controller.py:14-158): a module around a
-progressive model (`sin_inn_amd.flownet.PRBFModel` / `PFFModel` / `PUFFModel`) that owns the per-feature mask and opens it
+progressive model (`sin_inn_amd.flownet.PRBFModel` / `PFFModel` / `PUFFModel` / .. / `MPFFModel`) that owns the per-feature mask and opens it
 block by block as training goes on, as video-interpolation/main.py:136-143 wraps every `is_progressive` network.
 
     ProgressiveEncoderController   progressive_controller.py:14-92
@@ -31,6 +31,9 @@ otherwise).  The box blurs (mask and loss log) are sums of shifted slices, axis 
 conv3d: the same numbers to fp32 rounding, bitwise the same whether six columns or all 515 are blurred, and no convolution library
 in a training step.  `stash_iteration` takes the per-point loss the class is written for; the reference's own trainer passes a
 scalar there and fails with an IndexError, here that is a ValueError that says so.
+
+Every 515-wide progressive network runs under every controller here, `MPFFModel` (the piecewise-linear encoding) included; `PPEModel`
+(27 wide) under the linear ones only.
 
 Out of scope: FixedSpatialController, AdaptiveController, the `--spatially-adaptive` switch of video-interpolation/main.py, and
 `mask_dim` other than the three coordinates.

@@ -7,7 +7,7 @@ FLOP counts come from the shapes (2 N (E*256 + 2*256*256 + 256*4) forward, E = 5
 the weight gradients of all four); `mfma_peak_share` is those executed FLOPs over the event time against the 157.3 TFLOP/s f32
 matrix peak of an MI355X -- the share of the whole call, not of one kernel.  --baseline times the same module composed from
 torch's own GPU ops (tools/fit_flow.composed_flow_fields) in the same process, alternating windows with the fused path.
-The progressive nets (PRBF, PFF, PUFF, PRBFG, PPE) run under a prefix mask of --k-active leading ones (default 515: all ones; clamped to
+The progressive nets (PRBF, PFF, PUFF, PRBFG, PPE, MPFF) run under a prefix mask of --k-active leading ones (default 515: all ones; clamped to
 the network's width, 27 for PPE), given as a
 host tensor so that the kernels skip the closed features as they do under a controller; the FLOP counts stay those of the full
 network, so the share of a skipped run is not a utilisation.  The mask sits in a controller, which uploads it once.

@@ -7,6 +7,7 @@
     python tools/fit_flow.py --net RBFG
     python tools/fit_flow.py --net PPE
     python tools/fit_flow.py --net siren
+    python tools/fit_flow.py --net MPFF
     python tools/fit_flow.py --optimizer lamb
     python tools/fit_flow.py --net PRBF --controller spatial --res 7
     python tools/fit_flow.py --net RBF --points 4096
@@ -16,7 +17,7 @@
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
 
-A progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, PPE) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
+A progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, PPE, MPFF) is wrapped in LinearControllerEarly(net, max_iteration, epsilon=1e-3) as
 video-interpolation/main.py:136-143 does, and the controller sees the loss after every step (trainer.py:75), which opens the mask.
 
 `--controller spatial [--res R]` wraps a 515-wide progressive network in StashedSpatialController(net, R) instead (the reference's
@@ -75,13 +76,26 @@ def make_pair(h, w, seed, device):
     return f1[None].to(device).contiguous(), f2[None].to(device).contiguous(), torch.stack((u, v))[None].to(device)
 
 
+PIECEWISE = 5                                                     # sin_inn_amd.flownet.PIECEWISE: the `kind` of MPFF's encoding
+
+
+def composed_piecewise(enc, x):
+    """PieceWiseEncoding.forward, model.py:634-646 line by line, on the port's buffer (out of place where the reference assigns
+    through a mask: autograd-safe, the same values)"""
+    out = torch.matmul(x + 1, enc.frequencies)
+    out = torch.stack((out, out + 1), dim=2).view(-1, enc.output_channels)
+    out = torch.fmod(out, 2) - 1
+    return torch.where(out.lt(0), 2 * out + 1, 1 - 2 * out)
+
+
 def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     """FlowTrainer.forward (trainer.py:37-45) with torch's own GPU ops on the port's buffers and parameters: what a user of the
     reference runs, and the baseline of tools/bench_flownet.py.  A progressive network reads cat((poses, encoding)) times the
     mask of its controller (or `override_mask`; a bare network: no mask), model.py:532-535 and 89-99.  A learnable encoding (RFF /
     PRFF) normalises its frequencies and scales them by the magnitudes on every call, model.py:274.  The radial-basis grid (RBFG / PRBFG)
     is model.py:375-387 line by line, with its N x 256 x 2 x 3 intermediate; the positional encoding (PE / PPE) is the einsum / cat of
-    model.py:331-332, without the `.view(-1, 21)` that raises unless N is a multiple of 7 (the cat is already (N, 4, 6)).  A SirenModel has
+    model.py:331-332, without the `.view(-1, 21)` that raises unless N is a multiple of 7 (the cat is already (N, 4, 6)); the piecewise-linear
+    encoding (MPFF) is composed_piecewise.  A SirenModel has
     no encoding: sin(omega_0 * linear(x)) four times and the last nn.Linear, model.py:145-146, 163-171."""
     mask = override_mask
     spatial = None
@@ -109,6 +123,8 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     elif hasattr(enc, 'freqs'):
         x = torch.einsum('f,nd->nfd', enc.freqs, x)
         x = torch.cat((torch.cos(x), torch.sin(x)), dim=2).view(x.shape[0], -1)
+    elif getattr(enc, 'kind', None) == PIECEWISE:
+        x = composed_piecewise(enc, x)
     elif hasattr(enc, 'offsets'):
         x_a = x[:, None, :] + enc.offsets[None, :]
         x_b = x_a + (1 / enc.sigma[None, :, None])
@@ -150,6 +166,8 @@ def composed_flow_at(net, poses, scale=1.0, override_mask=None):
     elif hasattr(enc, 'freqs'):
         x = torch.einsum('f,nd->nfd', enc.freqs, x)
         x = torch.cat((torch.cos(x), torch.sin(x)), dim=2).view(x.shape[0], -1)
+    elif getattr(enc, 'kind', None) == PIECEWISE:
+        x = composed_piecewise(enc, x)
     elif hasattr(enc, 'offsets'):
         x_a = x[:, None, :] + enc.offsets[None, :]
         x_b = x_a + (1 / enc.sigma[None, :, None])
@@ -220,7 +238,7 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
     spatial = controller == 'spatial'
     if spatial:
         if not net.is_progressive or net.encoding_dim != 515:
-            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG); got {name}')
+            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, MPFF); got {name}')
         net = progressive.StashedSpatialController(net, res)
     elif net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
@@ -270,7 +288,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     spatial = controller == 'spatial'
     if spatial:
         if not net.is_progressive or net.encoding_dim != 515:
-            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG); got {net_name}')
+            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, MPFF); got {net_name}')
         net = progressive.StashedSpatialController(net, res)
     elif net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
