@@ -738,6 +738,24 @@ size_t sininn_flownet_workspace_bytes(int64_t n_points);
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_forward(const sininn_flownet_args* args, void* stream);
 int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
+/* Two coordinates per point (one frame pair: video-interpolation/pair_flow.py, ModelParams(domain_dim=2), poses (y, x)).  The dimension is an
+ * ARGUMENT of these entry points; the descriptor, its size and its tag are unchanged, and domain_dim = 3 makes each of them the call of the
+ * same name without `_dim` (the same kernels, the same bits).  With domain_dim = 2:
+ *   networks  SININN_FLOWNET_RBF (enc_a = centres [512][2]), SININN_FLOWNET_FOURIER (enc_a = frequencies [2][256], rows y, x) and
+ *             SININN_FLOWNET_RBFG (enc_a = offsets [256][2]); enc_b as above.  enc_dim 512, w[0] [256][512]; progressive: enc_dim 514, w[0]
+ *             [256][514] = the columns of cat((y, x), enc), mask [514], k_active 0 .. 514, gw[0] [256][514] with an exact +0 where the mask is
+ *             zero or an encoded column lies past k_active.  Every encoder evaluates the reference's two-term expressions; no t term exists.
+ *   points    the descriptor's grid is (ys, xs): T must be 1, `times` is not read (NULL is fine), flows / dflows are [1][4][H][W]; the
+ *             `_points_dim` calls take poses [n][2], columns (y, x), and the planar [4][n] flows / dflows of the `_points` calls.
+ *   sizes     sininn_flownet_saved_bytes, sininn_flownet_workspace_bytes and sininn_flownet_forward_workspace_bytes are those above.
+ *   refused   SININN_FLOWNET_PE and SININN_FLOWNET_PIECEWISE (sininn_flownet_supported_dim is 0, the error names the dimension), any other
+ *             domain_dim, T != 1.  The frequency gradient, the coordinate gradient and the per-point masks have no call that takes a dimension:
+ *             they exist for three coordinates only. */
+int sininn_flownet_supported_dim(const sininn_flownet_args* args, int domain_dim);
+int sininn_flownet_forward_dim(const sininn_flownet_args* args, int domain_dim, void* stream);
+int sininn_flownet_backward_dim(const sininn_flownet_args* args, int domain_dim, void* stream);
+int sininn_flownet_forward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream);
+int sininn_flownet_backward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream);
 size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args);
 int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
                                     void* stream);

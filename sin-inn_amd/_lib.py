@@ -277,6 +277,11 @@ _SIGS = {
     'sininn_bayer_demosaic': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'sininn_frames_to_u8': (C.c_int, [c_f, I64x4, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'sininn_flownet_supported': (C.c_int, [C.POINTER(FlowNetArgs)]),
+    'sininn_flownet_supported_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int]),
+    'sininn_flownet_forward_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, C.c_void_p]),
+    'sininn_flownet_backward_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, C.c_void_p]),
+    'sininn_flownet_forward_points_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, c_f, C.c_int64, C.c_void_p]),
+    'sininn_flownet_backward_points_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, c_f, C.c_int64, C.c_void_p]),
     'sininn_flownet_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_flownet_workspace_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_flownet_forward_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),

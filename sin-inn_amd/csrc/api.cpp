@@ -119,6 +119,9 @@ int profile_classes_bytes(int n, double* bytes);
 void profile_begin(int h, unsigned long long* stamps, int max_launches);
 int profile_end(int* count, float* total_ms);
 int flownet_supported(const sininn_flownet_args* a, const char* who);
+int flownet_supported_dim(const sininn_flownet_args* a, int dim, const char* who);
+int flownet_forward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st);
+int flownet_backward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st);
 size_t flownet_saved_bytes(int64_t n);
 size_t flownet_workspace_bytes(int64_t n);
 size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a);
@@ -606,6 +609,21 @@ int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 }
 
 int sininn_flownet_supported(const sininn_flownet_args* args) { return flownet_supported(args, "sininn_flownet_supported"); }
+int sininn_flownet_supported_dim(const sininn_flownet_args* args, int domain_dim) {
+  return flownet_supported_dim(args, domain_dim, "sininn_flownet_supported_dim");
+}
+int sininn_flownet_forward_dim(const sininn_flownet_args* args, int domain_dim, void* stream) {
+  return flownet_forward_dim_launch(args, domain_dim, nullptr, 0, 0, ST(stream));
+}
+int sininn_flownet_backward_dim(const sininn_flownet_args* args, int domain_dim, void* stream) {
+  return flownet_backward_dim_launch(args, domain_dim, nullptr, 0, 0, ST(stream));
+}
+int sininn_flownet_forward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream) {
+  return flownet_forward_dim_launch(args, domain_dim, poses, n, 1, ST(stream));
+}
+int sininn_flownet_backward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream) {
+  return flownet_backward_dim_launch(args, domain_dim, poses, n, 1, ST(stream));
+}
 size_t sininn_flownet_saved_bytes(int64_t n_points) { return flownet_saved_bytes(n_points); }
 size_t sininn_flownet_workspace_bytes(int64_t n_points) { return flownet_workspace_bytes(n_points); }
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args) { return flownet_forward_workspace_bytes(args); }

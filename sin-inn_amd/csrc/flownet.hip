@@ -62,6 +62,15 @@
 //           call's bits.  Combined with the spatial mode (sininn_flownet_*_spatial_points) it is PoseList plus Spatial in one FlowNetDev:
 //           the SPATIAL instantiations below take a point's coordinates through point_coord as well, so they serve a pose list as they are.
 //
+// two coordinates (sininn_flownet_*_dim with domain_dim = 2: one frame pair, poses (y, x)) the number of coordinates is a template
+//           parameter DIM of flownet_fwd_kernel, flownet_wgrad_kernel, flownet_pack_kernel and flownet_reduce_l1_kernel, 3 by default: the
+//           three-coordinate instantiations are the code they were.  DIM = 2 exists for the Enc<> rows that say PAIR (RBF, Fourier, RBFG):
+//           point_coord_dim<2> reads two values per point, encode4<KIND, 2> reads centres [512][2] / frequencies [2][256] / offsets [256][2]
+//           and evaluates two-term expressions (no zero is fed for t: in RBFG it would not drop out), the progressive W1 is [256][514] and
+//           its two coordinate columns fill the [256][4] K group with two zero columns, the coordinate sums of gW1 are two.  The chain
+//           kernel, the hidden layers' weight gradient and every workspace size do not see the dimension.  No per-point mask, frequency
+//           gradient or pose gradient at DIM = 2: no entry point offers them.
+//
 // pose gradient (sininn_flownet_backward_posegrad_points) after the whole backward of a points call: flownet_posegrad_kernel contracts
 //           dE = dh1 W1 (the GEMM of the frequency gradient, for every encoding) with the analytic derivative of the encoding over the
 //           FEATURES of each point: g_poses [N][3].  A tile owns its points: no partial sums in memory, no atomics, a fixed order.  DESIGN 14.8
@@ -97,7 +106,8 @@ constexpr int FN_WT = 128;          // weight-gradient output tile (FN_WT x FN_W
 constexpr int FN_WS = FN_WT + 16;   // floats per point row of a weight-gradient operand tile (4 rows x 16 lanes -> 64 banks)
 constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunks) x (output tiles) is about 512 blocks
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
-constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features
+constexpr int FN_FWD_MAX_BLOCKS = 2048;   // the forward launch: at most this many blocks, grid-stride over the 64-point tiles
+constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features (two of them at domain_dim = 2)
 constexpr int FN_GW = 512 + FN_DOM;  // spatial: floats per row of the mask grid and of the W1 it goes with
 constexpr int FN_CN = 16;           // spatial: floats per point of the corner tile in LDS: 8 weights, 8 row offsets
 constexpr size_t FN_CN_LDS = (size_t)(FN_P * FN_CN) * sizeof(float);
@@ -116,8 +126,9 @@ struct LayerInput {
   static constexpr bool ENC_B = ENC_B_;                // the encoding reads enc_b
   static constexpr bool FREQ_GRAD = FREQ_GRAD_;        // the gradient with respect to enc_a exists
   static constexpr bool PLAIN = true;                  // the network without the coordinates and the mask exists (a row may say no)
+  static constexpr bool PAIR = false;                  // the kernels exist for two coordinates per point as well (a row may say yes)
   static constexpr int KSTEPS = KW / 16;
-  static constexpr int width(bool prog) { return LIVE + (prog ? FN_DOM : 0); }   // enc_dim: a row of nn.Linear's W1
+  static constexpr int width(bool prog, int dim = FN_DOM) { return LIVE + (prog ? dim : 0); }   // enc_dim: a row of nn.Linear's W1
   static constexpr int w1_stride(bool prog) { return prog ? KW : LIVE; }         // a row of the W1 the forward reads: packed / in place
   static constexpr size_t PACK_FLOATS = (size_t)FN_HID * (KW + FN_CS);           // progressive: W1p [256][KW] and wc [256][4]
   // the weight gradient: a block owns 128 x KT outputs, a wave AT x AT accumulator tiles (wide: 64 x 64, narrow: 32 x 32)
@@ -129,9 +140,18 @@ struct LayerInput {
 };
 
 template <int KIND> struct Enc;
-template <> struct Enc<SININN_FLOWNET_RBF> : LayerInput<512, 512, true> { static constexpr const char* NAME = "RBF"; };
-template <> struct Enc<SININN_FLOWNET_FOURIER> : LayerInput<512, 512, false, true> { static constexpr const char* NAME = "Fourier"; };
-template <> struct Enc<SININN_FLOWNET_RBFG> : LayerInput<512, 512, true> { static constexpr const char* NAME = "RBFG"; };
+template <> struct Enc<SININN_FLOWNET_RBF> : LayerInput<512, 512, true> {
+  static constexpr const char* NAME = "RBF";
+  static constexpr bool PAIR = true;
+};
+template <> struct Enc<SININN_FLOWNET_FOURIER> : LayerInput<512, 512, false, true> {
+  static constexpr const char* NAME = "Fourier";
+  static constexpr bool PAIR = true;
+};
+template <> struct Enc<SININN_FLOWNET_RBFG> : LayerInput<512, 512, true> {
+  static constexpr const char* NAME = "RBFG";
+  static constexpr bool PAIR = true;
+};
 // 4 frequencies x 3 coordinates x (cos, sin), padded to two K steps
 template <> struct Enc<SININN_FLOWNET_PE> : LayerInput<24, 32> { static constexpr const char* NAME = "PE"; };
 // the triangle wave of MPFF: the shape of the Fourier kind, no frequency gradient; the reference has the progressive network only, so the
@@ -291,6 +311,14 @@ __device__ __forceinline__ void fourier_sincos(const Coord c, float fa, float fb
   sincospif(2.f * r, &s, &co);
 }
 
+// two coordinates (domain_dim = 2): the same phase from the two products the reference's (y, x) @ frequencies [2][256] has
+__device__ __forceinline__ void fourier_sincos2(const Coord c, float fb, float fc, float& s, float& co) {
+  const float p1 = c.y * fb, p2 = c.x * fc;
+  const float e = fmaf(c.y, fb, -p1) + fmaf(c.x, fc, -p2);
+  const float r = ((p1 - rintf(p1)) + (p2 - rintf(p2))) + e;
+  sincospif(2.f * r, &s, &co);
+}
+
 // the piecewise-linear kind (model.py:638-644).  piecewise_arg: u = (c + 1) . f for one frequency f = (fa, fb, fc), each c_d + 1 rounded
 // as the reference rounds it before its matmul; explicit fmaf, for the reason recorded at the RBF branch below.  piecewise_rem:
 // r = fmod(w, 2) - 1 with torch.fmod's truncation (the sign follows the dividend, NOT the floor-mod of the RBFG branch):
@@ -310,10 +338,57 @@ __device__ __forceinline__ float piecewise_tri(float w) {
 }
 
 // features f0 .. f0 + 3 (f0 % 4 == 0) of one point
-template <int KIND>
+// DIM = 2 (RBF, Fourier, RBFG): the parameters have the reference's two-coordinate layouts, centres [512][2], frequencies [2][256], offsets
+// [256][2], and every expression its two terms (y, x); c.t is not read.  The t term is ABSENT, not fed as zero: in RBFG a zero t would not
+// drop out, (0 mod p) 2 - p = -p
+template <int KIND, int DIM = 3>
 __device__ __forceinline__ f32x4 encode4(const FlowNetDev& q, const Coord c, int f0) {
+  static_assert(DIM == 3 || (DIM == 2 && Enc<KIND>::PAIR), "two coordinates: RBF, Fourier and RBFG");
   f32x4 o;
-  if constexpr (KIND == SININN_FLOWNET_RBF) {
+  if constexpr (DIM == 2 && KIND == SININN_FLOWNET_RBF) {
+    const f32x4* cp = reinterpret_cast<const f32x4*>(q.enc_a + 2 * f0);   // centres [512][2]
+    const f32x4 c0 = cp[0], c1 = cp[1];
+    const f32x4 sg = *reinterpret_cast<const f32x4*>(q.enc_b + f0);
+    const float cc[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float dy = c.y - cc[2 * j], dx = c.x - cc[2 * j + 1];
+      const float d = fmaf(dx, dx, dy * dy);                               // explicit fmaf, for the reason recorded below
+      o[j] = expf(-(d * (sg[j] * sg[j])));
+    }
+  } else if constexpr (DIM == 2 && KIND == SININN_FLOWNET_RBFG) {
+    const int f = f0 >> 1;                                                 // offsets [256][2], sigma [256]
+    const f32x4 ov = *reinterpret_cast<const f32x4*>(q.enc_a + 2 * f);
+    const f32x2 sg = *reinterpret_cast<const f32x2*>(q.enc_b + f);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const float is = 1.f / sg[u], p = 2.f * is, hp = 0.5f * sg[u], s2 = sg[u] * sg[u];
+      const float xa[2] = {c.y + ov[2 * u], c.x + ov[2 * u + 1]};
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        float w[2];
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+          const float x = v ? xa[d] + is : xa[d];
+          const float r = fmaf(-floorf(x * hp), p, x);                     // Python's remainder, as below
+          w[d] = fmaf(r, 2.f, -p);
+        }
+        const float d = fmaf(w[1], w[1], w[0] * w[0]);
+        o[2 * u + v] = fmaf(expf(-(d * s2)), 2.f, -1.f);
+      }
+    }
+  } else if constexpr (DIM == 2) {
+    const int f = f0 >> 1;                                                 // frequencies [2][256]
+    const f32x2 fb = *reinterpret_cast<const f32x2*>(q.enc_a + f);
+    const f32x2 fc = *reinterpret_cast<const f32x2*>(q.enc_a + 256 + f);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      float s, co;
+      fourier_sincos2(c, fb[u], fc[u], s, co);
+      o[2 * u] = s;
+      o[2 * u + 1] = co;
+    }
+  } else if constexpr (KIND == SININN_FLOWNET_RBF) {
     const f32x4* cp = reinterpret_cast<const f32x4*>(q.enc_a + 3 * f0);   // centres [512][3]
     const f32x4 c0 = cp[0], c1 = cp[1], c2 = cp[2];
     const f32x4 sg = *reinterpret_cast<const f32x4*>(q.enc_b + f0);
@@ -407,9 +482,12 @@ struct PlainAddZero {
 
 // PROG: q.w[0] is the packed W1p [256][KW], q.wc the coordinate columns, q.ksteps the length of the K loop
 // SPATIAL (with PROG): q.w[0] is nn.Linear's own W1 [256][FN_GW], the operand is multiplied by the point's mask, q.ksteps as above
-template <int KIND, bool PROG = false, bool SPATIAL = false>
+// DIM = 2: two coordinates per point (point_coord_dim, encode4<KIND, 2>); PROG: the coordinate K group is y, x, 0, 0 and q.wc holds the
+// two coordinate columns of W1 [256][514] and two zero columns
+template <int KIND, bool PROG = false, bool SPATIAL = false, int DIM = 3>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
   static_assert(PROG || !SPATIAL, "a spatial mask is a progressive network's");
+  static_assert(DIM == 3 || !SPATIAL, "per-point masks are a grid over (t, y, x)");
   using E = Enc<KIND>;
   constexpr int EW = SPATIAL ? FN_GW : E::w1_stride(PROG);   // floats per row of q.w[0]
   extern __shared__ __attribute__((aligned(16))) float fn_smem[];
@@ -425,7 +503,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
   for (int tile = blockIdx.x; tile < q.ntiles; tile += gridDim.x) {
     Coord pc[4];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) pc[m] = point_coord(q, tile * FN_P + 16 * m + li);
+    for (int m = 0; m < 4; ++m) pc[m] = point_coord_dim<DIM>(q, tile * FN_P + 16 * m + li);
 
     f32x4 acc[4][4];
     zero_acc(acc);
@@ -437,7 +515,10 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
       // ---- the coordinates: one K group, k = kq: t, y, x, 0 ----
       float a[4], b[4];
 #pragma unroll
-      for (int m = 0; m < 4; ++m) a[m] = kq == 0 ? pc[m].t : kq == 1 ? pc[m].y : kq == 2 ? pc[m].x : 0.f;
+      for (int m = 0; m < 4; ++m) {
+        if constexpr (DIM == 3) a[m] = kq == 0 ? pc[m].t : kq == 1 ? pc[m].y : kq == 2 ? pc[m].x : 0.f;
+        else a[m] = kq == 0 ? pc[m].y : kq == 1 ? pc[m].x : 0.f;
+      }
       if constexpr (SPATIAL) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -466,7 +547,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_fwd_kernel(FlowNetDev q) {
       }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        af[m] = encode4<KIND>(q, pc[m], 16 * s + 4 * kq);
+        af[m] = encode4<KIND, DIM>(q, pc[m], 16 * s + 4 * kq);
         if constexpr (SPATIAL) {
           float mk[4];
           sample_cols<4>(q.sp.grid, load_corners(cns + (16 * m + li) * FN_CN), FN_DOM + 16 * s + 4 * kq, mk);
@@ -529,23 +610,24 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_transpose_kernel(const float*
 
 // progressive: w1p[j][k] = w1[j][3 + k] mask[3 + k] (k < 512), wc[j][c] = w1[j][c] mask[c] (c < 3), wc[j][3] = 0; block = row j.
 // A closed feature gets an exact zero whatever the weight holds.  EW > LIVE (PE: w1 is [256][3 + LIVE], w1p [256][KW]): zeros from LIVE on.
-// Instantiated as <E::KW, E::LIVE>: encodings of one shape share one kernel
-template <int EW, int LIVE>
+// Instantiated as <E::KW, E::LIVE>: encodings of one shape share one kernel.  DOM = 2: w1 is [256][2 + LIVE], mask [2 + LIVE]; wc[j] =
+// (w1[j][0] mask[0], w1[j][1] mask[1], 0, 0)
+template <int EW, int LIVE, int DOM = FN_DOM>
 __global__ __launch_bounds__(FN_NTHR) void flownet_pack_kernel(const float* w1, const float* mask, float* w1p, float* wc) {
   const int j = blockIdx.x, tid = threadIdx.x;
-  const float* row = w1 + (size_t)j * (FN_DOM + LIVE);
+  const float* row = w1 + (size_t)j * (DOM + LIVE);
 #pragma unroll
   for (int k = tid; k < EW; k += FN_NTHR) {
     float v = 0.f;
     if (k < LIVE) {
-      const float m = mask[FN_DOM + k];
-      v = m == 0.f ? 0.f : row[FN_DOM + k] * m;
+      const float m = mask[DOM + k];
+      v = m == 0.f ? 0.f : row[DOM + k] * m;
     }
     w1p[(size_t)j * EW + k] = v;
   }
   if (tid < FN_CS) {
     float v = 0.f;
-    if (tid < FN_DOM) {
+    if (tid < DOM) {
       const float m = mask[tid];
       v = m == 0.f ? 0.f : row[tid] * m;
     }
@@ -644,9 +726,11 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_bwd_chain_kernel(FlowNetDe
 // PROG (with ENC): + [chunk][256 * KF + 256 + 4 j + c] = sum_p dh[p][j] coordinate_c[p]; the grid may cover the leading k tiles only.
 // NARROW (an encoding of fewer than 128 padded features): grid = (2, chunks), a block owns 128 x KF and a wave 32 x 32 of it
 // SPATIAL (with PROG): the input is times the point's mask, as the forward pass made it, the coordinates included
-template <int KIND, bool ENC, bool PROG = false, bool SPATIAL = false>
+// DIM = 2 (with ENC): two coordinates per point; PROG: the coordinate sums are two, [chunk][256 * KF + 256 + 4 j + c], c = 0: y, 1: x
+template <int KIND, bool ENC, bool PROG = false, bool SPATIAL = false, int DIM = 3>
 __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q, const float* dh, const float* in) {
   static_assert(ENC || !PROG, "the progressive weight gradient is layer 1's");
+  static_assert(DIM == 3 || (ENC && !SPATIAL), "two coordinates: layer 1 under a global mask or none");
   static_assert(PROG || !SPATIAL, "a spatial mask is a progressive network's");
   using L = std::conditional_t<ENC, Enc<KIND>, Hidden>;
   constexpr bool NARROW = L::NARROW;
@@ -702,7 +786,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
       *reinterpret_cast<f32x4*>(as + row * FN_WS + c4) = va[u];
       if (u < NUB) {
         const int rb = NARROW ? f / (KT / 4) : row, cb = NARROW ? (f % (KT / 4)) * 4 : c4;
-        if constexpr (ENC) vb[u] = encode4<KIND>(q, point_coord(q, tile * FN_P + rb), k0 + cb);
+        if constexpr (ENC) vb[u] = encode4<KIND, DIM>(q, point_coord_dim<DIM>(q, tile * FN_P + rb), k0 + cb);
         if constexpr (SPATIAL) {
           float mk[4];
           sample_cols<4>(q.sp.grid, load_corners(cns + rb * FN_CN), FN_DOM + k0 + cb, mk);
@@ -713,7 +797,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
       }
     }
     if constexpr (PROG && !SPATIAL) {
-      if (k0 == 0 && tid < FN_P) stage_coord(q, cs, tile, tid);
+      if (k0 == 0 && tid < FN_P) stage_coord_dim<DIM>(q, cs, tile, tid);
     }
     __syncthreads();
     if (tile + nchunks < q.ntiles) fetch(tile + nchunks);
@@ -728,7 +812,7 @@ __global__ __launch_bounds__(FN_NTHR, 2) void flownet_wgrad_kernel(FlowNetDev q,
           s += d;
           st = fmaf(d, c[0], st);
           sy = fmaf(d, c[1], sy);
-          sx = fmaf(d, c[2], sx);
+          if constexpr (DIM == 3) sx = fmaf(d, c[2], sx);                // DIM = 2: the tile's columns are y, x, 0, 0
         }
         csum[0] += st;
         csum[1] += sy;
@@ -787,10 +871,11 @@ __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_kernel(const float* pa
 // k - 3), an exact zero where the mask is zero or the column lies beyond the `kcols` encoded columns that were computed; gb as above.
 // mask == nullptr (spatial: the mask is in the partial sums already): the sums as they are, zeros beyond `kcols`.
 // EW: columns of a row of the partial sums, LIVE: encoded columns of gw (<E::KW, E::LIVE>).  !PROG (PE): gw [256][LIVE], no mask
-template <int EW, int LIVE, bool PROG>
+// DOMAIN = 2: gw [256][2 + LIVE], the coordinate sums are entries 0 and 1 of a row's four
+template <int EW, int LIVE, bool PROG, int DOMAIN = FN_DOM>
 __global__ __launch_bounds__(FN_NTHR) void flownet_reduce_l1_kernel(const float* part, int nparts, const float* mask, int kcols, float* gw,
                                                                     float* gb) {
-  constexpr int DOM = PROG ? FN_DOM : 0;
+  constexpr int DOM = PROG ? DOMAIN : 0;
   constexpr int WIDTH = DOM + LIVE;
   constexpr int NW = FN_HID * WIDTH;
   constexpr size_t STRIDE = LayerInput<LIVE, EW>::part_stride(PROG);
@@ -1289,7 +1374,7 @@ size_t part_floats(int ntiles) {
 }
 
 // encoded features in front of the last open one
-int open_encoded(const sininn_flownet_args* a) { return a->k_active > FN_DOM ? a->k_active - FN_DOM : 0; }
+int open_encoded(const sininn_flownet_args* a, int dim = FN_DOM) { return a->k_active > dim ? a->k_active - dim : 0; }
 
 void reduce_launch(const FlowNetDev& q, int nparts, int nw, int nb, float* gw, float* gb, hipStream_t st) {
   hipLaunchKernelGGL(flownet_reduce_kernel, dim3((nw + nb + FN_NTHR - 1) / FN_NTHR), dim3(FN_NTHR), 0, st, (const float*)q.part, nparts, nw, nb, gw, gb);
@@ -1316,6 +1401,41 @@ int hidden_wgrad_launch(int ntiles, const float* dh, const float* in, float* par
 }
 
 // the support table; a refusal leaves its reason, with the table, as the library's last error
+int flownet_supported(const sininn_flownet_args* a, const char* who);
+
+// two coordinates per point (domain_dim = 2): the encodings whose Enc<> row says PAIR, 512 wide, progressive 514
+static int flownet_supported_pair(const sininn_flownet_args* a, const char* who) {
+  const bool prog = a->progressive == 1;
+  const bool ok = (a->progressive == 0 || prog) && a->hidden == FN_HID && a->layers == 3 && a->out_dim == FN_OUT &&
+                  for_kind(a->encoding, false, [&](auto k) {
+                    using E = Enc<decltype(k)::value>;
+                    return E::PAIR && a->enc_dim == E::width(prog, 2);
+                  });
+  if (!ok) {
+    std::string table;
+    for (int kind : FN_KINDS)
+      for_kind(kind, 0, [&](auto k) {
+        using E = Enc<decltype(k)::value>;
+        if (E::PAIR)
+          table += std::string(table.empty() ? "" : ", ") + E::NAME + " " + std::to_string(E::width(false, 2)) + " (progressive: " +
+                   std::to_string(E::width(true, 2)) + ")";
+        return 0;
+      });
+    set_error("%s: unsupported network at domain_dim 2 (encoding %d, %d -> %d x %d -> %d, progressive %d; with two coordinates per point the "
+              "kernels are built for %s -> %d x 3 -> %d; PE and PieceWise take three coordinates only)", who, a->encoding, a->enc_dim, a->hidden,
+              a->layers, a->out_dim, a->progressive, table.c_str(), FN_HID, FN_OUT);
+  }
+  return ok;
+}
+
+int flownet_supported_dim(const sininn_flownet_args* a, int dim, const char* who) {
+  if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
+  if (dim == FN_DOM) return flownet_supported(a, who);
+  if (dim == 2) return flownet_supported_pair(a, who);
+  set_error("%s: domain_dim %d: the kernels take 3 coordinates per point (t, y, x) or 2 (y, x)", who, dim);
+  return 0;
+}
+
 int flownet_supported(const sininn_flownet_args* a, const char* who) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
   const bool prog = a->progressive == 1;
@@ -1372,11 +1492,12 @@ struct SpatialArgs {
 // the head of every entry point: a struct of this library's size that describes a network the kernels are built for; spatial != nullptr:
 // and the spatial mode, a 515-wide progressive network and a grid the kernels can index.  Everything a launch would trip over, before any
 // launch
-static int check_head(const sininn_flownet_args* a, const char* who, const SpatialArgs* spatial) {
+// dim: coordinates per point; 2 exists without a spatial mask only (the entry points that take a dimension take no grid)
+static int check_head(const sininn_flownet_args* a, const char* who, const SpatialArgs* spatial, int dim = FN_DOM) {
   SININN_CHECK(a != nullptr, "%s: null args", who);
   SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
                a->struct_bytes, sizeof(sininn_flownet_args));
-  if (!flownet_supported(a, who)) return 1;
+  if (!flownet_supported_dim(a, dim, who)) return 1;
   if (!spatial) return 0;
   SININN_CHECK(a->progressive == 1, "%s: a spatial mask needs a progressive network (progressive = 1)", who);
   SININN_CHECK(a->enc_dim == FN_GW,
@@ -1406,7 +1527,9 @@ static Spatial spatial_of(const SpatialArgs* s) {
 
 // the descriptor of a call whose entry point has called check_head, checked and copied into q.  spatial != nullptr: the descriptor's mask
 // is ignored, the grid goes to q.sp.  pl != nullptr: the points are that pose list, not the descriptor's grid (with or without spatial)
-static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
+// dim = 2: the grid is (ys, xs) with T = 1, `times` is not read; a pose list is [n][2]
+static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& q, const SpatialArgs* spatial, const PoseList* pl = nullptr,
+                     int dim = FN_DOM) {
   q = FlowNetDev{};
   q.sp = spatial_of(spatial);
   if (a->progressive) {
@@ -1414,7 +1537,17 @@ static int fill_args(const sininn_flownet_args* a, const char* who, FlowNetDev& 
     SININN_CHECK(a->k_active >= 0 && a->k_active <= a->enc_dim, "%s: k_active %d (0 .. %d)", who, a->k_active, a->enc_dim);
   }
   const bool enc_b = for_kind(a->encoding, false, [](auto k) { return Enc<decltype(k)::value>::ENC_B; });
-  if (int rc = check_points(a, who, q, pl, a->enc_a && (a->enc_b || !enc_b), pl ? "encoding" : "axis / encoding")) return rc;
+  if (dim == 2 && !pl) {
+    SININN_CHECK(a->T == 1 && a->H > 0 && a->W > 0 && (int64_t)a->H * a->W <= (int64_t)1 << 22,
+                 "%s: domain_dim 2: grid %d x %d x %d (T = 1: one frame pair; 1 .. 2^22 points)", who, a->T, a->H, a->W);
+    SININN_CHECK(a->ys && a->xs && a->enc_a && (a->enc_b || !enc_b), "%s: null axis / encoding pointer", who);
+    q.T = 1; q.H = a->H; q.W = a->W;
+    q.ys = a->ys; q.xs = a->xs;
+    q.N = q.H * q.W;
+    q.ntiles = (q.N + FN_P - 1) / FN_P;
+  } else if (int rc = check_points(a, who, q, pl, a->enc_a && (a->enc_b || !enc_b), pl ? "encoding" : "axis / encoding")) {
+    return rc;
+  }
   SININN_CHECK(aligned16(a->enc_a) && aligned16(a->enc_b), "%s: encoding buffers must be 16-byte aligned", who);
   if (int rc = check_layers<4>(a, who, q)) return rc;
   q.scale = a->scale;
@@ -1436,6 +1569,16 @@ static int for_mode(const sininn_flownet_args* a, bool spatial, F&& f) {
   });
 }
 
+// f(KIND, PROG) for a network that flownet_supported_pair has accepted: the kinds with two-coordinate kernels
+template <class F>
+static int for_pair(const sininn_flownet_args* a, F&& f) {
+  return for_kind(a->encoding, 1, [&](auto k) {
+    using E = Enc<decltype(k)::value>;
+    if constexpr (E::PAIR) return a->progressive ? f(k, std::true_type{}) : f(k, std::false_type{});
+    else return 1;
+  });
+}
+
 // the name an entry point refuses under: <stem>[_spatial][_points]
 static const char* call_name(const char* plain, const char* spatial_name, const char* points_name, const char* both, const SpatialArgs* spatial,
                              const PoseList* pl) {
@@ -1443,16 +1586,16 @@ static const char* call_name(const char* plain, const char* spatial_name, const 
 }
 
 // layer 1: gW1 = dh1^T (regenerated input), gb1, and their reduction into nn.Linear's layout
-template <int KIND, bool PROG, bool SPATIAL>
+template <int KIND, bool PROG, bool SPATIAL, int DIM = FN_DOM>
 static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hipStream_t st) {
   using E = Enc<KIND>;
   constexpr size_t lds = wgrad_lds(PROG, SPATIAL);
-  auto k = flownet_wgrad_kernel<KIND, true, PROG, SPATIAL>;
+  auto k = flownet_wgrad_kernel<KIND, true, PROG, SPATIAL, DIM>;
   if (raise_lds(k, lds, "flownet_wgrad")) return 1;
   const int nc = wgrad_chunks(q.ntiles, E::CHUNK_KF);  // not a function of k_active: the order of every sum stays the same
   // progressive, wide: the open 128-column tiles of the encoded features only (at least one: it carries gb1 and the coordinate
   // columns); narrow: the one column tile, always whole
-  const int oe = open_encoded(a);
+  const int oe = open_encoded(a, DIM);
   const int ktiles = PROG && !E::NARROW ? (oe > 0 ? (oe + FN_WT - 1) / FN_WT : 1) : E::KW / E::KT;
   hipLaunchKernelGGL(k, dim3(2 * ktiles, nc), dim3(FN_NTHR), lds, st, q, (const float*)q.dh, (const float*)nullptr);
   SININN_LAUNCH_CHECK("flownet_wgrad");
@@ -1460,7 +1603,7 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
     reduce_launch(q, nc, FN_HID * E::LIVE, FN_HID, a->gw[0], a->gb[0], st);
   } else {
     const int kcols = !PROG ? E::LIVE : E::NARROW ? oe : ktiles * FN_WT;
-    hipLaunchKernelGGL((flownet_reduce_l1_kernel<E::KW, E::LIVE, PROG>), dim3((FN_HID * E::width(PROG) + FN_HID + FN_NTHR - 1) / FN_NTHR),
+    hipLaunchKernelGGL((flownet_reduce_l1_kernel<E::KW, E::LIVE, PROG, DIM>), dim3((FN_HID * E::width(PROG, DIM) + FN_HID + FN_NTHR - 1) / FN_NTHR),
                        dim3(FN_NTHR), 0, st, (const float*)q.part, nc, PROG && !SPATIAL ? a->mask : (const float*)nullptr, kcols, a->gw[0], a->gb[0]);
   }
   SININN_LAUNCH_CHECK("flownet_reduce");
@@ -1471,10 +1614,11 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
 // spatial != nullptr: layer 1 under the per-point mask of that grid.  pl != nullptr: at that pose list.  The entry point has called check_head
 // who != nullptr: the name every refusal is made under (the posegrad call), else the names the backward calls have always used.
 // out_q != nullptr: receives the kernels' descriptor of the call (dh1 is slot 0 of q.dh) for a kernel the caller launches after these
+// dim = 2: two coordinates per point; no grid, no frequency gradient (the entry points that take a dimension offer neither)
 static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial,
-                           const PoseList* pl = nullptr, const char* who = nullptr, FlowNetDev* out_q = nullptr) {
+                           const PoseList* pl = nullptr, const char* who = nullptr, FlowNetDev* out_q = nullptr, int dim = FN_DOM) {
   FlowNetDev q;
-  if (int rc = fill_args(a, who ? who : spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl)) return rc;
+  if (int rc = fill_args(a, who ? who : spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl, dim)) return rc;
   if (int rc = check_backward_buffers<4>(a, who ? who : pl ? "flownet_backward_points" : "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q))
     return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
@@ -1494,10 +1638,14 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
   SININN_LAUNCH_CHECK("flownet_reduce");
   for (int l = 2; l >= 1; --l)                         // gW3 = dh3^T h2, gW2 = dh2^T h1
     if (int rc = hidden_wgrad_launch(q.ntiles, q.dh + l * lstride, q.saved + (l - 1) * lstride, q.part, a->gw[l], a->gb[l], st)) return rc;
-  if (int rc = for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
-        return wgrad_l1_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, st);
-      }))
+  if (dim == 2) {
+    if (int rc = for_pair(a, [&](auto k, auto prog) { return wgrad_l1_launch<decltype(k)::value, decltype(prog)::value, false, 2>(a, q, st); }))
+      return rc;
+  } else if (int rc = for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
+               return wgrad_l1_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, st);
+             })) {
     return rc;
+  }
   if (g_enc_a) {
     float* const epart = enc_ws + (size_t)Fourier::LIVE * FN_HID;
     const float* const mask = a->progressive && !spatial ? a->mask : nullptr;
@@ -1518,7 +1666,7 @@ static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* 
 }
 
 // PROG without SPATIAL: the pack step, W1 times the global mask into the workspace; SPATIAL: W1 in place, no pack kernel, no workspace
-template <int KIND, bool PROG, bool SPATIAL>
+template <int KIND, bool PROG, bool SPATIAL, int DIM = FN_DOM>
 static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipStream_t st) {
   using E = Enc<KIND>;
   constexpr const char* who = SPATIAL ? "flownet_forward_spatial" : "flownet_forward";
@@ -1529,26 +1677,29 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
     SININN_CHECK(aligned16(a->workspace), "flownet_forward: workspace must be 16-byte aligned");
     float* const w1p = static_cast<float*>(a->workspace);
     float* const wc = w1p + (size_t)FN_HID * E::KW;
-    hipLaunchKernelGGL((flownet_pack_kernel<E::KW, E::LIVE>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
+    hipLaunchKernelGGL((flownet_pack_kernel<E::KW, E::LIVE, DIM>), dim3(FN_HID), dim3(FN_NTHR), 0, st, a->w[0], a->mask, w1p, wc);
     SININN_LAUNCH_CHECK("flownet_pack");
     q.w[0] = w1p;
     q.wc = wc;
   }
-  if constexpr (PROG) q.ksteps = (open_encoded(a) + 15) / 16;
-  auto k = flownet_fwd_kernel<KIND, PROG, SPATIAL>;
+  if constexpr (PROG) q.ksteps = (open_encoded(a, DIM) + 15) / 16;
+  auto k = flownet_fwd_kernel<KIND, PROG, SPATIAL, DIM>;
   if (raise_lds(k, tile_lds(SPATIAL), who)) return 1;
-  const int blocks = q.ntiles < 2048 ? q.ntiles : 2048;
+  const int blocks = q.ntiles < FN_FWD_MAX_BLOCKS ? q.ntiles : FN_FWD_MAX_BLOCKS;
   hipLaunchKernelGGL(k, dim3(blocks), dim3(FN_NTHR), tile_lds(SPATIAL), st, q);
   SININN_LAUNCH_CHECK(who);
   return 0;
 }
 
-static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
+static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr,
+                          int dim = FN_DOM) {
   const char* who = call_name("flownet_forward", "flownet_forward_spatial", "flownet_forward_points", "flownet_forward_spatial_points", spatial, pl);
   FlowNetDev q;
-  if (int rc = check_head(a, who, spatial)) return rc;
-  if (int rc = fill_args(a, who, q, spatial, pl)) return rc;
+  if (int rc = check_head(a, who, spatial, dim)) return rc;
+  if (int rc = fill_args(a, who, q, spatial, pl, dim)) return rc;
   if (int rc = check_forward_buffers(a, pl ? who : "flownet_forward", flownet_saved_bytes(q.N), q)) return rc;
+  if (dim == 2)
+    return for_pair(a, [&](auto k, auto prog) { return forward_kind_launch<decltype(k)::value, decltype(prog)::value, false, 2>(a, q, st); });
   return for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
     return forward_kind_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, st);
   });
@@ -1561,10 +1712,22 @@ int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* gr
   return forward_launch(a, st, &s);
 }
 
-static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr) {
+static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr,
+                                 int dim = FN_DOM) {
   const char* who = call_name("flownet_backward", "flownet_backward_spatial", "flownet_backward_points", "flownet_backward_spatial_points", spatial, pl);
-  if (int rc = check_head(a, who, spatial)) return rc;
-  return backward_launch(a, nullptr, nullptr, st, spatial, pl, spatial && pl ? who : nullptr);   // the earlier calls keep their sentences
+  if (int rc = check_head(a, who, spatial, dim)) return rc;
+  return backward_launch(a, nullptr, nullptr, st, spatial, pl, spatial && pl ? who : nullptr, nullptr, dim);   // the earlier calls keep their sentences
+}
+
+// ---- the dimension as an argument: 3 is the calls above, 2 a network on (y, x) (one frame pair); poses == nullptr: the descriptor's grid ----
+int flownet_forward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return forward_launch(a, st, nullptr, points ? &pl : nullptr, dim);
+}
+
+int flownet_backward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st) {
+  const PoseList pl{poses, n};
+  return backward_plain_launch(a, st, nullptr, points ? &pl : nullptr, dim);
 }
 
 int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_plain_launch(a, st, nullptr); }

@@ -39,6 +39,23 @@ __device__ __forceinline__ Coord point_coord(const Q& q, int p) {
   return Coord{q.times[t], q.ys[y], q.xs[x]};
 }
 
+// DIM coordinates per point.  3: point_coord above, as it is.  2 (one frame pair, domain_dim = 2): row p of the pose list [N][2], columns
+// (y, x), else point p of the (ys, xs) grid (T = 1, `times` is not read); t is a literal zero that no encoder of this dimension reads
+template <int DIM, class Q>
+__device__ __forceinline__ Coord point_coord_dim(const Q& q, int p) {
+  if constexpr (DIM == 3) {
+    return point_coord(q, p);
+  } else {
+    p = p < q.N ? p : q.N - 1;
+    if (q.poses) {
+      const float* const r = q.poses + 2 * p;
+      return Coord{0.f, r[0], r[1]};
+    }
+    const int y = p / q.W, x = p - y * q.W;
+    return Coord{0.f, q.ys[y], q.xs[x]};
+  }
+}
+
 // acc[m][n] += A[rows 16 m ..][k] W[cols cw + 16 n ..][k]: A from the LDS tile, W row-major [256][256] from L2
 __device__ __forceinline__ void gemm_lds(const float* hs, const float* w, int cw, int li, int kq, f32x4 (&acc)[4][4]) {
 #pragma unroll 2
@@ -118,6 +135,17 @@ template <class Q>
 __device__ __forceinline__ void stage_coord(const Q& q, float* cs, int tile, int tid) {
   const Coord c = point_coord(q, tile * FN_P + tid);
   *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.t, c.y, c.x, 0.f};
+}
+
+// DIM = 2: row tid = (y, x, 0, 0), the order of the two coordinate columns of a [256][514] layer 1
+template <int DIM, class Q>
+__device__ __forceinline__ void stage_coord_dim(const Q& q, float* cs, int tile, int tid) {
+  if constexpr (DIM == 3) {
+    stage_coord(q, cs, tile, tid);
+  } else {
+    const Coord c = point_coord_dim<2>(q, tile * FN_P + tid);
+    *reinterpret_cast<f32x4*>(cs + tid * FN_CS) = (f32x4){c.y, c.x, 0.f, 0.f};
+  }
 }
 
 // ---- host: the parts of a descriptor that do not depend on the network.  A: the C struct of a call, Q: the kernels' descriptor ----

@@ -94,6 +94,16 @@ Per-point masks at pose lists: `controller(poses)` of a `StashedSpatialControlle
 interpolates it under no_grad: the pose gradient has no d mask / d pose term.  A bare progressive model with a grid is still refused at a
 pose list: the interpolation is a controller's.
 
+Two coordinates (`ModelParams(domain_dim=2)`, the network of video-interpolation/pair_flow.py:39-42): RBF, FFN, UFF, RBFG and their
+progressive forms PRBF, PFF, PUFF, PRBFG are built on (y, x) with the reference's layouts (`encode.centres` [512][2], `encode.frequencies`
+[2][256], `encode.offsets` [256][2], a progressive first weight [256][514] = the columns of cat((y, x), enc)) and run in the DIM = 2
+instantiations of the kernels (`sininn_flownet_{forward,backward}[_points]_dim`, the dimension an argument beside the unchanged descriptor).
+`flow_fields(net_or_controller, None, h, w, scale)` is one frame pair, poses linspace(-1, 1, h) x linspace(-1, 1, w) (pair_flow.py:55-59),
+flows (1, 4, h, w): `times` must be None.  `flow_at`, `net(poses)` and `controller(poses, ..)` take (..., 2) -> (..., 4).  The global mask has
+514 values in blocks of 4, `override_mask`, `get_mask` and `k_active` work as at three coordinates.  Refused there, each with a ValueError
+that names the dimension and the mode (`_refuse_pair_modes`): RFF / PRFF, PE / PPE, MPFF, SIREN, per-point masks (StashedSpatialController,
+2-D `override_mask` grids), `pose_grad=True`, `times` for such a network, and poses of the other dimension either way.
+
 Out of scope: a plain (non-progressive) piecewise network and a frequency gradient for that encoding, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
 `--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
 closed, and of `MPFF` its `--net MPFF` (video-interpolation/main.py still refuses both).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
@@ -525,18 +535,28 @@ class Mask(NamedTuple):
 
 
 # ---- the descriptors: what is particular to a kind of network, then the part they share ----
-def _points_and_layers(a, lins, times, ys, xs, scale):
+def _points_and_layers(a, lins, times, ys, xs, scale, dim=3):
     """the grid of points (axes on the GPU, T H W, scale, pointers) and the nn.Linear layers of a descriptor.  `ys is None`: `times`
-    is a pose list (N, 3); the descriptor gets the planar shape T = H = 1, W = N that `flows` / `dflows` have then and no axis
-    pointers, and `a._poses` is what the points entry points take beside it"""
+    is a pose list (N, dim); the descriptor gets the planar shape T = H = 1, W = N that `flows` / `dflows` have then and no axis
+    pointers, and `a._poses` is what the points entry points take beside it.  `dim == 2` on a grid: the axes are (ys, xs), `times`
+    is None and T = 1"""
     if ys is None:
         poses = times
         _on_gpu(poses, 'pose list')
-        assert poses.dtype == torch.float32 and poses.dim() == 2 and poses.shape[1] == 3, 'a pose list (N, 3), fp32'
+        assert poses.dtype == torch.float32 and poses.dim() == 2 and poses.shape[1] == dim, f'a pose list (N, {dim}), fp32'
         poses = poses.contiguous()
         a.T, a.H, a.W, a.scale = 1, 1, poses.shape[0], float(scale)
         a._axes, a._device = (poses,), poses.device
         a._poses = (ptr(poses) if poses.numel() else None, poses.shape[0])
+    elif dim == 2:
+        if times is not None:
+            raise ValueError('domain_dim 2: a network on (y, x) has no times; pass times=None')
+        for t in (ys, xs):
+            _on_gpu(t)
+        ys, xs = ys.contiguous(), xs.contiguous()
+        a.T, a.H, a.W, a.scale = 1, ys.numel(), xs.numel(), float(scale)
+        a.ys, a.xs = ptr(ys), ptr(xs)
+        a._axes, a._device = (ys, xs), ys.device
     else:
         for t in (times, ys, xs):
             _on_gpu(t)
@@ -551,16 +571,55 @@ def _points_and_layers(a, lins, times, ys, xs, scale):
     return a
 
 
+PAIR_KINDS = (RBF, FOURIER, RBFG)                       # the encodings whose kernels exist for two coordinates per point
+
+
+def _refuse_pair_modes(net, dim, spatial=False, enc_a=None):
+    """a network with domain_dim != 3: what the kernels do not do for it, each refusal under the dimension and the mode"""
+    if dim != 2:
+        raise ValueError(f'domain_dim {dim}: the flownet kernels take 3 coordinates per point (t, y, x) or 2 (y, x)')
+    if isinstance(net, SirenModel):
+        raise ValueError('domain_dim 2: SIREN is out of scope: its kernels take three coordinates')
+    enc = net.encode
+    if isinstance(enc, RotatedFourierFeatures) or enc_a is not None:
+        raise ValueError('domain_dim 2: RFF / PRFF (learnable frequencies) are out of scope: the frequency gradient exists for three '
+                         'coordinates only')
+    if enc.kind == PE:
+        raise ValueError('domain_dim 2: PE / PPE are out of scope: 16 features, a layer 1 of another width than the kernels are built for')
+    if enc.kind == PIECEWISE:
+        raise ValueError('domain_dim 2: MPFF (the piecewise-linear encoding) is out of scope: its kernels take three coordinates')
+    if spatial:
+        raise ValueError('domain_dim 2: per-point masks (StashedSpatialController, a 2-D override_mask grid) are out of scope: the mask grid '
+                         'is one over (t, y, x)')
+    assert enc.kind in PAIR_KINDS
+
+
+def _call_dim(net, override_mask=None, pose_grad=False):
+    """domain_dim of a model or a controller; other than 3: every refusal of that dimension that a public call can meet, before any
+    device is looked at"""
+    from .progressive import ProgressiveEncoderController
+    dim = net.domain_dim
+    if dim != 3:
+        _refuse_pair_modes(net.model if isinstance(net, ProgressiveEncoderController) else net, dim,
+                           spatial=override_mask is not None and override_mask.dim() == 2)
+        if pose_grad:
+            raise ValueError(f'domain_dim {dim}: pose_grad=True is out of scope: the coordinate gradient exists for three coordinates only')
+    return dim
+
+
 def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spatial=False):
     lins = net.linears()
     a = _lib.FlowNetArgs()
     a.encoding = net.encode.kind
     a.progressive = int(bool(net.is_progressive))
     a.enc_dim, a.hidden, a.layers, a.out_dim = net.encoding_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
-    if not _lib.lib().sininn_flownet_supported(C.byref(a)):      # the library's refusal names the sizes it is built for
+    dim = a._dim = int(net.opt.domain_dim)               # travels beside the descriptor, to the `_dim` entry points
+    if dim != 3:
+        _refuse_pair_modes(net, dim, spatial, enc_a)
+    if not _lib.lib().sininn_flownet_supported_dim(C.byref(a), dim):   # the library's refusal names the sizes it is built for
         raise ValueError(_lib.lib().sininn_last_error().decode())
-    if net.opt.domain_dim != 3 or len(lins) != 4:
-        raise ValueError(f'flownet kernels take 3 coordinates and 4 linear layers; got {net.opt.domain_dim} and {len(lins)}')
+    if len(lins) != 4:
+        raise ValueError(f'flownet kernels take 4 linear layers; got {len(lins)}')
     if spatial:                                          # the grid goes beside the descriptor, its `mask` is ignored
         if not a.progressive:
             raise ValueError('a spatial mask needs a progressive network')
@@ -574,7 +633,7 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spati
         a.k_active = a.enc_dim if k_active is None else int(k_active)
     elif mask is not None:
         raise ValueError('a mask needs a progressive network')
-    _points_and_layers(a, lins, times, ys, xs, scale)
+    _points_and_layers(a, lins, times, ys, xs, scale, dim)
     if enc_a is None:
         ea, eb = net.encode.kernel_buffers()
     else:                                                # learnable frequencies: F_eff of this call
@@ -592,7 +651,10 @@ def _siren_args(net, times, ys, xs, scale, omega=None):
     a.in_dim, a.hidden, a.layers, a.out_dim = net.opt.domain_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
     a.omega = net.omega if omega is None else float(omega)
     if not _lib.lib().sininn_siren_supported(C.byref(a)):        # the library's refusal names the sizes it is built for
-        raise ValueError(_lib.lib().sininn_last_error().decode())
+        why = _lib.lib().sininn_last_error().decode()
+        if net.opt.domain_dim != 3:
+            why += f' (domain_dim {net.opt.domain_dim}: the SIREN kernels take three coordinates)'
+        raise ValueError(why)
     if len(lins) != 5:
         raise ValueError(f'siren kernels take 5 linear layers; got {len(lins)}')
     return _points_and_layers(a, lins, times, ys, xs, scale)
@@ -684,6 +746,8 @@ def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_a
     number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
     (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
     a = _pack_workspace(_args(net, times, ys, xs, scale, mask, k_active, enc_a))
+    if a._dim != 3:                                      # two coordinates: `times` is None, the axes are (ys, xs)
+        return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_dim, a._dim)
     return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward)
 
 
@@ -695,6 +759,9 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, m
     matrix the kernels read; `enc_workspace`: optional fp32 tensor of sininn_flownet_encgrad_workspace_bytes bytes for it,
     `g_enc_a`: optional (3, 256) fp32 tensor that receives gF."""
     a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
+    if a._dim != 3:
+        return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward_dim,
+                         a._dim)
     return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward,
                      enc_call=_lib.lib().sininn_flownet_backward_encgrad if enc_grad else None, enc_workspace=enc_workspace, g_enc_a=g_enc_a)
 
@@ -744,7 +811,10 @@ def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, ome
 def flownet_forward_points(net, poses, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
     """flownet_forward at a pose list (N, 3) on the device: flows (4, N) = net(poses)^T * scale; `saved` as there, for N points"""
     a = _pack_workspace(_args(net, poses, None, None, scale, mask, k_active, enc_a))
-    flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_points, *a._poses)
+    if a._dim != 3:                                      # a pose list (N, 2), columns (y, x)
+        flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_points_dim, a._dim, *a._poses)
+    else:
+        flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_points, *a._poses)
     return flows.view(4, -1), saved
 
 
@@ -756,6 +826,11 @@ def flownet_backward_points(net, poses, scale, dflows, saved, workspace=None, ma
     tensor of sininn_flownet_posegrad_workspace_bytes bytes (it holds the frequency gradient's workspace too: `enc_workspace` is refused),
     `g_poses`: optional (N, 3) fp32 tensor that receives the gradient"""
     a = _args(net, poses, None, None, scale, mask, k_active, enc_a)
+    if a._dim != 3:
+        if pose_grad:
+            raise ValueError(f'domain_dim {a._dim}: pose_grad=True is out of scope: the coordinate gradient exists for three coordinates only')
+        return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
+                         _lib.lib().sininn_flownet_backward_points_dim, a._dim, *a._poses)
     if pose_grad:
         assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
         return _backward_posegrad(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_backward_posegrad_points, a._poses, enc_grad,
@@ -951,6 +1026,9 @@ def _resolve_mask(net, override_mask, device):
         if override_mask is not None:
             raise ValueError('override_mask needs a progressive network')
         return model, Mask()
+    if override_mask is not None and override_mask.dim() == 2 and model.domain_dim != 3:
+        raise ValueError(f'domain_dim {model.domain_dim}: a 2-D override_mask (a grid of per-point masks) is out of scope: the mask grid is one '
+                         'over (t, y, x)')
     if override_mask is not None and override_mask.dim() == 2:
         # a raw grid (res^3, enc_dim) on the device: not inspected, nothing skipped; the cell map is the spatial controller's, else identity
         g = override_mask.detach()
@@ -983,11 +1061,22 @@ def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
     A StashedSpatialController, or an `override_mask` of shape (res^3, 515) on the device, evaluates the network under the per-point
     mask interpolated from that grid.  `get_mask=True` (the reference's keyword) returns (flow12, flow21, mask): the mask in use, (515,)
     or, spatial, the interpolated (t h w, 515)."""
-    _on_gpu(times)
-    assert times.dtype == torch.float32 and times.dim() == 1
+    dim = _call_dim(net, override_mask)
+    if dim == 2:
+        # one frame pair (pair_flow.py:55-59): poses linspace(-1, 1, h) x linspace(-1, 1, w), no time axis; flows (1, 4, h, w)
+        if times is not None:
+            raise ValueError('domain_dim 2: `times` given for a network on (y, x): flow_fields(net, None, h, w, scale) evaluates one frame pair')
+        like = next(net.parameters())
+        _on_gpu(like, 'parameter')
+    else:
+        if times is None:
+            raise ValueError(f'domain_dim {dim}: times=None is the call of a network on (y, x) (domain_dim 2); this one needs its times')
+        _on_gpu(times)
+        assert times.dtype == torch.float32 and times.dim() == 1
+        like = times
     controller = net
-    net, mask = _resolve_mask(net, override_mask, times.device)
-    ys, xs = grid_axes(net, times, h, w)
+    net, mask = _resolve_mask(net, override_mask, like.device)
+    ys, xs = grid_axes(net, like, h, w)
     if mask.spatial and hasattr(controller, 'note_grid'):
         controller.note_grid(times, ys, xs)              # stash_iteration finds the cells of these points
     if get_mask:
@@ -1019,8 +1108,10 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     by the fused kernels: sininn_flownet_backward_posegrad_points / sininn_siren_backward_posegrad_points), which chains queries:
     flow_at(net, p + pad(flow_at(net, p, pose_grad=True)[..., :2]), pose_grad=True).  Once differentiable.  Without the keyword there is no
     gradient with respect to the coordinates: poses that require one are refused."""
-    if not torch.is_tensor(poses) or poses.dim() < 1 or poses.shape[-1] != 3:
-        raise ValueError(f'flow_at: poses of shape (..., 3), columns (t, y, x); got {tuple(poses.shape) if torch.is_tensor(poses) else type(poses)}')
+    dim = _call_dim(net, override_mask, pose_grad)
+    if not torch.is_tensor(poses) or poses.dim() < 1 or poses.shape[-1] != dim:
+        raise ValueError(f'flow_at: domain_dim {dim}: poses of shape (..., {dim}), columns {"(t, y, x)" if dim == 3 else "(y, x)"}; got '
+                         f'{tuple(poses.shape) if torch.is_tensor(poses) else type(poses)}')
     if poses.dtype != torch.float32:
         raise ValueError(f'flow_at: fp32 poses; got {poses.dtype}')
     if poses.requires_grad and not pose_grad:
@@ -1028,7 +1119,7 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
                                   'or poses.detach()')
     _on_gpu(poses, 'pose list')
     lead = poses.shape[:-1]
-    flat = poses.reshape(-1, 3).contiguous()
+    flat = poses.reshape(-1, dim).contiguous()
     controller = net
     net, mask = _resolve_mask(net, override_mask, poses.device)
     if mask.spatial and controller is net:

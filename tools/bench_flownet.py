@@ -23,6 +23,9 @@ weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines 
 layout) instead of a grid; the --baseline is tools/fit_flow.composed_flow_at on the same list.  The FLOP counts are those of N points.
 --points N --spatial R [--pose-grad] calls the StashedSpatialController on the pose list (sininn_flownet_*_spatial_points); the --baseline is
 composed_flow_at under the controller's `interpolate` (gather + einsum, (N, 8, 515)) on every call.
+--dim 2 builds the network on two coordinates, ModelParams(domain_dim=2) (RBF, FFN, UFF, RBFG and their progressive forms, 514 wide), and
+times flow_fields(net, None, height, width, .), the call of video-interpolation/pair_flow.py: one frame, no times; the --baseline is
+composed_flow_fields on the same network.  Grids only (no --points, --spatial, --frames).
 """
 import argparse
 import json
@@ -85,14 +88,16 @@ def main():
     ap.add_argument('--spatial', type=int, default=0, metavar='R', help='progressive nets: a per-point mask from an R^3 grid (0: the global mask)')
     ap.add_argument('--pose-grad', action='store_true', help='--points: the step also differentiates the poses (flow_at(.., pose_grad=True); the '
                     'baseline: the composed network with the poses as a leaf); adds no_pose_grad_step_ms, the same step without it, and pose_grad_cost_ms / pose_grad_cost_ratio')
+    ap.add_argument('--dim', type=int, default=3, choices=[2, 3], help='coordinates per point: 3 (t, y, x) or 2 (y, x), one frame pair')
     a = ap.parse_args()
+    assert a.dim == 3 or not (a.points or a.spatial or a.frames > 1), '--dim 2: one frame on its (y, x) grid'
     assert a.points or not a.pose_grad, '--pose-grad: the coordinate gradient exists at pose lists (--points)'
     from fit_flow import composed_flow_at, composed_flow_fields
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
     learnable = a.net in flownet.learnable_model_dict
     siren = a.net in flownet.siren_model_dict
-    net = flownet.flow_model_dict[a.net](flownet.ModelParams()).to(dev)
+    net = flownet.flow_model_dict[a.net](flownet.ModelParams(domain_dim=a.dim)).to(dev)
     prog = net.is_progressive
     target = net
     if a.spatial:
@@ -112,6 +117,8 @@ def main():
         target.mask[:a.k_active] = 1
         mask_dev = target.mask.to(dev)
     times = torch.linspace(0, 1, a.frames, device=dev) if a.frames > 1 else torch.zeros(1, device=dev)
+    if a.dim == 2:
+        times = None
     n = a.points if a.points else a.frames * a.height * a.width
     up = torch.randn(a.frames, 4, a.height, a.width, device=dev) if not a.points else None
     params = list(net.parameters())
@@ -168,7 +175,7 @@ def main():
     f_fwd, f_step = flops_siren(n) if siren else flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
     sizes = (_lib.lib().sininn_siren_saved_bytes, _lib.lib().sininn_siren_workspace_bytes) if siren else \
         (_lib.lib().sininn_flownet_saved_bytes, _lib.lib().sininn_flownet_workspace_bytes)
-    out = dict(net=a.net, **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(mode='points', pose_grad=a.pose_grad) if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
+    out = dict(net=a.net, **(dict(dim=a.dim) if a.dim != 3 else {}), **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(mode='points', pose_grad=a.pose_grad) if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=sizes[0](n), workspace_bytes=sizes[1](n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):

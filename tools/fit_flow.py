@@ -13,6 +13,7 @@
     python tools/fit_flow.py --net RBF --points 4096
     python tools/fit_flow.py --net RBF --points 4096 --cycle
     python tools/fit_flow.py --net PRBF --points 4096 --controller spatial --res 7 [--cycle]
+    python tools/fit_flow.py --net PRBF --dim 2
 
 `--optimizer lamb` steps with FusedLAMB(net.parameters(), lr=lr), the optimiser of FlowTrainer.configure_optimizers
 (trainer.py:134-135); the default stays FusedAdam.
@@ -96,7 +97,9 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
     is model.py:375-387 line by line, with its N x 256 x 2 x 3 intermediate; the positional encoding (PE / PPE) is the einsum / cat of
     model.py:331-332, without the `.view(-1, 21)` that raises unless N is a multiple of 7 (the cat is already (N, 4, 6)); the piecewise-linear
     encoding (MPFF) is composed_piecewise.  A SirenModel has
-    no encoding: sin(omega_0 * linear(x)) four times and the last nn.Linear, model.py:145-146, 163-171."""
+    no encoding: sin(omega_0 * linear(x)) four times and the last nn.Linear, model.py:145-146, 163-171.  A network on two coordinates
+    (ModelParams(domain_dim=2)) takes `times=None`: the poses are (y, x) on the h x w grid and the encoders, written over the last axis, are
+    the reference's two-term expressions."""
     mask = override_mask
     spatial = None
     if hasattr(net, 'mask'):                                      # a controller
@@ -105,10 +108,17 @@ def composed_flow_fields(net, times, h, w, scale, override_mask=None):
         else:
             mask = net.mask if mask is None else mask
         net = net.model
-    ys = torch.linspace(-1, 1, h).to(times)
-    xs = torch.linspace(-1, 1, w).to(times)
-    gt, gh, gw = torch.meshgrid(times, ys, xs, indexing='ij')
-    x = poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
+    if net.domain_dim == 2:                                       # one frame pair, pair_flow.py:55-58: poses (y, x), no times
+        assert times is None, 'a network on (y, x) has no times'
+        like = next(net.parameters())
+        gh, gw = torch.meshgrid(torch.linspace(-1, 1, h).to(like), torch.linspace(-1, 1, w).to(like), indexing='ij')
+        x = poses = torch.stack((gh, gw), dim=-1).view(-1, 2)
+        times = like.new_zeros(1)                                 # one frame: flows (1, 4, h, w)
+    else:
+        ys = torch.linspace(-1, 1, h).to(times)
+        xs = torch.linspace(-1, 1, w).to(times)
+        gt, gh, gw = torch.meshgrid(times, ys, xs, indexing='ij')
+        x = poses = torch.stack((gt, gh, gw), dim=-1).view(-1, 3)
     if spatial is not None and mask is None:
         mask = spatial.interpolate(poses)                         # (N, 515), one row per point
     if not hasattr(net, 'encode'):                                # siren
@@ -277,13 +287,15 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
 
 
 def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, device='cuda', log=None, max_iteration=1000,
-        info=None, optimizer='adam', controller='early', res=7):
+        info=None, optimizer='adam', controller='early', res=7, dim=3):
     """returns the list of per-step losses (floats); `info`: a dict that receives the network (the controller of a progressive one,
-    and under `controller='spatial'` the number of update_progress calls as info['progress'])"""
+    and under `controller='spatial'` the number of update_progress calls as info['progress']).  `dim=2`: the network is built on two
+    coordinates, ModelParams(domain_dim=2), and evaluated on the (y, x) grid of the pair"""
     from sin_inn_amd import FusedAdam, FusedLAMB, flowloss as FL, flownet, progressive
     from sin_inn_amd.functional import flow_warp_l1
     torch.manual_seed(seed)
-    net = flownet.flow_model_dict[net_name](flownet.ModelParams()).to(device)
+    assert dim in (2, 3), dim
+    net = flownet.flow_model_dict[net_name](flownet.ModelParams(domain_dim=dim)).to(device)
     assert controller in ('early', 'spatial'), controller
     spatial = controller == 'spatial'
     if spatial:
@@ -299,7 +311,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     frame1, frame2, true_flow = make_pair(h, w, seed + 1, device)
     if info is not None:
         info['progress'] = 0
-    times = torch.zeros(1, device=device)
+    times = torch.zeros(1, device=device) if dim == 3 else None
     l1, census, smooth = FL.L1Loss(1.0), FL.CensusLoss(0.1, max_distance=3), FL.BilateralSmooth(0.1, 'gauss', 150, 1)
     fields = composed_flow_fields if composed else flownet.flow_fields
     losses = []
@@ -349,11 +361,14 @@ def main():
     ap.add_argument('--optimizer', default='adam', choices=['adam', 'lamb'])
     ap.add_argument('--controller', default='early', choices=['early', 'spatial'], help='progressive nets: the mask is global / per grid cell')
     ap.add_argument('--res', type=int, default=7, help='--controller spatial: cells per axis of the mask grid')
+    ap.add_argument('--dim', type=int, default=3, choices=[2, 3], help='coordinates per point: 3 (t, y, x), or 2 (y, x), the network of '
+                    'video-interpolation/pair_flow.py (RBF, FFN, UFF, RBFG and their progressive forms; not with --points)')
     ap.add_argument('--points', type=int, default=0, metavar='N', help='fit net(poses) at N random points per step (fit_points) instead of a frame pair')
     ap.add_argument('--cycle', action='store_true', help='--points: add the forward-backward consistency term at p + flow12(p); runs the '
                     'fused and the composed loop and prints both')
     a = ap.parse_args()
     assert a.points or not a.cycle, '--cycle is a term of the --points loop'
+    assert a.dim == 3 or not a.points, '--points fits the three-coordinate clip; --dim 2 is the frame-pair loop'
     if a.cycle:
         for what, comp in (('fused', False), ('composed', True)):
             losses = fit_points(a.net, a.points, a.steps, comp, lr=a.lr, seed=a.seed, log=lambda m, w=what: print(w, m),
@@ -366,7 +381,7 @@ def main():
         print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
         return
     losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration,
-                 optimizer=a.optimizer, controller=a.controller, res=a.res)
+                 optimizer=a.optimizer, controller=a.controller, res=a.res, dim=a.dim)
     print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
 
 
