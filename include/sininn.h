@@ -29,6 +29,8 @@
 extern "C" {
 #endif
 
+/* stays 4 although the flow-network entry points changed: the in-tree ctypes binding is the library's only consumer and checks every symbol
+ * and every struct size when it loads it */
 #define SININN_ABI_VERSION 4
 #define SININN_HIDDEN 256 /* hidden width of subnet_conv / subnet_conv_1x1, archs.py:12,16 */
 
@@ -670,7 +672,7 @@ int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int 
  *   backward call needs no more than sininn_flownet_workspace_bytes(N), and `saved` has the same size.
  * Learnable frequencies (model.py:263-307 RotatedFourierFeatures, RFFModel model.py:436-451, PRFFModel model.py:586-590): the caller passes
  *   F_eff = normalize(frequencies, dim 0) * magnitudes as enc_a (768 values, computed with its own ops) and the forward call is the
- *   Fourier one.  sininn_flownet_backward_encgrad does everything sininn_flownet_backward does (the eight gradients are bitwise the same)
+ *   Fourier one.  The ENCGRAD mode of sininn_flownet_backward does everything the call without it does (the eight gradients are bitwise the same)
  *   and also writes g_enc_a [3][256] (OVERWRITTEN), the gradient with respect to the matrix passed as enc_a:
  *     dE[p][k] = sum_j dh1[p][j] w[0][j][k] (progressive: w[0][j][3 + k] * mask[3 + k]), never stored;
  *     dphi[p][f] = dE[p][2 f] cos(phi[p][f]) - dE[p][2 f + 1] sin(phi[p][f]), sin / cos as the forward pass computed them;
@@ -736,79 +738,61 @@ int sininn_flownet_supported(const sininn_flownet_args* args);
 size_t sininn_flownet_saved_bytes(int64_t n_points);
 size_t sininn_flownet_workspace_bytes(int64_t n_points);
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args);
-int sininn_flownet_forward(const sininn_flownet_args* args, void* stream);
-int sininn_flownet_backward(const sininn_flownet_args* args, void* stream);
-/* Two coordinates per point (one frame pair: video-interpolation/pair_flow.py, ModelParams(domain_dim=2), poses (y, x)).  The dimension is an
- * ARGUMENT of these entry points; the descriptor, its size and its tag are unchanged, and domain_dim = 3 makes each of them the call of the
- * same name without `_dim` (the same kernels, the same bits).  With domain_dim = 2:
- *   networks  SININN_FLOWNET_RBF (enc_a = centres [512][2]), SININN_FLOWNET_FOURIER (enc_a = frequencies [2][256], rows y, x) and
- *             SININN_FLOWNET_RBFG (enc_a = offsets [256][2]); enc_b as above.  enc_dim 512, w[0] [256][512]; progressive: enc_dim 514, w[0]
- *             [256][514] = the columns of cat((y, x), enc), mask [514], k_active 0 .. 514, gw[0] [256][514] with an exact +0 where the mask is
- *             zero or an encoded column lies past k_active.  Every encoder evaluates the reference's two-term expressions; no t term exists.
- *   points    the descriptor's grid is (ys, xs): T must be 1, `times` is not read (NULL is fine), flows / dflows are [1][4][H][W]; the
- *             `_points_dim` calls take poses [n][2], columns (y, x), and the planar [4][n] flows / dflows of the `_points` calls.
- *   sizes     sininn_flownet_saved_bytes, sininn_flownet_workspace_bytes and sininn_flownet_forward_workspace_bytes are those above.
- *   refused   SININN_FLOWNET_PE and SININN_FLOWNET_PIECEWISE (sininn_flownet_supported_dim is 0, the error names the dimension), any other
- *             domain_dim, T != 1.  The frequency gradient, the coordinate gradient and the per-point masks have no call that takes a dimension:
- *             they exist for three coordinates only. */
-int sininn_flownet_supported_dim(const sininn_flownet_args* args, int domain_dim);
-int sininn_flownet_forward_dim(const sininn_flownet_args* args, int domain_dim, void* stream);
-int sininn_flownet_backward_dim(const sininn_flownet_args* args, int domain_dim, void* stream);
-int sininn_flownet_forward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream);
-int sininn_flownet_backward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream);
 size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args);
-int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                    void* stream);
+size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad);
+int sininn_flownet_supported_dim(const sininn_flownet_args* args, int domain_dim);
 
-/* Spatially adaptive progression (progressive_controller.py:461-710 StashedSpatialController, what --spatially-adaptive builds): every
- * point has its own 515 mask values, interpolated trilinearly from a DEVICE grid G [res^3][515] (fp32, row-major, features contiguous:
- * the controller's blurred mask).  The descriptor is the one above with progressive = 1; its `mask` is ignored and may be NULL.
- *   centre_scale: HOST array of 6 floats, read during the call: centre (t, y, x), then scale (t, y, x), the reference's center_scale;
- *   identity is 0, 0, 0, 1, 1, 1.  For the point with coordinates x_d, d = 0 .. 2 = (t, y, x), as interpolate_ does
- *   (progressive_controller.py:655-664), every operation a rounded fp32 one, nothing contracted:
+/* The call descriptor: everything a call takes BESIDE the network descriptor, which it leaves unchanged (its size and its tag too).  One
+ * struct serves the flow networks and SIREN.  `mode` states what the call is, bit by bit; nothing is inferred from a null pointer, and a
+ * field whose bit is clear is not read.  A NULL call descriptor is the plain call: the descriptor's grid of points, three coordinates, no
+ * extra output.  A new mode is one bit here, one branch in the validator (check_call, csrc/flownet_tile.h) and one clause in the Python
+ * builder (flownet.py, _call).
+ *
+ *   bit          fields read                          shapes                                   workspace                          refused
+ *   AT_POINTS    poses, n                             poses DEVICE [n][domain_dim] fp32;       saved / workspace sized for n      null poses, n < 1, n > 2^22
+ *                                                     flows / dflows planar [4][n]
+ *   SPATIAL      grid, res, centre_scale              grid DEVICE [res^3][515] fp32,           none (no forward pack)             null grid / centre_scale, res < 3, res^3 * 515 > 2^31 - 1,
+ *                                                     centre_scale HOST [6]                                                       not progressive, PPE; SIREN; domain_dim 2
+ *   ENCGRAD      g_enc_a, enc_workspace[_bytes]       g_enc_a DEVICE [3][256], OVERWRITTEN     sininn_flownet_encgrad_workspace_  forward / sample_mask; encoding != FOURIER, null g_enc_a,
+ *   (backward)                                                                                 bytes(args), 16-byte aligned       null / short enc_workspace; SIREN; domain_dim 2
+ *   POSEGRAD     g_poses, extra_workspace[_bytes]     g_poses DEVICE [n][3], OVERWRITTEN       sininn_flownet_posegrad_workspace_ forward / sample_mask; without AT_POINTS; null g_poses,
+ *   (backward)                                                                                 bytes(args, ENCGRAD set) in        null / short extra_workspace; domain_dim 2
+ *                                                                                              extra_workspace, which then holds
+ *                                                                                              the ENCGRAD workspace too
+ *                                                                                              (enc_workspace is not read);
+ *                                                                                              SIREN: none
+ *   domain_dim   3: points (t, y, x).  2: points (y, x), one frame pair (flow networks only, see below).  Anything else is refused.
+ *   also refused: a wrong struct_bytes, an unknown bit, sininn_flownet_sample_mask without SPATIAL.
+ * Every refusal comes before any launch and is one sentence under the call's name, flownet_<forward | backward | backward_encgrad |
+ * backward_posegrad>[_spatial][_points] or flownet_sample_mask[_points] (siren_...), as the mode spells it.
+ *
+ * AT_POINTS (net(poses), trainer.py:43-44, pair_flow.py:58-59, progressive_controller.py:45-53): row p of poses = (t, y, x) of point p, a
+ *   contiguous torch (n, 3) tensor, 4-byte alignment, read in place where the grid call reads the axis vectors:
+ *     flows[c][p] = net(poses[p])[c] * scale              flows / dflows are [4][n] (the grid layout with T = H = 1, W = n)
+ *   T, H, W, times, ys, xs of the descriptor are ignored and may be 0 / NULL; every other field keeps its meaning.  Tiles, partial sums and
+ *   the order of every sum depend on n alone: a pose list that spells out meshgrid(times, ys, xs) gives bitwise the flows and gradients (and,
+ *   SPATIAL, the sampled mask) of the grid call, two calls are bitwise equal and any valid k_active gives the same bits.
+ * SPATIAL (progressive_controller.py:461-710 StashedSpatialController, what --spatially-adaptive builds; at a pose list: controller(poses),
+ *   progressive_controller.py:655-680): every point has its own 515 mask values, interpolated trilinearly from the grid G (row-major,
+ *   features contiguous: the controller's blurred mask).  The descriptor has progressive = 1; its `mask` is ignored and may be NULL.
+ *   centre_scale is read during the call: centre (t, y, x), then scale (t, y, x), the reference's center_scale; identity is 0, 0, 0, 1, 1, 1.
+ *   For the point with coordinates x_d, d = 0 .. 2 = (t, y, x), as interpolate_ does (progressive_controller.py:655-664), every operation a
+ *   rounded fp32 one, nothing contracted:
  *     u_d = ((x_d - centre_d) * scale_d + 1) / 2 * max(res - 2, 1) + 0.5;   i0 = floor(u_d), i1 = ceil(u_d + 1e-6);
  *     a0 = i1 - u_d, a1 = u_d - i0 (their sum is 2 where u_d lies within 1e-6 below an integer, as in the reference);
  *     corner c = 0 .. 7 takes i / a number (c >> 2) & 1 of t, (c >> 1) & 1 of y, c & 1 of x: row = i_t + i_y res + i_x res^2 (t has
  *     stride 1), weight = (a_t a_y) a_x;   m_k(p) = sum over c in that order of weight_c * G[row_c][k].
  *   Corner indices are clamped to [0, res - 1] before the load: where the reference would raise an index error the edge cell is read.
- *   Nothing is validated on the device and nothing is read back.
- * Layer 1 reads cat((t, y, x), enc)_k * m_k(p): the mask multiplies the generated operand in registers, w[0] [256][515] is read in place;
- * there is no pack step and no forward workspace.  gw[0][j][k] = sum_p dh1[p][j] feature_k[p] m_k(p), and for the Fourier encoding
- * dE[p][k] = m_{3 + k}(p) sum_j dh1[p][j] w[0][j][3 + k] feeds g_enc_a as above.  k_active keeps its meaning: every entry of G in a
- * column from k_active on must be zero (515 is always valid); any valid value gives bitwise the same flows and gradients (finite
- * weights), every sum over points keeps its fixed order, two calls are bitwise equal, and a column of gw[0] whose grid column is all
- * zero is an exact +0.  Workspaces and `saved` have the sizes of the calls above.
- *   sininn_flownet_sample_mask writes m_k(p) for the descriptor's grid of points, out [N][515] (device): what the kernels multiply by.
- * Refused before any launch: a null grid or centre_scale, res < 3, res^3 * 515 beyond 2^31 - 1 (32-bit indexing in the kernels), a
- * descriptor that is not progressive, and PPE (27 features and a packed narrow layer 1 of its own: out of scope for this mode). */
-int sininn_flownet_forward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream);
-int sininn_flownet_backward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream);
-int sininn_flownet_backward_encgrad_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                            float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, void* stream);
-int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, float* out,
-                               void* stream);
-
-/* Arbitrary points (net(poses), trainer.py:43-44, pair_flow.py:58-59, progressive_controller.py:45-53): the same kernels at a caller's pose
- * list instead of a grid.  poses: DEVICE [n][3] fp32, row-major, row p = (t, y, x) of point p: a contiguous torch (n, 3) tensor; 4-byte
- * alignment.  It is read in place where the grid calls read the axis vectors; no pose list is copied and no encoding is stored.
- *     flows[c][p] = net(poses[p])[c] * scale              flows / dflows are [4][n] (the grid layout with T = H = 1, W = n)
- *   The descriptor is the one above; its T, H, W, times, ys, xs are ignored and may be 0 / NULL.  Every other field means what it means in
- *   the grid calls: encoding, progressive / mask / k_active, enc_a, scale; `saved` and the workspaces have the sizes of
- *   sininn_flownet_saved_bytes(n), sininn_flownet_workspace_bytes(n), sininn_flownet_forward_workspace_bytes(args) and
- *   sininn_flownet_encgrad_workspace_bytes(args).  Tiles, partial sums and the order of every sum depend on n alone: a pose list that
- *   spells out meshgrid(times, ys, xs) gives bitwise the flows and gradients of the grid call, two calls are bitwise equal and any valid
- *   k_active gives the same bits.  The gradient with respect to the coordinates is a call of its own, below.
- * Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse.  Under a spatial mask: the
- * sininn_flownet_*_spatial_points calls below. */
-int sininn_flownet_forward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
-int sininn_flownet_backward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream);
-int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a,
-                                           void* enc_workspace, size_t enc_workspace_bytes, void* stream);
-
-/* Gradient with respect to the coordinates (points mode, global masks): sininn_flownet_backward_posegrad_points does everything
- * sininn_flownet_backward_points does, and with g_enc_a != NULL everything sininn_flownet_backward_encgrad_points does (the eight gradients and
- * g_enc_a are bitwise those calls'), and also writes g_poses [n][3] fp32 (DEVICE, the layout of poses, OVERWRITTEN: it needs no
- * initialisation), the gradient of sum(dflows * flows) with respect to poses, `scale` included:
+ *   Nothing is validated on the device and nothing is read back.  Layer 1 reads cat((t, y, x), enc)_k * m_k(p): the mask multiplies the
+ *   generated operand in registers, w[0] [256][515] is read in place.  gw[0][j][k] = sum_p dh1[p][j] feature_k[p] m_k(p), and for the Fourier
+ *   encoding dE[p][k] = m_{3 + k}(p) sum_j dh1[p][j] w[0][j][3 + k] feeds g_enc_a.  k_active keeps its meaning: every entry of G in a column
+ *   from k_active on must be zero (515 is always valid); any valid value gives bitwise the same flows and gradients (finite weights), every
+ *   sum over points keeps its fixed order, and a column of gw[0] whose grid column is all zero is an exact +0.
+ *   sininn_flownet_sample_mask writes m_k(p) for the points of the call, out [N][515] (device): what the kernels multiply by.
+ * ENCGRAD: the frequency gradient of "Learnable frequencies" above, beside the eight gradients, which are bitwise those of the call without
+ *   the bit.
+ * POSEGRAD: everything the backward call at the pose list does (the eight gradients and, with ENCGRAD, g_enc_a are bitwise the same), and
+ *   g_poses, which needs no initialisation: the gradient of sum(dflows * flows) with respect to poses, `scale` included:
  *     dE[p][k]    = sum_j dh1[p][j] w[0][j][k]           (progressive: w[0][j][3 + k] * mask[3 + k], an exact zero for a closed feature)
  *     g_poses[p][d] = sum_k dE[p][k] * d feature_k / d x_d (p)   (progressive: + mask[d] * sum_j dh1[p][j] w[0][j][d])
  *   with the derivative of each encoding evaluated from the forward pass's own inputs, x = poses[p], d = 0 .. 2 = (t, y, x):
@@ -822,43 +806,36 @@ int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, cons
  *   The order of every sum is fixed and depends on nothing but the encoding: the four features of a lane in index order, the 16 lanes of a
  *   feature group by an xor butterfly, the groups of 64 features in index order, then the coordinate column.  No atomics, nothing crosses a
  *   tile: two calls are bitwise equal, a point's gradient does not depend on n or on its place in the list, and any valid k_active gives
- *   the same bits.  There is no second derivative.
- *   extra_workspace: sininn_flownet_posegrad_workspace_bytes(args, with_enc_grad) bytes, 16-byte aligned (a packed, mask-folded copy of
- *   w[0], plus, with_enc_grad != 0, what the encgrad call needs); g_enc_a may be NULL (no frequency gradient).
- * Refused before any launch: a null g_poses, a non-null g_enc_a for an encoding other than SININN_FLOWNET_FOURIER, a null or short
- * extra_workspace, and everything the points calls refuse, each with a sentence under this entry point's name.  Under a spatial mask:
- * sininn_flownet_backward_posegrad_spatial_points below. */
-size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad);
-int sininn_flownet_backward_posegrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
-                                            void* extra_workspace, size_t extra_workspace_bytes, void* stream);
-
-/* Per-point masks at pose lists (controller(poses) of a StashedSpatialController, progressive_controller.py:655-680: the reference's own way to
- * evaluate one): the spatial calls at a caller's pose list, and the points calls under the mask grid.  Every argument means what it means in
- * its two twins above: (grid, res, centre_scale) as in sininn_flownet_*_spatial, (poses, n) and the planar flows / dflows [4][n] as in
- * sininn_flownet_*_points, the trailing arguments those of the points call of the same name.  The descriptor's grid of points and its `mask`
- * are ignored.  The kernels are the spatial ones (a point's coordinates come from row p of the list): a pose list that spells out
- * meshgrid(times, ys, xs) gives bitwise the flows, the eight gradients, g_enc_a and the sampled mask of the spatial grid calls; two calls are
- * bitwise equal; any valid k_active gives the same bits.  Workspaces and `saved` have the sizes of the points calls for n
- * (sininn_flownet_posegrad_workspace_bytes for the posegrad call: the packed copy of w[0] is unmasked here).
- *   sininn_flownet_backward_posegrad_spatial_points: g_poses[p][d] = sum_k (m_{3 + k}(p) dE[p][k]) * d feature_k / d x_d (p)
- *     + m_d(p) * sum_j dh1[p][j] w[0][j][d], dE[p][k] = sum_j dh1[p][j] w[0][j][3 + k], each product with the mask a rounded fp32 one, the
- *     order of every sum that of sininn_flownet_backward_posegrad_points.  The mask is a CONSTANT of the point: the reference interpolates it
- *     under no_grad, so there is no d mask / d pose term, although m_k(p) is piecewise trilinear in the pose.
- *   sininn_flownet_sample_mask_points: out [n][515] = m_k(p) at the pose list.
- * Refused before any launch, each under its own name: everything the spatial twin refuses (a null grid or centre_scale, res, a descriptor that
- * is not progressive, PPE), everything the points twin refuses (null poses, n < 1, n > 2^22, ...). */
-int sininn_flownet_forward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                          const float* poses, int64_t n, void* stream);
-int sininn_flownet_backward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                           const float* poses, int64_t n, void* stream);
-int sininn_flownet_backward_encgrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
-                                                   size_t enc_workspace_bytes, void* stream);
-int sininn_flownet_backward_posegrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
-                                                    size_t extra_workspace_bytes, void* stream);
-int sininn_flownet_sample_mask_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                      const float* poses, int64_t n, float* out, void* stream);
+ *   the same bits.  There is no second derivative.  extra_workspace holds a packed, mask-folded copy of w[0] (SPATIAL: unmasked).
+ *   With SPATIAL: g_poses[p][d] = sum_k (m_{3 + k}(p) dE[p][k]) * d feature_k / d x_d (p) + m_d(p) * sum_j dh1[p][j] w[0][j][d], dE[p][k] =
+ *     sum_j dh1[p][j] w[0][j][3 + k], each product with the mask a rounded fp32 one, the order of every sum as above.  The mask is a CONSTANT
+ *     of the point: the reference interpolates it under no_grad, so there is no d mask / d pose term, although m_k(p) is piecewise trilinear
+ *     in the pose.
+ * domain_dim = 2 (one frame pair: video-interpolation/pair_flow.py, ModelParams(domain_dim=2), poses (y, x)):
+ *   networks  SININN_FLOWNET_RBF (enc_a = centres [512][2]), SININN_FLOWNET_FOURIER (enc_a = frequencies [2][256], rows y, x) and
+ *             SININN_FLOWNET_RBFG (enc_a = offsets [256][2]); enc_b as above.  enc_dim 512, w[0] [256][512]; progressive: enc_dim 514, w[0]
+ *             [256][514] = the columns of cat((y, x), enc), mask [514], k_active 0 .. 514, gw[0] [256][514] with an exact +0 where the mask is
+ *             zero or an encoded column lies past k_active.  Every encoder evaluates the reference's two-term expressions; no t term exists.
+ *   points    the descriptor's grid is (ys, xs): T must be 1, `times` is not read (NULL is fine), flows / dflows are [1][4][H][W]; AT_POINTS
+ *             takes poses [n][2], columns (y, x).  The size queries are those of three coordinates.
+ *   refused   SININN_FLOWNET_PE and SININN_FLOWNET_PIECEWISE (sininn_flownet_supported_dim is 0, the error names the dimension), T != 1, and
+ *             SPATIAL, ENCGRAD, POSEGRAD: they exist for three coordinates only. */
+#define SININN_FLOWNET_AT_POINTS 1u /* the points are `poses` [n][domain_dim], not the descriptor's grid                        */
+#define SININN_FLOWNET_SPATIAL 2u   /* per-point mask from `grid`; the descriptor's mask is ignored                             */
+#define SININN_FLOWNET_ENCGRAD 4u   /* backward: also g_enc_a, with enc_workspace                                               */
+#define SININN_FLOWNET_POSEGRAD 8u  /* backward: also g_poses, with extra_workspace                                             */
+typedef struct sininn_flownet_call {
+  size_t struct_bytes;                    /* must be sizeof(sininn_flownet_call)                                          */
+  unsigned mode;                          /* SININN_FLOWNET_* bits                                                        */
+  int domain_dim;                         /* 3 or 2                                                                       */
+  const float* poses; int64_t n;          /* AT_POINTS                                                                    */
+  const float* grid; int res; const float* centre_scale;                       /* SPATIAL                                 */
+  float* g_enc_a; void* enc_workspace; size_t enc_workspace_bytes;             /* ENCGRAD                                 */
+  float* g_poses; void* extra_workspace; size_t extra_workspace_bytes;         /* POSEGRAD                                */
+} sininn_flownet_call;
+int sininn_flownet_forward(const sininn_flownet_args* args, const sininn_flownet_call* call, void* stream);
+int sininn_flownet_backward(const sininn_flownet_args* args, const sininn_flownet_call* call, void* stream);
+int sininn_flownet_sample_mask(const sininn_flownet_args* args, const sininn_flownet_call* call, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).
@@ -903,18 +880,15 @@ typedef struct sininn_siren_args {
 int sininn_siren_supported(const sininn_siren_args* args);
 size_t sininn_siren_saved_bytes(int64_t n_points);
 size_t sininn_siren_workspace_bytes(int64_t n_points);
-int sininn_siren_forward(const sininn_siren_args* args, void* stream);
-int sininn_siren_backward(const sininn_siren_args* args, void* stream);
-/* Arbitrary points: h_0 = poses[p], DEVICE [n][3] fp32 row-major (4-byte alignment), read in place; flows / dflows are [4][n],
- * flows[c][p] = out[p][c] * scale.  T, H, W, times, ys, xs of the descriptor are ignored (0 / NULL); saved and workspace have the sizes of
- * sininn_siren_saved_bytes(n) / sininn_siren_workspace_bytes(n).  The same kernels: a pose list that spells out the grid gives bitwise the
- * grid call's flows and gradients.  Refused before any launch: null poses, n < 1, n > 2^22, and everything the grid calls refuse. */
-int sininn_siren_forward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream);
-int sininn_siren_backward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream);
-/* sininn_siren_backward_points, and also g_poses [n][3] (DEVICE, OVERWRITTEN, the layout of poses): g_poses[p][d] = sum_j dz_1[p][j] w[0][j][d],
- * dz_1 = omega dh_1 cos(u_1), `scale` included; 256 terms in a fixed order, no atomics; the ten gradients are bitwise those of
- * sininn_siren_backward_points.  Refused before any launch: a null g_poses and everything that call refuses. */
-int sininn_siren_backward_posegrad_points(const sininn_siren_args* args, const float* poses, int64_t n, float* g_poses, void* stream);
+/* The call descriptor is sininn_flownet_call, above (NULL: the plain call).  AT_POINTS: h_0 = poses[p], DEVICE [n][3] fp32 row-major (4-byte
+ * alignment), read in place; flows / dflows are [4][n], flows[c][p] = out[p][c] * scale; T, H, W, times, ys, xs of the descriptor are ignored
+ * (0 / NULL); saved and workspace have the sizes of sininn_siren_saved_bytes(n) / sininn_siren_workspace_bytes(n).  The same kernels: a pose
+ * list that spells out the grid gives bitwise the grid call's flows and gradients.  POSEGRAD (backward, with AT_POINTS): also g_poses [n][3]
+ * (DEVICE, OVERWRITTEN, the layout of poses): g_poses[p][d] = sum_j dz_1[p][j] w[0][j][d], dz_1 = omega dh_1 cos(u_1), `scale` included; 256
+ * terms in a fixed order, no atomics, no extra workspace; the ten gradients are bitwise those of the call without the bit.  Refused before
+ * any launch: null poses, n < 1, n > 2^22, a null g_poses, SPATIAL, ENCGRAD, a domain_dim other than 3, and everything the grid calls refuse. */
+int sininn_siren_forward(const sininn_siren_args* args, const sininn_flownet_call* call, void* stream);
+int sininn_siren_backward(const sininn_siren_args* args, const sininn_flownet_call* call, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LAMB, the optimiser of the flow trainer (video-interpolation/trainer.py:134-135: apex.optimizers.FusedLAMB(params, lr=lr)),

@@ -139,6 +139,23 @@ class SirenArgs(C.Structure):
         self.struct_bytes = C.sizeof(SirenArgs)
 
 
+AT_POINTS, SPATIAL, ENCGRAD, POSEGRAD = 1, 2, 4, 8       # SININN_FLOWNET_* mode bits of a call
+
+
+class FlowNetCall(C.Structure):
+    """Mirror of sininn_flownet_call: what a flow-network or SIREN call takes beside its network descriptor."""
+    _fields_ = [('struct_bytes', C.c_size_t), ('mode', C.c_uint), ('domain_dim', C.c_int),
+                ('poses', c_f), ('n', C.c_int64),
+                ('grid', c_f), ('res', C.c_int), ('centre_scale', C.c_void_p),
+                ('g_enc_a', c_f), ('enc_workspace', C.c_void_p), ('enc_workspace_bytes', C.c_size_t),
+                ('g_poses', c_f), ('extra_workspace', C.c_void_p), ('extra_workspace_bytes', C.c_size_t)]
+
+    def __init__(self, *a, **kw):
+        kw.setdefault('domain_dim', 3)
+        super().__init__(*a, **kw)
+        self.struct_bytes = C.sizeof(FlowNetCall)
+
+
 class LambArgs(C.Structure):
     """Mirror of sininn_lamb_args."""
     _fields_ = [('struct_bytes', C.c_size_t),
@@ -278,42 +295,19 @@ _SIGS = {
     'sininn_frames_to_u8': (C.c_int, [c_f, I64x4, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'sininn_flownet_supported': (C.c_int, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_supported_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int]),
-    'sininn_flownet_forward_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, C.c_void_p]),
-    'sininn_flownet_backward_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, C.c_void_p]),
-    'sininn_flownet_forward_points_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, c_f, C.c_int64, C.c_void_p]),
-    'sininn_flownet_backward_points_dim': (C.c_int, [C.POINTER(FlowNetArgs), C.c_int, c_f, C.c_int64, C.c_void_p]),
     'sininn_flownet_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_flownet_workspace_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_flownet_forward_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
-    'sininn_flownet_forward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
-    'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.c_void_p]),
+    'sininn_flownet_forward': (C.c_int, [C.POINTER(FlowNetArgs), C.POINTER(FlowNetCall), C.c_void_p]),
+    'sininn_flownet_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.POINTER(FlowNetCall), C.c_void_p]),
+    'sininn_flownet_sample_mask': (C.c_int, [C.POINTER(FlowNetArgs), C.POINTER(FlowNetCall), c_f, C.c_void_p]),
     'sininn_flownet_encgrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
-    'sininn_flownet_backward_encgrad': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
-    'sininn_flownet_forward_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, C.c_void_p]),
-    'sininn_flownet_backward_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, C.c_void_p]),
-    'sininn_flownet_backward_encgrad_spatial': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_void_p, C.c_size_t,
-                                                          C.c_void_p]),
-    'sininn_flownet_sample_mask': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_void_p]),
-    'sininn_flownet_forward_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, C.c_void_p]),
-    'sininn_flownet_backward_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, C.c_void_p]),
-    'sininn_flownet_backward_encgrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
     'sininn_flownet_posegrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs), C.c_int]),
-    'sininn_flownet_backward_posegrad_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int64, c_f, c_f, C.c_void_p, C.c_size_t, C.c_void_p]),
-    'sininn_flownet_forward_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, C.c_void_p]),
-    'sininn_flownet_backward_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, C.c_void_p]),
-    'sininn_flownet_backward_encgrad_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, c_f, C.c_void_p,
-                                                                 C.c_size_t, C.c_void_p]),
-    'sininn_flownet_backward_posegrad_spatial_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, c_f, c_f,
-                                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
-    'sininn_flownet_sample_mask_points': (C.c_int, [C.POINTER(FlowNetArgs), c_f, C.c_int, c_f, c_f, C.c_int64, c_f, C.c_void_p]),
-    'sininn_siren_backward_posegrad_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, c_f, C.c_void_p]),
     'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
     'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_siren_workspace_bytes': (C.c_size_t, [C.c_int64]),
-    'sininn_siren_forward': (C.c_int, [C.POINTER(SirenArgs), C.c_void_p]),
-    'sininn_siren_backward': (C.c_int, [C.POINTER(SirenArgs), C.c_void_p]),
-    'sininn_siren_forward_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, C.c_void_p]),
-    'sininn_siren_backward_points': (C.c_int, [C.POINTER(SirenArgs), c_f, C.c_int64, C.c_void_p]),
+    'sininn_siren_forward': (C.c_int, [C.POINTER(SirenArgs), C.POINTER(FlowNetCall), C.c_void_p]),
+    'sininn_siren_backward': (C.c_int, [C.POINTER(SirenArgs), C.POINTER(FlowNetCall), C.c_void_p]),
     'sininn_adam_step': (C.c_int, [c_f, c_f, c_f, c_f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                    C.c_float, C.c_int, C.c_float, C.c_void_p]),
     'sininn_lamb_workspace_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
@@ -345,7 +339,7 @@ def lib():
         if handle.sininn_version() != 4:
             raise ImportError('libsininn.so ABI version mismatch')
         for which, mirror in enumerate((ConvArgs, WgradItem, DenseArgs, GlowArgs, SubnetArgs, PackDesc, DenseBf16Args,
-                                        FlowNetArgs, LambArgs, SirenArgs)):
+                                        FlowNetArgs, LambArgs, SirenArgs, FlowNetCall)):
             if handle.sininn_sizeof(which) != C.sizeof(mirror):
                 raise ImportError(f'{mirror.__name__}: the ctypes mirror has {C.sizeof(mirror)} bytes, libsininn.so was built '
                                   f'with {handle.sininn_sizeof(which)} (include/sininn.h changed without _lib.py)')

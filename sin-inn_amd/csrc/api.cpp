@@ -120,47 +120,19 @@ void profile_begin(int h, unsigned long long* stamps, int max_launches);
 int profile_end(int* count, float* total_ms);
 int flownet_supported(const sininn_flownet_args* a, const char* who);
 int flownet_supported_dim(const sininn_flownet_args* a, int dim, const char* who);
-int flownet_forward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st);
-int flownet_backward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st);
 size_t flownet_saved_bytes(int64_t n);
 size_t flownet_workspace_bytes(int64_t n);
 size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a);
-int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st);
-int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st);
+int flownet_forward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, hipStream_t st);
+int flownet_backward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, hipStream_t st);
+int flownet_sample_mask_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, float* out, hipStream_t st);
 size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a);
-int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
-int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st);
-int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st);
-int flownet_backward_encgrad_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* g_enc_a,
-                                            void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st);
-int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st);
-int flownet_forward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st);
-int flownet_backward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st);
-int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
-                                           size_t enc_workspace_bytes, hipStream_t st);
 size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad);
-int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
-                                            void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st);
-int flownet_forward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
-                                          int64_t n, hipStream_t st);
-int flownet_backward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
-                                           int64_t n, hipStream_t st);
-int flownet_backward_encgrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
-                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                                   hipStream_t st);
-int flownet_backward_posegrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
-                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
-                                                    size_t extra_workspace_bytes, hipStream_t st);
-int flownet_sample_mask_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
-                                      int64_t n, float* out, hipStream_t st);
-int siren_backward_posegrad_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, float* g_poses, hipStream_t st);
 int siren_supported(const sininn_siren_args* a, const char* who);
 size_t siren_saved_bytes(int64_t n);
 size_t siren_workspace_bytes(int64_t n);
-int siren_forward_launch(const sininn_siren_args* a, hipStream_t st);
-int siren_backward_launch(const sininn_siren_args* a, hipStream_t st);
-int siren_forward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st);
-int siren_backward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st);
+int siren_forward_launch(const sininn_siren_args* a, const sininn_flownet_call* call, hipStream_t st);
+int siren_backward_launch(const sininn_siren_args* a, const sininn_flownet_call* call, hipStream_t st);
 size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
 int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st);
 int lamb_step_launch(const sininn_lamb_args* a, hipStream_t st);
@@ -295,6 +267,7 @@ size_t sininn_sizeof(int which) {
     case 7: return sizeof(sininn_flownet_args);
     case 8: return sizeof(sininn_lamb_args);
     case 9: return sizeof(sininn_siren_args);
+    case 10: return sizeof(sininn_flownet_call);
     default: return 0;
   }
 }
@@ -612,96 +585,30 @@ int sininn_flownet_supported(const sininn_flownet_args* args) { return flownet_s
 int sininn_flownet_supported_dim(const sininn_flownet_args* args, int domain_dim) {
   return flownet_supported_dim(args, domain_dim, "sininn_flownet_supported_dim");
 }
-int sininn_flownet_forward_dim(const sininn_flownet_args* args, int domain_dim, void* stream) {
-  return flownet_forward_dim_launch(args, domain_dim, nullptr, 0, 0, ST(stream));
-}
-int sininn_flownet_backward_dim(const sininn_flownet_args* args, int domain_dim, void* stream) {
-  return flownet_backward_dim_launch(args, domain_dim, nullptr, 0, 0, ST(stream));
-}
-int sininn_flownet_forward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream) {
-  return flownet_forward_dim_launch(args, domain_dim, poses, n, 1, ST(stream));
-}
-int sininn_flownet_backward_points_dim(const sininn_flownet_args* args, int domain_dim, const float* poses, int64_t n, void* stream) {
-  return flownet_backward_dim_launch(args, domain_dim, poses, n, 1, ST(stream));
-}
 size_t sininn_flownet_saved_bytes(int64_t n_points) { return flownet_saved_bytes(n_points); }
 size_t sininn_flownet_workspace_bytes(int64_t n_points) { return flownet_workspace_bytes(n_points); }
 size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* args) { return flownet_forward_workspace_bytes(args); }
-int sininn_flownet_forward(const sininn_flownet_args* args, void* stream) { return flownet_forward_launch(args, ST(stream)); }
-int sininn_flownet_backward(const sininn_flownet_args* args, void* stream) { return flownet_backward_launch(args, ST(stream)); }
+int sininn_flownet_forward(const sininn_flownet_args* args, const sininn_flownet_call* call, void* stream) {
+  return flownet_forward_launch(args, call, ST(stream));
+}
+int sininn_flownet_backward(const sininn_flownet_args* args, const sininn_flownet_call* call, void* stream) {
+  return flownet_backward_launch(args, call, ST(stream));
+}
+int sininn_flownet_sample_mask(const sininn_flownet_args* args, const sininn_flownet_call* call, float* out, void* stream) {
+  return flownet_sample_mask_launch(args, call, out, ST(stream));
+}
 size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args) { return flownet_encgrad_workspace_bytes(args); }
-int sininn_flownet_backward_encgrad(const sininn_flownet_args* args, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                    void* stream) {
-  return flownet_backward_encgrad_launch(args, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
-}
-int sininn_flownet_forward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream) {
-  return flownet_forward_spatial_launch(args, grid, res, centre_scale, ST(stream));
-}
-int sininn_flownet_backward_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, void* stream) {
-  return flownet_backward_spatial_launch(args, grid, res, centre_scale, ST(stream));
-}
-int sininn_flownet_backward_encgrad_spatial(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                            float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, void* stream) {
-  return flownet_backward_encgrad_spatial_launch(args, grid, res, centre_scale, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
-}
-int sininn_flownet_sample_mask(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, float* out,
-                               void* stream) {
-  return flownet_sample_mask_launch(args, grid, res, centre_scale, out, ST(stream));
-}
-int sininn_flownet_forward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream) {
-  return flownet_forward_points_launch(args, poses, n, ST(stream));
-}
-int sininn_flownet_backward_points(const sininn_flownet_args* args, const float* poses, int64_t n, void* stream) {
-  return flownet_backward_points_launch(args, poses, n, ST(stream));
-}
-int sininn_flownet_backward_encgrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
-                                           size_t enc_workspace_bytes, void* stream) {
-  return flownet_backward_encgrad_points_launch(args, poses, n, g_enc_a, enc_workspace, enc_workspace_bytes, ST(stream));
-}
 size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad) {
   return flownet_posegrad_workspace_bytes(args, with_enc_grad);
-}
-int sininn_flownet_backward_posegrad_points(const sininn_flownet_args* args, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
-                                            void* extra_workspace, size_t extra_workspace_bytes, void* stream) {
-  return flownet_backward_posegrad_points_launch(args, poses, n, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, ST(stream));
-}
-int sininn_flownet_forward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                          const float* poses, int64_t n, void* stream) {
-  return flownet_forward_spatial_points_launch(args, grid, res, centre_scale, poses, n, ST(stream));
-}
-int sininn_flownet_backward_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                           const float* poses, int64_t n, void* stream) {
-  return flownet_backward_spatial_points_launch(args, grid, res, centre_scale, poses, n, ST(stream));
-}
-int sininn_flownet_backward_encgrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
-                                                   size_t enc_workspace_bytes, void* stream) {
-  return flownet_backward_encgrad_spatial_points_launch(args, grid, res, centre_scale, poses, n, g_enc_a, enc_workspace, enc_workspace_bytes,
-                                                        ST(stream));
-}
-int sininn_flownet_backward_posegrad_spatial_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale,
-                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
-                                                    size_t extra_workspace_bytes, void* stream) {
-  return flownet_backward_posegrad_spatial_points_launch(args, grid, res, centre_scale, poses, n, g_poses, g_enc_a, extra_workspace,
-                                                         extra_workspace_bytes, ST(stream));
-}
-int sininn_flownet_sample_mask_points(const sininn_flownet_args* args, const float* grid, int res, const float* centre_scale, const float* poses,
-                                      int64_t n, float* out, void* stream) {
-  return flownet_sample_mask_points_launch(args, grid, res, centre_scale, poses, n, out, ST(stream));
-}
-int sininn_siren_backward_posegrad_points(const sininn_siren_args* args, const float* poses, int64_t n, float* g_poses, void* stream) {
-  return siren_backward_posegrad_points_launch(args, poses, n, g_poses, ST(stream));
 }
 int sininn_siren_supported(const sininn_siren_args* args) { return siren_supported(args, "sininn_siren_supported"); }
 size_t sininn_siren_saved_bytes(int64_t n_points) { return siren_saved_bytes(n_points); }
 size_t sininn_siren_workspace_bytes(int64_t n_points) { return siren_workspace_bytes(n_points); }
-int sininn_siren_forward(const sininn_siren_args* args, void* stream) { return siren_forward_launch(args, ST(stream)); }
-int sininn_siren_backward(const sininn_siren_args* args, void* stream) { return siren_backward_launch(args, ST(stream)); }
-int sininn_siren_forward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream) {
-  return siren_forward_points_launch(args, poses, n, ST(stream));
+int sininn_siren_forward(const sininn_siren_args* args, const sininn_flownet_call* call, void* stream) {
+  return siren_forward_launch(args, call, ST(stream));
 }
-int sininn_siren_backward_points(const sininn_siren_args* args, const float* poses, int64_t n, void* stream) {
-  return siren_backward_points_launch(args, poses, n, ST(stream));
+int sininn_siren_backward(const sininn_siren_args* args, const sininn_flownet_call* call, void* stream) {
+  return siren_backward_launch(args, call, ST(stream));
 }
 
 size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors) { return lamb_workspace_bytes(n_chunks, n_tensors); }

@@ -55,26 +55,26 @@
 //           next to gb1 and is launched on the open 128-column tiles only; flownet_reduce_l1_kernel scatters the sums into
 //           nn.Linear's [256][515] layout, times the mask, exact zeros where the mask is zero.
 //
-// points    (sininn_flownet_*_points) the coordinates of point p are row p of a caller's pose list [N][3] instead of an entry of each axis
+// points    (SININN_FLOWNET_AT_POINTS) the coordinates of point p are row p of a caller's pose list [N][3] instead of an entry of each axis
 //           vector: point_coord (flownet_tile.h) branches on q.poses, a kernel argument, and the host sets T = H = 1, W = N, which makes
 //           the [T][4][H][W] indexing of flows / dflows the planar [4][N].  No kernel is instantiated for it and nothing else differs:
 //           tiles, `saved`, workspaces and the order of every sum depend on N alone, so a pose list that spells out a grid gives the grid
-//           call's bits.  Combined with the spatial mode (sininn_flownet_*_spatial_points) it is PoseList plus Spatial in one FlowNetDev:
+//           call's bits.  Combined with the spatial mode (AT_POINTS | SPATIAL) it is PoseList plus Spatial in one FlowNetDev:
 //           the SPATIAL instantiations below take a point's coordinates through point_coord as well, so they serve a pose list as they are.
 //
-// two coordinates (sininn_flownet_*_dim with domain_dim = 2: one frame pair, poses (y, x)) the number of coordinates is a template
+// two coordinates (domain_dim = 2 in the call descriptor: one frame pair, poses (y, x)) the number of coordinates is a template
 //           parameter DIM of flownet_fwd_kernel, flownet_wgrad_kernel, flownet_pack_kernel and flownet_reduce_l1_kernel, 3 by default: the
 //           three-coordinate instantiations are the code they were.  DIM = 2 exists for the Enc<> rows that say PAIR (RBF, Fourier, RBFG):
 //           point_coord_dim<2> reads two values per point, encode4<KIND, 2> reads centres [512][2] / frequencies [2][256] / offsets [256][2]
 //           and evaluates two-term expressions (no zero is fed for t: in RBFG it would not drop out), the progressive W1 is [256][514] and
 //           its two coordinate columns fill the [256][4] K group with two zero columns, the coordinate sums of gW1 are two.  The chain
 //           kernel, the hidden layers' weight gradient and every workspace size do not see the dimension.  No per-point mask, frequency
-//           gradient or pose gradient at DIM = 2: no entry point offers them.
+//           gradient or pose gradient at DIM = 2: check_call refuses them.
 //
-// pose gradient (sininn_flownet_backward_posegrad_points) after the whole backward of a points call: flownet_posegrad_kernel contracts
+// pose gradient (SININN_FLOWNET_POSEGRAD) after the whole backward of a points call: flownet_posegrad_kernel contracts
 //           dE = dh1 W1 (the GEMM of the frequency gradient, for every encoding) with the analytic derivative of the encoding over the
 //           FEATURES of each point: g_poses [N][3].  A tile owns its points: no partial sums in memory, no atomics, a fixed order.  DESIGN 14.8
-//           SPATIAL (sininn_flownet_backward_posegrad_spatial_points): a per-point mask cannot be folded into the packed W1, so the pack is
+//           SPATIAL (POSEGRAD | SPATIAL): a per-point mask cannot be folded into the packed W1, so the pack is
 //           unmasked and the kernel multiplies dE[p][k] by m_k(p) after the GEMM, and the coordinate column's sum by m_d(p), from the corner
 //           tile staged once per tile.  The mask is a CONSTANT of the point: the reference interpolates it under no_grad
 //           (progressive_controller.py:655-680), so there is no d mask / d pose term.  DESIGN 14.9
@@ -1482,17 +1482,10 @@ size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
   return has ? FN_EG_FLOATS * sizeof(float) : 0;
 }
 
-// what the spatial entry points take beside the descriptor
-struct SpatialArgs {
-  const float* grid;
-  int res;
-  const float* centre_scale;   // host [6]
-};
-
 // the head of every entry point: a struct of this library's size that describes a network the kernels are built for; spatial != nullptr:
 // and the spatial mode, a 515-wide progressive network and a grid the kernels can index.  Everything a launch would trip over, before any
 // launch
-// dim: coordinates per point; 2 exists without a spatial mask only (the entry points that take a dimension take no grid)
+// dim: coordinates per point; 2 exists without a spatial mask only (check_call has refused the grid there)
 static int check_head(const sininn_flownet_args* a, const char* who, const SpatialArgs* spatial, int dim = FN_DOM) {
   SININN_CHECK(a != nullptr, "%s: null args", who);
   SININN_CHECK(a->struct_bytes == sizeof(sininn_flownet_args), "%s: struct_bytes is %zu, this library was built with %zu", who,
@@ -1579,12 +1572,6 @@ static int for_pair(const sininn_flownet_args* a, F&& f) {
   });
 }
 
-// the name an entry point refuses under: <stem>[_spatial][_points]
-static const char* call_name(const char* plain, const char* spatial_name, const char* points_name, const char* both, const SpatialArgs* spatial,
-                             const PoseList* pl) {
-  return spatial ? (pl ? both : spatial_name) : (pl ? points_name : plain);
-}
-
 // layer 1: gW1 = dh1^T (regenerated input), gb1, and their reduction into nn.Linear's layout
 template <int KIND, bool PROG, bool SPATIAL, int DIM = FN_DOM>
 static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hipStream_t st) {
@@ -1610,13 +1597,18 @@ static int wgrad_l1_launch(const sininn_flownet_args* a, const FlowNetDev& q, hi
   return 0;
 }
 
-// g_enc_a != nullptr: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own
-// spatial != nullptr: layer 1 under the per-point mask of that grid.  pl != nullptr: at that pose list.  The entry point has called check_head
-// who != nullptr: the name every refusal is made under (the posegrad call), else the names the backward calls have always used.
+// ENCGRAD: also the gradient of the frequencies, from dh1 (which the weight-gradient kernels only read) and a workspace of its own, enc_ws
+// SPATIAL: layer 1 under the per-point mask of that grid.  AT_POINTS: at that pose list.  The caller has called check_head
+// Every refusal is made under the call's own name where that is the posegrad call or the spatial call at a pose list, else under the names
+// the backward calls have always used.
 // out_q != nullptr: receives the kernels' descriptor of the call (dh1 is slot 0 of q.dh) for a kernel the caller launches after these
-// dim = 2: two coordinates per point; no grid, no frequency gradient (the entry points that take a dimension offer neither)
-static int backward_launch(const sininn_flownet_args* a, float* g_enc_a, float* enc_ws, hipStream_t st, const SpatialArgs* spatial,
-                           const PoseList* pl = nullptr, const char* who = nullptr, FlowNetDev* out_q = nullptr, int dim = FN_DOM) {
+// domain_dim 2: two coordinates per point; no grid, no frequency gradient (check_call has refused both)
+static int backward_launch(const sininn_flownet_args* a, const Call& c, float* enc_ws, hipStream_t st, FlowNetDev* out_q = nullptr) {
+  const SpatialArgs* const spatial = c.spatial();
+  const PoseList* const pl = c.pl();
+  const int dim = c.c.domain_dim;
+  float* const g_enc_a = c.has(SININN_FLOWNET_ENCGRAD) ? c.c.g_enc_a : nullptr;
+  const char* const who = c.has(SININN_FLOWNET_POSEGRAD) || (spatial && pl) ? c.who() : nullptr;
   FlowNetDev q;
   if (int rc = fill_args(a, who ? who : spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl, dim)) return rc;
   if (int rc = check_backward_buffers<4>(a, who ? who : pl ? "flownet_backward_points" : "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q))
@@ -1691,9 +1683,13 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
   return 0;
 }
 
-static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr,
-                          int dim = FN_DOM) {
-  const char* who = call_name("flownet_forward", "flownet_forward_spatial", "flownet_forward_points", "flownet_forward_spatial_points", spatial, pl);
+int flownet_forward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, hipStream_t st) {
+  Call c;
+  if (int rc = check_call(call, "flownet", CALL_FORWARD, c)) return rc;
+  const SpatialArgs* const spatial = c.spatial();
+  const PoseList* const pl = c.pl();
+  const int dim = c.c.domain_dim;
+  const char* const who = c.who();
   FlowNetDev q;
   if (int rc = check_head(a, who, spatial, dim)) return rc;
   if (int rc = fill_args(a, who, q, spatial, pl, dim)) return rc;
@@ -1705,102 +1701,38 @@ static int forward_launch(const sininn_flownet_args* a, hipStream_t st, const Sp
   });
 }
 
-int flownet_forward_launch(const sininn_flownet_args* a, hipStream_t st) { return forward_launch(a, st, nullptr); }
-
-int flownet_forward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  return forward_launch(a, st, &s);
-}
-
-static int backward_plain_launch(const sininn_flownet_args* a, hipStream_t st, const SpatialArgs* spatial, const PoseList* pl = nullptr,
-                                 int dim = FN_DOM) {
-  const char* who = call_name("flownet_backward", "flownet_backward_spatial", "flownet_backward_points", "flownet_backward_spatial_points", spatial, pl);
-  if (int rc = check_head(a, who, spatial, dim)) return rc;
-  return backward_launch(a, nullptr, nullptr, st, spatial, pl, spatial && pl ? who : nullptr, nullptr, dim);   // the earlier calls keep their sentences
-}
-
-// ---- the dimension as an argument: 3 is the calls above, 2 a network on (y, x) (one frame pair); poses == nullptr: the descriptor's grid ----
-int flownet_forward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return forward_launch(a, st, nullptr, points ? &pl : nullptr, dim);
-}
-
-int flownet_backward_dim_launch(const sininn_flownet_args* a, int dim, const float* poses, int64_t n, int points, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return backward_plain_launch(a, st, nullptr, points ? &pl : nullptr, dim);
-}
-
-int flownet_backward_launch(const sininn_flownet_args* a, hipStream_t st) { return backward_plain_launch(a, st, nullptr); }
-
-int flownet_backward_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  return backward_plain_launch(a, st, &s);
-}
-
-static int sample_mask_launch(const sininn_flownet_args* a, const SpatialArgs& s, const PoseList* pl, float* out, hipStream_t st) {
-  const char* who = pl ? "flownet_sample_mask_points" : "flownet_sample_mask";
-  if (int rc = check_head(a, who, &s)) return rc;
+int flownet_sample_mask_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, float* out, hipStream_t st) {
+  Call c;
+  if (int rc = check_call(call, "flownet", CALL_SAMPLE_MASK, c)) return rc;
+  const char* const who = c.who();
+  if (int rc = check_head(a, who, c.spatial())) return rc;
   SININN_CHECK(out != nullptr, "%s: null out", who);
   FlowNetDev q{};
-  if (int rc = check_points(a, who, q, pl)) return rc;
-  q.sp = spatial_of(&s);
+  if (int rc = check_points(a, who, q, c.pl())) return rc;
+  q.sp = spatial_of(c.spatial());
   const size_t units = ((size_t)q.N * FN_GROUPS + FN_NTHR - 1) / FN_NTHR;
   hipLaunchKernelGGL(flownet_sample_mask_kernel, dim3((unsigned)(units < 8192 ? units : 8192)), dim3(FN_NTHR), 0, st, q, out);
   SININN_LAUNCH_CHECK("flownet_sample_mask");
   return 0;
 }
 
-int flownet_sample_mask_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* out, hipStream_t st) {
-  return sample_mask_launch(a, SpatialArgs{grid, res, centre_scale}, nullptr, out, st);
-}
-
-// the head under this entry point's own name, so that a refusal of the spatial mode (PPE, a null grid, res) comes before the Fourier-only
+// the head under this call's own name, so that a refusal of the spatial mode (PPE, a null grid, res) comes before the Fourier-only
 // refusal, which would hide it
-static int backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st,
-                                   const SpatialArgs* spatial, const PoseList* pl = nullptr) {
-  const char* who = call_name("flownet_backward_encgrad", "flownet_backward_encgrad_spatial", "flownet_backward_encgrad_points",
-                              "flownet_backward_encgrad_spatial_points", spatial, pl);
-  if (int rc = check_head(a, who, spatial)) return rc;
+static int backward_encgrad_launch(const sininn_flownet_args* a, const Call& c, hipStream_t st) {
+  const char* const who = c.who();
+  if (int rc = check_head(a, who, c.spatial())) return rc;
   SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
                a->encoding);
-  SININN_CHECK(g_enc_a != nullptr, "%s: null g_enc_a", who);
-  SININN_CHECK(enc_workspace != nullptr && enc_workspace_bytes >= flownet_encgrad_workspace_bytes(a),
-               "%s: enc_workspace holds %zu bytes, %zu needed", who, enc_workspace ? enc_workspace_bytes : (size_t)0,
+  SININN_CHECK(c.c.g_enc_a != nullptr, "%s: null g_enc_a", who);
+  SININN_CHECK(c.c.enc_workspace != nullptr && c.c.enc_workspace_bytes >= flownet_encgrad_workspace_bytes(a),
+               "%s: enc_workspace holds %zu bytes, %zu needed", who, c.c.enc_workspace ? c.c.enc_workspace_bytes : (size_t)0,
                flownet_encgrad_workspace_bytes(a));
-  SININN_CHECK(aligned16(enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
-  return backward_launch(a, g_enc_a, static_cast<float*>(enc_workspace), st, spatial, pl, spatial && pl ? who : nullptr);
+  SININN_CHECK(aligned16(c.c.enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
+  return backward_launch(a, c, static_cast<float*>(c.c.enc_workspace), st);
 }
 
-int flownet_backward_encgrad_launch(const sininn_flownet_args* a, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                    hipStream_t st) {
-  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, nullptr);
-}
-
-int flownet_backward_encgrad_spatial_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, float* g_enc_a,
-                                            void* enc_workspace, size_t enc_workspace_bytes, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, &s);
-}
-
-// ---- points mode: the same launches at a pose list [n][3]; the descriptor's grid is not read, flows / dflows are [4][n] ----
-int flownet_forward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return forward_launch(a, st, nullptr, &pl);
-}
-
-int flownet_backward_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return backward_plain_launch(a, st, nullptr, &pl);
-}
-
-int flownet_backward_encgrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_enc_a, void* enc_workspace,
-                                           size_t enc_workspace_bytes, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, nullptr, &pl);
-}
-
-// ---- points mode with the gradient of the coordinates.  extra workspace: the packed W1 of flownet_posegrad_pack_kernel, then (with the
-// frequency gradient) the workspace of the encgrad call ----
+// ---- POSEGRAD: the gradient of the coordinates.  extra workspace: the packed W1 of flownet_posegrad_pack_kernel, then (with ENCGRAD) the
+// workspace of the frequency gradient ----
 static size_t posegrad_pack_bytes(const sininn_flownet_args* a) {
   return for_kind(a->encoding, (size_t)0, [](auto k) { return posegrad_pack_floats<decltype(k)::value>() * sizeof(float); });
 }
@@ -1829,65 +1761,34 @@ static int posegrad_kind_launch(const sininn_flownet_args* a, const FlowNetDev& 
   return 0;
 }
 
-static int backward_posegrad_launch(const sininn_flownet_args* a, const SpatialArgs* spatial, const PoseList& pl, float* g_poses, float* g_enc_a,
-                                    void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st) {
-  const char* who = spatial ? "flownet_backward_posegrad_spatial_points" : "flownet_backward_posegrad_points";
-  if (int rc = check_head(a, who, spatial)) return rc;
-  SININN_CHECK(g_poses != nullptr, "%s: null g_poses", who);
-  SININN_CHECK(g_enc_a == nullptr || flownet_encgrad_workspace_bytes(a) != 0,
+static int backward_posegrad_launch(const sininn_flownet_args* a, const Call& c, hipStream_t st) {
+  const char* const who = c.who();
+  const bool enc_grad = c.has(SININN_FLOWNET_ENCGRAD);
+  if (int rc = check_head(a, who, c.spatial())) return rc;
+  SININN_CHECK(c.c.g_poses != nullptr, "%s: null g_poses", who);
+  SININN_CHECK(!enc_grad || flownet_encgrad_workspace_bytes(a) != 0,
                "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only (pass a null g_enc_a)", who, a->encoding);
-  const size_t need = flownet_posegrad_workspace_bytes(a, g_enc_a != nullptr);
-  SININN_CHECK(extra_workspace != nullptr && extra_workspace_bytes >= need, "%s: extra_workspace holds %zu bytes, %zu needed", who,
-               extra_workspace ? extra_workspace_bytes : (size_t)0, need);
-  SININN_CHECK(aligned16(extra_workspace), "%s: extra_workspace must be 16-byte aligned", who);
-  float* const wt = static_cast<float*>(extra_workspace);
-  float* const enc_ws = g_enc_a ? wt + posegrad_pack_bytes(a) / sizeof(float) : nullptr;
+  SININN_CHECK(!enc_grad || c.c.g_enc_a != nullptr, "%s: null g_enc_a", who);
+  const size_t need = flownet_posegrad_workspace_bytes(a, enc_grad);
+  SININN_CHECK(c.c.extra_workspace != nullptr && c.c.extra_workspace_bytes >= need, "%s: extra_workspace holds %zu bytes, %zu needed", who,
+               c.c.extra_workspace ? c.c.extra_workspace_bytes : (size_t)0, need);
+  SININN_CHECK(aligned16(c.c.extra_workspace), "%s: extra_workspace must be 16-byte aligned", who);
+  float* const wt = static_cast<float*>(c.c.extra_workspace);
+  float* const enc_ws = enc_grad ? wt + posegrad_pack_bytes(a) / sizeof(float) : nullptr;
   FlowNetDev q;                                        // every check is backward_launch's, made before its first launch
-  if (int rc = backward_launch(a, g_enc_a, enc_ws, st, spatial, &pl, who, &q)) return rc;
-  return for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
-    return posegrad_kind_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, wt, g_poses, st);
+  if (int rc = backward_launch(a, c, enc_ws, st, &q)) return rc;
+  return for_mode(a, c.spatial() != nullptr, [&](auto k, auto prog, auto sp) {
+    return posegrad_kind_launch<decltype(k)::value, decltype(prog)::value, decltype(sp)::value>(a, q, wt, c.c.g_poses, st);
   });
 }
 
-int flownet_backward_posegrad_points_launch(const sininn_flownet_args* a, const float* poses, int64_t n, float* g_poses, float* g_enc_a,
-                                            void* extra_workspace, size_t extra_workspace_bytes, hipStream_t st) {
-  return backward_posegrad_launch(a, nullptr, PoseList{poses, n}, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, st);
-}
-
-// ---- points mode under a per-point mask: PoseList plus Spatial in one call; the kernels are the SPATIAL instantiations ----
-int flownet_forward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
-                                          int64_t n, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  const PoseList pl{poses, n};
-  return forward_launch(a, st, &s, &pl);
-}
-
-int flownet_backward_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
-                                           int64_t n, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  const PoseList pl{poses, n};
-  return backward_plain_launch(a, st, &s, &pl);
-}
-
-int flownet_backward_encgrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
-                                                   const float* poses, int64_t n, float* g_enc_a, void* enc_workspace, size_t enc_workspace_bytes,
-                                                   hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  const PoseList pl{poses, n};
-  return backward_encgrad_launch(a, g_enc_a, enc_workspace, enc_workspace_bytes, st, &s, &pl);
-}
-
-int flownet_backward_posegrad_spatial_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale,
-                                                    const float* poses, int64_t n, float* g_poses, float* g_enc_a, void* extra_workspace,
-                                                    size_t extra_workspace_bytes, hipStream_t st) {
-  const SpatialArgs s{grid, res, centre_scale};
-  return backward_posegrad_launch(a, &s, PoseList{poses, n}, g_poses, g_enc_a, extra_workspace, extra_workspace_bytes, st);
-}
-
-int flownet_sample_mask_points_launch(const sininn_flownet_args* a, const float* grid, int res, const float* centre_scale, const float* poses,
-                                      int64_t n, float* out, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return sample_mask_launch(a, SpatialArgs{grid, res, centre_scale}, &pl, out, st);
+int flownet_backward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, hipStream_t st) {
+  Call c;
+  if (int rc = check_call(call, "flownet", CALL_BACKWARD, c)) return rc;
+  if (c.has(SININN_FLOWNET_POSEGRAD)) return backward_posegrad_launch(a, c, st);
+  if (c.has(SININN_FLOWNET_ENCGRAD)) return backward_encgrad_launch(a, c, st);
+  if (int rc = check_head(a, c.who(), c.spatial(), c.c.domain_dim)) return rc;
+  return backward_launch(a, c, nullptr, st);
 }
 
 }  // namespace sininn

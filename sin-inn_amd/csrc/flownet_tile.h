@@ -5,7 +5,8 @@
 //           into a helper, each of them changed the instructions of a hot kernel.  The two transpose kernels stay where they are too
 //   host    check_points / check_layers / check_saved / check_forward_buffers / check_backward_buffers: the parts of a descriptor and
 //           their refusals that do not depend on the network (check_points: the grid of a call, or, poses != nullptr, its pose list);
-//           chain_blocks, raise_lds
+//           chain_blocks, raise_lds; Call / check_call / call_name: the call descriptor of an entry point, validated, and the name it
+//           refuses under
 #pragma once
 #include "common.h"
 
@@ -174,6 +175,81 @@ int check_points(const A* a, const char* who, Q& q, const PoseList* pl = nullptr
   }
   q.N = q.T * q.H * q.W;
   q.ntiles = (q.N + FN_P - 1) / FN_P;
+  return 0;
+}
+
+// the per-point mask of a call: what SPATIAL adds
+struct SpatialArgs {
+  const float* grid;
+  int res;
+  const float* centre_scale;   // host [6]
+};
+
+// ---- the call descriptor (sininn_flownet_call) as the launch functions take it: validated by check_call, the plain call for a null one ----
+enum CallKind { CALL_FORWARD, CALL_BACKWARD, CALL_SAMPLE_MASK };
+
+struct Call {
+  sininn_flownet_call c;
+  PoseList points;
+  SpatialArgs grid;
+  std::string name;            // the name the call refuses under: <stem>[_spatial][_points]
+  bool has(unsigned bit) const { return (c.mode & bit) != 0; }
+  const PoseList* pl() const { return has(SININN_FLOWNET_AT_POINTS) ? &points : nullptr; }
+  const SpatialArgs* spatial() const { return has(SININN_FLOWNET_SPATIAL) ? &grid : nullptr; }
+  const char* who() const { return name.c_str(); }
+};
+
+// the name an entry point refuses under: <net>_<forward | backward[_encgrad | _posegrad]>[_spatial][_points], <net>_sample_mask[_points]
+std::string call_name(const char* net, CallKind kind, unsigned mode) {
+  const char* const stem = kind == CALL_FORWARD                 ? "_forward"
+                           : kind == CALL_SAMPLE_MASK           ? "_sample_mask"
+                           : mode & SININN_FLOWNET_POSEGRAD     ? "_backward_posegrad"
+                           : mode & SININN_FLOWNET_ENCGRAD      ? "_backward_encgrad"
+                                                                : "_backward";
+  return std::string(net) + stem + (mode & SININN_FLOWNET_SPATIAL && kind != CALL_SAMPLE_MASK ? "_spatial" : "") +
+         (mode & SININN_FLOWNET_AT_POINTS ? "_points" : "");
+}
+
+// the head of every run entry point: the call descriptor itself (its size, its bits, its dimension) and the combinations no kernel exists
+// for, each refused in one sentence that names it, before the network descriptor is looked at.  net: "flownet" or "siren"
+int check_call(const sininn_flownet_call* in, const char* net, CallKind kind, Call& out) {
+  const bool siren = net[0] == 's';
+  out.c = sininn_flownet_call{};
+  out.c.struct_bytes = sizeof(sininn_flownet_call);
+  out.c.domain_dim = 3;
+  if (in) {
+    out.name = call_name(net, kind, 0);
+    SININN_CHECK(in->struct_bytes == sizeof(sininn_flownet_call), "%s: call descriptor: struct_bytes is %zu, this library was built with %zu",
+                 out.who(), in->struct_bytes, sizeof(sininn_flownet_call));
+    out.c = *in;
+  }
+  const unsigned known = SININN_FLOWNET_AT_POINTS | SININN_FLOWNET_SPATIAL | SININN_FLOWNET_ENCGRAD | SININN_FLOWNET_POSEGRAD;
+  const unsigned mode = out.c.mode;
+  const int dim = out.c.domain_dim;
+  out.name = call_name(net, kind, mode);
+  out.points = PoseList{out.c.poses, out.c.n};
+  out.grid = SpatialArgs{out.c.grid, out.c.res, out.c.centre_scale};
+  const char* const who = out.who();
+  SININN_CHECK((mode & ~known) == 0, "%s: call descriptor: unknown mode bits 0x%x (AT_POINTS 1, SPATIAL 2, ENCGRAD 4, POSEGRAD 8)", who,
+               mode & ~known);
+  if (siren) {
+    SININN_CHECK(dim == 3, "%s: domain_dim %d: the SIREN kernels take three coordinates per point", who, dim);
+    SININN_CHECK(!out.has(SININN_FLOWNET_SPATIAL), "%s: SPATIAL with SIREN: a per-point mask needs a progressive encoding, SIREN has none", who);
+    SININN_CHECK(!out.has(SININN_FLOWNET_ENCGRAD), "%s: ENCGRAD with SIREN: there is no frequency matrix to differentiate", who);
+  } else {
+    SININN_CHECK(dim == 3 || dim == 2, "%s: domain_dim %d: the kernels take 3 coordinates per point (t, y, x) or 2 (y, x)", who, dim);
+  }
+  if (kind != CALL_BACKWARD)
+    SININN_CHECK(!(mode & (SININN_FLOWNET_ENCGRAD | SININN_FLOWNET_POSEGRAD)),
+                 "%s: ENCGRAD / POSEGRAD outside a backward call: the frequency and the coordinate gradient are outputs of the backward pass", who);
+  SININN_CHECK(kind != CALL_SAMPLE_MASK || out.has(SININN_FLOWNET_SPATIAL), "%s: sample_mask without SPATIAL: the mask it samples is the grid's", who);
+  SININN_CHECK(!out.has(SININN_FLOWNET_POSEGRAD) || out.has(SININN_FLOWNET_AT_POINTS),
+               "%s: POSEGRAD without AT_POINTS: the coordinate gradient is one with respect to a pose list", who);
+  if (dim == 2) {
+    SININN_CHECK(!out.has(SININN_FLOWNET_SPATIAL), "%s: domain_dim 2 with SPATIAL: the mask grid is one over (t, y, x)", who);
+    SININN_CHECK(!out.has(SININN_FLOWNET_ENCGRAD), "%s: domain_dim 2 with ENCGRAD: the frequency gradient exists for three coordinates only", who);
+    SININN_CHECK(!out.has(SININN_FLOWNET_POSEGRAD), "%s: domain_dim 2 with POSEGRAD: the coordinate gradient exists for three coordinates only", who);
+  }
   return 0;
 }
 

@@ -24,9 +24,9 @@
 //           buffers of a forward / backward call; from flownet.hip the hidden layers' weight gradient (hidden_wgrad_launch).  The output
 //           layer, dout, the tile load, the column sums and the transpose kernel match flownet.hip's text but stay spelled out: as helpers
 //           they changed the instructions, or the placement, of these kernels.
-// points    (sininn_siren_*_points) point_coord reads row p of a caller's pose list [N][3] instead of the axis vectors; T = H = 1, W = N makes
+// points    (SININN_FLOWNET_AT_POINTS) point_coord reads row p of a caller's pose list [N][3] instead of the axis vectors; T = H = 1, W = N makes
 //           flows / dflows the planar [4][N].  The same kernels, nothing else differs (see flownet.hip)
-// pose gradient (sininn_siren_backward_posegrad_points) siren_bwd_chain_kernel<true> also writes g_poses[p][d] = sum_j dz_1[p][j] W1[j][d] from the
+// pose gradient (SININN_FLOWNET_POSEGRAD) siren_bwd_chain_kernel<true> also writes g_poses[p][d] = sum_j dz_1[p][j] W1[j][d] from the
 //           dz_1 tile it holds at the end of a tile; <false> is the kernel as it was, instruction for instruction
 // Rows of the last tile beyond N are computed on a clamped point in the forward pass and carry dout = 0 in the backward pass, so every
 // saved / workspace row is written before it is read and contributes exact zeros to every sum.
@@ -351,10 +351,12 @@ static int check_args(const sininn_siren_args* a, const char* who, SirenDev& q, 
   return 0;
 }
 
-static int forward_launch(const sininn_siren_args* a, hipStream_t st, const PoseList* pl) {
+int siren_forward_launch(const sininn_siren_args* a, const sininn_flownet_call* call, hipStream_t st) {
+  Call c;
+  if (int rc = check_call(call, "siren", CALL_FORWARD, c)) return rc;
   SirenDev q;
-  const char* who = pl ? "siren_forward_points" : "siren_forward";
-  if (int rc = check_args(a, who, q, pl)) return rc;
+  const char* const who = c.who();
+  if (int rc = check_args(a, who, q, c.pl())) return rc;
   if (int rc = check_forward_buffers(a, who, siren_saved_bytes(q.N), q)) return rc;
   if (raise_lds(siren_fwd_kernel, SR_LDS, "siren_forward")) return 1;
   hipLaunchKernelGGL(siren_fwd_kernel, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), SR_LDS, st, q);   // two resident blocks per CU
@@ -362,11 +364,15 @@ static int forward_launch(const sininn_siren_args* a, hipStream_t st, const Pose
   return 0;
 }
 
-// g_poses != nullptr (with a pose list): the chain kernel that also writes the gradient of the coordinates; everything else is the same
-static int backward_launch(const sininn_siren_args* a, hipStream_t st, const PoseList* pl, float* g_poses = nullptr) {
+// POSEGRAD (with a pose list): the chain kernel that also writes the gradient of the coordinates; everything else is the same
+int siren_backward_launch(const sininn_siren_args* a, const sininn_flownet_call* call, hipStream_t st) {
+  Call c;
+  if (int rc = check_call(call, "siren", CALL_BACKWARD, c)) return rc;
   SirenPoseDev q;
-  const char* who = g_poses ? "siren_backward_posegrad_points" : pl ? "siren_backward_points" : "siren_backward";
-  if (int rc = check_args(a, who, q, pl)) return rc;
+  const char* const who = c.who();
+  float* const g_poses = c.has(SININN_FLOWNET_POSEGRAD) ? c.c.g_poses : nullptr;
+  SININN_CHECK(!c.has(SININN_FLOWNET_POSEGRAD) || g_poses != nullptr, "%s: null g_poses", who);
+  if (int rc = check_args(a, who, q, c.pl())) return rc;
   q.g_poses = g_poses;
   if (int rc = check_backward_buffers<SR_SINES + 1>(a, who, siren_saved_bytes(q.N), siren_workspace_bytes(q.N), q)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
@@ -394,26 +400,6 @@ static int backward_launch(const sininn_siren_args* a, hipStream_t st, const Pos
   for (int l = SR_SINES - 1; l >= 1; --l)                // gW_{l+1} = dz_{l+1}^T h_l
     if (int rc = hidden_wgrad_launch(q.ntiles, q.dz + (l - 1) * lstride, q.hin + (l - 1) * lstride, q.part, a->gw[l], a->gb[l], st)) return rc;
   return 0;
-}
-
-int siren_forward_launch(const sininn_siren_args* a, hipStream_t st) { return forward_launch(a, st, nullptr); }
-int siren_backward_launch(const sininn_siren_args* a, hipStream_t st) { return backward_launch(a, st, nullptr); }
-
-// points mode: the same launches at a pose list [n][3]; the descriptor's grid is not read, flows / dflows are [4][n]
-int siren_forward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return forward_launch(a, st, &pl);
-}
-
-int siren_backward_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, hipStream_t st) {
-  const PoseList pl{poses, n};
-  return backward_launch(a, st, &pl);
-}
-
-int siren_backward_posegrad_points_launch(const sininn_siren_args* a, const float* poses, int64_t n, float* g_poses, hipStream_t st) {
-  SININN_CHECK(g_poses != nullptr, "siren_backward_posegrad_points: null g_poses");
-  const PoseList pl{poses, n};
-  return backward_launch(a, st, &pl, g_poses);
 }
 
 }  // namespace sininn

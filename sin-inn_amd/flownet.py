@@ -31,7 +31,7 @@ tensor is not inspected on the host and runs over all 515 features.  Both give b
 `RFF` / `PRFF` train the encoding itself: `encode.frequencies` is an nn.Parameter [3][256] and the network uses
 `F_eff = normalize(frequencies, dim=0) * magnitudes` (`magnitudes` a buffer).  `flow_fields` computes F_eff with torch ops under
 autograd on every call (768 values) and hands it to the kernels as the frequency matrix, so the forward pass is the Fourier one;
-the backward pass (`sininn_flownet_backward_encgrad`) carries the gradient through layer 1 onto F_eff, all in fp32 with a fixed
+the backward pass (`sininn_flownet_backward` in its ENCGRAD mode) carries the gradient through layer 1 onto F_eff, all in fp32 with a fixed
 summation order, and torch's `normalize` backward takes it to `encode.frequencies.grad`.  With `frequencies.requires_grad` false,
 or grad mode off, the plain backward / inference path runs and nothing extra is computed.
 
@@ -65,31 +65,35 @@ then `weight.uniform_`).  It runs in kernels of its own (csrc/siren.hip, `siren_
 Spatially adaptive progression (`sin_inn_amd.progressive.StashedSpatialController`, the reference's `--spatially-adaptive`): every
 point has its own 515 mask values, interpolated trilinearly from the controller's blurred grid [res^3][515] on the device.  The
 per-point mask never exists in memory either: the kernels sample the grid while they generate the operand of layer 1
-(`flownet_forward_spatial` / `flownet_backward_spatial`, `sininn_flownet_*_spatial`), W1 is read in place and there is no pack step.
+(`flownet_forward_spatial` / `flownet_backward_spatial`, the SPATIAL mode), W1 is read in place and there is no pack step.
 `flow_fields` takes that controller (`k_active` = its `next_block`), or a raw grid as a 2-D `override_mask`; `flownet_sample_mask`
 returns the interpolated mask itself (the reference's `get_mask=` keyword).  All 515-wide progressive networks; `PPE` is refused.
 
-One call path serves the three modes (global mask or none, per-point mask, SIREN).  `Mask` is the mask of a call: the device tensor,
+One call path serves every mode.  The library has five run entry points, `sininn_{flownet,siren}_{forward,backward}` and
+`sininn_flownet_sample_mask`; each takes the network descriptor and, beside it, a call descriptor (`_lib.FlowNetCall`) whose mode bits say
+what the call is: AT_POINTS (a pose list, not the descriptor's grid), SPATIAL (a per-point mask), ENCGRAD / POSEGRAD (the backward call also
+returns the frequency / the coordinate gradient), and the number of coordinates.  `Mask` is the mask of a call: the device tensor,
 `k_active` and, for a grid, `res` and `centre_scale`; `.spatial` is the one way to ask which it is, and `_resolve_mask`, the controllers'
-`device_mask` / `device_grid`, `_FlowFields` and `flow_fields` pass it around.  A descriptor is built by `_args` / `_siren_args`, which share
-the grid of points and the layers (`_points_and_layers`); `_forward` allocates `flows` / `saved` and calls, `_backward` checks `dflows`, allocates
-the workspace and the gradients, calls, and carries the optional frequency gradient.  The six public forward / backward functions name their
-descriptor builder, their size queries and their library call and nothing else; `_FlowFields` is the one autograd function, `_mode` picks
-the pair of functions and their keyword arguments for it (`_SirenFields.apply` is its SIREN call under the earlier name).
+`device_mask` / `device_grid`, `_FlowFields` and `flow_fields` pass it around.  A network descriptor is built by `_args` / `_siren_args`, which
+share the points (a grid or a pose list) and the layers (`_points_and_layers`); `_call` builds the call descriptor from it, one clause per
+bit; `_forward` allocates `flows` / `saved` and calls, `_backward` checks `dflows`, allocates the workspace and the gradients, calls, and returns
+the extra gradients the mode asked for.  The public forward / backward functions name their two builders and nothing else; `_FlowFields` and
+`_FlowAt` are the two autograd functions over one body (`_fields_forward` / `_fields_backward`), `_functions` picks the pair of functions and
+their keyword arguments for them (`_SirenFields.apply` is the SIREN call of `_FlowFields` under the earlier name).
 
 Arbitrary points: `flow_at(net, poses, scale)` and, through it, `net(poses)` and `controller(poses, override_mask=, get_mask=)`
-evaluate the same kernels at a caller's pose list (..., 3) -> (..., 4) (`sininn_flownet_*_points` / `sininn_siren_*_points`): the kernels
+evaluate the same kernels at a caller's pose list (..., 3) -> (..., 4) (the AT_POINTS mode): the kernels
 read point p's coordinates from row p of the list where the grid mode reads the three axis vectors, and nothing else differs, so the
 flows and gradients of a list that spells out a grid are bitwise those of the grid call.  The kernels write the planar (4, N) layout
 (`planar=True` returns it); the transpose to the reference's (N, 4) is a torch op.  Differentiable with respect to the parameters
 (`_FlowAt`, next to `_FlowFields`), learnable frequencies included, and, with `pose_grad=True`, with respect to the coordinates: the
-backward pass then is `sininn_flownet_backward_posegrad_points` / `sininn_siren_backward_posegrad_points`, which contract dh1 W1 with the
+backward pass then runs in the POSEGRAD mode, which contracts dh1 W1 with the
 analytic derivative of the encoding over the features of each point (csrc/flownet.hip, flownet_posegrad_kernel).
 
 Per-point masks at pose lists: `controller(poses)` of a `StashedSpatialController` is the reference's own way to evaluate one
 (progressive_controller.py:670-680), and `flow_at` takes that controller, or any controller with a grid (res^3, 515) on the device as a 2-D
 `override_mask`.  The calls are `flownet_forward_spatial_points` / `flownet_backward_spatial_points` / `flownet_sample_mask_points`
-(`sininn_flownet_*_spatial_points`): the spatial kernels at a pose list, bitwise the spatial grid call where the list spells out a grid;
+(AT_POINTS | SPATIAL): the spatial kernels at a pose list, bitwise the spatial grid call where the list spells out a grid;
 `pose_grad=True` runs the SPATIAL form of flownet_posegrad_kernel.  The mask is a constant of the point there, as in the reference, which
 interpolates it under no_grad: the pose gradient has no d mask / d pose term.  A bare progressive model with a grid is still refused at a
 pose list: the interpolation is a controller's.
@@ -97,7 +101,7 @@ pose list: the interpolation is a controller's.
 Two coordinates (`ModelParams(domain_dim=2)`, the network of video-interpolation/pair_flow.py:39-42): RBF, FFN, UFF, RBFG and their
 progressive forms PRBF, PFF, PUFF, PRBFG are built on (y, x) with the reference's layouts (`encode.centres` [512][2], `encode.frequencies`
 [2][256], `encode.offsets` [256][2], a progressive first weight [256][514] = the columns of cat((y, x), enc)) and run in the DIM = 2
-instantiations of the kernels (`sininn_flownet_{forward,backward}[_points]_dim`, the dimension an argument beside the unchanged descriptor).
+instantiations of the kernels (`domain_dim = 2` in the call descriptor, beside the unchanged network descriptor).
 `flow_fields(net_or_controller, None, h, w, scale)` is one frame pair, poses linspace(-1, 1, h) x linspace(-1, 1, w) (pair_flow.py:55-59),
 flows (1, 4, h, w): `times` must be None.  `flow_at`, `net(poses)` and `controller(poses, ..)` take (..., 2) -> (..., 4).  The global mask has
 514 values in blocks of 4, `override_mask`, `get_mask` and `k_active` work as at three coordinates.  Refused there, each with a ValueError
@@ -538,7 +542,7 @@ class Mask(NamedTuple):
 def _points_and_layers(a, lins, times, ys, xs, scale, dim=3):
     """the grid of points (axes on the GPU, T H W, scale, pointers) and the nn.Linear layers of a descriptor.  `ys is None`: `times`
     is a pose list (N, dim); the descriptor gets the planar shape T = H = 1, W = N that `flows` / `dflows` have then and no axis
-    pointers, and `a._poses` is what the points entry points take beside it.  `dim == 2` on a grid: the axes are (ys, xs), `times`
+    pointers, and `a._poses` is what the call descriptor takes of it (None on a grid).  `dim == 2` on a grid: the axes are (ys, xs), `times`
     is None and T = 1"""
     if ys is None:
         poses = times
@@ -556,14 +560,14 @@ def _points_and_layers(a, lins, times, ys, xs, scale, dim=3):
         ys, xs = ys.contiguous(), xs.contiguous()
         a.T, a.H, a.W, a.scale = 1, ys.numel(), xs.numel(), float(scale)
         a.ys, a.xs = ptr(ys), ptr(xs)
-        a._axes, a._device = (ys, xs), ys.device
+        a._axes, a._device, a._poses = (ys, xs), ys.device, None
     else:
         for t in (times, ys, xs):
             _on_gpu(t)
         times, ys, xs = times.contiguous(), ys.contiguous(), xs.contiguous()
         a.T, a.H, a.W, a.scale = times.numel(), ys.numel(), xs.numel(), float(scale)
         a.times, a.ys, a.xs = ptr(times), ptr(ys), ptr(xs)
-        a._axes, a._device = (times, ys, xs), times.device       # the contiguous copies live as long as the descriptor
+        a._axes, a._device, a._poses = (times, ys, xs), times.device, None   # the contiguous copies live as long as the descriptor
     for l, lin in enumerate(lins):
         _on_gpu(lin.weight, 'parameter')
         assert lin.weight.is_contiguous() and lin.bias.is_contiguous()
@@ -613,7 +617,7 @@ def _args(net, times, ys, xs, scale, mask=None, k_active=None, enc_a=None, spati
     a.encoding = net.encode.kind
     a.progressive = int(bool(net.is_progressive))
     a.enc_dim, a.hidden, a.layers, a.out_dim = net.encoding_dim, net.opt.hidden_dim, net.opt.num_layers, net.opt.output_channels
-    dim = a._dim = int(net.opt.domain_dim)               # travels beside the descriptor, to the `_dim` entry points
+    dim = a._dim = int(net.opt.domain_dim)               # travels beside the descriptor, in the call descriptor
     if dim != 3:
         _refuse_pair_modes(net, dim, spatial, enc_a)
     if not _lib.lib().sininn_flownet_supported_dim(C.byref(a), dim):   # the library's refusal names the sizes it is built for
@@ -657,53 +661,18 @@ def _siren_args(net, times, ys, xs, scale, omega=None):
         raise ValueError(why)
     if len(lins) != 5:
         raise ValueError(f'siren kernels take 5 linear layers; got {len(lins)}')
+    a._dim = 3
     return _points_and_layers(a, lins, times, ys, xs, scale)
 
 
 def _spatial(a, grid, res, centre_scale):
-    """(device grid, res, the six host floats) as the spatial entry points take them, checked against the descriptor"""
+    """(device grid, res, the six host floats) as the call descriptor takes them, checked against the descriptor"""
     _on_gpu(grid, 'mask grid')
     res = int(res)
     assert grid.dtype == torch.float32 and grid.is_contiguous() and tuple(grid.shape) == (res ** 3, a.enc_dim), \
         f'a mask grid of shape (res^3, {a.enc_dim}), contiguous fp32'
     a._cs = (C.c_float * 6)(*[float(v) for v in (IDENTITY_SCALE if centre_scale is None else centre_scale)])
     return ptr(grid), res, C.cast(a._cs, C.c_void_p)
-
-
-# ---- the two halves every call shares: a = a finished descriptor, `call` its library entry point, `extra` what that takes beside it ----
-def _forward(a, train, saved, saved_shape, call, *extra):
-    """allocate flows and (train) `saved` of `saved_shape()`, call, return (flows, saved)"""
-    flows = torch.empty(a.T, 4, a.H, a.W, device=a._device, dtype=torch.float32)
-    a.flows = ptr(flows)
-    if train:
-        if saved is None:
-            saved = torch.empty(saved_shape(), device=a._device, dtype=torch.float32)
-        assert saved.is_cuda and saved.is_contiguous() and saved.dtype == torch.float32
-        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
-    else:
-        saved = None
-    check(call(C.byref(a), *extra, _stream()))
-    return flows, saved
-
-
-def _backward_buffers(a, net, dflows, saved, workspace, workspace_bytes):
-    """check dflows, allocate the workspace (`workspace_bytes(N)`) and the gradients into the descriptor.  Returns ([gW1, gb1, ..], keep):
-    `keep` holds the tensors the descriptor points into (the contiguous dflows, the workspace); the caller keeps it until the library call
-    has been made, so that nothing it allocates in between lands in their memory"""
-    _on_gpu(dflows)
-    dflows = dflows.contiguous()
-    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
-    if workspace is None:
-        workspace = torch.empty(workspace_bytes(a.T * a.H * a.W) // 4, device=a._device, dtype=torch.float32)
-    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
-    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
-    a.dflows = ptr(dflows)
-    grads = []
-    for l, lin in enumerate(net.linears()):
-        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
-        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
-        grads += [gw, gb]
-    return grads, (dflows, workspace)
 
 
 def _out_tensor(given, shape, device):
@@ -713,42 +682,111 @@ def _out_tensor(given, shape, device):
     return t
 
 
-def _backward(a, net, dflows, saved, workspace, workspace_bytes, call, *extra, enc_call=None, enc_workspace=None, g_enc_a=None):
-    """the backward half: `_backward_buffers`, then `call`; `enc_call`: the entry point that also returns the frequency gradient,
-    ([gW1, ..], gF) then"""
-    grads, keep = _backward_buffers(a, net, dflows, saved, workspace, workspace_bytes)  # noqa: F841 (keep: alive until the call is made)
-    if enc_call is None:
-        check(call(C.byref(a), *extra, _stream()))
-        return grads
-    if enc_workspace is None:
-        enc_workspace = torch.empty(_lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
-    g_enc = _out_tensor(g_enc_a, (3, 256), a._device)
-    check(enc_call(C.byref(a), *extra, ptr(g_enc), ptr(enc_workspace), enc_workspace.numel() * 4, _stream()))
-    return grads, g_enc
+def _call(a, mask=None, enc_grad=False, enc_workspace=None, g_enc_a=None, pose_grad=False, pose_workspace=None, g_poses=None):
+    """the call descriptor of a finished network descriptor `a`: what the call takes beside it, one clause per mode bit.  The dimension and
+    the pose list are the descriptor's (`_args` / `_siren_args`), `mask` a Mask that is `.spatial` (or None), `enc_grad` / `pose_grad` the
+    extra gradients of a backward call, with the caller's buffers or new ones.  `c._g_enc` / `c._g_poses` are those outputs; `c._keep` holds
+    every tensor the descriptor points into, for as long as the descriptor lives"""
+    c = _lib.FlowNetCall(domain_dim=a._dim)
+    c._g_enc = c._g_poses = None
+    if a._poses is not None:
+        c.mode |= _lib.AT_POINTS
+        c.poses, c.n = a._poses
+    if mask is not None and mask.spatial:
+        c.mode |= _lib.SPATIAL
+        c.grid, c.res, c.centre_scale = _spatial(a, mask.tensor, mask.res, mask.centre_scale)
+    if pose_grad:
+        if a._dim != 3:
+            raise ValueError(f'domain_dim {a._dim}: pose_grad=True is out of scope: the coordinate gradient exists for three coordinates only')
+        assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
+        c.mode |= _lib.POSEGRAD
+        c._g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
+        c.g_poses = ptr(c._g_poses)
+        if isinstance(a, _lib.FlowNetArgs):              # SIREN's posegrad call takes no extra workspace
+            if pose_workspace is None:
+                nbytes = _lib.lib().sininn_flownet_posegrad_workspace_bytes(C.byref(a), int(enc_grad))
+                pose_workspace = torch.empty(nbytes // 4, device=a._device, dtype=torch.float32)
+            c.extra_workspace, c.extra_workspace_bytes = ptr(pose_workspace), pose_workspace.numel() * 4
+    if enc_grad:
+        c.mode |= _lib.ENCGRAD
+        c._g_enc = _out_tensor(g_enc_a, (3, 256), a._device)
+        c.g_enc_a = ptr(c._g_enc)
+        if not pose_grad:
+            if enc_workspace is None:
+                nbytes = _lib.lib().sininn_flownet_encgrad_workspace_bytes(C.byref(a))
+                enc_workspace = torch.empty(nbytes // 4, device=a._device, dtype=torch.float32)
+            c.enc_workspace, c.enc_workspace_bytes = ptr(enc_workspace), enc_workspace.numel() * 4
+    c._keep = (mask, enc_workspace, pose_workspace)
+    return c
+
+
+# ---- the two halves every call shares: a = a finished descriptor, `stem` its family of entry points (sininn_<stem>_forward / _backward),
+# c = its call descriptor ----
+def _forward(a, train, saved, saved_shape, stem, c):
+    """allocate flows and (train) `saved` of `saved_shape()`, call, return (flows, saved); at a pose list flows is the planar (4, N)"""
+    flows = torch.empty(a.T, 4, a.H, a.W, device=a._device, dtype=torch.float32)
+    a.flows = ptr(flows)
+    if train:
+        if saved is None:
+            saved = torch.empty(saved_shape(), device=a._device, dtype=torch.float32)
+        assert saved.is_cuda and saved.is_contiguous() and saved.dtype == torch.float32
+        a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    else:
+        saved = None
+    check(getattr(_lib.lib(), f'sininn_{stem}_forward')(C.byref(a), C.byref(c), _stream()))
+    return (flows.view(4, -1) if a._poses is not None else flows), saved
+
+
+def _backward(a, net, dflows, saved, workspace, stem, c):
+    """the backward half: check dflows (at a pose list: (4, N)), allocate the workspace (sininn_<stem>_workspace_bytes(N)) and the gradients
+    into the descriptor, call.  [gW1, gb1, ..]; with the frequency gradient (grads, gF); with the pose gradient (either of those, g_poses)"""
+    lib = _lib.lib()
+    _on_gpu(dflows)
+    dflows = (dflows.reshape(1, 4, 1, -1) if a._poses is not None else dflows).contiguous()
+    assert tuple(dflows.shape) == (a.T, 4, a.H, a.W) and dflows.dtype == torch.float32
+    if workspace is None:
+        workspace = torch.empty(getattr(lib, f'sininn_{stem}_workspace_bytes')(a.T * a.H * a.W) // 4, device=a._device, dtype=torch.float32)
+    a.saved, a.saved_bytes = ptr(saved), saved.numel() * 4
+    a.workspace, a.workspace_bytes = ptr(workspace), workspace.numel() * 4
+    a.dflows = ptr(dflows)
+    grads = []
+    for l, lin in enumerate(net.linears()):
+        gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
+        a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
+        grads += [gw, gb]
+    check(getattr(lib, f'sininn_{stem}_backward')(C.byref(a), C.byref(c), _stream()))   # dflows, workspace: alive until the call is made
+    out = grads if c._g_enc is None else (grads, c._g_enc)
+    return out if c._g_poses is None else (out, c._g_poses)
 
 
 def _flownet_saved_shape(a):
     return lambda: (3, _lib.lib().sininn_flownet_saved_bytes(a.T * a.H * a.W) // (3 * 256 * 4), 256)
 
 
+def _siren_saved_shape(a):
+    return lambda: _lib.lib().sininn_siren_saved_bytes(a.T * a.H * a.W) // 4
+
+
 def _pack_workspace(a):
-    """a progressive forward call: the workspace of the packed, masked copy of W1"""
+    """a progressive forward call under a global mask: the workspace of the packed, masked copy of W1"""
     if a.progressive:
         a._pack = torch.empty(_lib.lib().sininn_flownet_forward_workspace_bytes(C.byref(a)) // 4, device=a._device, dtype=torch.float32)
         a.workspace, a.workspace_bytes = ptr(a._pack), a._pack.numel() * 4
     return a
 
 
+# ---- the public calls: `times, ys, xs` a grid of points, or (the `_points` forms) a pose list (N, domain_dim) with planar flows / dflows
+# (4, N); a global mask or none, or (the `_spatial` forms) a per-point mask from a grid.  Each builds its descriptor and its call
+# descriptor and names the family ----
 def flownet_forward(net, times, ys, xs, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
     """flows (t, 4, h, w) = net(meshgrid(times, ys, xs)) * scale, and (train) the saved hidden layers as a
     (3, Npad, 256) tensor -- the post-ReLU activations, so `saved > 0` are the gates the kernel took (`saved`: optional
     caller-provided buffer of that shape).  Progressive networks: `mask` is a device tensor of 515 floats (PPE: 27) and `k_active` a
     number of leading features after which the mask is all zero (None: 515, nothing is skipped).  `enc_a`: the frequency matrix
-    (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here)."""
+    (3, 256) to use instead of the encoding's own (learnable encodings: F_eff; None: computed here).  Two coordinates: `times` is None,
+    the axes are (ys, xs)."""
     a = _pack_workspace(_args(net, times, ys, xs, scale, mask, k_active, enc_a))
-    if a._dim != 3:                                      # two coordinates: `times` is None, the axes are (ys, xs)
-        return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_dim, a._dim)
-    return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward)
+    return _forward(a, train, saved, _flownet_saved_shape(a), 'flownet', _call(a))
 
 
 def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
@@ -759,11 +797,7 @@ def flownet_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, m
     matrix the kernels read; `enc_workspace`: optional fp32 tensor of sininn_flownet_encgrad_workspace_bytes bytes for it,
     `g_enc_a`: optional (3, 256) fp32 tensor that receives gF."""
     a = _args(net, times, ys, xs, scale, mask, k_active, enc_a)
-    if a._dim != 3:
-        return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward_dim,
-                         a._dim)
-    return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward,
-                     enc_call=_lib.lib().sininn_flownet_backward_encgrad if enc_grad else None, enc_workspace=enc_workspace, g_enc_a=g_enc_a)
+    return _backward(a, net, dflows, saved, workspace, 'flownet', _call(a, None, enc_grad, enc_workspace, g_enc_a))
 
 
 def flownet_forward_spatial(net, times, ys, xs, scale, train, grid, res, centre_scale=None, k_active=None, saved=None, enc_a=None):
@@ -771,24 +805,24 @@ def flownet_forward_spatial(net, times, ys, xs, scale, train, grid, res, centre_
     host floats, centre (t, y, x) then scale (t, y, x), None: identity; `k_active`: every grid column from there on is zero (None:
     515).  No workspace: W1 is read in place."""
     a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
-    return _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_spatial, *_spatial(a, grid, res, centre_scale))
+    return _forward(a, train, saved, _flownet_saved_shape(a), 'flownet', _call(a, Mask(grid, k_active, res, centre_scale)))
 
 
 def flownet_backward_spatial(net, times, ys, xs, scale, dflows, saved, grid, res, centre_scale=None, k_active=None, workspace=None,
                              enc_a=None, enc_grad=False, enc_workspace=None, g_enc_a=None):
     """flownet_backward under the per-point mask of the forward call; the arguments of flownet_backward and flownet_forward_spatial"""
     a = _args(net, times, ys, xs, scale, None, k_active, enc_a, spatial=True)
-    return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_workspace_bytes, _lib.lib().sininn_flownet_backward_spatial,
-                     *_spatial(a, grid, res, centre_scale), enc_call=_lib.lib().sininn_flownet_backward_encgrad_spatial if enc_grad else None,
-                     enc_workspace=enc_workspace, g_enc_a=g_enc_a)
+    return _backward(a, net, dflows, saved, workspace, 'flownet',
+                     _call(a, Mask(grid, k_active, res, centre_scale), enc_grad, enc_workspace, g_enc_a))
 
 
 def flownet_sample_mask(net, times, ys, xs, grid, res, centre_scale=None):
-    """the interpolated mask (N, 515) of the grid of points, bitwise what the spatial kernels multiply layer 1's input by"""
+    """the interpolated mask (N, 515) of the grid of points (`ys is None`: of the pose list `times`), bitwise what the spatial kernels
+    multiply layer 1's input by"""
     a = _args(net, times, ys, xs, 1.0, spatial=True)
-    extra = _spatial(a, grid, res, centre_scale)
+    c = _call(a, Mask(grid, None, res, centre_scale))
     out = torch.empty(a.T * a.H * a.W, a.enc_dim, device=a._device, dtype=torch.float32)
-    check(_lib.lib().sininn_flownet_sample_mask(C.byref(a), *extra, ptr(out), _stream()))
+    check(_lib.lib().sininn_flownet_sample_mask(C.byref(a), C.byref(c), ptr(out), _stream()))
     return out
 
 
@@ -797,156 +831,119 @@ def siren_forward(net, times, ys, xs, scale, train, saved=None, omega=None):
     opaque fp32 tensor of sininn_siren_saved_bytes(N) bytes (`saved`: optional caller-provided buffer of that size).  `omega`:
     instead of the network's own omega_0 (None)."""
     a = _siren_args(net, times, ys, xs, scale, omega)
-    return _forward(a, train, saved, lambda: _lib.lib().sininn_siren_saved_bytes(a.T * a.H * a.W) // 4, _lib.lib().sininn_siren_forward)
+    return _forward(a, train, saved, _siren_saved_shape(a), 'siren', _call(a))
 
 
 def siren_backward(net, times, ys, xs, scale, dflows, saved, workspace=None, omega=None):
     """[gW1, gb1, .., gW5, gb5] for an upstream gradient dflows (t, 4, h, w); `saved`: that of the forward call on the same weights
     and omega; `workspace`: optional fp32 tensor of at least sininn_siren_workspace_bytes(N) bytes (allocated here otherwise)."""
     a = _siren_args(net, times, ys, xs, scale, omega)
-    return _backward(a, net, dflows, saved, workspace, _lib.lib().sininn_siren_workspace_bytes, _lib.lib().sininn_siren_backward)
+    return _backward(a, net, dflows, saved, workspace, 'siren', _call(a))
 
 
-# ---- the same four calls at a pose list (N, 3): flows and dflows are planar, (4, N) ----
 def flownet_forward_points(net, poses, scale, train, saved=None, mask=None, k_active=None, enc_a=None):
-    """flownet_forward at a pose list (N, 3) on the device: flows (4, N) = net(poses)^T * scale; `saved` as there, for N points"""
-    a = _pack_workspace(_args(net, poses, None, None, scale, mask, k_active, enc_a))
-    if a._dim != 3:                                      # a pose list (N, 2), columns (y, x)
-        flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_points_dim, a._dim, *a._poses)
-    else:
-        flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_points, *a._poses)
-    return flows.view(4, -1), saved
+    """flownet_forward at a pose list (N, 3) on the device (two coordinates: (N, 2), columns (y, x)): flows (4, N) = net(poses)^T * scale;
+    `saved` as there, for N points"""
+    return flownet_forward(net, poses, None, None, scale, train, saved, mask, k_active, enc_a)
 
 
 def flownet_backward_points(net, poses, scale, dflows, saved, workspace=None, mask=None, k_active=None, enc_a=None, enc_grad=False,
                             enc_workspace=None, g_enc_a=None, pose_grad=False, pose_workspace=None, g_poses=None):
     """flownet_backward at the pose list of the forward call, dflows (4, N); everything else as there.  `pose_grad=True` returns
-    (what the call returns without it, g_poses): g_poses (N, 3), the gradient with respect to the coordinates, from
-    sininn_flownet_backward_posegrad_points, which computes everything else as well (bitwise the same); `pose_workspace`: optional fp32
+    (what the call returns without it, g_poses): g_poses (N, 3), the gradient with respect to the coordinates, from the POSEGRAD mode of
+    sininn_flownet_backward, which computes everything else as well (bitwise the same); `pose_workspace`: optional fp32
     tensor of sininn_flownet_posegrad_workspace_bytes bytes (it holds the frequency gradient's workspace too: `enc_workspace` is refused),
     `g_poses`: optional (N, 3) fp32 tensor that receives the gradient"""
     a = _args(net, poses, None, None, scale, mask, k_active, enc_a)
-    if a._dim != 3:
-        if pose_grad:
-            raise ValueError(f'domain_dim {a._dim}: pose_grad=True is out of scope: the coordinate gradient exists for three coordinates only')
-        return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
-                         _lib.lib().sininn_flownet_backward_points_dim, a._dim, *a._poses)
-    if pose_grad:
-        assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
-        return _backward_posegrad(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_backward_posegrad_points, a._poses, enc_grad,
-                                  g_enc_a, pose_workspace, g_poses)
-    return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
-                     _lib.lib().sininn_flownet_backward_points, *a._poses,
-                     enc_call=_lib.lib().sininn_flownet_backward_encgrad_points if enc_grad else None, enc_workspace=enc_workspace,
-                     g_enc_a=g_enc_a)
+    return _backward(a, net, dflows, saved, workspace, 'flownet',
+                     _call(a, None, enc_grad, enc_workspace, g_enc_a, pose_grad, pose_workspace, g_poses))
 
 
-def _backward_posegrad(a, net, dflows, saved, workspace, call, extra, enc_grad, g_enc_a, pose_workspace, g_poses):
-    """the posegrad call of a points descriptor: `_backward_buffers`, g_poses (N, 3), the optional frequency gradient and the extra workspace,
-    then `call(a, *extra, ..)`: ((grads[, gF]), g_poses)"""
-    lib = _lib.lib()
-    grads, keep = _backward_buffers(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, lib.sininn_flownet_workspace_bytes)  # noqa: F841
-    g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
-    g_enc = _out_tensor(g_enc_a, (3, 256), a._device) if enc_grad else None
-    if pose_workspace is None:
-        nbytes = lib.sininn_flownet_posegrad_workspace_bytes(C.byref(a), int(enc_grad))
-        pose_workspace = torch.empty(nbytes // 4, device=a._device, dtype=torch.float32)
-    check(call(C.byref(a), *extra, ptr(g_poses), ptr(g_enc), ptr(pose_workspace), pose_workspace.numel() * 4, _stream()))
-    return ((grads, g_enc) if enc_grad else grads), g_poses
-
-
-# ---- and under a per-point mask: the spatial calls at a pose list ----
 def flownet_forward_spatial_points(net, poses, scale, train, grid, res, centre_scale=None, k_active=None, saved=None, enc_a=None):
     """flownet_forward_points under the per-point mask of flownet_forward_spatial: flows (4, N)"""
-    a = _args(net, poses, None, None, scale, None, k_active, enc_a, spatial=True)
-    flows, saved = _forward(a, train, saved, _flownet_saved_shape(a), _lib.lib().sininn_flownet_forward_spatial_points,
-                            *_spatial(a, grid, res, centre_scale), *a._poses)
-    return flows.view(4, -1), saved
+    return flownet_forward_spatial(net, poses, None, None, scale, train, grid, res, centre_scale, k_active, saved, enc_a)
 
 
 def flownet_backward_spatial_points(net, poses, scale, dflows, saved, grid, res, centre_scale=None, k_active=None, workspace=None, enc_a=None,
                                     enc_grad=False, enc_workspace=None, g_enc_a=None, pose_grad=False, pose_workspace=None, g_poses=None):
-    """flownet_backward_points under the per-point mask of the forward call, dflows (4, N); `pose_grad=True` as there, from
-    sininn_flownet_backward_posegrad_spatial_points: the mask is a constant of the point, there is no d mask / d pose term"""
+    """flownet_backward_points under the per-point mask of the forward call, dflows (4, N); `pose_grad=True` as there: the mask is a
+    constant of the point, there is no d mask / d pose term"""
     a = _args(net, poses, None, None, scale, None, k_active, enc_a, spatial=True)
-    extra = (*_spatial(a, grid, res, centre_scale), *a._poses)
-    if pose_grad:
-        assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
-        return _backward_posegrad(a, net, dflows, saved, workspace, _lib.lib().sininn_flownet_backward_posegrad_spatial_points, extra, enc_grad,
-                                  g_enc_a, pose_workspace, g_poses)
-    return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_flownet_workspace_bytes,
-                     _lib.lib().sininn_flownet_backward_spatial_points, *extra,
-                     enc_call=_lib.lib().sininn_flownet_backward_encgrad_spatial_points if enc_grad else None, enc_workspace=enc_workspace,
-                     g_enc_a=g_enc_a)
+    return _backward(a, net, dflows, saved, workspace, 'flownet',
+                     _call(a, Mask(grid, k_active, res, centre_scale), enc_grad, enc_workspace, g_enc_a, pose_grad, pose_workspace, g_poses))
 
 
 def flownet_sample_mask_points(net, poses, grid, res, centre_scale=None):
     """the interpolated mask (N, 515) at a pose list (N, 3), bitwise what the spatial kernels multiply layer 1's input by"""
-    a = _args(net, poses, None, None, 1.0, spatial=True)
-    extra = _spatial(a, grid, res, centre_scale)
-    out = torch.empty(a.W, a.enc_dim, device=a._device, dtype=torch.float32)
-    check(_lib.lib().sininn_flownet_sample_mask_points(C.byref(a), *extra, *a._poses, ptr(out), _stream()))
-    return out
+    return flownet_sample_mask(net, poses, None, None, grid, res, centre_scale)
 
 
 def siren_forward_points(net, poses, scale, train, saved=None, omega=None):
     """siren_forward at a pose list (N, 3) on the device: flows (4, N)"""
-    a = _siren_args(net, poses, None, None, scale, omega)
-    flows, saved = _forward(a, train, saved, lambda: _lib.lib().sininn_siren_saved_bytes(a.W) // 4, _lib.lib().sininn_siren_forward_points,
-                            *a._poses)
-    return flows.view(4, -1), saved
+    return siren_forward(net, poses, None, None, scale, train, saved, omega)
 
 
 def siren_backward_points(net, poses, scale, dflows, saved, workspace=None, omega=None, pose_grad=False, g_poses=None):
     """siren_backward at the pose list of the forward call, dflows (4, N).  `pose_grad=True` returns (the gradients, g_poses (N, 3)),
-    from sininn_siren_backward_posegrad_points"""
+    from the POSEGRAD mode of sininn_siren_backward"""
     a = _siren_args(net, poses, None, None, scale, omega)
-    if pose_grad:
-        lib = _lib.lib()
-        grads, keep = _backward_buffers(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, lib.sininn_siren_workspace_bytes)  # noqa: F841
-        g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
-        check(lib.sininn_siren_backward_posegrad_points(C.byref(a), *a._poses, ptr(g_poses), _stream()))
-        return grads, g_poses
-    return _backward(a, net, dflows.reshape(1, 4, 1, -1), saved, workspace, _lib.lib().sininn_siren_workspace_bytes,
-                     _lib.lib().sininn_siren_backward_points, *a._poses)
+    return _backward(a, net, dflows, saved, workspace, 'siren', _call(a, pose_grad=pose_grad, g_poses=g_poses))
 
 
-def _mode(net, mask, enc_a):
-    """(forward, backward, the keyword arguments both take) of a call: a SirenModel, a per-point mask, or a global mask / none"""
+def _functions(net, mask, enc_a, points):
+    """(forward, backward, the keyword arguments both take) of a call: a SirenModel, a per-point mask, or a global mask / none; on a grid
+    or at a pose list"""
     if isinstance(net, SirenModel):
-        return siren_forward, siren_backward, {}
+        return (siren_forward_points, siren_backward_points, {}) if points else (siren_forward, siren_backward, {})
     if mask.spatial:
-        return flownet_forward_spatial, flownet_backward_spatial, dict(grid=mask.tensor, res=mask.res, centre_scale=mask.centre_scale,
-                                                                       k_active=mask.k_active, enc_a=enc_a)
-    return flownet_forward, flownet_backward, dict(mask=mask.tensor, k_active=mask.k_active, enc_a=enc_a)
+        kw = dict(grid=mask.tensor, res=mask.res, centre_scale=mask.centre_scale, k_active=mask.k_active, enc_a=enc_a)
+        return (flownet_forward_spatial_points, flownet_backward_spatial_points, kw) if points else (flownet_forward_spatial, flownet_backward_spatial, kw)
+    kw = dict(mask=mask.tensor, k_active=mask.k_active, enc_a=enc_a)
+    return (flownet_forward_points, flownet_backward_points, kw) if points else (flownet_forward, flownet_backward, kw)
+
+
+def _fields_forward(ctx, name, net, where, scale, train, mask, enc_a, enc_slot, pose_slot=None):
+    """the forward half of `_FlowFields` (where = (times, ys, xs)) and `_FlowAt` (where = (poses,)): choose the functions, call, and note
+    what the backward half needs; `enc_slot` / `pose_slot`: the positions of enc_a / the poses among the autograd inputs"""
+    if enc_a is not None:
+        enc_a = enc_a.detach().contiguous()
+    forward, ctx.backward_fn, ctx.kw = _functions(net, mask, enc_a, points=len(where) == 1)
+    flows, saved = forward(net, *where, scale, train, **ctx.kw)
+    ctx.name, ctx.net, ctx.where, ctx.scale, ctx.saved, ctx.mask = name, net, where, scale, saved, mask
+    if mask.spatial:
+        ctx.grid_version = mask.tensor._version          # the controller updates its grid in place
+    if enc_a is not None and ctx.needs_input_grad[enc_slot]:
+        ctx.kw['enc_grad'] = True
+    if pose_slot is not None and ctx.needs_input_grad[pose_slot]:
+        ctx.kw['pose_grad'] = True
+    return flows
+
+
+def _fields_backward(ctx, dflows):
+    """the backward half of both: (the parameters' gradients, g_enc or None, g_poses or None)"""
+    if ctx.saved is None:
+        raise RuntimeError(f'{ctx.name}: backward through an inference-mode forward')
+    if ctx.mask.spatial and ctx.mask.tensor._version != ctx.grid_version:
+        raise RuntimeError(f'{ctx.name}: the mask grid changed between the forward and the backward pass (run backward before '
+                           'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
+    grads, g_enc, g_poses = ctx.backward_fn(ctx.net, *ctx.where, ctx.scale, dflows, ctx.saved, **ctx.kw), None, None
+    if ctx.kw.get('pose_grad'):
+        grads, g_poses = grads
+    if ctx.kw.get('enc_grad'):
+        grads, g_enc = grads
+    ctx.saved = None
+    return tuple(grads), g_enc, g_poses
 
 
 class _FlowFields(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, times, ys, xs, scale, train, mask, enc_a, *params):
-        if enc_a is not None:
-            enc_a = enc_a.detach().contiguous()
-        forward, ctx.backward_fn, ctx.kw = _mode(net, mask, enc_a)
-        flows, saved = forward(net, times, ys, xs, scale, train, **ctx.kw)
-        ctx.net, ctx.axes, ctx.scale, ctx.saved, ctx.mask = net, (times, ys, xs), scale, saved, mask
-        if mask.spatial:
-            ctx.grid_version = mask.tensor._version      # the controller updates its grid in place
-        if enc_a is not None and ctx.needs_input_grad[7]:
-            ctx.kw['enc_grad'] = True
-        return flows
+        return _fields_forward(ctx, 'flow_fields', net, (times, ys, xs), scale, train, mask, enc_a, 7)
 
     @staticmethod
     def backward(ctx, dflows):
-        if ctx.saved is None:
-            raise RuntimeError('flow_fields: backward through an inference-mode forward')
-        if ctx.mask.spatial and ctx.mask.tensor._version != ctx.grid_version:
-            raise RuntimeError('flow_fields: the mask grid changed between the forward and the backward pass (run backward before '
-                               'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
-        grads, g_enc = ctx.backward_fn(ctx.net, *ctx.axes, ctx.scale, dflows, ctx.saved, **ctx.kw), None
-        if ctx.kw.get('enc_grad'):
-            grads, g_enc = grads
-        ctx.saved = None
-        return (None,) * 7 + (g_enc,) + tuple(grads)
+        grads, g_enc, _ = _fields_backward(ctx, dflows)
+        return (None,) * 7 + (g_enc,) + grads
 
 
 class _SirenFields:
@@ -963,41 +960,13 @@ class _FlowAt(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, poses, scale, train, mask, enc_a, pose_grad, *params):
-        if enc_a is not None:
-            enc_a = enc_a.detach().contiguous()
-        if isinstance(net, SirenModel):
-            forward, ctx.backward_fn, ctx.kw = siren_forward_points, siren_backward_points, {}
-        elif mask.spatial:
-            forward, ctx.backward_fn = flownet_forward_spatial_points, flownet_backward_spatial_points
-            ctx.kw = dict(grid=mask.tensor, res=mask.res, centre_scale=mask.centre_scale, k_active=mask.k_active, enc_a=enc_a)
-        else:
-            forward, ctx.backward_fn = flownet_forward_points, flownet_backward_points
-            ctx.kw = dict(mask=mask.tensor, k_active=mask.k_active, enc_a=enc_a)
-        flows, saved = forward(net, poses, scale, train, **ctx.kw)
-        ctx.net, ctx.poses, ctx.scale, ctx.saved, ctx.mask = net, poses, scale, saved, mask
-        if mask.spatial:
-            ctx.grid_version = mask.tensor._version      # the controller updates its grid in place
-        if enc_a is not None and ctx.needs_input_grad[5]:
-            ctx.kw['enc_grad'] = True
-        if pose_grad and ctx.needs_input_grad[1]:
-            ctx.kw['pose_grad'] = True
-        return flows
+        return _fields_forward(ctx, 'flow_at', net, (poses,), scale, train, mask, enc_a, 5, 1 if pose_grad else None)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dflows):
-        if ctx.saved is None:
-            raise RuntimeError('flow_at: backward through an inference-mode forward')
-        if ctx.mask.spatial and ctx.mask.tensor._version != ctx.grid_version:
-            raise RuntimeError('flow_at: the mask grid changed between the forward and the backward pass (run backward before '
-                               'the controller\'s next stash_iteration / update_progress: its grid is updated in place)')
-        grads, g_enc, g_poses = ctx.backward_fn(ctx.net, ctx.poses, ctx.scale, dflows, ctx.saved, **ctx.kw), None, None
-        if ctx.kw.get('pose_grad'):
-            grads, g_poses = grads
-        if ctx.kw.get('enc_grad'):
-            grads, g_enc = grads
-        ctx.saved = None
-        return (None, g_poses, None, None, None, g_enc, None) + tuple(grads)
+        grads, g_enc, g_poses = _fields_backward(ctx, dflows)
+        return (None, g_poses, None, None, None, g_enc, None) + grads
 
 
 def grid_axes(net, times, h, w):
@@ -1105,7 +1074,7 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     Differentiable with respect to the parameters (and `encode.frequencies` of RFF / PRFF); under torch.no_grad() (or with no trainable
     parameter) the inference mode runs and nothing is saved.  `get_mask=True` returns (out, the mask in use on the device).
     `pose_grad=True`: poses that require a gradient get one (d flow / d pose against the upstream gradient, `scale` included, computed
-    by the fused kernels: sininn_flownet_backward_posegrad_points / sininn_siren_backward_posegrad_points), which chains queries:
+    by the fused kernels: the POSEGRAD mode of sininn_flownet_backward / sininn_siren_backward), which chains queries:
     flow_at(net, p + pad(flow_at(net, p, pose_grad=True)[..., :2]), pose_grad=True).  Once differentiable.  Without the keyword there is no
     gradient with respect to the coordinates: poses that require one are refused."""
     dim = _call_dim(net, override_mask, pose_grad)

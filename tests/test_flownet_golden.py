@@ -102,7 +102,7 @@ def test_abi_and_refusals():
     a.encoding, a.struct_bytes = 1, 8
     assert lib.sininn_flownet_supported(C.byref(a)) == 0
     a.struct_bytes = C.sizeof(_lib.FlowNetArgs)
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0          # no grid, no pointers: refused before any launch
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0          # no grid, no pointers: refused before any launch
     assert lib.sininn_last_error()
     n = 3 * 109 * 253
     npad = (n + 63) // 64 * 64

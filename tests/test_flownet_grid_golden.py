@@ -158,13 +158,13 @@ def test_abi_and_refusals():
     a.enc_dim, a.progressive = 512, 0
     assert lib.sininn_flownet_encgrad_workspace_bytes(C.byref(a)) == 0
     g = (C.c_float * 768)()
-    rc = lib.sininn_flownet_backward_encgrad(C.byref(a), g, None, 0, None)    # refused on the encoding, before any launch
+    rc = lib.sininn_flownet_backward(C.byref(a), C.byref(_lib.FlowNetCall(mode=_lib.ENCGRAD, g_enc_a=C.cast(g, C.c_void_p))), None)    # refused on the encoding, before any launch
     assert rc != 0 and b'SININN_FLOWNET_FOURIER' in lib.sininn_last_error()
     a.T, a.H, a.W = 2, 8, 8
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0                  # no pointers: refused before any launch
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0                  # no pointers: refused before any launch
     assert b'null' in lib.sininn_last_error()
     a.hidden = 128
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0
     assert b'RBFG' in lib.sininn_last_error()
     assert flownet.grid_model_dict == {'RBFG': flownet.RbfgModel, 'PRBFG': flownet.PRBFGModel}
     for name in NETS:

@@ -136,8 +136,16 @@ def test_abi_and_refusals():
     lib = _lib.lib()
     assert lib.sininn_version() == 4
     header = open(os.path.join(ROOT, 'include', 'sininn.h')).read()
-    for sym in ('sininn_flownet_encgrad_workspace_bytes', 'sininn_flownet_backward_encgrad'):
+    for sym in ('sininn_flownet_encgrad_workspace_bytes', 'sininn_flownet_backward'):
         assert hasattr(lib, sym) and sym in _lib.EXPORTED and re.search(r'\b' + sym + r'\s*\(', header), sym
+    for sym in ('sininn_flownet_backward_encgrad', 'sininn_flownet_backward_encgrad_spatial', 'sininn_flownet_backward_encgrad_points'):
+        assert sym not in _lib.EXPORTED and not hasattr(lib, sym) and not re.search(r'\b' + sym + r'\s*\(', header), sym
+
+    def backward_encgrad(a, g_enc_a, enc_workspace, enc_workspace_bytes, stream):
+        """the ENCGRAD mode of sininn_flownet_backward, with the arguments the entry point of that name took"""
+        call = _lib.FlowNetCall(mode=_lib.ENCGRAD, g_enc_a=g_enc_a and C.cast(g_enc_a, C.c_void_p),
+                                enc_workspace=enc_workspace and C.cast(enc_workspace, C.c_void_p), enc_workspace_bytes=enc_workspace_bytes)
+        return lib.sininn_flownet_backward(a, C.byref(call), stream)
     assert lib.sininn_sizeof(7) == C.sizeof(_lib.FlowNetArgs) == 280      # as before this entry point was added
     assert [f[0] for f in _lib.FlowNetArgs._fields_][-3:] == ['progressive', 'k_active', 'mask']
     a = _lib.FlowNetArgs()
@@ -150,20 +158,20 @@ def test_abi_and_refusals():
     # refused before any launch: nothing below is a device pointer and no GPU is needed
     a.encoding = 0
     assert lib.sininn_flownet_encgrad_workspace_bytes(C.byref(a)) == 0
-    assert lib.sininn_flownet_backward_encgrad(C.byref(a), g, ws, need, None) != 0
+    assert backward_encgrad(C.byref(a), g, ws, need, None) != 0
     assert b'encoding' in lib.sininn_last_error()
     a.encoding = 1
-    assert lib.sininn_flownet_backward_encgrad(C.byref(a), None, ws, need, None) != 0
+    assert backward_encgrad(C.byref(a), None, ws, need, None) != 0
     assert b'g_enc_a' in lib.sininn_last_error()
-    assert lib.sininn_flownet_backward_encgrad(C.byref(a), g, ws, need - 4, None) != 0
+    assert backward_encgrad(C.byref(a), g, ws, need - 4, None) != 0
     assert b'enc_workspace' in lib.sininn_last_error()
-    assert lib.sininn_flownet_backward_encgrad(C.byref(a), g, None, need, None) != 0
+    assert backward_encgrad(C.byref(a), g, None, need, None) != 0
     assert b'enc_workspace' in lib.sininn_last_error()
     a.struct_bytes = 8
-    assert lib.sininn_flownet_backward_encgrad(C.byref(a), g, ws, need, None) != 0
+    assert backward_encgrad(C.byref(a), g, ws, need, None) != 0
     assert b'struct_bytes' in lib.sininn_last_error()
     a.struct_bytes = C.sizeof(_lib.FlowNetArgs)
-    assert lib.sininn_flownet_backward_encgrad(C.byref(a), g, ws, need, None) != 0     # all of its own checks pass: the backward's null pointers
+    assert backward_encgrad(C.byref(a), g, ws, need, None) != 0     # all of its own checks pass: the backward's null pointers
     assert b'flownet_backward' in lib.sininn_last_error()
     assert sorted(flownet.model_dict) == ['FFN', 'RBF', 'UFF']
     assert sorted(flownet.progressive_model_dict) == ['PFF', 'PRBF', 'PUFF']

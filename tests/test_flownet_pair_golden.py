@@ -187,9 +187,15 @@ def test_library_support_table_per_network_and_dimension():
     from sin_inn_amd import _lib
     lib = _lib.lib()
     header = open(os.path.join(ROOT, 'include', 'sininn.h')).read()
-    for sym in ('sininn_flownet_supported_dim', 'sininn_flownet_forward_dim', 'sininn_flownet_backward_dim',
-                'sininn_flownet_forward_points_dim', 'sininn_flownet_backward_points_dim'):
-        assert hasattr(lib, sym) and sym in _lib.EXPORTED and sym in header
+    for sym in ('sininn_flownet_supported_dim', 'sininn_flownet_forward', 'sininn_flownet_backward'):
+        assert hasattr(lib, sym) and sym in _lib.EXPORTED and sym + '(' in header
+    for sym in ('sininn_flownet_forward_dim', 'sininn_flownet_backward_dim', 'sininn_flownet_forward_points_dim',
+                'sininn_flownet_backward_points_dim'):             # the dimension is a field of the call descriptor now
+        assert not hasattr(lib, sym) and sym not in _lib.EXPORTED and sym + '(' not in header
+    assert dict(_lib.FlowNetCall._fields_)['domain_dim'] is C.c_int
+
+    def at(dim, **points):
+        return C.byref(_lib.FlowNetCall(domain_dim=dim, **points))
     assert lib.sininn_version() == 4 and lib.sininn_sizeof(7) == C.sizeof(_lib.FlowNetArgs)      # additive: the descriptor is the one it was
     for name in ('RBF', 'FFN', 'UFF', 'RBFG'):
         for prog in (0, 1):
@@ -214,10 +220,10 @@ def test_library_support_table_per_network_and_dimension():
     # refused before any launch: T != 1 on the two-coordinate grid, a null mask
     a = descriptor(0, 514, 1)
     a.k_active, a.T, a.H, a.W = 514, 2, 8, 8
-    assert lib.sininn_flownet_forward_dim(C.byref(a), 2, None) != 0 and b'mask' in lib.sininn_last_error()
+    assert lib.sininn_flownet_forward(C.byref(a), at(2), None) != 0 and b'mask' in lib.sininn_last_error()
     a = descriptor(0, 512, 0)
     a.T, a.H, a.W = 2, 8, 8
-    assert lib.sininn_flownet_forward_dim(C.byref(a), 2, None) != 0 and b'T = 1' in lib.sininn_last_error()
-    assert lib.sininn_flownet_backward_dim(C.byref(a), 2, None) != 0 and b'T = 1' in lib.sininn_last_error()
-    assert lib.sininn_flownet_forward_points_dim(C.byref(a), 2, None, 4, None) != 0 and b'poses' in lib.sininn_last_error()
-    assert lib.sininn_flownet_forward_dim(C.byref(a), 5, None) != 0 and b'domain_dim 5' in lib.sininn_last_error()
+    assert lib.sininn_flownet_forward(C.byref(a), at(2), None) != 0 and b'T = 1' in lib.sininn_last_error()
+    assert lib.sininn_flownet_backward(C.byref(a), at(2), None) != 0 and b'T = 1' in lib.sininn_last_error()
+    assert lib.sininn_flownet_forward(C.byref(a), at(2, mode=_lib.AT_POINTS, poses=None, n=4), None) != 0 and b'poses' in lib.sininn_last_error()
+    assert lib.sininn_flownet_forward(C.byref(a), at(5), None) != 0 and b'domain_dim 5' in lib.sininn_last_error()

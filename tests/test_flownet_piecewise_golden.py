@@ -168,7 +168,7 @@ def test_abi_and_refusals():
             assert b'PieceWise progressive only: 515' in lib.sininn_last_error(), lib.sininn_last_error()
     a.enc_dim, a.progressive = 512, 0
     a.T, a.H, a.W = 2, 8, 8
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0                  # the plain form: refused on the table, before any pointer
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0                  # the plain form: refused on the table, before any pointer
     assert b'unsupported network (encoding 5, 512' in lib.sininn_last_error() and b'PieceWise' in lib.sininn_last_error()
     a.encoding = 2                                                            # still no encoding of this library
     assert lib.sininn_flownet_supported(C.byref(a)) == 0
@@ -180,9 +180,9 @@ def test_abi_and_refusals():
     a.encoding = 5
     assert lib.sininn_flownet_posegrad_workspace_bytes(C.byref(a), 0) == fourier > 0
     g = (C.c_float * 768)()
-    rc = lib.sininn_flownet_backward_encgrad(C.byref(a), g, None, 0, None)    # refused on the encoding, before any launch
+    rc = lib.sininn_flownet_backward(C.byref(a), C.byref(_lib.FlowNetCall(mode=_lib.ENCGRAD, g_enc_a=C.cast(g, C.c_void_p))), None)    # refused on the encoding, before any launch
     assert rc != 0 and b'SININN_FLOWNET_FOURIER' in lib.sininn_last_error()
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0                  # no pointers: refused before any launch
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0                  # no pointers: refused before any launch
     assert b'mask' in lib.sininn_last_error() or b'null' in lib.sininn_last_error()
     with pytest.raises(NotImplementedError):
         flownet.flow_fields(build(), torch.tensor([0.0, 0.5]), 8, 8, 1.0)

@@ -1,15 +1,24 @@
-"""No GPU needed: the points mode of the flow networks (net(poses), sin_inn_amd.flownet.flow_at, sininn_*_points) as far as the host
-decides it: the five symbols and their ctypes declarations, their refusals before any launch (null poses, n = 0, n = 2^22 + 1, a wrong
+"""No GPU needed: the points mode of the flow networks (net(poses), sin_inn_amd.flownet.flow_at, the AT_POINTS mode of the call descriptor,
+once the entry points sininn_*_points, whose names the refusals still carry) as far as the host decides it: the entry points and their ctypes
+declarations, their refusals before any launch (null poses, n = 0, n = 2^22 + 1, a wrong
 struct_bytes; each leaves a sentence that names the cause), an ABI that did not move (descriptor sizes, version 4), and the errors of
 flow_at / net(poses) / controller(poses) on tensors no kernel can take.  The numbers are tests/test_gpu_flownet_points.py's.
 """
 import ctypes as C
+import os
 
 import pytest
 import torch
 
 POINT_CALLS = ('sininn_flownet_forward_points', 'sininn_flownet_backward_points', 'sininn_flownet_backward_encgrad_points',
                'sininn_siren_forward_points', 'sininn_siren_backward_points')
+AT_POINTS, ENCGRAD = 1, 4
+# the five calls, by the names they had as entry points of their own: name -> (entry point, mode of the call descriptor)
+ENTRY = {'sininn_flownet_forward_points': ('sininn_flownet_forward', AT_POINTS),
+         'sininn_flownet_backward_points': ('sininn_flownet_backward', AT_POINTS),
+         'sininn_flownet_backward_encgrad_points': ('sininn_flownet_backward', AT_POINTS | ENCGRAD),
+         'sininn_siren_forward_points': ('sininn_siren_forward', AT_POINTS),
+         'sininn_siren_backward_points': ('sininn_siren_backward', AT_POINTS)}
 FAKE = 0x1000                                  # a non-null, 16-byte aligned address that is never read: every case is refused on the host
 
 
@@ -38,23 +47,30 @@ def siren_args(_lib):
 def calls(_lib):
     """name -> (descriptor factory, lambda (args, poses, n) -> return code)"""
     lib = _lib.lib()
-    enc = lambda a, p, n: lib.sininn_flownet_backward_encgrad_points(C.byref(a), p, n, FAKE, FAKE, 1 << 40, None)  # noqa: E731
-    plain = lambda name: (lambda a, p, n: getattr(lib, name)(C.byref(a), p, n, None))  # noqa: E731
-    return {'sininn_flownet_forward_points': (lambda: flownet_args(_lib), plain('sininn_flownet_forward_points')),
-            'sininn_flownet_backward_points': (lambda: flownet_args(_lib), plain('sininn_flownet_backward_points')),
-            'sininn_flownet_backward_encgrad_points': (lambda: flownet_args(_lib, encoding=1), enc),
-            'sininn_siren_forward_points': (lambda: siren_args(_lib), plain('sininn_siren_forward_points')),
-            'sininn_siren_backward_points': (lambda: siren_args(_lib), plain('sininn_siren_backward_points'))}
+
+    def call(name):
+        entry, mode = ENTRY[name]
+        return lambda a, p, n: getattr(lib, entry)(C.byref(a), C.byref(_lib.FlowNetCall(
+            mode=mode, poses=p, n=n, g_enc_a=FAKE, enc_workspace=FAKE, enc_workspace_bytes=1 << 40)), None)
+    return {'sininn_flownet_forward_points': (lambda: flownet_args(_lib), call('sininn_flownet_forward_points')),
+            'sininn_flownet_backward_points': (lambda: flownet_args(_lib), call('sininn_flownet_backward_points')),
+            'sininn_flownet_backward_encgrad_points': (lambda: flownet_args(_lib, encoding=1), call('sininn_flownet_backward_encgrad_points')),
+            'sininn_siren_forward_points': (lambda: siren_args(_lib), call('sininn_siren_forward_points')),
+            'sininn_siren_backward_points': (lambda: siren_args(_lib), call('sininn_siren_backward_points'))}
 
 
 def test_symbols_are_exported_and_declared():
     from sin_inn_amd import _lib
     lib = _lib.lib()
-    for name in POINT_CALLS:
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'include', 'sininn.h')).read()
+    for name in sorted({entry for entry, _ in ENTRY.values()}):
         assert name in _lib.EXPORTED, name
         fn = getattr(lib, name)
         assert fn.restype is C.c_int and fn.argtypes[0] in (C.POINTER(_lib.FlowNetArgs), C.POINTER(_lib.SirenArgs))
-        assert fn.argtypes[2] is C.c_int64 and fn.argtypes[-1] is C.c_void_p
+        assert fn.argtypes[1] == C.POINTER(_lib.FlowNetCall) and fn.argtypes[-1] is C.c_void_p
+    assert dict(_lib.FlowNetCall._fields_)['n'] is C.c_int64
+    for name in POINT_CALLS:                       # the entry points these calls had are gone
+        assert name not in _lib.EXPORTED and not hasattr(lib, name) and name + '(' not in header, name
 
 
 def test_abi_did_not_move():
@@ -105,11 +121,11 @@ def test_grid_calls_still_refuse_their_own_way():
     from sin_inn_amd import _lib
     lib = _lib.lib()
     a = flownet_args(_lib)
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0 and b'grid 0 x 0 x 0' in lib.sininn_last_error()
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0 and b'grid 0 x 0 x 0' in lib.sininn_last_error()
     a.T = a.H = a.W = 4
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0 and b'null axis' in lib.sininn_last_error()
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0 and b'null axis' in lib.sininn_last_error()
     s = siren_args(_lib)
-    assert lib.sininn_siren_backward(C.byref(s), None) != 0 and b'grid 0 x 0 x 0' in lib.sininn_last_error()
+    assert lib.sininn_siren_backward(C.byref(s), None, None) != 0 and b'grid 0 x 0 x 0' in lib.sininn_last_error()
 
 
 def nets():

@@ -1,29 +1,37 @@
-"""No GPU needed: the coordinate gradient of the flow networks (flow_at(.., pose_grad=True), sininn_flownet_backward_posegrad_points,
-sininn_siren_backward_posegrad_points) as far as the host decides it: the three symbols and their declarations, the workspace size, the
+"""No GPU needed: the coordinate gradient of the flow networks (flow_at(.., pose_grad=True), the POSEGRAD mode of sininn_flownet_backward and
+sininn_siren_backward, once entry points of their own, whose names the refusals still carry) as far as the host decides it: the symbols and
+their declarations, the workspace size, the
 refusals before any launch, each with a sentence under the entry point's name, and an ABI that did not move.  The numbers are
 tests/test_gpu_flownet_posegrad.py's.
 """
 import ctypes as C
 import inspect
+import os
 
 import pytest
 import torch
 
 from test_flownet_points_host import FAKE, flownet_args, nets, siren_args
 
-NEW = ('sininn_flownet_posegrad_workspace_bytes', 'sininn_flownet_backward_posegrad_points', 'sininn_siren_backward_posegrad_points')
+GONE = ('sininn_flownet_backward_posegrad_points', 'sininn_siren_backward_posegrad_points')   # the entry points the mode had
+AT_POINTS, ENCGRAD, POSEGRAD = 1, 4, 8
 ENCODINGS = {'RBF': (0, 512, 515), 'Fourier': (1, 512, 515), 'RBFG': (3, 512, 515), 'PE': (4, 24, 27)}
 
 
 def test_symbols_are_exported_and_declared():
     from sin_inn_amd import _lib
     lib = _lib.lib()
-    for name in NEW:
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'include', 'sininn.h')).read()
+    for name in ('sininn_flownet_posegrad_workspace_bytes', 'sininn_flownet_backward', 'sininn_siren_backward'):
         assert name in _lib.EXPORTED, name
     assert lib.sininn_flownet_posegrad_workspace_bytes.restype is C.c_size_t
-    for name, args in ((NEW[1], _lib.FlowNetArgs), (NEW[2], _lib.SirenArgs)):
+    for name, args in (('sininn_flownet_backward', _lib.FlowNetArgs), ('sininn_siren_backward', _lib.SirenArgs)):
         fn = getattr(lib, name)
-        assert fn.restype is C.c_int and fn.argtypes[0] is C.POINTER(args) and fn.argtypes[2] is C.c_int64 and fn.argtypes[-1] is C.c_void_p
+        assert fn.restype is C.c_int and fn.argtypes[0] is C.POINTER(args) and fn.argtypes[1] is C.POINTER(_lib.FlowNetCall)
+        assert fn.argtypes[-1] is C.c_void_p
+    assert dict(_lib.FlowNetCall._fields_)['n'] is C.c_int64
+    for name in GONE:
+        assert name not in _lib.EXPORTED and not hasattr(lib, name) and name + '(' not in header, name
 
 
 def test_abi_did_not_move():
@@ -62,7 +70,9 @@ def test_flownet_refusals_before_any_launch():
     name = b'flownet_backward_posegrad_points'
 
     def refused(a, poses, n, g_poses, g_enc, ws, nbytes, *words, who=name):
-        assert lib.sininn_flownet_backward_posegrad_points(C.byref(a), poses, n, g_poses, g_enc, ws, nbytes, None) != 0
+        c = _lib.FlowNetCall(mode=AT_POINTS | POSEGRAD | (ENCGRAD if g_enc else 0), poses=poses, n=n, g_poses=g_poses, g_enc_a=g_enc,
+                             extra_workspace=ws, extra_workspace_bytes=nbytes)          # a non-null g_enc_a was how the old call said ENCGRAD
+        assert lib.sininn_flownet_backward(C.byref(a), C.byref(c), None) != 0
         msg = lib.sininn_last_error()
         assert msg and who in msg, msg
         for w in words:
@@ -103,7 +113,8 @@ def test_siren_refusals_before_any_launch():
     lib = _lib.lib()
 
     def refused(a, poses, n, g_poses, *words):
-        assert lib.sininn_siren_backward_posegrad_points(C.byref(a), poses, n, g_poses, None) != 0
+        c = _lib.FlowNetCall(mode=AT_POINTS | POSEGRAD, poses=poses, n=n, g_poses=g_poses)
+        assert lib.sininn_siren_backward(C.byref(a), C.byref(c), None) != 0
         msg = lib.sininn_last_error()
         assert msg and b'siren_backward_posegrad_points' in msg, msg
         for w in words:

@@ -185,9 +185,9 @@ def test_abi_and_refusals():
     a = _lib.FlowNetArgs()
     a.encoding, a.enc_dim, a.hidden, a.layers, a.out_dim, a.progressive, a.k_active = 0, 515, 256, 3, 4, 1, 515
     a.T, a.H, a.W = 2, 8, 8
-    assert lib.sininn_flownet_forward(C.byref(a), None) != 0              # null mask: refused before any launch
+    assert lib.sininn_flownet_forward(C.byref(a), None, None) != 0              # null mask: refused before any launch
     assert b'mask' in lib.sininn_last_error()
-    assert lib.sininn_flownet_backward(C.byref(a), None) != 0
+    assert lib.sininn_flownet_backward(C.byref(a), None, None) != 0
     assert b'mask' in lib.sininn_last_error()
     n = 3 * 109 * 253
     npad = (n + 63) // 64 * 64

@@ -104,7 +104,9 @@ def test_abi_and_refusals():
         assert hasattr(lib, sym) and sym in _lib.EXPORTED and sym + '(' in header, sym
     assert lib.sininn_sizeof(9) == C.sizeof(_lib.SirenArgs) and lib.sininn_sizeof(9) > 0
     assert lib.sininn_sizeof(7) == 280 == C.sizeof(_lib.FlowNetArgs)
-    assert lib.sininn_sizeof(10) == 0 and lib.sininn_version() == 4
+    assert lib.sininn_sizeof(10) == C.sizeof(_lib.FlowNetCall) and lib.sininn_sizeof(11) == 0 and lib.sininn_version() == 4
+    for sym in ('sininn_siren_forward_points', 'sininn_siren_backward_points', 'sininn_siren_backward_posegrad_points'):
+        assert sym not in _lib.EXPORTED and not hasattr(lib, sym) and sym + '(' not in header, sym
 
     def fresh():
         a = _lib.SirenArgs()
@@ -116,7 +118,7 @@ def test_abi_and_refusals():
     a.struct_bytes -= 8
     assert lib.sininn_siren_supported(C.byref(a)) == 0
     for call in (lib.sininn_siren_forward, lib.sininn_siren_backward):
-        assert call(C.byref(a), None) != 0 and b'struct_bytes' in lib.sininn_last_error()
+        assert call(C.byref(a), None, None) != 0 and b'struct_bytes' in lib.sininn_last_error()
     # ---- sizes and omega: the message names what the library is built for ----
     for field, value in (('hidden', 128), ('layers', 2), ('in_dim', 2), ('out_dim', 2), ('omega', 0.0), ('omega', -30.0),
                          ('omega', float('inf')), ('omega', float('nan'))):
@@ -125,7 +127,7 @@ def test_abi_and_refusals():
         a.T, a.H, a.W = 2, 8, 8
         assert lib.sininn_siren_supported(C.byref(a)) == 0, (field, value)
         for call in (lib.sininn_siren_forward, lib.sininn_siren_backward):
-            assert call(C.byref(a), None) != 0, (field, value)
+            assert call(C.byref(a), None, None) != 0, (field, value)
             msg = lib.sininn_last_error()
             assert b'built for 3 -> 256 x (1 + 3) -> 4' in msg and b'omega > 0' in msg, msg
     # ---- sizes of the buffers ----
@@ -150,29 +152,29 @@ def test_abi_and_refusals():
         return a
     a = filled()
     a.T = 0
-    assert lib.sininn_siren_forward(C.byref(a), None) != 0 and b'grid' in lib.sininn_last_error()
+    assert lib.sininn_siren_forward(C.byref(a), None, None) != 0 and b'grid' in lib.sininn_last_error()
     a = filled()
     a.T, a.H, a.W = 1 << 10, 1 << 10, 8
-    assert lib.sininn_siren_forward(C.byref(a), None) != 0 and b'grid' in lib.sininn_last_error()
+    assert lib.sininn_siren_forward(C.byref(a), None, None) != 0 and b'grid' in lib.sininn_last_error()
     a = filled()
     a.flows = None
-    assert lib.sininn_siren_forward(C.byref(a), None) != 0 and b'null flows' in lib.sininn_last_error()
+    assert lib.sininn_siren_forward(C.byref(a), None, None) != 0 and b'null flows' in lib.sininn_last_error()
     a = filled()
     a.w[2] = None
-    assert lib.sininn_siren_forward(C.byref(a), None) != 0 and b'null weight' in lib.sininn_last_error()
+    assert lib.sininn_siren_forward(C.byref(a), None, None) != 0 and b'null weight' in lib.sininn_last_error()
     a = filled()
     a.saved_bytes -= 4
-    assert lib.sininn_siren_forward(C.byref(a), None) != 0 and b'saved holds' in lib.sininn_last_error()
-    assert lib.sininn_siren_backward(C.byref(a), None) != 0 and b'saved holds' in lib.sininn_last_error()
+    assert lib.sininn_siren_forward(C.byref(a), None, None) != 0 and b'saved holds' in lib.sininn_last_error()
+    assert lib.sininn_siren_backward(C.byref(a), None, None) != 0 and b'saved holds' in lib.sininn_last_error()
     a = filled()
     a.workspace_bytes -= 4
-    assert lib.sininn_siren_backward(C.byref(a), None) != 0 and b'workspace holds' in lib.sininn_last_error()
+    assert lib.sininn_siren_backward(C.byref(a), None, None) != 0 and b'workspace holds' in lib.sininn_last_error()
     a = filled()
     a.dflows = None
-    assert lib.sininn_siren_backward(C.byref(a), None) != 0 and b'null dflows' in lib.sininn_last_error()
+    assert lib.sininn_siren_backward(C.byref(a), None, None) != 0 and b'null dflows' in lib.sininn_last_error()
     a = filled()
     a.gb[4] = None
-    assert lib.sininn_siren_backward(C.byref(a), None) != 0 and b'null gradient' in lib.sininn_last_error()
+    assert lib.sininn_siren_backward(C.byref(a), None, None) != 0 and b'null gradient' in lib.sininn_last_error()
 
 
 def test_registry_and_command_line_stay_as_they_are(capsys):

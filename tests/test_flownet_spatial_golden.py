@@ -160,7 +160,7 @@ def test_stash_needs_a_per_point_loss_and_three_dimensions(gold):
 def test_abi_unchanged_and_spatial_entry_points_refuse_before_any_launch():
     from sin_inn_amd import _lib
     h = _lib.lib()
-    assert h.sininn_sizeof(7) == 280 and h.sininn_sizeof(10) == 0 and h.sininn_version() == 4
+    assert h.sininn_sizeof(7) == 280 and h.sininn_sizeof(10) == C.sizeof(_lib.FlowNetCall) and h.sininn_sizeof(11) == 0 and h.sininn_version() == 4
     cs = (C.c_float * 6)(0, 0, 0, 1, 1, 1)
     csp, fake = C.cast(cs, C.c_void_p), C.c_void_p(64)   # never dereferenced: every call below is refused first
 
@@ -169,15 +169,23 @@ def test_abi_unchanged_and_spatial_entry_points_refuse_before_any_launch():
         a.encoding, a.enc_dim, a.hidden, a.layers, a.out_dim, a.progressive = encoding, enc_dim, 256, 3, 4, progressive
         return a
 
-    calls = {
-        'sininn_flownet_forward_spatial': lambda a, g, r, c: h.sininn_flownet_forward_spatial(C.byref(a), g, r, c, None),
-        'sininn_flownet_backward_spatial': lambda a, g, r, c: h.sininn_flownet_backward_spatial(C.byref(a), g, r, c, None),
-        'sininn_flownet_backward_encgrad_spatial':
-            lambda a, g, r, c: h.sininn_flownet_backward_encgrad_spatial(C.byref(a), g, r, c, fake, fake, 1 << 30, None),
-        'sininn_flownet_sample_mask': lambda a, g, r, c: h.sininn_flownet_sample_mask(C.byref(a), g, r, c, fake, None),
+    def spatial(entry, mode, *tail):
+        """the SPATIAL mode of an entry point: lambda (args, grid, res, centre_scale) -> return code"""
+        return lambda a, g, r, c: getattr(h, entry)(C.byref(a), C.byref(_lib.FlowNetCall(
+            mode=_lib.SPATIAL | mode, grid=g, res=r, centre_scale=c, g_enc_a=fake, enc_workspace=fake, enc_workspace_bytes=1 << 30)), *tail, None)
+
+    calls = {        # by the names the modes had as entry points of their own
+        'sininn_flownet_forward_spatial': spatial('sininn_flownet_forward', 0),
+        'sininn_flownet_backward_spatial': spatial('sininn_flownet_backward', 0),
+        'sininn_flownet_backward_encgrad_spatial': spatial('sininn_flownet_backward', _lib.ENCGRAD),
+        'sininn_flownet_sample_mask': spatial('sininn_flownet_sample_mask', 0, fake),
     }
-    for name, call in calls.items():
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'include', 'sininn.h')).read()
+    for name in ('sininn_flownet_forward', 'sininn_flownet_backward', 'sininn_flownet_sample_mask'):
         assert name in _lib.EXPORTED
+    for name in ('sininn_flownet_forward_spatial', 'sininn_flownet_backward_spatial', 'sininn_flownet_backward_encgrad_spatial'):
+        assert name not in _lib.EXPORTED and not hasattr(h, name) and name + '(' not in header, name
+    for name, call in calls.items():
         enc = 1 if 'encgrad' in name else 0
         for why, needle, a, g, r in (('null grid', 'null grid', args(enc), None, 5),
                                      ('res < 3', 'at least 3', args(enc), fake, 2),

@@ -1,15 +1,24 @@
-"""No GPU needed: per-point masks at pose lists (sininn_flownet_*_spatial_points, sininn_flownet_sample_mask_points,
-StashedSpatialController.__call__) as far as the host decides them: the five symbols refuse null poses, n = 0, n = 2^22 + 1, a null grid, a
+"""No GPU needed: per-point masks at pose lists (the AT_POINTS | SPATIAL modes of sininn_flownet_forward / _backward / _sample_mask, once
+entry points of their own, whose names the refusals still carry; StashedSpatialController.__call__) as far as the host decides them: the
+five calls refuse null poses, n = 0, n = 2^22 + 1, a null grid, a
 descriptor that is not progressive and PPE before any launch, each under its own name; `note_poses` attributes a per-point loss to the cells
 `interpolate` finds; `mask_by` / `expand_by` are refused by name; CPU poses are still refused as GPU-only.  The numbers are
 tests/test_gpu_flownet_spatial_points.py's.
 """
 import ctypes as C
+import os
 
 import pytest
 import torch
 
 FAKE = 0x1000                                  # a non-null, 16-byte aligned address that is never read: every case is refused on the host
+# the five calls, by the names they had as entry points of their own (and still refuse under): name -> (entry point, mode of the call descriptor)
+AT_POINTS, SPATIAL, ENCGRAD, POSEGRAD = 1, 2, 4, 8
+ENTRY = {'sininn_flownet_forward_spatial_points': ('sininn_flownet_forward', AT_POINTS | SPATIAL),
+         'sininn_flownet_backward_spatial_points': ('sininn_flownet_backward', AT_POINTS | SPATIAL),
+         'sininn_flownet_backward_encgrad_spatial_points': ('sininn_flownet_backward', AT_POINTS | SPATIAL | ENCGRAD),
+         'sininn_flownet_backward_posegrad_spatial_points': ('sininn_flownet_backward', AT_POINTS | SPATIAL | POSEGRAD),
+         'sininn_flownet_sample_mask_points': ('sininn_flownet_sample_mask', AT_POINTS | SPATIAL)}
 CALLS = ('sininn_flownet_forward_spatial_points', 'sininn_flownet_backward_spatial_points', 'sininn_flownet_backward_encgrad_spatial_points',
          'sininn_flownet_backward_posegrad_spatial_points', 'sininn_flownet_sample_mask_points')
 
@@ -26,26 +35,34 @@ def args(_lib, encoding=0, enc_dim=515, progressive=1):
     return a
 
 
-def caller(_lib, name):
+def caller(_lib, name, g_poses=FAKE):
     """lambda (args, grid, poses, n) -> return code, every other pointer non-null"""
     lib = _lib.lib()
     cs = (C.c_float * 6)(0, 0, 0, 1, 1, 1)
-    csp = C.cast(cs, C.c_void_p)
-    tail = {'sininn_flownet_forward_spatial_points': (), 'sininn_flownet_backward_spatial_points': (),
-            'sininn_flownet_backward_encgrad_spatial_points': (FAKE, FAKE, 1 << 40),
-            'sininn_flownet_backward_posegrad_spatial_points': (FAKE, None, FAKE, 1 << 40),
-            'sininn_flownet_sample_mask_points': (FAKE,)}[name]
-    return lambda a, grid, poses, n, keep=cs: getattr(lib, name)(C.byref(a), grid, 3, csp, poses, n, *tail, None)
+    entry, mode = ENTRY[name]
+    tail = (FAKE,) if 'sample_mask' in name else ()
+
+    def call(a, grid, poses, n):
+        c = _lib.FlowNetCall(mode=mode, poses=poses, n=n, grid=grid, res=3, centre_scale=C.cast(cs, C.c_void_p), g_enc_a=FAKE,
+                             enc_workspace=FAKE, enc_workspace_bytes=1 << 40, g_poses=g_poses, extra_workspace=FAKE,
+                             extra_workspace_bytes=1 << 40)
+        return getattr(lib, entry)(C.byref(a), C.byref(c), *tail, None)
+    return call
 
 
 def test_symbols_are_exported_and_declared():
     from sin_inn_amd import _lib
     lib = _lib.lib()
-    for name in CALLS:
+    header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'include', 'sininn.h')).read()
+    for name in ('sininn_flownet_forward', 'sininn_flownet_backward', 'sininn_flownet_sample_mask'):
         assert name in _lib.EXPORTED, name
         fn = getattr(lib, name)
         assert fn.restype is C.c_int and fn.argtypes[0] == C.POINTER(_lib.FlowNetArgs)
-        assert fn.argtypes[2] is C.c_int and fn.argtypes[5] is C.c_int64 and fn.argtypes[-1] is C.c_void_p
+        assert fn.argtypes[1] == C.POINTER(_lib.FlowNetCall) and fn.argtypes[-1] is C.c_void_p
+    fields = dict(_lib.FlowNetCall._fields_)
+    assert fields['res'] is C.c_int and fields['n'] is C.c_int64
+    for name in CALLS:                             # the entry points these calls had are gone
+        assert name not in _lib.EXPORTED and not hasattr(lib, name) and name + '(' not in header, name
     assert lib.sininn_version() == 4 and lib.sininn_sizeof(7) == C.sizeof(_lib.FlowNetArgs) == 280
 
 
@@ -86,8 +103,7 @@ def test_refusals_before_any_launch(name):
         refused(a, FAKE, FAKE, 64, b'saved holds 16 bytes')
     if 'posegrad' in name:
         a = make()
-        assert lib.sininn_flownet_backward_posegrad_spatial_points(C.byref(a), FAKE, 3, C.cast((C.c_float * 6)(), C.c_void_p), FAKE, 64, None,
-                                                                   None, FAKE, 1 << 40, None) != 0
+        assert caller(_lib, name, g_poses=None)(a, FAKE, FAKE, 64) != 0
         assert b'flownet_backward_posegrad_spatial_points: null g_poses' in lib.sininn_last_error()
 
 

@@ -14,14 +14,14 @@ network, so the share of a skipped run is not a utilisation.  The mask sits in a
 RFF / PRFF (learnable frequencies) add the data gradient through layer 1 to the step (2 N 512*256 more FLOPs, counted) and the torch ops
 that make F_eff and carry its gradient to `encode.frequencies`; PRFF runs under the prefix mask like the other progressive nets.
 --spatial R (515-wide progressive nets) puts the network under a StashedSpatialController(net, R) whose every cell has the prefix mask of
---k-active ones: the fused path samples the grid [R^3][515] in the kernels (sininn_flownet_*_spatial, k_active = --k-active), the
+--k-active ones: the fused path samples the grid [R^3][515] in the kernels (the SPATIAL mode of the call descriptor, k_active = --k-active), the
 --baseline is composed_flow_fields with the reference's own gather + einsum, `get_mask()[inds]` (N, 8, 515) times the weights, on every
 call.  The FLOP counts stay those of the network; the interpolation is not counted.
 `siren` is 3-256-256-256-256-4: 2 N (3*256 + 3*256*256 + 256*4) FLOPs forward; backward adds the data gradients of layers 2-5 and the
 weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines in the backward pass) are not counted.
 --points N times the network at a pose list of N uniform random points of [-1, 1]^3 (flownet.flow_at, planar output: the kernels' own
 layout) instead of a grid; the --baseline is tools/fit_flow.composed_flow_at on the same list.  The FLOP counts are those of N points.
---points N --spatial R [--pose-grad] calls the StashedSpatialController on the pose list (sininn_flownet_*_spatial_points); the --baseline is
+--points N --spatial R [--pose-grad] calls the StashedSpatialController on the pose list (AT_POINTS | SPATIAL); the --baseline is
 composed_flow_at under the controller's `interpolate` (gather + einsum, (N, 8, 515)) on every call.
 --dim 2 builds the network on two coordinates, ModelParams(domain_dim=2) (RBF, FFN, UFF, RBFG and their progressive forms, 514 wide), and
 times flow_fields(net, None, height, width, .), the call of video-interpolation/pair_flow.py: one frame, no times; the --baseline is
