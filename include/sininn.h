@@ -969,6 +969,22 @@ int64_t sininn_flow2img_workspace_floats(int n, int h, int w);
 int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
                     int64_t workspace_floats, uint8_t* img, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Frame synthesis from a pair of flows (csrc/flowsynth.hip).  i0, i1: frames (B, C, H, W), C = 1 or 3; f01, f10: flows
+ * (B, 2, H, W) in pixels, channel 0 = x; tau: K DEVICE floats in [0, 1] (not validated here: the call reads no device memory on the
+ * host), K <= 64.  out (B, K, C, H, W):
+ *   Z0 = -20 mean_c |i0 - warp(i1, f01)|, Z1 = -20 mean_c |i1 - warp(i0, f10)|    warp = sininn_flow_warp_l1's rule; on an axis of
+ *                                                                                 length 1 its sample lies outside the frame (0)
+ *   S0 = softmax-splat(i0, tau_k f01, Z0), S1 = softmax-splat(i1, (1 - tau_k) f10, Z1);  N0, N1 = the splatted exp(Z) channels
+ *   a0 = (1 - tau_k) (N0 != 0), a1 = tau_k (N1 != 0);  out = (a0 S0 + a1 S1) / (a0 + a1), and (1 - tau_k) i0 + tau_k i1 where
+ *   a0 + a1 == 0; -0.0 counts as zero.
+ * out_u8 (may be NULL): the same layout in bytes, clamp(round-half-even(255 out), 0, 255).  `workspace`: DEVICE floats, at least
+ * the count the _workspace call returns (B K 2 (C + 1) H W; 0 for a non-positive size); it is zeroed inside the call, on `stream`,
+ * so it needs no initialisation.  Two kernel launches whatever K is.  Not differentiable. */
+int64_t sininn_flow_synth_workspace(int B, int K, int C, int H, int W);
+int sininn_flow_synth(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
+                      int H, int W, float* workspace, int64_t workspace_floats, float* out, unsigned char* out_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,9 @@ int splat_mask_launch(const float* mask, int mask_channels, const float* splat, 
 int64_t flow2img_workspace_floats(int n, int h, int w);
 int flow2img_launch(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
                     int64_t workspace_floats, uint8_t* img, hipStream_t st);
+int64_t flow_synth_workspace(int B, int K, int C, int H, int W);
+int flow_synth_launch(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
+                      int H, int W, float* workspace, int64_t workspace_floats, float* out, uint8_t* out_u8, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -627,6 +630,12 @@ int64_t sininn_flow2img_workspace_floats(int n, int h, int w) { return flow2img_
 int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
                     int64_t workspace_floats, uint8_t* img, void* stream) {
   return flow2img_launch(flow, n, h, w, clip, wheel, wheel_rows, workspace, workspace_floats, img, ST(stream));
+}
+
+int64_t sininn_flow_synth_workspace(int B, int K, int C, int H, int W) { return flow_synth_workspace(B, K, C, H, W); }
+int sininn_flow_synth(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
+                      int H, int W, float* workspace, int64_t workspace_floats, float* out, unsigned char* out_u8, void* stream) {
+  return flow_synth_launch(i0, i1, f01, f10, tau, B, K, C, H, W, workspace, workspace_floats, out, out_u8, ST(stream));
 }
 
 }  // extern "C"

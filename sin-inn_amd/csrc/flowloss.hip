@@ -6,34 +6,14 @@
 // (coalesced along x), scatters use the hardware fp32 atomic add (no CAS loop), the census kernel stages the two
 // grey-level tiles (+ halo) in LDS so every image byte is read once.
 #include "common.h"
+#include "splat_taps.h"
 
 namespace sininn {
 
-__device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
-
 // ------------------------------------------------------------------------------------------------
 // forward splat: out[b, c, y + fy .., x + fx ..] += in[b, c, y, x] * bilinear weight      (softsplat.py:8-52)
+//   atomic_add_f32, SplatTaps and splat_taps are in splat_taps.h
 // ------------------------------------------------------------------------------------------------
-struct SplatTaps {
-  int nwx, nwy;
-  float nw, ne, sw, se;
-  bool vnw, vne, vsw, vse;
-};
-
-__device__ __forceinline__ SplatTaps splat_taps(float ox, float oy, int H, int W) {
-  SplatTaps t;
-  t.nwx = (int)floorf(ox); t.nwy = (int)floorf(oy);
-  const float sex = (float)(t.nwx + 1), sey = (float)(t.nwy + 1), nwx = (float)t.nwx, nwy = (float)t.nwy;
-  t.nw = (sex - ox) * (sey - oy);
-  t.ne = (ox - nwx) * (sey - oy);
-  t.sw = (sex - ox) * (oy - nwy);
-  t.se = (ox - nwx) * (oy - nwy);
-  const bool x0 = t.nwx >= 0 && t.nwx < W, x1 = t.nwx + 1 >= 0 && t.nwx + 1 < W;
-  const bool y0 = t.nwy >= 0 && t.nwy < H, y1 = t.nwy + 1 >= 0 && t.nwy + 1 < H;
-  t.vnw = x0 && y0; t.vne = x1 && y0; t.vsw = x0 && y1; t.vse = x1 && y1;
-  return t;
-}
-
 // Block = 32 x 8 source pixels of one image.  Taps that land inside the block's window (tile + SP_R pixels all round)
 // are accumulated with LDS atomics (ds_add_f32) and the window is flushed once with coalesced global atomics; only taps
 // thrown further than SP_R pixels go to global memory directly.  For the smooth, few-pixel flows of the trainer that cuts

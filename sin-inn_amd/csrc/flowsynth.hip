@@ -1,0 +1,201 @@
+// Frame synthesis from a fitted pair of flows: softmax-splat both frames to K in-between times and blend them.
+//   Z0 = -20 mean_c |I0 - warp(I1, F01)|,  Z1 = -20 mean_c |I1 - warp(I0, F10)|          (trainer.py:61-68, Resample2d warp)
+//   S0 = softmax-splat(I0, tau F01, Z0),   S1 = softmax-splat(I1, (1 - tau) F10, Z1)     (softsplat.py:331-358)
+//   out = ((1 - tau) [N0 != 0] S0 + tau [N1 != 0] S1) / ((1 - tau) [N0 != 0] + tau [N1 != 0]),  (1 - tau) I0 + tau I1 where both
+//   splats are empty;  N = the splatted exp(Z) channel.
+// Two launches whatever K is: the scatter reads frame, flow and metric once and reuses them for every time; Z, the warped frame,
+// exp(Z) and the concatenated splat inputs never exist in HBM.  Both kernels are HBM / atomic bound.
+#include "common.h"
+#include "splat_taps.h"
+
+namespace sininn {
+
+constexpr int FS_TX = 32, FS_TY = 8;               // source tile of one block: a wave is two rows of 32 pixels
+constexpr int FS_SCATTER_MAX_BLOCKS = 2048;   // the scatter launch: at most this many blocks, block-stride over the source tiles
+constexpr int FS_MAX_K = 64;
+
+// Resample2d (my_utils/resample2d.py:52-72) sample of img[b, c] at pixel (x, y) + flow, the rule of flow_warp_l1_kernel:
+// grid = (coords + flow) / (W - 1, H - 1) * 2 - 1 read with align_corners = False, zeros outside.  On an axis of length 1 that
+// coordinate is infinite (or 0 / 0): the sample lies outside the frame and is 0.
+struct WarpTaps {
+  int x0, y0;
+  float wx0, wx1, wy0, wy1;
+  bool ok;
+};
+
+__device__ __forceinline__ WarpTaps warp_taps(int x, int y, float fx, float fy, int H, int W) {
+  WarpTaps t = {};
+  if (H < 2 || W < 2) return t;
+  const float gxn = (x + fx) / (float)(W - 1) * 2.f - 1.f, gyn = (y + fy) / (float)(H - 1) * 2.f - 1.f;
+  const float ix = ((gxn + 1.f) * W - 1.f) * 0.5f, iy = ((gyn + 1.f) * H - 1.f) * 0.5f;
+  if (!(fabsf(ix) < 1e9f) || !(fabsf(iy) < 1e9f)) return t;          // the float -> int conversions below stay defined
+  const float flx = floorf(ix), fly = floorf(iy);
+  t.x0 = (int)flx; t.y0 = (int)fly;
+  t.wx1 = ix - flx; t.wy1 = iy - fly; t.wx0 = 1.f - t.wx1; t.wy0 = 1.f - t.wy1;
+  t.ok = true;
+  return t;
+}
+
+// One lane per source pixel (b, y, x) of one source frame (side 0: I0 along F01, side 1: I1 along F10).
+// acc[B][K][2][C + 1][H][W], zeroed by the caller: channels 0..C-1 the splatted I * exp(Z), channel C the splatted exp(Z).
+template <int C>
+__global__ __launch_bounds__(FS_TX * FS_TY) void flowsynth_scatter_kernel(const float* __restrict__ i0, const float* __restrict__ i1,
+                                                                          const float* __restrict__ f01, const float* __restrict__ f10,
+                                                                          const float* __restrict__ tau, int B, int K, int H, int W,
+                                                                          float* __restrict__ acc) {
+  static_assert(FS_TX == 32, "the lane merges assume 32-pixel tile rows");
+  const int tiles_x = (W + FS_TX - 1) / FS_TX, tiles_y = (H + FS_TY - 1) / FS_TY;
+  const int64_t HW = (int64_t)H * W, ntiles = (int64_t)2 * B * tiles_y * tiles_x;
+  const int lx = threadIdx.x % FS_TX, ly = threadIdx.x / FS_TX, lane = threadIdx.x & 63;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {         // block-uniform: every shuffle below is wave-wide
+    int64_t q = tile;
+    const int tx = (int)(q % tiles_x); q /= tiles_x;
+    const int ty = (int)(q % tiles_y); q /= tiles_y;
+    const int b = (int)(q % B), side = (int)(q / B);
+    const int x = tx * FS_TX + lx, y = ty * FS_TY + ly;
+    const bool live = x < W && y < H;
+    const int64_t r = live ? (int64_t)y * W + x : 0;
+    const float* src = (side ? i1 : i0) + (int64_t)b * C * HW;
+    const float* oth = (side ? i0 : i1) + (int64_t)b * C * HW;
+    const float* flow = (side ? f10 : f01) + (int64_t)b * 2 * HW;
+    float v[C + 1], fx = 0.f, fy = 0.f;
+#pragma unroll
+    for (int c = 0; c <= C; ++c) v[c] = 0.f;
+    if (live) {
+      fx = flow[r]; fy = flow[HW + r];
+      const WarpTaps wt = warp_taps(x, y, fx, fy, H, W);
+      float l1 = 0.f;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float* base = oth + c * HW;
+        auto tap = [&](int yy, int xx) -> float {
+          return (wt.ok && yy >= 0 && yy < H && xx >= 0 && xx < W) ? base[(int64_t)yy * W + xx] : 0.f;
+        };
+        const float t00 = tap(wt.y0, wt.x0), t10 = tap(wt.y0 + 1, wt.x0), t01 = tap(wt.y0, wt.x0 + 1), t11 = tap(wt.y0 + 1, wt.x0 + 1);
+        const float warped = t00 * wt.wy0 * wt.wx0 + t01 * wt.wy0 * wt.wx1 + t10 * wt.wy1 * wt.wx0 + t11 * wt.wy1 * wt.wx1;
+        v[c] = src[c * HW + r];
+        l1 += fabsf(v[c] - warped);
+      }
+      const float w = expf(__fmul_rn(-20.f, l1 / (float)C));
+#pragma unroll
+      for (int c = 0; c < C; ++c) v[c] = __fmul_rn(v[c], w);
+      v[C] = w;
+    }
+    for (int k = 0; k < K; ++k) {
+      const float tk = tau[k], t = side ? 1.f - tk : tk;
+      SplatTaps tp = {};
+      bool any = false;
+      if (live) {
+        // the flow is scaled, rounded, then added to the pixel: the same two roundings as splatting the tensor t * F
+        const float ox = (float)x + __fmul_rn(t, fx), oy = (float)y + __fmul_rn(t, fy);
+        if (ox == ox && oy == oy && fabsf(ox) < 1e9f && fabsf(oy) < 1e9f) { tp = splat_taps(ox, oy, H, W); any = true; }
+      }
+      // Neighbouring sources of a smooth flow share taps (splat_fwd_kernel): the south taps of a pixel are the north taps of the
+      // pixel below it (the wave's other row), its east taps the west taps of its right neighbour.  Contributions are summed
+      // across lanes first, so an interior pixel issues one atomic per channel, not four.
+      const int anyi = any ? 1 : 0;
+      const int any_r = __shfl_down(anyi, 1), nwx_r = __shfl_down(tp.nwx, 1), nwy_r = __shfl_down(tp.nwy, 1);
+      const int any_d = __shfl_down(anyi, 32), nwx_d = __shfl_down(tp.nwx, 32), nwy_d = __shfl_down(tp.nwy, 32);
+      const bool give_h = any && (lane & 31) != 31 && any_r != 0 && nwx_r == tp.nwx + 1 && nwy_r == tp.nwy;
+      const bool give_v = any && lane < 32 && any_d != 0 && nwx_d == tp.nwx && nwy_d == tp.nwy + 1;
+      const int gh_l = __shfl_up(give_h ? 1 : 0, 1), gv_u = __shfl_up(give_v ? 1 : 0, 32);
+      const bool take_h = (lane & 31) != 0 && gh_l != 0;
+      const bool take_v = lane >= 32 && gv_u != 0;
+      const int64_t o_nw = (int64_t)tp.nwy * W + tp.nwx;
+      float* plane = acc + ((((int64_t)b * K + k) * 2 + side) * (C + 1)) * HW;
+#pragma unroll
+      for (int c = 0; c <= C; ++c) {
+        float cnw = 0.f, cne = 0.f, csw = 0.f, cse = 0.f;
+        if (any) {
+          cnw = tp.vnw ? v[c] * tp.nw : 0.f; cne = tp.vne ? v[c] * tp.ne : 0.f;
+          csw = tp.vsw ? v[c] * tp.sw : 0.f; cse = tp.vse ? v[c] * tp.se : 0.f;
+        }
+        const float rsw = __shfl_up(csw, 32), rse = __shfl_up(cse, 32);
+        if (take_v) { cnw += rsw; cne += rse; }
+        if (give_v) { csw = 0.f; cse = 0.f; }
+        const float sne = __shfl_up(cne, 1), sse = __shfl_up(cse, 1);
+        if (take_h) { cnw += sne; csw += sse; }
+        if (give_h) { cne = 0.f; cse = 0.f; }
+        if (any) {
+          // (a merged value lands where the receiving lane's own tap of that slot lands: same address, same validity)
+          float* o = plane + c * HW;
+          if (tp.vnw && cnw != 0.f) atomic_add_f32(o + o_nw, cnw);
+          if (tp.vne && cne != 0.f) atomic_add_f32(o + o_nw + 1, cne);
+          if (tp.vsw && csw != 0.f) atomic_add_f32(o + o_nw + W, csw);
+          if (tp.vse && cse != 0.f) atomic_add_f32(o + o_nw + W + 1, cse);
+        }
+      }
+    }
+  }
+}
+
+// One lane per output pixel (b, k, y, x): normalise both splats, form the hole masks and the blend; -0.0 counts as a hole.
+template <int C>
+__global__ void flowsynth_blend_kernel(const float* __restrict__ i0, const float* __restrict__ i1, const float* __restrict__ tau,
+                                       const float* __restrict__ acc, int B, int K, int H, int W, float* __restrict__ out,
+                                       uint8_t* __restrict__ out_u8) {
+  const int64_t HW = (int64_t)H * W, total = (int64_t)B * K * HW;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int64_t r = idx % HW, bk = idx / HW;
+  const int k = (int)(bk % K), b = (int)(bk / K);
+  const float tk = tau[k], sk = 1.f - tk;
+  const float* a0 = acc + (bk * 2 + 0) * (C + 1) * HW + r;
+  const float* a1 = acc + (bk * 2 + 1) * (C + 1) * HW + r;
+  const float n0 = a0[C * HW], n1 = a1[C * HW];
+  const float w0 = __fmul_rn(sk, n0 != 0.f ? 1.f : 0.f), w1 = __fmul_rn(tk, n1 != 0.f ? 1.f : 0.f);
+  const float den = __fadd_rn(w0, w1);
+  const float d0 = n0 == 0.f ? 1.f : n0, d1 = n1 == 0.f ? 1.f : n1;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    float o;
+    // every operation rounded once, no contraction: the expression `flowsynth.composed` evaluates in torch
+    if (den != 0.f) {
+      o = __fdiv_rn(__fadd_rn(__fmul_rn(w0, __fdiv_rn(a0[c * HW], d0)), __fmul_rn(w1, __fdiv_rn(a1[c * HW], d1))), den);
+    } else {
+      const int64_t p = ((int64_t)b * C + c) * HW + r;
+      o = __fadd_rn(__fmul_rn(sk, i0[p]), __fmul_rn(tk, i1[p]));
+    }
+    const int64_t q = (bk * C + c) * HW + r;
+    out[q] = o;
+    if (out_u8) out_u8[q] = (uint8_t)fminf(fmaxf(rintf(__fmul_rn(o, 255.f)), 0.f), 255.f);
+  }
+}
+
+int64_t flow_synth_workspace(int B, int K, int C, int H, int W) {
+  if (B <= 0 || K <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+  return (int64_t)B * K * 2 * (C + 1) * H * W;
+}
+
+int flow_synth_launch(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
+                      int H, int W, float* workspace, int64_t workspace_floats, float* out, uint8_t* out_u8, hipStream_t st) {
+  SININN_CHECK(i0 && i1 && f01 && f10 && tau && workspace && out, "flow_synth: null pointer");
+  SININN_CHECK(B > 0 && K > 0 && C > 0 && H > 0 && W > 0, "flow_synth: bad shape (every size must be positive)");
+  SININN_CHECK(K <= FS_MAX_K, "flow_synth: K = %d times in one call, at most %d", K, FS_MAX_K);
+  SININN_CHECK(C == 1 || C == 3, "flow_synth: frames have 1 or 3 channels (got %d)", C);
+  const int64_t need = flow_synth_workspace(B, K, C, H, W);
+  SININN_CHECK(workspace_floats >= need, "flow_synth: workspace of %lld floats, need %lld", (long long)workspace_floats,
+               (long long)need);
+  const int64_t total = (int64_t)B * K * H * W;
+  SININN_CHECK((total + 255) / 256 < ((int64_t)1 << 31), "flow_synth: B * K * H * W too large for one launch");
+  hipError_t e = hipMemsetAsync(workspace, 0, (size_t)need * sizeof(float), st);
+  SININN_CHECK(e == hipSuccess, "flow_synth: zeroing the workspace failed: %s", hipGetErrorString(e));
+  const int64_t ntiles = (int64_t)2 * B * ((H + FS_TY - 1) / FS_TY) * ((W + FS_TX - 1) / FS_TX);
+  const int blocks = (int)(ntiles < FS_SCATTER_MAX_BLOCKS ? ntiles : FS_SCATTER_MAX_BLOCKS);
+  const dim3 bgrid((unsigned)((total + 255) / 256));
+  if (C == 1) {
+    hipLaunchKernelGGL(flowsynth_scatter_kernel<1>, dim3(blocks), dim3(FS_TX * FS_TY), 0, st, i0, i1, f01, f10, tau, B, K, H, W,
+                       workspace);
+    SININN_LAUNCH_CHECK("flowsynth_scatter");
+    hipLaunchKernelGGL(flowsynth_blend_kernel<1>, bgrid, dim3(256), 0, st, i0, i1, tau, workspace, B, K, H, W, out, out_u8);
+  } else {
+    hipLaunchKernelGGL(flowsynth_scatter_kernel<3>, dim3(blocks), dim3(FS_TX * FS_TY), 0, st, i0, i1, f01, f10, tau, B, K, H, W,
+                       workspace);
+    SININN_LAUNCH_CHECK("flowsynth_scatter");
+    hipLaunchKernelGGL(flowsynth_blend_kernel<3>, bgrid, dim3(256), 0, st, i0, i1, tau, workspace, B, K, H, W, out, out_u8);
+  }
+  SININN_LAUNCH_CHECK("flowsynth_blend");
+  return 0;
+}
+
+}  // namespace sininn

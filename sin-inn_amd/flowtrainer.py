@@ -280,6 +280,21 @@ class FlowTrainer(LightningModule):
             self.logger.log_metrics({'test/EPE': epe, 'epoch': self.current_epoch}, getattr(self.trainer, 'global_step', 0))
         return epe
 
+    def interpolate(self, batch, taus, **kw):
+        """The frames at `taus` in [0, 1] between frame1 and frame2 of `batch` (frame1, frame2, times, scale, ...), (n, K, 3, h, w):
+        the network's two flows at the batch's time stamps, then `flowsynth.synthesize` (its keywords pass through).  No gradient;
+        the network is evaluated in eval() and left in the mode it was found in."""
+        from . import flowsynth
+        frame1, frame2, times, scale = batch[:4]
+        was_training = self.net.training
+        self.net.eval()
+        try:
+            with torch.no_grad():
+                flow12, flow21 = self.forward(frame1, times, scale)
+                return flowsynth.synthesize(frame1, frame2, flow12, flow21, taus, **kw)
+        finally:
+            self.net.train(was_training)
+
     def configure_optimizers(self):
         return FusedLAMB(self.net.parameters(), lr=self.lr)
 

@@ -1,0 +1,87 @@
+"""Time the frame synthesis (sin_inn_amd.flowsynth): the fused operator and, with --baseline, `flowsynth.composed` (the same
+definition from the existing operators) in the same process, alternating windows; device events, windows of at least --seconds
+after a warm-up; one JSON line per K, appended to profiles/flowsynth_bench.jsonl with --log.
+
+    python tools/bench_flowsynth.py --height 436 --width 1024 --batch 3 --factor 8 [--baseline]
+
+K = factor - 1 times per call (tau = j / factor), and K = 1 (tau = 1 / 2) beside it.  The inputs are a SyntheticClip pair and its
+ground-truth flows (the backward flow: the negative of the forward one): smooth flows of a few pixels, what a fitted network gives.
+`*_bytes_per_frame` count the HBM traffic of one output frame from the definition, not from counters.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'tools')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from bench_flownet import window  # noqa: E402
+
+
+def bytes_per_frame(k):
+    """(fused, composed) fp32 bytes per pixel of one output frame, C = 3, counted from the definition, in words:
+    fused     once per call 16 (per source frame: the frame 3, the gathered other frame 3, the flow 2); per frame 35 (the 8 accumulator
+              planes zeroed 8, atomically added to 16 -- a read and a write --, read back 8; the output 3)
+    composed  once per call 66 (per source frame: warp + metric 12, -20 * 2, exp twice 4, frame * exp 7, cat 8); per frame 148 (per
+              source frame 37.5: t * flow 4, zero-fill 4, splat 14, the guard 4, the divide 7, the hole mask 4.5; the blend 73)"""
+    return 4 * (16 / k + 35), 4 * (66 / k + 148)
+
+
+def main():
+    from sin_inn_amd import flowdata, flowsynth
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--height', type=int, default=436)
+    ap.add_argument('--width', type=int, default=1024)
+    ap.add_argument('--batch', type=int, default=3)
+    ap.add_argument('--factor', type=int, default=8)
+    ap.add_argument('--seconds', type=float, default=1.0)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--rounds', type=int, default=3, help='alternations of the fused and the composed windows')
+    ap.add_argument('--baseline', action='store_true')
+    ap.add_argument('--log', action='store_true', help='append the lines to profiles/flowsynth_bench.jsonl')
+    a = ap.parse_args()
+    assert 2 <= a.factor <= 65
+    dev = torch.device('cuda', 0)
+    clip = flowdata.SyntheticClip(a.batch + 1, a.height, a.width)
+    i0, i1 = clip.video[:-1].contiguous().to(dev), clip.video[1:].contiguous().to(dev)
+    f01 = clip.flow.contiguous().to(dev)
+    f10 = (-clip.flow).contiguous().to(dev)
+    lines = []
+    for k in sorted({1, a.factor - 1}):
+        taus = [0.5] if k == 1 else [j / a.factor for j in range(1, a.factor)]
+        tau_dev = torch.tensor(taus, dtype=torch.float32, device=dev)
+        ws = torch.empty(flowsynth.workspace_floats(a.batch, k, 3, a.height, a.width), device=dev)
+        out = torch.empty(a.batch, k, 3, a.height, a.width, device=dev)
+        todo = {'fused': lambda: flowsynth.synthesize(i0, i1, f01, f10, tau_dev, out=out, workspace=ws)}
+        if a.baseline:
+            todo['composed'] = lambda: flowsynth.composed(i0, i1, f01, f10, taus)
+        res = {name: [] for name in todo}
+        for _ in range(a.rounds):
+            for name, fn in todo.items():
+                res[name].append(window(fn, a.seconds, a.warmup))
+        fb, cb = bytes_per_frame(k)
+        line = dict(op='flowsynth', height=a.height, width=a.width, batch=a.batch, K=k, workspace_bytes=ws.numel() * 4,
+                    fused_bytes_per_pixel_frame=round(fb, 1), composed_bytes_per_pixel_frame=round(cb, 1))
+        for name in res:
+            meds = [w['median_ms'] for w in res[name]]
+            line[f'{name}_ms'] = round(min(meds), 4)
+            line[f'{name}_ms_windows'] = [round(m, 4) for m in meds]
+        line['fused_ms_per_frame'] = round(line['fused_ms'] / k, 4)
+        if a.baseline:
+            line['speedup'] = round(line['composed_ms'] / line['fused_ms'], 3)
+        print(json.dumps(line))
+        lines.append(line)
+    if a.log:
+        os.makedirs(os.path.join(ROOT, 'profiles'), exist_ok=True)
+        with open(os.path.join(ROOT, 'profiles', 'flowsynth_bench.jsonl'), 'a') as f:
+            for line in lines:
+                f.write(json.dumps(line) + '\n')
+
+
+if __name__ == '__main__':
+    main()

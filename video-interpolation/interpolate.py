@@ -1,0 +1,142 @@
+"""Slow motion from a fitted flow network: the frames between every consecutive pair of a clip, written as PNGs.
+
+    python video-interpolation/interpolate.py --input-video <sintel scene folder> --name NAME --net PRBF --factor 8
+    python video-interpolation/interpolate.py --synthetic 4 24 40 --name smoke --net RBF --fit-epochs 2 --factor 3 --out frames
+
+The network is the one `main.py train --name NAME --net NET` fitted to the clip: the newest checkpoint under
+checkpoints/<scene>/<NAME> is loaded as `main.py test` loads it (same folder, same tie-break).  For pair i of the clip and
+j = 0 .. factor - 1 the frame at tau = j / factor is written to <out>/frame_<i + 1:04d>_<j:02d>.png; j = 0 is the source frame
+itself, written from the data, the others come from `FlowTrainer.interpolate` (sin_inn_amd.flowsynth: softmax splatting of both
+frames along the pair's two flows, blended; one call per batch of pairs, whatever the factor).  After the last pair the last
+source frame is written as frame_<T:04d>_00.png.
+
+  --input-video DIR | --synthetic T H W   the clip: an `Images` folder, or a `SyntheticClip` of T frames of H x W
+  --factor F       F - 1 new frames per pair (default 2)
+  --size S         --input-video: the shorter side of the frames (default 436)
+  --out DIR        where the PNGs go (default results/interp_<scene>_<name>_x<factor>)
+  --gif            also results/interp_<scene>_<name>_x<factor>.gif
+  --fit-epochs N   train N epochs first through FlowTrainer (default 0: a checkpoint must exist); with it no checkpoint is read
+"""
+import argparse
+import importlib.util
+import os
+import os.path as path
+import sys
+
+ROOT = path.dirname(path.dirname(path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def flow_main():
+    """main.py of this folder as a module, loaded from its file (the repository root holds a main.py of its own)"""
+    spec = importlib.util.spec_from_file_location('flow_main', path.join(path.dirname(path.abspath(__file__)), 'main.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def get_parser():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument('--input-video', help='an Images scene folder (frame_0001.png ..)')
+    src.add_argument('--synthetic', nargs=3, type=int, metavar=('T', 'H', 'W'), help='a SyntheticClip of T frames of H x W')
+    ap.add_argument('--name', required=True, help='the run whose newest checkpoint is loaded')
+    ap.add_argument('--net', required=True, help='the network of that run (main.py --net)')
+    ap.add_argument('--factor', type=int, default=2, help='time steps per pair: factor - 1 new frames between two source frames')
+    ap.add_argument('--size', type=int, default=436, help='--input-video: the shorter side of the frames')
+    ap.add_argument('--out', help='folder of the PNGs (default results/interp_<scene>_<name>_x<factor>)')
+    ap.add_argument('--gif', action='store_true', help='also write results/interp_<scene>_<name>_x<factor>.gif')
+    ap.add_argument('--fit-epochs', type=int, default=0, metavar='N', help='train N epochs first instead of loading a checkpoint')
+    ap.add_argument('--batch', type=int, default=1, help='pairs per call')
+    return ap
+
+
+def get_args(argv=None):
+    ap = get_parser()
+    a = ap.parse_args(argv)
+    if a.factor < 1 or a.factor > 65:
+        ap.error('--factor: 1 .. 65 (one call synthesizes factor - 1 <= 64 times)')
+    if a.fit_epochs < 0 or a.batch < 1:
+        ap.error('--fit-epochs >= 0 and --batch >= 1')
+    return a
+
+
+def frame_plan(num_frames, factor):
+    """[(file name, pair index, j)] in writing order; j == 0: source frame `pair index`, the last entry the last source frame"""
+    plan = [(f'frame_{i + 1:04d}_{j:02d}.png', i, j) for i in range(num_frames - 1) for j in range(factor)]
+    plan.append((f'frame_{num_frames:04d}_00.png', num_frames - 1, 0))
+    return plan
+
+
+def trainer_args(a):
+    """the namespace of main.py (its defaults for the losses) for this clip, run and network"""
+    m = flow_main()
+    argv = ['test', '--name', a.name, '--net', a.net, '--size', str(a.size), '--test-size', str(a.size), '--test-batch', str(a.batch),
+            '--epochs', str(max(a.fit_epochs, 1))]
+    argv += ['--synthetic', *map(str, a.synthetic)] if a.synthetic else ['--input-video', a.input_video]
+    args = m.get_args(argv)
+    args.net = m.build_net(args)
+    return m, args
+
+
+def load_model(a):
+    """(FlowTrainer on the device, data module, scene name): fitted here for --fit-epochs, else from the newest checkpoint"""
+    import torch
+    from sin_inn_amd.flowdata import get_video
+    from sin_inn_amd.flowtrainer import FlowTrainer
+    from sin_inn_amd.lightning import Trainer
+    m, args = trainer_args(a)
+    video, scene = get_video(args.input_video, args)
+    device = torch.device('cuda', 0)
+    if a.fit_epochs:
+        model = FlowTrainer(args, test_tag=f'{scene}_{a.name}')
+        Trainer(gpus=[0], max_epochs=a.fit_epochs, check_val_every_n_epoch=a.fit_epochs + 1).fit(model, video)
+    else:
+        model = FlowTrainer.load_from_checkpoint(m._latest_ckpt(scene, a.name), args=args, test_tag=f'{scene}_{a.name}')
+    return model.to(device), video, scene
+
+
+def _to_device(batch, device):
+    import torch
+    return [t.to(device) if torch.is_tensor(t) else t for t in batch]
+
+
+def main(argv=None):
+    a = get_args(argv)
+    import numpy as np
+    import torch
+    from PIL import Image
+    from sin_inn_amd.flowtrainer import save_gif
+    model, video, scene = load_model(a)
+    device = next(model.parameters()).device
+    clip = video.testset.video                                    # (T, 3, h, w) in [0, 1], on the host
+    num_frames = clip.shape[0]
+    tag = f'interp_{scene}_{a.name}_x{a.factor}'
+    out_dir = a.out or path.join('results', tag)
+    os.makedirs(out_dir, exist_ok=True)
+    taus = [j / a.factor for j in range(1, a.factor)]
+    source = (clip * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).numpy()         # (T, h, w, 3)
+    between = {}                                                   # (pair, j) -> (h, w, 3) bytes
+    if taus:
+        first = 0
+        for batch in video.test_dataloader():
+            _, u8 = model.interpolate(_to_device(batch, device), taus, u8=True)
+            u8 = u8.permute(0, 1, 3, 4, 2).cpu().numpy()           # (n, K, h, w, 3)
+            for n in range(u8.shape[0]):
+                for j in range(1, a.factor):
+                    between[(first + n, j)] = u8[n, j - 1]
+            first += u8.shape[0]
+    written = []
+    for name, i, j in frame_plan(num_frames, a.factor):
+        img = source[i] if j == 0 else between[(i, j)]
+        Image.fromarray(np.ascontiguousarray(img)).save(path.join(out_dir, name))
+        written.append(img)
+    if a.gif:
+        os.makedirs('results', exist_ok=True)
+        save_gif(path.join('results', f'{tag}.gif'), np.stack(written), fps=4 * a.factor)
+    print(f'{len(written)} frames of {clip.shape[-2]} x {clip.shape[-1]} in {out_dir} ({num_frames} source frames, x{a.factor})')
+
+
+if __name__ == '__main__':
+    main()
