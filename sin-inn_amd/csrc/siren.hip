@@ -16,8 +16,9 @@
 //           l = 3, 2, 1:  dh_l = dz_{l+1} W_{l+1} with the forward's GEMM loop on transposed weights, (sin, cos)(u_l): h_l -> workspace (the
 //           operand of the next layer's weight gradient), dz_l = omega dh_l cos(u_l) -> workspace (l > 1);  gW1 [256][3] / gb1 partials from
 //           the dz_1 tile and the tile's coordinates.  gW_l = dz_l^T h_{l-1}, gb_l (l = 2 .. 4) are flownet.hip's split-over-points kernel and
-//           reduce; siren_reduce_kernel adds the chain kernel's per-block partial sums in block order.  No floating-point atomics: two
-//           calls are bitwise equal.
+//           reduce; siren_reduce_kernel adds the chain kernel's per-block partial sums in block order (gb5: each block's double sum
+//           travels as two floats and is rounded once, after the blocks are added).  No floating-point atomics: two calls are bitwise
+//           equal.
 // structure: what this file has of its own is the sine (sine_tile, the sincosf steps of the chain kernel), its descriptor and its partial
 //           sums.  From flownet_tile.h come the tile, gemm_lds, mfma_k4 for layer 1, store_acc with the Phase / Plain epilogues, copy_tile_out,
 //           stage_coord and the host checks of the point grid, the layers, `saved` and the
@@ -42,9 +43,10 @@ namespace {
 constexpr int SR_IN = 3;
 constexpr int SR_SINES = 4;                            // sine layers; SR_SINES + 1 nn.Linears
 constexpr size_t SR_LDS = (size_t)(FN_P * FN_HS + FN_P * FN_OUT + FN_P * FN_CS) * sizeof(float);
-// one chain block's partial sums: gW1 [256][3], gb1 [256], gW5 [4][256], gb5 [4]
+// one chain block's partial sums: gW1 [256][3], gb1 [256], gW5 [4][256], gb5 [4] as (hi [4], lo [4]): the block's double sum in two
+// floats, so that the reduce kernel adds the blocks' sums unrounded
 constexpr int SR_PART_GB1 = FN_HID * SR_IN, SR_PART_GW5 = SR_PART_GB1 + FN_HID, SR_PART_GB5 = SR_PART_GW5 + FN_OUT * FN_HID;
-constexpr int SR_PART = SR_PART_GB5 + FN_OUT;
+constexpr int SR_PART = SR_PART_GB5 + 2 * FN_OUT;
 
 struct SirenDev {
   int T, H, W, N, ntiles;
@@ -287,7 +289,11 @@ __global__ __launch_bounds__(FN_NTHR, 2) void siren_bwd_chain_kernel(std::condit
   out[SR_PART_GB1 + tid] = gb1;
 #pragma unroll
   for (int c = 0; c < 4; ++c) out[SR_PART_GW5 + c * FN_HID + tid] = gw5[c];
-  if (tid < FN_OUT) out[SR_PART_GB5 + tid] = (float)gb5;
+  if (tid < FN_OUT) {
+    const float hi = (float)gb5;
+    out[SR_PART_GB5 + tid] = hi;
+    out[SR_PART_GB5 + FN_OUT + tid] = (float)(gb5 - (double)hi);
+  }
 }
 
 // the chain kernel's partial sums, blocks in index order, into gW1 [256][3], gb1 [256], gW5 [4][256], gb5 [4]
@@ -295,8 +301,9 @@ __global__ __launch_bounds__(FN_NTHR) void siren_reduce_kernel(const float* part
   const int i = blockIdx.x * FN_NTHR + threadIdx.x;
   if (i >= SR_PART) return;
   if (i >= SR_PART_GB5) {                              // the output bias: block sums that largely cancel, added in double, rounded once
+    if (i >= SR_PART_GB5 + FN_OUT) return;             // the lo halves are read with their hi halves
     double d = 0.0;
-    for (int c = 0; c < nparts; ++c) d += (double)part[(size_t)c * SR_PART + i];
+    for (int c = 0; c < nparts; ++c) d += (double)part[(size_t)c * SR_PART + i] + (double)part[(size_t)c * SR_PART + i + FN_OUT];
     gb5[i - SR_PART_GB5] = (float)d;
     return;
   }
