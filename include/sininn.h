@@ -968,6 +968,26 @@ int sininn_splat_mask(const float* mask, int mask_channels, const float* splat, 
 int64_t sininn_flow2img_workspace_floats(int n, int h, int w);
 int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
                     int64_t workspace_floats, uint8_t* img, void* stream);
+/* The per-pixel photometric error of a step and its stash into the loss log of a spatially adaptive controller (DESIGN 16.2;
+ * progressive_controller.py:596-618 with the per-point loss the reference leaves undefined).  softmax*, frame*: (B, C, H, W), C = 1 or 3;
+ * mask*: (B, mask_channels, H, W), mask_channels 1 or C, the masks after sininn_splat_mask.
+ *   E[b][y][x]         = 0.5 (mean_c |m1 S1 - m1 I1| + mean_c |m2 S2 - m2 I2|)      the integrand of the two L1 terms; every product,
+ *                                                                                  difference and sum rounded once, no FMA
+ *   log_buffer[cell]  += sum of alpha(p, k) E[p] over the points p = (times[b], ys[y], xs[x]) and their 8 corners k with cell(p, k) == cell
+ *   log_counter[cell] += the same sum of alpha(p, k)
+ * Per axis, u = ((v - centre) scale + 1) / 2 * max(res - 2, 1) + 0.5 in fp32, the cells floor(u) and ceil(u + 1e-6) clamped to the grid,
+ * their weights ceil(u + 1e-6) - u and u - floor(u): alpha is the product over the axes, cell = i_t + res (i_y + res i_x) -- the cells and
+ * weights the flow-network kernels interpolate the per-point mask with.  times: B floats, ys: H, xs: W, all DEVICE; centre and scale by value.
+ * log_buffer, log_counter: DEVICE [res^3], read, added to and written.  Three launches, no atomics, every sum in a fixed order: two
+ * calls on equal inputs give bitwise equal buffers.  E (may be NULL): DEVICE (B, H, W), written when given.  `workspace`: DEVICE
+ * floats, at least the count the _workspace_floats call returns (0 for sizes the call refuses); needs no initialisation.
+ * 3 <= res <= 1024, H <= 65535, B <= 65534.  The call reads no device memory on the host.  Not differentiable. */
+int64_t sininn_flow_error_stash_workspace_floats(int B, int H, int W, int res);
+int sininn_flow_error_stash(const float* softmax1, const float* frame1, const float* mask1, const float* softmax2, const float* frame2,
+                            const float* mask2, int mask_channels, int B, int C, int H, int W, const float* times, const float* ys,
+                            const float* xs, int res, float centre_t, float centre_y, float centre_x, float scale_t, float scale_y,
+                            float scale_x, float* log_buffer, float* log_counter, float* E, float* workspace, int64_t workspace_floats,
+                            void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Frame synthesis from a pair of flows (csrc/flowsynth.hip).  i0, i1: frames (B, C, H, W), C = 1 or 3; f01, f10: flows

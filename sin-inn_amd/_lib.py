@@ -319,6 +319,9 @@ _SIGS = {
     'sininn_flow2img_workspace_floats': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     'sininn_flow2img': (C.c_int, [c_f, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, c_f, C.c_int64, C.c_void_p,
                                   C.c_void_p]),
+    'sininn_flow_error_stash_workspace_floats': (C.c_int64, [C.c_int] * 4),
+    'sininn_flow_error_stash': (C.c_int, [c_f] * 6 + [C.c_int] * 5 + [c_f] * 3 + [C.c_int] + [C.c_float] * 6 + [c_f] * 4
+                                + [C.c_int64, C.c_void_p]),
     'sininn_flow_synth_workspace': (C.c_int64, [C.c_int] * 5),
     'sininn_flow_synth': (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f, C.c_int64, c_f,
                                     C.c_void_p, C.c_void_p]),

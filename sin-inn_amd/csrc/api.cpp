@@ -141,6 +141,11 @@ int flow_epe_launch(const float* flow, int64_t flow_sample_stride, const float* 
                     int64_t n_partials, float* out, hipStream_t st);
 int splat_mask_launch(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, hipStream_t st);
 int64_t flow2img_workspace_floats(int n, int h, int w);
+int64_t flow_error_stash_workspace_floats(int B, int H, int W, int res);
+int flow_error_stash_launch(const float* softmax1, const float* frame1, const float* mask1, const float* softmax2, const float* frame2,
+                            const float* mask2, int mask_channels, int B, int C, int H, int W, const float* times, const float* ys,
+                            const float* xs, int res, const float* centre, const float* scale, float* log_buffer, float* log_counter,
+                            float* e_out, float* workspace, int64_t workspace_floats, hipStream_t st);
 int flow2img_launch(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
                     int64_t workspace_floats, uint8_t* img, hipStream_t st);
 int64_t flow_synth_workspace(int B, int K, int C, int H, int W);
@@ -625,6 +630,16 @@ int sininn_flow_epe(const float* flow, int64_t flow_sample_stride, const float* 
 }
 int sininn_splat_mask(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, void* stream) {
   return splat_mask_launch(mask, mask_channels, splat, n, c, h, w, out, ST(stream));
+}
+int64_t sininn_flow_error_stash_workspace_floats(int B, int H, int W, int res) { return flow_error_stash_workspace_floats(B, H, W, res); }
+int sininn_flow_error_stash(const float* softmax1, const float* frame1, const float* mask1, const float* softmax2, const float* frame2,
+                            const float* mask2, int mask_channels, int B, int C, int H, int W, const float* times, const float* ys,
+                            const float* xs, int res, float centre_t, float centre_y, float centre_x, float scale_t, float scale_y,
+                            float scale_x, float* log_buffer, float* log_counter, float* E, float* workspace, int64_t workspace_floats,
+                            void* stream) {
+  const float centre[3] = {centre_t, centre_y, centre_x}, scale[3] = {scale_t, scale_y, scale_x};
+  return flow_error_stash_launch(softmax1, frame1, mask1, softmax2, frame2, mask2, mask_channels, B, C, H, W, times, ys, xs, res, centre,
+                                 scale, log_buffer, log_counter, E, workspace, workspace_floats, ST(stream));
 }
 int64_t sininn_flow2img_workspace_floats(int n, int h, int w) { return flow2img_workspace_floats(n, h, w); }
 int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,

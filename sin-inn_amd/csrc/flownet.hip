@@ -97,6 +97,7 @@
 //           per tile is the 64 x (8 corner weights, 8 row offsets), 4 KiB, computed once per point by the first 64 threads.  k_active
 //           cuts the K loop and the weight-gradient tiles as above: the grid is zero from there on, the operand e * 0.
 #include "flownet_tile.h"
+#include "spatial_cells.h"   // FN_DOM, FN_GW, Spatial, Corners, corners_of
 
 namespace sininn {
 
@@ -107,8 +108,6 @@ constexpr int FN_WS = FN_WT + 16;   // floats per point row of a weight-gradient
 constexpr int FN_CHUNK_ELEMS = 1 << 15;   // split over points: (number of chunks) x (output tiles) is about 512 blocks
 constexpr size_t FN_WG_LDS = (size_t)(2 * FN_P * FN_WS) * sizeof(float);
 constexpr int FN_FWD_MAX_BLOCKS = 2048;   // the forward launch: at most this many blocks, grid-stride over the 64-point tiles
-constexpr int FN_DOM = 3;           // progressive: the raw coordinates lead the encoded features (two of them at domain_dim = 2)
-constexpr int FN_GW = 512 + FN_DOM;  // spatial: floats per row of the mask grid and of the W1 it goes with
 constexpr int FN_CN = 16;           // spatial: floats per point of the corner tile in LDS: 8 weights, 8 row offsets
 constexpr size_t FN_CN_LDS = (size_t)(FN_P * FN_CN) * sizeof(float);
 // the dynamic LDS of each kernel mode, for every launch of it: the forward, chain and frequency-gradient kernels hold the hidden tile and
@@ -176,14 +175,6 @@ R for_kind(int encoding, R otherwise, F&& f) {
   }
 }
 
-// spatial: the mask grid and the map from a coordinate to its cell
-struct Spatial {
-  const float* grid;       // [res^3][FN_GW]
-  int res;
-  float span;              // max(res - 2, 1)
-  float centre[3], scale[3];
-};
-
 struct FlowNetDev {
   int T, H, W, N, ntiles;
   float scale;
@@ -207,38 +198,6 @@ struct FlowNetDev {
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes at a dword-aligned address: rows of FN_GW floats
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-struct Corners {
-  float w[8];              // (a_t a_y) a_x of corner c: bit 2 of c chooses t's upper index, bit 1 y's, bit 0 x's
-  int row[8];              // FN_GW * (i_t + i_y res + i_x res^2), indices clamped to the grid
-};
-
-// interpolate_ of the reference in fp32, one rounding per operation as torch makes them: floor and ceil decide as they do there
-__device__ __forceinline__ Corners corners_of(const Spatial& sp, const Coord c) {
-#pragma clang fp contract(off)
-  const float x[3] = {c.t, c.y, c.x};
-  float a[3][2];
-  int i[3][2];
-  const float top = (float)(sp.res - 1);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float xs = (x[d] - sp.centre[d]) * sp.scale[d];
-    const float u = ((xs + 1.f) * 0.5f) * sp.span + 0.5f;
-    const float f0 = floorf(u), f1 = ceilf(u + 1e-6f);
-    a[d][0] = f1 - u;
-    a[d][1] = u - f0;
-    i[d][0] = (int)fminf(fmaxf(f0, 0.f), top);         // a NaN goes to cell 0
-    i[d][1] = (int)fminf(fmaxf(f1, 0.f), top);
-  }
-  Corners o;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int st = (k >> 2) & 1, sy = (k >> 1) & 1, sx = k & 1;
-    o.w[k] = (a[0][st] * a[1][sy]) * a[2][sx];
-    o.row[k] = (i[0][st] + (i[1][sy] + i[2][sx] * sp.res) * sp.res) * FN_GW;
-  }
-  return o;
-}
 
 __device__ __forceinline__ void store_corners(float* cn, const Corners& o) {
   *reinterpret_cast<f32x4*>(cn) = (f32x4){o.w[0], o.w[1], o.w[2], o.w[3]};

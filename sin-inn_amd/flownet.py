@@ -108,8 +108,8 @@ flows (1, 4, h, w): `times` must be None.  `flow_at`, `net(poses)` and `controll
 that names the dimension and the mode (`_refuse_pair_modes`): RFF / PRFF, PE / PPE, MPFF, SIREN, per-point masks (StashedSpatialController,
 2-D `override_mask` grids), `pose_grad=True`, `times` for such a network, and poses of the other dimension either way.
 
-Out of scope: a plain (non-progressive) piecewise network and a frequency gradient for that encoding, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`, the
-`--spatially-adaptive` switch of the command line, spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
+Out of scope: a plain (non-progressive) piecewise network and a frequency gradient for that encoding, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`,
+spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
 closed, and of `MPFF` its `--net MPFF` (video-interpolation/main.py still refuses both).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
 `sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
 `sin_inn_amd.FusedLAMB` is the reference's apex FusedLAMB (trainer.py:134-135) restated, `sin_inn_amd.FusedAdam` drives them as well.

@@ -1,10 +1,18 @@
 """FlowTrainer, the training / validation / test step of the flow path (video-interpolation/trainer.py:15-135), on this project's
 kernels: the flow-field network (`flownet.flow_fields`), the photometric losses (`flowloss`), the Resample2d warp
-(`functional.flow_warp_l1`), FusedLAMB, and three operators of csrc/flowtrain.hip that take the place of chains of small torch
-launches on strided views (the end-point error, `mask * (splat != 0)`) and of a per-frame trip to the host (flow2img).
+(`functional.flow_warp_l1`), FusedLAMB, and the operators of csrc/flowtrain.hip that take the place of chains of small torch
+launches on strided views (the end-point error, `mask * (splat != 0)`), of a per-frame trip to the host (flow2img) and of the
+(N, 8) index and weight tensors of a spatial controller's loss log (error_stash).
 
     flow_epe / splat_mask / flow2img / make_color_wheel   trainer.py:58, 64, 68; my_utils/flow_viz.py:6-127
+    error_stash / error_stash_composed / error_map        the per-point loss of the step and its stash
     FlowTrainer                                            trainer.py:15-135
+
+Under a StashedSpatialController (`main.py --spatially-adaptive`) the step needs a loss PER POINT.  The reference defines none: its
+trainer hands the controller the scalar and fails with an IndexError, and it never calls `update_progress`.  Here it is the integrand
+of the two L1 terms at the target pixel, E = 0.5 (mean_c |m1 S1 - m1 I1| + mean_c |m2 S2 - m2 I2|); `training_step` keeps the six
+tensors, `on_after_backward` (the controller updates its grid in place, so not before the backward pass) stashes them and runs
+`update_progress()` every `block_iterations` steps.
 
 The step makes no host round trip of its own.  The two it inherits: `LinearControllerEarly.stash_iteration` reads the loss
 (progressive networks only, as in the reference), and the flow scale of a batch is read once per frame size (it is a constant of
@@ -115,6 +123,75 @@ def flow2img(flow, clip=10):
     return img[0] if single else img
 
 
+def error_map(softmax1, frame1, mask1, softmax2, frame2, mask2):
+    """E (B, H, W) with torch ops: 0.5 (mean_c |m1 S1 - m1 I1| + mean_c |m2 S2 - m2 I2|), the integrand of the two L1 terms of the step
+    at every target pixel.  The composed partner of `error_stash(.., error_out=)`."""
+    e1 = (mask1 * softmax1 - mask1 * frame1).abs().mean(1)
+    e2 = (mask2 * softmax2 - mask2 * frame2).abs().mean(1)
+    return 0.5 * (e1 + e2)
+
+
+def _stash_inputs(tensors):
+    out = [_gpu32(t.detach().to(torch.float32) if t.dtype == torch.bool else t.detach()).contiguous() for t in tensors]
+    s1, i1, m1, s2, i2, m2 = out
+    b, c, h, w = s1.shape
+    assert i1.shape == s1.shape and s2.shape == s1.shape and i2.shape == s1.shape, 'error_stash: splats and frames of one shape (B, C, H, W)'
+    for m in (m1, m2):
+        assert m.dim() == 4 and m.shape[0] == b and tuple(m.shape[2:]) == (h, w), 'error_stash: mask and frames disagree'
+    if m1.shape[1] != m2.shape[1]:                             # one channel count per call: widen the narrower mask
+        m1, m2 = (m.expand(b, c, h, w).contiguous() for m in (m1, m2))
+    return s1, i1, m1, s2, i2, m2
+
+
+def error_stash(softmax1, frame1, mask1, softmax2, frame2, mask2, times, ys, xs, res, centre_scale, log_buffer, log_counter, *,
+                error_out=None, workspace=None):
+    """The per-point loss of the unsupervised step, stashed into the loss log of a spatially adaptive controller:
+
+        E[b][y][x]         = 0.5 (mean_c |m1 S1 - m1 I1| + mean_c |m2 S2 - m2 I2|)
+        log_buffer[cell]  += sum of alpha(p, k) E[p] over the points p = (times[b], ys[y], xs[x]) and their corners k in `cell`
+        log_counter[cell] += the same sum of alpha(p, k)
+
+    with the cells and weights of `StashedSpatialController.cells` (`res` cells per axis, `centre_scale` the six floats of
+    `centre_scale_host()`).  softmax*, frame*: (B, C, H, W); mask*: (B, 1 or C, H, W), the masks after `splat_mask`; times (B,), ys (H,),
+    xs (W,) on the device.  The two logs (res^3 fp32, device) are updated in place and returned.  Three launches, no atomics, a fixed
+    order of summation: equal inputs give equal bits.  `error_out`: an optional (B, H, W) tensor that receives E; `workspace`: an
+    optional fp32 device buffer of `sininn_flow_error_stash_workspace_floats(B, H, W, res)` values.  No gradient."""
+    s1, i1, m1, s2, i2, m2 = _stash_inputs((softmax1, frame1, mask1, softmax2, frame2, mask2))
+    b, c, h, w = s1.shape
+    times, ys, xs = (_gpu32(t.detach()).contiguous() for t in (times, ys, xs))
+    assert (times.numel(), ys.numel(), xs.numel()) == (b, h, w), 'error_stash: one time per frame, one coordinate per row and column'
+    cells = int(res) ** 3
+    for log in (log_buffer, log_counter):
+        _gpu32(log)
+        assert log.is_contiguous() and log.numel() == cells, 'error_stash: the logs hold res^3 values'
+    if error_out is not None:
+        assert _gpu32(error_out).is_contiguous() and tuple(error_out.shape) == (b, h, w), 'error_out: a contiguous (B, H, W) tensor'
+    need = _lib.lib().sininn_flow_error_stash_workspace_floats(b, h, w, int(res))
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), device=s1.device, dtype=torch.float32)
+    assert _gpu32(workspace).is_contiguous()
+    check(_lib.lib().sininn_flow_error_stash(ptr(s1), ptr(i1), ptr(m1), ptr(s2), ptr(i2), ptr(m2), m1.shape[1], b, c, h, w, ptr(times),
+                                             ptr(ys), ptr(xs), int(res), *(float(v) for v in centre_scale), ptr(log_buffer),
+                                             ptr(log_counter), ptr(error_out), ptr(workspace), workspace.numel(), _stream()))
+    return log_buffer, log_counter
+
+
+def error_stash_composed(softmax1, frame1, mask1, softmax2, frame2, mask2, times, ys, xs, cells, log_buffer, log_counter, *,
+                         error_out=None):
+    """`error_stash` with torch ops, its A / B partner: `error_map`, the flat list of the grid's points, `cells(points)` (a
+    StashedSpatialController's: the (N, 8) indices and weights) and two `index_add_`.  A sum, like the fused form, where
+    `stash_iteration`'s indexed `+=` keeps one write per repeated index; its order is whatever index_add_ makes it."""
+    with torch.no_grad():
+        e = error_map(*_stash_inputs((softmax1, frame1, mask1, softmax2, frame2, mask2)))
+        gt, gh, gw = torch.meshgrid(times, ys, xs, indexing='ij')
+        inds, alphas = cells(torch.stack((gt, gh, gw), dim=-1).view(-1, 3))
+        log_buffer.index_add_(0, inds.flatten(), (e.reshape(-1, 1) * alphas).flatten())
+        log_counter.index_add_(0, inds.flatten(), alphas.flatten())
+        if error_out is not None:
+            error_out.copy_(e)
+    return log_buffer, log_counter
+
+
 def save_gif(filename, frames, fps=4):
     """(n, h, w, c) uint8, c = 1 or 3 -> an animated GIF (imageio.mimsave(..., format='GIF', fps=4) in the reference)"""
     from PIL import Image
@@ -149,7 +226,8 @@ class FlowTrainer(LightningModule):
         self._scales = {}
         self._ones = {}
         self._epoch_means = {}
-        self.fused = True                    # False: the torch expressions of the three flowtrain operators (tools/bench_flowtrainer.py)
+        self.fused = True                    # False: the torch expressions of the flowtrain operators (tools/bench_flowtrainer.py)
+        self._stash = None                   # spatial controller: the six tensors of this step's per-point loss, until on_after_backward
 
     # ---- the pieces of the step ----
 
@@ -230,9 +308,13 @@ class FlowTrainer(LightningModule):
         if len(batch) == 5:
             self.log('train/EPE', self._epe(flow12, batch[-1]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])
         flow12, flow21 = flow12.contiguous(), flow21.contiguous()
-        l1_loss, census_loss, ssim_loss, smooth_loss, _ = self.losses(frame1, frame2, flow12, flow21)
+        l1_loss, census_loss, ssim_loss, smooth_loss, (mask1, mask2, softmax1, softmax2) = self.losses(frame1, frame2, flow12, flow21)
         loss = l1_loss + census_loss + ssim_loss + smooth_loss
-        self.net.stash_iteration(loss.detach())
+        if hasattr(self.net, 'stash_grid'):
+            # a spatial controller updates its mask grid in place and the backward pass checks the grid's version: on_after_backward stashes
+            self._stash = tuple(t.detach() for t in (softmax1, frame1, mask1, softmax2, frame2, mask2))
+        else:
+            self.net.stash_iteration(loss.detach())
 
         self.log('train/loss', loss)
         self.log('train/loss_epoch', loss, on_step=False, on_epoch=True, batch_size=frame1.shape[0])
@@ -242,6 +324,18 @@ class FlowTrainer(LightningModule):
             self.log('train/ssim', ssim_loss)
         self.log('train/smooth', smooth_loss)
         return loss
+
+    def on_after_backward(self):
+        """Lightning's hook, called by the trainer between backward() and the optimizer's step.  Under a StashedSpatialController: the
+        per-point loss of this step goes into the controller's log (`stash_grid`: the fused `error_stash`, or with `fused = False`
+        the composed form), and after `block_iterations` of them `update_progress()` closes the fitted cells, opens the next block in the
+        others and resets `iteration` -- the `(step + 1) % block_iterations == 0` of tools/fit_flow.py."""
+        stash, self._stash = self._stash, None
+        if stash is None:
+            return
+        self.net.stash_grid(*stash, fused=self.fused)
+        if self.net.iteration >= self.net.block_iterations:
+            self.net.update_progress()
 
     def on_train_end(self):
         self.completed_training = True
@@ -311,9 +405,25 @@ class FlowTrainer(LightningModule):
     def on_load_checkpoint(self, checkpoint):
         """Resume the controller's schedule: one `stash_iteration` per step, so `iteration` is the checkpoint's global step; the
         blocks opened so far are the whole blocks inside floor(mask_stashed), but never ahead of the schedule (a fully ramped
-        block counts as open in the sum half a period before the controller moves on)."""
+        block counts as open in the sum half a period before the controller moves on).
+
+        A StashedSpatialController keeps one mask per cell, so `mask_stashed` has res^3 entries and no single one speaks for the schedule:
+        `cur_block` is the largest multiple of `block_size` not above floor(max(mask_stashed)) (the cell that got furthest; never below
+        `block_size`), `next_block` follows from it by the class's rule, and `iteration = global_step % block_iterations`
+        (`update_progress` resets it every `block_iterations` steps).  `in_progress`, `log_buffer` and `log_counter` are registered
+        buffers: the state dict has restored them already."""
         net = self.net
         if not hasattr(net, 'cur_block'):
+            return
+        if hasattr(net, 'stash_grid'):
+            bs, dim = net.block_size, net.encoding_dim
+            opened = int(torch.floor(net.mask_stashed.max()))
+            net.cur_block = max(opened // bs * bs, bs)
+            net.next_block = net.cur_block + bs
+            if dim - net.next_block < bs:
+                net.next_block = dim
+            net.iteration = int(checkpoint.get('global_step', 0)) % max(net.block_iterations, 1)
+            print(f'resumed: iteration {net.iteration}, controller cur_block {net.cur_block} / {dim}')
             return
         net.iteration = int(checkpoint.get('global_step', 0))
         bs, dim = net.block_size, net.encoding_dim

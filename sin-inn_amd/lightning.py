@@ -343,6 +343,8 @@ class Trainer:
                 if automatic and torch.is_tensor(out) and out.requires_grad:
                     self.optimizer.zero_grad()
                     out.backward()
+                    if hasattr(model, 'on_after_backward'):
+                        model.on_after_backward()
                     self.optimizer.step()
                 self.global_step += 1
                 if self.logger is not None and self.global_step % self.log_every == 0:

@@ -26,17 +26,19 @@ StashedSpatialController keeps a mask PER GRID CELL, [res^3][515], and every poi
 blur.  At res = 50 that is 257 MB, so unlike the linear controllers its state lives on the DEVICE, next to the model (`.to()` /
 `.cuda()` move it), nothing is uploaded per step, and the blurred grid the kernels sample is cached and updated IN PLACE: between
 two `increase_block` calls only the six columns of the block in progress change and only they are blurred again.  A backward pass
-must therefore run before the next `stash_iteration` / `update_progress` (flow_fields checks the grid's version and raises
+must therefore run before the next `stash_iteration` / `stash_grid` / `update_progress` (flow_fields checks the grid's version and raises
 otherwise).  The box blurs (mask and loss log) are sums of shifted slices, axis by axis, in a fixed order instead of the reference's
 conv3d: the same numbers to fp32 rounding, bitwise the same whether six columns or all 515 are blurred, and no convolution library
 in a training step.  `stash_iteration` takes the per-point loss the class is written for; the reference's own trainer passes a
-scalar there and fails with an IndexError, here that is a ValueError that says so.
+scalar there and fails with an IndexError, here that is a ValueError that says so.  `stash_grid` is the form the flow trainer uses
+(`main.py --spatially-adaptive`): it takes the six tensors of the step's two L1 terms, and one fused operator computes the per-point
+loss on the grid evaluated last and SUMS it into the log, cell by cell in a fixed order (csrc/flowtrain.hip).
 
 Every 515-wide progressive network runs under every controller here, `MPFFModel` (the piecewise-linear encoding) included; `PPEModel`
 (27 wide) under the linear ones only.
 
-Out of scope: FixedSpatialController, AdaptiveController, the `--spatially-adaptive` switch of video-interpolation/main.py, and
-`mask_dim` other than the three coordinates.
+Out of scope: FixedSpatialController, AdaptiveController, `mask_dim` other than the three coordinates, and a fused stash for pose
+lists (they stay on `stash_iteration`).
 """
 import torch
 import torch.nn as nn
@@ -280,6 +282,29 @@ class StashedSpatialController(ProgressiveEncoderController):
             self.log_buffer[inds] += loss                # the reference's indexed +=: where indices repeat, one write stays
             self.log_counter[inds] += alphas.flatten()
         super().stash_iteration(loss)
+
+    def stash_grid(self, softmax1, frame1, mask1, softmax2, frame2, mask2, fused=True):
+        """The unsupervised step's form of stash_iteration: the per-point loss E of `flowtrainer.error_stash` at the points of the grid
+        `flow_fields` evaluated last, added to the log as a SUM over the points of a cell, in a fixed order (stash_iteration keeps the
+        reference's indexed `+=`: one write per repeated index); then `iteration += 1` and `update_mask()` as every stash does.
+        `fused=False`: the composed form (`cells` of the flat point list and index_add_).  Call it after the backward pass: update_mask
+        changes the mask grid in place."""
+        from . import flowtrainer
+        if self._last_grid is None:
+            raise RuntimeError('stash_grid: the last evaluation was a pose list; its stash is stash_iteration(loss per point)'
+                               if self._last_list is not None else 'stash_grid before any evaluation: no points to attribute the loss to')
+        times, ys, xs = self._last_grid
+        if (times.numel(), ys.numel(), xs.numel()) != (frame1.shape[0], frame1.shape[-2], frame1.shape[-1]):
+            raise ValueError(f'stash_grid: the grid evaluated last has {times.numel()} x {ys.numel()} x {xs.numel()} points, the frames '
+                             f'are {tuple(frame1.shape)}')
+        with torch.no_grad():
+            if fused:
+                flowtrainer.error_stash(softmax1, frame1, mask1, softmax2, frame2, mask2, times, ys, xs, self.res,
+                                        self.centre_scale_host(), self.log_buffer, self.log_counter)
+            else:
+                flowtrainer.error_stash_composed(softmax1, frame1, mask1, softmax2, frame2, mask2, times, ys, xs, self.cells,
+                                                 self.log_buffer, self.log_counter)
+        ProgressiveEncoderController.stash_iteration(self)
 
     def reset_buffer_(self):
         self.log_buffer[:] = 0

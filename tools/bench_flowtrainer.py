@@ -11,6 +11,16 @@ Three paths run in alternating windows in one process:
     network   flow_fields forward + backward alone on the same grid, with a random upstream gradient: the share of the step that is
               the network
 A progressive net runs under LinearControllerEarly(net, 5000): the controller reads the loss on every step, as in the reference.
+
+    python tools/bench_flowtrainer.py --spatially-adaptive [--net PRBF] [--res 50]
+
+times the step under StashedSpatialController(net, res) instead (training_step, backward, on_after_backward, optimizer step;
+block_iterations is set beyond the run, so no window contains an update_progress), again in alternating windows:
+    spatial_fused      the stash is the fused error_stash (csrc/flowtrain.hip)
+    spatial_composed   the stash is its composed form (FlowTrainer.fused = False; the two other operators stay fused)
+    linear             the same network's step under LinearControllerEarly, the baseline
+    stash_fused / stash_composed   the stash alone, on the tensors of one step
+and reports the bytes per pixel the fused stash moves, counted from its definition.
 """
 import argparse
 import json
@@ -38,9 +48,13 @@ def main():
     ap.add_argument('--seconds', type=float, default=1.0)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--rounds', type=int, default=2)
+    ap.add_argument('--spatially-adaptive', action='store_true', help='time the step under StashedSpatialController: fused and composed stash')
+    ap.add_argument('--res', type=int, default=50, help='--spatially-adaptive: cells per axis of the mask grid')
     a = ap.parse_args()
     from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
     dev = torch.device('cuda', 0)
+    if a.spatially_adaptive:
+        return spatial(a, dev)
     torch.manual_seed(0)
     net = flownet.all_model_dict[a.net](flownet.ModelParams())
     if net.is_progressive:
@@ -80,6 +94,79 @@ def main():
         out[f'{k}_ms_windows'] = [round(m, 4) for m in meds]
     out['network_share'] = round(out['network_ms'] / out['fused_ms'], 3)
     out['fused_over_torch'] = round(out['fused_ms'] / out['torch_ms'], 4)
+    print(json.dumps(out))
+
+
+def spatial(a, dev):
+    from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
+    name = a.net if a.net != 'RBF' else 'PRBF'
+    clip = flowdata.SyntheticClip(a.frames, a.height, a.width)
+    assert a.batch <= len(clip)
+    batch = [clip.video[:a.batch].to(dev), clip.video[1:a.batch + 1].to(dev), clip.T[:a.batch].to(dev),
+             torch.tensor([clip.flow_scale] * a.batch, dtype=torch.float64).to(dev), clip.flow[:a.batch].to(dev)]
+
+    def trainer(controller):
+        torch.manual_seed(0)
+        net = flownet.all_model_dict[name](flownet.ModelParams()).to(dev)
+        if controller == 'spatial':
+            net = progressive.StashedSpatialController(net, a.res, block_iterations=1 << 30, epsilon=1e-3)
+        else:
+            net = progressive.LinearControllerEarly(net, 5000, epsilon=1e-3)
+        args = argparse.Namespace(lr=1e-4, loss_l1=1, loss_census=0.1, loss_ssim=a.loss_ssim, census_width=3, loss_smooth1=0.1,
+                                  edge_constant=150, edge_func='gauss', occl='wang', occl_thresh=0.7, net=net)
+        model = flowtrainer.FlowTrainer(args).to(dev)
+        return model, model.attach_optimizer()
+
+    models = {'spatial': trainer('spatial'), 'linear': trainer('linear')}
+
+    def step(which, fused):
+        model, opt = models[which]
+
+        def run():
+            model.fused = fused
+            opt.zero_grad()
+            model.training_step(batch, 0).backward()
+            model.on_after_backward()
+            opt.step()
+            model.fused = True
+        return run
+
+    # the stash alone, on the tensors of one step
+    model, _ = models['spatial']
+    model.training_step(batch, 0).backward()
+    six, model._stash = model._stash, None
+    net = model.net
+    grid = net._last_grid
+    logs = torch.zeros_like(net.log_buffer), torch.zeros_like(net.log_counter)
+    ws = torch.empty(flowtrainer._lib.lib().sininn_flow_error_stash_workspace_floats(a.batch, a.height, a.width, a.res), device=dev)
+
+    def stash_fused():
+        flowtrainer.error_stash(*six, *grid, a.res, net.centre_scale_host(), *logs, workspace=ws)
+
+    def stash_composed():
+        flowtrainer.error_stash_composed(*six, *grid, net.cells, *logs)
+
+    todo = {'spatial_fused': step('spatial', True), 'spatial_composed': step('spatial', False), 'linear': step('linear', True),
+            'stash_fused': stash_fused, 'stash_composed': stash_composed}
+    res = {k: [] for k in todo}
+    for _ in range(a.rounds):
+        for k, fn in todo.items():
+            res[k].append(window(fn, a.seconds, a.warmup))
+    points = a.batch * a.height * a.width
+    channels = six[0].shape[1]
+    # per pixel: two splats and two frames of C floats, two masks of their channel count, read once; plus the row sums R1 (res floats
+    # per row and tile, written once and read once) and, per call, the logs (read and written) and R2 -- a few floats per cell
+    per_pixel = 4 * (4 * channels + six[2].shape[1] + six[5].shape[1])
+    per_call = 4 * (2 * a.batch * a.height * ((a.width + 1023) // 1024) * a.res + 2 * a.batch * a.res ** 2 + 4 * a.res ** 3)
+    out = dict(mode='spatially-adaptive', net=name, res=a.res, batch=a.batch, height=a.height, width=a.width, loss_ssim=a.loss_ssim,
+               points=points, stash_bytes_per_pixel=per_pixel, stash_bytes_per_call=points * per_pixel + per_call)
+    for k in res:
+        meds = [w['median_ms'] for w in res[k]]
+        out[f'{k}_ms'] = round(min(meds), 4)
+        out[f'{k}_ms_windows'] = [round(m, 4) for m in meds]
+    out['stash_fused_over_composed'] = round(out['stash_fused_ms'] / out['stash_composed_ms'], 4)
+    out['stash_fused_gb_per_s'] = round(out['stash_bytes_per_call'] / out['stash_fused_ms'] / 1e6, 1)
+    out['spatial_over_linear'] = round(out['spatial_fused_ms'] / out['linear_ms'], 4)
     print(json.dumps(out))
 
 

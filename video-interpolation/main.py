@@ -9,8 +9,12 @@ Differences from the reference, all to make the path runnable here:
   * the trainer, checkpoint callback and logger come from `sin_inn_amd.lightning` (pytorch_lightning and wandb are not installed):
     `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
   * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
-  * `--net` takes the twelve networks of `sin_inn_amd.flownet`; `siren`, `MPFF` and `--spatially-adaptive` exit with a
-    message (flownet.py lists them as out of scope; the spatial controller itself is ported, the switch stays closed);
+  * `--net` takes the twelve networks of `sin_inn_amd.flownet`; `siren` and `MPFF` exit with a message (flownet.py lists them as
+    out of scope);
+  * `--spatially-adaptive` puts PRBF, PFF, PUFF, PRFF or PRBFG under `StashedSpatialController(net, 50, block_iterations)`; with any
+    other network it exits with a message.  The reference's own run of this switch fails at the first step (its trainer hands the
+    controller a scalar loss) and never calls `update_progress`; here the trainer stashes a per-point loss after every backward pass
+    and closes / opens cells every `block_iterations` steps (sin_inn_amd/flowtrainer.py);
   * `--ngpus N` is N devices (cuda:0 .. cuda:N-1, the first is used), as in Lightning, not a device index;
   * a video file as `--input-video` (imageio + RAFT) is refused;
   * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)` (PPE: `// 12`), which is 0 below 112 (4) epochs, and the
@@ -30,6 +34,7 @@ if ROOT not in sys.path:
 
 NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE')
 OUT_OF_SCOPE_NETWORKS = ('siren', 'MPFF')
+SPATIAL_NETWORKS = ('PRBF', 'PFF', 'PUFF', 'PRFF', 'PRBFG')    # the 515-wide progressive networks of NETWORKS: --spatially-adaptive
 
 
 def get_parser():
@@ -76,10 +81,10 @@ def get_args(argv=None):
     args = parser.parse_args(argv)
     if args.occl == 'None':                                    # argparse cannot produce the reference's `None` choice from a string
         args.occl = None
-    if args.spatially_adaptive:
-        parser.error('--spatially-adaptive is out of scope here: sin_inn_amd.progressive.StashedSpatialController and the spatial '
-                     'kernels exist (tools/fit_flow.py --controller spatial drives them), but the controller needs a per-point loss '
-                     'and this trainer, like the reference\'s, hands its controller a scalar')
+    if args.spatially_adaptive and args.net not in SPATIAL_NETWORKS:
+        parser.error(f'--spatially-adaptive with --net {args.net} is out of scope here: the per-point masks of '
+                     f'sin_inn_amd.progressive.StashedSpatialController are built for the 515-wide progressive networks '
+                     f'({", ".join(SPATIAL_NETWORKS)})')
     if args.net in OUT_OF_SCOPE_NETWORKS:
         parser.error(f'--net {args.net} is out of scope: the fused kernels are built for {", ".join(NETWORKS)} '
                      '(sin_inn_amd/flownet.py)')
@@ -88,13 +93,23 @@ def get_args(argv=None):
     return args
 
 
-def build_net(args):
+def build_net(args, res=50):
     """main.py:136-143: the network, and LinearControllerEarly around a progressive one.  `args.net` is the network's name on the
-    first call; main() replaces it with the module, as the reference does, and keeps the name in `args.net_name`."""
+    first call; main() replaces it with the module, as the reference does, and keeps the name in `args.net_name`.
+    With --spatially-adaptive: StashedSpatialController(net, res, block_iterations, epsilon=1e-3), built on the device the trainer
+    uses (its grid of masks is res^3 x 515 floats, 257 MB at the reference's res = 50; `res` is a keyword for callers and tests, not
+    an option).  `block_iterations = max(3 * epochs // (4 * 84), 1)` is the block length LinearControllerEarly gets for the same run,
+    so both switches open the spectrum over the same span of steps; the reference passes `args.epochs` here, a block that no run
+    finishes, and never advances."""
     from sin_inn_amd import flownet, progressive
     if isinstance(args.net, str):
         args.net_name = args.net
     net = flownet.all_model_dict[args.net_name](flownet.ModelParams())
+    if getattr(args, 'spatially_adaptive', False):
+        import torch
+        if torch.cuda.is_available():
+            net = net.to(torch.device('cuda', _devices(args)[0]))
+        return progressive.StashedSpatialController(net, res, block_iterations=max(3 * args.epochs // (4 * 84), 1), epsilon=1e-3)
     if net.is_progressive:
         net = progressive.LinearControllerEarly(net, args.epochs, epsilon=1e-3)
         if net.block_iterations == 0:                          # fewer than 112 epochs (PPE: 4): the reference divides by zero here
