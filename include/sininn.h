@@ -1005,6 +1005,30 @@ int64_t sininn_flow_synth_workspace(int B, int K, int C, int H, int W);
 int sininn_flow_synth(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
                       int H, int W, float* workspace, int64_t workspace_floats, float* out, unsigned char* out_u8, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Frame quality (csrc/framequality.hip): PSNR and mean SSIM of predicted frames against real ones.  pred, target: DEVICE
+ * (B, C, H, W) fp32, contiguous, C = 1 or 3, H, W >= 11.  Per frame b:
+ *   sqerr[b]      = sum_{c,y,x} (p - t)^2       difference and square rounded once each in fp32; the sum in double, in a fixed order
+ *   out[0][b] mse = sqerr / (C H W)             formed in double, rounded to fp32 once
+ *   out[1][b] psnr = 10 log10(1 / mse)          data range 1; +inf where mse == 0; formed on the device
+ *   out[2][b] ssim = the mean over channels and over the (H - 10)(W - 10) windows per channel ("valid": no padding) of
+ *       ((2 mu_p mu_t + C1)(2 s_pt + C2)) / ((mu_p^2 + mu_t^2 + C1)(s_p + s_t + C2)),   C1 = 0.01^2, C2 = 0.03^2   (Wang et al. 2004)
+ *     mu_p, mu_t, E[pp], E[tt], E[pt]: the moments under the 11 x 11 window w[i] w[j], filtered along x, then y, in fp32;
+ *     s_p = E[pp] - mu_p^2, s_t = E[tt] - mu_t^2, s_pt = E[pt] - mu_p mu_t.  Every operation of the formula is rounded once and none
+ *     is contracted, so a frame against itself gives exactly 1 in every window.  The mean is carried in double, in a fixed order.
+ * `window`: 11 HOST floats, w[i] = exp(-(i - 5)^2 / 4.5) / sum for the standard sigma = 1.5; passed to the kernel by value.
+ * ssim_map (may be NULL): DEVICE (B, C, H - 10, W - 10), the per-window values.  sqerr: DEVICE B doubles.  out: DEVICE 3 B floats.
+ * quantize != 0: both inputs first become bytes by sininn_flow_synth's out_u8 rule, byte = clamp(round-half-even(255 v), 0, 255)
+ * with the product 255 v rounded to fp32 and NaN giving 0; sqerr is then the integer sum of squared byte differences (exact in the
+ * double), mse = sqerr / (255^2 C H W), and SSIM is taken on byte / 255 rounded to fp32.
+ * `workspace`: DEVICE, 8-byte aligned, at least the count of floats the _workspace_floats call returns (0 for a shape the call
+ * refuses); one partial per block, so it needs no initialisation.  Two launches, no atomics: two calls on equal inputs give equal
+ * bits, and a frame's results do not depend on B or on its place in the batch.  B C H W <= 2^31 - 1.  The call reads no device
+ * memory on the host.  Not differentiable. */
+int64_t sininn_frame_quality_workspace_floats(int B, int C, int H, int W);
+int sininn_frame_quality(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
+                         float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -325,6 +325,9 @@ _SIGS = {
     'sininn_flow_synth_workspace': (C.c_int64, [C.c_int] * 5),
     'sininn_flow_synth': (C.c_int, [c_f, c_f, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f, C.c_int64, c_f,
                                     C.c_void_p, C.c_void_p]),
+    'sininn_frame_quality_workspace_floats': (C.c_int64, [C.c_int] * 4),
+    'sininn_frame_quality': (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), c_f, C.c_int64,
+                                       C.c_void_p, c_f, c_f, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -151,6 +151,9 @@ int flow2img_launch(const float* flow, int n, int h, int w, float clip, const do
 int64_t flow_synth_workspace(int B, int K, int C, int H, int W);
 int flow_synth_launch(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
                       int H, int W, float* workspace, int64_t workspace_floats, float* out, uint8_t* out_u8, hipStream_t st);
+int64_t frame_quality_workspace_floats(int B, int C, int H, int W);
+int frame_quality_launch(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
+                         float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -651,6 +654,13 @@ int64_t sininn_flow_synth_workspace(int B, int K, int C, int H, int W) { return 
 int sininn_flow_synth(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
                       int H, int W, float* workspace, int64_t workspace_floats, float* out, unsigned char* out_u8, void* stream) {
   return flow_synth_launch(i0, i1, f01, f10, tau, B, K, C, H, W, workspace, workspace_floats, out, out_u8, ST(stream));
+}
+
+int64_t sininn_frame_quality_workspace_floats(int B, int C, int H, int W) { return frame_quality_workspace_floats(B, C, H, W); }
+int sininn_frame_quality(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
+                         float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, void* stream) {
+  return frame_quality_launch(pred, target, B, C, H, W, quantize, window, workspace, workspace_floats, sqerr, out, ssim_map,
+                              ST(stream));
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@ clip with analytic ground truth, and the data module that hands them to the trai
     BaseMedia / Images         video-interpolation/data.py:10-18, 67-89
     LightningLoader / get_video   video-interpolation/data.py:92-119   (num_workers=0: the clips are resident tensors)
     SyntheticClip              this project's; generalises tools/fit_flow.make_pair to a clip
+    Holdout                    this project's; every step-th frame of a clip, the frames between them kept back for scoring
 
 Everything here runs on the host; the trainer moves batches to the device.
 
@@ -169,6 +170,55 @@ class SyntheticClip(BaseMedia):
         self.flow_scale = w / 5
 
 
+class Holdout(BaseMedia):
+    """Every `step`-th frame of `base` (an `Images` or a `SyntheticClip`) as a clip of its own, the frames between them held out: fit
+    on this, synthesize the held-out frames, compare them with the real ones (`FlowTrainer.holdout_quality`).
+
+    The kept frames are base.video[::step], kept = (len - 1) // step + 1 of them, at the times linspace(-1, 1, kept); item i is the
+    pair (kept i, kept i + 1) as in `BaseMedia`, with the base's `flow_scale` and no ground-truth flow (`gt_available = False`: the
+    base's flows join neighbouring frames, not kept ones).  `held(i)` is the `step - 1` real frames between the two and the times
+    tau_j = j / step at which they sit.  The (len - 1) % step frames after the last kept one are dropped (`dropped`)."""
+
+    def __init__(self, base, step):
+        super().__init__()
+        step = int(step)
+        if step < 2:
+            raise ValueError(f'Holdout: step = {step}; at least every 2nd frame is kept')
+        frames = base.video.size(0)
+        if frames < step + 1:
+            raise ValueError(f'Holdout: a clip of {frames} frames is too short for step {step}: it needs at least {step + 1}')
+        self.base, self.step = base, step
+        self.kept_indices = list(range(0, frames, step))
+        self.dropped = (frames - 1) % step
+        self.video = base.video[::step]
+        self.T = torch.linspace(-1, 1, self.video.size(0))
+        self.flow_scale = base.flow_scale
+        self.gt_available = False
+
+    def held(self, i):
+        """(frames (step - 1, C, H, W), taus (step - 1,)) between kept frames i and i + 1"""
+        if not 0 <= i < len(self):
+            raise IndexError(f'Holdout.held: pair {i} of {len(self)}')
+        first = self.kept_indices[i]
+        taus = torch.arange(1, self.step, dtype=torch.float32) / self.step
+        return self.base.video[first + 1:first + self.step], taus
+
+    def with_held(self):
+        """the data set the validation step reads: item i = (kept i, kept i + 1, time, flow scale, held frames, taus)"""
+        return _HoldoutPairs(self)
+
+
+class _HoldoutPairs(data.Dataset):
+    def __init__(self, holdout):
+        self.holdout = holdout
+
+    def __len__(self):
+        return len(self.holdout)
+
+    def __getitem__(self, index):
+        return tuple(self.holdout[index]) + tuple(self.holdout.held(index))
+
+
 class LightningLoader(LightningDataModule):
     """data.py:92-104, with num_workers=0."""
 
@@ -189,9 +239,16 @@ class LightningLoader(LightningDataModule):
         return data.DataLoader(self.testset, batch_size=self.test_batch, num_workers=0)
 
 
+class HoldoutLoader(LightningLoader):
+    """LightningLoader over two `Holdout` sets: training and testing see the kept pairs, validation also the held-out frames"""
+
+    def val_dataloader(self):
+        return data.DataLoader(self.testset.with_held(), batch_size=self.test_batch, num_workers=0)
+
+
 def get_video(input_video, args):
     """data.py:107-119: (data module, scene name).  `args.synthetic = (frames, h, w)` selects a SyntheticClip, scene 'synthetic';
-    a file (the reference's VideoClip) is refused."""
+    a file (the reference's VideoClip) is refused.  `args.holdout = S` (main.py --holdout) wraps both sets in `Holdout(.., S)`."""
     synthetic = getattr(args, 'synthetic', None)
     if synthetic:
         frames, h, w = synthetic
@@ -205,4 +262,11 @@ def get_video(input_video, args):
         raise NotImplementedError(f'{input_video}: not a folder of frames; video files (VideoClip: imageio + RAFT) are out of scope')
     if trainset.gt_available:
         print(f'Max flow: {trainset.flow.max().item()}, estimated scale: {trainset.flow_scale}')
+    holdout = getattr(args, 'holdout', None)
+    if holdout:
+        trainset = Holdout(trainset, holdout)
+        testset = trainset if testset is trainset.base else Holdout(testset, holdout)
+        print(f'Holdout: every {holdout}. frame kept, {len(trainset.kept_indices)} of {trainset.base.video.size(0)}; '
+              f'{trainset.dropped} trailing frames dropped')
+        return HoldoutLoader(trainset, testset, args.batch, args.test_batch), scene
     return LightningLoader(trainset, testset, args.batch, args.test_batch), scene

@@ -14,8 +14,21 @@ The definition, for frames I0, I1 (B, C, H, W), flows F01, F10 (B, 2, H, W) in p
 
 -0.0 counts as zero.  Resample2d divides by (W - 1, H - 1): on an axis of length 1 its sampling coordinate is infinite, the sample
 lies outside the frame and the warped value is 0 there.  The operator is for inference and has no gradient.
+
+    quality(pred, target)            PSNR and mean SSIM per frame, the fused operator of csrc/framequality.hip
+    quality_composed(pred, target)   the same definition from torch ops, on any device, fp32 or fp64: its A/B partner and reference
+
+For frames p, t (B, C, H, W) with values in [0, 1] (data range 1):
+
+    mse = mean (p - t)^2,   psnr = 10 log10(1 / mse)  (+inf where mse == 0)
+    ssim = the mean over channels and all valid 11 x 11 windows of ((2 mu_p mu_t + C1)(2 s_pt + C2)) / ((mu_p^2 + mu_t^2 + C1)(s_p + s_t + C2))
+
+with the Gaussian window of sigma 1.5, C1 = 0.01^2, C2 = 0.03^2 (Wang et al. 2004).  `quantize=True` measures the frames as the bytes a
+PNG holds: both inputs go through `synthesize`'s u8 rule first, clamp(round-half-even(255 v), 0, 255).
 """
+import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -138,3 +151,105 @@ def composed(frame1, frame2, flow12, flow21, taus):
         frame1, frame2 = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous()
         flow12, flow21 = _gpu32(flow12).contiguous(), _gpu32(flow21).contiguous()
         return compose_from(frame1, frame2, flow12, flow21, values, metric, _FunctionSoftsplat.apply)
+
+
+# ---- frame quality ----
+
+Quality = collections.namedtuple('Quality', 'psnr ssim mse map')
+WINDOW, SIGMA = 11, 1.5
+SSIM_C1, SSIM_C2 = 0.01 ** 2, 0.03 ** 2
+
+
+def gaussian_window(size=WINDOW, sigma=SIGMA):
+    """the normalised 1-D window as Python floats (double): g_i = exp(-(i - size // 2)^2 / (2 sigma^2)) / sum"""
+    g = [math.exp(-(i - size // 2) ** 2 / (2 * sigma * sigma)) for i in range(size)]
+    total = math.fsum(g)
+    return [v / total for v in g]
+
+
+_WINDOW32 = (C.c_float * WINDOW)(*gaussian_window())
+
+
+def quality_workspace_floats(b, c, h, w):
+    return int(_lib.lib().sininn_frame_quality_workspace_floats(b, c, h, w))
+
+
+def _quality_inputs(who, pred, target):
+    for t in (pred, target):
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
+                               '(or call it under torch.no_grad())')
+    assert pred.shape == target.shape, f'flowsynth.{who}: pred and target differ in shape'
+    assert pred.dim() in (4, 5), f'flowsynth.{who}: frames are (B, C, H, W) or (B, K, C, H, W)'
+    lead = tuple(pred.shape[:-3])
+    c, h, w = pred.shape[-3:]
+    if c not in (1, 3):
+        raise ValueError(f'flowsynth.{who}: frames have 1 or 3 channels (got {c})')
+    if h < WINDOW or w < WINDOW:
+        raise ValueError(f'flowsynth.{who}: frames of {h} x {w} are smaller than the {WINDOW} x {WINDOW} window')
+    return lead, c, h, w
+
+
+def quality(pred, target, *, quantize=False, ssim_map=False, workspace=None):
+    """PSNR, mean SSIM and MSE of `pred` against `target`, per frame: a `Quality(psnr, ssim, mse, map)` of fp32 device tensors shaped
+    like the leading dimensions, (B,) for (B, C, H, W) frames and (B, K) for (B, K, C, H, W); `map` is None, or with `ssim_map=True`
+    the per-window SSIM, (..., C, H - 10, W - 10).  `quantize=True`: on the bytes of both frames (see the module text).  `workspace`:
+    an fp32 device buffer of at least `quality_workspace_floats(B, C, H, W)` values for the flattened batch (allocated here otherwise;
+    needs no initialisation).  Two launches, no atomics, nothing read back: equal inputs give equal bits.  No gradient."""
+    lead, c, h, w = _quality_inputs('quality', pred, target)
+    pred = _gpu32(pred).reshape(-1, c, h, w).contiguous()
+    target = _gpu32(target).reshape(-1, c, h, w).contiguous()
+    b, dev = pred.shape[0], pred.device
+    need = quality_workspace_floats(b, c, h, w)
+    if workspace is None:
+        workspace = torch.empty(max(need, 2), device=dev, dtype=torch.float32)
+    assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous(), 'workspace: contiguous fp32 on the device'
+    sqerr = torch.empty(max(b, 1), device=dev, dtype=torch.float64)
+    out = torch.empty((3, b), device=dev, dtype=torch.float32)
+    smap = torch.empty((b, c, h - WINDOW + 1, w - WINDOW + 1), device=dev, dtype=torch.float32) if ssim_map else None
+    check(_lib.lib().sininn_frame_quality(ptr(pred), ptr(target), b, c, h, w, int(bool(quantize)), _WINDOW32, ptr(workspace),
+                                          workspace.numel(), C.c_void_p(sqerr.data_ptr()), ptr(out), ptr(smap), _stream()))
+    if smap is not None:
+        smap = smap.reshape(*lead, *smap.shape[1:])
+    return Quality(out[1].reshape(lead), out[2].reshape(lead), out[0].reshape(lead), smap)
+
+
+def to_bytes(x):
+    """`synthesize`'s u8 rule as a float tensor of byte values, in the dtype of x: clamp(round-half-even(255 x), 0, 255)"""
+    return (x * 255).round().clamp(0, 255)
+
+
+def quality_composed(pred, target, *, quantize=False, ssim_map=False):
+    """`quality` from torch ops, in the dtype and on the device of the inputs (CPU or GPU, fp32 or fp64): per moment two `conv2d` with
+    the 1-D Gaussian, along x then along y.  With fp64 inputs it is the reference; in fp32 it rounds where the fused operator rounds,
+    except inside the two filters, whose order of accumulation is the library's.  The sums over a frame are carried in float64."""
+    lead, c, h, w = _quality_inputs('quality_composed', pred, target)
+    with torch.no_grad():
+        p = pred.detach().reshape(-1, 1, h, w)
+        t = target.detach().reshape(-1, 1, h, w)
+        assert p.dtype == t.dtype and p.dtype in (torch.float32, torch.float64), 'quality_composed: fp32 or fp64 frames of one dtype'
+        n = c * h * w
+        if quantize:
+            bp, bt = to_bytes(p), to_bytes(t)
+            sqerr = ((bp - bt) ** 2).to(torch.float64).reshape(-1, n).sum(1)        # integers: exact
+            mse = sqerr / (65025.0 * n)
+            p, t = bp / 255, bt / 255
+        else:
+            d = p - t
+            sqerr = (d * d).to(torch.float64).reshape(-1, n).sum(1)
+            mse = sqerr / n
+        psnr = torch.where(mse == 0, torch.full_like(mse, math.inf), 10 * torch.log10(1 / mse))
+        g = torch.tensor(gaussian_window(), dtype=p.dtype, device=p.device)
+        gx, gy = g.view(1, 1, 1, WINDOW), g.view(1, 1, WINDOW, 1)
+
+        def filt(x):
+            return torch.nn.functional.conv2d(torch.nn.functional.conv2d(x, gx), gy)
+
+        mp, mt = filt(p), filt(t)
+        mpp, mtt, mpt = mp * mp, mt * mt, mp * mt
+        s_p, s_t, s_pt = filt(p * p) - mpp, filt(t * t) - mtt, filt(p * t) - mpt
+        smap = ((2 * mpt + SSIM_C1) * (2 * s_pt + SSIM_C2)) / ((mpp + mtt + SSIM_C1) * (s_p + s_t + SSIM_C2))
+        smap = smap.reshape(*lead, c, h - WINDOW + 1, w - WINDOW + 1)
+        ssim = smap.to(torch.float64).flatten(-3).mean(-1)
+        dt = pred.dtype
+        return Quality(psnr.to(dt).reshape(lead), ssim.to(dt).reshape(lead), mse.to(dt).reshape(lead), smap if ssim_map else None)

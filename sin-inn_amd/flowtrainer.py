@@ -341,10 +341,18 @@ class FlowTrainer(LightningModule):
         self.completed_training = True
 
     def validation_step(self, batch, batch_idx):
-        """trainer.py:93-98"""
+        """trainer.py:93-98.  Under `flowdata.Holdout` (a batch of six: the pair, the held-out frames and their times) there is no
+        ground-truth flow: `val/PSNR` and `val/SSIM`, the means over the held-out frames, are logged in place of `val/EPE`."""
         frame1, _, times, scale = batch[:4]
         if batch_idx == 0:
             self._new_epoch('val/')
+        if len(batch) == 6:
+            held, taus = batch[4], batch[5][0]
+            net = self.holdout_quality(batch, held, taus)['net']
+            count = held.shape[0] * held.shape[1]
+            self.log('val/PSNR', net.psnr.mean(), on_step=False, on_epoch=True, batch_size=count)
+            self.log('val/SSIM', net.ssim.mean(), on_step=False, on_epoch=True, batch_size=count)
+            return
         flow_fw, _ = self.forward(frame1, times, scale)
         self.log('val/EPE', self._epe(flow_fw, batch[4]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])
 
@@ -388,6 +396,24 @@ class FlowTrainer(LightningModule):
                 return flowsynth.synthesize(frame1, frame2, flow12, flow21, taus, **kw)
         finally:
             self.net.train(was_training)
+
+    def holdout_quality(self, batch, held, taus, quantize=True, frames=None):
+        """Score the frames synthesized at `taus` between the pair of `batch` against the real frames `held` (n, K, 3, h, w): a dict of
+        `flowsynth.Quality`, each entry (n, K) -- 'net': `interpolate(batch, taus)`; and, through the same operator, the two
+        baselines that use no flow, 'blend': (1 - tau) frame1 + tau frame2, and 'repeat': the nearer source frame (frame1 up to
+        tau = 0.5).  `quantize=True` measures all three as bytes, as the written PNGs hold them.  `frames`: what `interpolate(batch, taus)`
+        returned, for a caller that has it already (the splat adds with atomics: a second call may differ in the last bits)."""
+        from . import flowsynth
+        frame1, frame2 = batch[0], batch[1]
+        values = flowsynth._host_taus(taus)
+        with torch.no_grad():
+            net = self.interpolate(batch, values) if frames is None else frames
+            tau = torch.tensor(values, dtype=frame1.dtype, device=frame1.device).view(1, -1, 1, 1, 1)
+            blend = (1 - tau) * frame1[:, None] + tau * frame2[:, None]
+            repeat = torch.where(tau <= 0.5, frame1[:, None], frame2[:, None])
+            held = held.to(frame1.device)
+            return {name: flowsynth.quality(frames, held, quantize=quantize)
+                    for name, frames in (('net', net), ('blend', blend), ('repeat', repeat))}
 
     def configure_optimizers(self):
         return FusedLAMB(self.net.parameters(), lr=self.lr)

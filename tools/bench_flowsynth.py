@@ -7,6 +7,11 @@ after a warm-up; one JSON line per K, appended to profiles/flowsynth_bench.jsonl
 K = factor - 1 times per call (tau = j / factor), and K = 1 (tau = 1 / 2) beside it.  The inputs are a SyntheticClip pair and its
 ground-truth flows (the backward flow: the negative of the forward one): smooth flows of a few pixels, what a fitted network gives.
 `*_bytes_per_frame` count the HBM traffic of one output frame from the definition, not from counters.
+
+    python tools/bench_flowsynth.py --quality [--baseline]
+
+times `flowsynth.quality` (csrc/framequality.hip) against `flowsynth.quality_composed` on batch x 7 frames, float and
+quantised mode, one line each.  `min_bytes` is both frames read once; `fused_tb_per_s` is that count over the fused time.
 """
 import argparse
 import json
@@ -32,6 +37,40 @@ def bytes_per_frame(k):
     return 4 * (16 / k + 35), 4 * (66 / k + 148)
 
 
+def quality_lines(a, dev):
+    from sin_inn_amd import flowdata, flowsynth
+    k = 7
+    yy, xx = torch.meshgrid(torch.arange(a.height, dtype=torch.float32), torch.arange(a.width, dtype=torch.float32), indexing='ij')
+    target = torch.stack([flowdata.texture(xx - 0.37 * n, yy + 0.21 * n, 0) for n in range(a.batch * k)]).clamp(0, 1)
+    pred = torch.stack([flowdata.texture(xx - 0.37 * n + 0.25, yy + 0.21 * n - 0.15, 0) for n in range(a.batch * k)]).clamp(0, 1)
+    target, pred = (t.view(a.batch, k, 3, a.height, a.width).to(dev) for t in (target, pred))
+    ws = torch.empty(flowsynth.quality_workspace_floats(a.batch * k, 3, a.height, a.width), device=dev)
+    lines = []
+    for quantize in (False, True):
+        todo = {'fused': lambda: flowsynth.quality(pred, target, quantize=quantize, workspace=ws)}
+        if a.baseline:
+            todo['composed'] = lambda: flowsynth.quality_composed(pred, target, quantize=quantize)
+        res = {name: [] for name in todo}
+        for _ in range(a.rounds):
+            for name, fn in todo.items():
+                res[name].append(window(fn, a.seconds, a.warmup))
+        min_bytes = 2 * 4 * pred.numel()
+        line = dict(op='frame_quality', height=a.height, width=a.width, batch=a.batch, K=k, quantize=quantize, min_bytes=min_bytes,
+                    workspace_bytes=ws.numel() * 4)
+        for name in res:
+            meds = [w['median_ms'] for w in res[name]]
+            line[f'{name}_ms'] = round(min(meds), 4)
+            line[f'{name}_ms_windows'] = [round(m, 4) for m in meds]
+        line['fused_tb_per_s'] = round(min_bytes / (line['fused_ms'] * 1e-3) / 1e12, 3)
+        if a.baseline:
+            line['speedup'] = round(line['composed_ms'] / line['fused_ms'], 3)
+            f, c = flowsynth.quality(pred, target, quantize=quantize), flowsynth.quality_composed(pred, target, quantize=quantize)
+            line['max_abs_ssim_diff'] = float((f.ssim - c.ssim).abs().max())
+            line['max_rel_mse_diff'] = float(((f.mse - c.mse).abs() / c.mse).max())
+        lines.append(line)
+    return lines
+
+
 def main():
     from sin_inn_amd import flowdata, flowsynth
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
@@ -44,9 +83,19 @@ def main():
     ap.add_argument('--rounds', type=int, default=3, help='alternations of the fused and the composed windows')
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--log', action='store_true', help='append the lines to profiles/flowsynth_bench.jsonl')
+    ap.add_argument('--quality', action='store_true', help='time flowsynth.quality (and with --baseline quality_composed) instead')
     a = ap.parse_args()
     assert 2 <= a.factor <= 65
     dev = torch.device('cuda', 0)
+    if a.quality:
+        lines = quality_lines(a, dev)
+        for line in lines:
+            print(json.dumps(line))
+        if a.log:
+            with open(os.path.join(ROOT, 'profiles', 'flowsynth_bench.jsonl'), 'a') as f:
+                for line in lines:
+                    f.write(json.dumps(line) + '\n')
+        return
     clip = flowdata.SyntheticClip(a.batch + 1, a.height, a.width)
     i0, i1 = clip.video[:-1].contiguous().to(dev), clip.video[1:].contiguous().to(dev)
     f01 = clip.flow.contiguous().to(dev)

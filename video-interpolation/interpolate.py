@@ -2,6 +2,7 @@
 
     python video-interpolation/interpolate.py --input-video <sintel scene folder> --name NAME --net PRBF --factor 8
     python video-interpolation/interpolate.py --synthetic 4 24 40 --name smoke --net RBF --fit-epochs 2 --factor 3 --out frames
+    python video-interpolation/interpolate.py --synthetic 9 24 40 --name smoke --net RBF --fit-epochs 2 --holdout 2
 
 The network is the one `main.py train --name NAME --net NET` fitted to the clip: the newest checkpoint under
 checkpoints/<scene>/<NAME> is loaded as `main.py test` loads it (same folder, same tie-break).  For pair i of the clip and
@@ -16,6 +17,11 @@ source frame is written as frame_<T:04d>_00.png.
   --out DIR        where the PNGs go (default results/interp_<scene>_<name>_x<factor>)
   --gif            also results/interp_<scene>_<name>_x<factor>.gif
   --fit-epochs N   train N epochs first through FlowTrainer (default 0: a checkpoint must exist); with it no checkpoint is read
+  --holdout S      score the network: keep every S-th frame of the clip (the network is the one fitted with `main.py --holdout S`, or
+                   is fitted here on the kept frames), synthesize the S - 1 frames between every kept pair (--factor becomes S) and
+                   compare them with the real ones by PSNR and SSIM, on the bytes the PNGs hold.  <out>/quality.jsonl gets one line
+                   per held-out frame (pair, j, tau, then psnr, ssim and mse of the network, of the linear blend of the two kept frames
+                   and of the nearer kept frame repeated) and a last line with the means, which are also printed as a table
 """
 import argparse
 import importlib.util
@@ -43,18 +49,27 @@ def get_parser():
     src.add_argument('--synthetic', nargs=3, type=int, metavar=('T', 'H', 'W'), help='a SyntheticClip of T frames of H x W')
     ap.add_argument('--name', required=True, help='the run whose newest checkpoint is loaded')
     ap.add_argument('--net', required=True, help='the network of that run (main.py --net)')
-    ap.add_argument('--factor', type=int, default=2, help='time steps per pair: factor - 1 new frames between two source frames')
+    ap.add_argument('--factor', type=int, help='time steps per pair: factor - 1 new frames between two source frames (default 2)')
     ap.add_argument('--size', type=int, default=436, help='--input-video: the shorter side of the frames')
     ap.add_argument('--out', help='folder of the PNGs (default results/interp_<scene>_<name>_x<factor>)')
     ap.add_argument('--gif', action='store_true', help='also write results/interp_<scene>_<name>_x<factor>.gif')
     ap.add_argument('--fit-epochs', type=int, default=0, metavar='N', help='train N epochs first instead of loading a checkpoint')
     ap.add_argument('--batch', type=int, default=1, help='pairs per call')
+    ap.add_argument('--holdout', type=int, metavar='S', help='keep every S-th frame and score the synthesis of the others; sets --factor')
     return ap
 
 
 def get_args(argv=None):
     ap = get_parser()
     a = ap.parse_args(argv)
+    if a.holdout is not None:
+        if a.holdout < 2:
+            ap.error('--holdout S: S >= 2 (every S-th frame is kept)')
+        if a.factor is not None and a.factor != a.holdout:
+            ap.error(f'--factor {a.factor} and --holdout {a.holdout} disagree: --holdout S sets the factor to S')
+        a.factor = a.holdout
+    elif a.factor is None:
+        a.factor = 2
     if a.factor < 1 or a.factor > 65:
         ap.error('--factor: 1 .. 65 (one call synthesizes factor - 1 <= 64 times)')
     if a.fit_epochs < 0 or a.batch < 1:
@@ -75,6 +90,8 @@ def trainer_args(a):
     argv = ['test', '--name', a.name, '--net', a.net, '--size', str(a.size), '--test-size', str(a.size), '--test-batch', str(a.batch),
             '--epochs', str(max(a.fit_epochs, 1))]
     argv += ['--synthetic', *map(str, a.synthetic)] if a.synthetic else ['--input-video', a.input_video]
+    if a.holdout:
+        argv += ['--holdout', str(a.holdout)]
     args = m.get_args(argv)
     args.net = m.build_net(args)
     return m, args
@@ -102,8 +119,43 @@ def _to_device(batch, device):
     return [t.to(device) if torch.is_tensor(t) else t for t in batch]
 
 
+METHODS = ('net', 'blend', 'repeat')
+
+
+def quality_records(scores, first):
+    """one record per held-out frame of a batch: `scores` is `FlowTrainer.holdout_quality`'s dict of (n, K) results, `first` the
+    index of the batch's first pair"""
+    host = {m: (scores[m].psnr.cpu().tolist(), scores[m].ssim.cpu().tolist(), scores[m].mse.cpu().tolist()) for m in METHODS}
+    n, k = len(host['net'][0]), len(host['net'][0][0])
+    records = []
+    for i in range(n):
+        for j in range(k):
+            rec = {'pair': first + i, 'j': j + 1, 'tau': (j + 1) / (k + 1)}
+            for m in METHODS:
+                rec[f'psnr_{m}'], rec[f'ssim_{m}'], rec[f'mse_{m}'] = host[m][0][i][j], host[m][1][i][j], host[m][2][i][j]
+            records.append(rec)
+    return records
+
+
+def quality_means(records):
+    """the last line of quality.jsonl: the means over the held-out frames (an infinite PSNR makes its mean infinite)"""
+    out = {'mean': True, 'frames': len(records)}
+    for m in METHODS:
+        for what in ('psnr', 'ssim', 'mse'):
+            out[f'{what}_{m}'] = sum(r[f'{what}_{m}'] for r in records) / len(records)
+    return out
+
+
+def quality_table(means):
+    names = {'net': 'network', 'blend': 'linear blend', 'repeat': 'nearer frame'}
+    lines = [f'{"":14s}{"PSNR / dB":>10s}{"SSIM":>9s}']
+    lines += [f'{names[m]:14s}{means["psnr_" + m]:10.3f}{means["ssim_" + m]:9.5f}' for m in METHODS]
+    return '\n'.join(lines)
+
+
 def main(argv=None):
     a = get_args(argv)
+    import json
     import numpy as np
     import torch
     from PIL import Image
@@ -118,10 +170,15 @@ def main(argv=None):
     taus = [j / a.factor for j in range(1, a.factor)]
     source = (clip * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).numpy()         # (T, h, w, 3)
     between = {}                                                   # (pair, j) -> (h, w, 3) bytes
+    records = []
     if taus:
         first = 0
         for batch in video.test_dataloader():
-            _, u8 = model.interpolate(_to_device(batch, device), taus, u8=True)
+            batch = _to_device(batch, device)
+            frames, u8 = model.interpolate(batch, taus, u8=True)
+            if a.holdout:
+                held = torch.stack([video.testset.held(first + n)[0] for n in range(batch[0].shape[0])])
+                records += quality_records(model.holdout_quality(batch, held, taus, frames=frames), first)
             u8 = u8.permute(0, 1, 3, 4, 2).cpu().numpy()           # (n, K, h, w, 3)
             for n in range(u8.shape[0]):
                 for j in range(1, a.factor):
@@ -135,6 +192,12 @@ def main(argv=None):
     if a.gif:
         os.makedirs('results', exist_ok=True)
         save_gif(path.join('results', f'{tag}.gif'), np.stack(written), fps=4 * a.factor)
+    if a.holdout:
+        means = quality_means(records)
+        with open(path.join(out_dir, 'quality.jsonl'), 'w') as f:
+            for rec in records + [means]:
+                f.write(json.dumps(rec) + '\n')
+        print(quality_table(means))
     print(f'{len(written)} frames of {clip.shape[-2]} x {clip.shape[-1]} in {out_dir} ({num_frames} source frames, x{a.factor})')
 
 

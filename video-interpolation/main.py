@@ -9,6 +9,9 @@ Differences from the reference, all to make the path runnable here:
   * the trainer, checkpoint callback and logger come from `sin_inn_amd.lightning` (pytorch_lightning and wandb are not installed):
     `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
   * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
+  * `--holdout S` fits (train) or evaluates (test) on every S-th frame of the clip only (`sin_inn_amd.flowdata.Holdout`); validation
+    then logs `val/PSNR` and `val/SSIM` of the synthesized held-out frames in place of `val/EPE`; the attribute exists only when
+    the flag is given;
   * `--net` takes the twelve networks of `sin_inn_amd.flownet`; `siren` and `MPFF` exit with a message (flownet.py lists them as
     out of scope);
   * `--spatially-adaptive` puts PRBF, PFF, PUFF, PRFF or PRBFG under `StashedSpatialController(net, 50, block_iterations)`; with any
@@ -52,6 +55,8 @@ def get_parser():
     parser.add_argument('--test-batch', default=1, type=int)
     parser.add_argument('--synthetic', nargs=3, type=int, metavar=('T', 'H', 'W'),
                         help='train / test on a synthetic clip of T frames of H x W instead of --input-video')
+    parser.add_argument('--holdout', type=int, metavar='S', default=argparse.SUPPRESS,
+                        help='keep every S-th frame, hold the others out and score their synthesis (val/PSNR, val/SSIM)')
     # Network options
     parser.add_argument('--net', default='RBF')
     parser.add_argument('--spatially-adaptive', action='store_true')
@@ -81,6 +86,8 @@ def get_args(argv=None):
     args = parser.parse_args(argv)
     if args.occl == 'None':                                    # argparse cannot produce the reference's `None` choice from a string
         args.occl = None
+    if getattr(args, 'holdout', 2) < 2:
+        parser.error('--holdout S: S >= 2 (every S-th frame is kept)')
     if args.spatially_adaptive and args.net not in SPATIAL_NETWORKS:
         parser.error(f'--spatially-adaptive with --net {args.net} is out of scope here: the per-point masks of '
                      f'sin_inn_amd.progressive.StashedSpatialController are built for the 515-wide progressive networks '
