@@ -36,6 +36,15 @@ __device__ __forceinline__ WarpTaps warp_taps(int x, int y, float fx, float fy, 
   return t;
 }
 
+// Landing coordinate p + fl(t * f): the flow is scaled, rounded, then added to the pixel -- the same two roundings as splatting the
+// tensor t * F.  hipcc's __fmul_rn is a plain product, which -ffp-contract=fast fuses into the add that follows (one rounding, a
+// coordinate one ulp off the definition's); the pragma is what keeps the two apart.
+__device__ __forceinline__ float landing(int p, float t, float f) {
+#pragma clang fp contract(off)
+  const float scaled = t * f;
+  return (float)p + scaled;
+}
+
 // One lane per source pixel (b, y, x) of one source frame (side 0: I0 along F01, side 1: I1 along F10).
 // acc[B][K][2][C + 1][H][W], zeroed by the caller: channels 0..C-1 the splatted I * exp(Z), channel C the splatted exp(Z).
 template <int C>
@@ -86,8 +95,7 @@ __global__ __launch_bounds__(FS_TX * FS_TY) void flowsynth_scatter_kernel(const 
       SplatTaps tp = {};
       bool any = false;
       if (live) {
-        // the flow is scaled, rounded, then added to the pixel: the same two roundings as splatting the tensor t * F
-        const float ox = (float)x + __fmul_rn(t, fx), oy = (float)y + __fmul_rn(t, fy);
+        const float ox = landing(x, t, fx), oy = landing(y, t, fy);
         if (ox == ox && oy == oy && fabsf(ox) < 1e9f && fabsf(oy) < 1e9f) { tp = splat_taps(ox, oy, H, W); any = true; }
       }
       // Neighbouring sources of a smooth flow share taps (splat_fwd_kernel): the south taps of a pixel are the north taps of the
