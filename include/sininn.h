@@ -1029,6 +1029,28 @@ int64_t sininn_frame_quality_workspace_floats(int B, int C, int H, int W);
 int sininn_frame_quality(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
                          float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Frame synthesis by gathering (csrc/flowgather.hip): the flows are taken at the in-between time, on the grid of the frame
+ * being synthesized, and both source frames are read through a backward warp.  i0, i1: DEVICE (B, C, H, W) fp32, contiguous, C = 1 or 3.
+ * flows: DEVICE (T', 4, H, W) fp32 read in place: time slice t starts at flows + t * flow_sample_stride (floats, >= 4 H W) and its four
+ * channel planes are contiguous; channels 0..1 the forward flow (x, y), 2..3 the backward one, in pixels.  slots: DEVICE (B, K, 6)
+ * int32, per output frame idx0, idx1 (the time slices of G0, G1), ch0, ch1 (0 or 2, their first channel) and the bit patterns of the
+ * floats c0, c1.  tau: DEVICE K floats in [0, 1].  out: DEVICE (B, K, C, H, W); out_u8 (may be NULL): the same layout in bytes,
+ * clamp(round-half-even(255 out), 0, 255).  Per output pixel p = (x, y), every operation rounded once and none contracted:
+ *   q0 = p + c0 G0(p), q1 = p + c1 G1(p)                 the product is rounded, then the sum
+ *   (W0, n0) = sample(i0, q0), (W1, n1) = sample(i1, q1) bilinear with pixel centres at integers; a tap outside the frame adds 0 to W
+ *                                                        and to n, the sum of the weights inside; a coordinate that is not finite or
+ *                                                        is 1e9 or more in size has no tap inside
+ *   a0 = 1 - tau, a1 = tau, L = a0 i0(p) + a1 i1(p)
+ *   out = (a0 W0 + a1 W1 + e L) / (a0 n0 + a1 n1 + e),   e = 2^-10
+ * The slot table is NOT validated on the device: the caller guarantees 0 <= idx < T' and ch in {0, 2}.  k_loop != 0: a lane walks the
+ * K times of its pixel and loads i0(p), i1(p) once; 0: one lane per (b, k, y, x).  Both give the same bits.  One launch whatever K is,
+ * no workspace, no atomics: equal inputs give equal bits, and a frame's result does not depend on B or on its place in the batch.
+ * H W <= 2^31 - 1 and B K ceil(H W / 256) <= 2^31 - 1.  Not differentiable. */
+int sininn_flow_gather(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, unsigned char* out_u8,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,8 @@ int flow_synth_launch(const float* i0, const float* i1, const float* f01, const 
 int64_t frame_quality_workspace_floats(int B, int C, int H, int W);
 int frame_quality_launch(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
                          float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, hipStream_t st);
+int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -661,6 +663,12 @@ int sininn_frame_quality(const float* pred, const float* target, int B, int C, i
                          float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, void* stream) {
   return frame_quality_launch(pred, target, B, C, H, W, quantize, window, workspace, workspace_floats, sqerr, out, ssim_map,
                               ST(stream));
+}
+
+int sininn_flow_gather(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, unsigned char* out_u8,
+                       void* stream) {
+  return flow_gather_launch(i0, i1, flows, flow_sample_stride, slots, tau, B, K, C, H, W, k_loop, out, out_u8, ST(stream));
 }
 
 }  // extern "C"

@@ -1,0 +1,134 @@
+// Frame synthesis by gathering: the flows are taken at the in-between time s, on the grid of the frame being synthesized,
+// so both source frames are read through a backward warp -- no accumulator, no zero-fill, no atomics, no holes.
+//   q0 = p + c0 G0(p),  q1 = p + c1 G1(p)                        G0 toward the previous frame, G1 toward the next, in pixels
+//   (W0, n0) = sample(I0, q0),  (W1, n1) = sample(I1, q1)        exact-geometry bilinear; a tap outside the frame adds 0 to W and to n
+//   a0 = 1 - tau, a1 = tau,  L = a0 I0(p) + a1 I1(p)
+//   out = (a0 W0 + a1 W1 + e L) / (a0 n0 + a1 n1 + e),  e = 2^-10
+// G0 and G1 are channel pairs of time slices of one (T', 4, H, W) tensor, named per (b, k) by a slot table the host has validated:
+// six ints a row -- idx0, idx1 (time slice), ch0, ch1 (0 or 2), then the bits of the floats c0, c1.  One launch whatever K is.
+// Every operation is rounded once and none is contracted (`flowsynth.gather_composed` evaluates the same expression in torch).
+#include "common.h"
+
+namespace sininn {
+
+constexpr int FG_THREADS = 256;         // one block: 256 consecutive pixels of one frame's flattened H W
+constexpr int FG_MAX_K = 64;
+constexpr int FG_SLOT_INTS = 6;
+
+// The four taps of one sample: the offset of the north-west tap and the weights, zero where the tap lies outside the frame.
+// n is the sum of the weights inside.  A coordinate that is not finite, or too large for an int, has no tap inside.
+struct GatherTaps {
+  int64_t nw;
+  float w00, w01, w10, w11, n;
+  bool v00, v01, v10, v11;
+};
+
+__device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float gx, float gy, int H, int W) {
+#pragma clang fp contract(off)
+  GatherTaps t = {};
+  const float sx = c * gx, sy = c * gy;                   // the product is rounded, then the sum
+  const float qx = (float)x + sx, qy = (float)y + sy;
+  if (!(fabsf(qx) < 1e9f) || !(fabsf(qy) < 1e9f)) return t;       // NaN and inf fail the comparison too
+  const float flx = floorf(qx), fly = floorf(qy);
+  const int x0 = (int)flx, y0 = (int)fly;
+  const float wx1 = qx - flx, wy1 = qy - fly, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+  const bool xa = x0 >= 0 && x0 < W, xb = x0 + 1 >= 0 && x0 + 1 < W, ya = y0 >= 0 && y0 < H, yb = y0 + 1 >= 0 && y0 + 1 < H;
+  t.v00 = ya && xa; t.v01 = ya && xb; t.v10 = yb && xa; t.v11 = yb && xb;
+  t.w00 = t.v00 ? wy0 * wx0 : 0.f; t.w01 = t.v01 ? wy0 * wx1 : 0.f;
+  t.w10 = t.v10 ? wy1 * wx0 : 0.f; t.w11 = t.v11 ? wy1 * wx1 : 0.f;
+  t.n = ((t.w00 + t.w01) + t.w10) + t.w11;
+  t.nw = (int64_t)y0 * W + x0;                            // read only through a tap that is inside
+  return t;
+}
+
+__device__ __forceinline__ float gather_sample(const float* __restrict__ plane, const GatherTaps& t, int W) {
+#pragma clang fp contract(off)
+  const float t00 = t.v00 ? plane[t.nw] : 0.f, t01 = t.v01 ? plane[t.nw + 1] : 0.f;
+  const float t10 = t.v10 ? plane[t.nw + W] : 0.f, t11 = t.v11 ? plane[t.nw + W + 1] : 0.f;
+  return ((t.w00 * t00 + t.w01 * t01) + t.w10 * t10) + t.w11 * t11;
+}
+
+// One output pixel of frame (b, k): `here0`, `here1` are I0(p), I1(p), loaded by the caller.
+template <int C>
+__device__ __forceinline__ void gather_pixel(const float* __restrict__ i0b, const float* __restrict__ i1b, const float* here0,
+                                             const float* here1, const float* __restrict__ flows, int64_t flow_stride,
+                                             const int* __restrict__ slot, float tk, int x, int y, int64_t r, int H, int W, int64_t HW,
+                                             float* __restrict__ out, uint8_t* __restrict__ out_u8, int64_t o) {
+#pragma clang fp contract(off)
+  const float* g0 = flows + slot[0] * flow_stride + slot[2] * HW + r;
+  const float* g1 = flows + slot[1] * flow_stride + slot[3] * HW + r;
+  const float c0 = __int_as_float(slot[4]), c1 = __int_as_float(slot[5]);
+  const GatherTaps t0 = gather_taps(x, y, c0, g0[0], g0[HW], H, W);
+  const GatherTaps t1 = gather_taps(x, y, c1, g1[0], g1[HW], H, W);
+  const float a0 = 1.f - tk, a1 = tk, e = 0.0009765625f;
+  const float den = (a0 * t0.n + a1 * t1.n) + e;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float w0 = gather_sample(i0b + c * HW, t0, W), w1 = gather_sample(i1b + c * HW, t1, W);
+    const float lin = a0 * here0[c] + a1 * here1[c];
+    const float num = (a0 * w0 + a1 * w1) + e * lin;
+    const float v = __fdiv_rn(num, den);
+    out[o + c * HW] = v;
+    if (out_u8) out_u8[o + c * HW] = (uint8_t)fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f);
+  }
+}
+
+// KLOOP = false: a block is 256 pixels of one (b, k).  KLOOP = true: a block is 256 pixels of one b and every lane walks k, so I0(p)
+// and I1(p) are loaded once for all K.  The slot row and tau are block-uniform either way.
+template <int C, bool KLOOP>
+__global__ __launch_bounds__(FG_THREADS) void flowgather_kernel(const float* __restrict__ i0, const float* __restrict__ i1,
+                                                                const float* __restrict__ flows, int64_t flow_stride,
+                                                                const int* __restrict__ slots, const float* __restrict__ tau, int K,
+                                                                int H, int W, int tiles, float* __restrict__ out,
+                                                                uint8_t* __restrict__ out_u8) {
+  const int64_t HW = (int64_t)H * W;
+  const unsigned frame = blockIdx.x / (unsigned)tiles;    // b k, or with KLOOP b
+  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;         // H W < 2^31: 32-bit divisions only
+  if (pix >= HW) return;
+  const int x = (int)(pix % (unsigned)W), y = (int)(pix / (unsigned)W);
+  const int64_t r = pix, b = KLOOP ? frame : frame / (unsigned)K;
+  const float* i0b = i0 + b * C * HW;
+  const float* i1b = i1 + b * C * HW;
+  float here0[C], here1[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) { here0[c] = i0b[c * HW + r]; here1[c] = i1b[c * HW + r]; }
+  if (KLOOP) {
+    for (int k = 0; k < K; ++k) {
+      const int64_t bk = b * K + k;
+      gather_pixel<C>(i0b, i1b, here0, here1, flows, flow_stride, slots + bk * FG_SLOT_INTS, tau[k], x, y, r, H, W, HW, out, out_u8,
+                      bk * C * HW + r);
+    }
+  } else {
+    const int64_t bk = frame;
+    gather_pixel<C>(i0b, i1b, here0, here1, flows, flow_stride, slots + bk * FG_SLOT_INTS, tau[frame % (unsigned)K], x, y, r, H, W, HW,
+                    out, out_u8, bk * C * HW + r);
+  }
+}
+
+int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st) {
+  SININN_CHECK(i0 && i1 && flows && slots && tau && out, "flow_gather: null pointer");
+  SININN_CHECK(B > 0 && H > 0 && W > 0, "flow_gather: bad shape (every size must be positive)");
+  SININN_CHECK(C == 1 || C == 3, "flow_gather: frames have 1 or 3 channels (got %d)", C);
+  SININN_CHECK(K >= 1 && K <= FG_MAX_K, "flow_gather: K = %d times in one call, 1 to %d are supported", K, FG_MAX_K);
+  const int64_t HW = (int64_t)H * W;
+  SININN_CHECK(HW <= 0x7fffffff, "flow_gather: H * W = %lld is past an int index", (long long)HW);
+  const int64_t tiles = (HW + FG_THREADS - 1) / FG_THREADS;
+  const int64_t blocks = (int64_t)B * (k_loop ? 1 : K) * tiles;
+  SININN_CHECK((int64_t)B * K * tiles <= 0x7fffffff, "flow_gather: B * K * H * W = %lld needs more blocks than one launch has",
+               (long long)B * K * HW);
+  SININN_CHECK((int64_t)B * K * C <= INT64_MAX / HW, "flow_gather: B * K * C * H * W is past a 64-bit index");
+  SININN_CHECK(flow_sample_stride >= 4 * HW, "flow_gather: sample stride %lld is smaller than four channel planes (%lld)",
+               (long long)flow_sample_stride, (long long)(4 * HW));
+  const dim3 grid((unsigned)blocks), block(FG_THREADS);
+#define FG_LAUNCH(CH, LOOP) \
+  hipLaunchKernelGGL((flowgather_kernel<CH, LOOP>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H, W, \
+                     (int)tiles, out, out_u8)
+  if (C == 1) { if (k_loop) FG_LAUNCH(1, true); else FG_LAUNCH(1, false); }
+  else        { if (k_loop) FG_LAUNCH(3, true); else FG_LAUNCH(3, false); }
+#undef FG_LAUNCH
+  SININN_LAUNCH_CHECK("flowgather");
+  return 0;
+}
+
+}  // namespace sininn

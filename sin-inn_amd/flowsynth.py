@@ -15,6 +15,23 @@ The definition, for frames I0, I1 (B, C, H, W), flows F01, F10 (B, 2, H, W) in p
 -0.0 counts as zero.  Resample2d divides by (W - 1, H - 1): on an axis of length 1 its sampling coordinate is infinite, the sample
 lies outside the frame and the warped value is 0 there.  The operator is for inference and has no gradient.
 
+    gather(frame1, frame2, flows, slots, taus)            the second synthesis rule, csrc/flowgather.hip: one launch
+    gather_composed(frame1, frame2, flows, slots, taus)   the same definition from torch ops, on any device, fp32 or fp64
+    gather_slots(times, taus, dt, back)                   host logic: the time stamps to evaluate the network at, and the slot table
+
+`gather` takes the flows at the in-between time s = t0 + tau dt, where they live on the grid of the frame being synthesized, and reads
+both source frames through a backward warp.  `flows` is a (T', 4, H, W) tensor in `flow_fields`' layout (channels 0-1 forward, 2-3
+backward); per output frame (b, k) the slot table names the time slice and channel pair of G0 (toward the previous frame) and of G1
+(toward the next one) and the coefficients c0, c1:
+
+    q0 = p + c0 G0(p),  q1 = p + c1 G1(p);    (W0, n0) = sample(I0, q0),  (W1, n1) = sample(I1, q1)
+    a0 = 1 - tau, a1 = tau,  L = a0 I0(p) + a1 I1(p);    out = (a0 W0 + a1 W1 + e L) / (a0 n0 + a1 n1 + e),  e = 2^-10
+
+`sample` is the bilinear gather with pixel centres at integers (not Resample2d's geometry): a tap outside the frame adds 0 to W and to
+n, the sum of the weights inside.  The regular slot is G1 = fw(s), c1 = 1 - tau, G0 = bw(s - dt), c0 = tau; where s - dt lies before
+the clip's first frame, and throughout under back='reverse', G0 = fw(s) with c0 = -tau (constant velocity).  No atomics and no
+accumulator: equal inputs give equal bits.  No gradient.
+
     quality(pred, target)            PSNR and mean SSIM per frame, the fused operator of csrc/framequality.hip
     quality_composed(pred, target)   the same definition from torch ops, on any device, fp32 or fp64: its A/B partner and reference
 
@@ -29,6 +46,7 @@ PNG holds: both inputs go through `synthesize`'s u8 rule first, clamp(round-half
 import collections
 import ctypes as C
 import math
+import struct
 
 import torch
 
@@ -151,6 +169,207 @@ def composed(frame1, frame2, flow12, flow21, taus):
         frame1, frame2 = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous()
         flow12, flow21 = _gpu32(flow12).contiguous(), _gpu32(flow21).contiguous()
         return compose_from(frame1, frame2, flow12, flow21, values, metric, _FunctionSoftsplat.apply)
+
+
+# ---- synthesis by gathering ----
+
+GATHER_EPS = 2.0 ** -10
+SLOT_INTS = 6           # FG_SLOT_INTS of csrc/flowgather.hip: idx0, idx1, ch0, ch1, bits of c0, bits of c1
+K_LOOP = False          # the launch shape of `gather`: one lane per (b, k, y, x); True: a lane walks the K times of its pixel
+DeviceSlots = collections.namedtuple('DeviceSlots', 'table slices')     # a validated table on the device; slices: the T' it needs
+
+
+def _f32(v):
+    """v rounded to fp32, as a Python float"""
+    return struct.unpack('<f', struct.pack('<f', v))[0]
+
+
+def _f32_bits(v):
+    return struct.unpack('<i', struct.pack('<f', v))[0]
+
+
+def slot_coefficients(slots):
+    """(c0, c1) of a host slot table as an fp32 tensor (B, K, 2)"""
+    return slots[..., 4:].contiguous().view(torch.float32)
+
+
+def gather_slots(times, taus, dt, back='network', first=-1.0):
+    """Where to evaluate the network for `gather`, and what to read from the result.  `times`: the frame-1 time stamps of the batch's
+    pairs (B values; a sequence or a tensor), `taus`: K values in [0, 1], `dt`: the spacing of the clip's times, `first`: the time of
+    the clip's first frame.  Returns (stamps, slots):
+
+        stamps   Python floats, each an fp32 value: first s_{b,k} = times[b] + taus[k] dt in (b, k) order -- slice b K + k --, then,
+                 under back='network', s_{b,k} - dt in the same order for every (b, k) where that is not before `first`
+        slots    the table, a host int32 tensor (B, K, 6): idx0, idx1, ch0, ch1 and the bits of c0, c1 (`slot_coefficients`).
+                 G1 = fw(s): idx1 = b K + k, ch1 = 0, c1 = 1 - tau.  G0 = bw(s - dt): idx0 the slice of s - dt, ch0 = 2, c0 = tau.
+                 Where s - dt < first (pairs of the clip's first frame, tau < 1), and everywhere under back='reverse':
+                 G0 = fw(s), idx0 = idx1, ch0 = 0, c0 = -tau.
+
+    `s - dt < first` is decided with a slack of dt / 1000, which covers the fp32 rounding of the clip's times.  Pure host logic."""
+    if back not in ('network', 'reverse'):
+        raise ValueError(f"flowsynth.gather_slots: back is 'network' or 'reverse', got {back!r}")
+    values = _host_taus(taus)
+    t0s = [float(t) for t in (times.detach().cpu().to(torch.float64).tolist() if torch.is_tensor(times) else times)]
+    dt = float(dt)
+    if not t0s or not dt > 0:
+        raise ValueError('flowsynth.gather_slots: at least one pair, and dt > 0')
+    k = len(values)
+    stamps = [_f32(t0 + tau * dt) for t0 in t0s for tau in values]
+    rows = []
+    for b, t0 in enumerate(t0s):
+        for j, tau in enumerate(values):
+            tau32 = _f32(tau)
+            idx1 = b * k + j
+            before = t0 + tau * dt - dt
+            if back == 'network' and before >= first - 1e-3 * dt:
+                idx0, ch0, c0 = len(stamps), 2, tau32
+                stamps.append(_f32(before))
+            else:
+                idx0, ch0, c0 = idx1, 0, -tau32
+            rows.append([idx0, idx1, ch0, 0, _f32_bits(c0), _f32_bits(_f32(1.0 - tau32))])
+    return stamps, torch.tensor(rows, dtype=torch.int32).reshape(len(t0s), k, SLOT_INTS)
+
+
+def _host_slots(who, slots, b, k):
+    """the host table, validated: (B, K, 6) int32, slices >= 0, channel pairs 0 or 2, finite coefficients; returns the T' it needs"""
+    if not torch.is_tensor(slots) or slots.is_cuda or slots.dtype != torch.int32 or tuple(slots.shape) != (b, k, SLOT_INTS):
+        raise ValueError(f'flowsynth.{who}: slots is a host int32 tensor ({b}, {k}, {SLOT_INTS}), what gather_slots returns '
+                         '(or, for gather, upload_slots)')
+    if bool((slots[..., :2] < 0).any()):
+        raise ValueError(f'flowsynth.{who}: a slot names a negative time slice')
+    if not bool(((slots[..., 2:4] == 0) | (slots[..., 2:4] == 2)).all()):
+        raise ValueError(f'flowsynth.{who}: a channel pair starts at channel 0 (forward) or 2 (backward)')
+    if not bool(torch.isfinite(slot_coefficients(slots)).all()):
+        raise ValueError(f'flowsynth.{who}: a slot coefficient is not finite')
+    return int(slots[..., :2].max()) + 1
+
+
+def upload_slots(slots, device):
+    """A host table, validated and moved to `device`: what `gather` does with a host table on every call, done once"""
+    if not torch.is_tensor(slots) or slots.dim() != 3:
+        raise ValueError('flowsynth.upload_slots: slots is the host table of gather_slots, (B, K, 6) int32')
+    b, k, _ = slots.shape
+    return DeviceSlots(slots.contiguous().to(device), _host_slots('upload_slots', slots, b, k))
+
+
+def _gather_inputs(who, frame1, frame2, flows):
+    for t in (frame1, frame2, flows):
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
+                               '(or call it under torch.no_grad())')
+    b, c, h, w = frame1.shape
+    assert frame2.shape == frame1.shape, f'flowsynth.{who}: the two frames differ in shape'
+    if c not in (1, 3):
+        raise ValueError(f'flowsynth.{who}: frames have 1 or 3 channels (got {c})')
+    assert flows.dim() == 4 and tuple(flows.shape[1:]) == (4, h, w), f'flowsynth.{who}: flows is (T, 4, H, W), the layout of flow_fields'
+    return b, c, h, w
+
+
+def joined_flows(flow12, flow21):
+    """The (T, 4, H, W) tensor whose channel slices `flow_fields` returned, without a copy"""
+    t, two, h, w = flow12.shape
+    assert two == 2 and flow21.shape == flow12.shape and flow12.stride() == flow21.stride() == (4 * h * w, h * w, w, 1) \
+        and flow21.data_ptr() == flow12.data_ptr() + 2 * h * w * flow12.element_size(), \
+        'joined_flows: the two results of one flow_fields call, channels 0-1 and 2-3 of one (T, 4, H, W) tensor'
+    return flow12.as_strided((t, 4, h, w), flow12.stride(), flow12.storage_offset())
+
+
+def gather(frame1, frame2, flows, slots, taus, *, out=None, u8=False, k_loop=None):
+    """The frames at `taus` between frame1 and frame2 from flows taken at the in-between times: (B, K, C, H, W) fp32, and with u8=True
+    also the bytes, by `synthesize`'s rule.  `flows`: (T', 4, H, W) fp32 on the device, read in place -- any stride between time slices,
+    the four channel planes of a slice contiguous.  `slots`: the host table of `gather_slots` (validated and uploaded here), or what
+    `upload_slots` made of it.  `k_loop`: the launch shape (None: `K_LOOP`); both give the same bits.  One launch, no workspace."""
+    b, c, h, w = _gather_inputs('gather', frame1, frame2, flows)
+    values = _host_taus(taus)
+    k = len(values)
+    frame1, frame2, flows = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous(), _gpu32(flows)
+    dev = frame1.device
+    if not isinstance(slots, DeviceSlots):
+        need = _host_slots('gather', slots, b, k)
+        slots = DeviceSlots(slots.contiguous().to(dev), need)
+    table, need = slots
+    if not (table.is_cuda and table.dtype == torch.int32 and tuple(table.shape) == (b, k, SLOT_INTS) and table.is_contiguous()):
+        raise ValueError(f'flowsynth.gather: the uploaded table is not ({b}, {k}, {SLOT_INTS}) int32 on the device')
+    if need > flows.shape[0]:
+        raise ValueError(f'flowsynth.gather: the slots name time slice {need - 1}, flows has {flows.shape[0]}')
+    if flows.stride()[1:] != (h * w, w, 1) and flows.numel() > 0:
+        raise ValueError('flowsynth.gather: the four channel planes of a time slice must be contiguous (any stride between slices)')
+    stride = flows.stride(0) if flows.shape[0] > 1 else 4 * h * w
+    if torch.is_tensor(taus) and taus.is_cuda and taus.dtype == torch.float32:
+        tau = taus.detach().contiguous()
+    else:
+        tau = torch.tensor(values, dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty((b, k, c, h, w), device=dev, dtype=torch.float32)
+    assert tuple(out.shape) == (b, k, c, h, w) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+    bytes_ = torch.empty((b, k, c, h, w), device=dev, dtype=torch.uint8) if u8 else None
+    check(_lib.lib().sininn_flow_gather(ptr(frame1), ptr(frame2), ptr(flows), stride, C.c_void_p(table.data_ptr()), ptr(tau), b, k, c,
+                                        h, w, int(K_LOOP if k_loop is None else k_loop), ptr(out),
+                                        C.c_void_p(bytes_.data_ptr()) if u8 else None, _stream()))
+    return (out, bytes_) if u8 else out
+
+
+def bilinear_gather(img, qx, qy):
+    """sample(I, q) of the definition with torch ops: img (B, C, H, W), qx, qy (B, K, H, W) -> (W (B, K, C, H, W), n (B, K, H, W)).
+    Pixel centres at integers; a tap outside the frame adds 0 to both; a coordinate that is not finite, or 1e9 or more in size, has no
+    tap inside.  The four products are summed in the kernel's order."""
+    b, c, h, w = img.shape
+    k = qx.shape[1]
+    ok = (qx.abs() < 1e9) & (qy.abs() < 1e9)
+    qx, qy = torch.where(ok, qx, torch.zeros_like(qx)), torch.where(ok, qy, torch.zeros_like(qy))
+    fx, fy = qx.floor(), qy.floor()
+    x0, y0 = fx.long(), fy.long()
+    wx1, wy1 = qx - fx, qy - fy
+    wx0, wy0 = 1 - wx1, 1 - wy1
+    flat = img.reshape(b, 1, c, h * w).expand(b, k, c, h * w)
+    total, n = None, None
+    for dy, dx, wy, wx in ((0, 0, wy0, wx0), (0, 1, wy0, wx1), (1, 0, wy1, wx0), (1, 1, wy1, wx1)):
+        yy, xx = y0 + dy, x0 + dx
+        inside = ok & (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+        weight = torch.where(inside, wy * wx, torch.zeros_like(wx))
+        at = (yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1)).reshape(b, k, 1, h * w).expand(b, k, c, h * w)
+        term = weight[:, :, None] * flat.gather(3, at).reshape(b, k, c, h, w)
+        total = term if total is None else total + term
+        n = weight if n is None else n + weight
+    return total, n
+
+
+def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, eps=GATHER_EPS):
+    """The definition, operation by operation, in the dtype and on the device of the frames.  `sample` and `eps` are the two places a
+    test swaps in something else (another geometry, no renormalisation, no guard)."""
+    b, c, h, w = frame1.shape
+    dt, dev = frame1.dtype, frame1.device
+    flows = flows.to(device=dev, dtype=dt)
+    idx = slots[..., :4].to(dev, torch.long)
+    coef = slot_coefficients(slots).to(dev, dt)
+    a1 = torch.tensor(values, dtype=torch.float32).to(dev, dt).view(1, -1, 1, 1, 1)
+    a0 = 1 - a1
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=dt), torch.arange(w, device=dev, dtype=dt), indexing='ij')
+    pair = torch.arange(2, device=dev)
+
+    def warped(img, which):
+        g = flows[idx[:, :, which, None], idx[:, :, 2 + which, None] + pair]                  # (B, K, 2, H, W)
+        cf = coef[:, :, which, None, None]
+        return sample(img, xs + cf * g[:, :, 0], ys + cf * g[:, :, 1])
+
+    (w0, n0), (w1, n1) = warped(frame1, 0), warped(frame2, 1)
+    lin = a0 * frame1[:, None] + a1 * frame2[:, None]
+    num = (a0 * w0 + a1 * w1) + eps * lin
+    den = (a0[:, :, 0] * n0 + a1[:, :, 0] * n1) + eps
+    return num / den[:, :, None]
+
+
+def gather_composed(frame1, frame2, flows, slots, taus):
+    """`gather` from torch ops, on the device and in the dtype of the frames (CPU or GPU, fp32 or fp64): index arithmetic and
+    `torch.gather` for the taps, a few dozen launches.  `slots` is the host table.  In fp32 it rounds where the fused operator rounds."""
+    b, c, h, w = _gather_inputs('gather_composed', frame1, frame2, flows)
+    values = _host_taus(taus)
+    need = _host_slots('gather_composed', slots, b, len(values))
+    if need > flows.shape[0]:
+        raise ValueError(f'flowsynth.gather_composed: the slots name time slice {need - 1}, flows has {flows.shape[0]}')
+    assert frame1.dtype in (torch.float32, torch.float64) and frame2.dtype == frame1.dtype
+    with torch.no_grad():
+        return gather_from(frame1.detach(), frame2.detach(), flows.detach(), slots, values)
 
 
 # ---- frame quality (DESIGN 18) ----

@@ -12,6 +12,16 @@ ground-truth flows (the backward flow: the negative of the forward one): smooth 
 
 times `flowsynth.quality` (csrc/framequality.hip) against `flowsynth.quality_composed` on batch x 7 frames, float and
 quantised mode, one line each.  `min_bytes` is both frames read once; `fused_tb_per_s` is that count over the fused time.
+
+    python tools/bench_flowsynth.py --gather [--baseline]
+
+times the gather synthesis (csrc/flowgather.hip) at K = 1 and K = factor - 1, one `flowgather` line each: the fused operator
+in both launch shapes (`lane`: one lane per (b, k, y, x); `kloop`: a lane walks the K times of its pixel), and with --baseline
+`flowsynth.gather_composed` and `flowsynth.synthesize` on the same frames, alternating.  The flows are the clip's ground truth
+repeated over the slot table's time slices (the operator's time does not depend on their values beyond locality).  `min_bytes` counts
+4 flow words, 2 C words of the two frames at the pixel and C written per output pixel-frame (`kloop`: the 2 C words once per pixel).
+Then one `flowgather_interpolate` line per K: the whole `FlowTrainer.interpolate` call -- network evaluations included, an unfitted
+--net under its controller -- for splat, gather/network and gather/reverse.
 """
 import argparse
 import json
@@ -71,6 +81,73 @@ def quality_lines(a, dev):
     return lines
 
 
+def _timed(todo, a):
+    """name -> (best median ms, the medians of the alternating windows)"""
+    res = {name: [] for name in todo}
+    for _ in range(a.rounds):
+        for name, fn in todo.items():
+            res[name].append(window(fn, a.seconds, a.warmup)['median_ms'])
+    return {name: (round(min(m), 4), [round(v, 4) for v in m]) for name, m in res.items()}
+
+
+def gather_lines(a, dev):
+    from sin_inn_amd import flowdata, flownet, flowsynth, flowtrainer, progressive
+    clip = flowdata.SyntheticClip(a.batch + 1, a.height, a.width)
+    i0, i1 = clip.video[:-1].contiguous().to(dev), clip.video[1:].contiguous().to(dev)
+    f01 = clip.flow.contiguous().to(dev)
+    f10 = (-clip.flow).contiguous().to(dev)
+    dt = 2 / a.batch
+    times = clip.T[:-1]
+    torch.manual_seed(0)
+    net = flownet.flow_model_dict[a.net](flownet.ModelParams())
+    if getattr(net, 'is_progressive', False):
+        net = progressive.LinearControllerEarly(net, 1000, epsilon=1e-3)
+    args = argparse.Namespace(lr=1e-4, loss_l1=1, loss_census=0.1, loss_ssim=0.05, census_width=3, loss_smooth1=0.1, edge_constant=150,
+                              edge_func='gauss', occl='wang', occl_thresh=0.7, net=net.to(dev))
+    model = flowtrainer.FlowTrainer(args).to(dev)
+    batch = [i0, i1, times.to(dev), clip.flow_scale]
+    lines = []
+    for k in sorted({1, a.factor - 1}):
+        taus = [0.5] if k == 1 else [j / a.factor for j in range(1, a.factor)]
+        tau_dev = torch.tensor(taus, dtype=torch.float32, device=dev)
+        stamps, slots = flowsynth.gather_slots(times, taus, dt)
+        per_b = len(stamps) // a.batch + 1
+        flows = torch.cat([f01, f10], 1).repeat_interleave(per_b, 0)[:len(stamps)].contiguous()     # every slice a ground-truth pair
+        table = flowsynth.upload_slots(slots, dev)
+        out = torch.empty(a.batch, k, 3, a.height, a.width, device=dev)
+        ws = torch.empty(flowsynth.workspace_floats(a.batch, k, 3, a.height, a.width), device=dev)
+        todo = {'lane': lambda: flowsynth.gather(i0, i1, flows, table, tau_dev, out=out, k_loop=False),
+                'kloop': lambda: flowsynth.gather(i0, i1, flows, table, tau_dev, out=out, k_loop=True)}
+        if a.baseline:
+            todo['composed'] = lambda: flowsynth.gather_composed(i0, i1, flows, slots, taus)
+            todo['splat'] = lambda: flowsynth.synthesize(i0, i1, f01, f10, tau_dev, out=out, workspace=ws)
+        pixels = a.batch * a.height * a.width
+        line = dict(op='flowgather', height=a.height, width=a.width, batch=a.batch, K=k, slices=len(stamps),
+                    min_bytes_lane=4 * pixels * k * (4 + 6 + 3), min_bytes_kloop=4 * pixels * (k * (4 + 3) + 6))
+        for name, (best, meds) in _timed(todo, a).items():
+            line[f'{name}_ms'], line[f'{name}_ms_windows'] = best, meds
+        for name in ('lane', 'kloop'):
+            line[f'{name}_tb_per_s'] = round(line[f'min_bytes_{name}'] / (line[f'{name}_ms'] * 1e-3) / 1e12, 3)
+        if a.baseline:
+            best = min(line['lane_ms'], line['kloop_ms'])
+            line['composed_over_fused'] = round(line['composed_ms'] / best, 3)
+            line['splat_over_gather'] = round(line['splat_ms'] / best, 3)
+            line['max_abs_diff_composed'] = float((flowsynth.gather(i0, i1, flows, table, tau_dev)
+                                                   - flowsynth.gather_composed(i0, i1, flows, slots, taus)).abs().max())
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        calls = {'splat': lambda: model.interpolate(batch, taus),
+                 'gather_network': lambda: model.interpolate(batch, taus, synthesis='gather', dt=dt),
+                 'gather_reverse': lambda: model.interpolate(batch, taus, synthesis='gather', dt=dt, back='reverse')}
+        line = dict(op='flowgather_interpolate', net=a.net, height=a.height, width=a.width, batch=a.batch, K=k,
+                    stamps_splat=a.batch, stamps_gather_network=len(stamps), stamps_gather_reverse=a.batch * k)
+        for name, (best, meds) in _timed(calls, a).items():
+            line[f'{name}_ms'], line[f'{name}_ms_windows'] = best, meds
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def main():
     from sin_inn_amd import flowdata, flowsynth
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
@@ -84,12 +161,14 @@ def main():
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--log', action='store_true', help='append the lines to profiles/flowsynth_bench.jsonl')
     ap.add_argument('--quality', action='store_true', help='time flowsynth.quality (and with --baseline quality_composed) instead')
+    ap.add_argument('--gather', action='store_true', help='time flowsynth.gather and the whole interpolate call instead (DESIGN 19)')
+    ap.add_argument('--net', default='PRBF', help='--gather: the network of the whole-call lines')
     a = ap.parse_args()
     assert 2 <= a.factor <= 65
     dev = torch.device('cuda', 0)
-    if a.quality:
-        lines = quality_lines(a, dev)
-        for line in lines:
+    if a.quality or a.gather:
+        lines = gather_lines(a, dev) if a.gather else quality_lines(a, dev)
+        for line in ([] if a.gather else lines):           # the gather lines are printed as they are measured
             print(json.dumps(line))
         if a.log:
             with open(os.path.join(ROOT, 'profiles', 'flowsynth_bench.jsonl'), 'a') as f:

@@ -22,6 +22,11 @@ source frame is written as frame_<T:04d>_00.png.
                    compare them with the real ones by PSNR and SSIM, on the bytes the PNGs hold.  <out>/quality.jsonl gets one line
                    per held-out frame (pair, j, tau, then psnr, ssim and mse of the network, of the linear blend of the two kept frames
                    and of the nearer kept frame repeated) and a last line with the means, which are also printed as a table
+  --synthesis R    splat (default): the network's flows at the pair's time stamp, scaled by tau, softmax-splatted (DESIGN 17);
+                   gather: the network's flows at the in-between time itself, both frames read through a backward warp.
+                   The files written and quality.jsonl keep their format; the last line of quality.jsonl names the synthesis
+  --back B         --synthesis gather: network (default) takes the flow toward the previous frame from the network at s - dt;
+                   reverse uses the negated forward flow at s and evaluates half the time stamps
 """
 import argparse
 import importlib.util
@@ -56,6 +61,9 @@ def get_parser():
     ap.add_argument('--fit-epochs', type=int, default=0, metavar='N', help='train N epochs first instead of loading a checkpoint')
     ap.add_argument('--batch', type=int, default=1, help='pairs per call')
     ap.add_argument('--holdout', type=int, metavar='S', help='keep every S-th frame and score the synthesis of the others; sets --factor')
+    ap.add_argument('--synthesis', choices=('splat', 'gather'), default='splat', help='the synthesis rule (DESIGN 17 / 19)')
+    ap.add_argument('--back', choices=('network', 'reverse'), default='network',
+                    help='--synthesis gather: where the flow toward the previous frame comes from')
     return ap
 
 
@@ -169,13 +177,16 @@ def main(argv=None):
     os.makedirs(out_dir, exist_ok=True)
     taus = [j / a.factor for j in range(1, a.factor)]
     source = (clip * 255).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).numpy()         # (T, h, w, 3)
+    how = {}
+    if a.synthesis == 'gather':
+        how = dict(synthesis='gather', dt=2 / (num_frames - 1), back=a.back)        # the clip fitted: under --holdout the kept frames
     between = {}                                                   # (pair, j) -> (h, w, 3) bytes
     records = []
     if taus:
         first = 0
         for batch in video.test_dataloader():
             batch = _to_device(batch, device)
-            frames, u8 = model.interpolate(batch, taus, u8=True)
+            frames, u8 = model.interpolate(batch, taus, u8=True, **how)
             if a.holdout:
                 held = torch.stack([video.testset.held(first + n)[0] for n in range(batch[0].shape[0])])
                 records += quality_records(model.holdout_quality(batch, held, taus, frames=frames), first)
@@ -194,6 +205,7 @@ def main(argv=None):
         save_gif(path.join('results', f'{tag}.gif'), np.stack(written), fps=4 * a.factor)
     if a.holdout:
         means = quality_means(records)
+        means['synthesis'] = a.synthesis if a.synthesis == 'splat' else f'gather/{a.back}'
         with open(path.join(out_dir, 'quality.jsonl'), 'w') as f:
             for rec in records + [means]:
                 f.write(json.dumps(rec) + '\n')
