@@ -98,4 +98,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Sum of a double over a block of 256 threads, the same value in every thread; lds holds four doubles.  Fixed order: xor butterfly
+// inside a wave, then the four waves as (0 + 1) + (2 + 3).  The leading barrier makes a second call with the same lds safe.
+__device__ __forceinline__ double block_sum_f64(double v, double* lds) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  __syncthreads();                                   // lds may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+
 }  // namespace sininn

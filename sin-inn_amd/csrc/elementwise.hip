@@ -1,6 +1,7 @@
 // HBM-bound kernels of the sin-inn training path: weight packing, coupling backward tail, index maps
 // (squeeze / permute / layout import-export), losses, warps, frame-window sampler, Adam.
 #include "common.h"
+#include "bilinear_taps.h"
 
 namespace sininn {
 
@@ -452,15 +453,11 @@ __global__ void affine_warp_kernel(const float* __restrict__ img, Str4 is, const
     decode4(idx, C, H, W, x_fastest, b, c, y, x);
     float ix, iy;
     affine_src(theta + b * 6, x, y, H, W, ix, iy);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const float wx1 = ix - fx, wy1 = iy - fy, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+    const BilinearTaps t = bilinear_taps(ix, iy);
     const float* base = img + b * is.b + c * is.c;
-    auto tap = [&](int yy, int xx) -> float {
-      return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? base[yy * is.h + xx * is.w] : 0.f;
-    };
-    const float val = tap(y0, x0) * wy0 * wx0 + tap(y0, x0 + 1) * wy0 * wx1 + tap(y0 + 1, x0) * wy1 * wx0 +
-                      tap(y0 + 1, x0 + 1) * wy1 * wx1;
+    auto tap = [&](int yy, int xx) -> float { return tap_inside(yy, xx, H, W) ? base[yy * is.h + xx * is.w] : 0.f; };
+    const float val = tap(t.y0, t.x0) * t.wy0 * t.wx0 + tap(t.y0, t.x0 + 1) * t.wy0 * t.wx1 + tap(t.y0 + 1, t.x0) * t.wy1 * t.wx0 +
+                      tap(t.y0 + 1, t.x0 + 1) * t.wy1 * t.wx1;
     out[b * os.b + c * os.c + y * os.h + x * os.w] = val;
     if (ref) { const float d = val - ref[b * rs.b + c * rs.c + y * rs.h + x * rs.w]; acc += d * d; }
   }
@@ -495,15 +492,14 @@ __global__ void affine_warp_bwd_kernel(const float* __restrict__ gout, Str4 gs, 
     decode4(idx, C, H, W, x_fastest, b, c, y, x);
     float ix, iy;
     affine_src(theta + b * 6, x, y, H, W, ix, iy);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const float wx1 = ix - fx, wy1 = iy - fy, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+    const BilinearTaps t = bilinear_taps(ix, iy);
     const float g = gout[b * gs.b + c * gs.c + y * gs.h + x * gs.w];
     float* base = gimg + b * gis.b + c * gis.c;
     auto put = [&](int yy, int xx, float wgt) {
-      if (yy >= 0 && yy < H && xx >= 0 && xx < W) atomicAdd(base + yy * gis.h + xx * gis.w, g * wgt);
+      if (tap_inside(yy, xx, H, W)) atomicAdd(base + yy * gis.h + xx * gis.w, g * wgt);
     };
-    put(y0, x0, wy0 * wx0); put(y0, x0 + 1, wy0 * wx1); put(y0 + 1, x0, wy1 * wx0); put(y0 + 1, x0 + 1, wy1 * wx1);
+    put(t.y0, t.x0, t.wy0 * t.wx0); put(t.y0, t.x0 + 1, t.wy0 * t.wx1);
+    put(t.y0 + 1, t.x0, t.wy1 * t.wx0); put(t.y0 + 1, t.x0 + 1, t.wy1 * t.wx1);
   }
 }
 
@@ -546,26 +542,21 @@ __global__ void flow_warp_l1_kernel(const T* __restrict__ img, const float* __re
   const int64_t r = pidx % HW;
   const int y = (int)(r / W), x = (int)(r % W);
   const float fx = flow[(b * 2 + 0) * HW + r], fy = flow[(b * 2 + 1) * HW + r];
-  // grid = (coords+flow)/(W-1,H-1)*2-1, sampled with align_corners=False  (quirk C-18 kept)
-  const float gxn = (x + fx) / (float)(W - 1) * 2.f - 1.f, gyn = (y + fy) / (float)(H - 1) * 2.f - 1.f;
-  const float ix = ((gxn + 1.f) * W - 1.f) * 0.5f, iy = ((gyn + 1.f) * H - 1.f) * 0.5f;
-  const float flx = floorf(ix), fly = floorf(iy);
-  const int x0 = (int)flx, y0 = (int)fly;
-  const float wx1 = ix - flx, wy1 = iy - fly, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+  float ix, iy;
+  resample2d_coord(x, y, fx, fy, H, W, ix, iy);
+  const BilinearTaps t = bilinear_taps(ix, iy);
   const int lane = threadIdx.x & 63;
-  const int nx0 = __shfl_down(x0, 1), ny0 = __shfl_down(y0, 1), nb = __shfl_down(b, 1);
-  const bool share = (lane < 63) && (nb == b) && (nx0 == x0 + 1) && (ny0 == y0);
+  const int nx0 = __shfl_down(t.x0, 1), ny0 = __shfl_down(t.y0, 1), nb = __shfl_down(b, 1);
+  const bool share = (lane < 63) && (nb == b) && (nx0 == t.x0 + 1) && (ny0 == t.y0);
   float l1 = 0.f;
   for (int c = 0; c < C; ++c) {
     const T* base = img + ((int64_t)b * C + c) * HW;
-    auto tap = [&](int yy, int xx) -> float {
-      return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? fw_ld(base, (int64_t)yy * W + xx) : 0.f;
-    };
-    const float t00 = tap(y0, x0), t10 = tap(y0 + 1, x0);
+    auto tap = [&](int yy, int xx) -> float { return tap_inside(yy, xx, H, W) ? fw_ld(base, (int64_t)yy * W + xx) : 0.f; };
+    const float t00 = tap(t.y0, t.x0), t10 = tap(t.y0 + 1, t.x0);
     const float n00 = __shfl_down(t00, 1), n10 = __shfl_down(t10, 1);
-    const float t01 = share ? n00 : tap(y0, x0 + 1);
-    const float t11 = share ? n10 : tap(y0 + 1, x0 + 1);
-    float val = t00 * wy0 * wx0 + t01 * wy0 * wx1 + t10 * wy1 * wx0 + t11 * wy1 * wx1;
+    const float t01 = share ? n00 : tap(t.y0, t.x0 + 1);
+    const float t11 = share ? n10 : tap(t.y0 + 1, t.x0 + 1);
+    float val = t00 * t.wy0 * t.wx0 + t01 * t.wy0 * t.wx1 + t10 * t.wy1 * t.wx0 + t11 * t.wy1 * t.wx1;
     if (live) {
       if (warped) {
         fw_st(warped, ((int64_t)b * C + c) * HW + r, val);
@@ -612,11 +603,9 @@ __global__ void flow_warp_l1_bwd_kernel(const T* __restrict__ img, const float* 
   const int64_t r = idx % HW;
   const int y = (int)(r / W), x = (int)(r % W);
   const float fx = flow[(b * 2 + 0) * HW + r], fy = flow[(b * 2 + 1) * HW + r];
-  const float gxn = (x + fx) / (float)(W - 1) * 2.f - 1.f, gyn = (y + fy) / (float)(H - 1) * 2.f - 1.f;
-  const float ix = ((gxn + 1.f) * W - 1.f) * 0.5f, iy = ((gyn + 1.f) * H - 1.f) * 0.5f;
-  const float flx = floorf(ix), fly = floorf(iy);
-  const int x0 = (int)flx, y0 = (int)fly;
-  const float wx1 = ix - flx, wy1 = iy - fly, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+  float ix, iy;
+  resample2d_coord(x, y, fx, fy, H, W, ix, iy);
+  const BilinearTaps t = bilinear_taps(ix, iy);
   const float gm = gmetric ? gmetric[(int64_t)b * HW + r] / (float)C : 0.f;
   float gix = 0.f, giy = 0.f;
   for (int c = 0; c < C; ++c) {
@@ -627,17 +616,16 @@ __global__ void flow_warp_l1_bwd_kernel(const T* __restrict__ img, const float* 
       g += (d > 0.f) ? -gm : ((d < 0.f) ? gm : 0.f);
     }
     const T* base = img + o;
-    auto tap = [&](int yy, int xx) -> float {
-      return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? fw_ld(base, (int64_t)yy * W + xx) : 0.f;
-    };
-    const float t00 = tap(y0, x0), t01 = tap(y0, x0 + 1), t10 = tap(y0 + 1, x0), t11 = tap(y0 + 1, x0 + 1);
-    gix += g * ((t01 - t00) * wy0 + (t11 - t10) * wy1);
-    giy += g * ((t10 - t00) * wx0 + (t11 - t01) * wx1);
+    auto tap = [&](int yy, int xx) -> float { return tap_inside(yy, xx, H, W) ? fw_ld(base, (int64_t)yy * W + xx) : 0.f; };
+    const float t00 = tap(t.y0, t.x0), t01 = tap(t.y0, t.x0 + 1), t10 = tap(t.y0 + 1, t.x0), t11 = tap(t.y0 + 1, t.x0 + 1);
+    gix += g * ((t01 - t00) * t.wy0 + (t11 - t10) * t.wy1);
+    giy += g * ((t10 - t00) * t.wx0 + (t11 - t01) * t.wx1);
     if (gimg) {
       auto put = [&](int yy, int xx, float wgt) {
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) atomicAdd(gimg + o + (int64_t)yy * W + xx, g * wgt);
+        if (tap_inside(yy, xx, H, W)) atomicAdd(gimg + o + (int64_t)yy * W + xx, g * wgt);
       };
-      put(y0, x0, wy0 * wx0); put(y0, x0 + 1, wy0 * wx1); put(y0 + 1, x0, wy1 * wx0); put(y0 + 1, x0 + 1, wy1 * wx1);
+      put(t.y0, t.x0, t.wy0 * t.wx0); put(t.y0, t.x0 + 1, t.wy0 * t.wx1);
+      put(t.y0 + 1, t.x0, t.wy1 * t.wx0); put(t.y0 + 1, t.x0 + 1, t.wy1 * t.wx1);
     }
   }
   if (gflow) {
@@ -677,30 +665,18 @@ __global__ __launch_bounds__(FB_TX * FB_TY) void flow_warp_l1_bwd_tiled_kernel(
   const int64_t r = live ? (int64_t)y * W + x : 0;
   float fx = 0.f, fy = 0.f;
   if (live) { fx = flow[(b * 2 + 0) * HW + r]; fy = flow[(b * 2 + 1) * HW + r]; }
-  const float gxn = (x + fx) / (float)(W - 1) * 2.f - 1.f, gyn = (y + fy) / (float)(H - 1) * 2.f - 1.f;
-  const float ix = ((gxn + 1.f) * W - 1.f) * 0.5f, iy = ((gyn + 1.f) * H - 1.f) * 0.5f;
+  float ix, iy;
+  resample2d_coord(x, y, fx, fy, H, W, ix, iy);
   const bool finite = live && fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;      // also false for NaN
-  const float flx = finite ? floorf(ix) : 0.f, fly = finite ? floorf(iy) : 0.f;
-  const int x0 = (int)flx, y0 = (int)fly;
-  const float wx1 = ix - flx, wy1 = iy - fly, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
+  const BilinearTaps t = bilinear_taps(finite ? ix : 0.f, finite ? iy : 0.f);
   const float gm = (live && gmetric) ? gmetric[(int64_t)b * HW + r] / (float)C : 0.f;
-  const int wx = x0 - (bx0 - FB_R), wy = y0 - (by0 - FB_R);             // window coordinates of the north-west tap
-  // neighbour relations inside the wave (lanes 0..31 = one tile row, 32..63 = the row below it; FB_TX == 32)
-  static_assert(FB_TX == 32, "the lane merges assume 32-pixel tile rows");
-  const int lane = threadIdx.x & 63;
-  const int fin = finite ? 1 : 0;
-  // (every shuffle is executed by all 64 lanes before anything is combined: no short-circuit around a cross-lane read)
-  const int fin_r = __shfl_down(fin, 1), x0_r = __shfl_down(x0, 1), y0_r = __shfl_down(y0, 1);
-  const int fin_d = __shfl_down(fin, 32), x0_d = __shfl_down(x0, 32), y0_d = __shfl_down(y0, 32);
-  const bool give_h = finite && (lane & 31) != 31 && fin_r != 0 && x0_r == x0 + 1 && y0_r == y0;
-  const bool give_v = finite && lane < 32 && fin_d != 0 && x0_d == x0 && y0_d == y0 + 1;
-  const int gh_l = __shfl_up(give_h ? 1 : 0, 1), gv_u = __shfl_up(give_v ? 1 : 0, 32);
-  const bool take_h = (lane & 31) != 0 && gh_l != 0;
-  const bool take_v = lane >= 32 && gv_u != 0;
+  const int wx = t.x0 - (bx0 - FB_R), wy = t.y0 - (by0 - FB_R);         // window coordinates of the north-west tap
+  const TapMerge mg = tap_merge_plan<FB_TX>(finite, t.x0, t.y0);        // neighbouring outputs share taps (bilinear_taps.h)
+  float* wflat = &win[0][0][0];
   float gix = 0.f, giy = 0.f;
   for (int c0 = 0; c0 < C; c0 += CC) {
     const int cc = min(CC, C - c0);
-    for (int e = threadIdx.x; e < cc * FB_WY * FB_WX; e += FB_TX * FB_TY) (&win[0][0][0])[e] = 0.f;
+    tap_window_zero(wflat, cc * FB_WY * FB_WX, FB_TX * FB_TY);
     __syncthreads();
     for (int c = 0; c < cc; ++c) {                      // every lane walks the channels: the merges below are wave-wide
       const int64_t o = ((int64_t)b * C + c0 + c) * HW;
@@ -712,43 +688,26 @@ __global__ __launch_bounds__(FB_TX * FB_TY) void flow_warp_l1_bwd_tiled_kernel(
           g += (d > 0.f) ? -gm : ((d < 0.f) ? gm : 0.f);
         }
         const T* base = img + o;
-        auto tap = [&](int yy, int xx) -> float {
-          return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? fw_ld(base, (int64_t)yy * W + xx) : 0.f;
-        };
-        const float t00 = tap(y0, x0), t01 = tap(y0, x0 + 1), t10 = tap(y0 + 1, x0), t11 = tap(y0 + 1, x0 + 1);
-        gix += g * ((t01 - t00) * wy0 + (t11 - t10) * wy1);
-        giy += g * ((t10 - t00) * wx0 + (t11 - t01) * wx1);
-        c00 = g * wy0 * wx0; c01 = g * wy0 * wx1; c10 = g * wy1 * wx0; c11 = g * wy1 * wx1;
+        auto tap = [&](int yy, int xx) -> float { return tap_inside(yy, xx, H, W) ? fw_ld(base, (int64_t)yy * W + xx) : 0.f; };
+        const float t00 = tap(t.y0, t.x0), t01 = tap(t.y0, t.x0 + 1), t10 = tap(t.y0 + 1, t.x0), t11 = tap(t.y0 + 1, t.x0 + 1);
+        gix += g * ((t01 - t00) * t.wy0 + (t11 - t10) * t.wy1);
+        giy += g * ((t10 - t00) * t.wx0 + (t11 - t01) * t.wx1);
+        c00 = g * t.wy0 * t.wx0; c01 = g * t.wy0 * t.wx1; c10 = g * t.wy1 * t.wx0; c11 = g * t.wy1 * t.wx1;
       }
-      // For a locally smooth flow the four taps of neighbouring output pixels coincide: the bottom taps of a pixel are the top
-      // taps of the pixel below it (the wave's other row), its right taps the left taps of its right neighbour.  The
-      // contributions are summed across lanes first, so an interior pixel issues ONE LDS atomic per channel instead of four
-      // (every lane then adds to a different address: no same-address serialisation inside the wave).
-      const float r10 = __shfl_up(c10, 32), r11 = __shfl_up(c11, 32);
-      if (take_v) { c00 += r10; c01 += r11; }
-      if (give_v) { c10 = 0.f; c11 = 0.f; }
-      const float s01 = __shfl_up(c01, 1), s11 = __shfl_up(c11, 1);
-      if (take_h) { c00 += s01; c10 += s11; }
-      if (give_h) { c01 = 0.f; c11 = 0.f; }
+      tap_merge(mg, c00, c01, c10, c11);
       auto put = [&](int dy, int dx, float val) {
-        const int yy = y0 + dy, xx = x0 + dx;
-        if (val != 0.f && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+        const int yy = t.y0 + dy, xx = t.x0 + dx;
+        if (val != 0.f && tap_inside(yy, xx, H, W)) {
           const int qy = wy + dy, qx = wx + dx;
-          if (qy >= 0 && qy < FB_WY && qx >= 0 && qx < FB_WX) atomicAdd(&win[c][qy][qx], val);
+          if (tap_inside(qy, qx, FB_WY, FB_WX)) atomicAdd(&win[c][qy][qx], val);
           else atomicAdd(gimg + o + (int64_t)yy * W + xx, val);
         }
       };
       if (finite) { put(0, 0, c00); put(0, 1, c01); put(1, 0, c10); put(1, 1, c11); }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < cc * FB_WY * FB_WX; e += FB_TX * FB_TY) {
-      const float v = (&win[0][0][0])[e];
-      if (v != 0.f) {
-        const int c = e / (FB_WY * FB_WX), q = e % (FB_WY * FB_WX);
-        const int gy = by0 - FB_R + q / FB_WX, gx = bx0 - FB_R + q % FB_WX;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) atomicAdd(gimg + ((int64_t)b * C + c0 + c) * HW + (int64_t)gy * W + gx, v);
-      }
-    }
+    tap_window_flush<FB_WY, FB_WX, FB_R>(wflat, cc, by0, bx0, H, W, gimg + ((int64_t)b * C + c0) * HW, FB_TX * FB_TY,
+                                         [](float* p, float v) { atomicAdd(p, v); });
     __syncthreads();
   }
   if (live && gflow) {

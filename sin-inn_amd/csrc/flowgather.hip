@@ -8,6 +8,7 @@
 // six ints a row -- idx0, idx1 (time slice), ch0, ch1 (0 or 2), then the bits of the floats c0, c1.  One launch whatever K is.
 // Every operation is rounded once and none is contracted (`flowsynth.gather_composed` evaluates the same expression in torch).
 #include "common.h"
+#include "bilinear_taps.h"
 
 namespace sininn {
 
@@ -29,15 +30,13 @@ __device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float g
   const float sx = c * gx, sy = c * gy;                   // the product is rounded, then the sum
   const float qx = (float)x + sx, qy = (float)y + sy;
   if (!(fabsf(qx) < 1e9f) || !(fabsf(qy) < 1e9f)) return t;       // NaN and inf fail the comparison too
-  const float flx = floorf(qx), fly = floorf(qy);
-  const int x0 = (int)flx, y0 = (int)fly;
-  const float wx1 = qx - flx, wy1 = qy - fly, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
-  const bool xa = x0 >= 0 && x0 < W, xb = x0 + 1 >= 0 && x0 + 1 < W, ya = y0 >= 0 && y0 < H, yb = y0 + 1 >= 0 && y0 + 1 < H;
+  const BilinearTaps b = bilinear_taps(qx, qy);
+  const bool xa = b.x0 >= 0 && b.x0 < W, xb = b.x0 + 1 >= 0 && b.x0 + 1 < W, ya = b.y0 >= 0 && b.y0 < H, yb = b.y0 + 1 >= 0 && b.y0 + 1 < H;
   t.v00 = ya && xa; t.v01 = ya && xb; t.v10 = yb && xa; t.v11 = yb && xb;
-  t.w00 = t.v00 ? wy0 * wx0 : 0.f; t.w01 = t.v01 ? wy0 * wx1 : 0.f;
-  t.w10 = t.v10 ? wy1 * wx0 : 0.f; t.w11 = t.v11 ? wy1 * wx1 : 0.f;
+  t.w00 = t.v00 ? b.wy0 * b.wx0 : 0.f; t.w01 = t.v01 ? b.wy0 * b.wx1 : 0.f;
+  t.w10 = t.v10 ? b.wy1 * b.wx0 : 0.f; t.w11 = t.v11 ? b.wy1 * b.wx1 : 0.f;
   t.n = ((t.w00 + t.w01) + t.w10) + t.w11;
-  t.nw = (int64_t)y0 * W + x0;                            // read only through a tap that is inside
+  t.nw = (int64_t)b.y0 * W + b.x0;                           // read only through a tap that is inside
   return t;
 }
 
@@ -69,7 +68,7 @@ __device__ __forceinline__ void gather_pixel(const float* __restrict__ i0b, cons
     const float num = (a0 * w0 + a1 * w1) + e * lin;
     const float v = __fdiv_rn(num, den);
     out[o + c * HW] = v;
-    if (out_u8) out_u8[o + c * HW] = (uint8_t)fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f);
+    if (out_u8) out_u8[o + c * HW] = (uint8_t)frame_byte(v);
   }
 }
 

@@ -6,13 +6,13 @@
 // (coalesced along x), scatters use the hardware fp32 atomic add (no CAS loop), the census kernel stages the two
 // grey-level tiles (+ halo) in LDS so every image byte is read once.
 #include "common.h"
-#include "splat_taps.h"
+#include "bilinear_taps.h"
 
 namespace sininn {
 
 // ------------------------------------------------------------------------------------------------
 // forward splat: out[b, c, y + fy .., x + fx ..] += in[b, c, y, x] * bilinear weight      (softsplat.py:8-52)
-//   atomic_add_f32, SplatTaps and splat_taps are in splat_taps.h
+//   atomic_add_f32, SplatTaps, splat_taps, the wave merge and the LDS window are in bilinear_taps.h
 // ------------------------------------------------------------------------------------------------
 // Block = 32 x 8 source pixels of one image.  Taps that land inside the block's window (tile + SP_R pixels all round)
 // are accumulated with LDS atomics (ds_add_f32) and the window is flushed once with coalesced global atomics; only taps
@@ -44,28 +44,14 @@ __global__ __launch_bounds__(SP_TX * SP_TY) void splat_fwd_kernel(const float* _
   }
   // window coordinates of the north-west tap
   const int wx = t.nwx - (x0 - SP_R), wy = t.nwy - (y0 - SP_R);
-  const bool in_nw = wx >= 0 && wx < SP_WX && wy >= 0 && wy < SP_WY;
-  const bool in_ne = wx + 1 >= 0 && wx + 1 < SP_WX && wy >= 0 && wy < SP_WY;
-  const bool in_sw = wx >= 0 && wx < SP_WX && wy + 1 >= 0 && wy + 1 < SP_WY;
-  const bool in_se = wx + 1 >= 0 && wx + 1 < SP_WX && wy + 1 >= 0 && wy + 1 < SP_WY;
+  const bool in_nw = tap_inside(wy, wx, SP_WY, SP_WX), in_ne = tap_inside(wy, wx + 1, SP_WY, SP_WX);
+  const bool in_sw = tap_inside(wy + 1, wx, SP_WY, SP_WX), in_se = tap_inside(wy + 1, wx + 1, SP_WY, SP_WX);
   const int64_t o_nw = (int64_t)t.nwy * W + t.nwx;
-  // For a locally smooth flow the taps of neighbouring source pixels coincide (the south taps of a pixel are the north taps of
-  // the pixel below it -- the wave's other row --, its east taps the west taps of its right neighbour): the contributions are
-  // summed across lanes first, so an interior pixel issues one atomic per channel instead of four, all to different addresses
-  // (as in flow_warp_l1_bwd_tiled_kernel).  Every shuffle is executed by all 64 lanes.
-  static_assert(SP_TX == 32, "the lane merges assume 32-pixel tile rows");
-  const int lane = threadIdx.x & 63;
-  const int anyi = any ? 1 : 0;
-  const int any_r = __shfl_down(anyi, 1), nwx_r = __shfl_down(t.nwx, 1), nwy_r = __shfl_down(t.nwy, 1);
-  const int any_d = __shfl_down(anyi, 32), nwx_d = __shfl_down(t.nwx, 32), nwy_d = __shfl_down(t.nwy, 32);
-  const bool give_h = any && (lane & 31) != 31 && any_r != 0 && nwx_r == t.nwx + 1 && nwy_r == t.nwy;
-  const bool give_v = any && lane < 32 && any_d != 0 && nwx_d == t.nwx && nwy_d == t.nwy + 1;
-  const int gh_l = __shfl_up(give_h ? 1 : 0, 1), gv_u = __shfl_up(give_v ? 1 : 0, 32);
-  const bool take_h = (lane & 31) != 0 && gh_l != 0;
-  const bool take_v = lane >= 32 && gv_u != 0;
+  const TapMerge mg = tap_merge_plan<SP_TX>(any, t.nwx, t.nwy);     // neighbouring sources share taps (bilinear_taps.h)
+  float* wflat = &win[0][0][0];
   for (int c0 = 0; c0 < C; c0 += SP_CC) {
     const int cc = min(SP_CC, C - c0);
-    for (int e = threadIdx.x; e < cc * SP_WY * SP_WX; e += blockDim.x) (&win[0][0][0])[e] = 0.f;
+    tap_window_zero(wflat, cc * SP_WY * SP_WX, blockDim.x);
     __syncthreads();
     for (int c = 0; c < cc; ++c) {                      // every lane walks the channels: the merges are wave-wide
       float cnw = 0.f, cne = 0.f, csw = 0.f, cse = 0.f;
@@ -73,15 +59,9 @@ __global__ __launch_bounds__(SP_TX * SP_TY) void splat_fwd_kernel(const float* _
         const float v = ONES ? 1.f : in[((int64_t)b * C + c0 + c) * HW + r];
         cnw = t.vnw ? v * t.nw : 0.f; cne = t.vne ? v * t.ne : 0.f; csw = t.vsw ? v * t.sw : 0.f; cse = t.vse ? v * t.se : 0.f;
       }
-      const float rsw = __shfl_up(csw, 32), rse = __shfl_up(cse, 32);
-      if (take_v) { cnw += rsw; cne += rse; }
-      if (give_v) { csw = 0.f; cse = 0.f; }
-      const float sne = __shfl_up(cne, 1), sse = __shfl_up(cse, 1);
-      if (take_h) { cnw += sne; csw += sse; }
-      if (give_h) { cne = 0.f; cse = 0.f; }
+      tap_merge(mg, cnw, cne, csw, cse);
       if (any) {
         float* o = out + ((int64_t)b * C + c0 + c) * HW;
-        // (a merged value lands where the receiving lane's own tap of that slot lands: same address, same validity)
         if (t.vnw && cnw != 0.f) { if (in_nw) atomic_add_f32(&win[c][wy][wx], cnw); else atomic_add_f32(o + o_nw, cnw); }
         if (t.vne && cne != 0.f) { if (in_ne) atomic_add_f32(&win[c][wy][wx + 1], cne); else atomic_add_f32(o + o_nw + 1, cne); }
         if (t.vsw && csw != 0.f) { if (in_sw) atomic_add_f32(&win[c][wy + 1][wx], csw); else atomic_add_f32(o + o_nw + W, csw); }
@@ -89,14 +69,8 @@ __global__ __launch_bounds__(SP_TX * SP_TY) void splat_fwd_kernel(const float* _
       }
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < cc * SP_WY * SP_WX; e += blockDim.x) {
-      const float v = (&win[0][0][0])[e];
-      if (v != 0.f) {
-        const int c = e / (SP_WY * SP_WX), q = e % (SP_WY * SP_WX);
-        const int gy = y0 - SP_R + q / SP_WX, gx = x0 - SP_R + q % SP_WX;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) atomic_add_f32(out + ((int64_t)b * C + c0 + c) * HW + (int64_t)gy * W + gx, v);
-      }
-    }
+    tap_window_flush<SP_WY, SP_WX, SP_R>(wflat, cc, y0, x0, H, W, out + ((int64_t)b * C + c0) * HW, blockDim.x,
+                                         [](float* p, float v) { atomic_add_f32(p, v); });
     __syncthreads();
   }
 }

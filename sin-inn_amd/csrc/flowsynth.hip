@@ -6,7 +6,7 @@
 // Two launches whatever K is: the scatter reads frame, flow and metric once and reuses them for every time; Z, the warped frame,
 // exp(Z) and the concatenated splat inputs never exist in HBM.  Both kernels are HBM / atomic bound.
 #include "common.h"
-#include "splat_taps.h"
+#include "bilinear_taps.h"
 
 namespace sininn {
 
@@ -14,26 +14,16 @@ constexpr int FS_TX = 32, FS_TY = 8;               // source tile of one block: 
 constexpr int FS_SCATTER_MAX_BLOCKS = 2048;   // the scatter launch: at most this many blocks, block-stride over the source tiles
 constexpr int FS_MAX_K = 64;
 
-// Resample2d (my_utils/resample2d.py:52-72) sample of img[b, c] at pixel (x, y) + flow, the rule of flow_warp_l1_kernel:
-// grid = (coords + flow) / (W - 1, H - 1) * 2 - 1 read with align_corners = False, zeros outside.  On an axis of length 1 that
-// coordinate is infinite (or 0 / 0): the sample lies outside the frame and is 0.
-struct WarpTaps {
-  int x0, y0;
-  float wx0, wx1, wy0, wy1;
-  bool ok;
-};
-
-__device__ __forceinline__ WarpTaps warp_taps(int x, int y, float fx, float fy, int H, int W) {
-  WarpTaps t = {};
-  if (H < 2 || W < 2) return t;
-  const float gxn = (x + fx) / (float)(W - 1) * 2.f - 1.f, gyn = (y + fy) / (float)(H - 1) * 2.f - 1.f;
-  const float ix = ((gxn + 1.f) * W - 1.f) * 0.5f, iy = ((gyn + 1.f) * H - 1.f) * 0.5f;
-  if (!(fabsf(ix) < 1e9f) || !(fabsf(iy) < 1e9f)) return t;          // the float -> int conversions below stay defined
-  const float flx = floorf(ix), fly = floorf(iy);
-  t.x0 = (int)flx; t.y0 = (int)fly;
-  t.wx1 = ix - flx; t.wy1 = iy - fly; t.wx0 = 1.f - t.wx1; t.wy0 = 1.f - t.wy1;
-  t.ok = true;
-  return t;
+// The Resample2d sample of img[b, c] at pixel (x, y) + flow (resample2d_coord, zeros outside): false where it has no tap inside the
+// frame at all -- on an axis of length 1 the coordinate is infinite (or 0 / 0) -- or the coordinate is too large for an int.
+__device__ __forceinline__ bool warp_taps(int x, int y, float fx, float fy, int H, int W, BilinearTaps& t) {
+  t = {};
+  if (H < 2 || W < 2) return false;
+  float ix, iy;
+  resample2d_coord(x, y, fx, fy, H, W, ix, iy);
+  if (!(fabsf(ix) < 1e9f) || !(fabsf(iy) < 1e9f)) return false;      // the float -> int conversions stay defined
+  t = bilinear_taps(ix, iy);
+  return true;
 }
 
 // Landing coordinate p + fl(t * f): the flow is scaled, rounded, then added to the pixel -- the same two roundings as splatting the
@@ -52,10 +42,9 @@ __global__ __launch_bounds__(FS_TX * FS_TY) void flowsynth_scatter_kernel(const 
                                                                           const float* __restrict__ f01, const float* __restrict__ f10,
                                                                           const float* __restrict__ tau, int B, int K, int H, int W,
                                                                           float* __restrict__ acc) {
-  static_assert(FS_TX == 32, "the lane merges assume 32-pixel tile rows");
   const int tiles_x = (W + FS_TX - 1) / FS_TX, tiles_y = (H + FS_TY - 1) / FS_TY;
   const int64_t HW = (int64_t)H * W, ntiles = (int64_t)2 * B * tiles_y * tiles_x;
-  const int lx = threadIdx.x % FS_TX, ly = threadIdx.x / FS_TX, lane = threadIdx.x & 63;
+  const int lx = threadIdx.x % FS_TX, ly = threadIdx.x / FS_TX;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {         // block-uniform: every shuffle below is wave-wide
     int64_t q = tile;
     const int tx = (int)(q % tiles_x); q /= tiles_x;
@@ -72,14 +61,13 @@ __global__ __launch_bounds__(FS_TX * FS_TY) void flowsynth_scatter_kernel(const 
     for (int c = 0; c <= C; ++c) v[c] = 0.f;
     if (live) {
       fx = flow[r]; fy = flow[HW + r];
-      const WarpTaps wt = warp_taps(x, y, fx, fy, H, W);
+      BilinearTaps wt;
+      const bool ok = warp_taps(x, y, fx, fy, H, W, wt);
       float l1 = 0.f;
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const float* base = oth + c * HW;
-        auto tap = [&](int yy, int xx) -> float {
-          return (wt.ok && yy >= 0 && yy < H && xx >= 0 && xx < W) ? base[(int64_t)yy * W + xx] : 0.f;
-        };
+        auto tap = [&](int yy, int xx) -> float { return (ok && tap_inside(yy, xx, H, W)) ? base[(int64_t)yy * W + xx] : 0.f; };
         const float t00 = tap(wt.y0, wt.x0), t10 = tap(wt.y0 + 1, wt.x0), t01 = tap(wt.y0, wt.x0 + 1), t11 = tap(wt.y0 + 1, wt.x0 + 1);
         const float warped = t00 * wt.wy0 * wt.wx0 + t01 * wt.wy0 * wt.wx1 + t10 * wt.wy1 * wt.wx0 + t11 * wt.wy1 * wt.wx1;
         v[c] = src[c * HW + r];
@@ -98,17 +86,7 @@ __global__ __launch_bounds__(FS_TX * FS_TY) void flowsynth_scatter_kernel(const 
         const float ox = landing(x, t, fx), oy = landing(y, t, fy);
         if (ox == ox && oy == oy && fabsf(ox) < 1e9f && fabsf(oy) < 1e9f) { tp = splat_taps(ox, oy, H, W); any = true; }
       }
-      // Neighbouring sources of a smooth flow share taps (splat_fwd_kernel): the south taps of a pixel are the north taps of the
-      // pixel below it (the wave's other row), its east taps the west taps of its right neighbour.  Contributions are summed
-      // across lanes first, so an interior pixel issues one atomic per channel, not four.
-      const int anyi = any ? 1 : 0;
-      const int any_r = __shfl_down(anyi, 1), nwx_r = __shfl_down(tp.nwx, 1), nwy_r = __shfl_down(tp.nwy, 1);
-      const int any_d = __shfl_down(anyi, 32), nwx_d = __shfl_down(tp.nwx, 32), nwy_d = __shfl_down(tp.nwy, 32);
-      const bool give_h = any && (lane & 31) != 31 && any_r != 0 && nwx_r == tp.nwx + 1 && nwy_r == tp.nwy;
-      const bool give_v = any && lane < 32 && any_d != 0 && nwx_d == tp.nwx && nwy_d == tp.nwy + 1;
-      const int gh_l = __shfl_up(give_h ? 1 : 0, 1), gv_u = __shfl_up(give_v ? 1 : 0, 32);
-      const bool take_h = (lane & 31) != 0 && gh_l != 0;
-      const bool take_v = lane >= 32 && gv_u != 0;
+      const TapMerge mg = tap_merge_plan<FS_TX>(any, tp.nwx, tp.nwy);       // neighbouring sources share taps (bilinear_taps.h)
       const int64_t o_nw = (int64_t)tp.nwy * W + tp.nwx;
       float* plane = acc + ((((int64_t)b * K + k) * 2 + side) * (C + 1)) * HW;
 #pragma unroll
@@ -118,14 +96,8 @@ __global__ __launch_bounds__(FS_TX * FS_TY) void flowsynth_scatter_kernel(const 
           cnw = tp.vnw ? v[c] * tp.nw : 0.f; cne = tp.vne ? v[c] * tp.ne : 0.f;
           csw = tp.vsw ? v[c] * tp.sw : 0.f; cse = tp.vse ? v[c] * tp.se : 0.f;
         }
-        const float rsw = __shfl_up(csw, 32), rse = __shfl_up(cse, 32);
-        if (take_v) { cnw += rsw; cne += rse; }
-        if (give_v) { csw = 0.f; cse = 0.f; }
-        const float sne = __shfl_up(cne, 1), sse = __shfl_up(cse, 1);
-        if (take_h) { cnw += sne; csw += sse; }
-        if (give_h) { cne = 0.f; cse = 0.f; }
+        tap_merge(mg, cnw, cne, csw, cse);
         if (any) {
-          // (a merged value lands where the receiving lane's own tap of that slot lands: same address, same validity)
           float* o = plane + c * HW;
           if (tp.vnw && cnw != 0.f) atomic_add_f32(o + o_nw, cnw);
           if (tp.vne && cne != 0.f) atomic_add_f32(o + o_nw + 1, cne);
@@ -166,7 +138,7 @@ __global__ void flowsynth_blend_kernel(const float* __restrict__ i0, const float
     }
     const int64_t q = (bk * C + c) * HW + r;
     out[q] = o;
-    if (out_u8) out_u8[q] = (uint8_t)fminf(fmaxf(rintf(__fmul_rn(o, 255.f)), 0.f), 255.f);
+    if (out_u8) out_u8[q] = (uint8_t)frame_byte(o);
   }
 }
 

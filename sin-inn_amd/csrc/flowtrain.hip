@@ -23,14 +23,7 @@ constexpr int FT_THREADS = 256;          // one pixel per thread: consecutive la
 constexpr int FT_WAVES = FT_THREADS / 64;
 constexpr int F2I_PIX = 1024;            // pixels of one frame per block in flow2img pass 1 (four per thread)
 
-// sum over the block in a fixed order (xor butterfly inside a wave, then the four waves as (0 + 1) + (2 + 3)); valid in thread 0
-__device__ __forceinline__ double ft_block_sum(double v, double* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
+static_assert(FT_WAVES == 4, "block_sum_f64 adds four waves");
 
 // ---- end-point error ------------------------------------------------------------------------------------------------------------
 
@@ -49,7 +42,7 @@ __global__ __launch_bounds__(FT_THREADS) void flow_epe_kernel(const float* __res
     const float du = f[0] - g[0], dv = f[hw] - g[hw];
     e = (double)sqrtf(du * du + dv * dv);
   }
-  const double sum = ft_block_sum(e, lds);
+  const double sum = block_sum_f64(e, lds);
   if (threadIdx.x == 0) part[blockIdx.x] = sum;
 }
 

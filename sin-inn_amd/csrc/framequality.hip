@@ -12,6 +12,7 @@
 // the last tile row and column also own the frame's last 10 rows and columns (all inside their halo), every pixel exactly once.
 // No loop is grid-strided: one block per tile.
 #include "common.h"
+#include "bilinear_taps.h"
 
 namespace sininn {
 
@@ -23,9 +24,6 @@ constexpr int FQ_FINISH_THREADS = 256;
 static_assert(FQ_THREADS == FQ_TX * FQ_TY / 2, "a thread evaluates two vertically adjacent windows");
 
 struct FqWindow { float g[FQ_WIN]; };
-
-// the byte rule of flowsynth_blend_kernel's u8 output: clamp(round-half-even(255 v), 0, 255); NaN gives 0
-__device__ __forceinline__ float fq_byte(float v) { return fminf(fmaxf(rintf(__fmul_rn(v, 255.f)), 0.f), 255.f); }
 
 // a fixed-order sum over the block: the tree is the same whatever the data
 __device__ __forceinline__ double fq_block_sum(double v, double* red, int tid, int threads) {
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(FQ_THREADS) void frame_quality_tile_kernel(const fl
       p = pp[(int64_t)y * W + x];
       t = tp[(int64_t)y * W + x];
       if (quantize) {
-        const float bp = fq_byte(p), bt = fq_byte(t);
+        const float bp = frame_byte(p), bt = frame_byte(t);
         if (ly < own_y && lx < own_x) {
           const int d = (int)bp - (int)bt;
           sq += (double)(d * d);                        // integers: every sum of them below 2^53 is exact

@@ -37,23 +37,15 @@ static inline LambWs lamb_ws(void* ws, int64_t n_chunks, int n_tensors) {
   return LambWs{f, d, d + nc, d + 2 * nc};
 }
 
-// Sum over the block, the same value in every thread.  Fixed order: xor butterfly inside a wave, then the four waves as (0 + 1) + (2 + 3).
-// Sums of squares are carried in double from the first addition on: two double FMAs per element are free next to five fp32 streams,
-// and a norm is then the norm of the fp32 values themselves, whatever the tensor's size.
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();                                   // lds may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
+// Block sums are block_sum_f64 (common.h).  Sums of squares are carried in double from the first addition on: two double FMAs per
+// element are free next to five fp32 streams, and a norm is then the norm of the fp32 values themselves, whatever the tensor's size.
+static_assert(LAMB_THREADS == 256, "block_sum_f64 adds four waves");
 
-// part[lo .. hi) added in index order: thread j takes lo + j, lo + j + 256, ..., then block_sum.
+// part[lo .. hi) added in index order: thread j takes lo + j, lo + j + 256, ..., then block_sum_f64.
 __device__ __forceinline__ double ordered_sum(const double* __restrict__ part, int64_t lo, int64_t hi, double* lds) {
   double acc = 0.0;
   for (int64_t c = lo + threadIdx.x; c < hi; c += LAMB_THREADS) acc += part[c];
-  return block_sum(acc, lds);
+  return block_sum_f64(acc, lds);
 }
 
 // The chunk table is device data the library cannot read on the host: a chunk that does not lie inside its tensor, inside the
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_gradnorm_kernel(const float
       }
       for (int i = (n4 << 2) + threadIdx.x; i < len; i += LAMB_THREADS) { const double s = (double)(gscale * gc[i]); acc += s * s; }
     }
-    acc = block_sum(acc, lds);
+    acc = block_sum_f64(acc, lds);
     if (threadIdx.x == 0) gpart[c] = acc;
   }
 }
@@ -136,7 +128,7 @@ __global__ __launch_bounds__(LAMB_THREADS) void lamb_stage1_kernel(const float* 
       }
       for (int i = (n4 << 2) + threadIdx.x; i < len; i += LAMB_THREADS) uc[i] = upd(pc[i], gc[i], mc[i], vc[i]);
     }
-    const double sp = block_sum(up2, lds), su = block_sum(uu2, lds);
+    const double sp = block_sum_f64(up2, lds), su = block_sum_f64(uu2, lds);
     if (threadIdx.x == 0) { ppart[c] = sp; upart[c] = su; }
   }
 }
