@@ -453,11 +453,13 @@ __global__ void affine_warp_kernel(const float* __restrict__ img, Str4 is, const
     decode4(idx, C, H, W, x_fastest, b, c, y, x);
     float ix, iy;
     affine_src(theta + b * 6, x, y, H, W, ix, iy);
-    const BilinearTaps t = bilinear_taps(ix, iy);
+    const bool finite = fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;            // also false for NaN: no footprint, the value is 0
+    const BilinearTaps t = bilinear_taps(finite ? ix : 0.f, finite ? iy : 0.f);
     const float* base = img + b * is.b + c * is.c;
     auto tap = [&](int yy, int xx) -> float { return tap_inside(yy, xx, H, W) ? base[yy * is.h + xx * is.w] : 0.f; };
-    const float val = tap(t.y0, t.x0) * t.wy0 * t.wx0 + tap(t.y0, t.x0 + 1) * t.wy0 * t.wx1 + tap(t.y0 + 1, t.x0) * t.wy1 * t.wx0 +
-                      tap(t.y0 + 1, t.x0 + 1) * t.wy1 * t.wx1;
+    float val = tap(t.y0, t.x0) * t.wy0 * t.wx0 + tap(t.y0, t.x0 + 1) * t.wy0 * t.wx1 + tap(t.y0 + 1, t.x0) * t.wy1 * t.wx0 +
+                tap(t.y0 + 1, t.x0 + 1) * t.wy1 * t.wx1;
+    if (!finite) val = 0.f;
     out[b * os.b + c * os.c + y * os.h + x * os.w] = val;
     if (ref) { const float d = val - ref[b * rs.b + c * rs.c + y * rs.h + x * rs.w]; acc += d * d; }
   }
@@ -492,6 +494,7 @@ __global__ void affine_warp_bwd_kernel(const float* __restrict__ gout, Str4 gs, 
     decode4(idx, C, H, W, x_fastest, b, c, y, x);
     float ix, iy;
     affine_src(theta + b * 6, x, y, H, W, ix, iy);
+    if (!(fabsf(ix) < 1e9f && fabsf(iy) < 1e9f)) continue;               // non-finite or huge: no footprint, nothing to add
     const BilinearTaps t = bilinear_taps(ix, iy);
     const float g = gout[b * gs.b + c * gs.c + y * gs.h + x * gs.w];
     float* base = gimg + b * gis.b + c * gis.c;
@@ -544,9 +547,12 @@ __global__ void flow_warp_l1_kernel(const T* __restrict__ img, const float* __re
   const float fx = flow[(b * 2 + 0) * HW + r], fy = flow[(b * 2 + 1) * HW + r];
   float ix, iy;
   resample2d_coord(x, y, fx, fy, H, W, ix, iy);
-  const BilinearTaps t = bilinear_taps(ix, iy);
+  // A non-finite or huge coordinate has no footprint: its value is 0.  The lane still walks every shuffle below, on the
+  // taps of coordinate 0, and hands its neighbour sample -1, so that no lane takes an east tap from it.
+  const bool finite = fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;              // also false for NaN
+  const BilinearTaps t = bilinear_taps(finite ? ix : 0.f, finite ? iy : 0.f);
   const int lane = threadIdx.x & 63;
-  const int nx0 = __shfl_down(t.x0, 1), ny0 = __shfl_down(t.y0, 1), nb = __shfl_down(b, 1);
+  const int nx0 = __shfl_down(t.x0, 1), ny0 = __shfl_down(t.y0, 1), nb = __shfl_down(finite ? b : -1, 1);
   const bool share = (lane < 63) && (nb == b) && (nx0 == t.x0 + 1) && (ny0 == t.y0);
   float l1 = 0.f;
   for (int c = 0; c < C; ++c) {
@@ -557,6 +563,7 @@ __global__ void flow_warp_l1_kernel(const T* __restrict__ img, const float* __re
     const float t01 = share ? n00 : tap(t.y0, t.x0 + 1);
     const float t11 = share ? n10 : tap(t.y0 + 1, t.x0 + 1);
     float val = t00 * t.wy0 * t.wx0 + t01 * t.wy0 * t.wx1 + t10 * t.wy1 * t.wx0 + t11 * t.wy1 * t.wx1;
+    if (!finite) val = 0.f;
     if (live) {
       if (warped) {
         fw_st(warped, ((int64_t)b * C + c) * HW + r, val);
@@ -605,7 +612,10 @@ __global__ void flow_warp_l1_bwd_kernel(const T* __restrict__ img, const float* 
   const float fx = flow[(b * 2 + 0) * HW + r], fy = flow[(b * 2 + 1) * HW + r];
   float ix, iy;
   resample2d_coord(x, y, fx, fy, H, W, ix, iy);
-  const BilinearTaps t = bilinear_taps(ix, iy);
+  // non-finite or huge: no footprint.  As in the tiled kernel such a lane walks the taps of coordinate 0; its sums are dropped at the
+  // end and it adds nothing to gimg.
+  const bool finite = fabsf(ix) < 1e9f && fabsf(iy) < 1e9f;              // also false for NaN
+  const BilinearTaps t = bilinear_taps(finite ? ix : 0.f, finite ? iy : 0.f);
   const float gm = gmetric ? gmetric[(int64_t)b * HW + r] / (float)C : 0.f;
   float gix = 0.f, giy = 0.f;
   for (int c = 0; c < C; ++c) {
@@ -620,7 +630,7 @@ __global__ void flow_warp_l1_bwd_kernel(const T* __restrict__ img, const float* 
     const float t00 = tap(t.y0, t.x0), t01 = tap(t.y0, t.x0 + 1), t10 = tap(t.y0 + 1, t.x0), t11 = tap(t.y0 + 1, t.x0 + 1);
     gix += g * ((t01 - t00) * t.wy0 + (t11 - t10) * t.wy1);
     giy += g * ((t10 - t00) * t.wx0 + (t11 - t01) * t.wx1);
-    if (gimg) {
+    if (gimg && finite) {
       auto put = [&](int yy, int xx, float wgt) {
         if (tap_inside(yy, xx, H, W)) atomicAdd(gimg + o + (int64_t)yy * W + xx, g * wgt);
       };
@@ -629,8 +639,8 @@ __global__ void flow_warp_l1_bwd_kernel(const T* __restrict__ img, const float* 
     }
   }
   if (gflow) {
-    gflow[(b * 2 + 0) * HW + r] = gix * (float)W / (float)(W - 1);
-    gflow[(b * 2 + 1) * HW + r] = giy * (float)H / (float)(H - 1);
+    gflow[(b * 2 + 0) * HW + r] = finite ? gix * (float)W / (float)(W - 1) : 0.f;
+    gflow[(b * 2 + 1) * HW + r] = finite ? giy * (float)H / (float)(H - 1) : 0.f;
   }
 }
 

@@ -1,4 +1,5 @@
-"""Microbenchmark of the flow-loss operators (csrc/flowloss.hip) at BASELINE config-3 size (512x512) on the GPU box:
+"""Microbenchmark of the flow-loss operators (csrc/flowloss.hip) and the two warps of csrc/elementwise.hip (flow warp + L1 at batch
+16, affine warp at 16 x 3 x 256 x 256) at BASELINE config-3 size (512x512) on the GPU box:
     python tools/bench_flowloss.py [--batch 4] [--size 512] [--reps 20]
 Prints time and achieved GB/s of ALGORITHMIC bytes (every operand read / written once) against the 8 TB/s HBM roof."""
 import argparse
@@ -105,6 +106,22 @@ def main():
     s4 = sflow[:b].contiguous()
     rows.append(('softsplat fwd, smooth flow', timeit(lambda: lib.sininn_softsplat(ptr(x4), ptr(s4), b, 4, h, w, ptr(out), st()), a.reps), px * 4 * (4 + 2 + 4)))
     rows.append(('occlusion_wang, smooth flow', timeit(lambda: lib.sininn_occlusion_wang(ptr(s4), b, h, w, 0.7, ptr(corr), ptr(m), st()), a.reps), px * 4 * (2 + 1 + 1 + 1)))
+    # the affine warp of tcr.py at BASELINE configs[1] size (batch 16, 256 x 256): a rotation of 5 degrees and a small shift
+    ab, ah = 16, 256
+    apx = ab * 3 * ah * ah
+    aimg = torch.rand(ab, 3, ah, ah, device=dev); aout = torch.empty_like(aimg)
+    agout = torch.randn_like(aimg); agimg = torch.zeros_like(aimg)
+    ca, sa = 0.9961947, 0.0871557
+    theta = torch.tensor([[ca, sa, 0.02], [-sa, ca, -0.03]], device=dev).repeat(ab, 1, 1).contiguous()
+    s4x = FL._lib.I64x4(*aimg.stride())
+    rows.append(('affine_warp fwd (batch 16, 256 x 256)',
+                 timeit(lambda: lib.sininn_affine_warp(ptr(aimg), s4x, ptr(theta), ab, 3, ah, ah, ptr(aout), s4x, None, FL._lib.I64x4(), None, st()), a.reps),
+                 apx * 4 * 2))
+
+    def aff_bwd():
+        agimg.zero_()
+        lib.sininn_affine_warp_bwd(ptr(agout), s4x, ptr(theta), ab, 3, ah, ah, ptr(agimg), s4x, st())
+    rows.append(('affine_warp bwd (batch 16, 256 x 256, incl. zero fill)', timeit(aff_bwd, a.reps), apx * 4 * 3))
     for name, ms, nbytes in rows:
         print(f'{name:66s} {ms * 1e3:9.1f} us  {nbytes / ms / 1e6:8.1f} GB/s algorithmic = {nbytes / ms / 1e6 / 8000 * 100:5.1f} % of the HBM roof')
 
