@@ -1046,10 +1046,29 @@ int sininn_frame_quality(const float* pred, const float* target, int B, int C, i
  * The slot table is NOT validated on the device: the caller guarantees 0 <= idx < T' and ch in {0, 2}.  k_loop != 0: a lane walks the
  * K times of its pixel and loads i0(p), i1(p) once; 0: one lane per (b, k, y, x).  Both give the same bits.  One launch whatever K is,
  * no workspace, no atomics: equal inputs give equal bits, and a frame's result does not depend on B or on its place in the batch.
- * H W <= 2^31 - 1 and B K ceil(H W / 256) <= 2^31 - 1.  Not differentiable. */
+ * H W <= 2^31 - 1 and B K ceil(H W / 256) <= 2^31 - 1.  Its gradient with respect to `flows`: sininn_flow_gather_bwd. */
 int sininn_flow_gather(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
                        const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, unsigned char* out_u8,
                        void* stream);
+
+/* The gradient of sininn_flow_gather with respect to `flows`.  i0 .. tau, B .. W as in sininn_flow_gather; grad_out:
+ * DEVICE (B, K, C, H, W), contiguous, d loss / d out.  dflows: DEVICE (T, 4, H, W), contiguous, every element written.  At pixel p
+ * of row (b, k), with D = a0 n0 + a1 n1 + e and out_c recomputed as the forward pass rounds it,
+ *   dG0 = c0 a0 / D  sum_c g_c (grad_q W0_c - out_c grad_q n0),   dG1 = c1 a1 / D  sum_c g_c (grad_q W1_c - out_c grad_q n1)
+ * grad_q: the derivative of the bilinear interpolant of the zero-padded plane in the cell floor(q) (on a cell border: the right-hand
+ * derivative); a sample whose coordinate is not finite, or 1e9 or more in size, has gradient 0.  dG0 is added to channels ch0, ch0 + 1
+ * of slice idx0, dG1 to channels ch1, ch1 + 1 of slice idx1; elements no row names are 0.  No gradient to the frames, tau or the
+ * coefficients.  No atomics: the rows that share a target are summed in ascending b K + k, dG0 before dG1.
+ * reduce_list: DEVICE ints, NOT validated on the device -- for each of the 2 T targets (2 slice + ch / 2) the begin of its entries,
+ * 2 T + 1 ints (the last: the number of entries), then the entries 2 (b K + k) + which (0: dG0, 1: dG1), ascending within a target;
+ * reduce_ints: its length.  Two launches: the per-row gradients go to `workspace` (DEVICE floats, at least what the _workspace call
+ * returns, B K 4 H W; 0 for a non-positive size; no initialisation), a second kernel sums them.  reduce_list == NULL: the caller
+ * guarantees that no two (row, sample) name the same target; dflows is zeroed and the one kernel writes in place, `workspace` is
+ * not used and may be NULL.  Both paths give the same bits on such a table.  T 4 ceil(H W / 256) <= 2^31 - 1.  Once differentiable. */
+int64_t sininn_flow_gather_bwd_workspace(int B, int K, int H, int W);
+int sininn_flow_gather_bwd(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                           const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
+                           int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, void* stream);
 
 #ifdef __cplusplus
 }

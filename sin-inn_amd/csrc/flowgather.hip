@@ -4,6 +4,7 @@
 //   (W0, n0) = sample(I0, q0),  (W1, n1) = sample(I1, q1)        exact-geometry bilinear; a tap outside the frame adds 0 to W and to n
 //   a0 = 1 - tau, a1 = tau,  L = a0 I0(p) + a1 I1(p)
 //   out = (a0 W0 + a1 W1 + e L) / (a0 n0 + a1 n1 + e),  e = 2^-10
+// The gradient with respect to the flows is at the end of the file: flowgather_bwd_kernel and flowgather_reduce_kernel.
 // G0 and G1 are channel pairs of time slices of one (T', 4, H, W) tensor, named per (b, k) by a slot table the host has validated:
 // six ints a row -- idx0, idx1 (time slice), ch0, ch1 (0 or 2), then the bits of the floats c0, c1.  One launch whatever K is.
 // Every operation is rounded once and none is contracted (`flowsynth.gather_composed` evaluates the same expression in torch).
@@ -18,9 +19,11 @@ constexpr int FG_SLOT_INTS = 6;
 
 // The four taps of one sample: the offset of the north-west tap and the weights, zero where the tap lies outside the frame.
 // n is the sum of the weights inside.  A coordinate that is not finite, or too large for an int, has no tap inside.
+// wx0 .. wy1 are the four one-dimensional weights of the cell floor(q) (zero without a tap inside): the backward pass differentiates them.
 struct GatherTaps {
   int64_t nw;
   float w00, w01, w10, w11, n;
+  float wx0, wx1, wy0, wy1;
   bool v00, v01, v10, v11;
 };
 
@@ -33,6 +36,7 @@ __device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float g
   const BilinearTaps b = bilinear_taps(qx, qy);
   const bool xa = b.x0 >= 0 && b.x0 < W, xb = b.x0 + 1 >= 0 && b.x0 + 1 < W, ya = b.y0 >= 0 && b.y0 < H, yb = b.y0 + 1 >= 0 && b.y0 + 1 < H;
   t.v00 = ya && xa; t.v01 = ya && xb; t.v10 = yb && xa; t.v11 = yb && xb;
+  t.wx0 = b.wx0; t.wx1 = b.wx1; t.wy0 = b.wy0; t.wy1 = b.wy1;
   t.w00 = t.v00 ? b.wy0 * b.wx0 : 0.f; t.w01 = t.v01 ? b.wy0 * b.wx1 : 0.f;
   t.w10 = t.v10 ? b.wy1 * b.wx0 : 0.f; t.w11 = t.v11 ? b.wy1 * b.wx1 : 0.f;
   t.n = ((t.w00 + t.w01) + t.w10) + t.w11;
@@ -127,6 +131,170 @@ int flow_gather_launch(const float* i0, const float* i1, const float* flows, int
   else        { if (k_loop) FG_LAUNCH(3, true); else FG_LAUNCH(3, false); }
 #undef FG_LAUNCH
   SININN_LAUNCH_CHECK("flowgather");
+  return 0;
+}
+
+// ---- the gradient with respect to the flows ----
+//   dG0 = c0 a0 / D  sum_c g_c (grad_q W0_c - out_c grad_q n0),   dG1 = c1 a1 / D  sum_c g_c (grad_q W1_c - out_c grad_q n1)
+// grad_q is the derivative of the bilinear interpolant of the zero-padded plane inside the cell floor(q) the forward pass took (on a
+// cell border: the right-hand derivative).  A sample without a tap (a coordinate that is not finite, or 1e9 or more in size) has all
+// weights zero, so its gradient is 0.  No gradient to the frames, tau or the coefficients.
+
+// The slopes of one sampled plane along x and y: taps outside the frame are 0.
+__device__ __forceinline__ void gather_slopes(const float* __restrict__ plane, const GatherTaps& t, int W, float& dx, float& dy) {
+#pragma clang fp contract(off)
+  const float t00 = t.v00 ? plane[t.nw] : 0.f, t01 = t.v01 ? plane[t.nw + 1] : 0.f;
+  const float t10 = t.v10 ? plane[t.nw + W] : 0.f, t11 = t.v11 ? plane[t.nw + W + 1] : 0.f;
+  dx = t.wy0 * (t01 - t00) + t.wy1 * (t11 - t10);
+  dy = t.wx0 * (t10 - t00) + t.wx1 * (t11 - t01);
+}
+
+// The same for the all-ones image: the slopes of n.
+__device__ __forceinline__ void gather_slopes_ones(const GatherTaps& t, float& dx, float& dy) {
+#pragma clang fp contract(off)
+  const float t00 = t.v00 ? 1.f : 0.f, t01 = t.v01 ? 1.f : 0.f, t10 = t.v10 ? 1.f : 0.f, t11 = t.v11 ? 1.f : 0.f;
+  dx = t.wy0 * (t01 - t00) + t.wy1 * (t11 - t10);
+  dy = t.wx0 * (t10 - t00) + t.wx1 * (t11 - t01);
+}
+
+// One lane per (b, k, y, x), the forward kernel's KLOOP = false shape.  The lane recomputes the two tap sets and out_c exactly as the
+// forward pass rounds them, reads C words of g and writes four floats: dG0 (x, y), dG1 (x, y).  `dflows` == nullptr: into the per-row
+// buffer `rows` (B, K, 4, H, W), which flowgather_reduce_kernel sums per target.  Otherwise straight into channels ch0, ch0 + 1 of
+// slice idx0 and ch1, ch1 + 1 of slice idx1 of the contiguous (T, 4, H, W) `dflows`: the host guarantees that no two rows share a
+// target.  Either way the addresses of a wave are 64 consecutive floats of one plane.
+template <int C>
+__global__ __launch_bounds__(FG_THREADS) void flowgather_bwd_kernel(const float* __restrict__ i0, const float* __restrict__ i1,
+                                                                    const float* __restrict__ flows, int64_t flow_stride,
+                                                                    const int* __restrict__ slots, const float* __restrict__ tau,
+                                                                    const float* __restrict__ gout, int K, int H, int W, int tiles,
+                                                                    float* __restrict__ rows, float* __restrict__ dflows) {
+#pragma clang fp contract(off)
+  const int64_t HW = (int64_t)H * W;
+  const unsigned frame = blockIdx.x / (unsigned)tiles;    // b K + k
+  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;         // H W < 2^31: 32-bit divisions only
+  if (pix >= HW) return;
+  const int x = (int)(pix % (unsigned)W), y = (int)(pix / (unsigned)W);
+  const int64_t r = pix, bk = frame, b = frame / (unsigned)K;
+  const float* i0b = i0 + b * C * HW;
+  const float* i1b = i1 + b * C * HW;
+  const int* slot = slots + bk * FG_SLOT_INTS;
+  const float tk = tau[frame % (unsigned)K];
+  const float* g0 = flows + slot[0] * flow_stride + slot[2] * HW + r;
+  const float* g1 = flows + slot[1] * flow_stride + slot[3] * HW + r;
+  const float c0 = __int_as_float(slot[4]), c1 = __int_as_float(slot[5]);
+  const GatherTaps t0 = gather_taps(x, y, c0, g0[0], g0[HW], H, W);
+  const GatherTaps t1 = gather_taps(x, y, c1, g1[0], g1[HW], H, W);
+  const float a0 = 1.f - tk, a1 = tk, e = 0.0009765625f;
+  const float den = (a0 * t0.n + a1 * t1.n) + e;
+  float n0x, n0y, n1x, n1y;
+  gather_slopes_ones(t0, n0x, n0y);
+  gather_slopes_ones(t1, n1x, n1y);
+  float s0x = 0.f, s0y = 0.f, s1x = 0.f, s1y = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const float w0 = gather_sample(i0b + c * HW, t0, W), w1 = gather_sample(i1b + c * HW, t1, W);
+    const float lin = a0 * i0b[c * HW + r] + a1 * i1b[c * HW + r];
+    const float num = (a0 * w0 + a1 * w1) + e * lin;
+    const float v = __fdiv_rn(num, den);                    // out_c, the forward pass's bits
+    const float g = gout[(bk * C + c) * HW + r];
+    float w0x, w0y, w1x, w1y;
+    gather_slopes(i0b + c * HW, t0, W, w0x, w0y);
+    gather_slopes(i1b + c * HW, t1, W, w1x, w1y);
+    s0x = s0x + g * (w0x - v * n0x); s0y = s0y + g * (w0y - v * n0y);
+    s1x = s1x + g * (w1x - v * n1x); s1y = s1y + g * (w1y - v * n1y);
+  }
+  const float k0 = __fdiv_rn(c0 * a0, den), k1 = __fdiv_rn(c1 * a1, den);
+  float* d0;
+  float* d1;
+  if (dflows) {
+    d0 = dflows + (slot[0] * (int64_t)4 + slot[2]) * HW + r;
+    d1 = dflows + (slot[1] * (int64_t)4 + slot[3]) * HW + r;
+  } else {
+    d0 = rows + bk * 4 * HW + r;
+    d1 = d0 + 2 * HW;
+  }
+  d0[0] = k0 * s0x; d0[HW] = k0 * s0y;
+  d1[0] = k1 * s1x; d1[HW] = k1 * s1y;
+}
+
+// One lane per element of dflows.  `list`: for each of the 2 T targets (slice, channel pair) -- target 2 slice + pair -- the begin of its
+// entries, 2 T + 1 ints, then the entries: 2 (b K + k) + which (0: dG0, 1: dG1), ascending within a target, so the sum has a fixed
+// order; the first entry starts the sum (a target with one entry gets that entry's bits, the in-place path's), no entry gives 0.
+__global__ __launch_bounds__(FG_THREADS) void flowgather_reduce_kernel(const float* __restrict__ rows, const int* __restrict__ list,
+                                                                       int targets, int H, int W, int tiles,
+                                                                       float* __restrict__ dflows) {
+#pragma clang fp contract(off)
+  const int64_t HW = (int64_t)H * W;
+  const unsigned plane = blockIdx.x / (unsigned)tiles;    // 2 target + component
+  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;
+  if (pix >= HW) return;
+  const unsigned target = plane >> 1, comp = plane & 1;
+  const int begin = list[target], end = list[target + 1];
+  const int* entries = list + targets + 1;
+  float sum = 0.f;
+  for (int i = begin; i < end; ++i) {
+    const float v = rows[((int64_t)entries[i] * 2 + comp) * HW + pix];
+    sum = i == begin ? v : sum + v;
+  }
+  dflows[(int64_t)plane * HW + pix] = sum;
+}
+
+int64_t flow_gather_bwd_workspace(int B, int K, int H, int W) {
+  if (B <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
+  const int64_t HW = (int64_t)H * W;
+  if ((int64_t)B * K * 4 > INT64_MAX / HW) return 0;
+  return (int64_t)B * K * 4 * HW;
+}
+
+int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                           const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
+                           int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, hipStream_t st) {
+  SININN_CHECK(i0 && i1 && flows && slots && tau, "flow_gather_bwd: null pointer");
+  SININN_CHECK(grad_out, "flow_gather_bwd: the gradient of the output is null");
+  SININN_CHECK(dflows, "flow_gather_bwd: the gradient of the flows is null");
+  SININN_CHECK(B > 0 && H > 0 && W > 0 && T > 0, "flow_gather_bwd: bad shape (every size must be positive)");
+  SININN_CHECK(C == 1 || C == 3, "flow_gather_bwd: frames have 1 or 3 channels (got %d)", C);
+  SININN_CHECK(K >= 1 && K <= FG_MAX_K, "flow_gather_bwd: K = %d times in one call, 1 to %d are supported", K, FG_MAX_K);
+  const int64_t HW = (int64_t)H * W;
+  SININN_CHECK(HW <= 0x7fffffff, "flow_gather_bwd: H * W = %lld is past an int index", (long long)HW);
+  const int64_t tiles = (HW + FG_THREADS - 1) / FG_THREADS;
+  SININN_CHECK((int64_t)B * K * tiles <= 0x7fffffff, "flow_gather_bwd: B * K * H * W = %lld needs more blocks than one launch has",
+               (long long)B * K * HW);
+  SININN_CHECK((int64_t)B * K * (C > 4 ? C : 4) <= INT64_MAX / HW, "flow_gather_bwd: B * K * C * H * W is past a 64-bit index");
+  SININN_CHECK(flow_sample_stride >= 4 * HW, "flow_gather_bwd: sample stride %lld is smaller than four channel planes (%lld)",
+               (long long)flow_sample_stride, (long long)(4 * HW));
+  SININN_CHECK((int64_t)T * 4 * tiles <= 0x7fffffff, "flow_gather_bwd: T * 4 * H * W = %lld needs more blocks than one launch has",
+               (long long)T * 4 * HW);
+  if (reduce_list) {
+    SININN_CHECK(workspace, "flow_gather_bwd: the workspace is null");
+    SININN_CHECK(workspace_floats >= flow_gather_bwd_workspace(B, K, H, W),
+                 "flow_gather_bwd: the workspace holds %lld floats, %lld are needed", (long long)workspace_floats,
+                 (long long)flow_gather_bwd_workspace(B, K, H, W));
+    SININN_CHECK(reduce_ints >= 2 * (int64_t)T + 1 && reduce_ints <= 2 * (int64_t)T + 1 + 2 * (int64_t)B * K,
+                 "flow_gather_bwd: a reduce list of %lld ints; 2 T + 1 begins and at most 2 B K entries are expected",
+                 (long long)reduce_ints);
+  }
+  const dim3 block(FG_THREADS);
+  const dim3 grid((unsigned)((int64_t)B * K * tiles));
+  if (!reduce_list) {       // in place: the targets no row names stay 0
+    SININN_CHECK(hipMemsetAsync(dflows, 0, sizeof(float) * 4 * (size_t)T * (size_t)HW, st) == hipSuccess,
+                 "flow_gather_bwd: hipMemsetAsync failed");
+  }
+  float* rows = reduce_list ? workspace : nullptr;
+  float* direct = reduce_list ? nullptr : dflows;
+  if (C == 1)
+    hipLaunchKernelGGL((flowgather_bwd_kernel<1>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, grad_out, K, H, W,
+                       (int)tiles, rows, direct);
+  else
+    hipLaunchKernelGGL((flowgather_bwd_kernel<3>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, grad_out, K, H, W,
+                       (int)tiles, rows, direct);
+  SININN_LAUNCH_CHECK("flowgather_bwd");
+  if (reduce_list) {
+    const dim3 rgrid((unsigned)((int64_t)T * 4 * tiles));
+    hipLaunchKernelGGL(flowgather_reduce_kernel, rgrid, block, 0, st, (const float*)workspace, reduce_list, 2 * T, H, W, (int)tiles,
+                       dflows);
+    SININN_LAUNCH_CHECK("flowgather_reduce");
+  }
   return 0;
 }
 

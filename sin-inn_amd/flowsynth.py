@@ -30,7 +30,19 @@ backward); per output frame (b, k) the slot table names the time slice and chann
 `sample` is the bilinear gather with pixel centres at integers (not Resample2d's geometry): a tap outside the frame adds 0 to W and to
 n, the sum of the weights inside.  The regular slot is G1 = fw(s), c1 = 1 - tau, G0 = bw(s - dt), c0 = tau; where s - dt lies before
 the clip's first frame, and throughout under back='reverse', G0 = fw(s) with c0 = -tau (constant velocity).  No atomics and no
-accumulator: equal inputs give equal bits.  No gradient.
+accumulator: equal inputs give equal bits.
+
+    gather(.., flow_grad=True), gather_composed(.., flow_grad=True)    the result carries a gradient to `flows`
+    gather_reduce_list(slots, slices)                                  host logic: which rows add to which slice, in which order
+
+Without the keyword both are inference operators and refuse inputs that require grad.  With it, `gather` differentiates with respect to
+the flows -- and nothing else: not the frames, tau or the coefficients; once -- through the backward kernels of csrc/flowgather.hip:
+
+    dG0 = c0 a0 / D  sum_c g_c (grad_q W0_c - out_c grad_q n0),   dG1 likewise;   D = a0 n0 + a1 n1 + e
+
+grad_q is the derivative of the bilinear interpolant of the zero-padded plane in the cell floor(q) (on a cell border the right-hand
+derivative, what autograd gives through `gather_from`); a sample whose coordinate is not finite, or 1e9 or more in size, has gradient 0.
+Rows that name the same slice and channel pair are summed in ascending b K + k, dG0 before dG1, without atomics.
 
     quality(pred, target)            PSNR and mean SSIM per frame, the fused operator of csrc/framequality.hip
     quality_composed(pred, target)   the same definition from torch ops, on any device, fp32 or fp64: its A/B partner and reference
@@ -175,6 +187,8 @@ def composed(frame1, frame2, flow12, flow21, taus):
 
 GATHER_EPS = 2.0 ** -10
 SLOT_INTS = 6           # FG_SLOT_INTS of csrc/flowgather.hip: idx0, idx1, ch0, ch1, bits of c0, bits of c1
+BWD_IN_PLACE = None     # the backward path of `gather(.., flow_grad=True)`: None: one launch where the table's targets are distinct, else
+                        # two; True / False force a path (True needs distinct targets).  Both give the same bits
 K_LOOP = False          # the launch shape of `gather`: one lane per (b, k, y, x); True: a lane walks the K times of its pixel
 DeviceSlots = collections.namedtuple('DeviceSlots', 'table slices')     # a validated table on the device; slices: the T' it needs
 
@@ -252,9 +266,11 @@ def upload_slots(slots, device):
     return DeviceSlots(slots.contiguous().to(device), _host_slots('upload_slots', slots, b, k))
 
 
-def _gather_inputs(who, frame1, frame2, flows):
-    for t in (frame1, frame2, flows):
+def _gather_inputs(who, frame1, frame2, flows, flow_grad=False):
+    for t in (frame1, frame2) if flow_grad else (frame1, frame2, flows):
         if t.requires_grad and torch.is_grad_enabled():
+            if flow_grad:
+                raise RuntimeError(f'flowsynth.{who}(.., flow_grad=True) has a gradient with respect to the flows only: detach the frames')
             raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
                                '(or call it under torch.no_grad())')
     b, c, h, w = frame1.shape
@@ -274,12 +290,95 @@ def joined_flows(flow12, flow21):
     return flow12.as_strided((t, 4, h, w), flow12.stride(), flow12.storage_offset())
 
 
-def gather(frame1, frame2, flows, slots, taus, *, out=None, u8=False, k_loop=None):
+def gather_reduce_list(slots, slices):
+    """The order in which the backward pass sums the per-row gradients into d flows (`slices`, 4, H, W), from a host slot table
+    (B, K, 6).  Target 2 slice + ch / 2 is one channel pair of one slice; entry 2 (b K + k) + which is dG0 (which = 0) or dG1 (1) of
+    row (b, k).  Returns (list, distinct): `list` the Python ints the kernel reads -- the 2 slices + 1 begins of the targets' entries
+    (the last: the number of entries), then the entries, ascending within a target (ascending b K + k, dG0 before dG1) -- and
+    `distinct`: no target has more than one entry.  Pure host logic."""
+    b, k, _ = slots.shape
+    rows = slots.reshape(b * k, SLOT_INTS).tolist()
+    per = [[] for _ in range(2 * slices)]
+    for bk, (idx0, idx1, ch0, ch1, _c0, _c1) in enumerate(rows):
+        for which, (idx, ch) in enumerate(((idx0, ch0), (idx1, ch1))):
+            if not (0 <= idx < slices and ch in (0, 2)):
+                raise ValueError(f'flowsynth.gather_reduce_list: row {bk} names slice {idx}, channel {ch}; there are {slices} slices')
+            per[2 * idx + ch // 2].append(2 * bk + which)           # visited in ascending 2 bk + which
+    begins, entries = [0], []
+    for target in per:
+        entries.extend(target)
+        begins.append(len(entries))
+    return begins + entries, all(len(target) <= 1 for target in per)
+
+
+class _GatherFlowGrad(torch.autograd.Function):
+    """`gather` with a gradient to `flows`: the forward kernel, then sininn_flow_gather_bwd on the path `BWD_IN_PLACE` names"""
+
+    @staticmethod
+    def forward(ctx, flows, frame1, frame2, host_slots, table, tau, values, k_loop):
+        ctx.save_for_backward(flows, frame1, frame2, table, tau)
+        ctx.host_slots = host_slots
+        with torch.no_grad():
+            return gather(frame1, frame2, flows, DeviceSlots(table, flows.shape[0]), values, k_loop=k_loop)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        flows, frame1, frame2, table, tau = ctx.saved_tensors
+        b, c, h, w = frame1.shape
+        k, t = table.shape[1], flows.shape[0]
+        grad_out = _gpu32(grad_out).contiguous()
+        assert tuple(grad_out.shape) == (b, k, c, h, w)
+        ints, distinct = gather_reduce_list(ctx.host_slots, t)
+        in_place = distinct if BWD_IN_PLACE is None else bool(BWD_IN_PLACE)
+        if in_place and not distinct:
+            raise ValueError('flowsynth.gather: the in-place backward needs a table whose (slice, channel pair) targets are distinct')
+        dev = frame1.device
+        dflows = torch.empty((t, 4, h, w), device=dev, dtype=torch.float32)
+        stride = flows.stride(0) if t > 1 else 4 * h * w
+        lib = _lib.lib()
+        if in_place:
+            rlist, n_ints, ws, n_ws = None, 0, None, 0
+        else:
+            rl = torch.tensor(ints, dtype=torch.int32).to(dev)
+            work = torch.empty(max(int(lib.sininn_flow_gather_bwd_workspace(b, k, h, w)), 1), device=dev, dtype=torch.float32)
+            rlist, n_ints, ws, n_ws = C.c_void_p(rl.data_ptr()), rl.numel(), ptr(work), work.numel()
+        check(lib.sininn_flow_gather_bwd(ptr(frame1), ptr(frame2), ptr(flows), stride, C.c_void_p(table.data_ptr()), ptr(tau),
+                                         ptr(grad_out), b, k, c, h, w, t, rlist, n_ints, ws, n_ws, ptr(dflows), _stream()))
+        return (dflows,) + (None,) * 7
+
+
+def gather(frame1, frame2, flows, slots, taus, *, out=None, u8=False, k_loop=None, flow_grad=False):
     """The frames at `taus` between frame1 and frame2 from flows taken at the in-between times: (B, K, C, H, W) fp32, and with u8=True
     also the bytes, by `synthesize`'s rule.  `flows`: (T', 4, H, W) fp32 on the device, read in place -- any stride between time slices,
     the four channel planes of a slice contiguous.  `slots`: the host table of `gather_slots` (validated and uploaded here), or what
-    `upload_slots` made of it.  `k_loop`: the launch shape (None: `K_LOOP`); both give the same bits.  One launch, no workspace."""
-    b, c, h, w = _gather_inputs('gather', frame1, frame2, flows)
+    `upload_slots` made of it.  `k_loop`: the launch shape (None: `K_LOOP`); both give the same bits.  One launch, no workspace.
+
+    `flow_grad=True`: where `flows` requires grad the result carries a gradient to it (see the module text); `slots` is then the host
+    table (the backward pass builds its reduce list from it), and `u8` and `out=` are not supported."""
+    b, c, h, w = _gather_inputs('gather', frame1, frame2, flows, flow_grad)
+    if flow_grad and (u8 or out is not None):
+        raise ValueError('flowsynth.gather: flow_grad=True with u8=True or out= is not supported (bytes carry no gradient, and autograd '
+                         'owns the result)')
+    if flow_grad and flows.requires_grad and torch.is_grad_enabled():
+        values = _host_taus(taus)
+        k = len(values)
+        if isinstance(slots, DeviceSlots):
+            raise ValueError('flowsynth.gather: flow_grad=True takes the host table of gather_slots (the backward pass builds its '
+                             'reduce list from it)')
+        need = _host_slots('gather', slots, b, k)
+        if need > flows.shape[0]:
+            raise ValueError(f'flowsynth.gather: the slots name time slice {need - 1}, flows has {flows.shape[0]}')
+        _gpu32(flows)
+        if flows.stride()[1:] != (h * w, w, 1) and flows.numel() > 0:
+            raise ValueError('flowsynth.gather: the four channel planes of a time slice must be contiguous (any stride between slices)')
+        frame1, frame2 = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous()
+        if torch.is_tensor(taus) and taus.is_cuda and taus.dtype == torch.float32:
+            tau = taus.detach().contiguous()
+        else:
+            tau = torch.tensor(values, dtype=torch.float32, device=frame1.device)
+        host = slots.contiguous().clone()
+        return _GatherFlowGrad.apply(flows, frame1, frame2, host, host.to(frame1.device), tau, values, k_loop)
     values = _host_taus(taus)
     k = len(values)
     frame1, frame2, flows = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous(), _gpu32(flows)
@@ -359,15 +458,18 @@ def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, ep
     return num / den[:, :, None]
 
 
-def gather_composed(frame1, frame2, flows, slots, taus):
+def gather_composed(frame1, frame2, flows, slots, taus, *, flow_grad=False):
     """`gather` from torch ops, on the device and in the dtype of the frames (CPU or GPU, fp32 or fp64): index arithmetic and
-    `torch.gather` for the taps, a few dozen launches.  `slots` is the host table.  In fp32 it rounds where the fused operator rounds."""
-    b, c, h, w = _gather_inputs('gather_composed', frame1, frame2, flows)
+    `torch.gather` for the taps, a few dozen launches.  `slots` is the host table.  In fp32 it rounds where the fused operator rounds.
+    `flow_grad=True`: where `flows` requires grad, `gather_from` runs with autograd on and the result carries a gradient to `flows`."""
+    b, c, h, w = _gather_inputs('gather_composed', frame1, frame2, flows, flow_grad)
     values = _host_taus(taus)
     need = _host_slots('gather_composed', slots, b, len(values))
     if need > flows.shape[0]:
         raise ValueError(f'flowsynth.gather_composed: the slots name time slice {need - 1}, flows has {flows.shape[0]}')
     assert frame1.dtype in (torch.float32, torch.float64) and frame2.dtype == frame1.dtype
+    if flow_grad and flows.requires_grad and torch.is_grad_enabled():
+        return gather_from(frame1.detach(), frame2.detach(), flows, slots, values)
     with torch.no_grad():
         return gather_from(frame1.detach(), frame2.detach(), flows.detach(), slots, values)
 

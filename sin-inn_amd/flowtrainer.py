@@ -28,9 +28,14 @@ Differences from the reference, all on purpose:
     `test/EPE`.
   * on resume the controller of a progressive network gets its `iteration`, `cur_block` and `next_block` back (`on_load_checkpoint`);
     the reference restores the mask alone and restarts the schedule.
+  * `--loss-between W` adds a photometric consistency term at random in-between times, which the reference has not:
+    the virtual frame at s = t0 + tau dt is read once from frame 1 alone and once from frame 2 alone through `flowsynth.gather`
+    (blend weights 0 and 1), and W mean |A - B| trains the flows at s through the operator's gradient.  Off (W = 0) the step is
+    the reference's, launch for launch.
 """
 import ctypes as C
 import os
+import random
 
 import numpy as np
 import torch
@@ -231,6 +236,26 @@ class FlowTrainer(LightningModule):
         self._epoch_means = {}
         self.fused = True                    # False: the torch expressions of the flowtrain operators (tools/bench_flowtrainer.py)
         self._stash = None                   # spatial controller: the six tensors of this step's per-point loss, until on_after_backward
+        # the in-between consistency loss: off unless the namespace carries a non-zero weight
+        self.between_weight = float(getattr(args, 'loss_between', 0) or 0)
+        self.between_rng = None
+        if self.between_weight != 0:
+            dim = int(self.net.domain_dim)
+            if dim != 3:
+                raise ValueError(f'domain_dim {dim}: --loss-between evaluates the network at times between two frames; a network on '
+                                 '(y, x) has no time axis')
+            self.between_taus = int(getattr(args, 'between_taus', 1))
+            self.between_back = getattr(args, 'between_back', 'network')
+            self.between_dt = getattr(args, 'between_dt', None)
+            if not 1 <= self.between_taus <= 32:
+                raise ValueError(f'--between-taus {self.between_taus}: 1 to 32 times a step (two rows of one gather call each)')
+            if self.between_back not in ('network', 'reverse'):
+                raise ValueError(f"--between-back is 'network' or 'reverse', got {self.between_back!r}")
+            if self.between_dt is None or not float(self.between_dt) > 0:
+                raise ValueError('--loss-between needs between_dt, the spacing of the clip\'s times, 2 / (frames - 1)')
+            self.between_rng = random.Random(getattr(args, 'between_seed', 0))          # seeded once per trainer; host only
+            self.between_flows = None            # test hook: the (T', 4, h, w) flows of the last between term
+            self.between_frames = None           # test hook: its synthesized frames X (B, 2K, C, h, w)
 
     # ---- the pieces of the step ----
 
@@ -300,6 +325,48 @@ class FlowTrainer(LightningModule):
         smooth_loss = self.smooth1(frame1, flow12) + self.smooth1(frame2, flow21)
         return l1_loss, census_loss, ssim_loss, smooth_loss, (mask1, mask2, softmax1, softmax2)
 
+    def on_before_batch_transfer(self, batch, dataloader_idx=0):
+        """Lightning's hook, called by the trainer while the batch is on the host: with the between loss on, keep the pairs' time
+        stamps as Python floats, so that building the slot table reads nothing back from the device"""
+        self._times_on_host = None
+        if self.between_weight != 0 and torch.is_tensor(batch[2]) and not batch[2].is_cuda:
+            self._times_on_host = [float(t) for t in batch[2].reshape(-1).tolist()]
+        return batch
+
+    def _host_times(self, times):
+        """the batch's stamps as Python floats: what `on_before_batch_transfer` kept; a caller that hands `training_step` a device
+        batch directly pays one read of B floats"""
+        kept, self._times_on_host = getattr(self, '_times_on_host', None), None
+        if kept is not None and len(kept) == times.numel():
+            return kept
+        return [float(t) for t in times.detach().reshape(-1).cpu().tolist()]
+
+    def between_table(self, times, taus):
+        """(stamps, slots, blend) of the between term: `gather_slots(times, taus, dt, back)`, its table repeated along K to
+        (B, 2K, 6), and the blend weights [0] * K + [1] * K: rows 0 .. K-1 read frame 1 alone (A), rows K .. 2K-1 frame 2 alone (B)"""
+        from . import flowsynth
+        stamps, slots = flowsynth.gather_slots(times, taus, self.between_dt, self.between_back)
+        k = len(taus)
+        return stamps, torch.cat([slots, slots], dim=1).contiguous(), [0.0] * k + [1.0] * k
+
+    def between_loss(self, frame1, frame2, times, scale):
+        """weight * mean |A - B| at K fresh times tau ~ U(0, 1) drawn on the host: A = (W0 + e I0(p)) / (n0 + e) and
+        B = (W1 + e I1(p)) / (n1 + e) are two rows of one `gather` call whose flows come from one more `flow_fields` call, with
+        gradient, at the in-between stamps.  `times` is the host list of the batch's stamps."""
+        from . import flowsynth
+        k = self.between_taus
+        taus = [self.between_rng.random() for _ in range(k)]
+        taus = [t if t > 0.0 else 0.5 for t in taus]                 # random() is in [0, 1): keep tau inside (0, 1)
+        stamps, table, blend = self.between_table(times, taus)
+        at = torch.tensor(stamps, dtype=torch.float32, device=frame1.device)
+        per = max(1, GRID_POINTS // (frame1.shape[-2] * frame1.shape[-1]))
+        parts = [torch.cat(self.forward(frame1, at[i:i + per], scale), dim=1) for i in range(0, len(stamps), per)]
+        flows = parts[0] if len(parts) == 1 else torch.cat(parts)
+        synth = flowsynth.gather if self.fused else flowsynth.gather_composed
+        frames = synth(frame1, frame2, flows, table, blend, flow_grad=True)
+        self.between_flows, self.between_frames = flows, frames
+        return self.between_weight * (frames[:, :k] - frames[:, k:]).abs().mean()
+
     # ---- the LightningModule surface ----
 
     def training_step(self, batch, batch_idx):
@@ -307,12 +374,17 @@ class FlowTrainer(LightningModule):
         frame1, frame2, times, scale = batch[:4]
         if batch_idx == 0:
             self._new_epoch('train/')
+        if self.between_weight != 0:
+            # before the step's own flow_fields call: a spatial controller stashes at the grid evaluated LAST, the frame times'
+            between_loss = self.between_loss(frame1, frame2, self._host_times(times), scale)
         flow12, flow21 = self.forward(frame1, times, scale)
         if len(batch) == 5:
             self.log('train/EPE', self._epe(flow12, batch[-1]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])
         flow12, flow21 = flow12.contiguous(), flow21.contiguous()
         l1_loss, census_loss, ssim_loss, smooth_loss, (mask1, mask2, softmax1, softmax2) = self.losses(frame1, frame2, flow12, flow21)
         loss = l1_loss + census_loss + ssim_loss + smooth_loss
+        if self.between_weight != 0:
+            loss = loss + between_loss
         if hasattr(self.net, 'stash_grid'):
             # a spatial controller updates its mask grid in place and the backward pass checks the grid's version: on_after_backward stashes
             self._stash = tuple(t.detach() for t in (softmax1, frame1, mask1, softmax2, frame2, mask2))
@@ -326,6 +398,8 @@ class FlowTrainer(LightningModule):
         if self.ssim.weight != 0:
             self.log('train/ssim', ssim_loss)
         self.log('train/smooth', smooth_loss)
+        if self.between_weight != 0:
+            self.log('train/between', between_loss)
         return loss
 
     def on_after_backward(self):

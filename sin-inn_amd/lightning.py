@@ -339,6 +339,8 @@ class Trainer:
             self.current_epoch = epoch
             model.train()
             for i, batch in enumerate(train_loader):
+                if hasattr(model, 'on_before_batch_transfer'):     # Lightning's hook: the batch while it is still on the host
+                    batch = model.on_before_batch_transfer(batch, 0)
                 out = model.training_step(_to_device(batch, device), i)
                 if automatic and torch.is_tensor(out) and out.requires_grad:
                     self.optimizer.zero_grad()

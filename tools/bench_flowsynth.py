@@ -148,6 +148,47 @@ def gather_lines(a, dev):
     return lines
 
 
+def gather_grad_lines(a, dev):
+    """forward plus backward of gather(.., flow_grad=True) against the autograd of gather_composed on the device, K = 1
+    and factor - 1, on the regular table of gather_slots (reverse rows for the clip's first pair: the two-launch backward path)"""
+    from sin_inn_amd import flowdata, flowsynth
+    clip = flowdata.SyntheticClip(a.batch + 1, a.height, a.width)
+    i0, i1 = clip.video[:-1].contiguous().to(dev), clip.video[1:].contiguous().to(dev)
+    f01, f10 = clip.flow.contiguous().to(dev), (-clip.flow).contiguous().to(dev)
+    dt, times = 2 / a.batch, clip.T[:-1]
+    lines = []
+    for k in sorted({1, a.factor - 1}):
+        taus = [0.5] if k == 1 else [j / a.factor for j in range(1, a.factor)]
+        stamps, slots = flowsynth.gather_slots(times, taus, dt)
+        per_b = len(stamps) // a.batch + 1
+        flows = torch.cat([f01, f10], 1).repeat_interleave(per_b, 0)[:len(stamps)].contiguous().requires_grad_(True)
+        g = torch.randn(a.batch, k, 3, a.height, a.width, device=dev)
+
+        def step(fn):
+            flows.grad = None
+            fn(i0, i1, flows, slots, taus, flow_grad=True).backward(g)
+            return flows.grad
+
+        todo = {'fused': lambda: step(flowsynth.gather)}
+        if a.baseline:
+            todo['composed'] = lambda: step(flowsynth.gather_composed)
+        pixels = a.batch * a.height * a.width
+        # words per pixel-frame, C = 3: forward 13 (DESIGN 19.5); backward flows 4, taps 6, I(p) 6, g 3, the row buffer written 4 and
+        # read 4; and d flows written once, 4 words per pixel of every slice
+        min_bytes = 4 * pixels * k * (13 + 27) + 4 * 4 * len(stamps) * a.height * a.width
+        line = dict(op='flowgather_grad', height=a.height, width=a.width, batch=a.batch, K=k, slices=len(stamps), min_bytes=min_bytes,
+                    min_bytes_backward=min_bytes - 4 * pixels * k * 13)
+        for name, (best, meds) in _timed(todo, a).items():
+            line[f'{name}_ms'], line[f'{name}_ms_windows'] = best, meds
+        line['fused_tb_per_s'] = round(min_bytes / (line['fused_ms'] * 1e-3) / 1e12, 3)       # forward plus backward bytes over their time
+        if a.baseline:
+            line['composed_over_fused'] = round(line['composed_ms'] / line['fused_ms'], 3)
+            line['max_abs_diff_composed'] = float((step(flowsynth.gather).clone() - step(flowsynth.gather_composed)).abs().max())
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def main():
     from sin_inn_amd import flowdata, flowsynth
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
@@ -162,13 +203,15 @@ def main():
     ap.add_argument('--log', action='store_true', help='append the lines to profiles/flowsynth_bench.jsonl')
     ap.add_argument('--quality', action='store_true', help='time flowsynth.quality (and with --baseline quality_composed) instead')
     ap.add_argument('--gather', action='store_true', help='time flowsynth.gather and the whole interpolate call instead (DESIGN 19)')
+    ap.add_argument('--gather-grad', action='store_true',
+                    help='time forward plus backward of flowsynth.gather(.., flow_grad=True) (and with --baseline the autograd of gather_composed) instead (DESIGN 22)')
     ap.add_argument('--net', default='PRBF', help='--gather: the network of the whole-call lines')
     a = ap.parse_args()
     assert 2 <= a.factor <= 65
     dev = torch.device('cuda', 0)
-    if a.quality or a.gather:
-        lines = gather_lines(a, dev) if a.gather else quality_lines(a, dev)
-        for line in ([] if a.gather else lines):           # the gather lines are printed as they are measured
+    if a.quality or a.gather or a.gather_grad:
+        lines = gather_grad_lines(a, dev) if a.gather_grad else gather_lines(a, dev) if a.gather else quality_lines(a, dev)
+        for line in ([] if a.gather or a.gather_grad else lines):           # the gather lines are printed as they are measured
             print(json.dumps(line))
         if a.log:
             with open(os.path.join(ROOT, 'profiles', 'flowsynth_bench.jsonl'), 'a') as f:

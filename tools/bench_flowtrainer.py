@@ -21,6 +21,16 @@ block_iterations is set beyond the run, so no window contains an update_progress
     linear             the same network's step under LinearControllerEarly, the baseline
     stash_fused / stash_composed   the stash alone, on the tensors of one step
 and reports the bytes per pixel the fused stash moves, counted from its definition.
+
+    python tools/bench_flowtrainer.py --loss-between 1 [--between-taus 1] [--between-back network] [--log]
+
+adds the step with the in-between consistency loss next to the step without it, in the same alternating windows:
+    between_fused      the loss through flowsynth.gather(.., flow_grad=True) (the backward kernels of csrc/flowgather.hip)
+    between_composed   the loss through gather_composed(.., flow_grad=True) (FlowTrainer.fused = False; as `torch` above, the two
+                       flowtrain operators are torch expressions too)
+    between_network    flow_fields forward + backward alone at the stamps of one between term: what the extra evaluations cost
+The generator is reset before every window, so all windows draw the same times.  --log appends the line to
+profiles/flowtrainer_bench.jsonl.
 """
 import argparse
 import json
@@ -50,6 +60,10 @@ def main():
     ap.add_argument('--rounds', type=int, default=2)
     ap.add_argument('--spatially-adaptive', action='store_true', help='time the step under StashedSpatialController: fused and composed stash')
     ap.add_argument('--res', type=int, default=50, help='--spatially-adaptive: cells per axis of the mask grid')
+    ap.add_argument('--loss-between', type=float, default=0.0, help='also time the step with the in-between loss of this weight')
+    ap.add_argument('--between-taus', type=int, default=1)
+    ap.add_argument('--between-back', default='network', choices=['network', 'reverse'])
+    ap.add_argument('--log', action='store_true', help='append the line to profiles/flowtrainer_bench.jsonl')
     a = ap.parse_args()
     from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
     dev = torch.device('cuda', 0)
@@ -83,9 +97,45 @@ def main():
         torch.autograd.backward([f12, f21], [up[:, :2], up[:, 2:]])
 
     todo = {'fused': step(True), 'torch': step(False), 'network': network}
+    if a.loss_between != 0:
+        from sin_inn_amd import flowsynth
+        dt = 2 / (a.frames - 1)
+        torch.manual_seed(0)
+        net2 = flownet.all_model_dict[a.net](flownet.ModelParams())
+        if net2.is_progressive:
+            net2 = progressive.LinearControllerEarly(net2, 5000, epsilon=1e-3)
+        args2 = argparse.Namespace(**{**vars(args), 'net': net2, 'loss_between': a.loss_between, 'between_taus': a.between_taus,
+                                      'between_back': a.between_back, 'between_dt': dt})
+        model2 = flowtrainer.FlowTrainer(args2).to(dev)
+        opt2 = model2.attach_optimizer()
+        times_host = clip.T[:a.batch].tolist()
+        state = model2.between_rng.getstate()
+        stamps, _ = flowsynth.gather_slots(times_host, [0.5] * a.between_taus, dt, a.between_back)
+        at = torch.tensor(stamps, dtype=torch.float32, device=dev)
+        up2 = torch.randn(len(stamps), 4, a.height, a.width, device=dev)
+
+        def between(fused):
+            def run():
+                model2.fused = fused
+                model2._times_on_host = times_host           # what the trainer loop's on_before_batch_transfer keeps
+                opt2.zero_grad()
+                model2.training_step(batch, 0).backward()
+                opt2.step()
+            return run
+
+        def between_network():
+            opt2.zero_grad()
+            per = max(1, flowtrainer.GRID_POINTS // (a.height * a.width))
+            for i in range(0, len(stamps), per):
+                f12, f21 = model2(batch[0], at[i:i + per], batch[3])
+                torch.autograd.backward([f12, f21], [up2[i:i + per, :2], up2[i:i + per, 2:]])
+
+        todo.update(between_fused=between(True), between_composed=between(False), between_network=between_network)
     res = {k: [] for k in todo}
     for _ in range(a.rounds):
         for k, fn in todo.items():
+            if a.loss_between != 0:
+                model2.between_rng.setstate(state)
             res[k].append(window(fn, a.seconds, a.warmup))
     out = dict(net=a.net, batch=a.batch, height=a.height, width=a.width, loss_ssim=a.loss_ssim, points=a.batch * a.height * a.width)
     for k in res:
@@ -94,7 +144,15 @@ def main():
         out[f'{k}_ms_windows'] = [round(m, 4) for m in meds]
     out['network_share'] = round(out['network_ms'] / out['fused_ms'], 3)
     out['fused_over_torch'] = round(out['fused_ms'] / out['torch_ms'], 4)
+    if a.loss_between != 0:
+        out.update(loss_between=a.loss_between, between_taus=a.between_taus, between_back=a.between_back, between_stamps=len(stamps))
+        out['between_extra_ms'] = round(out['between_fused_ms'] - out['fused_ms'], 4)
+        out['between_network_share_of_extra'] = round(out['between_network_ms'] / out['between_extra_ms'], 3)
+        out['between_fused_over_composed'] = round(out['between_fused_ms'] / out['between_composed_ms'], 4)
     print(json.dumps(out))
+    if a.log:
+        with open(os.path.join(ROOT, 'profiles', 'flowtrainer_bench.jsonl'), 'a') as f:
+            f.write(json.dumps(out) + '\n')
 
 
 def spatial(a, dev):

@@ -64,6 +64,10 @@ def get_parser():
     ap.add_argument('--synthesis', choices=('splat', 'gather'), default='splat', help='the synthesis rule (DESIGN 17 / 19)')
     ap.add_argument('--back', choices=('network', 'reverse'), default='network',
                     help='--synthesis gather: where the flow toward the previous frame comes from')
+    ap.add_argument('--loss-between', type=float, default=0, metavar='W',
+                    help='--fit-epochs: weight of the in-between consistency loss (main.py --loss-between; DESIGN 22)')
+    ap.add_argument('--between-taus', type=int, default=1, metavar='K', help='--loss-between: in-between times drawn per step')
+    ap.add_argument('--between-back', choices=('network', 'reverse'), default='network', help='--loss-between: as --back')
     return ap
 
 
@@ -100,6 +104,8 @@ def trainer_args(a):
     argv += ['--synthetic', *map(str, a.synthetic)] if a.synthetic else ['--input-video', a.input_video]
     if a.holdout:
         argv += ['--holdout', str(a.holdout)]
+    if a.loss_between and a.fit_epochs:
+        argv += ['--loss-between', str(a.loss_between), '--between-taus', str(a.between_taus), '--between-back', a.between_back]
     args = m.get_args(argv)
     args.net = m.build_net(args)
     return m, args
@@ -115,6 +121,8 @@ def load_model(a):
     video, scene = get_video(args.input_video, args)
     device = torch.device('cuda', 0)
     if a.fit_epochs:
+        if getattr(args, 'loss_between', 0) != 0:
+            args.between_dt = 2 / (len(video.testset.T) - 1)   # the clip being fitted: under --holdout the kept frames
         model = FlowTrainer(args, test_tag=f'{scene}_{a.name}')
         Trainer(gpus=[0], max_epochs=a.fit_epochs, check_val_every_n_epoch=a.fit_epochs + 1).fit(model, video)
     else:

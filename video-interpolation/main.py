@@ -23,7 +23,9 @@ Differences from the reference, all to make the path runnable here:
   * LinearControllerEarly(net, epochs) computes `block_iterations = 3 * epochs // (4 * 84)` (PPE: `// 12`), which is 0 below 112 (4) epochs, and the
     reference then divides by it; here such a short run opens one block per step;
   * checkpoints are written every max(epochs // 100, 1) epochs (the reference's `every_n_epochs=0` below 100 epochs writes none)
-    whenever `--wandb` is given, `test` and `sintel` load the newest one, and `train` resumes from it.
+    whenever `--wandb` is given, `test` and `sintel` load the newest one, and `train` resumes from it;
+  * `--loss-between W` (with `--between-taus K`, `--between-back {network,reverse}`) adds the in-between consistency loss of
+    sin_inn_amd/flowtrainer.py to the training step; the default 0 leaves the step as it was.
 """
 import argparse
 import os
@@ -74,6 +76,13 @@ def get_parser():
     parser.add_argument('--occl', default='wang', choices=['brox', 'wang', 'None', None],
                         help="'None' on the command line stands for the reference's None (no occlusion masks)")
     parser.add_argument('--occl-thresh', default=0.7, type=float)
+    # like --holdout, the three attributes exist only when their flag is given: the default namespace stays the reference's
+    parser.add_argument('--loss-between', default=argparse.SUPPRESS, type=float, metavar='W',
+                        help='weight of the photometric consistency loss at random in-between times (default 0: off, the step as it was)')
+    parser.add_argument('--between-taus', default=argparse.SUPPRESS, type=int, metavar='K',
+                        help='--loss-between: in-between times drawn per step (default 1)')
+    parser.add_argument('--between-back', default=argparse.SUPPRESS, choices=['network', 'reverse'],
+                        help="--loss-between: the flow toward the previous frame, as interpolate.py's --back (default network)")
     # Logging options
     parser.add_argument('--wandb', help='any name: selects the JSON-lines FileLogger and checkpointing')
     parser.add_argument('--log-gt', action='store_true')
@@ -148,6 +157,8 @@ def train_model(args):
     dataset = video.testset
     if not args.val_iter:
         args.val_iter = args.epochs + 1
+    if getattr(args, 'loss_between', 0) != 0:
+        args.between_dt = 2 / (len(dataset.T) - 1)             # the clip being fitted: under --holdout the kept frames
 
     logger, latest_ckpt, clbks = None, None, []
     if args.wandb:
