@@ -1070,6 +1070,26 @@ int sininn_flow_gather_bwd(const float* i0, const float* i1, const float* flows,
                            const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
                            int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, void* stream);
 
+/* The same rule at a list of N points.  i0, i1: DEVICE (B, C, H, W) fp32, contiguous, C = 1 or 3.  pix: DEVICE (N, 2)
+ * fp32, (y, x) in pixels, any value, 8-byte aligned; pair: DEVICE N int32, the pair of the batch a point reads; tau: DEVICE N floats;
+ * rev: DEVICE N bytes, or NULL for none set.  flows: DEVICE (S, 4, N) fp32, contiguous, S = 1 or 2, rows (x, y) forward, (x, y)
+ * backward.  G1 = flows[0, 0:2, n], c1 = 1 - tau[n];  G0 = flows[1, 2:4, n], c0 = tau[n] where S == 2 and rev[n] == 0, else G0 = G1,
+ * c0 = -tau[n].  blend: HOST R floats, R in 1..4, or NULL (R must be 1): a1 = tau[n] per point.  out: DEVICE (R, N, C),
+ *   out[r, n, c] = (a0 W0 + a1 W1 + e (a0 H0 + a1 H1)) / (a0 n0 + a1 n1 + e),   a1 = blend[r], a0 = 1 - a1, e = 2^-10
+ * with (W0, n0) = sample(i0[b], p + c0 G0), (W1, n1) = sample(i1[b], p + c1 G1), H0 = sample(i0[b], p).W, H1 = sample(i1[b], p).W and
+ * `sample` that of sininn_flow_gather.  Nothing on the device is trusted: a pair outside [0, B) gives a row of zeros (and a zero
+ * gradient), a coordinate that is not finite or is 1e9 or more in size has no tap, and no value makes the kernel read outside its
+ * inputs.  One launch, one lane per point, no workspace, no atomics.  N <= 2^31 - 1, H W <= 2^31 - 1.
+ * _bwd: grad_out DEVICE (R, N, C); dflows DEVICE (S, 4, N), every element written by the lane of its column: dG1 in [0, 0:2], dG0 in
+ * [1, 2:4] -- or, where G0 = G1, added as dG0 + dG1 -- and zeros elsewhere; the R blends are summed in ascending r.  The formulas
+ * are those of sininn_flow_gather_bwd.  One launch; equal inputs give equal bits.  Once differentiable. */
+int sininn_flow_gather_at(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                          const unsigned char* rev, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W, float* out,
+                          void* stream);
+int sininn_flow_gather_at_bwd(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair,
+                              const float* tau, const unsigned char* rev, const float* blend, const float* grad_out, int R, int S,
+                              int64_t N, int B, int C, int H, int W, float* dflows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -332,6 +332,10 @@ _SIGS = {
     'sininn_flow_gather_bwd_workspace': (C.c_int64, [C.c_int] * 4),
     'sininn_flow_gather_bwd': (C.c_int, [c_f, c_f, c_f, C.c_int64, C.c_void_p, c_f, c_f] + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_f,
                                          C.c_int64, c_f, C.c_void_p]),
+    'sininn_flow_gather_at': (C.c_int, [c_f, c_f, c_f, c_f, C.c_void_p, c_f, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int,
+                                        C.c_int64] + [C.c_int] * 4 + [c_f, C.c_void_p]),
+    'sininn_flow_gather_at_bwd': (C.c_int, [c_f, c_f, c_f, c_f, C.c_void_p, c_f, C.c_void_p, C.POINTER(C.c_float), c_f, C.c_int,
+                                            C.c_int, C.c_int64] + [C.c_int] * 4 + [c_f, C.c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -160,6 +160,12 @@ int64_t flow_gather_bwd_workspace(int B, int K, int H, int W);
 int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
                            const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
                            int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, hipStream_t st);
+int flow_gather_at_launch(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                          const uint8_t* rev, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W, float* out,
+                          hipStream_t st);
+int flow_gather_at_bwd_launch(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                              const uint8_t* rev, const float* blend, const float* grad_out, int R, int S, int64_t N, int B, int C,
+                              int H, int W, float* dflows, hipStream_t st);
 int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st);
 int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
                          float* gflow, hipStream_t st);
@@ -681,6 +687,18 @@ int sininn_flow_gather_bwd(const float* i0, const float* i1, const float* flows,
                            int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, void* stream) {
   return flow_gather_bwd_launch(i0, i1, flows, flow_sample_stride, slots, tau, grad_out, B, K, C, H, W, T, reduce_list, reduce_ints,
                                 workspace, workspace_floats, dflows, ST(stream));
+}
+
+int sininn_flow_gather_at(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                          const unsigned char* rev, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W, float* out,
+                          void* stream) {
+  return flow_gather_at_launch(i0, i1, flows, pix, pair, tau, rev, blend, R, S, N, B, C, H, W, out, ST(stream));
+}
+
+int sininn_flow_gather_at_bwd(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair,
+                              const float* tau, const unsigned char* rev, const float* blend, const float* grad_out, int R, int S,
+                              int64_t N, int B, int C, int H, int W, float* dflows, void* stream) {
+  return flow_gather_at_bwd_launch(i0, i1, flows, pix, pair, tau, rev, blend, grad_out, R, S, N, B, C, H, W, dflows, ST(stream));
 }
 
 }  // extern "C"

@@ -27,11 +27,12 @@ struct GatherTaps {
   bool v00, v01, v10, v11;
 };
 
-__device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float gx, float gy, int H, int W) {
+// (px, py): the point the sample is displaced from, a pixel of the grid or (flowgather_points_kernel) any fp32 coordinate.
+__device__ __forceinline__ GatherTaps gather_taps_at(float px, float py, float c, float gx, float gy, int H, int W) {
 #pragma clang fp contract(off)
   GatherTaps t = {};
   const float sx = c * gx, sy = c * gy;                   // the product is rounded, then the sum
-  const float qx = (float)x + sx, qy = (float)y + sy;
+  const float qx = px + sx, qy = py + sy;
   if (!(fabsf(qx) < 1e9f) || !(fabsf(qy) < 1e9f)) return t;       // NaN and inf fail the comparison too
   const BilinearTaps b = bilinear_taps(qx, qy);
   const bool xa = b.x0 >= 0 && b.x0 < W, xb = b.x0 + 1 >= 0 && b.x0 + 1 < W, ya = b.y0 >= 0 && b.y0 < H, yb = b.y0 + 1 >= 0 && b.y0 + 1 < H;
@@ -42,6 +43,10 @@ __device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float g
   t.n = ((t.w00 + t.w01) + t.w10) + t.w11;
   t.nw = (int64_t)b.y0 * W + b.x0;                           // read only through a tap that is inside
   return t;
+}
+
+__device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float gx, float gy, int H, int W) {
+  return gather_taps_at((float)x, (float)y, c, gx, gy, H, W);
 }
 
 __device__ __forceinline__ float gather_sample(const float* __restrict__ plane, const GatherTaps& t, int W) {
@@ -295,6 +300,213 @@ int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows,
                        dflows);
     SININN_LAUNCH_CHECK("flowgather_reduce");
   }
+  return 0;
+}
+
+// ---- the rule at a list of points ----
+// Point n: p = pix[n] = (py, px), any fp32 coordinate; b = pair[n]; flows (S, 4, N) planar, what a stack of flow_at(.., planar = True)
+// holds.  G1 = flows[0, 0:2, n], c1 = 1 - tau[n].  G0 = flows[1, 2:4, n], c0 = tau[n] where S == 2 and not rev[n]; else G0 = G1,
+// c0 = -tau[n].  H0, H1 = sample(I0, p), sample(I1, p), the bilinear form of the grid kernels' I0(p), I1(p): on an integer pixel it is
+// that value.  R blends a1 = blend[r] (or, per point, tau[n]) over one set of taps:
+//   out[r, n, c] = (a0 W0 + a1 W1 + e (a0 H0 + a1 H1)) / (a0 n0 + a1 n1 + e)
+// Nothing here is validated on the host: a pair outside [0, B) gives a row of zeros, a coordinate without a tap reads nothing.
+constexpr int FGP_MAX_R = 4;
+struct GatherBlend { float a1[FGP_MAX_R]; };
+
+struct GatherPoint {
+  GatherTaps t0, t1, th;
+  float c0, c1, tau;
+  bool rev;
+};
+
+__device__ __forceinline__ GatherPoint gather_point(const float* __restrict__ flows, const float* __restrict__ pix,
+                                                    const float* __restrict__ tau, const uint8_t* __restrict__ rev, int S, int64_t N,
+                                                    int64_t n, int H, int W) {
+#pragma clang fp contract(off)
+  GatherPoint p;
+  const float2 yx = reinterpret_cast<const float2*>(pix)[n];      // one 8-byte load: (py, px)
+  p.tau = tau[n];
+  p.rev = S == 1 || (rev != nullptr && rev[n] != 0);
+  const float g1x = flows[n], g1y = flows[N + n];
+  float g0x = g1x, g0y = g1y;
+  if (!p.rev) { g0x = flows[6 * N + n]; g0y = flows[7 * N + n]; }
+  p.c0 = p.rev ? -p.tau : p.tau;
+  p.c1 = 1.f - p.tau;
+  p.t0 = gather_taps_at(yx.y, yx.x, p.c0, g0x, g0y, H, W);
+  p.t1 = gather_taps_at(yx.y, yx.x, p.c1, g1x, g1y, H, W);
+  p.th = gather_taps_at(yx.y, yx.x, 0.f, 0.f, 0.f, H, W);
+  return p;
+}
+
+// One lane per point, 256 points a block.
+template <int C>
+__global__ __launch_bounds__(FG_THREADS) void flowgather_points_kernel(const float* __restrict__ i0, const float* __restrict__ i1,
+                                                                       const float* __restrict__ flows, const float* __restrict__ pix,
+                                                                       const int* __restrict__ pair, const float* __restrict__ tau,
+                                                                       const uint8_t* __restrict__ rev, GatherBlend blend, int per_point,
+                                                                       int R, int S, int64_t N, int B, int H, int W,
+                                                                       float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t n = (int64_t)blockIdx.x * FG_THREADS + threadIdx.x;
+  if (n >= N) return;
+  const int64_t HW = (int64_t)H * W;
+  const int b = pair[n];
+  if (b < 0 || b >= B) {
+#pragma unroll
+    for (int r = 0; r < FGP_MAX_R; ++r)
+      if (r < R)
+#pragma unroll
+        for (int c = 0; c < C; ++c) out[(r * N + n) * C + c] = 0.f;
+    return;
+  }
+  const float* i0b = i0 + (int64_t)b * C * HW;
+  const float* i1b = i1 + (int64_t)b * C * HW;
+  const GatherPoint p = gather_point(flows, pix, tau, rev, S, N, n, H, W);
+  float w0[C], w1[C], h0[C], h1[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    w0[c] = gather_sample(i0b + c * HW, p.t0, W); w1[c] = gather_sample(i1b + c * HW, p.t1, W);
+    h0[c] = gather_sample(i0b + c * HW, p.th, W); h1[c] = gather_sample(i1b + c * HW, p.th, W);
+  }
+  const float e = 0.0009765625f;
+#pragma unroll
+  for (int r = 0; r < FGP_MAX_R; ++r) {
+    if (r < R) {
+      const float a1 = per_point ? p.tau : blend.a1[r], a0 = 1.f - a1;
+      const float den = (a0 * p.t0.n + a1 * p.t1.n) + e;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float lin = a0 * h0[c] + a1 * h1[c];
+        const float num = (a0 * w0[c] + a1 * w1[c]) + e * lin;
+        out[(r * N + n) * C + c] = __fdiv_rn(num, den);
+      }
+    }
+  }
+}
+
+// The gradient with respect to the flows, by the formulas of flowgather_bwd_kernel.  Lane n writes the 4 S values of column n itself:
+// dG1 into flows[0, 0:2], dG0 into flows[1, 2:4], or under rev (and S == 1) added to dG1's pair as dG0 + dG1; the others are 0.  The R
+// blends are summed in ascending r, the first starting the sum.  No atomics, no second pass.
+template <int C>
+__global__ __launch_bounds__(FG_THREADS) void flowgather_points_bwd_kernel(const float* __restrict__ i0, const float* __restrict__ i1,
+                                                                           const float* __restrict__ flows,
+                                                                           const float* __restrict__ pix, const int* __restrict__ pair,
+                                                                           const float* __restrict__ tau,
+                                                                           const uint8_t* __restrict__ rev, GatherBlend blend,
+                                                                           int per_point, int R, int S, int64_t N, int B, int H, int W,
+                                                                           const float* __restrict__ gout, float* __restrict__ dflows) {
+#pragma clang fp contract(off)
+  const int64_t n = (int64_t)blockIdx.x * FG_THREADS + threadIdx.x;
+  if (n >= N) return;
+  const int64_t HW = (int64_t)H * W;
+  const int b = pair[n];
+  float d0x = 0.f, d0y = 0.f, d1x = 0.f, d1y = 0.f;
+  bool reversed = S == 1;
+  if (b >= 0 && b < B) {
+    const float* i0b = i0 + (int64_t)b * C * HW;
+    const float* i1b = i1 + (int64_t)b * C * HW;
+    const GatherPoint p = gather_point(flows, pix, tau, rev, S, N, n, H, W);
+    reversed = p.rev;
+    float n0x, n0y, n1x, n1y;
+    gather_slopes_ones(p.t0, n0x, n0y);
+    gather_slopes_ones(p.t1, n1x, n1y);
+    float w0[C], w1[C], h0[C], h1[C], w0x[C], w0y[C], w1x[C], w1y[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      w0[c] = gather_sample(i0b + c * HW, p.t0, W); w1[c] = gather_sample(i1b + c * HW, p.t1, W);
+      h0[c] = gather_sample(i0b + c * HW, p.th, W); h1[c] = gather_sample(i1b + c * HW, p.th, W);
+      gather_slopes(i0b + c * HW, p.t0, W, w0x[c], w0y[c]);
+      gather_slopes(i1b + c * HW, p.t1, W, w1x[c], w1y[c]);
+    }
+    const float e = 0.0009765625f;
+#pragma unroll
+    for (int r = 0; r < FGP_MAX_R; ++r) {
+      if (r < R) {
+        const float a1 = per_point ? p.tau : blend.a1[r], a0 = 1.f - a1;
+        const float den = (a0 * p.t0.n + a1 * p.t1.n) + e;
+        float s0x = 0.f, s0y = 0.f, s1x = 0.f, s1y = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const float lin = a0 * h0[c] + a1 * h1[c];
+          const float num = (a0 * w0[c] + a1 * w1[c]) + e * lin;
+          const float v = __fdiv_rn(num, den);                  // out[r, n, c], the forward pass's bits
+          const float g = gout[(r * N + n) * C + c];
+          s0x = s0x + g * (w0x[c] - v * n0x); s0y = s0y + g * (w0y[c] - v * n0y);
+          s1x = s1x + g * (w1x[c] - v * n1x); s1y = s1y + g * (w1y[c] - v * n1y);
+        }
+        const float k0 = __fdiv_rn(p.c0 * a0, den), k1 = __fdiv_rn(p.c1 * a1, den);
+        const float v0x = k0 * s0x, v0y = k0 * s0y, v1x = k1 * s1x, v1y = k1 * s1y;
+        d0x = r == 0 ? v0x : d0x + v0x; d0y = r == 0 ? v0y : d0y + v0y;
+        d1x = r == 0 ? v1x : d1x + v1x; d1y = r == 0 ? v1y : d1y + v1y;
+      }
+    }
+  }
+  float* col = dflows + n;
+  col[0] = reversed ? d0x + d1x : d1x;
+  col[N] = reversed ? d0y + d1y : d1y;
+  col[2 * N] = 0.f; col[3 * N] = 0.f;
+  if (S == 2) {
+    col[4 * N] = 0.f; col[5 * N] = 0.f;
+    col[6 * N] = reversed ? 0.f : d0x;
+    col[7 * N] = reversed ? 0.f : d0y;
+  }
+}
+
+static int flow_gather_at_check(const char* who, const void* i0, const void* i1, const void* flows, const void* pix, const void* pair,
+                                const void* tau, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W) {
+  SININN_CHECK(i0 && i1 && flows && pix && pair && tau, "%s: null pointer", who);
+  SININN_CHECK(B > 0 && H > 0 && W > 0, "%s: bad shape (every size must be positive)", who);
+  SININN_CHECK(C == 1 || C == 3, "%s: frames have 1 or 3 channels (got %d)", who, C);
+  SININN_CHECK(S == 1 || S == 2, "%s: flows is (S, 4, N) with S = 1 or 2 (got %d)", who, S);
+  SININN_CHECK(R >= 1 && R <= FGP_MAX_R, "%s: R = %d blends in one call, 1 to %d are supported", who, R, FGP_MAX_R);
+  SININN_CHECK(blend || R == 1, "%s: blend == NULL is the per-point blend a1 = tau[n], R = 1 (got R = %d)", who, R);
+  SININN_CHECK(N >= 1, "%s: N = %lld points, at least one is needed", who, (long long)N);
+  SININN_CHECK(N <= 0x7fffffff, "%s: N = %lld is past an int index", who, (long long)N);
+  const int64_t HW = (int64_t)H * W;
+  SININN_CHECK(HW <= 0x7fffffff, "%s: H * W = %lld is past an int index", who, (long long)HW);
+  SININN_CHECK((int64_t)B * C <= INT64_MAX / HW, "%s: B * C * H * W is past a 64-bit index", who);
+  SININN_CHECK(((uintptr_t)pix & 7) == 0, "%s: pix is read as 8-byte (y, x) pairs and must be 8-byte aligned", who);
+  return 0;
+}
+
+static GatherBlend flow_gather_at_blend(const float* blend, int R) {
+  GatherBlend v = {};
+  for (int r = 0; blend && r < R; ++r) v.a1[r] = blend[r];
+  return v;
+}
+
+int flow_gather_at_launch(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                          const uint8_t* rev, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W, float* out,
+                          hipStream_t st) {
+  if (flow_gather_at_check("flow_gather_at", i0, i1, flows, pix, pair, tau, blend, R, S, N, B, C, H, W)) return 1;
+  SININN_CHECK(out, "flow_gather_at: null pointer");
+  const dim3 grid((unsigned)((N + FG_THREADS - 1) / FG_THREADS)), block(FG_THREADS);
+  const GatherBlend a1 = flow_gather_at_blend(blend, R);
+  if (C == 1)
+    hipLaunchKernelGGL((flowgather_points_kernel<1>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R, S, N,
+                       B, H, W, out);
+  else
+    hipLaunchKernelGGL((flowgather_points_kernel<3>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R, S, N,
+                       B, H, W, out);
+  SININN_LAUNCH_CHECK("flowgather_points");
+  return 0;
+}
+
+int flow_gather_at_bwd_launch(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                              const uint8_t* rev, const float* blend, const float* grad_out, int R, int S, int64_t N, int B, int C,
+                              int H, int W, float* dflows, hipStream_t st) {
+  if (flow_gather_at_check("flow_gather_at_bwd", i0, i1, flows, pix, pair, tau, blend, R, S, N, B, C, H, W)) return 1;
+  SININN_CHECK(grad_out, "flow_gather_at_bwd: the gradient of the output is null");
+  SININN_CHECK(dflows, "flow_gather_at_bwd: the gradient of the flows is null");
+  const dim3 grid((unsigned)((N + FG_THREADS - 1) / FG_THREADS)), block(FG_THREADS);
+  const GatherBlend a1 = flow_gather_at_blend(blend, R);
+  if (C == 1)
+    hipLaunchKernelGGL((flowgather_points_bwd_kernel<1>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R,
+                       S, N, B, H, W, grad_out, dflows);
+  else
+    hipLaunchKernelGGL((flowgather_points_bwd_kernel<3>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R,
+                       S, N, B, H, W, grad_out, dflows);
+  SININN_LAUNCH_CHECK("flowgather_points_bwd");
   return 0;
 }
 

@@ -474,6 +474,181 @@ def gather_composed(frame1, frame2, flows, slots, taus, *, flow_grad=False):
         return gather_from(frame1.detach(), frame2.detach(), flows.detach(), slots, values)
 
 
+# ---- the gather rule at a list of points ----
+
+MAX_BLENDS = 4          # FGP_MAX_R of csrc/flowgather.hip
+
+
+def _gather_at_inputs(who, frame1, frame2, flows, pix, pair, tau, rev, blend, flow_grad):
+    """shapes and dtypes of the point form, checked on the host (the VALUES of the device tensors cannot be, and need not: the
+    operator is safe for any); returns (b, c, h, w, s, n, blend as a list of fp32 values or None)"""
+    for t in (frame1, frame2) if flow_grad else (frame1, frame2, flows):
+        if t.requires_grad and torch.is_grad_enabled():
+            if flow_grad:
+                raise RuntimeError(f'flowsynth.{who}(.., flow_grad=True) has a gradient with respect to the flows only: detach the frames')
+            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
+                               '(or call it under torch.no_grad(), or pass flow_grad=True for the gradient to the flows)')
+    for name, t in (('pix', pix), ('tau', tau)):
+        if t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f'flowsynth.{who} has no gradient with respect to {name}: detach it')
+    if frame1.dim() != 4 or frame2.shape != frame1.shape:
+        raise ValueError(f'flowsynth.{who}: two frames of one shape (B, C, H, W)')
+    b, c, h, w = frame1.shape
+    if c not in (1, 3):
+        raise ValueError(f'flowsynth.{who}: frames have 1 or 3 channels (got {c})')
+    if flows.dim() != 3 or flows.shape[0] not in (1, 2) or flows.shape[1] != 4:
+        raise ValueError(f'flowsynth.{who}: flows is (S, 4, N) with S = 1 or 2, a stack of flow_at(.., planar=True) results; got '
+                         f'{tuple(flows.shape)}')
+    s, _, n = flows.shape
+    if n < 1:
+        raise ValueError(f'flowsynth.{who}: an empty point list')
+    if tuple(pix.shape) != (n, 2) or tuple(pair.shape) != (n,) or tuple(tau.shape) != (n,):
+        raise ValueError(f'flowsynth.{who}: pix is ({n}, 2), pair and tau ({n},); got {tuple(pix.shape)}, {tuple(pair.shape)}, '
+                         f'{tuple(tau.shape)}')
+    if pair.dtype != torch.int32:
+        raise ValueError(f'flowsynth.{who}: pair is int32 (got {pair.dtype})')
+    if rev is not None and (tuple(rev.shape) != (n,) or rev.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError(f'flowsynth.{who}: rev is ({n},) bool or uint8')
+    if blend is not None:
+        blend = [_f32(float(v)) for v in blend]
+        if not 1 <= len(blend) <= MAX_BLENDS or not all(math.isfinite(v) for v in blend):
+            raise ValueError(f'flowsynth.{who}: blend is 1 to {MAX_BLENDS} finite floats on the host (None: a1 = tau per point)')
+    return b, c, h, w, s, n, blend
+
+
+def _gather_at_call(entry, frame1, frame2, flows, pix, pair, tau, rev, blend, extra, result):
+    b, c, h, w = frame1.shape
+    s, _, n = flows.shape
+    r = 1 if blend is None else len(blend)
+    host = (C.c_float * r)(*blend) if blend is not None else None
+    check(entry(ptr(frame1), ptr(frame2), ptr(flows), ptr(pix), C.c_void_p(pair.data_ptr()), ptr(tau),
+                C.c_void_p(rev.data_ptr()) if rev is not None else None, host, *extra, r, s, n, b, c, h, w, ptr(result), _stream()))
+    return result
+
+
+class _GatherAtFlowGrad(torch.autograd.Function):
+    """`gather_at` with a gradient to `flows`: flowgather_points_kernel, then flowgather_points_bwd_kernel"""
+
+    @staticmethod
+    def forward(ctx, flows, frame1, frame2, pix, pair, tau, rev, blend):
+        flows = flows.contiguous()
+        ctx.save_for_backward(flows, frame1, frame2, pix, pair, tau, rev)
+        ctx.blend = blend
+        r = 1 if blend is None else len(blend)
+        out = torch.empty((r, flows.shape[2], frame1.shape[1]), device=frame1.device, dtype=torch.float32)
+        return _gather_at_call(_lib.lib().sininn_flow_gather_at, frame1, frame2, flows, pix, pair, tau, rev, blend, (), out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        flows, frame1, frame2, pix, pair, tau, rev = ctx.saved_tensors
+        grad_out = _gpu32(grad_out).contiguous()
+        dflows = torch.empty_like(flows)
+        _gather_at_call(_lib.lib().sininn_flow_gather_at_bwd, frame1, frame2, flows, pix, pair, tau, rev, ctx.blend, (ptr(grad_out),),
+                        dflows)
+        return (dflows,) + (None,) * 7
+
+
+def gather_at(frame1, frame2, flows, pix, pair, tau, rev=None, *, blend=None, flow_grad=False):
+    """`gather`'s rule at a list of N points: (R, N, C) fp32.  Point n lies at pix[n] = (y, x), fp32 pixel coordinates of any
+    value, in pair pair[n] (int32) of the batch, at the in-between time tau[n]; everything but `blend` is on the device.
+
+        G1 = flows[0, 0:2, n], c1 = 1 - tau[n];   G0 = flows[1, 2:4, n], c0 = tau[n] where S == 2 and not rev[n], else G0 = G1, c0 = -tau[n]
+        q0 = p + c0 G0, q1 = p + c1 G1;   (W0, n0) = sample(I0[b], q0), (W1, n1) = sample(I1[b], q1), H0 = sample(I0[b], p).W, H1 likewise
+        out[r, n, c] = (a0 W0 + a1 W1 + e (a0 H0 + a1 H1)) / (a0 n0 + a1 n1 + e),   a1 = blend[r], a0 = 1 - a1, e = 2^-10
+
+    `flows`: (S, 4, N), S = 1 or 2 -- torch.stack of `flownet.flow_at(.., planar=True)` results at (s, y, x) and, for S = 2, at
+    (s - dt, y, x).  `blend`: 1 to 4 host floats; None: one blend, a1 = tau[n], the interpolated frame.  A point on an integer pixel
+    gets the bits `gather` gives that pixel.  Nothing in a device tensor is trusted: a pair outside [0, B) gives a row of zeros and a
+    zero gradient, a coordinate that is not finite (or 1e9 or more in size) has no tap.  One launch, no workspace, no atomics.
+
+    `flow_grad=True`: where `flows` requires grad the result carries a gradient to it, and to nothing else, by `gather`'s formulas in
+    one more launch: dG1 lands in [0, 0:2], dG0 in [1, 2:4] or, where G0 = G1, is added as dG0 + dG1; the other values of the column
+    are zeros; the R blends are summed in ascending r.  Equal inputs give equal bits."""
+    b, c, h, w, s, n, blend = _gather_at_inputs('gather_at', frame1, frame2, flows, pix, pair, tau, rev, blend, flow_grad)
+    frame1, frame2 = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous()
+    pix, tau = _gpu32(pix).contiguous(), _gpu32(tau).contiguous()
+    if pix.data_ptr() % 8:
+        pix = pix.clone()                   # the kernel reads (y, x) as one 8-byte load
+    if not pair.is_cuda or (rev is not None and not rev.is_cuda):
+        raise NotImplementedError('sin-inn_amd flow-synthesis operators run on the GPU only (got a CPU tensor)')
+    pair = pair.detach().contiguous()
+    if rev is not None:
+        rev = rev.detach().contiguous()
+        rev = rev.view(torch.uint8) if rev.dtype == torch.bool else rev
+    _gpu32(flows)
+    if flow_grad and flows.requires_grad and torch.is_grad_enabled():
+        return _GatherAtFlowGrad.apply(flows, frame1, frame2, pix, pair, tau, rev, blend)
+    out = torch.empty((1 if blend is None else len(blend), n, c), device=frame1.device, dtype=torch.float32)
+    return _gather_at_call(_lib.lib().sininn_flow_gather_at, frame1, frame2, flows.detach().contiguous(), pix, pair, tau, rev, blend,
+                           (), out)
+
+
+def bilinear_gather_at(img, pair, qx, qy):
+    """sample(I[pair], q) with torch ops at a list: img (B, C, H, W), pair (N,) long inside [0, B), qx, qy (N,) -> (W (N, C), n (N,)).
+    `bilinear_gather`'s rule and order of summation."""
+    b, c, h, w = img.shape
+    ok = (qx.abs() < 1e9) & (qy.abs() < 1e9)
+    qx, qy = torch.where(ok, qx, torch.zeros_like(qx)), torch.where(ok, qy, torch.zeros_like(qy))
+    fx, fy = qx.floor(), qy.floor()
+    x0, y0 = fx.long(), fy.long()
+    wx1, wy1 = qx - fx, qy - fy
+    wx0, wy0 = 1 - wx1, 1 - wy1
+    flat = img.reshape(b, c, h * w)
+    total, n = None, None
+    for dy, dx, wy, wx in ((0, 0, wy0, wx0), (0, 1, wy0, wx1), (1, 0, wy1, wx0), (1, 1, wy1, wx1)):
+        yy, xx = y0 + dy, x0 + dx
+        inside = ok & (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+        weight = torch.where(inside, wy * wx, torch.zeros_like(wx))
+        term = weight[:, None] * flat[pair, :, yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1)]
+        total = term if total is None else total + term
+        n = weight if n is None else n + weight
+    return total, n
+
+
+def gather_at_from(frame1, frame2, flows, pix, pair, tau, rev, blend, sample=bilinear_gather_at, eps=GATHER_EPS):
+    """The definition of `gather_at`, operation by operation, in the dtype and on the device of the frames.  `sample` and `eps` are
+    the places a test swaps in something else."""
+    dt, dev = frame1.dtype, frame1.device
+    b = frame1.shape[0]
+    flows, pix, tau = flows.to(device=dev, dtype=dt), pix.to(device=dev, dtype=dt), tau.to(device=dev, dtype=dt)
+    pair = pair.to(dev).long()
+    inside = (pair >= 0) & (pair < b)
+    at = pair.clamp(0, b - 1)
+    py, px = pix[:, 0], pix[:, 1]
+    g1 = flows[0, 0:2]
+    if flows.shape[0] == 2 and rev is not None:
+        back = rev.to(dev).bool()
+        g0, c0 = torch.where(back, g1, flows[1, 2:4]), torch.where(back, -tau, tau)
+    elif flows.shape[0] == 2:
+        g0, c0 = flows[1, 2:4], tau
+    else:
+        g0, c0 = g1, -tau
+    c1 = 1 - tau
+    (w0, n0), (w1, n1) = sample(frame1, at, px + c0 * g0[0], py + c0 * g0[1]), sample(frame2, at, px + c1 * g1[0], py + c1 * g1[1])
+    h0, h1 = sample(frame1, at, px, py)[0], sample(frame2, at, px, py)[0]
+    rows = []
+    for a1 in ([tau] if blend is None else [torch.full_like(tau, v) for v in blend]):
+        a0 = 1 - a1
+        num = (a0[:, None] * w0 + a1[:, None] * w1) + eps * (a0[:, None] * h0 + a1[:, None] * h1)
+        den = (a0 * n0 + a1 * n1) + eps
+        rows.append(torch.where(inside[:, None], num / den[:, None], torch.zeros_like(num)))
+    return torch.stack(rows)
+
+
+def gather_at_composed(frame1, frame2, flows, pix, pair, tau, rev=None, *, blend=None, flow_grad=False):
+    """`gather_at` from torch ops, on the device and in the dtype of the frames (CPU or GPU, fp32 or fp64; the other float inputs are
+    converted to it): the baseline and the reference.  In fp32 it rounds where the fused operator rounds.  `flow_grad=True`: where
+    `flows` requires grad the result carries autograd's gradient to it."""
+    _, _, _, _, _, _, blend = _gather_at_inputs('gather_at_composed', frame1, frame2, flows, pix, pair, tau, rev, blend, flow_grad)
+    assert frame1.dtype in (torch.float32, torch.float64) and frame2.dtype == frame1.dtype
+    args = (frame1.detach(), frame2.detach(), flows, pix.detach(), pair, tau.detach(), rev, blend)
+    if flow_grad and flows.requires_grad and torch.is_grad_enabled():
+        return gather_at_from(*args)
+    with torch.no_grad():
+        return gather_at_from(*args)
+
+
 # ---- frame quality (DESIGN 18) ----
 
 Quality = collections.namedtuple('Quality', 'psnr ssim mse map')

@@ -31,7 +31,9 @@ Differences from the reference, all on purpose:
   * `--loss-between W` adds a photometric consistency term at random in-between times, which the reference has not:
     the virtual frame at s = t0 + tau dt is read once from frame 1 alone and once from frame 2 alone through `flowsynth.gather`
     (blend weights 0 and 1), and W mean |A - B| trains the flows at s through the operator's gradient.  Off (W = 0) the step is
-    the reference's, launch for launch.
+    the reference's, launch for launch.  `--between-points N` draws the term at N random (pair, tau, y, x) a step
+    instead of whole frames: the network runs on N or 2 N points through `flownet.flow_at` and `flowsynth.gather_at` reads the
+    two frames at them.
 """
 import ctypes as C
 import os
@@ -239,6 +241,7 @@ class FlowTrainer(LightningModule):
         # the in-between consistency loss: off unless the namespace carries a non-zero weight
         self.between_weight = float(getattr(args, 'loss_between', 0) or 0)
         self.between_rng = None
+        self.between_points = None
         if self.between_weight != 0:
             dim = int(self.net.domain_dim)
             if dim != 3:
@@ -256,6 +259,17 @@ class FlowTrainer(LightningModule):
             self.between_rng = random.Random(getattr(args, 'between_seed', 0))          # seeded once per trainer; host only
             self.between_flows = None            # test hook: the (T', 4, h, w) flows of the last between term
             self.between_frames = None           # test hook: its synthesized frames X (B, 2K, C, h, w)
+            # at sampled points: N random (pair, tau, y, x) a step instead of whole grids; present only when given
+            self.between_points = getattr(args, 'between_points', None)
+            if self.between_points is not None:
+                if hasattr(args, 'between_taus'):
+                    raise ValueError('--between-taus draws whole frames, --between-points sampled points: give one of them')
+                self.between_points = int(self.between_points)
+                if not 1 <= self.between_points <= GRID_POINTS:
+                    raise ValueError(f'--between-points {self.between_points}: 1 to {GRID_POINTS} points a step (one flow_at call a slab)')
+                self.between_seed = int(getattr(args, 'between_seed', 0))
+                self._between_gens = {}          # device -> torch.Generator, seeded once per trainer
+                self.between_sample = None       # test hook: (pix, pair, tau, rev) of the last between term
 
     # ---- the pieces of the step ----
 
@@ -367,6 +381,42 @@ class FlowTrainer(LightningModule):
         self.between_flows, self.between_frames = flows, frames
         return self.between_weight * (frames[:, :k] - frames[:, k:]).abs().mean()
 
+    def between_points_table(self, times, b, h, w):
+        """The point list of one step, drawn with torch ops on the device of `times` from a generator seeded once per
+        trainer; nothing is read back.  pair ~ U{0 .. B-1}, tau ~ U[0, 1), py ~ U[0, H-1], px ~ U[0, W-1]; the poses
+        (times[pair] + tau dt, 2 py / (H-1) - 1, 2 px / (W-1) - 1), and under back='network' the same poses at s - dt, with rev set
+        where s - dt lies before the clip's first stamp (-1; `gather_slots`' slack of dt / 1000).  Returns
+        (pix (N, 2), pair (N,) int32, tau (N,), rev (N,) bool or None, [poses (N, 3) per slab])."""
+        dev, n, dt = times.device, self.between_points, float(self.between_dt)
+        if dev not in self._between_gens:
+            self._between_gens[dev] = torch.Generator(device=dev).manual_seed(self.between_seed)
+        gen = self._between_gens[dev]
+        pair = torch.randint(0, b, (n,), generator=gen, device=dev, dtype=torch.int32)
+        u = torch.rand(3, n, generator=gen, device=dev, dtype=torch.float32)
+        tau, py, px = u[0], u[1] * (h - 1), u[2] * (w - 1)
+        s = times.detach().to(torch.float32).reshape(-1)[pair.long()] + tau * dt
+        ys, xs = 2 * py / max(h - 1, 1) - 1, 2 * px / max(w - 1, 1) - 1
+        poses, rev = [torch.stack((s, ys, xs), dim=1)], None
+        if self.between_back == 'network':
+            before = s - dt
+            rev = before < -1.0 - 1e-3 * dt
+            poses.append(torch.stack((before, ys, xs), dim=1))
+        return torch.stack((py, px), dim=1), pair, tau, rev, poses
+
+    def between_points_loss(self, frame1, frame2, times, scale):
+        """weight * mean |A - B| at N fresh points: the network at the N (under back='network' 2 N) poses through `flow_at`, one call
+        a slab, then one `gather_at` call with blends 0 and 1 and its gradient to the flows.  `times`: the batch's stamps, on the
+        device."""
+        from . import flowsynth
+        b, _, h, w = frame1.shape
+        pix, pair, tau, rev, poses = self.between_points_table(times, b, h, w)
+        factor = self._scale(scale, frame1)
+        flows = torch.stack([flownet.flow_at(self.net, p, factor, planar=True) for p in poses])
+        synth = flowsynth.gather_at if self.fused else flowsynth.gather_at_composed
+        out = synth(frame1, frame2, flows, pix, pair, tau, rev, blend=(0.0, 1.0), flow_grad=True)
+        self.between_flows, self.between_frames, self.between_sample = flows, out, (pix, pair, tau, rev)
+        return self.between_weight * (out[0] - out[1]).abs().mean()
+
     # ---- the LightningModule surface ----
 
     def training_step(self, batch, batch_idx):
@@ -376,7 +426,10 @@ class FlowTrainer(LightningModule):
             self._new_epoch('train/')
         if self.between_weight != 0:
             # before the step's own flow_fields call: a spatial controller stashes at the grid evaluated LAST, the frame times'
-            between_loss = self.between_loss(frame1, frame2, self._host_times(times), scale)
+            if self.between_points is not None:
+                between_loss = self.between_points_loss(frame1, frame2, times, scale)
+            else:
+                between_loss = self.between_loss(frame1, frame2, self._host_times(times), scale)
         flow12, flow21 = self.forward(frame1, times, scale)
         if len(batch) == 5:
             self.log('train/EPE', self._epe(flow12, batch[-1]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])

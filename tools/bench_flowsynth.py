@@ -22,6 +22,11 @@ repeated over the slot table's time slices (the operator's time does not depend 
 4 flow words, 2 C words of the two frames at the pixel and C written per output pixel-frame (`kloop`: the 2 C words once per pixel).
 Then one `flowgather_interpolate` line per K: the whole `FlowTrainer.interpolate` call -- network evaluations included, an unfitted
 --net under its controller -- for splat, gather/network and gather/reverse.
+
+    python tools/bench_flowsynth.py --gather-at N [--baseline]
+
+times forward plus backward of the point form `flowsynth.gather_at(.., blend=(0, 1), flow_grad=True)` at N random points of
+the batch, one `flowgather_at_grad` line for S = 2 and one for S = 1, with --baseline against the autograd of `gather_at_composed`.
 """
 import argparse
 import json
@@ -189,6 +194,49 @@ def gather_grad_lines(a, dev):
     return lines
 
 
+def gather_at_lines(a, dev):
+    """forward plus backward of gather_at(.., blend=(0, 1), flow_grad=True) at N random points against the autograd of
+    gather_at_composed on the device: S = 2 with the first pair's points reversed, and S = 1.  min_bytes, C = 3, per
+    point: forward pix 2, pair, tau, flows 4, taps 2 x 4 x 3 x 2 (q and p), out 2 x 3 written; backward the same reads, g 6 read, the
+    column's 4 S words written."""
+    from sin_inn_amd import flowdata, flowsynth
+    clip = flowdata.SyntheticClip(a.batch + 1, a.height, a.width)
+    i0, i1 = clip.video[:-1].contiguous().to(dev), clip.video[1:].contiguous().to(dev)
+    n = a.gather_at
+    gen = torch.Generator(device=dev).manual_seed(0)
+    pair = torch.randint(0, a.batch, (n,), generator=gen, device=dev, dtype=torch.int32)
+    u = torch.rand(3, n, generator=gen, device=dev)
+    tau, pix = u[0].contiguous(), torch.stack((u[1] * (a.height - 1), u[2] * (a.width - 1)), 1)
+    at = pair.long() * a.height * a.width + pix[:, 0].round().long() * a.width + pix[:, 1].round().long()
+    truth = torch.cat([clip.flow, -clip.flow], 1).to(dev).permute(1, 0, 2, 3).reshape(4, -1)[:, at]       # the clip's flows at the points
+    lines = []
+    for s in (2, 1):
+        flows = torch.stack([truth] * s).contiguous().requires_grad_(True)
+        rev = (pair == 0) if s == 2 else None
+        g = torch.randn(2, n, 3, device=dev)
+
+        def step(fn):
+            flows.grad = None
+            fn(i0, i1, flows, pix, pair, tau, rev, blend=(0.0, 1.0), flow_grad=True).backward(g)
+            return flows.grad
+
+        todo = {'fused': lambda: step(flowsynth.gather_at)}
+        if a.baseline:
+            todo['composed'] = lambda: step(flowsynth.gather_at_composed)
+        reads = 2 + 1 + 1 + 4 + 48
+        min_bytes = 4 * n * ((reads + 6) + (reads + 6 + 4 * s))
+        line = dict(op='flowgather_at_grad', height=a.height, width=a.width, batch=a.batch, N=n, S=s, R=2, min_bytes=min_bytes)
+        for name, (best, meds) in _timed(todo, a).items():
+            line[f'{name}_ms'], line[f'{name}_ms_windows'] = best, meds
+        line['fused_tb_per_s'] = round(min_bytes / (line['fused_ms'] * 1e-3) / 1e12, 3)
+        if a.baseline:
+            line['composed_over_fused'] = round(line['composed_ms'] / line['fused_ms'], 3)
+            line['max_abs_diff_composed'] = float((step(flowsynth.gather_at).clone() - step(flowsynth.gather_at_composed)).abs().max())
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def main():
     from sin_inn_amd import flowdata, flowsynth
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
@@ -205,13 +253,16 @@ def main():
     ap.add_argument('--gather', action='store_true', help='time flowsynth.gather and the whole interpolate call instead (DESIGN 19)')
     ap.add_argument('--gather-grad', action='store_true',
                     help='time forward plus backward of flowsynth.gather(.., flow_grad=True) (and with --baseline the autograd of gather_composed) instead (DESIGN 22)')
+    ap.add_argument('--gather-at', type=int, metavar='N',
+                    help='time forward plus backward of flowsynth.gather_at at N points (and with --baseline the autograd of gather_at_composed) instead (DESIGN 23)')
     ap.add_argument('--net', default='PRBF', help='--gather: the network of the whole-call lines')
     a = ap.parse_args()
     assert 2 <= a.factor <= 65
     dev = torch.device('cuda', 0)
-    if a.quality or a.gather or a.gather_grad:
-        lines = gather_grad_lines(a, dev) if a.gather_grad else gather_lines(a, dev) if a.gather else quality_lines(a, dev)
-        for line in ([] if a.gather or a.gather_grad else lines):           # the gather lines are printed as they are measured
+    if a.quality or a.gather or a.gather_grad or a.gather_at:
+        lines = (gather_at_lines(a, dev) if a.gather_at else gather_grad_lines(a, dev) if a.gather_grad else gather_lines(a, dev)
+                 if a.gather else quality_lines(a, dev))
+        for line in ([] if a.gather or a.gather_grad or a.gather_at else lines):   # the gather lines are printed as they are measured
             print(json.dumps(line))
         if a.log:
             with open(os.path.join(ROOT, 'profiles', 'flowsynth_bench.jsonl'), 'a') as f:

@@ -29,6 +29,8 @@ adds the step with the in-between consistency loss next to the ste
     between_composed   the loss through gather_composed(.., flow_grad=True) (FlowTrainer.fused = False; as `torch` above, the two
                        flowtrain operators are torch expressions too)
     between_network    flow_fields forward + backward alone at the stamps of one between term: what the extra evaluations cost
+With --between-points N the loss is drawn at N random points a step -- flowsynth.gather_at, or gather_at_composed -- and
+between_network is flow_at forward + backward at the N (under --between-back network 2 N) poses of one draw.
 The generator is reset before every window, so all windows draw the same times.  --log appends the line to
 profiles/flowtrainer_bench.jsonl.
 """
@@ -63,6 +65,8 @@ def main():
     ap.add_argument('--loss-between', type=float, default=0.0, help='also time the step with the in-between loss of this weight')
     ap.add_argument('--between-taus', type=int, default=1)
     ap.add_argument('--between-back', default='network', choices=['network', 'reverse'])
+    ap.add_argument('--between-points', type=int, metavar='N',
+                    help='--loss-between: the loss at N random points a step (DESIGN 23) instead of --between-taus whole frames')
     ap.add_argument('--log', action='store_true', help='append the line to profiles/flowtrainer_bench.jsonl')
     a = ap.parse_args()
     from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
@@ -104,8 +108,9 @@ def main():
         net2 = flownet.all_model_dict[a.net](flownet.ModelParams())
         if net2.is_progressive:
             net2 = progressive.LinearControllerEarly(net2, 5000, epsilon=1e-3)
-        args2 = argparse.Namespace(**{**vars(args), 'net': net2, 'loss_between': a.loss_between, 'between_taus': a.between_taus,
-                                      'between_back': a.between_back, 'between_dt': dt})
+        how = {'between_points': a.between_points} if a.between_points else {'between_taus': a.between_taus}
+        args2 = argparse.Namespace(**{**vars(args), 'net': net2, 'loss_between': a.loss_between, 'between_back': a.between_back,
+                                      'between_dt': dt, **how})
         model2 = flowtrainer.FlowTrainer(args2).to(dev)
         opt2 = model2.attach_optimizer()
         times_host = clip.T[:a.batch].tolist()
@@ -123,7 +128,18 @@ def main():
                 opt2.step()
             return run
 
+        def points_network():
+            opt2.zero_grad()
+            for p, u in zip(poses, up_points):
+                flownet.flow_at(model2.net, p, clip.flow_scale, planar=True).backward(u)
+
+        if a.between_points:
+            poses = model2.between_points_table(batch[2], a.batch, a.height, a.width)[4]
+            up_points = [torch.randn(4, a.between_points, device=dev) for _ in poses]
+
         def between_network():
+            if a.between_points:
+                return points_network()
             opt2.zero_grad()
             per = max(1, flowtrainer.GRID_POINTS // (a.height * a.width))
             for i in range(0, len(stamps), per):
@@ -146,6 +162,9 @@ def main():
     out['fused_over_torch'] = round(out['fused_ms'] / out['torch_ms'], 4)
     if a.loss_between != 0:
         out.update(loss_between=a.loss_between, between_taus=a.between_taus, between_back=a.between_back, between_stamps=len(stamps))
+        if a.between_points:
+            del out['between_taus'], out['between_stamps']
+            out.update(between_points=a.between_points, between_network_points=a.between_points * len(poses))
         out['between_extra_ms'] = round(out['between_fused_ms'] - out['fused_ms'], 4)
         out['between_network_share_of_extra'] = round(out['between_network_ms'] / out['between_extra_ms'], 3)
         out['between_fused_over_composed'] = round(out['between_fused_ms'] / out['between_composed_ms'], 4)

@@ -66,7 +66,9 @@ def get_parser():
                     help='--synthesis gather: where the flow toward the previous frame comes from')
     ap.add_argument('--loss-between', type=float, default=0, metavar='W',
                     help='--fit-epochs: weight of the in-between consistency loss (main.py --loss-between; DESIGN 22)')
-    ap.add_argument('--between-taus', type=int, default=1, metavar='K', help='--loss-between: in-between times drawn per step')
+    ap.add_argument('--between-taus', type=int, metavar='K', help='--loss-between: in-between times drawn per step (default 1)')
+    ap.add_argument('--between-points', type=int, metavar='N',
+                    help='--loss-between: N random points a step instead of whole frames (main.py --between-points; DESIGN 23)')
     ap.add_argument('--between-back', choices=('network', 'reverse'), default='network', help='--loss-between: as --back')
     return ap
 
@@ -84,6 +86,10 @@ def get_args(argv=None):
         a.factor = 2
     if a.factor < 1 or a.factor > 65:
         ap.error('--factor: 1 .. 65 (one call synthesizes factor - 1 <= 64 times)')
+    if a.between_points is not None and a.between_taus is not None:
+        ap.error('--between-taus draws whole frames, --between-points sampled points: give one of them')
+    if a.between_points is not None and a.between_points < 1:
+        ap.error('--between-points N: N >= 1')
     if a.fit_epochs < 0 or a.batch < 1:
         ap.error('--fit-epochs >= 0 and --batch >= 1')
     return a
@@ -105,7 +111,8 @@ def trainer_args(a):
     if a.holdout:
         argv += ['--holdout', str(a.holdout)]
     if a.loss_between and a.fit_epochs:
-        argv += ['--loss-between', str(a.loss_between), '--between-taus', str(a.between_taus), '--between-back', a.between_back]
+        argv += ['--loss-between', str(a.loss_between), '--between-back', a.between_back]
+        argv += ['--between-points', str(a.between_points)] if a.between_points is not None else ['--between-taus', str(a.between_taus or 1)]
     args = m.get_args(argv)
     args.net = m.build_net(args)
     return m, args

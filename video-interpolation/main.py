@@ -25,7 +25,8 @@ Differences from the reference, all to make the path runnable here:
   * checkpoints are written every max(epochs // 100, 1) epochs (the reference's `every_n_epochs=0` below 100 epochs writes none)
     whenever `--wandb` is given, `test` and `sintel` load the newest one, and `train` resumes from it;
   * `--loss-between W` (with `--between-taus K`, `--between-back {network,reverse}`) adds the in-between consistency loss of
-    sin_inn_amd/flowtrainer.py to the training step; the default 0 leaves the step as it was.
+    sin_inn_amd/flowtrainer.py to the training step; the default 0 leaves the step as it was.  `--between-points N` in
+    place of `--between-taus` draws it at N random points a step.
 """
 import argparse
 import os
@@ -83,6 +84,8 @@ def get_parser():
                         help='--loss-between: in-between times drawn per step (default 1)')
     parser.add_argument('--between-back', default=argparse.SUPPRESS, choices=['network', 'reverse'],
                         help="--loss-between: the flow toward the previous frame, as interpolate.py's --back (default network)")
+    parser.add_argument('--between-points', default=argparse.SUPPRESS, type=int, metavar='N',
+                        help='--loss-between: draw the term at N random (pair, tau, y, x) a step instead of whole frames (DESIGN 23)')
     # Logging options
     parser.add_argument('--wandb', help='any name: selects the JSON-lines FileLogger and checkpointing')
     parser.add_argument('--log-gt', action='store_true')
@@ -97,6 +100,11 @@ def get_args(argv=None):
         args.occl = None
     if getattr(args, 'holdout', 2) < 2:
         parser.error('--holdout S: S >= 2 (every S-th frame is kept)')
+    if hasattr(args, 'between_points'):
+        if hasattr(args, 'between_taus'):
+            parser.error('--between-taus draws whole frames, --between-points sampled points: give one of them')
+        if args.between_points < 1:
+            parser.error('--between-points N: N >= 1')
     if args.spatially_adaptive and args.net not in SPATIAL_NETWORKS:
         parser.error(f'--spatially-adaptive with --net {args.net} is out of scope here: the per-point masks of '
                      f'sin_inn_amd.progressive.StashedSpatialController are built for the 515-wide progressive networks '
