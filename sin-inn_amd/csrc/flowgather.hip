@@ -4,10 +4,13 @@
 //   (W0, n0) = sample(I0, q0),  (W1, n1) = sample(I1, q1)        exact-geometry bilinear; a tap outside the frame adds 0 to W and to n
 //   a0 = 1 - tau, a1 = tau,  L = a0 I0(p) + a1 I1(p)
 //   out = (a0 W0 + a1 W1 + e L) / (a0 n0 + a1 n1 + e),  e = 2^-10
-// The gradient with respect to the flows is at the end of the file: flowgather_bwd_kernel and flowgather_reduce_kernel.
 // G0 and G1 are channel pairs of time slices of one (T', 4, H, W) tensor, named per (b, k) by a slot table the host has validated:
 // six ints a row -- idx0, idx1 (time slice), ch0, ch1 (0 or 2), then the bits of the floats c0, c1.  One launch whatever K is.
 // Every operation is rounded once and none is contracted (`flowsynth.gather_composed` evaluates the same expression in torch).
+// Each piece of that arithmetic is one helper with its own `fp contract(off)` (the pragma does not reach into a callee), and every
+// kernel is made of them, so they agree to the bit: the grid rule (flowgather_kernel), its gradient with respect to the flows (DESIGN 22:
+// flowgather_bwd_kernel, flowgather_reduce_kernel) and both at a list of points (flowgather_points_kernel, .._bwd_kernel).
+#include <type_traits>
 #include "common.h"
 #include "bilinear_taps.h"
 
@@ -16,6 +19,14 @@ namespace sininn {
 constexpr int FG_THREADS = 256;         // one block: 256 consecutive pixels of one frame's flattened H W
 constexpr int FG_MAX_K = 64;
 constexpr int FG_SLOT_INTS = 6;
+
+static int64_t gather_tiles(int64_t n) { return (n + FG_THREADS - 1) / FG_THREADS; }         // blocks of FG_THREADS lanes over n
+// launch(std::integral_constant<int, C>()): the kernels exist for C = 1 and C = 3, and the checks admit no other.
+template <typename Launch>
+static void gather_per_channels(int C, Launch launch) {
+  if (C == 1) launch(std::integral_constant<int, 1>());
+  else launch(std::integral_constant<int, 3>());
+}
 
 // The four taps of one sample: the offset of the north-west tap and the weights, zero where the tap lies outside the frame.
 // n is the sum of the weights inside.  A coordinate that is not finite, or too large for an int, has no tap inside.
@@ -45,40 +56,85 @@ __device__ __forceinline__ GatherTaps gather_taps_at(float px, float py, float c
   return t;
 }
 
-__device__ __forceinline__ GatherTaps gather_taps(int x, int y, float c, float gx, float gy, int H, int W) {
-  return gather_taps_at((float)x, (float)y, c, gx, gy, H, W);
+// The four taps of one plane, fetched once: a tap outside the frame is 0 and is not read.
+struct GatherTapValues { float t00, t01, t10, t11; };
+
+__device__ __forceinline__ GatherTapValues gather_fetch(const float* __restrict__ plane, const GatherTaps& t, int W) {
+  return {t.v00 ? plane[t.nw] : 0.f, t.v01 ? plane[t.nw + 1] : 0.f, t.v10 ? plane[t.nw + W] : 0.f, t.v11 ? plane[t.nw + W + 1] : 0.f};
 }
 
-__device__ __forceinline__ float gather_sample(const float* __restrict__ plane, const GatherTaps& t, int W) {
-#pragma clang fp contract(off)
-  const float t00 = t.v00 ? plane[t.nw] : 0.f, t01 = t.v01 ? plane[t.nw + 1] : 0.f;
-  const float t10 = t.v10 ? plane[t.nw + W] : 0.f, t11 = t.v11 ? plane[t.nw + W + 1] : 0.f;
-  return ((t.w00 * t00 + t.w01 * t01) + t.w10 * t10) + t.w11 * t11;
+// The taps of the all-ones image: n and its slopes are gather_sample and gather_slopes of these.
+__device__ __forceinline__ GatherTapValues gather_ones(const GatherTaps& t) {
+  return {t.v00 ? 1.f : 0.f, t.v01 ? 1.f : 0.f, t.v10 ? 1.f : 0.f, t.v11 ? 1.f : 0.f};
 }
 
-// One output pixel of frame (b, k): `here0`, `here1` are I0(p), I1(p), loaded by the caller.
-template <int C>
-__device__ __forceinline__ void gather_pixel(const float* __restrict__ i0b, const float* __restrict__ i1b, const float* here0,
-                                             const float* here1, const float* __restrict__ flows, int64_t flow_stride,
-                                             const int* __restrict__ slot, float tk, int x, int y, int64_t r, int H, int W, int64_t HW,
-                                             float* __restrict__ out, uint8_t* __restrict__ out_u8, int64_t o) {
+__device__ __forceinline__ float gather_sample(const GatherTapValues& v, const GatherTaps& t) {
 #pragma clang fp contract(off)
-  const float* g0 = flows + slot[0] * flow_stride + slot[2] * HW + r;
-  const float* g1 = flows + slot[1] * flow_stride + slot[3] * HW + r;
-  const float c0 = __int_as_float(slot[4]), c1 = __int_as_float(slot[5]);
-  const GatherTaps t0 = gather_taps(x, y, c0, g0[0], g0[HW], H, W);
-  const GatherTaps t1 = gather_taps(x, y, c1, g1[0], g1[HW], H, W);
-  const float a0 = 1.f - tk, a1 = tk, e = 0.0009765625f;
-  const float den = (a0 * t0.n + a1 * t1.n) + e;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const float w0 = gather_sample(i0b + c * HW, t0, W), w1 = gather_sample(i1b + c * HW, t1, W);
-    const float lin = a0 * here0[c] + a1 * here1[c];
-    const float num = (a0 * w0 + a1 * w1) + e * lin;
-    const float v = __fdiv_rn(num, den);
-    out[o + c * HW] = v;
-    if (out_u8) out_u8[o + c * HW] = (uint8_t)frame_byte(v);
-  }
+  return ((t.w00 * v.t00 + t.w01 * v.t01) + t.w10 * v.t10) + t.w11 * v.t11;
+}
+
+// The slopes of one sampled plane along x and y: the derivative of the bilinear interpolant of the zero-padded plane inside
+// the cell floor(q) the forward pass took (on a cell border: the right-hand derivative).  A sample without a tap has all weights zero.
+__device__ __forceinline__ float2 gather_slopes(const GatherTapValues& v, const GatherTaps& t) {
+#pragma clang fp contract(off)
+  return {t.wy0 * (v.t01 - v.t00) + t.wy1 * (v.t11 - v.t10), t.wx0 * (v.t10 - v.t00) + t.wx1 * (v.t11 - v.t01)};
+}
+
+// One channel of the rule: D = a0 n0 + a1 n1 + e, then out = (a0 W0 + a1 W1 + e (a0 h0 + a1 h1)) / D.  h0, h1 are the two frames at the
+// point itself: I0(p), I1(p) in the grid kernels, sample(I0, p), sample(I1, p) in the point kernels.
+constexpr float FG_EPS = 0.0009765625f;
+
+__device__ __forceinline__ float gather_den(float a0, float a1, float n0, float n1) {
+#pragma clang fp contract(off)
+  return (a0 * n0 + a1 * n1) + FG_EPS;
+}
+
+__device__ __forceinline__ float gather_blend(float a0, float a1, float den, float w0, float w1, float h0, float h1) {
+#pragma clang fp contract(off)
+  const float lin = a0 * h0 + a1 * h1;
+  const float num = (a0 * w0 + a1 * w1) + FG_EPS * lin;
+  return __fdiv_rn(num, den);
+}
+
+// The gradient with respect to the flows, for one of the two samples (W, n, c, a), `w` and `n` the slopes of W_c and of n:
+//   dG = c a / D  sum_c g_c (grad_q W_c - out_c grad_q n)
+// gather_grad_add takes one channel into the sum, gather_grad_scale closes it.  No gradient to the frames, tau or the coefficients.
+__device__ __forceinline__ void gather_grad_add(float g, float v, float2 w, float2 n, float2& s) {
+#pragma clang fp contract(off)
+  s.x = s.x + g * (w.x - v * n.x); s.y = s.y + g * (w.y - v * n.y);
+}
+
+__device__ __forceinline__ float2 gather_grad_scale(float c, float a, float den, float2 s) {
+#pragma clang fp contract(off)
+  const float k = __fdiv_rn(c * a, den);
+  return {k * s.x, k * s.y};
+}
+
+// The prologue of the grid kernels.  A block is 256 consecutive pixels of one plane: `frame` counts the blocks' planes (b K + k, with
+// KLOOP b, in the reduce kernel 2 target + component), r = y W + x.  False past the plane's last pixel.
+struct GatherLane { unsigned frame; int x, y; int64_t r; };
+
+__device__ __forceinline__ bool gather_lane(int tiles, int W, int64_t HW, GatherLane& p) {
+  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;         // H W < 2^31: 32-bit divisions only
+  p = {blockIdx.x / (unsigned)tiles, (int)(pix % (unsigned)W), (int)(pix / (unsigned)W), pix};
+  return pix < HW;
+}
+
+// Row (b, k) of the slot table at the lane's pixel: the two tap sets, the coefficients, the blend weights and D.
+struct GatherRow { GatherTaps t0, t1; float c0, c1, a0, a1, den; };
+
+__device__ __forceinline__ GatherRow gather_row(const float* __restrict__ flows, int64_t flow_stride, const int* __restrict__ slot,
+                                                float tk, const GatherLane& p, int H, int W, int64_t HW) {
+#pragma clang fp contract(off)
+  GatherRow row;
+  const float* g0 = flows + slot[0] * flow_stride + slot[2] * HW + p.r;
+  const float* g1 = flows + slot[1] * flow_stride + slot[3] * HW + p.r;
+  row.c0 = __int_as_float(slot[4]); row.c1 = __int_as_float(slot[5]);
+  row.t0 = gather_taps_at((float)p.x, (float)p.y, row.c0, g0[0], g0[HW], H, W);
+  row.t1 = gather_taps_at((float)p.x, (float)p.y, row.c1, g1[0], g1[HW], H, W);
+  row.a0 = 1.f - tk; row.a1 = tk;
+  row.den = gather_den(row.a0, row.a1, row.t0.n, row.t1.n);
+  return row;
 }
 
 // KLOOP = false: a block is 256 pixels of one (b, k).  KLOOP = true: a block is 256 pixels of one b and every lane walks k, so I0(p)
@@ -90,78 +146,67 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_kernel(const float* __r
                                                                 int H, int W, int tiles, float* __restrict__ out,
                                                                 uint8_t* __restrict__ out_u8) {
   const int64_t HW = (int64_t)H * W;
-  const unsigned frame = blockIdx.x / (unsigned)tiles;    // b k, or with KLOOP b
-  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;         // H W < 2^31: 32-bit divisions only
-  if (pix >= HW) return;
-  const int x = (int)(pix % (unsigned)W), y = (int)(pix / (unsigned)W);
-  const int64_t r = pix, b = KLOOP ? frame : frame / (unsigned)K;
+  GatherLane p;
+  if (!gather_lane(tiles, W, HW, p)) return;
+  const int64_t r = p.r, b = KLOOP ? p.frame : p.frame / (unsigned)K;
   const float* i0b = i0 + b * C * HW;
   const float* i1b = i1 + b * C * HW;
   float here0[C], here1[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) { here0[c] = i0b[c * HW + r]; here1[c] = i1b[c * HW + r]; }
-  if (KLOOP) {
-    for (int k = 0; k < K; ++k) {
-      const int64_t bk = b * K + k;
-      gather_pixel<C>(i0b, i1b, here0, here1, flows, flow_stride, slots + bk * FG_SLOT_INTS, tau[k], x, y, r, H, W, HW, out, out_u8,
-                      bk * C * HW + r);
+  auto pixel = [&](int64_t bk, float tk) {                 // one output pixel of frame (b, k)
+    const GatherRow row = gather_row(flows, flow_stride, slots + bk * FG_SLOT_INTS, tk, p, H, W, HW);
+    const int64_t o = bk * C * HW + r;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float w0 = gather_sample(gather_fetch(i0b + c * HW, row.t0, W), row.t0);
+      const float w1 = gather_sample(gather_fetch(i1b + c * HW, row.t1, W), row.t1);
+      const float v = gather_blend(row.a0, row.a1, row.den, w0, w1, here0[c], here1[c]);
+      out[o + c * HW] = v;
+      if (out_u8) out_u8[o + c * HW] = (uint8_t)frame_byte(v);
     }
-  } else {
-    const int64_t bk = frame;
-    gather_pixel<C>(i0b, i1b, here0, here1, flows, flow_stride, slots + bk * FG_SLOT_INTS, tau[frame % (unsigned)K], x, y, r, H, W, HW,
-                    out, out_u8, bk * C * HW + r);
-  }
+  };
+  if (KLOOP) for (int k = 0; k < K; ++k) pixel(b * K + k, tau[k]);
+  else pixel(p.frame, tau[p.frame % (unsigned)K]);
+}
+
+// What the forward and the backward launch both refuse, each under its own name.  `planes`: the most H W planes a (b, k) has in a buffer.
+static int flow_gather_check(const char* who, const void* i0, const void* i1, const void* flows, const void* slots, const void* tau,
+                             int64_t flow_sample_stride, int B, int K, int C, int H, int W, int planes) {
+  SININN_CHECK(i0 && i1 && flows && slots && tau, "%s: null pointer", who);
+  SININN_CHECK(B > 0 && H > 0 && W > 0, "%s: bad shape (every size must be positive)", who);
+  SININN_CHECK(C == 1 || C == 3, "%s: frames have 1 or 3 channels (got %d)", who, C);
+  SININN_CHECK(K >= 1 && K <= FG_MAX_K, "%s: K = %d times in one call, 1 to %d are supported", who, K, FG_MAX_K);
+  const int64_t HW = (int64_t)H * W;
+  SININN_CHECK(HW <= 0x7fffffff, "%s: H * W = %lld is past an int index", who, (long long)HW);
+  SININN_CHECK((int64_t)B * K * gather_tiles(HW) <= 0x7fffffff, "%s: B * K * H * W = %lld needs more blocks than one launch has", who,
+               (long long)B * K * HW);
+  SININN_CHECK((int64_t)B * K * planes <= INT64_MAX / HW, "%s: B * K * C * H * W is past a 64-bit index", who);
+  SININN_CHECK(flow_sample_stride >= 4 * HW, "%s: sample stride %lld is smaller than four channel planes (%lld)", who,
+               (long long)flow_sample_stride, (long long)(4 * HW));
+  return 0;
 }
 
 int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
                        const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st) {
-  SININN_CHECK(i0 && i1 && flows && slots && tau && out, "flow_gather: null pointer");
-  SININN_CHECK(B > 0 && H > 0 && W > 0, "flow_gather: bad shape (every size must be positive)");
-  SININN_CHECK(C == 1 || C == 3, "flow_gather: frames have 1 or 3 channels (got %d)", C);
-  SININN_CHECK(K >= 1 && K <= FG_MAX_K, "flow_gather: K = %d times in one call, 1 to %d are supported", K, FG_MAX_K);
-  const int64_t HW = (int64_t)H * W;
-  SININN_CHECK(HW <= 0x7fffffff, "flow_gather: H * W = %lld is past an int index", (long long)HW);
-  const int64_t tiles = (HW + FG_THREADS - 1) / FG_THREADS;
-  const int64_t blocks = (int64_t)B * (k_loop ? 1 : K) * tiles;
-  SININN_CHECK((int64_t)B * K * tiles <= 0x7fffffff, "flow_gather: B * K * H * W = %lld needs more blocks than one launch has",
-               (long long)B * K * HW);
-  SININN_CHECK((int64_t)B * K * C <= INT64_MAX / HW, "flow_gather: B * K * C * H * W is past a 64-bit index");
-  SININN_CHECK(flow_sample_stride >= 4 * HW, "flow_gather: sample stride %lld is smaller than four channel planes (%lld)",
-               (long long)flow_sample_stride, (long long)(4 * HW));
-  const dim3 grid((unsigned)blocks), block(FG_THREADS);
-#define FG_LAUNCH(CH, LOOP) \
-  hipLaunchKernelGGL((flowgather_kernel<CH, LOOP>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H, W, \
-                     (int)tiles, out, out_u8)
-  if (C == 1) { if (k_loop) FG_LAUNCH(1, true); else FG_LAUNCH(1, false); }
-  else        { if (k_loop) FG_LAUNCH(3, true); else FG_LAUNCH(3, false); }
-#undef FG_LAUNCH
+  SININN_CHECK(out, "flow_gather: null pointer");
+  if (flow_gather_check("flow_gather", i0, i1, flows, slots, tau, flow_sample_stride, B, K, C, H, W, C)) return 1;
+  const int64_t tiles = gather_tiles((int64_t)H * W);
+  const dim3 grid((unsigned)((int64_t)B * (k_loop ? 1 : K) * tiles)), block(FG_THREADS);
+  gather_per_channels(C, [&](auto ch) {
+    constexpr int CH = decltype(ch)::value;
+    if (k_loop)
+      hipLaunchKernelGGL((flowgather_kernel<CH, true>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H, W,
+                         (int)tiles, out, out_u8);
+    else
+      hipLaunchKernelGGL((flowgather_kernel<CH, false>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H, W,
+                         (int)tiles, out, out_u8);
+  });
   SININN_LAUNCH_CHECK("flowgather");
   return 0;
 }
 
 // ---- the gradient with respect to the flows ----
-//   dG0 = c0 a0 / D  sum_c g_c (grad_q W0_c - out_c grad_q n0),   dG1 = c1 a1 / D  sum_c g_c (grad_q W1_c - out_c grad_q n1)
-// grad_q is the derivative of the bilinear interpolant of the zero-padded plane inside the cell floor(q) the forward pass took (on a
-// cell border: the right-hand derivative).  A sample without a tap (a coordinate that is not finite, or 1e9 or more in size) has all
-// weights zero, so its gradient is 0.  No gradient to the frames, tau or the coefficients.
-
-// The slopes of one sampled plane along x and y: taps outside the frame are 0.
-__device__ __forceinline__ void gather_slopes(const float* __restrict__ plane, const GatherTaps& t, int W, float& dx, float& dy) {
-#pragma clang fp contract(off)
-  const float t00 = t.v00 ? plane[t.nw] : 0.f, t01 = t.v01 ? plane[t.nw + 1] : 0.f;
-  const float t10 = t.v10 ? plane[t.nw + W] : 0.f, t11 = t.v11 ? plane[t.nw + W + 1] : 0.f;
-  dx = t.wy0 * (t01 - t00) + t.wy1 * (t11 - t10);
-  dy = t.wx0 * (t10 - t00) + t.wx1 * (t11 - t01);
-}
-
-// The same for the all-ones image: the slopes of n.
-__device__ __forceinline__ void gather_slopes_ones(const GatherTaps& t, float& dx, float& dy) {
-#pragma clang fp contract(off)
-  const float t00 = t.v00 ? 1.f : 0.f, t01 = t.v01 ? 1.f : 0.f, t10 = t.v10 ? 1.f : 0.f, t11 = t.v11 ? 1.f : 0.f;
-  dx = t.wy0 * (t01 - t00) + t.wy1 * (t11 - t10);
-  dy = t.wx0 * (t10 - t00) + t.wx1 * (t11 - t01);
-}
-
 // One lane per (b, k, y, x), the forward kernel's KLOOP = false shape.  The lane recomputes the two tap sets and out_c exactly as the
 // forward pass rounds them, reads C words of g and writes four floats: dG0 (x, y), dG1 (x, y).  `dflows` == nullptr: into the per-row
 // buffer `rows` (B, K, 4, H, W), which flowgather_reduce_kernel sums per target.  Otherwise straight into channels ch0, ch0 + 1 of
@@ -173,42 +218,25 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_bwd_kernel(const float*
                                                                     const int* __restrict__ slots, const float* __restrict__ tau,
                                                                     const float* __restrict__ gout, int K, int H, int W, int tiles,
                                                                     float* __restrict__ rows, float* __restrict__ dflows) {
-#pragma clang fp contract(off)
   const int64_t HW = (int64_t)H * W;
-  const unsigned frame = blockIdx.x / (unsigned)tiles;    // b K + k
-  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;         // H W < 2^31: 32-bit divisions only
-  if (pix >= HW) return;
-  const int x = (int)(pix % (unsigned)W), y = (int)(pix / (unsigned)W);
-  const int64_t r = pix, bk = frame, b = frame / (unsigned)K;
+  GatherLane p;
+  if (!gather_lane(tiles, W, HW, p)) return;
+  const int64_t r = p.r, bk = p.frame, b = p.frame / (unsigned)K;
   const float* i0b = i0 + b * C * HW;
   const float* i1b = i1 + b * C * HW;
   const int* slot = slots + bk * FG_SLOT_INTS;
-  const float tk = tau[frame % (unsigned)K];
-  const float* g0 = flows + slot[0] * flow_stride + slot[2] * HW + r;
-  const float* g1 = flows + slot[1] * flow_stride + slot[3] * HW + r;
-  const float c0 = __int_as_float(slot[4]), c1 = __int_as_float(slot[5]);
-  const GatherTaps t0 = gather_taps(x, y, c0, g0[0], g0[HW], H, W);
-  const GatherTaps t1 = gather_taps(x, y, c1, g1[0], g1[HW], H, W);
-  const float a0 = 1.f - tk, a1 = tk, e = 0.0009765625f;
-  const float den = (a0 * t0.n + a1 * t1.n) + e;
-  float n0x, n0y, n1x, n1y;
-  gather_slopes_ones(t0, n0x, n0y);
-  gather_slopes_ones(t1, n1x, n1y);
-  float s0x = 0.f, s0y = 0.f, s1x = 0.f, s1y = 0.f;
+  const GatherRow row = gather_row(flows, flow_stride, slot, tau[p.frame % (unsigned)K], p, H, W, HW);
+  const float2 n0 = gather_slopes(gather_ones(row.t0), row.t0), n1 = gather_slopes(gather_ones(row.t1), row.t1);
+  float2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const float w0 = gather_sample(i0b + c * HW, t0, W), w1 = gather_sample(i1b + c * HW, t1, W);
-    const float lin = a0 * i0b[c * HW + r] + a1 * i1b[c * HW + r];
-    const float num = (a0 * w0 + a1 * w1) + e * lin;
-    const float v = __fdiv_rn(num, den);                    // out_c, the forward pass's bits
+    const GatherTapValues v0 = gather_fetch(i0b + c * HW, row.t0, W), v1 = gather_fetch(i1b + c * HW, row.t1, W);
+    const float v = gather_blend(row.a0, row.a1, row.den, gather_sample(v0, row.t0), gather_sample(v1, row.t1), i0b[c * HW + r],
+                                 i1b[c * HW + r]);             // out_c, the forward pass's bits
     const float g = gout[(bk * C + c) * HW + r];
-    float w0x, w0y, w1x, w1y;
-    gather_slopes(i0b + c * HW, t0, W, w0x, w0y);
-    gather_slopes(i1b + c * HW, t1, W, w1x, w1y);
-    s0x = s0x + g * (w0x - v * n0x); s0y = s0y + g * (w0y - v * n0y);
-    s1x = s1x + g * (w1x - v * n1x); s1y = s1y + g * (w1y - v * n1y);
+    gather_grad_add(g, v, gather_slopes(v0, row.t0), n0, s0);
+    gather_grad_add(g, v, gather_slopes(v1, row.t1), n1, s1);
   }
-  const float k0 = __fdiv_rn(c0 * a0, den), k1 = __fdiv_rn(c1 * a1, den);
   float* d0;
   float* d1;
   if (dflows) {
@@ -218,8 +246,8 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_bwd_kernel(const float*
     d0 = rows + bk * 4 * HW + r;
     d1 = d0 + 2 * HW;
   }
-  d0[0] = k0 * s0x; d0[HW] = k0 * s0y;
-  d1[0] = k1 * s1x; d1[HW] = k1 * s1y;
+  const float2 e0 = gather_grad_scale(row.c0, row.a0, row.den, s0), e1 = gather_grad_scale(row.c1, row.a1, row.den, s1);
+  d0[0] = e0.x; d0[HW] = e0.y; d1[0] = e1.x; d1[HW] = e1.y;
 }
 
 // One lane per element of dflows.  `list`: for each of the 2 T targets (slice, channel pair) -- target 2 slice + pair -- the begin of its
@@ -230,18 +258,17 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_reduce_kernel(const flo
                                                                        float* __restrict__ dflows) {
 #pragma clang fp contract(off)
   const int64_t HW = (int64_t)H * W;
-  const unsigned plane = blockIdx.x / (unsigned)tiles;    // 2 target + component
-  const unsigned pix = (blockIdx.x % (unsigned)tiles) * FG_THREADS + threadIdx.x;
-  if (pix >= HW) return;
-  const unsigned target = plane >> 1, comp = plane & 1;
+  GatherLane p;
+  if (!gather_lane(tiles, W, HW, p)) return;
+  const unsigned target = p.frame >> 1, comp = p.frame & 1;
   const int begin = list[target], end = list[target + 1];
   const int* entries = list + targets + 1;
   float sum = 0.f;
   for (int i = begin; i < end; ++i) {
-    const float v = rows[((int64_t)entries[i] * 2 + comp) * HW + pix];
+    const float v = rows[((int64_t)entries[i] * 2 + comp) * HW + p.r];
     sum = i == begin ? v : sum + v;
   }
-  dflows[(int64_t)plane * HW + pix] = sum;
+  dflows[(int64_t)p.frame * HW + p.r] = sum;
 }
 
 int64_t flow_gather_bwd_workspace(int B, int K, int H, int W) {
@@ -254,20 +281,11 @@ int64_t flow_gather_bwd_workspace(int B, int K, int H, int W) {
 int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
                            const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
                            int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, hipStream_t st) {
-  SININN_CHECK(i0 && i1 && flows && slots && tau, "flow_gather_bwd: null pointer");
+  if (flow_gather_check("flow_gather_bwd", i0, i1, flows, slots, tau, flow_sample_stride, B, K, C, H, W, 4)) return 1;
   SININN_CHECK(grad_out, "flow_gather_bwd: the gradient of the output is null");
   SININN_CHECK(dflows, "flow_gather_bwd: the gradient of the flows is null");
-  SININN_CHECK(B > 0 && H > 0 && W > 0 && T > 0, "flow_gather_bwd: bad shape (every size must be positive)");
-  SININN_CHECK(C == 1 || C == 3, "flow_gather_bwd: frames have 1 or 3 channels (got %d)", C);
-  SININN_CHECK(K >= 1 && K <= FG_MAX_K, "flow_gather_bwd: K = %d times in one call, 1 to %d are supported", K, FG_MAX_K);
-  const int64_t HW = (int64_t)H * W;
-  SININN_CHECK(HW <= 0x7fffffff, "flow_gather_bwd: H * W = %lld is past an int index", (long long)HW);
-  const int64_t tiles = (HW + FG_THREADS - 1) / FG_THREADS;
-  SININN_CHECK((int64_t)B * K * tiles <= 0x7fffffff, "flow_gather_bwd: B * K * H * W = %lld needs more blocks than one launch has",
-               (long long)B * K * HW);
-  SININN_CHECK((int64_t)B * K * (C > 4 ? C : 4) <= INT64_MAX / HW, "flow_gather_bwd: B * K * C * H * W is past a 64-bit index");
-  SININN_CHECK(flow_sample_stride >= 4 * HW, "flow_gather_bwd: sample stride %lld is smaller than four channel planes (%lld)",
-               (long long)flow_sample_stride, (long long)(4 * HW));
+  SININN_CHECK(T > 0, "flow_gather_bwd: bad shape (every size must be positive)");
+  const int64_t HW = (int64_t)H * W, tiles = gather_tiles(HW);
   SININN_CHECK((int64_t)T * 4 * tiles <= 0x7fffffff, "flow_gather_bwd: T * 4 * H * W = %lld needs more blocks than one launch has",
                (long long)T * 4 * HW);
   if (reduce_list) {
@@ -279,20 +297,15 @@ int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows,
                  "flow_gather_bwd: a reduce list of %lld ints; 2 T + 1 begins and at most 2 B K entries are expected",
                  (long long)reduce_ints);
   }
-  const dim3 block(FG_THREADS);
-  const dim3 grid((unsigned)((int64_t)B * K * tiles));
+  const dim3 grid((unsigned)((int64_t)B * K * tiles)), block(FG_THREADS);
   if (!reduce_list) {       // in place: the targets no row names stay 0
     SININN_CHECK(hipMemsetAsync(dflows, 0, sizeof(float) * 4 * (size_t)T * (size_t)HW, st) == hipSuccess,
                  "flow_gather_bwd: hipMemsetAsync failed");
   }
-  float* rows = reduce_list ? workspace : nullptr;
-  float* direct = reduce_list ? nullptr : dflows;
-  if (C == 1)
-    hipLaunchKernelGGL((flowgather_bwd_kernel<1>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, grad_out, K, H, W,
-                       (int)tiles, rows, direct);
-  else
-    hipLaunchKernelGGL((flowgather_bwd_kernel<3>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, grad_out, K, H, W,
-                       (int)tiles, rows, direct);
+  gather_per_channels(C, [&](auto ch) {
+    hipLaunchKernelGGL((flowgather_bwd_kernel<decltype(ch)::value>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau,
+                       grad_out, K, H, W, (int)tiles, reduce_list ? workspace : nullptr, reduce_list ? nullptr : dflows);
+  });
   SININN_LAUNCH_CHECK("flowgather_bwd");
   if (reduce_list) {
     const dim3 rgrid((unsigned)((int64_t)T * 4 * tiles));
@@ -365,21 +378,16 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_points_kernel(const flo
   float w0[C], w1[C], h0[C], h1[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    w0[c] = gather_sample(i0b + c * HW, p.t0, W); w1[c] = gather_sample(i1b + c * HW, p.t1, W);
-    h0[c] = gather_sample(i0b + c * HW, p.th, W); h1[c] = gather_sample(i1b + c * HW, p.th, W);
+    w0[c] = gather_sample(gather_fetch(i0b + c * HW, p.t0, W), p.t0); w1[c] = gather_sample(gather_fetch(i1b + c * HW, p.t1, W), p.t1);
+    h0[c] = gather_sample(gather_fetch(i0b + c * HW, p.th, W), p.th); h1[c] = gather_sample(gather_fetch(i1b + c * HW, p.th, W), p.th);
   }
-  const float e = 0.0009765625f;
 #pragma unroll
   for (int r = 0; r < FGP_MAX_R; ++r) {
     if (r < R) {
       const float a1 = per_point ? p.tau : blend.a1[r], a0 = 1.f - a1;
-      const float den = (a0 * p.t0.n + a1 * p.t1.n) + e;
+      const float den = gather_den(a0, a1, p.t0.n, p.t1.n);
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        const float lin = a0 * h0[c] + a1 * h1[c];
-        const float num = (a0 * w0[c] + a1 * w1[c]) + e * lin;
-        out[(r * N + n) * C + c] = __fdiv_rn(num, den);
-      }
+      for (int c = 0; c < C; ++c) out[(r * N + n) * C + c] = gather_blend(a0, a1, den, w0[c], w1[c], h0[c], h1[c]);
     }
   }
 }
@@ -407,37 +415,32 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_points_bwd_kernel(const
     const float* i1b = i1 + (int64_t)b * C * HW;
     const GatherPoint p = gather_point(flows, pix, tau, rev, S, N, n, H, W);
     reversed = p.rev;
-    float n0x, n0y, n1x, n1y;
-    gather_slopes_ones(p.t0, n0x, n0y);
-    gather_slopes_ones(p.t1, n1x, n1y);
-    float w0[C], w1[C], h0[C], h1[C], w0x[C], w0y[C], w1x[C], w1y[C];
+    const float2 n0 = gather_slopes(gather_ones(p.t0), p.t0), n1 = gather_slopes(gather_ones(p.t1), p.t1);
+    float w0[C], w1[C], h0[C], h1[C];
+    float2 g0[C], g1[C];                    // the slopes of W0_c, W1_c
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      w0[c] = gather_sample(i0b + c * HW, p.t0, W); w1[c] = gather_sample(i1b + c * HW, p.t1, W);
-      h0[c] = gather_sample(i0b + c * HW, p.th, W); h1[c] = gather_sample(i1b + c * HW, p.th, W);
-      gather_slopes(i0b + c * HW, p.t0, W, w0x[c], w0y[c]);
-      gather_slopes(i1b + c * HW, p.t1, W, w1x[c], w1y[c]);
+      const GatherTapValues v0 = gather_fetch(i0b + c * HW, p.t0, W), v1 = gather_fetch(i1b + c * HW, p.t1, W);
+      w0[c] = gather_sample(v0, p.t0); w1[c] = gather_sample(v1, p.t1);
+      h0[c] = gather_sample(gather_fetch(i0b + c * HW, p.th, W), p.th); h1[c] = gather_sample(gather_fetch(i1b + c * HW, p.th, W), p.th);
+      g0[c] = gather_slopes(v0, p.t0); g1[c] = gather_slopes(v1, p.t1);
     }
-    const float e = 0.0009765625f;
 #pragma unroll
     for (int r = 0; r < FGP_MAX_R; ++r) {
       if (r < R) {
         const float a1 = per_point ? p.tau : blend.a1[r], a0 = 1.f - a1;
-        const float den = (a0 * p.t0.n + a1 * p.t1.n) + e;
-        float s0x = 0.f, s0y = 0.f, s1x = 0.f, s1y = 0.f;
+        const float den = gather_den(a0, a1, p.t0.n, p.t1.n);
+        float2 s0 = {0.f, 0.f}, s1 = {0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-          const float lin = a0 * h0[c] + a1 * h1[c];
-          const float num = (a0 * w0[c] + a1 * w1[c]) + e * lin;
-          const float v = __fdiv_rn(num, den);                  // out[r, n, c], the forward pass's bits
+          const float v = gather_blend(a0, a1, den, w0[c], w1[c], h0[c], h1[c]);         // out[r, n, c], the forward pass's bits
           const float g = gout[(r * N + n) * C + c];
-          s0x = s0x + g * (w0x[c] - v * n0x); s0y = s0y + g * (w0y[c] - v * n0y);
-          s1x = s1x + g * (w1x[c] - v * n1x); s1y = s1y + g * (w1y[c] - v * n1y);
+          gather_grad_add(g, v, g0[c], n0, s0);
+          gather_grad_add(g, v, g1[c], n1, s1);
         }
-        const float k0 = __fdiv_rn(p.c0 * a0, den), k1 = __fdiv_rn(p.c1 * a1, den);
-        const float v0x = k0 * s0x, v0y = k0 * s0y, v1x = k1 * s1x, v1y = k1 * s1y;
-        d0x = r == 0 ? v0x : d0x + v0x; d0y = r == 0 ? v0y : d0y + v0y;
-        d1x = r == 0 ? v1x : d1x + v1x; d1y = r == 0 ? v1y : d1y + v1y;
+        const float2 e0 = gather_grad_scale(p.c0, a0, den, s0), e1 = gather_grad_scale(p.c1, a1, den, s1);
+        d0x = r == 0 ? e0.x : d0x + e0.x; d0y = r == 0 ? e0.y : d0y + e0.y;
+        d1x = r == 0 ? e1.x : d1x + e1.x; d1y = r == 0 ? e1.y : d1y + e1.y;
       }
     }
   }
@@ -480,14 +483,12 @@ int flow_gather_at_launch(const float* i0, const float* i1, const float* flows, 
                           hipStream_t st) {
   if (flow_gather_at_check("flow_gather_at", i0, i1, flows, pix, pair, tau, blend, R, S, N, B, C, H, W)) return 1;
   SININN_CHECK(out, "flow_gather_at: null pointer");
-  const dim3 grid((unsigned)((N + FG_THREADS - 1) / FG_THREADS)), block(FG_THREADS);
+  const dim3 grid((unsigned)gather_tiles(N)), block(FG_THREADS);
   const GatherBlend a1 = flow_gather_at_blend(blend, R);
-  if (C == 1)
-    hipLaunchKernelGGL((flowgather_points_kernel<1>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R, S, N,
-                       B, H, W, out);
-  else
-    hipLaunchKernelGGL((flowgather_points_kernel<3>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R, S, N,
-                       B, H, W, out);
+  gather_per_channels(C, [&](auto ch) {
+    hipLaunchKernelGGL((flowgather_points_kernel<decltype(ch)::value>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1,
+                       blend ? 0 : 1, R, S, N, B, H, W, out);
+  });
   SININN_LAUNCH_CHECK("flowgather_points");
   return 0;
 }
@@ -498,14 +499,12 @@ int flow_gather_at_bwd_launch(const float* i0, const float* i1, const float* flo
   if (flow_gather_at_check("flow_gather_at_bwd", i0, i1, flows, pix, pair, tau, blend, R, S, N, B, C, H, W)) return 1;
   SININN_CHECK(grad_out, "flow_gather_at_bwd: the gradient of the output is null");
   SININN_CHECK(dflows, "flow_gather_at_bwd: the gradient of the flows is null");
-  const dim3 grid((unsigned)((N + FG_THREADS - 1) / FG_THREADS)), block(FG_THREADS);
+  const dim3 grid((unsigned)gather_tiles(N)), block(FG_THREADS);
   const GatherBlend a1 = flow_gather_at_blend(blend, R);
-  if (C == 1)
-    hipLaunchKernelGGL((flowgather_points_bwd_kernel<1>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R,
-                       S, N, B, H, W, grad_out, dflows);
-  else
-    hipLaunchKernelGGL((flowgather_points_bwd_kernel<3>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1, blend ? 0 : 1, R,
-                       S, N, B, H, W, grad_out, dflows);
+  gather_per_channels(C, [&](auto ch) {
+    hipLaunchKernelGGL((flowgather_points_bwd_kernel<decltype(ch)::value>), grid, block, 0, st, i0, i1, flows, pix, pair, tau, rev, a1,
+                       blend ? 0 : 1, R, S, N, B, H, W, grad_out, dflows);
+  });
   SININN_LAUNCH_CHECK("flowgather_points_bwd");
   return 0;
 }

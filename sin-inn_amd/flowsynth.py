@@ -85,11 +85,24 @@ def _host_taus(taus):
     return values
 
 
+def _refuse_grad(who, tensors, flow_grad=False, hint=''):
+    """the refusal of inputs that require grad: every input of an inference operator, the frames under flow_grad=True"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        if flow_grad:
+            raise RuntimeError(f'flowsynth.{who}(.., flow_grad=True) has a gradient with respect to the flows only: detach the frames')
+        raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
+                           f'(or call it under torch.no_grad(){hint})')
+
+
+def _device_tau(taus, values, device):
+    """the validated times as an fp32 tensor on `device`: `taus` itself where it already is one"""
+    if torch.is_tensor(taus) and taus.is_cuda and taus.dtype == torch.float32:
+        return taus.detach().contiguous()
+    return torch.tensor(values, dtype=torch.float32, device=device)
+
+
 def _check_inputs(who, frame1, frame2, flow12, flow21):
-    for t in (frame1, frame2, flow12, flow21):
-        if t.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
-                               '(or call it under torch.no_grad())')
+    _refuse_grad(who, (frame1, frame2, flow12, flow21))
     b, c, h, w = frame1.shape
     assert frame2.shape == frame1.shape, f'flowsynth.{who}: the two frames differ in shape'
     assert tuple(flow12.shape) == (b, 2, h, w) and tuple(flow21.shape) == (b, 2, h, w), f'flowsynth.{who}: flows are (B, 2, H, W)'
@@ -123,10 +136,7 @@ def synthesize(frame1, frame2, flow12, flow21, taus, *, out=None, u8=False, work
     flow12, flow21 = _planes(_gpu32(flow12)), _planes(_gpu32(flow21))
     k = len(values)
     dev = frame1.device
-    if torch.is_tensor(taus) and taus.is_cuda and taus.dtype == torch.float32:
-        tau = taus.detach().contiguous()
-    else:
-        tau = torch.tensor(values, dtype=torch.float32, device=dev)
+    tau = _device_tau(taus, values, dev)
     need = workspace_floats(b, k, c, h, w)
     if workspace is None:
         workspace = torch.empty(need, device=dev, dtype=torch.float32)
@@ -267,12 +277,7 @@ def upload_slots(slots, device):
 
 
 def _gather_inputs(who, frame1, frame2, flows, flow_grad=False):
-    for t in (frame1, frame2) if flow_grad else (frame1, frame2, flows):
-        if t.requires_grad and torch.is_grad_enabled():
-            if flow_grad:
-                raise RuntimeError(f'flowsynth.{who}(.., flow_grad=True) has a gradient with respect to the flows only: detach the frames')
-            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
-                               '(or call it under torch.no_grad())')
+    _refuse_grad(who, (frame1, frame2) if flow_grad else (frame1, frame2, flows), flow_grad)
     b, c, h, w = frame1.shape
     assert frame2.shape == frame1.shape, f'flowsynth.{who}: the two frames differ in shape'
     if c not in (1, 3):
@@ -360,77 +365,80 @@ def gather(frame1, frame2, flows, slots, taus, *, out=None, u8=False, k_loop=Non
     if flow_grad and (u8 or out is not None):
         raise ValueError('flowsynth.gather: flow_grad=True with u8=True or out= is not supported (bytes carry no gradient, and autograd '
                          'owns the result)')
-    if flow_grad and flows.requires_grad and torch.is_grad_enabled():
-        values = _host_taus(taus)
-        k = len(values)
-        if isinstance(slots, DeviceSlots):
-            raise ValueError('flowsynth.gather: flow_grad=True takes the host table of gather_slots (the backward pass builds its '
-                             'reduce list from it)')
-        need = _host_slots('gather', slots, b, k)
-        if need > flows.shape[0]:
-            raise ValueError(f'flowsynth.gather: the slots name time slice {need - 1}, flows has {flows.shape[0]}')
-        _gpu32(flows)
-        if flows.stride()[1:] != (h * w, w, 1) and flows.numel() > 0:
-            raise ValueError('flowsynth.gather: the four channel planes of a time slice must be contiguous (any stride between slices)')
-        frame1, frame2 = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous()
-        if torch.is_tensor(taus) and taus.is_cuda and taus.dtype == torch.float32:
-            tau = taus.detach().contiguous()
-        else:
-            tau = torch.tensor(values, dtype=torch.float32, device=frame1.device)
-        host = slots.contiguous().clone()
-        return _GatherFlowGrad.apply(flows, frame1, frame2, host, host.to(frame1.device), tau, values, k_loop)
+    grad = flow_grad and flows.requires_grad and torch.is_grad_enabled()
     values = _host_taus(taus)
     k = len(values)
-    frame1, frame2, flows = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous(), _gpu32(flows)
+    if grad and isinstance(slots, DeviceSlots):
+        raise ValueError('flowsynth.gather: flow_grad=True takes the host table of gather_slots (the backward pass builds its '
+                         'reduce list from it)')
+    frame1, frame2, data = _gpu32(frame1).contiguous(), _gpu32(frame2).contiguous(), _gpu32(flows)
     dev = frame1.device
     if not isinstance(slots, DeviceSlots):
-        need = _host_slots('gather', slots, b, k)
-        slots = DeviceSlots(slots.contiguous().to(dev), need)
+        need, host = _host_slots('gather', slots, b, k), slots
+        slots = DeviceSlots(host.contiguous().to(dev), need)
     table, need = slots
     if not (table.is_cuda and table.dtype == torch.int32 and tuple(table.shape) == (b, k, SLOT_INTS) and table.is_contiguous()):
         raise ValueError(f'flowsynth.gather: the uploaded table is not ({b}, {k}, {SLOT_INTS}) int32 on the device')
-    if need > flows.shape[0]:
-        raise ValueError(f'flowsynth.gather: the slots name time slice {need - 1}, flows has {flows.shape[0]}')
-    if flows.stride()[1:] != (h * w, w, 1) and flows.numel() > 0:
+    if need > data.shape[0]:
+        raise ValueError(f'flowsynth.gather: the slots name time slice {need - 1}, flows has {data.shape[0]}')
+    if data.stride()[1:] != (h * w, w, 1) and data.numel() > 0:
         raise ValueError('flowsynth.gather: the four channel planes of a time slice must be contiguous (any stride between slices)')
-    stride = flows.stride(0) if flows.shape[0] > 1 else 4 * h * w
-    if torch.is_tensor(taus) and taus.is_cuda and taus.dtype == torch.float32:
-        tau = taus.detach().contiguous()
-    else:
-        tau = torch.tensor(values, dtype=torch.float32, device=dev)
+    tau = _device_tau(taus, values, dev)
+    if grad:
+        return _GatherFlowGrad.apply(flows, frame1, frame2, host.contiguous().clone(), table, tau, values, k_loop)
+    stride = data.stride(0) if data.shape[0] > 1 else 4 * h * w
     if out is None:
         out = torch.empty((b, k, c, h, w), device=dev, dtype=torch.float32)
     assert tuple(out.shape) == (b, k, c, h, w) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
     bytes_ = torch.empty((b, k, c, h, w), device=dev, dtype=torch.uint8) if u8 else None
-    check(_lib.lib().sininn_flow_gather(ptr(frame1), ptr(frame2), ptr(flows), stride, C.c_void_p(table.data_ptr()), ptr(tau), b, k, c,
+    check(_lib.lib().sininn_flow_gather(ptr(frame1), ptr(frame2), ptr(data), stride, C.c_void_p(table.data_ptr()), ptr(tau), b, k, c,
                                         h, w, int(K_LOOP if k_loop is None else k_loop), ptr(out),
                                         C.c_void_p(bytes_.data_ptr()) if u8 else None, _stream()))
     return (out, bytes_) if u8 else out
 
 
-def bilinear_gather(img, qx, qy):
-    """sample(I, q) of the definition with torch ops: img (B, C, H, W), qx, qy (B, K, H, W) -> (W (B, K, C, H, W), n (B, K, H, W)).
-    Pixel centres at integers; a tap outside the frame adds 0 to both; a coordinate that is not finite, or 1e9 or more in size, has no
-    tap inside.  The four products are summed in the kernel's order."""
-    b, c, h, w = img.shape
-    k = qx.shape[1]
+def _tap_walk(qx, qy, h, w, term):
+    """The four taps of sample(I, q) for coordinates of any one shape: `term(weight, at)` is weight times the image at the flat offsets
+    `at` = y W + x, with the channel axis where the caller keeps it.  Pixel centres at integers; a tap outside the frame adds 0 to W
+    and to n; a coordinate that is not finite, or 1e9 or more in size, has no tap inside.  The four products are summed in the
+    kernel's order.  Returns (W, n)."""
     ok = (qx.abs() < 1e9) & (qy.abs() < 1e9)
     qx, qy = torch.where(ok, qx, torch.zeros_like(qx)), torch.where(ok, qy, torch.zeros_like(qy))
     fx, fy = qx.floor(), qy.floor()
     x0, y0 = fx.long(), fy.long()
     wx1, wy1 = qx - fx, qy - fy
     wx0, wy0 = 1 - wx1, 1 - wy1
-    flat = img.reshape(b, 1, c, h * w).expand(b, k, c, h * w)
     total, n = None, None
     for dy, dx, wy, wx in ((0, 0, wy0, wx0), (0, 1, wy0, wx1), (1, 0, wy1, wx0), (1, 1, wy1, wx1)):
         yy, xx = y0 + dy, x0 + dx
         inside = ok & (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
         weight = torch.where(inside, wy * wx, torch.zeros_like(wx))
-        at = (yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1)).reshape(b, k, 1, h * w).expand(b, k, c, h * w)
-        term = weight[:, :, None] * flat.gather(3, at).reshape(b, k, c, h, w)
-        total = term if total is None else total + term
+        value = term(weight, yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1))
+        total = value if total is None else total + value
         n = weight if n is None else n + weight
     return total, n
+
+
+def bilinear_gather(img, qx, qy):
+    """sample(I, q) of the definition with torch ops: img (B, C, H, W), qx, qy (B, K, H, W) -> (W (B, K, C, H, W), n (B, K, H, W)),
+    by `_tap_walk`'s rule and order of summation."""
+    b, c, h, w = img.shape
+    k = qx.shape[1]
+    flat = img.reshape(b, 1, c, h * w).expand(b, k, c, h * w)
+
+    def term(weight, at):
+        return weight[:, :, None] * flat.gather(3, at.reshape(b, k, 1, h * w).expand(b, k, c, h * w)).reshape(b, k, c, h, w)
+
+    return _tap_walk(qx, qy, h, w, term)
+
+
+def _blend(a0, a1, w0, w1, n0, n1, h0, h1, eps, axis):
+    """out = (a0 W0 + a1 W1 + eps (a0 h0 + a1 h1)) / (a0 n0 + a1 n1 + eps): W and h carry the channels at `axis`, a and n have no such
+    axis"""
+    c0, c1 = a0.unsqueeze(axis), a1.unsqueeze(axis)
+    num = (c0 * w0 + c1 * w1) + eps * (c0 * h0 + c1 * h1)
+    den = (a0 * n0 + a1 * n1) + eps
+    return num / den.unsqueeze(axis)
 
 
 def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, eps=GATHER_EPS):
@@ -441,8 +449,7 @@ def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, ep
     flows = flows.to(device=dev, dtype=dt)
     idx = slots[..., :4].to(dev, torch.long)
     coef = slot_coefficients(slots).to(dev, dt)
-    a1 = torch.tensor(values, dtype=torch.float32).to(dev, dt).view(1, -1, 1, 1, 1)
-    a0 = 1 - a1
+    a1 = torch.tensor(values, dtype=torch.float32).to(dev, dt).view(1, -1, 1, 1)
     ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=dt), torch.arange(w, device=dev, dtype=dt), indexing='ij')
     pair = torch.arange(2, device=dev)
 
@@ -452,10 +459,7 @@ def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, ep
         return sample(img, xs + cf * g[:, :, 0], ys + cf * g[:, :, 1])
 
     (w0, n0), (w1, n1) = warped(frame1, 0), warped(frame2, 1)
-    lin = a0 * frame1[:, None] + a1 * frame2[:, None]
-    num = (a0 * w0 + a1 * w1) + eps * lin
-    den = (a0[:, :, 0] * n0 + a1[:, :, 0] * n1) + eps
-    return num / den[:, :, None]
+    return _blend(1 - a1, a1, w0, w1, n0, n1, frame1[:, None], frame2[:, None], eps, 2)
 
 
 def gather_composed(frame1, frame2, flows, slots, taus, *, flow_grad=False):
@@ -482,12 +486,8 @@ MAX_BLENDS = 4          # FGP_MAX_R of csrc/flowgather.hip
 def _gather_at_inputs(who, frame1, frame2, flows, pix, pair, tau, rev, blend, flow_grad):
     """shapes and dtypes of the point form, checked on the host (the VALUES of the device tensors cannot be, and need not: the
     operator is safe for any); returns (b, c, h, w, s, n, blend as a list of fp32 values or None)"""
-    for t in (frame1, frame2) if flow_grad else (frame1, frame2, flows):
-        if t.requires_grad and torch.is_grad_enabled():
-            if flow_grad:
-                raise RuntimeError(f'flowsynth.{who}(.., flow_grad=True) has a gradient with respect to the flows only: detach the frames')
-            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
-                               '(or call it under torch.no_grad(), or pass flow_grad=True for the gradient to the flows)')
+    _refuse_grad(who, (frame1, frame2) if flow_grad else (frame1, frame2, flows), flow_grad,
+                 ', or pass flow_grad=True for the gradient to the flows')
     for name, t in (('pix', pix), ('tau', tau)):
         if t.requires_grad and torch.is_grad_enabled():
             raise RuntimeError(f'flowsynth.{who} has no gradient with respect to {name}: detach it')
@@ -588,22 +588,8 @@ def bilinear_gather_at(img, pair, qx, qy):
     """sample(I[pair], q) with torch ops at a list: img (B, C, H, W), pair (N,) long inside [0, B), qx, qy (N,) -> (W (N, C), n (N,)).
     `bilinear_gather`'s rule and order of summation."""
     b, c, h, w = img.shape
-    ok = (qx.abs() < 1e9) & (qy.abs() < 1e9)
-    qx, qy = torch.where(ok, qx, torch.zeros_like(qx)), torch.where(ok, qy, torch.zeros_like(qy))
-    fx, fy = qx.floor(), qy.floor()
-    x0, y0 = fx.long(), fy.long()
-    wx1, wy1 = qx - fx, qy - fy
-    wx0, wy0 = 1 - wx1, 1 - wy1
     flat = img.reshape(b, c, h * w)
-    total, n = None, None
-    for dy, dx, wy, wx in ((0, 0, wy0, wx0), (0, 1, wy0, wx1), (1, 0, wy1, wx0), (1, 1, wy1, wx1)):
-        yy, xx = y0 + dy, x0 + dx
-        inside = ok & (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
-        weight = torch.where(inside, wy * wx, torch.zeros_like(wx))
-        term = weight[:, None] * flat[pair, :, yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1)]
-        total = term if total is None else total + term
-        n = weight if n is None else n + weight
-    return total, n
+    return _tap_walk(qx, qy, h, w, lambda weight, at: weight[:, None] * flat[pair, :, at])
 
 
 def gather_at_from(frame1, frame2, flows, pix, pair, tau, rev, blend, sample=bilinear_gather_at, eps=GATHER_EPS):
@@ -629,10 +615,8 @@ def gather_at_from(frame1, frame2, flows, pix, pair, tau, rev, blend, sample=bil
     h0, h1 = sample(frame1, at, px, py)[0], sample(frame2, at, px, py)[0]
     rows = []
     for a1 in ([tau] if blend is None else [torch.full_like(tau, v) for v in blend]):
-        a0 = 1 - a1
-        num = (a0[:, None] * w0 + a1[:, None] * w1) + eps * (a0[:, None] * h0 + a1[:, None] * h1)
-        den = (a0 * n0 + a1 * n1) + eps
-        rows.append(torch.where(inside[:, None], num / den[:, None], torch.zeros_like(num)))
+        value = _blend(1 - a1, a1, w0, w1, n0, n1, h0, h1, eps, 1)
+        rows.append(torch.where(inside[:, None], value, torch.zeros_like(value)))
     return torch.stack(rows)
 
 
@@ -671,10 +655,7 @@ def quality_workspace_floats(b, c, h, w):
 
 
 def _quality_inputs(who, pred, target):
-    for t in (pred, target):
-        if t.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError(f'flowsynth.{who} is an inference operator and has no gradient: detach its inputs '
-                               '(or call it under torch.no_grad())')
+    _refuse_grad(who, (pred, target))
     assert pred.shape == target.shape, f'flowsynth.{who}: pred and target differ in shape'
     assert pred.dim() in (4, 5), f'flowsynth.{who}: frames are (B, C, H, W) or (B, K, C, H, W)'
     lead = tuple(pred.shape[:-3])
