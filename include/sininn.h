@@ -837,6 +837,34 @@ int sininn_flownet_forward(const sininn_flownet_args* args, const sininn_flownet
 int sininn_flownet_backward(const sininn_flownet_args* args, const sininn_flownet_call* call, void* stream);
 int sininn_flownet_sample_mask(const sininn_flownet_args* args, const sininn_flownet_call* call, float* out, void* stream);
 
+/* The Jacobian of the network as an output with a gradient to the parameters (csrc/flownet_jacobian.h).  Plain arguments beside
+ * the two descriptors, which keep their size, every meaning and every refusal; no mode bit is added.  dirs: the direction set D, bit 0 t,
+ * bit 1 y, bit 2 x; slots of jac / djac / tsaved follow the set bits in that order.  With g_l = [h_l > 0], the gates of the value pass:
+ *     t_1 = g_1 . (W1' dE_d(p) [+ wc[:, d]])   t_2 = g_2 . (W2 t_1)   t_3 = g_3 . (W3 t_2)   jac[slot][c][p] = scale * (W4 t_3)[c]
+ *   W1' is the layer-1 matrix the forward pass multiplies (progressive: the mask-folded pack, wc its coordinate columns), dE_d the POSEGRAD
+ *   derivative of the encoding above (RBF, Fourier); no bias enters a tangent.  jac is DEVICE planar [|D|][4][n], flow units per unit of
+ *   the normalised coordinate.
+ * sininn_flownet_jacobian_forward: does everything sininn_flownet_forward does with the same (args, call) in its training mode (flows and
+ *   `saved` are bitwise that call's; args->saved must not be NULL; progressive: args->workspace as there), then writes jac and the gated
+ *   tangents tsaved [|D|][3][Npad][256] (sininn_flownet_jacobian_saved_bytes(n, |D|) bytes, 16-byte aligned).
+ * sininn_flownet_jacobian_backward: does everything sininn_flownet_backward does with the same (args, call) for args->dflows (gw / gb are
+ *   bitwise that call's when djac is all zero), then adds to gw[0..3], for every d in D in the order t, y, x, the gradient of
+ *   sum(djac_d * jac_d):  dt_3 = g_3 . (W4^T scale djac_d), dt_2 = g_2 . (W3^T dt_3), dt_1 = g_1 . (W2^T dt_2);
+ *   gw[3] += (scale djac_d)^T t_3, gw[2] += dt_3^T t_2, gw[1] += dt_2^T t_1, gw[0][:, enc k] += mask_k sum_p dt_1[p] dE_d,k(p),
+ *   gw[0][:, coord d] += mask_d sum_p dt_1[p].  The gates carry no gradient, the biases get none from a tangent, the poses and the
+ *   encoding's buffers get none.  djac DEVICE [|D|][4][n]; tsaved: the forward call's; jac_workspace:
+ *   sininn_flownet_jacobian_workspace_bytes(args, n, |D|) bytes, 16-byte aligned.  Every sum has a fixed order (partial sums in the
+ *   workspace, reduced in index order, then value + t + y + x), no atomics: two calls are bitwise equal, any valid k_active gives the same bits.
+ * Refused, each before any launch, in one sentence under flownet_jacobian_forward / flownet_jacobian_backward: dirs of 0 or above 7; a NULL
+ *   call descriptor or one without AT_POINTS; SPATIAL, ENCGRAD, POSEGRAD; domain_dim != 3; an encoding other than SININN_FLOWNET_RBF /
+ *   SININN_FLOWNET_FOURIER; NULL jac / djac / tsaved / jac_workspace / saved; short or misaligned buffers; and whatever the plain call refuses. */
+size_t sininn_flownet_jacobian_saved_bytes(int64_t n_points, int n_dirs);
+size_t sininn_flownet_jacobian_workspace_bytes(const sininn_flownet_args* args, int64_t n_points, int n_dirs);
+int sininn_flownet_jacobian_forward(const sininn_flownet_args* args, const sininn_flownet_call* call, unsigned dirs, float* jac, float* tsaved,
+                                    size_t tsaved_bytes, void* stream);
+int sininn_flownet_jacobian_backward(const sininn_flownet_args* args, const sininn_flownet_call* call, unsigned dirs, const float* djac,
+                                     const float* tsaved, size_t tsaved_bytes, void* jac_workspace, size_t jac_workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * The SIREN flow network of the flow trainer: sine MLP on the raw coordinates, forward and backward (csrc/siren.hip).
  *   video-interpolation/model.py:123-146 SineLayer (sin(omega_0 * linear(x)), omega_0 = 30), model.py:149-171 SirenModel with the

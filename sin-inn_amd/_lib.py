@@ -303,6 +303,11 @@ _SIGS = {
     'sininn_flownet_sample_mask': (C.c_int, [C.POINTER(FlowNetArgs), C.POINTER(FlowNetCall), c_f, C.c_void_p]),
     'sininn_flownet_encgrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs)]),
     'sininn_flownet_posegrad_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs), C.c_int]),
+    'sininn_flownet_jacobian_saved_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'sininn_flownet_jacobian_workspace_bytes': (C.c_size_t, [C.POINTER(FlowNetArgs), C.c_int64, C.c_int]),
+    'sininn_flownet_jacobian_forward': (C.c_int, [C.POINTER(FlowNetArgs), C.POINTER(FlowNetCall), C.c_uint, c_f, c_f, C.c_size_t, C.c_void_p]),
+    'sininn_flownet_jacobian_backward': (C.c_int, [C.POINTER(FlowNetArgs), C.POINTER(FlowNetCall), C.c_uint, c_f, c_f, C.c_size_t, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p]),
     'sininn_siren_supported': (C.c_int, [C.POINTER(SirenArgs)]),
     'sininn_siren_saved_bytes': (C.c_size_t, [C.c_int64]),
     'sininn_siren_workspace_bytes': (C.c_size_t, [C.c_int64]),

@@ -128,6 +128,12 @@ int flownet_backward_launch(const sininn_flownet_args* a, const sininn_flownet_c
 int flownet_sample_mask_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, float* out, hipStream_t st);
 size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a);
 size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad);
+size_t flownet_jacobian_saved_bytes(int64_t n, int n_dirs);
+size_t flownet_jacobian_workspace_bytes(const sininn_flownet_args* a, int64_t n, int n_dirs);
+int flownet_jacobian_forward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, unsigned dirs, float* jac, float* tsaved,
+                                    size_t tsaved_bytes, hipStream_t st);
+int flownet_jacobian_backward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, unsigned dirs, const float* djac,
+                                     const float* tsaved, size_t tsaved_bytes, void* jac_workspace, size_t jac_workspace_bytes, hipStream_t st);
 int siren_supported(const sininn_siren_args* a, const char* who);
 size_t siren_saved_bytes(int64_t n);
 size_t siren_workspace_bytes(int64_t n);
@@ -623,6 +629,18 @@ int sininn_flownet_sample_mask(const sininn_flownet_args* args, const sininn_flo
 size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* args) { return flownet_encgrad_workspace_bytes(args); }
 size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* args, int with_enc_grad) {
   return flownet_posegrad_workspace_bytes(args, with_enc_grad);
+}
+size_t sininn_flownet_jacobian_saved_bytes(int64_t n_points, int n_dirs) { return flownet_jacobian_saved_bytes(n_points, n_dirs); }
+size_t sininn_flownet_jacobian_workspace_bytes(const sininn_flownet_args* args, int64_t n_points, int n_dirs) {
+  return flownet_jacobian_workspace_bytes(args, n_points, n_dirs);
+}
+int sininn_flownet_jacobian_forward(const sininn_flownet_args* args, const sininn_flownet_call* call, unsigned dirs, float* jac, float* tsaved,
+                                    size_t tsaved_bytes, void* stream) {
+  return flownet_jacobian_forward_launch(args, call, dirs, jac, tsaved, tsaved_bytes, ST(stream));
+}
+int sininn_flownet_jacobian_backward(const sininn_flownet_args* args, const sininn_flownet_call* call, unsigned dirs, const float* djac,
+                                     const float* tsaved, size_t tsaved_bytes, void* jac_workspace, size_t jac_workspace_bytes, void* stream) {
+  return flownet_jacobian_backward_launch(args, call, dirs, djac, tsaved, tsaved_bytes, jac_workspace, jac_workspace_bytes, ST(stream));
 }
 int sininn_siren_supported(const sininn_siren_args* args) { return siren_supported(args, "sininn_siren_supported"); }
 size_t sininn_siren_saved_bytes(int64_t n_points) { return siren_saved_bytes(n_points); }

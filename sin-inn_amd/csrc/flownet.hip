@@ -1750,4 +1750,6 @@ int flownet_backward_launch(const sininn_flownet_args* a, const sininn_flownet_c
   return backward_launch(a, c, nullptr, st);
 }
 
+#include "flownet_jacobian.h"   // the Jacobian as an output: new kernels beside the ones above, which it launches and does not change
+
 }  // namespace sininn

@@ -387,8 +387,9 @@ class _EncodedMlpModel(nn.Module):
         return [m for m in self.model.model if isinstance(m, nn.Linear)]
 
     def forward(self, x, *args, **kwargs):
-        """net(poses), model.py:97-103: (..., 3) -> (..., 4) in the fused kernels (`flow_at`)"""
-        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False))
+        """net(poses), model.py:97-103: (..., 3) -> (..., 4) in the fused kernels (`flow_at`); `jacobian=` is flow_at's"""
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False),
+                       jacobian=kwargs.get('jacobian'))
 
 
 class ProgressiveModel(_EncodedMlpModel):
@@ -505,8 +506,9 @@ class SirenModel(nn.Module):
         return [m.linear if isinstance(m, SineLayer) else m for m in self.model]
 
     def forward(self, x, *args, **kwargs):
-        """net(poses), model.py:167-171: (..., 3) -> (..., 4) in the fused kernels (`flow_at`)"""
-        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False))
+        """net(poses), model.py:167-171: (..., 3) -> (..., 4) in the fused kernels (`flow_at`); `jacobian=` is flow_at's (and refused)"""
+        return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), pose_grad=kwargs.get('pose_grad', False),
+                       jacobian=kwargs.get('jacobian'))
 
 
 # the piecewise-linear progressive network (model.py:600-604): beside all_model_dict, like siren; the reference's model_dict lacks it too
@@ -737,8 +739,8 @@ def _forward(a, train, saved, saved_shape, stem, c):
     return (flows.view(4, -1) if a._poses is not None else flows), saved
 
 
-def _backward(a, net, dflows, saved, workspace, stem, c):
-    """the backward half: check dflows (at a pose list: (4, N)), allocate the workspace (sininn_<stem>_workspace_bytes(N)) and the gradients
+def _backward(a, net, dflows, saved, workspace, stem, c, entry=None):
+    """the backward half (`entry(a, c)`: the library call to make instead of sininn_<stem>_backward, on the same descriptors): check dflows (at a pose list: (4, N)), allocate the workspace (sininn_<stem>_workspace_bytes(N)) and the gradients
     into the descriptor, call.  [gW1, gb1, ..]; with the frequency gradient (grads, gF); with the pose gradient (either of those, g_poses)"""
     lib = _lib.lib()
     _on_gpu(dflows)
@@ -754,7 +756,10 @@ def _backward(a, net, dflows, saved, workspace, stem, c):
         gw, gb = torch.empty_like(lin.weight), torch.empty_like(lin.bias)
         a.gw[l], a.gb[l] = ptr(gw), ptr(gb)
         grads += [gw, gb]
-    check(getattr(lib, f'sininn_{stem}_backward')(C.byref(a), C.byref(c), _stream()))   # dflows, workspace: alive until the call is made
+    if entry is not None:
+        check(entry(a, c))
+    else:
+        check(getattr(lib, f'sininn_{stem}_backward')(C.byref(a), C.byref(c), _stream()))   # dflows, workspace: alive until the call is made
     out = grads if c._g_enc is None else (grads, c._g_enc)
     return out if c._g_poses is None else (out, c._g_poses)
 
@@ -969,6 +974,166 @@ class _FlowAt(torch.autograd.Function):
         return (None, g_poses, None, None, None, g_enc, None) + grads
 
 
+# ---- the Jacobian as an output: d flow / d (t, y, x) at a pose list, with a gradient to the parameters (csrc/flownet_jacobian.h) ----
+JACOBIAN_AXES = 'tyx'
+
+
+def jacobian_dirs(jacobian):
+    """the direction set of a `jacobian=` keyword as indices into (t, y, x), ascending: a string of distinct letters from 'tyx', True: 'yx'"""
+    if jacobian is True:
+        jacobian = 'yx'
+    if not isinstance(jacobian, str) or not jacobian or len(set(jacobian)) != len(jacobian) or any(ch not in JACOBIAN_AXES for ch in jacobian):
+        raise ValueError(f'jacobian: a non-empty string of distinct letters from {JACOBIAN_AXES!r} (True: \'yx\'); got {jacobian!r}')
+    return tuple(d for d, ch in enumerate(JACOBIAN_AXES) if ch in jacobian)
+
+
+def _refuse_jacobian(net, override_mask=None, pose_grad=False, poses=None, what='flow_at(.., jacobian=)'):
+    """what the Jacobian kernels do not do, each refusal a ValueError that names what is missing; `net`: a model or a controller.  Needs no
+    device"""
+    from .progressive import ProgressiveEncoderController, StashedSpatialController
+    model = net.model if isinstance(net, ProgressiveEncoderController) else net
+    if isinstance(model, SirenModel):
+        raise ValueError(f'{what}: SIREN is out of scope: the tangent of a sine layer is no gated copy of the network (no kernel evaluates it)')
+    enc = model.encode
+    if isinstance(enc, RotatedFourierFeatures):
+        raise ValueError(f'{what}: RFF / PRFF are out of scope: learnable frequencies would need the second derivative of the encoding')
+    if enc.kind == RBFG:
+        raise ValueError(f'{what}: RBFG / PRBFG are out of scope: no tangent kernel exists for the radial-basis grid')
+    if enc.kind == PE:
+        raise ValueError(f'{what}: PE / PPE are out of scope: no tangent kernel exists for the narrow positional layer 1')
+    if enc.kind == PIECEWISE:
+        raise ValueError(f'{what}: MPFF is out of scope: no tangent kernel exists for the piecewise-linear encoding')
+    if model.domain_dim != 3:
+        raise ValueError(f'{what}: domain_dim {model.domain_dim} is out of scope: the Jacobian kernels take three coordinates (t, y, x)')
+    if isinstance(net, StashedSpatialController) or (override_mask is not None and override_mask.dim() == 2):
+        raise ValueError(f'{what}: per-point (spatial) masks are out of scope: the tangent passes read the mask-folded layer 1 of a global mask')
+    if pose_grad:
+        raise ValueError(f'{what}: pose_grad=True cannot be combined with the Jacobian: there is no gradient to the poses through it')
+    if poses is not None and poses.requires_grad:
+        raise ValueError(f'{what}: poses that require a gradient: there is no gradient to the poses through the Jacobian (poses.detach())')
+    assert enc.kind in (RBF, FOURIER)
+
+
+def _dirs_bits(dirs):
+    return sum(1 << d for d in dirs)
+
+
+def flownet_jacobian_forward_points(net, poses, scale, dirs, mask=None, k_active=None):
+    """(flows (4, N), jac (|D|, 4, N), saved, tsaved) at a pose list (N, 3): sininn_flownet_jacobian_forward.  `dirs`: ascending indices into
+    (t, y, x).  flows and `saved` are bitwise those of flownet_forward_points(.., train=True); jac[i] = scale d out / d x_dirs[i]; tsaved
+    (|D|, 3, Npad, 256) holds the gated tangents for the backward call"""
+    a = _pack_workspace(_args(net, poses, None, None, scale, mask, k_active))
+    c = _call(a)
+    lib, n, nd = _lib.lib(), a.W, len(dirs)
+    flows = torch.empty(1, 4, 1, n, device=a._device, dtype=torch.float32)
+    saved = torch.empty(_flownet_saved_shape(a)(), device=a._device, dtype=torch.float32)
+    jac = torch.empty(nd, 4, n, device=a._device, dtype=torch.float32)
+    tsaved = torch.empty((nd,) + tuple(saved.shape), device=a._device, dtype=torch.float32)
+    a.flows, a.saved, a.saved_bytes = ptr(flows), ptr(saved), saved.numel() * 4
+    check(lib.sininn_flownet_jacobian_forward(C.byref(a), C.byref(c), _dirs_bits(dirs), ptr(jac), ptr(tsaved), tsaved.numel() * 4, _stream()))
+    return flows.view(4, -1), jac, saved, tsaved
+
+
+def flownet_jacobian_backward_points(net, poses, scale, dirs, dflows, djac, saved, tsaved, workspace=None, jac_workspace=None, mask=None,
+                                     k_active=None):
+    """[gW1, gb1, .., gW4, gb4] of sum(dflows * flows) + sum(djac * jac): sininn_flownet_jacobian_backward.  dflows (4, N), djac (|D|, 4, N);
+    with djac all zero the gradients are bitwise flownet_backward_points'.  `jac_workspace`: optional fp32 tensor of
+    sininn_flownet_jacobian_workspace_bytes bytes"""
+    a = _args(net, poses, None, None, scale, mask, k_active)
+    lib, n, nd = _lib.lib(), a.W, len(dirs)
+    _on_gpu(djac)
+    djac = djac.contiguous()
+    assert tuple(djac.shape) == (nd, 4, n) and djac.dtype == torch.float32
+    if jac_workspace is None:
+        jac_workspace = torch.empty(lib.sininn_flownet_jacobian_workspace_bytes(C.byref(a), n, nd) // 4, device=a._device, dtype=torch.float32)
+
+    def entry(a, c):
+        return lib.sininn_flownet_jacobian_backward(C.byref(a), C.byref(c), _dirs_bits(dirs), ptr(djac), ptr(tsaved), tsaved.numel() * 4,
+                                                    ptr(jac_workspace), jac_workspace.numel() * 4, _stream())
+    return _backward(a, net, dflows, saved, workspace, 'flownet', _call(a), entry)
+
+
+class _FlowJacobianAt(torch.autograd.Function):
+    """(flows (4, N), jac (|D|, 4, N)) of one call; both carry a gradient to the parameters.  Once differentiable; an upstream of None for
+    either output is a zero"""
+
+    @staticmethod
+    def forward(ctx, net, poses, scale, train, mask, dirs, *params):
+        kw = dict(mask=mask.tensor, k_active=mask.k_active)
+        flows, jac, saved, tsaved = flownet_jacobian_forward_points(net, poses, scale, dirs, **kw)
+        ctx.net, ctx.poses, ctx.scale, ctx.dirs, ctx.kw = net, poses, scale, dirs, kw
+        ctx.saved, ctx.tsaved = (saved, tsaved) if train else (None, None)
+        return flows, jac
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dflows, djac):
+        if ctx.saved is None:
+            raise RuntimeError('flow_at(.., jacobian=): backward through an inference-mode forward')
+        if dflows is None:
+            dflows = torch.zeros(4, ctx.poses.shape[0], device=ctx.poses.device)
+        if djac is None:                                 # the flows alone: the plain backward call
+            grads = flownet_backward_points(ctx.net, ctx.poses, ctx.scale, dflows, ctx.saved, **ctx.kw)
+        else:
+            grads = flownet_jacobian_backward_points(ctx.net, ctx.poses, ctx.scale, ctx.dirs, dflows, djac, ctx.saved, ctx.tsaved, **ctx.kw)
+        ctx.saved = ctx.tsaved = None
+        return (None,) * 6 + tuple(grads)
+
+
+def _encoding_with_tangents(enc, x, dirs):
+    """(E (N, 512), [dE_d (N, 512) for d in dirs]) of a RadialBasisEncoding / a fixed Fourier encoding in x's dtype, torch ops"""
+    if enc.kind == RBF:
+        centres, s2 = enc.centres.to(x), enc.sigma.to(x)[None, :] ** 2
+        diff = x[:, None, :] - centres[None, :, :]
+        e = torch.exp(-(diff.pow(2).sum(2) * s2))
+        return e, [(-2 * s2) * diff[:, :, d] * e for d in dirs]
+    freq = enc.frequencies.to(x)
+    phi = torch.matmul(x * 2 * math.pi, freq)
+    sn, co = torch.sin(phi), torch.cos(phi)
+    e = torch.stack((sn, co), dim=2).view(x.shape[0], -1)
+    return e, [torch.stack(((2 * math.pi * freq[d])[None, :] * co, (-2 * math.pi * freq[d])[None, :] * sn), dim=2).view(x.shape[0], -1)
+               for d in dirs]
+
+
+def flow_jacobian_composed(net, poses, scale=1.0, jacobian='yx', override_mask=None, planar=False, gates=None):
+    """(flow, jac) as flow_at(net, poses, scale, jacobian=..) returns them, from torch ops on any device in the dtype of `poses` (fp32 or
+    fp64): the value pass of the module, then one forward-mode tangent pass per direction under the value pass's own ReLU decisions,
+    no bias, the tangent of cat((t, y, x), enc) = (e_d, dE_d).  Differentiable with respect to the parameters by ordinary autograd (the gates
+    carry no gradient).  The baseline of the fused call and the CPU path.  `gates`: three bool (N, 256) tensors that replace the ReLU
+    decisions (the tests force the kernel's own)"""
+    dirs = jacobian_dirs(jacobian)
+    _refuse_jacobian(net, override_mask, what='flow_jacobian_composed')
+    if not torch.is_tensor(poses) or poses.dim() < 1 or poses.shape[-1] != 3 or poses.dtype not in (torch.float32, torch.float64):
+        raise ValueError('flow_jacobian_composed: poses of shape (..., 3), fp32 or fp64')
+    lead = poses.shape[:-1]
+    x = poses.detach().reshape(-1, 3)
+    from .progressive import ProgressiveEncoderController
+    model = net.model if isinstance(net, ProgressiveEncoderController) else net
+    e, de = _encoding_with_tangents(model.encode, x, dirs)
+    if model.is_progressive:
+        # the mask of the call, as _resolve_mask chooses it, read where it lives (a controller keeps its own on the host)
+        m = override_mask if override_mask is not None else net.mask if model is not net else torch.ones(model.encoding_dim)
+        m = m.detach().to(x)[None, :]
+        e = torch.cat((x, e), dim=1) * m
+        unit = torch.eye(3, dtype=x.dtype, device=x.device)
+        de = [torch.cat((unit[d][None, :].expand(x.shape[0], 3), t), dim=1) * m
+              for d, t in zip(dirs, de)]
+    lins = model.linears()
+    h, ts = e, de
+    for l in range(3):
+        w, b = lins[l].weight.to(x.dtype), lins[l].bias.to(x.dtype)
+        pre = nnf.linear(h, w, b)
+        g = ((pre > 0) if gates is None else gates[l]).to(x.dtype)
+        h = pre * g
+        ts = [nnf.linear(t, w) * g for t in ts]
+    w, b = lins[3].weight.to(x.dtype), lins[3].bias.to(x.dtype)
+    flow = nnf.linear(h, w, b) * scale
+    jac = torch.stack([nnf.linear(t, w) * scale for t in ts], dim=0)          # (|D|, N, 4)
+    if planar:
+        return flow.t().contiguous(), jac.permute(0, 2, 1).contiguous()
+    return flow.view(*lead, 4), jac.permute(1, 2, 0).contiguous().view(*lead, 4, len(dirs))
+
+
 def grid_axes(net, times, h, w):
     """linspace(-1, 1, h) / (w) as trainer.py:40-41 makes them: on the CPU, then moved next to `times` (bit-identical
     coordinates); cached per size and device."""
@@ -1063,7 +1228,7 @@ def flow_fields(net, times, h, w, scale, override_mask=None, get_mask=False):
     return flows[:, :2], flows[:, 2:]
 
 
-def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=False, pose_grad=False):
+def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=False, pose_grad=False, jacobian=None):
     """net(poses) * scale (trainer.py:43-44, progressive_controller.py:45-53) at arbitrary points: `poses` (..., 3) fp32 on the GPU,
     columns (t, y, x) -> (..., 4), contiguous.  `net`: what flow_fields takes, a model or a LinearController / LinearControllerEarly
     around a progressive one; `override_mask` (515 values, PPE: 27) replaces the controller's mask.  A StashedSpatialController, or a
@@ -1076,7 +1241,18 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     `pose_grad=True`: poses that require a gradient get one (d flow / d pose against the upstream gradient, `scale` included, computed
     by the fused kernels: the POSEGRAD mode of sininn_flownet_backward / sininn_siren_backward), which chains queries:
     flow_at(net, p + pad(flow_at(net, p, pose_grad=True)[..., :2]), pose_grad=True).  Once differentiable.  Without the keyword there is no
-    gradient with respect to the coordinates: poses that require one are refused."""
+    gradient with respect to the coordinates: poses that require one are refused.
+    `jacobian`: a string of distinct letters from 'tyx' (True: 'yx') returns (out, jac): jac (..., 4, |D|) (`planar=True`: (|D|, 4, N)), the
+    derivative of `out` along each named coordinate, always in the order t, y, x, in flow units (`scale` included) per unit of the normalised
+    coordinate.  `out` is bitwise the call's without the keyword, and BOTH carry a gradient to the parameters (one autograd function, the
+    tangent kernels of csrc/flownet_jacobian.h), so a loss on the derivative trains.  RBF, FFN, UFF and PRBF, PFF, PUFF under a global mask;
+    everything else, `pose_grad=True`, poses that require a gradient and `get_mask` with it are refused with a ValueError."""
+    dirs = None
+    if jacobian is not None and jacobian is not False:
+        dirs = jacobian_dirs(jacobian)
+        _refuse_jacobian(net, override_mask, pose_grad, poses if torch.is_tensor(poses) else None)
+        if get_mask:
+            raise ValueError('flow_at(.., jacobian=): get_mask cannot be combined with the Jacobian; ask for the mask in a call of its own')
     dim = _call_dim(net, override_mask, pose_grad)
     if not torch.is_tensor(poses) or poses.dim() < 1 or poses.shape[-1] != dim:
         raise ValueError(f'flow_at: domain_dim {dim}: poses of shape (..., {dim}), columns {"(t, y, x)" if dim == 3 else "(y, x)"}; got '
@@ -1103,6 +1279,11 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     enc_a = net.encode.effective_frequencies() if isinstance(getattr(net, 'encode', None), RotatedFourierFeatures) else None
     train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or (enc_a is not None and enc_a.requires_grad) or
                                          (pose_grad and poses.requires_grad))
+    if dirs is not None:
+        out, jac = _FlowJacobianAt.apply(net, flat, float(scale), train, mask, dirs, *params)
+        if planar:
+            return out, jac
+        return out.t().contiguous().view(*lead, 4), jac.permute(2, 1, 0).contiguous().view(*lead, 4, len(dirs))
     out = _FlowAt.apply(net, flat, float(scale), train, mask, enc_a, bool(pose_grad), *params)
     if not planar:
         out = out.t().contiguous().view(*lead, 4)

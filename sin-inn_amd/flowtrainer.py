@@ -271,6 +271,18 @@ class FlowTrainer(LightningModule):
                 self._between_gens = {}          # device -> torch.Generator, seeded once per trainer
                 self.between_sample = None       # test hook: (pix, pair, tau, rev) of the last between term
 
+        # the smoothness prior at sampled points: off unless the namespace carries a non-zero weight; the attributes exist only then
+        self.smooth_at_weight = float(getattr(args, 'loss_smooth_at', 0) or 0)
+        if self.smooth_at_weight != 0:
+            flownet._refuse_jacobian(self.net, what='--loss-smooth-at')
+            self.loss_smooth_at = self.smooth_at_weight
+            self.smooth_points = int(getattr(args, 'smooth_points', None) or 4096)
+            if not 1 <= self.smooth_points <= GRID_POINTS:
+                raise ValueError(f'--smooth-points {self.smooth_points}: 1 to {GRID_POINTS} points a step (one flow_at call)')
+            self.smooth_seed = int(getattr(args, 'smooth_seed', 0))
+            self._smooth_gens = {}               # device -> torch.Generator of its own: the --between-points draw is unchanged
+            self.smooth_sample = None            # test hook: (pair, py, px, poses) of the last term
+
     # ---- the pieces of the step ----
 
     def _scale(self, scale, frame):
@@ -417,6 +429,64 @@ class FlowTrainer(LightningModule):
         self.between_flows, self.between_frames, self.between_sample = flows, out, (pix, pair, tau, rev)
         return self.between_weight * (out[0] - out[1]).abs().mean()
 
+    def smooth_points_table(self, times, b, h, w):
+        """(pair (N,) int64, py (N,), px (N,), poses (N, 3)) of one step: pair ~ U{0 .. B-1}, py ~ U[0, H-1], px ~ U[0, W-1] from a device
+        generator seeded once per trainer (`smooth_seed`); nothing is read back"""
+        dev, n = times.device, self.smooth_points
+        if dev not in self._smooth_gens:
+            self._smooth_gens[dev] = torch.Generator(device=dev).manual_seed(self.smooth_seed)
+        gen = self._smooth_gens[dev]
+        pair = torch.randint(0, b, (n,), generator=gen, device=dev)
+        u = torch.rand(2, n, generator=gen, device=dev, dtype=torch.float32)
+        py, px = u[0] * (h - 1), u[1] * (w - 1)
+        t = times.detach().to(torch.float32).reshape(-1)[pair]
+        poses = torch.stack((t, 2 * py / max(h - 1, 1) - 1, 2 * px / max(w - 1, 1) - 1), dim=1)
+        return pair, py, px, poses
+
+    @staticmethod
+    def _sample_clamped(img, pair, py, px):
+        """img (B, C, H, W) at (pair, py, px): bilinear with clamped taps, torch index arithmetic; (N, C)"""
+        h, w = img.shape[-2:]
+        y0, x0 = py.floor(), px.floor()
+        fy, fx = (py - y0)[:, None], (px - x0)[:, None]
+        y0i, x0i = y0.long().clamp(0, h - 1), x0.long().clamp(0, w - 1)
+        y1i, x1i = (y0.long() + 1).clamp(0, h - 1), (x0.long() + 1).clamp(0, w - 1)
+        top = img[pair, :, y0i, x0i] * (1 - fx) + img[pair, :, y0i, x1i] * fx
+        bottom = img[pair, :, y1i, x0i] * (1 - fx) + img[pair, :, y1i, x1i] * fx
+        return top * (1 - fy) + bottom * fy
+
+    def smooth_at_loss(self, frame1, frame2, times, scale):
+        """W * sum over (channels 0:2 guided by frame1, 2:4 by frame2) of 0.5 (mean(w_y robust_l1(gy)) + mean(w_x robust_l1(gx))): the
+        reference's BilateralSmooth of order 1 with its finite difference over the pixel grid replaced by the network's analytic derivative
+        at N random points, gy / gx the flow change per pixel (image_grads' unit).  One flow_at(.., jacobian='yx') call (fused = False:
+        flow_jacobian_composed)"""
+        b, _, h, w = frame1.shape
+        pair, py, px, poses = self.smooth_points_table(times, b, h, w)
+        factor = self._scale(scale, frame1)
+        if self.fused:
+            _, jac = flownet.flow_at(self.net, poses, factor, planar=True, jacobian='yx')
+        else:
+            _, jac = flownet.flow_jacobian_composed(self.net, poses, factor, 'yx', planar=True)
+        self.smooth_sample = (pair, py, px, poses)
+        gy, gx = jac[0] * (2.0 / max(h - 1, 1)), jac[1] * (2.0 / max(w - 1, 1))          # (4, N) each
+        gauss, k = self.args.edge_func == 'gauss', float(self.args.edge_constant)
+
+        def edge(d):
+            d = k * d
+            return torch.exp(-(d * d if gauss else d.abs()).mean(dim=1))
+
+        def robust(v):
+            return torch.sqrt(v * v + 1e-6)
+
+        total = 0
+        for ch, img in ((slice(0, 2), frame1), (slice(2, 4), frame2)):
+            img = img.detach().to(torch.float32)
+            at = self._sample_clamped(img, pair, py, px)
+            w_y = edge(self._sample_clamped(img, pair, py + 1, px) - at)
+            w_x = edge(self._sample_clamped(img, pair, py, px + 1) - at)
+            total = total + 0.5 * ((w_y[None] * robust(gy[ch])).mean() + (w_x[None] * robust(gx[ch])).mean())
+        return self.smooth_at_weight * total
+
     # ---- the LightningModule surface ----
 
     def training_step(self, batch, batch_idx):
@@ -430,6 +500,8 @@ class FlowTrainer(LightningModule):
                 between_loss = self.between_points_loss(frame1, frame2, times, scale)
             else:
                 between_loss = self.between_loss(frame1, frame2, self._host_times(times), scale)
+        if self.smooth_at_weight != 0:
+            smooth_at_loss = self.smooth_at_loss(frame1, frame2, times, scale)
         flow12, flow21 = self.forward(frame1, times, scale)
         if len(batch) == 5:
             self.log('train/EPE', self._epe(flow12, batch[-1]), on_step=False, on_epoch=True, batch_size=frame1.shape[0])
@@ -438,6 +510,8 @@ class FlowTrainer(LightningModule):
         loss = l1_loss + census_loss + ssim_loss + smooth_loss
         if self.between_weight != 0:
             loss = loss + between_loss
+        if self.smooth_at_weight != 0:
+            loss = loss + smooth_at_loss
         if hasattr(self.net, 'stash_grid'):
             # a spatial controller updates its mask grid in place and the backward pass checks the grid's version: on_after_backward stashes
             self._stash = tuple(t.detach() for t in (softmax1, frame1, mask1, softmax2, frame2, mask2))
@@ -453,6 +527,8 @@ class FlowTrainer(LightningModule):
         self.log('train/smooth', smooth_loss)
         if self.between_weight != 0:
             self.log('train/between', between_loss)
+        if self.smooth_at_weight != 0:
+            self.log('train/smooth_at', smooth_at_loss)
         return loss
 
     def on_after_backward(self):

@@ -81,8 +81,9 @@ class ProgressiveEncoderController(nn.Module):
         with its k_active), an `override_mask` as flow_at takes it; `get_mask` among the keywords returns (out, that mask); `pose_grad=True` is flow_at's"""
         override_mask = kwargs.get('override_mask')
         if override_mask is not None and override_mask.dim() == 2:    # a grid (res^3, 515): the per-point mask, interpolated by the kernels
-            return flow_at(self, x, 1.0, override_mask=override_mask, get_mask='get_mask' in kwargs, pose_grad=kwargs.get('pose_grad', False))
-        out = flow_at(self, x, 1.0, override_mask=override_mask, pose_grad=kwargs.get('pose_grad', False))
+            return flow_at(self, x, 1.0, override_mask=override_mask, get_mask='get_mask' in kwargs, pose_grad=kwargs.get('pose_grad', False),
+                           jacobian=kwargs.get('jacobian'))
+        out = flow_at(self, x, 1.0, override_mask=override_mask, pose_grad=kwargs.get('pose_grad', False), jacobian=kwargs.get('jacobian'))
         if 'get_mask' in kwargs:
             return out, self.mask if override_mask is None else override_mask
         return out
@@ -458,7 +459,7 @@ class StashedSpatialController(ProgressiveEncoderController):
                 raise NotImplementedError(f'StashedSpatialController: the `{key}` keyword is not supported: the mask is interpolated inside '
                                           f'the kernels at the poses themselves')
         return flow_at(self, x, 1.0, override_mask=kwargs.get('override_mask'), get_mask='get_mask' in kwargs,
-                       pose_grad=kwargs.get('pose_grad', False))
+                       pose_grad=kwargs.get('pose_grad', False), jacobian=kwargs.get('jacobian'))
 
     # ---- checkpoints ----
     def load_mask(self):

@@ -88,10 +88,14 @@ def main():
     ap.add_argument('--spatial', type=int, default=0, metavar='R', help='progressive nets: a per-point mask from an R^3 grid (0: the global mask)')
     ap.add_argument('--pose-grad', action='store_true', help='--points: the step also differentiates the poses (flow_at(.., pose_grad=True); the '
                     'baseline: the composed network with the poses as a leaf); adds no_pose_grad_step_ms, the same step without it, and pose_grad_cost_ms / pose_grad_cost_ratio')
+    ap.add_argument('--jacobian', metavar='D', help='--points: time flow_at(.., jacobian=D) (D from tyx, e.g. yx: DESIGN 24), forward and the step with '
+                    'upstream gradients for both outputs; adds plain_*_ms, the call without the keyword at the same N, and jacobian_ratio_*; the '
+                    '--baseline is flownet.flow_jacobian_composed')
     ap.add_argument('--dim', type=int, default=3, choices=[2, 3], help='coordinates per point: 3 (t, y, x) or 2 (y, x), one frame pair')
     a = ap.parse_args()
     assert a.dim == 3 or not (a.points or a.spatial or a.frames > 1), '--dim 2: one frame on its (y, x) grid'
     assert a.points or not a.pose_grad, '--pose-grad: the coordinate gradient exists at pose lists (--points)'
+    assert not a.jacobian or (a.points and not a.spatial and not a.pose_grad and a.dim == 3), '--jacobian: a pose list (--points), a global mask, three coordinates'
     from fit_flow import composed_flow_at, composed_flow_fields
     dev = torch.device('cuda', 0)
     torch.manual_seed(0)
@@ -157,7 +161,31 @@ def main():
             torch.autograd.backward([f12, f21], [up[:, :2], up[:, 2:]])
         return fwd, step
 
-    if a.points:
+    def jacobian_paths(composed):
+        poses = (torch.rand(n, 3, generator=torch.Generator().manual_seed(1)) * 2 - 1).to(dev)
+        nd = len(flownet.jacobian_dirs(a.jacobian))
+        up_p, up_j = torch.randn(4, n, device=dev), torch.randn(nd, 4, n, device=dev)
+        if composed:
+            kw = dict(override_mask=mask_dev) if prog else {}
+            call = lambda: flownet.flow_jacobian_composed(target, poses, 2.0, a.jacobian, planar=True, **kw)  # noqa: E731
+        else:
+            call = lambda: flownet.flow_at(target, poses, 2.0, planar=True, jacobian=a.jacobian)  # noqa: E731
+
+        def fwd():
+            with torch.no_grad():
+                call()
+
+        def step():
+            for p in params:
+                p.grad = None
+            torch.autograd.backward(list(call()), [up_p, up_j])
+        return fwd, step
+
+    if a.jacobian:
+        todo = {'fused': jacobian_paths(False), 'plain': point_paths(flownet.flow_at, planar=True)}
+        if a.baseline:
+            todo['torch'] = jacobian_paths(True)
+    elif a.points:
         todo = {'fused': point_paths(flownet.flow_at, a.pose_grad, planar=True)}
         if a.pose_grad:
             todo['no_pose_grad'] = point_paths(flownet.flow_at, planar=True)
@@ -175,7 +203,7 @@ def main():
     f_fwd, f_step = flops_siren(n) if siren else flops(n, learnable, net.encoding_dim if a.net in flownet.positional_model_dict else 512)
     sizes = (_lib.lib().sininn_siren_saved_bytes, _lib.lib().sininn_siren_workspace_bytes) if siren else \
         (_lib.lib().sininn_flownet_saved_bytes, _lib.lib().sininn_flownet_workspace_bytes)
-    out = dict(net=a.net, **(dict(dim=a.dim) if a.dim != 3 else {}), **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(mode='points', pose_grad=a.pose_grad) if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
+    out = dict(net=a.net, **(dict(dim=a.dim) if a.dim != 3 else {}), **(dict(k_active=a.k_active) if prog else {}), **(dict(spatial_res=target.res) if a.spatial else {}), **(dict(jacobian=a.jacobian) if a.jacobian else {}), **(dict(mode='points', pose_grad=a.pose_grad) if a.points else dict(frames=a.frames, height=a.height, width=a.width)), points=n, flop_forward=f_fwd, flop_step=f_step,
                saved_bytes=sizes[0](n), workspace_bytes=sizes[1](n))
     for k in res:
         for what, fl in (('forward', f_fwd), ('step', f_step)):
@@ -183,11 +211,14 @@ def main():
             best = min(meds)
             out[f'{k}_{what}_ms'] = best
             out[f'{k}_{what}_ms_windows'] = [round(m, 4) for m in meds]
-            if not (a.pose_grad and what == 'step' and k != 'no_pose_grad'):      # flop_step counts no pose gradient: no share for such a step
+            if not (a.pose_grad and what == 'step' and k != 'no_pose_grad') and not (a.jacobian and k != 'plain'):  # flop_* count the plain call      # flop_step counts no pose gradient: no share for such a step
                 out[f'{k}_{what}_mfma_peak_share'] = round(fl / (best * 1e-3) / PEAK_F32_MFMA, 4)
     if a.baseline:
         out['speedup_forward'] = round(out['torch_forward_ms'] / out['fused_forward_ms'], 3)
         out['speedup_step'] = round(out['torch_step_ms'] / out['fused_step_ms'], 3)
+    if a.jacobian:
+        out['jacobian_ratio_forward'] = round(out['fused_forward_ms'] / out['plain_forward_ms'], 3)
+        out['jacobian_ratio_step'] = round(out['fused_step_ms'] / out['plain_step_ms'], 3)
     if a.pose_grad:
         out['pose_grad_cost_ms'] = round(out['fused_step_ms'] - out['no_pose_grad_step_ms'], 4)
         out['pose_grad_cost_ratio'] = round(out['fused_step_ms'] / out['no_pose_grad_step_ms'], 3)

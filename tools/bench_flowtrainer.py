@@ -31,6 +31,8 @@ adds the step with the in-between consistency loss next to the ste
     between_network    flow_fields forward + backward alone at the stamps of one between term: what the extra evaluations cost
 With --between-points N the loss is drawn at N random points a step -- flowsynth.gather_at, or gather_at_composed -- and
 between_network is flow_at forward + backward at the N (under --between-back network 2 N) poses of one draw.
+    python tools/bench_flowtrainer.py --loss-smooth-at 1 --smooth-points N [--log]
+adds smooth_at_fused / smooth_at_composed, the step with the smoothness prior on the flow Jacobian at N sampled points.
 The generator is reset before every window, so all windows draw the same times.  --log appends the line to
 profiles/flowtrainer_bench.jsonl.
 """
@@ -67,6 +69,9 @@ def main():
     ap.add_argument('--between-back', default='network', choices=['network', 'reverse'])
     ap.add_argument('--between-points', type=int, metavar='N',
                     help='--loss-between: the loss at N random points a step (DESIGN 23) instead of --between-taus whole frames')
+    ap.add_argument('--loss-smooth-at', type=float, default=0.0, help='also time the step with the smoothness prior on the flow Jacobian at '
+                    'sampled points (DESIGN 24): smooth_at_fused / smooth_at_composed next to the step without it')
+    ap.add_argument('--smooth-points', type=int, default=4096, metavar='N', help='--loss-smooth-at: points a step')
     ap.add_argument('--log', action='store_true', help='append the line to profiles/flowtrainer_bench.jsonl')
     a = ap.parse_args()
     from sin_inn_amd import flowdata, flownet, flowtrainer, progressive
@@ -147,6 +152,23 @@ def main():
                 torch.autograd.backward([f12, f21], [up2[i:i + per, :2], up2[i:i + per, 2:]])
 
         todo.update(between_fused=between(True), between_composed=between(False), between_network=between_network)
+    if a.loss_smooth_at != 0:
+        torch.manual_seed(0)
+        net3 = flownet.all_model_dict[a.net](flownet.ModelParams())
+        if net3.is_progressive:
+            net3 = progressive.LinearControllerEarly(net3, 5000, epsilon=1e-3)
+        args3 = argparse.Namespace(**{**vars(args), 'net': net3, 'loss_smooth_at': a.loss_smooth_at, 'smooth_points': a.smooth_points})
+        model3 = flowtrainer.FlowTrainer(args3).to(dev)
+        opt3 = model3.attach_optimizer()
+
+        def smooth_at(fused):
+            def run():
+                model3.fused = fused
+                opt3.zero_grad()
+                model3.training_step(batch, 0).backward()
+                opt3.step()
+            return run
+        todo.update(smooth_at_fused=smooth_at(True), smooth_at_composed=smooth_at(False))
     res = {k: [] for k in todo}
     for _ in range(a.rounds):
         for k, fn in todo.items():
@@ -168,6 +190,10 @@ def main():
         out['between_extra_ms'] = round(out['between_fused_ms'] - out['fused_ms'], 4)
         out['between_network_share_of_extra'] = round(out['between_network_ms'] / out['between_extra_ms'], 3)
         out['between_fused_over_composed'] = round(out['between_fused_ms'] / out['between_composed_ms'], 4)
+    if a.loss_smooth_at != 0:
+        out.update(loss_smooth_at=a.loss_smooth_at, smooth_points=a.smooth_points)
+        out['smooth_at_extra_ms'] = round(out['smooth_at_fused_ms'] - out['fused_ms'], 4)
+        out['smooth_at_fused_over_composed'] = round(out['smooth_at_fused_ms'] / out['smooth_at_composed_ms'], 4)
     print(json.dumps(out))
     if a.log:
         with open(os.path.join(ROOT, 'profiles', 'flowtrainer_bench.jsonl'), 'a') as f:

@@ -234,11 +234,14 @@ def cycle_term(query, poses, out):
 
 
 def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, lr=1e-3, seed=0, device='cuda', log=None,
-               max_iteration=1000, cycle=False, cycle_weight=1.0, controller='early', res=7):
+               max_iteration=1000, cycle=False, cycle_weight=1.0, controller='early', res=7, smooth_at=0.0):
     """fit net(poses) to analytic_flow at `n_points` fresh uniform points of [-1, 1]^3 per step (a seeded generator): MSE, FusedAdam.
     `cycle`: plus cycle_weight x cycle_term, the forward-backward consistency at p' (a chained query).
     Returns the list of per-step losses (floats).  `info`: a dict that receives the network (the controller of a progressive one)
     as info['net'] and, as info['first'], the first step's `poses`, `target` and the network's `state` before that step.
+    `smooth_at`: plus smooth_at x the first-order smoothness of the network's analytic Jacobian at the same points:
+    0.5 (mean robust_l1(d flow / d y per pixel) + mean robust_l1(d flow / d x per pixel)), robust_l1(v) = sqrt(v^2 + 1e-6), no guide image;
+    flow_at(.., jacobian='yx'), or with `composed` flownet.flow_jacobian_composed.
     `controller='spatial'`: a StashedSpatialController(net, res) called on the pose list; it stashes the per-point squared error of flow12
     and runs update_progress every block_iterations steps (their number: info['progress'])"""
     from sin_inn_amd import FusedAdam, flownet, progressive
@@ -265,8 +268,14 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
         if info is not None and step == 0:
             info['first'] = dict(poses=poses, target=target, state={k: v.detach().clone() for k, v in net.state_dict().items()})
         opt.zero_grad()
-        out = at(net, poses, 1.0)
+        if smooth_at:
+            out, jac = flownet.flow_jacobian_composed(net, poses, 1.0, 'yx') if composed else flownet.flow_at(net, poses, 1.0, jacobian='yx')
+        else:
+            out = at(net, poses, 1.0)
         loss = torch.nn.functional.mse_loss(out, target)
+        if smooth_at:
+            gy, gx = jac[..., 0] * (2.0 / 63), jac[..., 1] * (2.0 / 95)      # per pixel of analytic_flow's 64 x 96 clip
+            loss = loss + smooth_at * 0.5 * (torch.sqrt(gy * gy + 1e-6).mean() + torch.sqrt(gx * gx + 1e-6).mean())
         if cycle:
             loss = loss + cycle_weight * cycle_term(query, poses, out)
         loss.backward()
@@ -366,7 +375,10 @@ def main():
     ap.add_argument('--points', type=int, default=0, metavar='N', help='fit net(poses) at N random points per step (fit_points) instead of a frame pair')
     ap.add_argument('--cycle', action='store_true', help='--points: add the forward-backward consistency term at p + flow12(p); runs the '
                     'fused and the composed loop and prints both')
+    ap.add_argument('--smooth-at', type=float, default=0.0, metavar='W', help='--points: add W x the smoothness of the analytic flow Jacobian '
+                    'at the sampled points (flow_at(.., jacobian=); DESIGN 24)')
     a = ap.parse_args()
+    assert a.points or not a.smooth_at, '--smooth-at is a term of the --points loop'
     assert a.points or not a.cycle, '--cycle is a term of the --points loop'
     assert a.dim == 3 or not a.points, '--points fits the three-coordinate clip; --dim 2 is the frame-pair loop'
     if a.cycle:
@@ -377,7 +389,7 @@ def main():
         return
     if a.points:
         losses = fit_points(a.net, a.points, a.steps, a.composed, lr=a.lr, seed=a.seed, log=print, max_iteration=a.max_iteration,
-                            controller=a.controller, res=a.res)
+                            controller=a.controller, res=a.res, smooth_at=a.smooth_at)
         print(f'first {losses[0]:.6f}  last {losses[-1]:.6f}')
         return
     losses = fit(a.net, a.height, a.width, a.steps, a.lr, a.seed, a.composed, log=print, max_iteration=a.max_iteration,

@@ -70,6 +70,9 @@ def get_parser():
     ap.add_argument('--between-points', type=int, metavar='N',
                     help='--loss-between: N random points a step instead of whole frames (main.py --between-points; DESIGN 23)')
     ap.add_argument('--between-back', choices=('network', 'reverse'), default='network', help='--loss-between: as --back')
+    ap.add_argument('--loss-smooth-at', type=float, default=0, metavar='W',
+                    help='--fit-epochs: weight of the smoothness prior on the flow Jacobian at random points (main.py --loss-smooth-at; DESIGN 24)')
+    ap.add_argument('--smooth-points', type=int, metavar='N', help='--loss-smooth-at: random points a step (default 4096)')
     return ap
 
 
@@ -110,6 +113,8 @@ def trainer_args(a):
     argv += ['--synthetic', *map(str, a.synthetic)] if a.synthetic else ['--input-video', a.input_video]
     if a.holdout:
         argv += ['--holdout', str(a.holdout)]
+    if a.loss_smooth_at and a.fit_epochs:
+        argv += ['--loss-smooth-at', str(a.loss_smooth_at)] + (['--smooth-points', str(a.smooth_points)] if a.smooth_points is not None else [])
     if a.loss_between and a.fit_epochs:
         argv += ['--loss-between', str(a.loss_between), '--between-back', a.between_back]
         argv += ['--between-points', str(a.between_points)] if a.between_points is not None else ['--between-taus', str(a.between_taus or 1)]

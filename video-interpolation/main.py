@@ -27,6 +27,8 @@ Differences from the reference, all to make the path runnable here:
   * `--loss-between W` (with `--between-taus K`, `--between-back {network,reverse}`) adds the in-between consistency loss of
     sin_inn_amd/flowtrainer.py to the training step; the default 0 leaves the step as it was.  `--between-points N` in
     place of `--between-taus` draws it at N random points a step.
+  * `--loss-smooth-at W --smooth-points N` adds the edge-aware smoothness prior on the network's analytic Jacobian at N random points a
+    step (`train/smooth_at`); RBF, FFN, UFF, PRBF, PFF, PUFF without --spatially-adaptive.
 """
 import argparse
 import os
@@ -40,6 +42,7 @@ if ROOT not in sys.path:
 
 NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE')
 OUT_OF_SCOPE_NETWORKS = ('siren', 'MPFF')
+JACOBIAN_NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF')   # the networks with tangent kernels: --loss-smooth-at
 SPATIAL_NETWORKS = ('PRBF', 'PFF', 'PUFF', 'PRFF', 'PRBFG')    # the 515-wide progressive networks of NETWORKS: --spatially-adaptive
 
 
@@ -86,6 +89,10 @@ def get_parser():
                         help="--loss-between: the flow toward the previous frame, as interpolate.py's --back (default network)")
     parser.add_argument('--between-points', default=argparse.SUPPRESS, type=int, metavar='N',
                         help='--loss-between: draw the term at N random (pair, tau, y, x) a step instead of whole frames (DESIGN 23)')
+    parser.add_argument('--loss-smooth-at', default=argparse.SUPPRESS, type=float, metavar='W',
+                        help='weight of the edge-aware smoothness prior on the analytic flow Jacobian at random points (DESIGN 24; default 0: off)')
+    parser.add_argument('--smooth-points', default=argparse.SUPPRESS, type=int, metavar='N',
+                        help='--loss-smooth-at: random (pair, y, x) a step (default 4096)')
     # Logging options
     parser.add_argument('--wandb', help='any name: selects the JSON-lines FileLogger and checkpointing')
     parser.add_argument('--log-gt', action='store_true')
@@ -105,6 +112,14 @@ def get_args(argv=None):
             parser.error('--between-taus draws whole frames, --between-points sampled points: give one of them')
         if args.between_points < 1:
             parser.error('--between-points N: N >= 1')
+    if hasattr(args, 'smooth_points') and args.smooth_points < 1:
+        parser.error('--smooth-points N: N >= 1')
+    if getattr(args, 'loss_smooth_at', 0) != 0:
+        if args.net not in JACOBIAN_NETWORKS:
+            parser.error(f'--loss-smooth-at with --net {args.net} is out of scope: the flow Jacobian is built for '
+                         f'{", ".join(JACOBIAN_NETWORKS)} (sin_inn_amd/flownet.py, flow_at(.., jacobian=))')
+        if args.spatially_adaptive:
+            parser.error('--loss-smooth-at with --spatially-adaptive is out of scope: the flow Jacobian takes a global mask, no per-point one')
     if args.spatially_adaptive and args.net not in SPATIAL_NETWORKS:
         parser.error(f'--spatially-adaptive with --net {args.net} is out of scope here: the per-point masks of '
                      f'sin_inn_amd.progressive.StashedSpatialController are built for the 515-wide progressive networks '
