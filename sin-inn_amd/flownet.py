@@ -67,7 +67,7 @@ point has its own 515 mask values, interpolated trilinearly from the controller'
 per-point mask never exists in memory either: the kernels sample the grid while they generate the operand of layer 1
 (`flownet_forward_spatial` / `flownet_backward_spatial`, the SPATIAL mode), W1 is read in place and there is no pack step.
 `flow_fields` takes that controller (`k_active` = its `next_block`), or a raw grid as a 2-D `override_mask`; `flownet_sample_mask`
-returns the interpolated mask itself (the reference's `get_mask=` keyword).  All 515-wide progressive networks; `PPE` is refused.
+returns the interpolated mask itself (the reference's `get_mask=` keyword).  The networks with the table's `spatial` (flowcaps.py).
 
 One call path serves every mode.  The library has five run entry points, `sininn_{flownet,siren}_{forward,backward}` and
 `sininn_flownet_sample_mask`; each takes the network descriptor and, beside it, a call descriptor (`_lib.FlowNetCall`) whose mode bits say
@@ -98,19 +98,20 @@ Per-point masks at pose lists: `controller(poses)` of a `StashedSpatialControlle
 interpolates it under no_grad: the pose gradient has no d mask / d pose term.  A bare progressive model with a grid is still refused at a
 pose list: the interpolation is a controller's.
 
-Two coordinates (`ModelParams(domain_dim=2)`, the network of video-interpolation/pair_flow.py:39-42): RBF, FFN, UFF, RBFG and their
-progressive forms PRBF, PFF, PUFF, PRBFG are built on (y, x) with the reference's layouts (`encode.centres` [512][2], `encode.frequencies`
+Two coordinates (`ModelParams(domain_dim=2)`, the network of video-interpolation/pair_flow.py:39-42): the networks with the table's `pair`
+are built on (y, x) with the reference's layouts (`encode.centres` [512][2], `encode.frequencies`
 [2][256], `encode.offsets` [256][2], a progressive first weight [256][514] = the columns of cat((y, x), enc)) and run in the DIM = 2
 instantiations of the kernels (`domain_dim = 2` in the call descriptor, beside the unchanged network descriptor).
 `flow_fields(net_or_controller, None, h, w, scale)` is one frame pair, poses linspace(-1, 1, h) x linspace(-1, 1, w) (pair_flow.py:55-59),
 flows (1, 4, h, w): `times` must be None.  `flow_at`, `net(poses)` and `controller(poses, ..)` take (..., 2) -> (..., 4).  The global mask has
 514 values in blocks of 4, `override_mask`, `get_mask` and `k_active` work as at three coordinates.  Refused there, each with a ValueError
-that names the dimension and the mode (`_refuse_pair_modes`): RFF / PRFF, PE / PPE, MPFF, SIREN, per-point masks (StashedSpatialController,
-2-D `override_mask` grids), `pose_grad=True`, `times` for such a network, and poses of the other dimension either way.
+that names the dimension and the mode (`_refuse_pair_modes`): the other networks, the modes of `flowcaps.PAIR_MODES`, `times` for such a
+network, and poses of the other dimension either way.
 
-Out of scope: a plain (non-progressive) piecewise network and a frequency gradient for that encoding, the `alpha=` keyword of ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`,
-spatial masks for `PPE`.  Of `siren` only the `--net siren` switch of the command line remains
-closed, and of `MPFF` its `--net MPFF` (video-interpolation/main.py still refuses both).  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
+Which network serves which call (two coordinates, per-point masks, the frequency, pose and Jacobian gradients, the command line) is the table
+of `sin_inn_amd/flowcaps.py`: every refusal of this module that is about the network reads it, and a network or a mode is
+added there.  Out of scope beside it: a plain (non-progressive) piecewise network, the `alpha=` keyword of
+ProgressiveModel.apply_control, `FixedSpatialController`, `AdaptiveController`.  Sintel / .flo IO and the trainer are `sin_inn_amd.flowdata` and
 `sin_inn_amd.flowtrainer`.  The optimiser: these modules expose ordinary nn.Parameters;
 `sin_inn_amd.FusedLAMB` is the reference's apex FusedLAMB (trainer.py:134-135) restated, `sin_inn_amd.FusedAdam` drives them as well.
 """
@@ -122,12 +123,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as nnf
 
-from . import _lib
+from . import _lib, flowcaps
+from .flowcaps import FOURIER, PE, PIECEWISE, RBF, RBFG
 from .ops import _stream, ptr
 
 check = _lib.check
 EPSILON = 1e-4
-RBF, FOURIER, RBFG, PE, PIECEWISE = 0, 1, 3, 4, 5
 
 
 class ModelParams:
@@ -577,39 +578,34 @@ def _points_and_layers(a, lins, times, ys, xs, scale, dim=3):
     return a
 
 
-PAIR_KINDS = (RBF, FOURIER, RBFG)                       # the encodings whose kernels exist for two coordinates per point
+def _row(net):
+    """(model, its row of flowcaps.TABLE) of a model or a controller: found by what the kernels evaluate"""
+    from .progressive import ProgressiveEncoderController
+    model = net.model if isinstance(net, ProgressiveEncoderController) else net
+    enc = getattr(model, 'encode', None)
+    return model, flowcaps.BY_ENCODING[getattr(enc, 'kind', None), isinstance(enc, RotatedFourierFeatures)]
 
 
-def _refuse_pair_modes(net, dim, spatial=False, enc_a=None):
+def _refuse_pair_modes(net, dim, spatial=False, enc_a=None, pose_grad=False):
     """a network with domain_dim != 3: what the kernels do not do for it, each refusal under the dimension and the mode"""
     if dim != 2:
         raise ValueError(f'domain_dim {dim}: the flownet kernels take 3 coordinates per point (t, y, x) or 2 (y, x)')
-    if isinstance(net, SirenModel):
-        raise ValueError('domain_dim 2: SIREN is out of scope: its kernels take three coordinates')
-    enc = net.encode
-    if isinstance(enc, RotatedFourierFeatures) or enc_a is not None:
-        raise ValueError('domain_dim 2: RFF / PRFF (learnable frequencies) are out of scope: the frequency gradient exists for three '
-                         'coordinates only')
-    if enc.kind == PE:
-        raise ValueError('domain_dim 2: PE / PPE are out of scope: 16 features, a layer 1 of another width than the kernels are built for')
-    if enc.kind == PIECEWISE:
-        raise ValueError('domain_dim 2: MPFF (the piecewise-linear encoding) is out of scope: its kernels take three coordinates')
+    row = _row(net)[1]
+    if enc_a is not None and row.kind is not None:       # a frequency matrix of the caller's is the learnable call, whatever the class
+        row = flowcaps.TABLE['RFF']
+    flowcaps.refuse(row, 'pair', 'domain_dim 2')
     if spatial:
-        raise ValueError('domain_dim 2: per-point masks (StashedSpatialController, a 2-D override_mask grid) are out of scope: the mask grid '
-                         'is one over (t, y, x)')
-    assert enc.kind in PAIR_KINDS
+        flowcaps.refuse(flowcaps.PAIR_MODES, 'spatial', 'domain_dim 2')
+    if pose_grad:
+        flowcaps.refuse(flowcaps.PAIR_MODES, 'pose_grad', 'domain_dim 2')
 
 
 def _call_dim(net, override_mask=None, pose_grad=False):
     """domain_dim of a model or a controller; other than 3: every refusal of that dimension that a public call can meet, before any
     device is looked at"""
-    from .progressive import ProgressiveEncoderController
     dim = net.domain_dim
     if dim != 3:
-        _refuse_pair_modes(net.model if isinstance(net, ProgressiveEncoderController) else net, dim,
-                           spatial=override_mask is not None and override_mask.dim() == 2)
-        if pose_grad:
-            raise ValueError(f'domain_dim {dim}: pose_grad=True is out of scope: the coordinate gradient exists for three coordinates only')
+        _refuse_pair_modes(net, dim, override_mask is not None and override_mask.dim() == 2, pose_grad=pose_grad)
     return dim
 
 
@@ -699,7 +695,7 @@ def _call(a, mask=None, enc_grad=False, enc_workspace=None, g_enc_a=None, pose_g
         c.grid, c.res, c.centre_scale = _spatial(a, mask.tensor, mask.res, mask.centre_scale)
     if pose_grad:
         if a._dim != 3:
-            raise ValueError(f'domain_dim {a._dim}: pose_grad=True is out of scope: the coordinate gradient exists for three coordinates only')
+            flowcaps.refuse(flowcaps.PAIR_MODES, 'pose_grad', f'domain_dim {a._dim}')
         assert enc_workspace is None, 'with pose_grad the frequency gradient\'s workspace is part of pose_workspace'
         c.mode |= _lib.POSEGRAD
         c._g_poses = _out_tensor(g_poses, (a.W, 3), a._device)
@@ -990,19 +986,9 @@ def jacobian_dirs(jacobian):
 def _refuse_jacobian(net, override_mask=None, pose_grad=False, poses=None, what='flow_at(.., jacobian=)'):
     """what the Jacobian kernels do not do, each refusal a ValueError that names what is missing; `net`: a model or a controller.  Needs no
     device"""
-    from .progressive import ProgressiveEncoderController, StashedSpatialController
-    model = net.model if isinstance(net, ProgressiveEncoderController) else net
-    if isinstance(model, SirenModel):
-        raise ValueError(f'{what}: SIREN is out of scope: the tangent of a sine layer is no gated copy of the network (no kernel evaluates it)')
-    enc = model.encode
-    if isinstance(enc, RotatedFourierFeatures):
-        raise ValueError(f'{what}: RFF / PRFF are out of scope: learnable frequencies would need the second derivative of the encoding')
-    if enc.kind == RBFG:
-        raise ValueError(f'{what}: RBFG / PRBFG are out of scope: no tangent kernel exists for the radial-basis grid')
-    if enc.kind == PE:
-        raise ValueError(f'{what}: PE / PPE are out of scope: no tangent kernel exists for the narrow positional layer 1')
-    if enc.kind == PIECEWISE:
-        raise ValueError(f'{what}: MPFF is out of scope: no tangent kernel exists for the piecewise-linear encoding')
+    from .progressive import StashedSpatialController
+    model, row = _row(net)
+    flowcaps.refuse(row, 'jacobian', what)
     if model.domain_dim != 3:
         raise ValueError(f'{what}: domain_dim {model.domain_dim} is out of scope: the Jacobian kernels take three coordinates (t, y, x)')
     if isinstance(net, StashedSpatialController) or (override_mask is not None and override_mask.dim() == 2):
@@ -1011,7 +997,6 @@ def _refuse_jacobian(net, override_mask=None, pose_grad=False, poses=None, what=
         raise ValueError(f'{what}: pose_grad=True cannot be combined with the Jacobian: there is no gradient to the poses through it')
     if poses is not None and poses.requires_grad:
         raise ValueError(f'{what}: poses that require a gradient: there is no gradient to the poses through the Jacobian (poses.detach())')
-    assert enc.kind in (RBF, FOURIER)
 
 
 def _dirs_bits(dirs):
@@ -1160,10 +1145,7 @@ def _resolve_mask(net, override_mask, device):
         if override_mask is not None:
             raise ValueError('override_mask needs a progressive network')
         return model, Mask()
-    if override_mask is not None and override_mask.dim() == 2 and model.domain_dim != 3:
-        raise ValueError(f'domain_dim {model.domain_dim}: a 2-D override_mask (a grid of per-point masks) is out of scope: the mask grid is one '
-                         'over (t, y, x)')
-    if override_mask is not None and override_mask.dim() == 2:
+    if override_mask is not None and override_mask.dim() == 2:            # three coordinates: _call_dim has refused a grid at two
         # a raw grid (res^3, enc_dim) on the device: not inspected, nothing skipped; the cell map is the spatial controller's, else identity
         g = override_mask.detach()
         _on_gpu(g, 'mask grid')
@@ -1245,8 +1227,8 @@ def flow_at(net, poses, scale=1.0, override_mask=None, get_mask=False, planar=Fa
     `jacobian`: a string of distinct letters from 'tyx' (True: 'yx') returns (out, jac): jac (..., 4, |D|) (`planar=True`: (|D|, 4, N)), the
     derivative of `out` along each named coordinate, always in the order t, y, x, in flow units (`scale` included) per unit of the normalised
     coordinate.  `out` is bitwise the call's without the keyword, and BOTH carry a gradient to the parameters (one autograd function, the
-    tangent kernels of csrc/flownet_jacobian.h), so a loss on the derivative trains.  RBF, FFN, UFF and PRBF, PFF, PUFF under a global mask;
-    everything else, `pose_grad=True`, poses that require a gradient and `get_mask` with it are refused with a ValueError."""
+    tangent kernels of csrc/flownet_jacobian.h), so a loss on the derivative trains.  The networks with the table's `jacobian` (flowcaps.py)
+    under a global mask; everything else, `pose_grad=True`, poses that require a gradient and `get_mask` with it are refused with a ValueError."""
     dirs = None
     if jacobian is not None and jacobian is not False:
         dirs = jacobian_dirs(jacobian)

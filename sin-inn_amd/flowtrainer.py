@@ -42,7 +42,7 @@ import random
 import numpy as np
 import torch
 
-from . import _lib, flowloss as FL, flownet
+from . import _lib, flowcaps, flowloss as FL, flownet
 from .functional import flow_warp_l1
 from .lightning import LightningModule, load_checkpoint
 from .ops import _stream, ptr
@@ -242,31 +242,22 @@ class FlowTrainer(LightningModule):
         self.between_weight = float(getattr(args, 'loss_between', 0) or 0)
         self.between_rng = None
         self.between_points = None
+        if self.between_weight != 0 and int(self.net.domain_dim) != 3:
+            raise ValueError(f'domain_dim {int(self.net.domain_dim)}: --loss-between evaluates the network at times between two frames; a '
+                             'network on (y, x) has no time axis')
+        # the options' own rules are the command line's (flowcaps); the network's Jacobian before the range of --smooth-points, as ever
+        flowcaps.check_step_options(args, GRID_POINTS, lambda: flownet._refuse_jacobian(self.net, what='--loss-smooth-at'))
         if self.between_weight != 0:
-            dim = int(self.net.domain_dim)
-            if dim != 3:
-                raise ValueError(f'domain_dim {dim}: --loss-between evaluates the network at times between two frames; a network on '
-                                 '(y, x) has no time axis')
             self.between_taus = int(getattr(args, 'between_taus', 1))
             self.between_back = getattr(args, 'between_back', 'network')
             self.between_dt = getattr(args, 'between_dt', None)
-            if not 1 <= self.between_taus <= 32:
-                raise ValueError(f'--between-taus {self.between_taus}: 1 to 32 times a step (two rows of one gather call each)')
-            if self.between_back not in ('network', 'reverse'):
-                raise ValueError(f"--between-back is 'network' or 'reverse', got {self.between_back!r}")
-            if self.between_dt is None or not float(self.between_dt) > 0:
-                raise ValueError('--loss-between needs between_dt, the spacing of the clip\'s times, 2 / (frames - 1)')
             self.between_rng = random.Random(getattr(args, 'between_seed', 0))          # seeded once per trainer; host only
             self.between_flows = None            # test hook: the (T', 4, h, w) flows of the last between term
             self.between_frames = None           # test hook: its synthesized frames X (B, 2K, C, h, w)
             # at sampled points: N random (pair, tau, y, x) a step instead of whole grids; present only when given
             self.between_points = getattr(args, 'between_points', None)
             if self.between_points is not None:
-                if hasattr(args, 'between_taus'):
-                    raise ValueError('--between-taus draws whole frames, --between-points sampled points: give one of them')
                 self.between_points = int(self.between_points)
-                if not 1 <= self.between_points <= GRID_POINTS:
-                    raise ValueError(f'--between-points {self.between_points}: 1 to {GRID_POINTS} points a step (one flow_at call a slab)')
                 self.between_seed = int(getattr(args, 'between_seed', 0))
                 self._between_gens = {}          # device -> torch.Generator, seeded once per trainer
                 self.between_sample = None       # test hook: (pix, pair, tau, rev) of the last between term
@@ -274,11 +265,8 @@ class FlowTrainer(LightningModule):
         # the smoothness prior at sampled points: off unless the namespace carries a non-zero weight; the attributes exist only then
         self.smooth_at_weight = float(getattr(args, 'loss_smooth_at', 0) or 0)
         if self.smooth_at_weight != 0:
-            flownet._refuse_jacobian(self.net, what='--loss-smooth-at')
             self.loss_smooth_at = self.smooth_at_weight
             self.smooth_points = int(getattr(args, 'smooth_points', None) or 4096)
-            if not 1 <= self.smooth_points <= GRID_POINTS:
-                raise ValueError(f'--smooth-points {self.smooth_points}: 1 to {GRID_POINTS} points a step (one flow_at call)')
             self.smooth_seed = int(getattr(args, 'smooth_seed', 0))
             self._smooth_gens = {}               # device -> torch.Generator of its own: the --between-points draw is unchanged
             self.smooth_sample = None            # test hook: (pair, py, px, poses) of the last term

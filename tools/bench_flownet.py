@@ -23,7 +23,7 @@ weight gradients of all five.  Its 4 * 256 sines per point (and as many cosines 
 layout) instead of a grid; the --baseline is tools/fit_flow.composed_flow_at on the same list.  The FLOP counts are those of N points.
 --points N --spatial R [--pose-grad] calls the StashedSpatialController on the pose list (AT_POINTS | SPATIAL); the --baseline is
 composed_flow_at under the controller's `interpolate` (gather + einsum, (N, 8, 515)) on every call.
---dim 2 builds the network on two coordinates, ModelParams(domain_dim=2) (RBF, FFN, UFF, RBFG and their progressive forms, 514 wide), and
+--dim 2 builds the network on two coordinates, ModelParams(domain_dim=2) (the networks with `pair` in sin_inn_amd/flowcaps.py), and
 times flow_fields(net, None, height, width, .), the call of video-interpolation/pair_flow.py: one frame, no times; the --baseline is
 composed_flow_fields on the same network.  Grids only (no --points, --spatial, --frames).
 """
@@ -73,7 +73,7 @@ def window(fn, seconds, warmup):
 
 
 def main():
-    from sin_inn_amd import _lib, flownet, progressive
+    from sin_inn_amd import _lib, flowcaps, flownet, progressive
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--net', default='RBF', choices=list(flownet.flow_model_dict))
     ap.add_argument('--k-active', type=int, default=515, help='progressive nets: leading open features of the mask (0 .. 515, clamped to the network\'s width: 27 for PPE)')
@@ -105,7 +105,7 @@ def main():
     prog = net.is_progressive
     target = net
     if a.spatial:
-        assert prog and net.encoding_dim == 515, '--spatial needs a 515-wide progressive network'
+        assert flowcaps.TABLE[a.net].spatial is flowcaps.OK, '--spatial needs a 515-wide progressive network'
         assert 6 <= a.k_active <= 515
         target = progressive.StashedSpatialController(net, a.spatial)
         target.mask.zero_()

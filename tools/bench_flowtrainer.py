@@ -49,11 +49,12 @@ for p in (ROOT, os.path.join(ROOT, 'tools')):
         sys.path.insert(0, p)
 
 from bench_flownet import window  # noqa: E402
+from sin_inn_amd import flowcaps  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--net', default='RBF', choices=['RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE'])
+    ap.add_argument('--net', default='RBF', choices=flowcaps.names(cli=True))
     ap.add_argument('--frames', type=int, default=4)
     ap.add_argument('--batch', type=int, default=3)
     ap.add_argument('--height', type=int, default=436)

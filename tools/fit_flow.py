@@ -233,6 +233,12 @@ def cycle_term(query, poses, out):
     return (back[:, 2:] + out[:, :2]).pow(2).mean()
 
 
+def _spatial_only(name, dim=3):
+    from sin_inn_amd import flowcaps
+    if flowcaps.TABLE[name].spatial is not flowcaps.OK or dim != 3:
+        raise ValueError(f'--controller spatial needs a 515-wide progressive network ({", ".join(flowcaps.names("spatial"))}); got {name}')
+
+
 def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, lr=1e-3, seed=0, device='cuda', log=None,
                max_iteration=1000, cycle=False, cycle_weight=1.0, controller='early', res=7, smooth_at=0.0):
     """fit net(poses) to analytic_flow at `n_points` fresh uniform points of [-1, 1]^3 per step (a seeded generator): MSE, FusedAdam.
@@ -250,8 +256,7 @@ def fit_points(name='RBF', n_points=4096, steps=60, composed=False, info=None, l
     assert controller in ('early', 'spatial'), controller
     spatial = controller == 'spatial'
     if spatial:
-        if not net.is_progressive or net.encoding_dim != 515:
-            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, MPFF); got {name}')
+        _spatial_only(name)
         net = progressive.StashedSpatialController(net, res)
     elif net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)
@@ -308,8 +313,7 @@ def fit(net_name='RBF', h=64, w=96, steps=60, lr=1e-3, seed=0, composed=False, d
     assert controller in ('early', 'spatial'), controller
     spatial = controller == 'spatial'
     if spatial:
-        if not net.is_progressive or net.encoding_dim != 515:
-            raise ValueError(f'--controller spatial needs a 515-wide progressive network (PRBF, PFF, PUFF, PRFF, PRBFG, MPFF); got {net_name}')
+        _spatial_only(net_name, dim)
         net = progressive.StashedSpatialController(net, res)
     elif net.is_progressive:
         net = progressive.LinearControllerEarly(net, max_iteration, epsilon=1e-3)

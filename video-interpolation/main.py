@@ -12,9 +12,8 @@ Differences from the reference, all to make the path runnable here:
   * `--holdout S` fits (train) or evaluates (test) on every S-th frame of the clip only (`sin_inn_amd.flowdata.Holdout`); validation
     then logs `val/PSNR` and `val/SSIM` of the synthesized held-out frames in place of `val/EPE`; the attribute exists only when
     the flag is given;
-  * `--net` takes the twelve networks of `sin_inn_amd.flownet`; `siren` and `MPFF` exit with a message (flownet.py lists them as
-    out of scope);
-  * `--spatially-adaptive` puts PRBF, PFF, PUFF, PRFF or PRBFG under `StashedSpatialController(net, 50, block_iterations)`; with any
+  * `--net` takes the networks that the table of sin_inn_amd/flowcaps.py opens (`cli`); the others exit with a message;
+  * `--spatially-adaptive` puts a network with the table's `spatial` under `StashedSpatialController(net, 50, block_iterations)`; with any
     other network it exits with a message.  The reference's own run of this switch fails at the first step (its trainer hands the
     controller a scalar loss) and never calls `update_progress`; here the trainer stashes a per-point loss after every backward pass
     and closes / opens cells every `block_iterations` steps (sin_inn_amd/flowtrainer.py);
@@ -28,9 +27,10 @@ Differences from the reference, all to make the path runnable here:
     sin_inn_amd/flowtrainer.py to the training step; the default 0 leaves the step as it was.  `--between-points N` in
     place of `--between-taus` draws it at N random points a step.
   * `--loss-smooth-at W --smooth-points N` adds the edge-aware smoothness prior on the network's analytic Jacobian at N random points a
-    step (`train/smooth_at`); RBF, FFN, UFF, PRBF, PFF, PUFF without --spatially-adaptive.
+    step (`train/smooth_at`); the networks with the table's `jacobian`, without --spatially-adaptive.
 """
 import argparse
+import importlib.util
 import os
 import os.path as path
 import sys
@@ -40,10 +40,13 @@ ROOT = path.dirname(path.dirname(path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF', 'RFF', 'PRFF', 'RBFG', 'PRBFG', 'PE', 'PPE')
-OUT_OF_SCOPE_NETWORKS = ('siren', 'MPFF')
-JACOBIAN_NETWORKS = ('RBF', 'FFN', 'UFF', 'PRBF', 'PFF', 'PUFF')   # the networks with tangent kernels: --loss-smooth-at
-SPATIAL_NETWORKS = ('PRBF', 'PFF', 'PUFF', 'PRFF', 'PRBFG')    # the 515-wide progressive networks of NETWORKS: --spatially-adaptive
+_spec = importlib.util.spec_from_file_location('flowcaps', path.join(ROOT, 'sin-inn_amd', 'flowcaps.py'))
+flowcaps = importlib.util.module_from_spec(_spec)              # by path: the package around it imports torch, parsing does not
+_spec.loader.exec_module(flowcaps)
+NETWORKS = flowcaps.names(cli=True)                            # the twelve --net opens
+OUT_OF_SCOPE_NETWORKS = flowcaps.names(cli=False)              # siren, MPFF
+JACOBIAN_NETWORKS = flowcaps.names('jacobian', cli=True)       # the networks with tangent kernels: --loss-smooth-at
+SPATIAL_NETWORKS = flowcaps.names('spatial', cli=True)         # the 515-wide progressive networks of NETWORKS: --spatially-adaptive
 
 
 def get_parser():
@@ -107,13 +110,10 @@ def get_args(argv=None):
         args.occl = None
     if getattr(args, 'holdout', 2) < 2:
         parser.error('--holdout S: S >= 2 (every S-th frame is kept)')
-    if hasattr(args, 'between_points'):
-        if hasattr(args, 'between_taus'):
-            parser.error('--between-taus draws whole frames, --between-points sampled points: give one of them')
-        if args.between_points < 1:
-            parser.error('--between-points N: N >= 1')
-    if hasattr(args, 'smooth_points') and args.smooth_points < 1:
-        parser.error('--smooth-points N: N >= 1')
+    try:
+        flowcaps.check_step_options(args)
+    except ValueError as e:
+        parser.error(str(e))
     if getattr(args, 'loss_smooth_at', 0) != 0:
         if args.net not in JACOBIAN_NETWORKS:
             parser.error(f'--loss-smooth-at with --net {args.net} is out of scope: the flow Jacobian is built for '

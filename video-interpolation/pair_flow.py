@@ -13,7 +13,7 @@ ground-truth flow).
 
   --input-video SCENE --index I   frames I, I + 1 of `sin_inn_amd.flowdata.Images(SCENE, --size)`
   --synthetic H W                 frames --index, --index + 1 of `SyntheticClip(max(--index + 2, 3), H, W)`, with its analytic flow
-  --net                           RBF, FFN, UFF, RBFG or their progressive forms PRBF (default), PFF, PUFF, PRBFG
+  --net                           a network with `pair` in the table of sin_inn_amd/flowcaps.py (default PRBF)
   --composed                      the same loop with the network evaluated by torch's own ops (tools/fit_flow.composed_flow_fields)
 
 The network runs in the fused kernels: `flow_fields(net, None, h, w, scale)`, the two-coordinate call of sin_inn_amd.flownet.
@@ -30,7 +30,9 @@ for p in (ROOT, os.path.join(ROOT, 'tools')):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-NETWORKS = ('RBF', 'FFN', 'UFF', 'RBFG', 'PRBF', 'PFF', 'PUFF', 'PRBFG')
+from sin_inn_amd import flowcaps  # noqa: E402
+
+NETWORKS = tuple(sorted(flowcaps.names('pair'), key=lambda name: flowcaps.TABLE[name].progressive))     # the plain ones first
 PARAMS = dict(domain_dim=2, std_rbf=50, std=50)          # pair_flow.py:39
 OCCL_THRESH, LR, EPSILON = 0.7, 1e-3, 1e-3
 
