@@ -1079,6 +1079,19 @@ int sininn_flow_gather(const float* i0, const float* i1, const float* flows, int
                        const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, unsigned char* out_u8,
                        void* stream);
 
+/* The occlusion-aware form of sininn_flow_gather.  Every argument of that call, with its meaning and its checks, and two
+ * visibility planes per pair: m0, m1 DEVICE (B, 1, H, W) fp32, contiguous, 4-byte aligned, not inside out or out_u8.  m0[b] is 1 where
+ * a pixel of i0[b] is visible in i1[b], m1[b] the same for i1[b] in i0[b]; they are read as numbers of any value and nothing is
+ * indexed with them.  With S(X, q) the four taps and weights of W (a tap outside the frame adds 0),
+ *   o0 = S(1 - m0, q0),  o1 = S(1 - m1, q1);   v0 = 1 - o1,  v1 = 1 - o0;   b0 = a0 v0,  b1 = a1 v1
+ *   out = (b0 W0 + b1 W1 + e L) / (b0 n0 + b1 n1 + e)
+ * each operation rounded once: a sample is trusted unless the surface the OTHER sample found is hidden in its frame.  With m0 = m1 = 1
+ * the result has the bits of sininn_flow_gather; where both v are 0 it is L.  One launch, no workspace, no atomics: equal inputs give
+ * equal bits.  It has no gradient. */
+int sininn_flow_gather_visible(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                               const float* tau, const float* m0, const float* m1, int B, int K, int C, int H, int W, int k_loop,
+                               float* out, unsigned char* out_u8, void* stream);
+
 /* The gradient of sininn_flow_gather with respect to `flows`.  i0 .. tau, B .. W as in sininn_flow_gather; grad_out:
  * DEVICE (B, K, C, H, W), contiguous, d loss / d out.  dflows: DEVICE (T, 4, H, W), contiguous, every element written.  At pixel p
  * of row (b, k), with D = a0 n0 + a1 n1 + e and out_c recomputed as the forward pass rounds it,

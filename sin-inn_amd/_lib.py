@@ -334,6 +334,8 @@ _SIGS = {
     'sininn_frame_quality': (C.c_int, [c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), c_f, C.c_int64,
                                        C.c_void_p, c_f, c_f, C.c_void_p]),
     'sininn_flow_gather': (C.c_int, [c_f, c_f, c_f, C.c_int64, C.c_void_p, c_f] + [C.c_int] * 6 + [c_f, C.c_void_p, C.c_void_p]),
+    'sininn_flow_gather_visible': (C.c_int, [c_f, c_f, c_f, C.c_int64, C.c_void_p, c_f, c_f, c_f] + [C.c_int] * 6
+                                   + [c_f, C.c_void_p, C.c_void_p]),
     'sininn_flow_gather_bwd_workspace': (C.c_int64, [C.c_int] * 4),
     'sininn_flow_gather_bwd': (C.c_int, [c_f, c_f, c_f, C.c_int64, C.c_void_p, c_f, c_f] + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_f,
                                          C.c_int64, c_f, C.c_void_p]),

@@ -162,6 +162,9 @@ int frame_quality_launch(const float* pred, const float* target, int B, int C, i
                          float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, hipStream_t st);
 int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
                        const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st);
+int flow_gather_visible_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                               const float* tau, const float* m0, const float* m1, int B, int K, int C, int H, int W, int k_loop,
+                               float* out, uint8_t* out_u8, hipStream_t st);
 int64_t flow_gather_bwd_workspace(int B, int K, int H, int W);
 int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
                            const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
@@ -697,6 +700,13 @@ int sininn_flow_gather(const float* i0, const float* i1, const float* flows, int
                        const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, unsigned char* out_u8,
                        void* stream) {
   return flow_gather_launch(i0, i1, flows, flow_sample_stride, slots, tau, B, K, C, H, W, k_loop, out, out_u8, ST(stream));
+}
+
+int sininn_flow_gather_visible(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                               const float* tau, const float* m0, const float* m1, int B, int K, int C, int H, int W, int k_loop,
+                               float* out, unsigned char* out_u8, void* stream) {
+  return flow_gather_visible_launch(i0, i1, flows, flow_sample_stride, slots, tau, m0, m1, B, K, C, H, W, k_loop, out, out_u8,
+                                    ST(stream));
 }
 
 int64_t sininn_flow_gather_bwd_workspace(int B, int K, int H, int W) { return flow_gather_bwd_workspace(B, K, H, W); }

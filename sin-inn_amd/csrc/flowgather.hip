@@ -10,6 +10,12 @@
 // Each piece of that arithmetic is one helper with its own `fp contract(off)` (the pragma does not reach into a callee), and every
 // kernel is made of them, so they agree to the bit: the grid rule (flowgather_kernel), its gradient with respect to the flows (DESIGN 22:
 // flowgather_bwd_kernel, flowgather_reduce_kernel) and both at a list of points (flowgather_points_kernel, .._bwd_kernel).
+// The occlusion-aware rule (flowgather_kernel<.., VIS = true>) takes two visibility planes per pair, M0 (1 where a pixel of
+// frame 0 is visible in frame 1) and M1 (the same for frame 1 in frame 0), and weighs each sample by what the OTHER sample found:
+//   o0 = S(1 - M0, q0),  o1 = S(1 - M1, q1)                      the taps and weights of W0, W1; a tap outside the frame adds 0
+//   v0 = 1 - o1,  v1 = 1 - o0;   b0 = a0 v0,  b1 = a1 v1
+//   out = (b0 W0 + b1 W1 + e L) / (b0 n0 + b1 n1 + e)
+// With M0 = M1 = 1 every 1 - M is an exact 0, v = 1, b = a: the plain rule's bits.
 #include <type_traits>
 #include "common.h"
 #include "bilinear_taps.h"
@@ -89,11 +95,32 @@ __device__ __forceinline__ float gather_den(float a0, float a1, float n0, float 
   return (a0 * n0 + a1 * n1) + FG_EPS;
 }
 
-__device__ __forceinline__ float gather_blend(float a0, float a1, float den, float w0, float w1, float h0, float h1) {
+// b0, b1 weigh the two samples and (a0, a1) the linear blend L: the same pair in the plain rule, a0 v0 and a1 v1 in the masked one.
+__device__ __forceinline__ float gather_blend_weighted(float a0, float a1, float b0, float b1, float den, float w0, float w1, float h0,
+                                                       float h1) {
 #pragma clang fp contract(off)
   const float lin = a0 * h0 + a1 * h1;
-  const float num = (a0 * w0 + a1 * w1) + FG_EPS * lin;
+  const float num = (b0 * w0 + b1 * w1) + FG_EPS * lin;
   return __fdiv_rn(num, den);
+}
+
+__device__ __forceinline__ float gather_blend(float a0, float a1, float den, float w0, float w1, float h0, float h1) {
+  return gather_blend_weighted(a0, a1, a0, a1, den, w0, w1, h0, h1);
+}
+
+// 1 - M at the four taps of one sample, for o = S(1 - M, q): a tap outside the frame stays 0 and is not read.  The mask is
+// read as a number and nothing is indexed with it.
+__device__ __forceinline__ GatherTapValues gather_hidden(const float* __restrict__ mask, const GatherTaps& t, int W) {
+#pragma clang fp contract(off)
+  const GatherTapValues m = gather_fetch(mask, t, W);
+  return {t.v00 ? 1.f - m.t00 : 0.f, t.v01 ? 1.f - m.t01 : 0.f, t.v10 ? 1.f - m.t10 : 0.f, t.v11 ? 1.f - m.t11 : 0.f};
+}
+
+// The sample weights of the masked rule: frame 0 is trusted unless the surface found in frame 1 is hidden in frame 0, and conversely.
+__device__ __forceinline__ float2 gather_visible_weights(float a0, float a1, float o0, float o1) {
+#pragma clang fp contract(off)
+  const float v0 = 1.f - o1, v1 = 1.f - o0;
+  return {a0 * v0, a1 * v1};
 }
 
 // The gradient with respect to the flows, for one of the two samples (W, n, c, a), `w` and `n` the slopes of W_c and of n:
@@ -137,14 +164,19 @@ __device__ __forceinline__ GatherRow gather_row(const float* __restrict__ flows,
   return row;
 }
 
+// The visibility planes of the masked rule, (B, 1, H, W) each; the plain rule carries none.
+template <bool VIS> struct GatherVisible {};
+template <> struct GatherVisible<true> { const float* m0; const float* m1; };
+
 // KLOOP = false: a block is 256 pixels of one (b, k).  KLOOP = true: a block is 256 pixels of one b and every lane walks k, so I0(p)
-// and I1(p) are loaded once for all K.  The slot row and tau are block-uniform either way.
-template <int C, bool KLOOP>
+// and I1(p) are loaded once for all K.  The slot row and tau are block-uniform either way.  VIS: the masked rule, four more
+// tap values per sample from the pair's mask plane, through the taps the sample has already.
+template <int C, bool KLOOP, bool VIS>
 __global__ __launch_bounds__(FG_THREADS) void flowgather_kernel(const float* __restrict__ i0, const float* __restrict__ i1,
                                                                 const float* __restrict__ flows, int64_t flow_stride,
                                                                 const int* __restrict__ slots, const float* __restrict__ tau, int K,
                                                                 int H, int W, int tiles, float* __restrict__ out,
-                                                                uint8_t* __restrict__ out_u8) {
+                                                                uint8_t* __restrict__ out_u8, GatherVisible<VIS> vis) {
   const int64_t HW = (int64_t)H * W;
   GatherLane p;
   if (!gather_lane(tiles, W, HW, p)) return;
@@ -157,11 +189,19 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_kernel(const float* __r
   auto pixel = [&](int64_t bk, float tk) {                 // one output pixel of frame (b, k)
     const GatherRow row = gather_row(flows, flow_stride, slots + bk * FG_SLOT_INTS, tk, p, H, W, HW);
     const int64_t o = bk * C * HW + r;
+    float b0 = row.a0, b1 = row.a1, den = row.den;
+    if constexpr (VIS) {
+      const float o0 = gather_sample(gather_hidden(vis.m0 + b * HW, row.t0, W), row.t0);
+      const float o1 = gather_sample(gather_hidden(vis.m1 + b * HW, row.t1, W), row.t1);
+      const float2 bw = gather_visible_weights(row.a0, row.a1, o0, o1);
+      b0 = bw.x; b1 = bw.y;
+      den = gather_den(b0, b1, row.t0.n, row.t1.n);
+    }
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const float w0 = gather_sample(gather_fetch(i0b + c * HW, row.t0, W), row.t0);
       const float w1 = gather_sample(gather_fetch(i1b + c * HW, row.t1, W), row.t1);
-      const float v = gather_blend(row.a0, row.a1, row.den, w0, w1, here0[c], here1[c]);
+      const float v = gather_blend_weighted(row.a0, row.a1, b0, b1, den, w0, w1, here0[c], here1[c]);
       out[o + c * HW] = v;
       if (out_u8) out_u8[o + c * HW] = (uint8_t)frame_byte(v);
     }
@@ -187,23 +227,53 @@ static int flow_gather_check(const char* who, const void* i0, const void* i1, co
   return 0;
 }
 
-int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
-                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st) {
-  SININN_CHECK(out, "flow_gather: null pointer");
-  if (flow_gather_check("flow_gather", i0, i1, flows, slots, tau, flow_sample_stride, B, K, C, H, W, C)) return 1;
+template <bool VIS>
+static int flow_gather_run(const char* who, const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride,
+                           const int* slots, const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out,
+                           uint8_t* out_u8, GatherVisible<VIS> vis, hipStream_t st) {
+  SININN_CHECK(out, "%s: null pointer", who);
+  if (flow_gather_check(who, i0, i1, flows, slots, tau, flow_sample_stride, B, K, C, H, W, C)) return 1;
   const int64_t tiles = gather_tiles((int64_t)H * W);
   const dim3 grid((unsigned)((int64_t)B * (k_loop ? 1 : K) * tiles)), block(FG_THREADS);
   gather_per_channels(C, [&](auto ch) {
     constexpr int CH = decltype(ch)::value;
     if (k_loop)
-      hipLaunchKernelGGL((flowgather_kernel<CH, true>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H, W,
-                         (int)tiles, out, out_u8);
+      hipLaunchKernelGGL((flowgather_kernel<CH, true, VIS>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H,
+                         W, (int)tiles, out, out_u8, vis);
     else
-      hipLaunchKernelGGL((flowgather_kernel<CH, false>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H, W,
-                         (int)tiles, out, out_u8);
+      hipLaunchKernelGGL((flowgather_kernel<CH, false, VIS>), grid, block, 0, st, i0, i1, flows, flow_sample_stride, slots, tau, K, H,
+                         W, (int)tiles, out, out_u8, vis);
   });
-  SININN_LAUNCH_CHECK("flowgather");
+  SININN_LAUNCH_CHECK(VIS ? "flowgather_visible" : "flowgather");
   return 0;
+}
+
+int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st) {
+  return flow_gather_run<false>("flow_gather", i0, i1, flows, flow_sample_stride, slots, tau, B, K, C, H, W, k_loop, out, out_u8, {}, st);
+}
+
+// [p, p + n) and [q, q + m) in bytes share nothing
+static bool gather_apart(const void* p, int64_t n, const void* q, int64_t m) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a + (uintptr_t)n <= b || b + (uintptr_t)m <= a;
+}
+
+// The masked rule: the plain call's checks, then the masks -- present, readable as floats, and not inside what is written.
+int flow_gather_visible_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                               const float* tau, const float* m0, const float* m1, int B, int K, int C, int H, int W, int k_loop,
+                               float* out, uint8_t* out_u8, hipStream_t st) {
+  const char* who = "flow_gather_visible";
+  SININN_CHECK(m0 && m1, "%s: a visibility mask is null", who);
+  SININN_CHECK(((uintptr_t)m0 & 3) == 0 && ((uintptr_t)m1 & 3) == 0, "%s: the masks are fp32 planes and must be 4-byte aligned", who);
+  SININN_CHECK(out, "%s: null pointer", who);
+  if (flow_gather_check(who, i0, i1, flows, slots, tau, flow_sample_stride, B, K, C, H, W, C)) return 1;
+  const int64_t HW = (int64_t)H * W, mask_bytes = 4 * (int64_t)B * HW, frames = (int64_t)B * K * C * HW;
+  SININN_CHECK(gather_apart(m0, mask_bytes, out, 4 * frames) && gather_apart(m1, mask_bytes, out, 4 * frames) &&
+                   (!out_u8 || (gather_apart(m0, mask_bytes, out_u8, frames) && gather_apart(m1, mask_bytes, out_u8, frames))),
+               "%s: a mask of B * H * W = %lld floats overlaps the output", who, (long long)B * HW);
+  return flow_gather_run<true>(who, i0, i1, flows, flow_sample_stride, slots, tau, B, K, C, H, W, k_loop, out, out_u8,
+                               GatherVisible<true>{m0, m1}, st);
 }
 
 // ---- the gradient with respect to the flows ----

@@ -5,6 +5,7 @@ clip with analytic ground truth, and the data module that hands them to the trai
     BaseMedia / Images         video-interpolation/data.py:10-18, 67-89
     LightningLoader / get_video   video-interpolation/data.py:92-119   (num_workers=0: the clips are resident tensors)
     SyntheticClip              this project's; generalises tools/fit_flow.make_pair to a clip
+    LayeredClip                this project's; two textured layers with constant velocities: real occlusion, analytic flows and masks
     Holdout                    this project's; every step-th frame of a clip, the frames between them kept back for scoring
 
 Everything here runs on the host; the trainer moves batches to the device.
@@ -170,6 +171,74 @@ class SyntheticClip(BaseMedia):
         self.flow_scale = w / 5
 
 
+class LayeredClip(BaseMedia):
+    """`frames` frames of h x w with real occlusion and analytic ground truth, the interface of `Images`: two layers
+    with constant velocities `bg`, `fg` = (vx, vy) in pixels per frame.
+
+    The background is the plane texture(.., seed) and fills the frame; the foreground is an axis-aligned rectangle of
+    (h // 3) x (w // 3) pixels textured with texture(.., seed + 1), placed so that it stays inside the frame for the whole clip (in the
+    middle of the positions that allow it, on a half-integer corner).  Its edge is hard: at the frame time s -- any real number, the
+    frames of `video` sit at s = 0 .. frames - 1 -- the pixel (x, y) shows the foreground where its centre lies inside the rectangle,
+    x0 + s vx <= x < x0 + s vx + rw and likewise in y, and the background elsewhere.  Each layer shows its texture at the pixel's
+    position minus s times the layer's velocity.  Everything is evaluated in float64; `video` and `flow` are its fp32 roundings.
+
+        frame_at(s)             the frame at time s, (3, h, w) float64;  sample_at(s, x, y): the same content at any coordinates
+        flow_between(s, s2)     (2, h, w) float64 on the grid at s: the velocity of the layer each pixel shows, times s2 - s
+        visible(i, j)           (h, w) bool: the pixels of the frame at i whose surface the frame at j still shows -- every foreground
+                                pixel, and a background pixel unless the rectangle covers its position at time j.  Leaving the
+                                frame is not counted: a sampler sees that from its taps
+
+    `flow[i]` is flow_between(i, i + 1), the ground truth of pair i."""
+
+    def __init__(self, frames, h, w, seed=0, bg=(3.0, 0.0), fg=(-2.0, 1.5)):
+        super().__init__()
+        assert frames >= 2 and h >= 8 and w >= 8, 'LayeredClip: at least 2 frames of 8 x 8'
+        self.h, self.w, self.seed = h, w, seed
+        self.bg, self.fg = (float(bg[0]), float(bg[1])), (float(fg[0]), float(fg[1]))
+        self.rh, self.rw = h // 3, w // 3
+        last = frames - 1
+
+        def start(size, length, v):
+            lo, hi = -min(0.0, last * v), size - length - max(0.0, last * v)      # the corner positions that keep the rectangle inside
+            if lo > hi:
+                raise ValueError(f'LayeredClip: a foreground of {length} pixels moving {v} a frame leaves a frame of {size} within '
+                                 f'{frames} frames')
+            return min(max(math.floor((lo + hi) / 2) + 0.5, lo), hi)
+
+        self.x0, self.y0 = start(w, self.rw, self.fg[0]), start(h, self.rh, self.fg[1])
+        self.yy, self.xx = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing='ij')
+        self.video = torch.stack([self.frame_at(i) for i in range(frames)]).to(torch.float32)
+        self.flow = torch.stack([self.flow_between(i, i + 1) for i in range(frames - 1)]).to(torch.float32)
+        self.T = torch.linspace(-1, 1, frames)
+        self.gt_available = True
+        self.flow_scale = w / 5
+
+    def covered(self, s, x, y):
+        """where the rectangle at time s covers the points (x, y) (float64, any shape)"""
+        left, top = self.x0 + s * self.fg[0], self.y0 + s * self.fg[1]
+        return (x >= left) & (x < left + self.rw) & (y >= top) & (y < top + self.rh)
+
+    def sample_at(self, s, x, y):
+        """the clip's content at time s at the points (x, y), two-dimensional float64 tensors of any values: (3, ..) float64"""
+        back = texture(x - s * self.bg[0], y - s * self.bg[1], self.seed)
+        front = texture(x - s * self.fg[0], y - s * self.fg[1], self.seed + 1)
+        return torch.where(self.covered(s, x, y)[None], front, back)
+
+    def frame_at(self, s):
+        return self.sample_at(float(s), self.xx, self.yy)
+
+    def flow_between(self, s, s2):
+        front = self.covered(float(s), self.xx, self.yy)
+        vx = torch.where(front, torch.full_like(self.xx, self.fg[0]), torch.full_like(self.xx, self.bg[0]))
+        vy = torch.where(front, torch.full_like(self.xx, self.fg[1]), torch.full_like(self.xx, self.bg[1]))
+        return torch.stack((vx, vy)) * (float(s2) - float(s))
+
+    def visible(self, i, j):
+        i, j = float(i), float(j)
+        back = ~self.covered(i, self.xx, self.yy)
+        return ~(back & self.covered(j, self.xx + (j - i) * self.bg[0], self.yy + (j - i) * self.bg[1]))
+
+
 class Holdout(BaseMedia):
     """Every `step`-th frame of `base` (an `Images` or a `SyntheticClip`) as a clip of its own, the frames between them held out: fit
     on this, synthesize the held-out frames, compare them with the real ones (`FlowTrainer.holdout_quality`).
@@ -247,13 +316,17 @@ class HoldoutLoader(LightningLoader):
 
 
 def get_video(input_video, args):
-    """data.py:107-119: (data module, scene name).  `args.synthetic = (frames, h, w)` selects a SyntheticClip, scene 'synthetic';
-    a file (the reference's VideoClip) is refused.  `args.holdout = S` (main.py --holdout) wraps both sets in `Holdout(.., S)`."""
-    synthetic = getattr(args, 'synthetic', None)
+    """data.py:107-119: (data module, scene name).  `args.synthetic = (frames, h, w)` selects a SyntheticClip, scene 'synthetic',
+    `args.layered = (frames, h, w)` a LayeredClip, scene 'layered'; a file (the reference's VideoClip) is refused.  `args.holdout = S` (main.py --holdout) wraps both sets in `Holdout(.., S)`."""
+    synthetic, layered = getattr(args, 'synthetic', None), getattr(args, 'layered', None)
     if synthetic:
         frames, h, w = synthetic
         trainset = testset = SyntheticClip(frames, h, w)
         scene = 'synthetic'
+    elif layered:
+        frames, h, w = layered
+        trainset = testset = LayeredClip(frames, h, w)
+        scene = 'layered'
     elif path.isdir(input_video):
         trainset = Images(input_video, size=args.size)
         testset = Images(input_video, size=args.test_size)

@@ -44,6 +44,16 @@ grad_q is the derivative of the bilinear interpolant of the zero-padded plane in
 derivative, what autograd gives through `gather_from`); a sample whose coordinate is not finite, or 1e9 or more in size, has gradient 0.
 Rows that name the same slice and channel pair are summed in ascending b K + k, dG0 before dG1, without atomics.
 
+    gather(.., visible=(m1, m2)), gather_composed(.., visible=(m1, m2))    the occlusion-aware rule
+
+m1 is 1 where a pixel of frame 1 is visible in frame 2, m2 the same for frame 2 in frame 1 (the trainer's mask1, mask2).  With
+S(X, q) the taps and weights of W (a tap outside the frame adds 0):
+
+    o0 = S(1 - m1, q0), o1 = S(1 - m2, q1);   v0 = 1 - o1, v1 = 1 - o0;   out = (a0 v0 W0 + a1 v1 W1 + e L) / (a0 v0 n0 + a1 v1 n1 + e)
+
+A sample is trusted unless the surface the other sample found is hidden in its frame.  All-ones masks give the plain rule's bits; where
+both v are 0 the result is L.  One launch; no gradient, and not at a point list.
+
     quality(pred, target)            PSNR and mean SSIM per frame, the fused operator of csrc/framequality.hip
     quality_composed(pred, target)   the same definition from torch ops, on any device, fp32 or fp64: its A/B partner and reference
 
@@ -353,15 +363,35 @@ class _GatherFlowGrad(torch.autograd.Function):
         return (dflows,) + (None,) * 7
 
 
-def gather(frame1, frame2, flows, slots, taus, *, out=None, u8=False, k_loop=None, flow_grad=False):
+def _visible_masks(who, visible, b, h, w, flow_grad):
+    """the two masks of `visible=(m1, m2)`, checked: (B, 1, H, W) each, no gradient, and not together with flow_grad=True"""
+    if flow_grad:
+        raise ValueError(f'flowsynth.{who}: the masked rule (visible=) has no gradient yet: flow_grad=True is the plain rule\'s')
+    if not isinstance(visible, (tuple, list)) or len(visible) != 2 or not all(torch.is_tensor(m) for m in visible):
+        raise ValueError(f'flowsynth.{who}: visible is a pair of masks (m1, m2), what the trainer calls mask1 and mask2')
+    for m in visible:
+        if tuple(m.shape) != (b, 1, h, w):
+            raise ValueError(f'flowsynth.{who}: a visibility mask is ({b}, 1, {h}, {w}), one plane per pair; got {tuple(m.shape)}')
+    _refuse_grad(who, visible)
+    return visible
+
+
+def gather(frame1, frame2, flows, slots, taus, *, visible=None, out=None, u8=False, k_loop=None, flow_grad=False):
     """The frames at `taus` between frame1 and frame2 from flows taken at the in-between times: (B, K, C, H, W) fp32, and with u8=True
     also the bytes, by `synthesize`'s rule.  `flows`: (T', 4, H, W) fp32 on the device, read in place -- any stride between time slices,
     the four channel planes of a slice contiguous.  `slots`: the host table of `gather_slots` (validated and uploaded here), or what
     `upload_slots` made of it.  `k_loop`: the launch shape (None: `K_LOOP`); both give the same bits.  One launch, no workspace.
 
     `flow_grad=True`: where `flows` requires grad the result carries a gradient to it (see the module text); `slots` is then the host
-    table (the backward pass builds its reduce list from it), and `u8` and `out=` are not supported."""
+    table (the backward pass builds its reduce list from it), and `u8` and `out=` are not supported.
+
+    `visible=(m1, m2)`: the occlusion-aware rule.  m1 (B, 1, H, W) is 1 where a pixel of frame1 is visible in frame2, m2 the
+    same for frame2 in frame1 -- the trainer's mask1 and mask2; any float or bool values, read as fp32 numbers.  Each sample is weighed
+    by 1 - S(1 - m, q) of the OTHER sample: b0 = a0 (1 - S(1 - m2, q1)), b1 = a1 (1 - S(1 - m1, q0)),
+    out = (b0 W0 + b1 W1 + e L) / (b0 n0 + b1 n1 + e).  All-ones masks give the plain rule's bits.  Still one launch; no gradient."""
     b, c, h, w = _gather_inputs('gather', frame1, frame2, flows, flow_grad)
+    if visible is not None:
+        visible = _visible_masks('gather', visible, b, h, w, flow_grad)
     if flow_grad and (u8 or out is not None):
         raise ValueError('flowsynth.gather: flow_grad=True with u8=True or out= is not supported (bytes carry no gradient, and autograd '
                          'owns the result)')
@@ -391,9 +421,13 @@ def gather(frame1, frame2, flows, slots, taus, *, out=None, u8=False, k_loop=Non
         out = torch.empty((b, k, c, h, w), device=dev, dtype=torch.float32)
     assert tuple(out.shape) == (b, k, c, h, w) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
     bytes_ = torch.empty((b, k, c, h, w), device=dev, dtype=torch.uint8) if u8 else None
-    check(_lib.lib().sininn_flow_gather(ptr(frame1), ptr(frame2), ptr(data), stride, C.c_void_p(table.data_ptr()), ptr(tau), b, k, c,
-                                        h, w, int(K_LOOP if k_loop is None else k_loop), ptr(out),
-                                        C.c_void_p(bytes_.data_ptr()) if u8 else None, _stream()))
+    tail = (b, k, c, h, w, int(K_LOOP if k_loop is None else k_loop), ptr(out), C.c_void_p(bytes_.data_ptr()) if u8 else None, _stream())
+    if visible is None:
+        check(_lib.lib().sininn_flow_gather(ptr(frame1), ptr(frame2), ptr(data), stride, C.c_void_p(table.data_ptr()), ptr(tau), *tail))
+    else:
+        m1, m2 = (_gpu32(m.to(torch.float32)).contiguous() for m in visible)
+        check(_lib.lib().sininn_flow_gather_visible(ptr(frame1), ptr(frame2), ptr(data), stride, C.c_void_p(table.data_ptr()), ptr(tau),
+                                                    ptr(m1), ptr(m2), *tail))
     return (out, bytes_) if u8 else out
 
 
@@ -432,18 +466,21 @@ def bilinear_gather(img, qx, qy):
     return _tap_walk(qx, qy, h, w, term)
 
 
-def _blend(a0, a1, w0, w1, n0, n1, h0, h1, eps, axis):
-    """out = (a0 W0 + a1 W1 + eps (a0 h0 + a1 h1)) / (a0 n0 + a1 n1 + eps): W and h carry the channels at `axis`, a and n have no such
-    axis"""
+def _blend(a0, a1, w0, w1, n0, n1, h0, h1, eps, axis, weights=None):
+    """out = (b0 W0 + b1 W1 + eps (a0 h0 + a1 h1)) / (b0 n0 + b1 n1 + eps): W and h carry the channels at `axis`, a, b and n have no
+    such axis.  `weights`: (b0, b1), the sample weights of the masked rule; None: b = a, the plain rule"""
+    b0, b1 = (a0, a1) if weights is None else weights
     c0, c1 = a0.unsqueeze(axis), a1.unsqueeze(axis)
-    num = (c0 * w0 + c1 * w1) + eps * (c0 * h0 + c1 * h1)
-    den = (a0 * n0 + a1 * n1) + eps
+    d0, d1 = b0.unsqueeze(axis), b1.unsqueeze(axis)
+    num = (d0 * w0 + d1 * w1) + eps * (c0 * h0 + c1 * h1)
+    den = (b0 * n0 + b1 * n1) + eps
     return num / den.unsqueeze(axis)
 
 
-def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, eps=GATHER_EPS):
+def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, eps=GATHER_EPS, visible=None):
     """The definition, operation by operation, in the dtype and on the device of the frames.  `sample` and `eps` are the two places a
-    test swaps in something else (another geometry, no renormalisation, no guard)."""
+    test swaps in something else (another geometry, no renormalisation, no guard).  `visible=(m1, m2)`: the masked rule --
+    o = sample(1 - m, q) through the sample's own coordinates, v0 = 1 - o1, v1 = 1 - o0, the sample weights b = a v."""
     b, c, h, w = frame1.shape
     dt, dev = frame1.dtype, frame1.device
     flows = flows.to(device=dev, dtype=dt)
@@ -453,20 +490,30 @@ def gather_from(frame1, frame2, flows, slots, values, sample=bilinear_gather, ep
     ys, xs = torch.meshgrid(torch.arange(h, device=dev, dtype=dt), torch.arange(w, device=dev, dtype=dt), indexing='ij')
     pair = torch.arange(2, device=dev)
 
-    def warped(img, which):
+    def warped(img, which, hidden=None):
         g = flows[idx[:, :, which, None], idx[:, :, 2 + which, None] + pair]                  # (B, K, 2, H, W)
         cf = coef[:, :, which, None, None]
-        return sample(img, xs + cf * g[:, :, 0], ys + cf * g[:, :, 1])
+        qx, qy = xs + cf * g[:, :, 0], ys + cf * g[:, :, 1]
+        got = sample(img, qx, qy)
+        return got if hidden is None else (*got, sample(hidden, qx, qy)[0][:, :, 0])       # (W, n) and o = S(1 - m, q)
 
-    (w0, n0), (w1, n1) = warped(frame1, 0), warped(frame2, 1)
-    return _blend(1 - a1, a1, w0, w1, n0, n1, frame1[:, None], frame2[:, None], eps, 2)
+    a0 = 1 - a1
+    if visible is None:
+        (w0, n0), (w1, n1) = warped(frame1, 0), warped(frame2, 1)
+        return _blend(a0, a1, w0, w1, n0, n1, frame1[:, None], frame2[:, None], eps, 2)
+    m1, m2 = (m.to(device=dev, dtype=dt) for m in visible)
+    (w0, n0, o0), (w1, n1, o1) = warped(frame1, 0, 1 - m1), warped(frame2, 1, 1 - m2)
+    return _blend(a0, a1, w0, w1, n0, n1, frame1[:, None], frame2[:, None], eps, 2, weights=(a0 * (1 - o1), a1 * (1 - o0)))
 
 
-def gather_composed(frame1, frame2, flows, slots, taus, *, flow_grad=False):
+def gather_composed(frame1, frame2, flows, slots, taus, *, visible=None, flow_grad=False):
     """`gather` from torch ops, on the device and in the dtype of the frames (CPU or GPU, fp32 or fp64): index arithmetic and
     `torch.gather` for the taps, a few dozen launches.  `slots` is the host table.  In fp32 it rounds where the fused operator rounds.
-    `flow_grad=True`: where `flows` requires grad, `gather_from` runs with autograd on and the result carries a gradient to `flows`."""
+    `flow_grad=True`: where `flows` requires grad, `gather_from` runs with autograd on and the result carries a gradient to `flows`.
+    `visible=(m1, m2)`: the masked rule, as `gather` takes it; the masks are converted to the dtype of the frames."""
     b, c, h, w = _gather_inputs('gather_composed', frame1, frame2, flows, flow_grad)
+    if visible is not None:
+        visible = _visible_masks('gather_composed', visible, b, h, w, flow_grad)
     values = _host_taus(taus)
     need = _host_slots('gather_composed', slots, b, len(values))
     if need > flows.shape[0]:
@@ -475,7 +522,7 @@ def gather_composed(frame1, frame2, flows, slots, taus, *, flow_grad=False):
     if flow_grad and flows.requires_grad and torch.is_grad_enabled():
         return gather_from(frame1.detach(), frame2.detach(), flows, slots, values)
     with torch.no_grad():
-        return gather_from(frame1.detach(), frame2.detach(), flows.detach(), slots, values)
+        return gather_from(frame1.detach(), frame2.detach(), flows.detach(), slots, values, visible=visible)
 
 
 # ---- the gather rule at a list of points ----

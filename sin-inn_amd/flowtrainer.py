@@ -576,7 +576,13 @@ class FlowTrainer(LightningModule):
             self.logger.log_metrics({'test/EPE': epe, 'epoch': self.current_epoch}, getattr(self.trainer, 'global_step', 0))
         return epe
 
-    def interpolate(self, batch, taus, synthesis='splat', dt=None, back='network', **kw):
+    def visibility_masks(self, flow12, flow21, occlusion):
+        """(mask1, mask2) of the step (`losses`) before the splat masks, from the flows at the frame times: `occlusion` is 'wang' or
+        'brox', the operators of `flowloss`, with the trainer's `occl_thresh`"""
+        op = {'wang': FL.occlusion_wang, 'brox': FL.occlusion_brox}[occlusion]
+        return op(flow12, flow21, self.args.occl_thresh), op(flow21, flow12, self.args.occl_thresh)
+
+    def interpolate(self, batch, taus, synthesis='splat', dt=None, back='network', occlusion=None, **kw):
         """The frames at `taus` in [0, 1] between frame1 and frame2 of `batch` (frame1, frame2, times, scale, ...), (n, K, 3, h, w):
         the network's two flows at the batch's time stamps, then `flowsynth.synthesize` (its keywords pass through).  No gradient;
         the network is evaluated in eval() and left in the mode it was found in.
@@ -584,11 +590,19 @@ class FlowTrainer(LightningModule):
         synthesis='gather' (DESIGN 19): the network is asked for its flows at the in-between times themselves -- one `flow_fields`
         call at the stamps of `flowsynth.gather_slots(times, taus, dt, back)`; several, joined, where the stamps times h w exceed
         the 2^22 points one call takes -- and `flowsynth.gather` reads both frames through them (its keywords pass through).  `dt`: the spacing of the clip's times, 2 / (frames - 1); back='reverse' evaluates half the stamps
-        and uses the negated forward flow for the previous frame."""
+        and uses the negated forward flow for the previous frame.
+
+        occlusion='wang' | 'brox' (synthesis='gather' only): the occlusion-aware rule.  The network's two flows at the
+        batch's time stamps -- what the splat path evaluates -- give the step's mask1 and mask2 (`visibility_masks`), and `gather`
+        takes them as `visible=(mask1, mask2)`."""
         from . import flowsynth
         frame1, frame2, times, scale = batch[:4]
         if synthesis not in ('splat', 'gather'):
             raise ValueError(f"interpolate: synthesis is 'splat' or 'gather', got {synthesis!r}")
+        if occlusion not in (None, 'wang', 'brox'):
+            raise ValueError(f"interpolate: occlusion is None, 'wang' or 'brox', got {occlusion!r}")
+        if occlusion is not None and synthesis != 'gather':
+            raise ValueError("interpolate: occlusion= is the masked gather rule and needs synthesis='gather'")
         if synthesis == 'gather':
             if dt is None:
                 raise ValueError("interpolate: synthesis='gather' evaluates the network between the frames and needs dt, the spacing "
@@ -608,24 +622,27 @@ class FlowTrainer(LightningModule):
                     per = max(1, GRID_POINTS // (frame1.shape[-2] * frame1.shape[-1]))
                     parts = [flowsynth.joined_flows(*self.forward(frame1, at[i:i + per], scale)) for i in range(0, len(stamps), per)]
                     flows = parts[0] if len(parts) == 1 else torch.cat(parts)
+                    if occlusion is not None:
+                        kw = dict(kw, visible=self.visibility_masks(*self.forward(frame1, times, scale), occlusion))
                     return flowsynth.gather(frame1, frame2, flows, slots, taus, **kw)
                 flow12, flow21 = self.forward(frame1, times, scale)
                 return flowsynth.synthesize(frame1, frame2, flow12, flow21, taus, **kw)
         finally:
             self.net.train(was_training)
 
-    def holdout_quality(self, batch, held, taus, quantize=True, frames=None, synthesis='splat', dt=None, back='network'):
+    def holdout_quality(self, batch, held, taus, quantize=True, frames=None, synthesis='splat', dt=None, back='network',
+                        occlusion=None):
         """Score the frames synthesized at `taus` between the pair of `batch` against the real frames `held` (n, K, 3, h, w): a dict of
         `flowsynth.Quality`, each entry (n, K) -- 'net': `interpolate(batch, taus)`; and, through the same operator, the two
         baselines that use no flow, 'blend': (1 - tau) frame1 + tau frame2, and 'repeat': the nearer source frame (frame1 up to
         tau = 0.5).  `quantize=True` measures all three as bytes, as the written PNGs hold them.  `frames`: what `interpolate(batch, taus)`
         returned, for a caller that has it already (the splat adds with atomics: a second call may differ in the last bits).
-        `synthesis`, `dt`, `back`: how 'net' is synthesized where `frames` is None, as `interpolate` takes them."""
+        `synthesis`, `dt`, `back`, `occlusion`: how 'net' is synthesized where `frames` is None, as `interpolate` takes them."""
         from . import flowsynth
         frame1, frame2 = batch[0], batch[1]
         values = flowsynth._host_taus(taus)
         with torch.no_grad():
-            net = self.interpolate(batch, values, synthesis=synthesis, dt=dt, back=back) if frames is None else frames
+            net = self.interpolate(batch, values, synthesis=synthesis, dt=dt, back=back, occlusion=occlusion) if frames is None else frames
             tau = torch.tensor(values, dtype=frame1.dtype, device=frame1.device).view(1, -1, 1, 1, 1)
             blend = (1 - tau) * frame1[:, None] + tau * frame2[:, None]
             repeat = torch.where(tau <= 0.5, frame1[:, None], frame2[:, None])

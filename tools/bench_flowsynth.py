@@ -23,6 +23,11 @@ repeated over the slot table's time slices (the operator's time does not depend 
 Then one `flowgather_interpolate` line per K: the whole `FlowTrainer.interpolate` call -- network evaluations included, an unfitted
 --net under its controller -- for splat, gather/network and gather/reverse.
 
+    python tools/bench_flowsynth.py --gather --visible [--baseline] [--build NAME]
+
+times the occlusion-aware rule `flowsynth.gather(.., visible=)` against the plain call in alternating windows, one
+`flowgather_visible` line per K with `visible_over_plain`, the number to report; with --baseline also `gather_composed(.., visible=)`.
+
     python tools/bench_flowsynth.py --gather-at N [--baseline]
 
 times forward plus backward of the point form `flowsynth.gather_at(.., blend=(0, 1), flow_grad=True)` at N random points of
@@ -153,6 +158,49 @@ def gather_lines(a, dev):
     return lines
 
 
+def gather_visible_lines(a, dev):
+    """the masked rule `gather(.., visible=)` against the plain call and (with --baseline) against `gather_composed(.., visible=)`
+    (DESIGN 26), K = 1 and factor - 1, in alternating windows of one session.  The masks are hard 0 / 1 planes with a hidden band of
+    width // 16 columns; min_bytes counts them as the 2 (4 taps, one cache line or two) planes more that a (b, k) lane reads."""
+    from sin_inn_amd import flowdata, flowsynth
+    clip = flowdata.SyntheticClip(a.batch + 1, a.height, a.width)
+    i0, i1 = clip.video[:-1].contiguous().to(dev), clip.video[1:].contiguous().to(dev)
+    f01, f10 = clip.flow.contiguous().to(dev), (-clip.flow).contiguous().to(dev)
+    dt, times = 2 / a.batch, clip.T[:-1]
+    m0 = torch.ones(a.batch, 1, a.height, a.width, device=dev)
+    m1 = torch.ones(a.batch, 1, a.height, a.width, device=dev)
+    m0[..., a.width // 4:a.width // 4 + a.width // 16] = 0
+    m1[..., a.width // 2:a.width // 2 + a.width // 16] = 0
+    lines = []
+    for k in sorted({1, a.factor - 1}):
+        taus = [0.5] if k == 1 else [j / a.factor for j in range(1, a.factor)]
+        tau_dev = torch.tensor(taus, dtype=torch.float32, device=dev)
+        stamps, slots = flowsynth.gather_slots(times, taus, dt)
+        per_b = len(stamps) // a.batch + 1
+        flows = torch.cat([f01, f10], 1).repeat_interleave(per_b, 0)[:len(stamps)].contiguous()
+        table = flowsynth.upload_slots(slots, dev)
+        out = torch.empty(a.batch, k, 3, a.height, a.width, device=dev)
+        todo = {'plain': lambda: flowsynth.gather(i0, i1, flows, table, tau_dev, out=out),
+                'visible': lambda: flowsynth.gather(i0, i1, flows, table, tau_dev, out=out, visible=(m0, m1))}
+        if a.baseline:
+            todo['composed'] = lambda: flowsynth.gather_composed(i0, i1, flows, slots, taus, visible=(m0, m1))
+        pixels = a.batch * a.height * a.width
+        line = dict(op='flowgather_visible', height=a.height, width=a.width, batch=a.batch, K=k, slices=len(stamps),
+                    min_bytes_plain=4 * pixels * k * (4 + 6 + 3), min_bytes_visible=4 * pixels * k * (4 + 6 + 3 + 2))
+        for name, (best, meds) in _timed(todo, a).items():
+            line[f'{name}_ms'], line[f'{name}_ms_windows'] = best, meds
+        line['visible_over_plain'] = round(line['visible_ms'] / line['plain_ms'], 3)
+        line['visible_tb_per_s'] = round(line['min_bytes_visible'] / (line['visible_ms'] * 1e-3) / 1e12, 3)
+        if a.baseline:
+            line['composed_over_fused'] = round(line['composed_ms'] / line['visible_ms'], 3)
+            line['max_abs_diff_composed'] = float((flowsynth.gather(i0, i1, flows, table, tau_dev, visible=(m0, m1))
+                                                   - flowsynth.gather_composed(i0, i1, flows, slots, taus, visible=(m0, m1))).abs().max())
+        line['build'] = a.build
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
+
+
 def gather_grad_lines(a, dev):
     """forward plus backward of gather(.., flow_grad=True) against the autograd of gather_composed on the device, K = 1
     and factor - 1, on the regular table of gather_slots (reverse rows for the clip's first pair: the two-launch backward path)"""
@@ -255,13 +303,16 @@ def main():
                     help='time forward plus backward of flowsynth.gather(.., flow_grad=True) (and with --baseline the autograd of gather_composed) instead (DESIGN 22)')
     ap.add_argument('--gather-at', type=int, metavar='N',
                     help='time forward plus backward of flowsynth.gather_at at N points (and with --baseline the autograd of gather_at_composed) instead (DESIGN 23)')
+    ap.add_argument('--visible', action='store_true',
+                    help='--gather: time the masked rule gather(.., visible=) against the plain call (and with --baseline gather_composed(.., visible=)) instead (DESIGN 26)')
+    ap.add_argument('--build', default='tree', help='--visible: what the `build` field of the lines says')
     ap.add_argument('--net', default='PRBF', help='--gather: the network of the whole-call lines')
     a = ap.parse_args()
     assert 2 <= a.factor <= 65
     dev = torch.device('cuda', 0)
     if a.quality or a.gather or a.gather_grad or a.gather_at:
-        lines = (gather_at_lines(a, dev) if a.gather_at else gather_grad_lines(a, dev) if a.gather_grad else gather_lines(a, dev)
-                 if a.gather else quality_lines(a, dev))
+        lines = (gather_at_lines(a, dev) if a.gather_at else gather_grad_lines(a, dev) if a.gather_grad else gather_visible_lines(a, dev)
+                 if a.gather and a.visible else gather_lines(a, dev) if a.gather else quality_lines(a, dev))
         for line in ([] if a.gather or a.gather_grad or a.gather_at else lines):   # the gather lines are printed as they are measured
             print(json.dumps(line))
         if a.log:

@@ -3,6 +3,7 @@
     python video-interpolation/interpolate.py --input-video <sintel scene folder> --name NAME --net PRBF --factor 8
     python video-interpolation/interpolate.py --synthetic 4 24 40 --name smoke --net RBF --fit-epochs 2 --factor 3 --out frames
     python video-interpolation/interpolate.py --synthetic 9 24 40 --name smoke --net RBF --fit-epochs 2 --holdout 2
+    python video-interpolation/interpolate.py --layered 9 96 160 --name occl --net RBF --fit-epochs 300 --holdout 2 --synthesis gather --occlusion wang
 
 The network is the one `main.py train --name NAME --net NET` fitted to the clip: the newest checkpoint under
 checkpoints/<scene>/<NAME> is loaded as `main.py test` loads it (same folder, same tie-break).  For pair i of the clip and
@@ -11,7 +12,8 @@ itself, written from the data, the others come from `FlowTrainer.interpolate` (s
 frames along the pair's two flows, blended; one call per batch of pairs, whatever the factor).  After the last pair the last
 source frame is written as frame_<T:04d>_00.png.
 
-  --input-video DIR | --synthetic T H W   the clip: an `Images` folder, or a `SyntheticClip` of T frames of H x W
+  --input-video DIR | --synthetic T H W | --layered T H W   the clip: an `Images` folder, a `SyntheticClip` of T frames of H x W, or a
+                   `LayeredClip` of that size (two moving layers: real occlusion)
   --factor F       F - 1 new frames per pair (default 2)
   --size S         --input-video: the shorter side of the frames (default 436)
   --out DIR        where the PNGs go (default results/interp_<scene>_<name>_x<factor>)
@@ -27,6 +29,8 @@ source frame is written as frame_<T:04d>_00.png.
                    The files written and quality.jsonl keep their format; the last line of quality.jsonl names the synthesis
   --back B         --synthesis gather: network (default) takes the flow toward the previous frame from the network at s - dt;
                    reverse uses the negated forward flow at s and evaluates half the time stamps
+  --occlusion O    --synthesis gather only: wang or brox, the occlusion-aware gather rule with the trainer's masks of that
+                   operator, computed from the network's flows at the frame times; the last line of quality.jsonl names it
 """
 import argparse
 import importlib.util
@@ -52,6 +56,7 @@ def get_parser():
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument('--input-video', help='an Images scene folder (frame_0001.png ..)')
     src.add_argument('--synthetic', nargs=3, type=int, metavar=('T', 'H', 'W'), help='a SyntheticClip of T frames of H x W')
+    src.add_argument('--layered', nargs=3, type=int, metavar=('T', 'H', 'W'), help='a LayeredClip of T frames of H x W (occlusion)')
     ap.add_argument('--name', required=True, help='the run whose newest checkpoint is loaded')
     ap.add_argument('--net', required=True, help='the network of that run (main.py --net)')
     ap.add_argument('--factor', type=int, help='time steps per pair: factor - 1 new frames between two source frames (default 2)')
@@ -64,6 +69,8 @@ def get_parser():
     ap.add_argument('--synthesis', choices=('splat', 'gather'), default='splat', help='the synthesis rule (DESIGN 17 / 19)')
     ap.add_argument('--back', choices=('network', 'reverse'), default='network',
                     help='--synthesis gather: where the flow toward the previous frame comes from')
+    ap.add_argument('--occlusion', choices=('wang', 'brox'),
+                    help='--synthesis gather: the occlusion-aware rule with the masks of this operator (DESIGN 26)')
     ap.add_argument('--loss-between', type=float, default=0, metavar='W',
                     help='--fit-epochs: weight of the in-between consistency loss (main.py --loss-between; DESIGN 22)')
     ap.add_argument('--between-taus', type=int, metavar='K', help='--loss-between: in-between times drawn per step (default 1)')
@@ -89,6 +96,8 @@ def get_args(argv=None):
         a.factor = 2
     if a.factor < 1 or a.factor > 65:
         ap.error('--factor: 1 .. 65 (one call synthesizes factor - 1 <= 64 times)')
+    if a.occlusion is not None and a.synthesis != 'gather':
+        ap.error(f'--occlusion {a.occlusion} is the masked gather rule: it is valid only with --synthesis gather')
     if a.between_points is not None and a.between_taus is not None:
         ap.error('--between-taus draws whole frames, --between-points sampled points: give one of them')
     if a.between_points is not None and a.between_points < 1:
@@ -110,7 +119,10 @@ def trainer_args(a):
     m = flow_main()
     argv = ['test', '--name', a.name, '--net', a.net, '--size', str(a.size), '--test-size', str(a.size), '--test-batch', str(a.batch),
             '--epochs', str(max(a.fit_epochs, 1))]
-    argv += ['--synthetic', *map(str, a.synthetic)] if a.synthetic else ['--input-video', a.input_video]
+    if a.layered:
+        argv += ['--layered', *map(str, a.layered)]
+    else:
+        argv += ['--synthetic', *map(str, a.synthetic)] if a.synthetic else ['--input-video', a.input_video]
     if a.holdout:
         argv += ['--holdout', str(a.holdout)]
     if a.loss_smooth_at and a.fit_epochs:
@@ -200,6 +212,8 @@ def main(argv=None):
     how = {}
     if a.synthesis == 'gather':
         how = dict(synthesis='gather', dt=2 / (num_frames - 1), back=a.back)        # the clip fitted: under --holdout the kept frames
+        if a.occlusion:
+            how['occlusion'] = a.occlusion
     between = {}                                                   # (pair, j) -> (h, w, 3) bytes
     records = []
     if taus:
@@ -225,7 +239,7 @@ def main(argv=None):
         save_gif(path.join('results', f'{tag}.gif'), np.stack(written), fps=4 * a.factor)
     if a.holdout:
         means = quality_means(records)
-        means['synthesis'] = a.synthesis if a.synthesis == 'splat' else f'gather/{a.back}'
+        means['synthesis'] = a.synthesis if a.synthesis == 'splat' else f'gather/{a.back}' + (f'/{a.occlusion}' if a.occlusion else '')
         with open(path.join(out_dir, 'quality.jsonl'), 'w') as f:
             for rec in records + [means]:
                 f.write(json.dumps(rec) + '\n')

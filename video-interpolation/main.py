@@ -9,6 +9,7 @@ Differences from the reference, all to make the path runnable here:
   * the trainer, checkpoint callback and logger come from `sin_inn_amd.lightning` (pytorch_lightning and wandb are not installed):
     `--wandb NAME` takes any name and writes JSON lines to ./NAME_<scene>_<name>.jsonl, one record per epoch;
   * `--synthetic T H W` trains and tests on `SyntheticClip(T, H, W)`, scene name `synthetic`; no data set is needed;
+  * `--layered T H W` does the same on `LayeredClip(T, H, W)`, two moving layers with real occlusion, scene name `layered`;
   * `--holdout S` fits (train) or evaluates (test) on every S-th frame of the clip only (`sin_inn_amd.flowdata.Holdout`); validation
     then logs `val/PSNR` and `val/SSIM` of the synthesized held-out frames in place of `val/EPE`; the attribute exists only when
     the flag is given;
@@ -64,6 +65,8 @@ def get_parser():
     parser.add_argument('--test-batch', default=1, type=int)
     parser.add_argument('--synthetic', nargs=3, type=int, metavar=('T', 'H', 'W'),
                         help='train / test on a synthetic clip of T frames of H x W instead of --input-video')
+    parser.add_argument('--layered', nargs=3, type=int, metavar=('T', 'H', 'W'), default=argparse.SUPPRESS,
+                        help='train / test on a LayeredClip of T frames of H x W (two layers, real occlusion) instead of --input-video')
     parser.add_argument('--holdout', type=int, metavar='S', default=argparse.SUPPRESS,
                         help='keep every S-th frame, hold the others out and score their synthesis (val/PSNR, val/SSIM)')
     # Network options
@@ -108,6 +111,8 @@ def get_args(argv=None):
     args = parser.parse_args(argv)
     if args.occl == 'None':                                    # argparse cannot produce the reference's `None` choice from a string
         args.occl = None
+    if args.synthetic and getattr(args, 'layered', None):
+        parser.error('--synthetic and --layered both name the clip: give one of them')
     if getattr(args, 'holdout', 2) < 2:
         parser.error('--holdout S: S >= 2 (every S-th frame is kept)')
     try:
@@ -257,14 +262,14 @@ def write_scene_flows(model, testset, outdir, device):
 
 def sintel_submission(args):
     """main.py:109-130: sintel_submission/<clean | final>/<scene>/frame_%04d.flo for every scene beside --input-video; the pass is
-    `clean` if --name ends in it, else `final` (the reference fails on a name that ends in neither).  With --synthetic the one
-    synthetic scene is written."""
+    `clean` if --name ends in it, else `final` (the reference fails on a name that ends in neither).  With --synthetic or
+    --layered the one generated scene is written."""
     import torch
     from sin_inn_amd.flowdata import get_video
     from sin_inn_amd.flowtrainer import FlowTrainer
     device = torch.device('cuda', _devices(args)[0])
     sintel_pass = 'clean' if args.name.endswith('clean') else 'final'
-    scenes = [None] if args.synthetic else sorted(os.listdir(path.dirname(args.input_video)))
+    scenes = [None] if args.synthetic or getattr(args, 'layered', None) else sorted(os.listdir(path.dirname(args.input_video)))
     for entry in scenes:
         video, scene = get_video(args.input_video if entry is None else path.join(path.dirname(args.input_video), entry), args)
         args.net = build_net(args)
