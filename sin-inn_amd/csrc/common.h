@@ -7,12 +7,11 @@
 #include <type_traits>
 
 #include "../../include/sininn.h"
+#include "launch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace sininn {
-
-void set_error(const char* fmt, ...);
 
 #define SININN_CHECK(cond, ...)                \
   do {                                         \

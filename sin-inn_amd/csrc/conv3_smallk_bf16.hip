@@ -212,7 +212,7 @@ static bool g_c3k_enabled = getenv("SININN_CONV3_SMALLK") == nullptr || atoi(get
 void conv3_smallk_enable(int on) { g_c3k_enabled = on != 0; }
 
 // conv1 of a 3x3 subnet on the mixed-precision path: fp32 input with at most 32 channels -> ReLU -> 256 bf16 channels
-int conv3_smallk_bf16_supported(const sininn_conv_args* a) {
+extern "C" int sininn_conv3_smallk_bits_supported(const sininn_conv_args* a) {
   if (!g_c3k_enabled || !a) return 0;
   if (a->ksize != 3 || !a->w_bf16 || a->in_bf16 || !a->out_bf16 || a->winograd) return 0;
   if (a->mode == SININN_CONV_RELU) { if (!a->bias) return 0; }
@@ -252,7 +252,7 @@ static int c3k_launch(const ConvDevB& q, int ntiles, unsigned* bits, hipStream_t
 // bits: NULL, or the gate bit mask [B*H*W][8] words that conv1 (mode RELU) writes and the masked data gradient (mode MASK) reads
 // instead of a->mask (block executor: the region lives in `saved`)
 int conv3_smallk_bf16_launch_bits(const sininn_conv_args* a, unsigned* bits, hipStream_t st) {
-  SININN_CHECK(conv3_smallk_bf16_supported(a), "conv3_smallk_bf16: unsupported conv");
+  SININN_CHECK(sininn_conv3_smallk_bits_supported(a), "conv3_smallk_bf16: unsupported conv");
   ConvDevB q;
   if (int rc = conv_bf16_prepare(a, q)) return rc;
   q.c.tiles_x = (a->W + 15) / 16; q.c.tiles_y = (a->H + 15) / 16;
@@ -273,6 +273,10 @@ int conv3_smallk_bf16_launch_bits(const sininn_conv_args* a, unsigned* bits, hip
   }
 }
 
-int conv3_smallk_bf16_launch(const sininn_conv_args* a, hipStream_t st) { return conv3_smallk_bf16_launch_bits(a, nullptr, st); }
+// the same launch on its own: the bit mask is then required
+extern "C" int sininn_conv3_smallk_bits(const sininn_conv_args* a, unsigned* bits, void* stream) {
+  SININN_CHECK(bits != nullptr, "sininn_conv3_smallk_bits: bits is NULL");
+  return conv3_smallk_bf16_launch_bits(a, bits, ST(stream));
+}
 
 }  // namespace sininn

@@ -477,11 +477,9 @@ int conv_bf16_prepare(const sininn_conv_args* a, ConvDevB& q) {
   return 0;
 }
 
-int conv3_smallk_bf16_supported(const sininn_conv_args* a);      // conv3_smallk_bf16.hip: Cin <= 32 -> 256, ReLU, bf16 out
-int conv3_smallk_bf16_launch(const sininn_conv_args* a, hipStream_t st);
-
 int conv_bf16_launch(const sininn_conv_args* a, hipStream_t st) {
-  if (conv3_smallk_bf16_supported(a)) return conv3_smallk_bf16_launch(a, st);
+  // conv3_smallk_bf16.hip: Cin <= 32 -> 256, ReLU, bf16 out
+  if (sininn_conv3_smallk_bits_supported(a)) return conv3_smallk_bf16_launch_bits(a, nullptr, st);
   ConvDevB q;
   if (int rc = conv_bf16_prepare(a, q)) return rc;
   return a->ksize == 3 ? launch_ks<3>(q, st) : launch_ks<1>(q, st);
@@ -513,8 +511,9 @@ __global__ void pack_bf16_kernel(const float* __restrict__ w, const float* __res
   }
 }
 
-int pack_bf16_launch(const float* w, const float* bias, int N, int Cin, int ksize, const int* colmap, int Np, void* wb_fwd,
-                     float* b_fwd, int Cdp, void* wb_dgrad, hipStream_t st) {
+extern "C" int sininn_pack_conv_weights_bf16(const float* w, const float* bias, int N, int Cin, int ksize, const int* colmap, int Np,
+                                             void* wb_fwd, float* b_fwd, int Cdp, void* wb_dgrad, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(w != nullptr && N > 0 && Cin > 0 && (ksize == 1 || ksize == 3), "pack_bf16: bad arguments");
   SININN_CHECK(!wb_fwd || Np >= 1, "pack_bf16: bad Np");
   SININN_CHECK(!wb_dgrad || Cdp >= Cin, "pack_bf16: Cdp < Cin");

@@ -20,7 +20,4 @@ struct ConvDevB {
                              // tensor mask_b (IRN DenseBlock data gradients; fp32-input 3x3 convs only)
 };
 
-
-int conv_bf16_prepare(const sininn_conv_args* a, ConvDevB& q);
-
 }  // namespace sininn

@@ -4,21 +4,14 @@
 
 namespace sininn {
 
-int conv_dispatch_k3(ConvDev& d, hipStream_t st, int force_cfg);
-int conv_dispatch_k1(ConvDev& d, hipStream_t st, int force_cfg);
-int conv32_dispatch_k3(ConvDev& d, hipStream_t st, int force_cfg, bool must);
-int conv32_dispatch_k1(ConvDev& d, hipStream_t st, int force_cfg, bool must);
-int wino_dispatch_k3(ConvDev& d, hipStream_t st, int cg2);
-
 int g_conv_dma = 0;
 static int g_force_cfg = 0;   // test hook: 0 auto, 1 force 8-row tiles, 2 force 4-row tiles
 static int g_force_ck = 0;
 static int g_ablate = 0;     // diagnostic: see ConvDev::ablate (results are wrong when set)    // test hook: override the channel chunk
 
-int conv_bf16_launch(const sininn_conv_args* a, hipStream_t st);
 extern int g_bf16_force_ck16;   // conv_bf16.hip: test hook, 16-channel chunks where launch_ks would take 32
 
-// argument validation + device-side descriptor of one fp32 conv (shared by conv_launch and the fused 1x1 pair)
+// argument validation + device-side descriptor of one fp32 conv (shared by sininn_conv and the fused 1x1 pair)
 int conv_prepare(const sininn_conv_args* a, ConvDev& d) {
   SININN_CHECK(a != nullptr, "conv: null args");
   SININN_CHECK(a->ksize == 1 || a->ksize == 3, "conv: ksize %d not in {1,3}", a->ksize);
@@ -100,7 +93,8 @@ int conv_prepare(const sininn_conv_args* a, ConvDev& d) {
   return 0;
 }
 
-int conv_launch(const sininn_conv_args* a, hipStream_t st) {
+extern "C" int sininn_conv(const sininn_conv_args* a, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(a != nullptr, "conv: null args");
   if (a->w_bf16) return conv_bf16_launch(a, st);
   ConvDev d;
@@ -125,7 +119,8 @@ int conv_launch(const sininn_conv_args* a, hipStream_t st) {
   return conv_dispatch_k1(d, st, fc);
 }
 
-void conv_set_test_hooks(int force_cfg, int force_ck) {
+/* test hook (not part of the documented surface): force tile configuration / channel chunk */
+extern "C" void sininn_conv_test_hooks(int force_cfg, int force_ck) {
   // force_cfg = ablate*1000 + dma*100 + cfg   (cfg >= 10 pins the 16-wide kernel; dma: 1 on, 2 off, 0 default)
   g_force_cfg = force_cfg % 100; g_force_ck = force_ck; g_ablate = force_cfg / 1000;
   g_bf16_force_ck16 = force_ck == 16;     // shared with the fp32 chunk override: tools/bench_kernels.py --ck 16 moves the bf16 kernels too

@@ -23,10 +23,6 @@
 
 namespace sininn {
 
-int conv_prepare(const sininn_conv_args* a, ConvDev& d);
-int conv_pair_bf16_supported(const sininn_conv_args* f, const sininn_conv_args* s);      // conv_pair_bf16.hip
-int conv_pair_bf16_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
-
 struct PairDev { ConvDev a, b; };
 
 // build tunables (A/B'd with tools/build_variant.sh + SININN_LIB on one box): how many 16-channel steps ahead the weight
@@ -312,7 +308,6 @@ static int pair_launch(PairDev& q, hipStream_t st) {
   return 0;
 }
 
-void conv_pair_k1_enable(int on);
 #ifndef PAIR_TH
 #define PAIR_TH 2
 #endif
@@ -321,7 +316,7 @@ static bool g_pair_enabled = getenv("SININN_PAIR_K1") == nullptr || atoi(getenv(
 void conv_pair_k1_enable(int on) { g_pair_enabled = on != 0; }     // test hook: A/B against the two-launch path
 
 // 1 when the pair (first: RELU or MASK into the 256-channel hidden tensor; second: any mode reading it) can run fused
-int conv_pair_k1_supported(const sininn_conv_args* f, const sininn_conv_args* s) {
+extern "C" int sininn_conv_pair_k1_supported(const sininn_conv_args* f, const sininn_conv_args* s) {
   if (!g_pair_enabled || !f || !s) return 0;
   if (f->w_bf16 || s->w_bf16) return conv_pair_bf16_supported(f, s);          // mixed-precision twin
   if (f->ksize != 1 || s->ksize != 1 || f->w_bf16 || s->w_bf16 || f->winograd || s->winograd) return 0;
@@ -349,8 +344,9 @@ int conv_pair_k1_preferred(const sininn_conv_args* f) {
   return !(f->mode == SININN_CONV_RELU && f->out && f->Cin < (f->w_bf16 ? fwd_mink_bf16 : fwd_mink));
 }
 
-int conv_pair_k1_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st) {
-  SININN_CHECK(conv_pair_k1_supported(f, s), "conv_pair: unsupported pair (check sininn_conv_pair_k1_supported first)");
+extern "C" int sininn_conv_pair_k1(const sininn_conv_args* f, const sininn_conv_args* s, void* stream) {
+  hipStream_t st = ST(stream);
+  SININN_CHECK(sininn_conv_pair_k1_supported(f, s), "conv_pair: unsupported pair (check sininn_conv_pair_k1_supported first)");
   if (f->w_bf16) return conv_pair_bf16_launch(f, s, st);
   SININN_CHECK((unsigned long long)f->H * f->W * f->in_stride * 4ull < (1ull << 31),
                "conv_pair: one image of the input exceeds the 2 GB a block addresses (raw buffer staging)");

@@ -32,8 +32,6 @@
 
 namespace sininn {
 
-int conv_prepare(const sininn_conv_args* a, ConvDev& d);
-
 template <int K1, int K2, bool STAMP>
 __global__ __launch_bounds__(S1_NTHR) void conv_sub1_bwd_kernel(Sub1Dev q) {
   using SH = Sub1Shape<K1, K2>;
@@ -720,17 +718,8 @@ __global__ __launch_bounds__(256) void sub1_reduce_kernel(const float* __restric
   }
 }
 
-// conv_sub1_bf16.hip: the mixed-precision twins (bf16 weight packs, fp32 tensors)
-bool conv_sub1_bf16_enabled();
-void conv_sub1_bf16_enable(int on);
-int conv_sub1_bf16_bwd_launch(const sininn_conv_args* rc, const sininn_conv_args* d2, const sininn_conv_args* d1, int no_dx, void* ws,
-                              size_t ws_bytes, int* slabs_out, hipStream_t st);
-int conv_sub1_bf16_fwd_supported(const sininn_conv_args* f, const sininn_conv_args* s);
-int conv_sub1_bf16_fwd_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
-
 static bool g_sub1_enabled = getenv("SININN_SUB1_BWD") == nullptr || atoi(getenv("SININN_SUB1_BWD")) != 0;   // A/B switch
 void conv_sub1_bwd_enable(int on) { g_sub1_enabled = on != 0; conv_sub1_bf16_enable(on); }
-bool conv_sub1_bwd_enabled() { return g_sub1_enabled; }
 
 static bool shape_ok(int k1, int k2) { return sub1_shape_ok(k1, k2); }
 
@@ -743,7 +732,7 @@ int conv_sub1_bwd_shape_supported(int ksize, int dtype, int cond_cin, int co) {
   return on && ksize == 1 && shape_ok(cond_cin, 2 * co);
 }
 
-size_t conv_sub1_bwd_workspace_bytes(int cond_cin, int co) {
+extern "C" size_t sininn_conv_sub1_bwd_workspace_bytes(int cond_cin, int co) {
   if (!shape_ok(cond_cin, 2 * co)) return 0;
   const int nu1 = (cond_cin + 16) / 16;
   return (size_t)S1_MAX_BLOCKS * ((size_t)2 * co * S1_HID + (size_t)S1_HID * 16 * nu1 + 64) * sizeof(float);
@@ -791,8 +780,8 @@ int conv_sub1_bwd_launch(const sininn_conv_args* rc, const sininn_conv_args* d2,
                "conv_sub1_bwd: operands must be 16-byte aligned with strides that are multiples of 4 floats");
   SININN_CHECK((unsigned long long)rc->H * rc->W * (rc->in_stride > d2->in_stride ? rc->in_stride : d2->in_stride) * 4ull < (1ull << 31),
                "conv_sub1_bwd: one image of an operand exceeds the 2 GB a block addresses (raw buffer staging)");
-  SININN_CHECK(ws_bytes >= conv_sub1_bwd_workspace_bytes(K1, K2 / 2), "conv_sub1_bwd: workspace too small (%zu < %zu)", ws_bytes,
-               conv_sub1_bwd_workspace_bytes(K1, K2 / 2));
+  SININN_CHECK(ws_bytes >= sininn_conv_sub1_bwd_workspace_bytes(K1, K2 / 2), "conv_sub1_bwd: workspace too small (%zu < %zu)", ws_bytes,
+               sininn_conv_sub1_bwd_workspace_bytes(K1, K2 / 2));
   if (!no_dx) {
     // the kernel's own epilogue (one quad per thread, side inputs requested a tile ahead) serves the modes the block executor uses
     const bool cbwd = d1->mode == SININN_CONV_ADD_CBWD_FWD || d1->mode == SININN_CONV_ADD_CBWD_INV;
@@ -836,6 +825,16 @@ int conv_sub1_bwd_reduce(int cond_cin, int co, const void* ws, int slabs, float*
   return sub1_reduce<24, 48>(s, slabs, gw2, gb2, gw1, gb1, st);
 }
 
+// the launch, then the reduce of its slabs into whichever gradients are asked for
+extern "C" int sininn_conv_sub1_bwd(const sininn_conv_args* recompute, const sininn_conv_args* d2, const sininn_conv_args* d1, int no_dx,
+                                    float* gw2, float* gb2, float* gw1, float* gb1, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = ST(stream);
+  int slabs = 0;
+  if (int rc = conv_sub1_bwd_launch(recompute, d2, d1, no_dx, workspace, workspace_bytes, &slabs, st)) return rc;
+  if (!gw2 && !gb2 && !gw1 && !gb1) return 0;
+  return conv_sub1_bwd_reduce(recompute->Cin, d2->Cin / 2, workspace, slabs, gw2, gb2, gw1, gb1, st);
+}
+
 // ---- forward --------------------------------------------------------------------------------------------------------------------
 template <int K1, int N2, int HT>
 static int sub1_fwd_launch(Sub1Dev& q, hipStream_t st) {
@@ -855,7 +854,7 @@ static int sub1_fwd_launch(Sub1Dev& q, hipStream_t st) {
 
 // first: conv1 of the subnet (mode RELU; `out` is ignored: the hidden tensor is never stored), second: conv2 with a coupling
 // epilogue (COUPLE_FWD / COUPLE_INV), described as for sininn_conv_pair_k1.
-int conv_sub1_fwd_supported(const sininn_conv_args* f, const sininn_conv_args* s) {
+extern "C" int sininn_conv_sub1_fwd_supported(const sininn_conv_args* f, const sininn_conv_args* s) {
   if (f && s && f->w_bf16) return conv_sub1_bf16_fwd_supported(f, s);
   if (!g_sub1_enabled || !f || !s) return 0;
   if (f->ksize != 1 || s->ksize != 1 || f->w_bf16 || s->w_bf16 || f->winograd || s->winograd || f->in_bf16 || s->in_bf16 || f->out_bf16) return 0;
@@ -866,8 +865,9 @@ int conv_sub1_fwd_supported(const sininn_conv_args* f, const sininn_conv_args* s
   return shape_ok(f->Cin, s->Np) ? 1 : 0;
 }
 
-int conv_sub1_fwd_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st) {
-  SININN_CHECK(conv_sub1_fwd_supported(f, s), "conv_sub1_fwd: unsupported subnet (check sininn_conv_sub1_fwd_supported first)");
+extern "C" int sininn_conv_sub1_fwd(const sininn_conv_args* f, const sininn_conv_args* s, void* stream) {
+  hipStream_t st = ST(stream);
+  SININN_CHECK(sininn_conv_sub1_fwd_supported(f, s), "conv_sub1_fwd: unsupported subnet (check sininn_conv_sub1_fwd_supported first)");
   if (f->w_bf16) return conv_sub1_bf16_fwd_launch(f, s, st);
   SININN_CHECK((unsigned long long)f->H * f->W * f->in_stride * 4ull < (1ull << 31),
                "conv_sub1_fwd: one image of the input exceeds the 2 GB a block addresses (raw buffer staging)");

@@ -1449,7 +1449,6 @@ __global__ __launch_bounds__(256) void wide_reduce2_kernel(const float* __restri
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-size_t conv_sub1_bwd_workspace_bytes(int cond_cin, int co);      // conv_sub1.hip: the slab layout is shared
 static bool g_sub1b_enabled = getenv("SININN_SUB1_BF16") == nullptr || atoi(getenv("SININN_SUB1_BF16")) != 0;   // A/B switch
 void conv_sub1_bf16_enable(int on) { g_sub1b_enabled = on != 0; }
 bool conv_sub1_bf16_enabled() { return g_sub1b_enabled; }
@@ -1493,8 +1492,8 @@ int conv_sub1_bf16_bwd_launch(const sininn_conv_args* rc, const sininn_conv_args
                aligned16(d1->w) && aligned16(ws), "conv_sub1_bf16_bwd: operands must be 16-byte aligned with strides that are multiples of 4 floats");
   SININN_CHECK((unsigned long long)rc->H * rc->W * (rc->in_stride > d2->in_stride ? rc->in_stride : d2->in_stride) * 4ull < (1ull << 31),
                "conv_sub1_bf16_bwd: one image of an operand exceeds the 2 GB a block addresses (raw buffer staging)");
-  SININN_CHECK(ws_bytes >= conv_sub1_bwd_workspace_bytes(K1, K2 / 2), "conv_sub1_bf16_bwd: workspace too small (%zu < %zu)", ws_bytes,
-               conv_sub1_bwd_workspace_bytes(K1, K2 / 2));
+  SININN_CHECK(ws_bytes >= sininn_conv_sub1_bwd_workspace_bytes(K1, K2 / 2),   // conv_sub1.hip: the slab layout is shared
+               "conv_sub1_bf16_bwd: workspace too small (%zu < %zu)", ws_bytes, sininn_conv_sub1_bwd_workspace_bytes(K1, K2 / 2));
   if (!no_dx) {
     const bool cbwd = d1->mode == SININN_CONV_ADD_CBWD_FWD || d1->mode == SININN_CONV_ADD_CBWD_INV;
     SININN_CHECK(cbwd || d1->mode == SININN_CONV_ADD, "conv_sub1_bf16_bwd: d1->mode must be ADD or ADD_CBWD_* (got %d)", d1->mode);
@@ -1751,6 +1750,28 @@ int conv_sub1_bf16_wide_wg2_launch(const float* dr, int dr_stride, const void* h
   hipLaunchKernelGGL((wide_reduce2_kernel<192>), dim3((ET + 31) / 32), dim3(256), 0, st, static_cast<const float*>(ws), blocks, gw2, gb2);
   SININN_LAUNCH_CHECK("conv_sub1_bf16_wide_reduce2");
   return 0;
+}
+
+// the block executor's level-1 riders, callable on their own (same internal functions, no other behaviour)
+extern "C" size_t sininn_conv_sub1_wide_bwd_workspace_bytes(int cin, int co) { return conv_sub1_bf16_wide_ws_bytes(1, 1, cin, co); }
+extern "C" int sininn_conv_sub1_wide_bwd(const sininn_conv_args* d2, const sininn_conv_args* d1, const float* x, int x_stride, float* gw1,
+                                         float* gb1, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = ST(stream);
+  SININN_CHECK(conv_sub1_bf16_wide_bwd_supported(d2, d1), "sininn_conv_sub1_wide_bwd: unsupported descriptor pair");
+  if (!x) {
+    SININN_CHECK(!gw1 && !gb1, "sininn_conv_sub1_wide_bwd: gw1 / gb1 need x");
+    return conv_sub1_bf16_wide_bwd_launch(d2, d1, st);
+  }
+  int slabs = 0;
+  if (int rc = conv_sub1_bf16_wide_bwd_wg1_launch(d2, d1, x, x_stride, workspace, workspace_bytes, &slabs, st)) return rc;
+  if (!gw1 && !gb1) return 0;
+  return conv_sub1_bf16_wide_reduce(workspace, slabs, gw1, gb1, st);
+}
+extern "C" size_t sininn_conv_sub1_wide_wg2_workspace_bytes(int cin, int co) { return conv_sub1_bf16_wide_wg2_ws_bytes(1, 1, cin, co); }
+extern "C" int sininn_conv_sub1_wide_wg2(const float* dr, int dr_stride, const void* h, int h_stride, int B, int H, int W, float* gw2,
+                                         float* gb2, void* workspace, size_t workspace_bytes, void* stream) {
+  SININN_CHECK(sininn_conv_sub1_wide_wg2_workspace_bytes(96, 96) > 0, "sininn_conv_sub1_wide_wg2: the wide kernels are switched off");
+  return conv_sub1_bf16_wide_wg2_launch(dr, dr_stride, h, h_stride, B, H, W, workspace, workspace_bytes, gw2, gb2, ST(stream));
 }
 
 }  // namespace sininn

@@ -228,7 +228,7 @@ void sub3_fusion_set(int on) { g_sub3_enabled = on; }
 
 // 1 when (first, second) is a 3x3 subnet this kernel runs: first = fp32 input -> 256 hidden channels (RELU, bf16 weights, no
 // hidden store: first->out == NULL), second = hidden -> fp32 coupling epilogue (COUPLE_FWD / COUPLE_INV, bf16 weights)
-int conv_sub3_bf16_supported(const sininn_conv_args* f, const sininn_conv_args* s) {
+extern "C" int sininn_conv_sub3_supported(const sininn_conv_args* f, const sininn_conv_args* s) {
   if (!f || !s || !f->w_bf16 || !s->w_bf16) return 0;
   if (f->ksize != 3 || s->ksize != 3 || f->winograd || s->winograd) return 0;
   if (f->in_bf16 || !f->out_bf16 || !s->in_bf16 || s->out_bf16) return 0;
@@ -242,8 +242,9 @@ int conv_sub3_bf16_supported(const sininn_conv_args* f, const sininn_conv_args* 
   return s->Np == 16 || s->Np == 32 || s->Np == 48 || s->Np == 64 || s->Np == 96 || s->Np == 192;
 }
 
-int conv_sub3_bf16_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st) {
-  SININN_CHECK(conv_sub3_bf16_supported(f, s), "conv_sub3_bf16: unsupported subnet (3x3, bf16 weights, fp32 input, no hidden store, coupling epilogue)");
+extern "C" int sininn_conv_sub3(const sininn_conv_args* f, const sininn_conv_args* s, void* stream) {
+  hipStream_t st = ST(stream);
+  SININN_CHECK(sininn_conv_sub3_supported(f, s), "conv_sub3_bf16: unsupported subnet (3x3, bf16 weights, fp32 input, no hidden store, coupling epilogue)");
   Sub3Dev q;
   sininn_conv_args fa = *f;
   alignas(16) __bf16 dummy[8] = {};                    // conv_bf16_prepare insists on an output / input pointer; neither is

@@ -44,7 +44,7 @@ __host__ __device__ static inline void pack_regions_bf16(const sininn_pack_desc&
   nb = d.b_fwd ? d.Np : 0;
 }
 
-int pack_work_items_bf16(const sininn_pack_desc* d) {
+extern "C" int sininn_pack_work_items_bf16(const sininn_pack_desc* d) {
   if (!d || d->wino_fwd || d->wino_dgrad || d->N <= 0 || d->Cin <= 0 || (d->ksize != 1 && d->ksize != 3)) return 0;
   int nf, nd, nb;
   pack_regions_bf16(*d, nf, nd, nb);
@@ -96,7 +96,8 @@ __global__ void pack_batch_bf16_kernel(const sininn_pack_desc* __restrict__ desc
   }
 }
 
-int pack_batch_bf16_launch(const sininn_pack_desc* descs, int n, int total, hipStream_t st) {
+extern "C" int sininn_pack_batch_bf16(const sininn_pack_desc* descs, int n, int total, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(descs != nullptr && n > 0 && total > 0, "pack_batch_bf16: bad arguments");
   hipLaunchKernelGGL(pack_batch_bf16_kernel, dim3((total + 255) / 256), dim3(256), 0, st, descs, n, total);
   SININN_LAUNCH_CHECK("pack_batch_bf16");

@@ -7,26 +7,9 @@
 
 namespace sininn {
 
-int conv_launch(const sininn_conv_args* a, hipStream_t st);
-int permute_launch(const float* in, int in_stride, float* out, int out_stride, int64_t M, int C, const int* idx, hipStream_t st);
-int lrelu_bwd_launch(float* g, int g_stride, const float* f, int f_stride, int64_t M, int n, float slope, hipStream_t st);
-int irn_coupling_bwd_launch(const float* dy, int dy_stride, const float* vy, int vy_stride, const float* hval, int64_t M,
-                            int Co, float clamp, int inverse, float* dG, int dG_stride, int dG_pad, float* dh, float* dv,
-                            int dv_stride, hipStream_t st);
-size_t wgrad_group_workspace_bytes(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize);
-int wgrad_group_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
-                       hipStream_t st);
-int copy_channels_launch(const float* in, int in_stride, float* out, int out_stride, int64_t M, int C, int Cpad, hipStream_t st);
-int copy_channels_bf16_launch(const float* in, int in_stride, void* out, int out_stride, int64_t M, int C, int Cpad, hipStream_t st);
-size_t wgrad_group_mixed_workspace_bytes(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize);
-int wgrad_group_mixed_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
-                             hipStream_t st);
-
 // per-class launch brackets of bench.py's roofline.classes (glow_exec.cpp); IRN uses the class slots as
 //   0 conv1-4 forward (+LeakyReLU)   1 conv5 forward (+ fused tail)   2 data gradient of conv5   3 data gradients of conv1-4
 //   4 the five weight gradients (one grouped launch pair)             5 elementwise (HBM-bound, no FLOPs counted)
-hipEvent_t class_scope_open(int cls, int ksize, double flops, hipStream_t st);
-void class_scope_close(hipEvent_t end, hipStream_t st);
 struct Scope {
   hipStream_t st; hipEvent_t b;
   Scope(int cls, double flops, hipStream_t s) : st(s), b(class_scope_open(cls, 3, flops, s)) {}
@@ -53,7 +36,7 @@ static void dense_items(const sininn_dense_args* a, sininn_wgrad_item it[5]) {
   }
 }
 
-size_t dense_workspace_bytes(int B, int H, int W, int cin, int cout) {
+extern "C" size_t sininn_dense_workspace_bytes(int B, int H, int W, int cin, int cout) {
   sininn_dense_args a = {};
   a.B = B; a.H = H; a.W = W; a.cin = cin; a.cout = cout;
   sininn_wgrad_item it[5];
@@ -65,7 +48,7 @@ size_t dense_workspace_bytes(int B, int H, int W, int cin, int cout) {
     int n = 0;
     for (int i = 0; i < 5; ++i)
       if (mask & (1 << i)) sub[n++] = it[i];
-    const size_t bytes = wgrad_group_workspace_bytes(sub, n, B, H, W, 3);
+    const size_t bytes = sininn_wgrad_group_workspace_bytes(sub, n, B, H, W, 3);
     w = bytes > w ? bytes : w;
   }
   return w;
@@ -105,7 +88,8 @@ static int check_backward_extents(const sininn_dense_args* a) {
   return 0;
 }
 
-int dense_forward(const sininn_dense_args* a, hipStream_t st) {
+extern "C" int sininn_dense_forward(const sininn_dense_args* a, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = check(a, "dense_forward")) return rc;
   const int64_t M = (int64_t)a->B * a->H * a->W;
   const int cin = a->cin, cinp = pad8(cin), bw = cinp + 4 * GC, cout = a->cout;
@@ -121,7 +105,7 @@ int dense_forward(const sininn_dense_args* a, hipStream_t st) {
     c.in = a->buf; c.in_stride = bw; c.Cin = k; c.w = a->w_fwd[i]; c.bias = a->b_fwd[i]; c.Np = GC; c.winograd = a->winograd;
     c.B = a->B; c.H = a->H; c.W = a->W; c.ksize = 3; c.mode = SININN_CONV_LRELU; c.clamp = SLOPE;
     c.out = a->buf + k; c.out_stride = bw; c.N = GC;
-    if (int rc = conv_launch(&c, st)) return rc;
+    if (int rc = sininn_conv(&c, st)) return rc;
   }
   sininn_conv_args c = {};
   c.in = a->buf; c.in_stride = bw; c.Cin = bw; c.w = a->w_fwd[4]; c.bias = a->b_fwd[4]; c.Np = pad16(pad8(cout)); c.winograd = a->winograd;
@@ -133,12 +117,11 @@ int dense_forward(const sininn_dense_args* a, hipStream_t st) {
     c.v = a->aux1; c.v_stride = a->aux1_stride; c.mask = a->aux2; c.mask_stride = cout; c.clamp = a->clamp;
   }
   Scope sc(1, cflops(M, cin + 4 * GC, cout), st);
-  return conv_launch(&c, st);
+  return sininn_conv(&c, st);
 }
 
-int order_after(hipStream_t waiter, hipStream_t producer);     // glow_exec.cpp: per-device event ring
-
-int dense_backward(const sininn_dense_args* a, hipStream_t st, hipStream_t wst) {
+extern "C" int sininn_dense_backward(const sininn_dense_args* a, void* stream, void* wgrad_stream) {
+  hipStream_t st = ST(stream), wst = ST(wgrad_stream);
   if (int rc = check(a, "dense_backward")) return rc;
   SININN_CHECK(a->dout && a->dF && a->workspace, "dense_backward: null tensor");
   for (int i = 0; i < 5; ++i) SININN_CHECK(a->w_dgrad[i], "dense_backward: missing dgrad weights");
@@ -176,7 +159,7 @@ int dense_backward(const sininn_dense_args* a, hipStream_t st, hipStream_t wst) 
     if (accumulate) { c.mode = SININN_CONV_ADD; c.addend = a->dF; c.addend_stride = bw; }
     else c.mode = SININN_CONV_LINEAR;
     if (tail >= 0) { c.mask = a->buf; c.mask_stride = bw; c.Co = tail; c.clamp = SLOPE; }
-    return conv_launch(&c, st);
+    return sininn_conv(&c, st);
   };
   {
     Scope sc(2, cflops(M, cout, cin + 4 * GC), st);
@@ -203,7 +186,7 @@ int dense_backward(const sininn_dense_args* a, hipStream_t st, hipStream_t wst) 
     for (int i = 0; i < 5; ++i)
       if (it[i].gw) fl += cflops(M, cin + GC * i, i < 4 ? GC : cout);
     Scope sc(4, fl, wst);
-    if (int rc = wgrad_group_launch(live, n, a->B, a->H, a->W, 3, a->workspace, a->workspace_bytes, wst)) return rc;
+    if (int rc = sininn_wgrad_group(live, n, a->B, a->H, a->W, 3, a->workspace, a->workspace_bytes, wst)) return rc;
   }
   return 0;
 }
@@ -231,7 +214,7 @@ static void dense_items_bf16(const sininn_dense_bf16_args* a, const float* dD, i
   }
 }
 
-size_t dense_bf16_workspace_bytes(int B, int H, int W, int cin, int cout) {
+extern "C" size_t sininn_dense_bf16_workspace_bytes(int B, int H, int W, int cin, int cout) {
   sininn_dense_bf16_args a = {};
   a.B = B; a.H = H; a.W = W; a.cin = cin; a.cout = cout;
   sininn_wgrad_item it[5];
@@ -276,7 +259,8 @@ static int check_bf16(const sininn_dense_bf16_args* a, const char* who) {
   return 0;
 }
 
-int dense_forward_bf16(const sininn_dense_bf16_args* a, hipStream_t st) {
+extern "C" int sininn_dense_forward_bf16(const sininn_dense_bf16_args* a, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = check_bf16(a, "dense_forward_bf16")) return rc;
   const int64_t M = (int64_t)a->B * a->H * a->W;
   const int cin = a->cin, cinp = pad8(cin), bw = cinp + 4 * GC, cout = a->cout;
@@ -293,7 +277,7 @@ int dense_forward_bf16(const sininn_dense_bf16_args* a, hipStream_t st) {
     c.bias = a->b_fwd[i]; c.Np = GC; c.B = a->B; c.H = a->H; c.W = a->W; c.ksize = 3; c.mode = SININN_CONV_LRELU; c.clamp = SLOPE;
     c.out = reinterpret_cast<float*>(buf + k); c.out_stride = bw; c.N = GC;
     c.w_bf16 = 1; c.in_bf16 = 1; c.out_bf16 = 1;
-    if (int rc = conv_launch(&c, st)) return rc;
+    if (int rc = sininn_conv(&c, st)) return rc;
   }
   sininn_conv_args c = {};
   c.in = reinterpret_cast<const float*>(buf); c.in_stride = bw; c.Cin = bw; c.w = static_cast<const float*>(a->w_fwd[4]);
@@ -306,10 +290,11 @@ int dense_forward_bf16(const sininn_dense_bf16_args* a, hipStream_t st) {
     c.v = a->aux1; c.v_stride = a->aux1_stride; c.mask = a->aux2; c.mask_stride = cout; c.clamp = a->clamp;
   }
   Scope sc(1, cflops(M, cin + 4 * GC, cout), st);
-  return conv_launch(&c, st);
+  return sininn_conv(&c, st);
 }
 
-int dense_backward_bf16(const sininn_dense_bf16_args* a, hipStream_t st, hipStream_t wst) {
+extern "C" int sininn_dense_backward_bf16(const sininn_dense_bf16_args* a, void* stream, void* wgrad_stream) {
+  hipStream_t st = ST(stream), wst = ST(wgrad_stream);
   if (int rc = check_bf16(a, "dense_backward_bf16")) return rc;
   SININN_CHECK(a->dout && a->dF && a->workspace, "dense_backward_bf16: null tensor");
   const int64_t M = (int64_t)a->B * a->H * a->W;
@@ -357,7 +342,7 @@ int dense_backward_bf16(const sininn_dense_bf16_args* a, hipStream_t st, hipStre
     if (accumulate) { c.mode = SININN_CONV_ADD; c.addend = a->dF; c.addend_stride = bw; }
     else c.mode = SININN_CONV_LINEAR;
     if (tail >= 0) { c.mask = reinterpret_cast<const float*>(buf); c.mask_bf16 = 1; c.mask_stride = bw; c.Co = tail; c.clamp = SLOPE; }
-    return conv_launch(&c, st);
+    return sininn_conv(&c, st);
   };
   {
     Scope sc(2, cflops(M, cout, cin + 4 * GC), st);

@@ -32,8 +32,9 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, const float* __
   }
 }
 
-int pack_launch(const float* w, const float* bias, int N, int Cin, int ksize, const int* colmap, int Np,
-                float* w_fwd, float* b_fwd, int Cdp, float* w_dgrad, hipStream_t st) {
+extern "C" int sininn_pack_conv_weights(const float* w, const float* bias, int N, int Cin, int ksize, const int* colmap, int Np,
+                                        float* w_fwd, float* b_fwd, int Cdp, float* w_dgrad, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(w != nullptr && N > 0 && Cin > 0 && (ksize == 1 || ksize == 3), "pack: bad arguments");
   SININN_CHECK(!w_fwd || Np >= 1, "pack: bad Np");
   SININN_CHECK(!w_dgrad || Cdp >= Cin, "pack: Cdp < Cin");
@@ -90,9 +91,10 @@ __global__ void coupling_bwd_kernel(const float* __restrict__ dy, int dy_stride,
   }
 }
 
-int coupling_bwd_launch(const float* dy, int dy_stride, const int* dy_map, const float* vy, int vy_stride,
-                        const int* vy_map, const float* s, const float* gld, int B, int HW, int Co, float clamp,
-                        int inverse, float* dr, float* dv, int dv_stride, hipStream_t st) {
+extern "C" int sininn_coupling_bwd(const float* dy, int dy_stride, const int* dy_map, const float* vy, int vy_stride,
+                                   const int* vy_map, const float* s, const float* gld, int B, int HW, int Co, float clamp,
+                                   int inverse, float* dr, float* dv, int dv_stride, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(dy && vy && s && dr && dv, "coupling_bwd: null pointer");
   SININN_CHECK(B > 0 && HW > 0 && Co > 0 && clamp > 0.f, "coupling_bwd: bad shape");
   SININN_CHECK(dy_stride >= Co && vy_stride >= Co && dv_stride >= Co, "coupling_bwd: stride < Co");
@@ -140,8 +142,9 @@ __global__ void squeeze_kernel(const float* __restrict__ in, Str4 is, float* __r
   }
 }
 
-int squeeze_launch(const float* in, const int64_t is[4], float* out, const int64_t os[4], int B, int C, int H, int W,
-                   int levels, int inverse, const int* chan_map, int map_on_out, hipStream_t st) {
+extern "C" int sininn_squeeze(const float* in, const int64_t is[4], float* out, const int64_t os[4], int B, int C, int H, int W,
+                              int levels, int inverse, const int* chan_map, int map_on_out, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && out && is && os, "squeeze: null pointer");
   SININN_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && levels >= 0 && levels <= 4, "squeeze: bad shape");
   SININN_CHECK((H % (1 << levels)) == 0 && (W % (1 << levels)) == 0, "squeeze: H=%d W=%d not divisible by 2^%d", H, W, levels);
@@ -164,8 +167,9 @@ __global__ void permute_kernel(const float* __restrict__ in, int in_stride, floa
   }
 }
 
-int permute_launch(const float* in, int in_stride, float* out, int out_stride, int64_t M, int C, const int* idx,
-                   hipStream_t st) {
+extern "C" int sininn_permute_channels(const float* in, int in_stride, float* out, int out_stride, int64_t M, int C, const int* idx,
+                                       void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && out && idx && M > 0 && C > 0 && in_stride >= C && out_stride >= C, "permute: bad arguments");
   const int64_t total = M * C;
   const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
@@ -201,8 +205,9 @@ __global__ void sqdiff_sum_kernel(const float* __restrict__ x, Str4 xs, const fl
   if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
 }
 
-int sqdiff_sum_launch(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H,
-                      int W, float* out, hipStream_t st) {
+extern "C" int sininn_sqdiff_sum(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H,
+                                 int W, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(x && xs && out && B > 0 && C > 0 && H > 0 && W > 0, "sqdiff_sum: bad arguments");
   SININN_CHECK(!y || ys, "sqdiff_sum: y without strides");
   const int64_t total = (int64_t)B * C * H * W;
@@ -232,9 +237,10 @@ __global__ void sqdiff_bwd_kernel(const float* __restrict__ x, Str4 xs, const fl
   }
 }
 
-int sqdiff_bwd_launch(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H,
-                      int W, const float* scale, float gscale, float* gx, const int64_t gxs[4], float* gy,
-                      const int64_t gys[4], hipStream_t st) {
+extern "C" int sininn_sqdiff_bwd(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H,
+                                 int W, const float* scale, float gscale, float* gx, const int64_t gxs[4], float* gy,
+                                 const int64_t gys[4], void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(x && xs && scale && (gx || gy), "sqdiff_bwd: bad arguments");
   SININN_CHECK((!gx || gxs) && (!gy || gys) && (!y || ys), "sqdiff_bwd: missing strides");
   const int64_t total = (int64_t)B * C * H * W;
@@ -298,8 +304,9 @@ __global__ void mmd_slots_kernel(float* __restrict__ g, int n) {
   g[i] = s;
 }
 
-int mmd_gram_launch(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H,
-                    int W, float* g, hipStream_t st) {
+extern "C" int sininn_mmd_gram(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H,
+                               int W, float* g, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(x && y && xs && ys && g, "mmd_gram: null pointer");
   SININN_CHECK(B > 0 && B <= 64 && C > 0 && H > 0 && W > 0, "mmd_gram: batch must be in 1..64 (got %d)", B);
   const int64_t K = (int64_t)C * H * W;
@@ -382,7 +389,8 @@ __global__ void mmd_finish_kernel(const float* __restrict__ g, int B, int rev, f
   }
 }
 
-int mmd_finish_launch(const float* g, int B, int rev, float* out, float* coef, hipStream_t st) {
+extern "C" int sininn_mmd_finish(const float* g, int B, int rev, float* out, float* coef, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(g && out && B > 0 && B <= 64, "mmd_finish: bad arguments");
   hipLaunchKernelGGL(mmd_finish_kernel, dim3(1), dim3(256), (size_t)3 * B * B * sizeof(float), st, g, B, rev ? 1 : 0,
                      out, coef);
@@ -417,9 +425,10 @@ __global__ void mmd_bwd_kernel(const float* __restrict__ x, Str4 xs, const float
   }
 }
 
-int mmd_bwd_launch(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H, int W,
-                   const float* coef, const float* scale, float* gx, const int64_t gxs[4], float* gy,
-                   const int64_t gys[4], hipStream_t st) {
+extern "C" int sininn_mmd_bwd(const float* x, const int64_t xs[4], const float* y, const int64_t ys[4], int B, int C, int H, int W,
+                              const float* coef, const float* scale, float* gx, const int64_t gxs[4], float* gy,
+                              const int64_t gys[4], void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(x && y && xs && ys && coef && scale && (gx || gy), "mmd_bwd: bad arguments");
   SININN_CHECK((!gx || gxs) && (!gy || gys), "mmd_bwd: missing strides");
   const int64_t total = (int64_t)B * C * H * W;
@@ -472,8 +481,9 @@ __global__ void affine_warp_kernel(const float* __restrict__ img, Str4 is, const
   }
 }
 
-int affine_warp_launch(const float* img, const int64_t is[4], const float* theta, int B, int C, int H, int W, float* out,
-                       const int64_t os[4], const float* ref, const int64_t rs[4], float* sse, hipStream_t st) {
+extern "C" int sininn_affine_warp(const float* img, const int64_t is[4], const float* theta, int B, int C, int H, int W, float* out,
+                                  const int64_t os[4], const float* ref, const int64_t rs[4], float* sse, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(img && is && theta && out && os && B > 0 && C > 0 && H > 0 && W > 0, "affine_warp: bad arguments");
   SININN_CHECK((!ref || (rs && sse)), "affine_warp: ref needs strides and sse");
   const int64_t total = (int64_t)B * C * H * W;
@@ -506,8 +516,9 @@ __global__ void affine_warp_bwd_kernel(const float* __restrict__ gout, Str4 gs, 
   }
 }
 
-int affine_warp_bwd_launch(const float* gout, const int64_t gs[4], const float* theta, int B, int C, int H, int W,
-                           float* gimg, const int64_t gis[4], hipStream_t st) {
+extern "C" int sininn_affine_warp_bwd(const float* gout, const int64_t gs[4], const float* theta, int B, int C, int H, int W,
+                                      float* gimg, const int64_t gis[4], void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(gout && gs && theta && gimg && gis && B > 0 && C > 0 && H > 0 && W > 0, "affine_warp_bwd: bad arguments");
   const int64_t total = (int64_t)B * C * H * W;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
@@ -587,14 +598,14 @@ static int flow_warp_l1_launch_t(const T* img, const float* flow, const T* targe
   SININN_LAUNCH_CHECK("flow_warp_l1");
   return 0;
 }
-int flow_warp_l1_launch(const float* img, const float* flow, const float* target, int B, int C, int H, int W,
-                        float* warped, float* metric, hipStream_t st) {
-  return flow_warp_l1_launch_t<float>(img, flow, target, B, C, H, W, warped, metric, st);
+extern "C" int sininn_flow_warp_l1(const float* img, const float* flow, const float* target, int B, int C, int H, int W,
+                                   float* warped, float* metric, void* stream) {
+  return flow_warp_l1_launch_t<float>(img, flow, target, B, C, H, W, warped, metric, ST(stream));
 }
-int flow_warp_l1_bf16_launch(const void* img, const float* flow, const void* target, int B, int C, int H, int W,
-                             void* warped, float* metric, hipStream_t st) {
+extern "C" int sininn_flow_warp_l1_bf16(const void* img, const float* flow, const void* target, int B, int C, int H, int W,
+                                        void* warped, float* metric, void* stream) {
   return flow_warp_l1_launch_t<__bf16>(static_cast<const __bf16*>(img), flow, static_cast<const __bf16*>(target), B, C, H, W,
-                                       static_cast<__bf16*>(warped), metric, st);
+                                       static_cast<__bf16*>(warped), metric, ST(stream));
 }
 
 template <typename T>
@@ -745,17 +756,17 @@ static int flow_warp_l1_bwd_launch_t(const T* img, const float* flow, const T* t
   SININN_LAUNCH_CHECK("flow_warp_l1_bwd");
   return 0;
 }
-int flow_warp_l1_bwd_launch(const float* img, const float* flow, const float* target, const float* warped,
-                            const float* gwarped, const float* gmetric, int B, int C, int H, int W, float* gimg,
-                            float* gflow, hipStream_t st) {
-  return flow_warp_l1_bwd_launch_t<float>(img, flow, target, warped, gwarped, gmetric, B, C, H, W, gimg, gflow, st);
+extern "C" int sininn_flow_warp_l1_bwd(const float* img, const float* flow, const float* target, const float* warped,
+                                       const float* gwarped, const float* gmetric, int B, int C, int H, int W, float* gimg,
+                                       float* gflow, void* stream) {
+  return flow_warp_l1_bwd_launch_t<float>(img, flow, target, warped, gwarped, gmetric, B, C, H, W, gimg, gflow, ST(stream));
 }
-int flow_warp_l1_bwd_bf16_launch(const void* img, const float* flow, const void* target, const void* warped,
-                                 const void* gwarped, const float* gmetric, int B, int C, int H, int W, float* gimg,
-                                 float* gflow, hipStream_t st) {
+extern "C" int sininn_flow_warp_l1_bwd_bf16(const void* img, const float* flow, const void* target, const void* warped,
+                                            const void* gwarped, const float* gmetric, int B, int C, int H, int W, float* gimg,
+                                            float* gflow, void* stream) {
   typedef const __bf16* P;
   return flow_warp_l1_bwd_launch_t<__bf16>(static_cast<P>(img), flow, static_cast<P>(target), static_cast<P>(warped),
-                                           static_cast<P>(gwarped), gmetric, B, C, H, W, gimg, gflow, st);
+                                           static_cast<P>(gwarped), gmetric, B, C, H, W, gimg, gflow, ST(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -789,13 +800,10 @@ __global__ void sample_windows_kernel(const uint8_t* __restrict__ hr_clip, const
   }
 }
 
-bool sample_windows_dense_try(const uint8_t* hr_clip, const uint8_t* lr_clip, const int* idx, int n, int T, int H, int W, int h,
-                              int w, int win, float* hr_out, const int64_t hs[4], float* lr_out, const int64_t ls[4],
-                              hipStream_t st);
-
-int sample_windows_launch(const uint8_t* hr_clip, const uint8_t* lr_clip, const int* idx, int n, int T, int H, int W,
-                          int h, int w, int win, float* hr_out, const int64_t hs[4], float* lr_out,
-                          const int64_t ls[4], hipStream_t st) {
+extern "C" int sininn_sample_windows(const uint8_t* hr_clip, const uint8_t* lr_clip, const int* idx, int n, int T, int H, int W,
+                                     int h, int w, int win, float* hr_out, const int64_t hs[4], float* lr_out,
+                                     const int64_t ls[4], void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(hr_clip && lr_clip && idx && hr_out && lr_out && hs && ls, "sample_windows: null pointer");
   SININN_CHECK(n > 0 && T > 0 && H > 0 && W > 0 && h > 0 && w > 0 && win >= 0, "sample_windows: bad shape");
   if (sample_windows_dense_try(hr_clip, lr_clip, idx, n, T, H, W, h, w, win, hr_out, hs, lr_out, ls, st)) {
@@ -837,8 +845,9 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   for (int64_t i = (n4 << 2) + tid; i < n; i += stride) upd(p[i], g[i], m[i], v[i]);
 }
 
-int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
-                float wd, int step, float gscale, hipStream_t st) {
+extern "C" int sininn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                                float wd, int step, float gscale, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(p && g && m && v && n > 0 && step >= 1, "adam: bad arguments");
   SININN_CHECK(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adam: buffers must be 16-byte aligned");
   // bias corrections in double like torch.optim.Adam's python-float arithmetic
@@ -885,8 +894,9 @@ __global__ void haar_kernel(const float* __restrict__ in, Str4 is, float* __rest
   }
 }
 
-int haar_launch(const float* in, const int64_t is[4], float* out, const int64_t os[4], int B, int C, int H, int W,
-                int inverse, hipStream_t st) {
+extern "C" int sininn_haar(const float* in, const int64_t is[4], float* out, const int64_t os[4], int B, int C, int H, int W,
+                           int inverse, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && out && is && os && B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, "haar: bad arguments");
   const int64_t total = (int64_t)B * C * (H / 2) * (W / 2);
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
@@ -907,7 +917,8 @@ __global__ void lrelu_bwd_kernel(float* __restrict__ g, int g_stride, const floa
   }
 }
 
-int lrelu_bwd_launch(float* g, int g_stride, const float* f, int f_stride, int64_t M, int n, float slope, hipStream_t st) {
+extern "C" int sininn_lrelu_bwd(float* g, int g_stride, const float* f, int f_stride, int64_t M, int n, float slope, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(g && f && M > 0 && n > 0 && g_stride >= n && f_stride >= n, "lrelu_bwd: bad arguments");
   const int64_t total = M * n;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
@@ -961,8 +972,9 @@ __global__ void irn_tail_kernel(const float* __restrict__ v, int v_stride, const
   }
 }
 
-int irn_tail_launch(const float* v, int v_stride, const float* h, const float* g, int64_t M, int Co, float clamp, int inverse,
-                    float* out, int out_stride, hipStream_t st) {
+extern "C" int sininn_irn_tail(const float* v, int v_stride, const float* h, const float* g, int64_t M, int Co, float clamp, int inverse,
+                               float* out, int out_stride, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(v && h && g && out && M > 0 && Co > 0 && Co % 4 == 0 && clamp > 0.f, "irn_tail: bad arguments");
   SININN_CHECK(v_stride >= Co && out_stride >= Co && v_stride % 4 == 0 && out_stride % 4 == 0, "irn_tail: strides");
   SININN_CHECK(aligned16(v) && aligned16(h) && aligned16(g) && aligned16(out), "irn_tail: 16-byte alignment");
@@ -986,6 +998,12 @@ int irn_coupling_bwd_launch(const float* dy, int dy_stride, const float* vy, int
                      Co, clamp, inverse, dG, dG_stride, dG_pad, dh, dv, dv_stride);
   SININN_LAUNCH_CHECK("irn_coupling_bwd");
   return 0;
+}
+extern "C" int sininn_irn_coupling_bwd(const float* dy, int dy_stride, const float* vy, int vy_stride, const float* hval, int64_t M,
+                                       int Co, float clamp, int inverse, float* dG, float* dh, float* dv, int dv_stride,
+                                       void* stream) {
+  return irn_coupling_bwd_launch(dy, dy_stride, vy, vy_stride, hval, M, Co, clamp, inverse, dG, Co, Co, dh, dv, dv_stride,
+                                 ST(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1022,7 +1040,8 @@ __global__ void bayer_bin_kernel(const uint8_t* __restrict__ hr, uint8_t* __rest
   }
 }
 
-int bayer_bin_launch(const uint8_t* hr, uint8_t* lr, int T, int H, int W, int scale, int reduce_sum, hipStream_t st) {
+extern "C" int sininn_bayer_bin(const uint8_t* hr, uint8_t* lr, int T, int H, int W, int scale, int reduce_sum, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(hr && lr && T > 0 && H > 0 && W > 0 && scale > 0, "bayer_bin: bad arguments");
   SININN_CHECK(H % (2 * scale) == 0 && W % (2 * scale) == 0, "bayer_bin: H and W must be multiples of 2*scale (prepare.py:152)");
   const int64_t total = (int64_t)T * (H / (2 * scale)) * (W / (2 * scale)) * 4;
@@ -1089,7 +1108,8 @@ __global__ void bayer_demosaic_kernel(const uint8_t* __restrict__ hr, uint8_t* _
   }
 }
 
-int bayer_demosaic_launch(const uint8_t* hr, uint8_t* rgb, int T, int H, int W, int scale, int reduce_sum, hipStream_t st) {
+extern "C" int sininn_bayer_demosaic(const uint8_t* hr, uint8_t* rgb, int T, int H, int W, int scale, int reduce_sum, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(hr && rgb && T > 0 && H > 0 && W > 0 && scale > 0, "bayer_demosaic: bad arguments");
   SININN_CHECK(H % (2 * scale) == 0 && W % (2 * scale) == 0, "bayer_demosaic: H and W must be multiples of 2*scale (prepare.py:152)");
   const int64_t total = (int64_t)T * (H / scale) * (W / scale);
@@ -1160,7 +1180,8 @@ __host__ __device__ static inline void pack_regions(const sininn_pack_desc& d, i
   nb = d.b_fwd ? d.Np : 0;
 }
 
-int pack_work_items(const sininn_pack_desc* d) {
+extern "C" int sininn_pack_work_items(const sininn_pack_desc* d) {
+  if (!d) return 0;
   int nf, nd, nb;
   pack_regions(*d, nf, nd, nb);
   return nf + nd + nb;
@@ -1233,15 +1254,17 @@ __global__ void pack_batch_kernel(const sininn_pack_desc* __restrict__ descs, in
   }
 }
 
-int pack_batch_launch(const sininn_pack_desc* descs, int n, int total, hipStream_t st) {
+extern "C" int sininn_pack_batch(const sininn_pack_desc* descs, int n, int total, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(descs != nullptr && n > 0 && total > 0, "pack_batch: bad arguments");
   hipLaunchKernelGGL(pack_batch_kernel, dim3((total + 255) / 256), dim3(256), 0, st, descs, n, total);
   SININN_LAUNCH_CHECK("pack_batch");
   return 0;
 }
 
-int pack_winograd_launch(const float* w, int N, int Cin, const int* colmap, int Np, float* u_fwd, int Cdp,
-                         float* u_dgrad, hipStream_t st) {
+extern "C" int sininn_pack_winograd(const float* w, int N, int Cin, const int* colmap, int Np, float* u_fwd, int Cdp,
+                                    float* u_dgrad, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(w != nullptr && N > 0 && Cin > 0 && (u_fwd || u_dgrad), "pack_winograd: bad arguments");
   SININN_CHECK(!u_fwd || Np >= 1, "pack_winograd: bad Np");
   SININN_CHECK(!u_dgrad || Cdp >= Cin, "pack_winograd: Cdp < Cin");

@@ -248,9 +248,10 @@ static int flow_gather_run(const char* who, const float* i0, const float* i1, co
   return 0;
 }
 
-int flow_gather_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
-                       const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, hipStream_t st) {
-  return flow_gather_run<false>("flow_gather", i0, i1, flows, flow_sample_stride, slots, tau, B, K, C, H, W, k_loop, out, out_u8, {}, st);
+extern "C" int sininn_flow_gather(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                                  const float* tau, int B, int K, int C, int H, int W, int k_loop, float* out, uint8_t* out_u8, void* stream) {
+  return flow_gather_run<false>("flow_gather", i0, i1, flows, flow_sample_stride, slots, tau, B, K, C, H, W, k_loop, out, out_u8, {},
+                                ST(stream));
 }
 
 // [p, p + n) and [q, q + m) in bytes share nothing
@@ -260,9 +261,10 @@ static bool gather_apart(const void* p, int64_t n, const void* q, int64_t m) {
 }
 
 // The masked rule: the plain call's checks, then the masks -- present, readable as floats, and not inside what is written.
-int flow_gather_visible_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
-                               const float* tau, const float* m0, const float* m1, int B, int K, int C, int H, int W, int k_loop,
-                               float* out, uint8_t* out_u8, hipStream_t st) {
+extern "C" int sininn_flow_gather_visible(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                                          const float* tau, const float* m0, const float* m1, int B, int K, int C, int H, int W, int k_loop,
+                                          float* out, uint8_t* out_u8, void* stream) {
+  hipStream_t st = ST(stream);
   const char* who = "flow_gather_visible";
   SININN_CHECK(m0 && m1, "%s: a visibility mask is null", who);
   SININN_CHECK(((uintptr_t)m0 & 3) == 0 && ((uintptr_t)m1 & 3) == 0, "%s: the masks are fp32 planes and must be 4-byte aligned", who);
@@ -341,16 +343,17 @@ __global__ __launch_bounds__(FG_THREADS) void flowgather_reduce_kernel(const flo
   dflows[(int64_t)p.frame * HW + p.r] = sum;
 }
 
-int64_t flow_gather_bwd_workspace(int B, int K, int H, int W) {
+extern "C" int64_t sininn_flow_gather_bwd_workspace(int B, int K, int H, int W) {
   if (B <= 0 || K <= 0 || H <= 0 || W <= 0) return 0;
   const int64_t HW = (int64_t)H * W;
   if ((int64_t)B * K * 4 > INT64_MAX / HW) return 0;
   return (int64_t)B * K * 4 * HW;
 }
 
-int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
-                           const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
-                           int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, hipStream_t st) {
+extern "C" int sininn_flow_gather_bwd(const float* i0, const float* i1, const float* flows, int64_t flow_sample_stride, const int* slots,
+                                      const float* tau, const float* grad_out, int B, int K, int C, int H, int W, int T, const int* reduce_list,
+                                      int64_t reduce_ints, float* workspace, int64_t workspace_floats, float* dflows, void* stream) {
+  hipStream_t st = ST(stream);
   if (flow_gather_check("flow_gather_bwd", i0, i1, flows, slots, tau, flow_sample_stride, B, K, C, H, W, 4)) return 1;
   SININN_CHECK(grad_out, "flow_gather_bwd: the gradient of the output is null");
   SININN_CHECK(dflows, "flow_gather_bwd: the gradient of the flows is null");
@@ -360,9 +363,9 @@ int flow_gather_bwd_launch(const float* i0, const float* i1, const float* flows,
                (long long)T * 4 * HW);
   if (reduce_list) {
     SININN_CHECK(workspace, "flow_gather_bwd: the workspace is null");
-    SININN_CHECK(workspace_floats >= flow_gather_bwd_workspace(B, K, H, W),
+    SININN_CHECK(workspace_floats >= sininn_flow_gather_bwd_workspace(B, K, H, W),
                  "flow_gather_bwd: the workspace holds %lld floats, %lld are needed", (long long)workspace_floats,
-                 (long long)flow_gather_bwd_workspace(B, K, H, W));
+                 (long long)sininn_flow_gather_bwd_workspace(B, K, H, W));
     SININN_CHECK(reduce_ints >= 2 * (int64_t)T + 1 && reduce_ints <= 2 * (int64_t)T + 1 + 2 * (int64_t)B * K,
                  "flow_gather_bwd: a reduce list of %lld ints; 2 T + 1 begins and at most 2 B K entries are expected",
                  (long long)reduce_ints);
@@ -548,9 +551,10 @@ static GatherBlend flow_gather_at_blend(const float* blend, int R) {
   return v;
 }
 
-int flow_gather_at_launch(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
-                          const uint8_t* rev, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W, float* out,
-                          hipStream_t st) {
+extern "C" int sininn_flow_gather_at(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                                     const uint8_t* rev, const float* blend, int R, int S, int64_t N, int B, int C, int H, int W, float* out,
+                                     void* stream) {
+  hipStream_t st = ST(stream);
   if (flow_gather_at_check("flow_gather_at", i0, i1, flows, pix, pair, tau, blend, R, S, N, B, C, H, W)) return 1;
   SININN_CHECK(out, "flow_gather_at: null pointer");
   const dim3 grid((unsigned)gather_tiles(N)), block(FG_THREADS);
@@ -563,9 +567,10 @@ int flow_gather_at_launch(const float* i0, const float* i1, const float* flows, 
   return 0;
 }
 
-int flow_gather_at_bwd_launch(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
-                              const uint8_t* rev, const float* blend, const float* grad_out, int R, int S, int64_t N, int B, int C,
-                              int H, int W, float* dflows, hipStream_t st) {
+extern "C" int sininn_flow_gather_at_bwd(const float* i0, const float* i1, const float* flows, const float* pix, const int* pair, const float* tau,
+                                         const uint8_t* rev, const float* blend, const float* grad_out, int R, int S, int64_t N, int B, int C,
+                                         int H, int W, float* dflows, void* stream) {
+  hipStream_t st = ST(stream);
   if (flow_gather_at_check("flow_gather_at_bwd", i0, i1, flows, pix, pair, tau, blend, R, S, N, B, C, H, W)) return 1;
   SININN_CHECK(grad_out, "flow_gather_at_bwd: the gradient of the output is null");
   SININN_CHECK(dflows, "flow_gather_at_bwd: the gradient of the flows is null");

@@ -112,7 +112,8 @@ __global__ void softsplat_bwd_kernel(const float* __restrict__ in, const float* 
   if (gflow) { gflow[(b * 2 + 0) * HW + r] = gfx; gflow[(b * 2 + 1) * HW + r] = gfy; }
 }
 
-int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H, int W, float* out, hipStream_t st) {
+extern "C" int sininn_softsplat(const float* in, const float* flow, int B, int C, int H, int W, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && flow && out, "softsplat: null pointer");
   SININN_CHECK(B > 0 && C > 0 && H > 0 && W > 0, "softsplat: bad shape");
   const int tiles = B * ((H + SP_TY - 1) / SP_TY) * ((W + SP_TX - 1) / SP_TX);
@@ -121,8 +122,9 @@ int softsplat_fwd_launch(const float* in, const float* flow, int B, int C, int H
   return 0;
 }
 
-int softsplat_bwd_launch(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
-                         float* gflow, hipStream_t st) {
+extern "C" int sininn_softsplat_bwd(const float* in, const float* flow, const float* gout, int B, int C, int H, int W, float* gin,
+                                    float* gflow, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && flow && gout && (gin || gflow), "softsplat_bwd: null pointer");
   SININN_CHECK(B > 0 && C > 0 && H > 0 && W > 0, "softsplat_bwd: bad shape");
   const int64_t total = (int64_t)B * H * W;
@@ -142,8 +144,9 @@ __global__ void occlusion_mask_kernel(const float* __restrict__ corr, int64_t n,
   if (i < n) mask[i] = (corr[i] <= thresh) ? 0.f : 1.f;
 }
 
-int occlusion_wang_launch(const float* flow21, int B, int H, int W, float thresh, float* corr_zeroed, float* mask,
-                          hipStream_t st) {
+extern "C" int sininn_occlusion_wang(const float* flow21, int B, int H, int W, float thresh, float* corr_zeroed, float* mask,
+                                     void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(flow21 && corr_zeroed, "occlusion_wang: null pointer");
   SININN_CHECK(B > 0 && H > 0 && W > 0, "occlusion_wang: bad shape");
   const int64_t total = (int64_t)B * H * W;
@@ -311,8 +314,9 @@ __global__ void census_finish_kernel(float* __restrict__ acc, float weight, floa
   if (threadIdx.x == 0) { acc[0] = a; acc[1] = m; out[0] = weight * a / m; }
 }
 
-int census_fwd_launch(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int H, int W,
-                      int max_distance, float weight, float* acc_zeroed, float* out, hipStream_t st) {
+extern "C" int sininn_census(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int H, int W,
+                             int max_distance, float weight, float* acc_zeroed, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   const int MC = mask_channels;
   SININN_CHECK(MC == 1 || MC == 3, "census: mask must have 1 or 3 channels");
   SININN_CHECK(im1 && im2 && mask && acc_zeroed && out, "census: null pointer");
@@ -328,9 +332,10 @@ int census_fwd_launch(const float* im1, const float* im2, const float* mask, int
   return 0;
 }
 
-int census_bwd_launch(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int H, int W,
-                      int max_distance, float weight, const float* acc, const float* gscale, float* g1, float* g2,
-                      hipStream_t st) {
+extern "C" int sininn_census_bwd(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int H, int W,
+                                 int max_distance, float weight, const float* acc, const float* gscale, float* g1, float* g2,
+                                 void* stream) {
+  hipStream_t st = ST(stream);
   const int MC = mask_channels;
   SININN_CHECK(MC == 1 || MC == 3, "census_bwd: mask must have 1 or 3 channels");
   SININN_CHECK(im1 && im2 && mask && acc && (g1 || g2), "census_bwd: null pointer");
@@ -395,8 +400,9 @@ __global__ void masked_l1_bwd_kernel(const float* __restrict__ a, const float* _
   }
 }
 
-int masked_l1_fwd_launch(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int C, int H, int W,
-                         float weight, float* acc_zeroed, float* out, hipStream_t st) {
+extern "C" int sininn_masked_l1(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int C, int H, int W,
+                                float weight, float* acc_zeroed, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(im1 && im2 && mask && acc_zeroed && out, "masked_l1: null pointer");
   SININN_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && (mask_channels == 1 || mask_channels == C), "masked_l1: bad shape");
   const int64_t total = (int64_t)B * H * W;
@@ -410,8 +416,9 @@ int masked_l1_fwd_launch(const float* im1, const float* im2, const float* mask, 
   return 0;
 }
 
-int masked_l1_bwd_launch(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int C, int H, int W,
-                         float weight, const float* acc, const float* gscale, float* g1, float* g2, hipStream_t st) {
+extern "C" int sininn_masked_l1_bwd(const float* im1, const float* im2, const float* mask, int mask_channels, int B, int C, int H, int W,
+                                    float weight, const float* acc, const float* gscale, float* g1, float* g2, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(im1 && im2 && mask && acc && (g1 || g2), "masked_l1_bwd: null pointer");
   SININN_CHECK(B > 0 && C > 0 && H > 0 && W > 0 && (mask_channels == 1 || mask_channels == C), "masked_l1_bwd: bad shape");
   const int64_t total = (int64_t)B * C * H * W;
@@ -511,8 +518,9 @@ static int smooth_setup(SmoothDev& p, const float* img, const float* flow, int B
   return 0;
 }
 
-int smooth_fwd_launch(const float* img, const float* flow, int B, int C, int H, int W, int order, int gauss, float k,
-                      float weight, float* acc_zeroed, float* out, hipStream_t st) {
+extern "C" int sininn_bilateral_smooth(const float* img, const float* flow, int B, int C, int H, int W, int order, int gauss, float k,
+                                       float weight, float* acc_zeroed, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   SmoothDev p; float ch, cw;
   if (int rc = smooth_setup(p, img, flow, B, C, H, W, order, gauss, k, weight, ch, cw)) return rc;
   SININN_CHECK(acc_zeroed && out, "smooth: null pointer");
@@ -525,8 +533,9 @@ int smooth_fwd_launch(const float* img, const float* flow, int B, int C, int H, 
   return 0;
 }
 
-int smooth_bwd_launch(const float* img, const float* flow, int B, int C, int H, int W, int order, int gauss, float k,
-                      float weight, const float* gscale, float* gflow, hipStream_t st) {
+extern "C" int sininn_bilateral_smooth_bwd(const float* img, const float* flow, int B, int C, int H, int W, int order, int gauss, float k,
+                                           float weight, const float* gscale, float* gflow, void* stream) {
+  hipStream_t st = ST(stream);
   SmoothDev p; float ch, cw;
   if (int rc = smooth_setup(p, img, flow, B, C, H, W, order, gauss, k, weight, ch, cw)) return rc;
   SININN_CHECK(gflow, "smooth_bwd: null pointer");
@@ -661,8 +670,9 @@ static int ssim_check(const float* im1, const float* im2, const float* mask, int
   return 0;
 }
 
-int ssim_fwd_launch(const float* im1, const float* im2, const float* mask, int MC, int B, int C, int H, int W, int md,
-                    float weight, float* acc_zeroed, float* out, hipStream_t st) {
+extern "C" int sininn_ssim(const float* im1, const float* im2, const float* mask, int MC, int B, int C, int H, int W, int md,
+                           float weight, float* acc_zeroed, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = ssim_check(im1, im2, mask, MC, B, C, H, W, md)) return rc;
   SININN_CHECK(acc_zeroed && out, "ssim: null pointer");
   const int Ho = H - 2 * md, Wo = W - 2 * md, TW = SS_T + 2 * md;
@@ -677,8 +687,9 @@ int ssim_fwd_launch(const float* im1, const float* im2, const float* mask, int M
   return 0;
 }
 
-int ssim_bwd_launch(const float* im1, const float* im2, const float* mask, int MC, int B, int C, int H, int W, int md,
-                    float weight, const float* acc, const float* gscale, float* g1, float* g2, hipStream_t st) {
+extern "C" int sininn_ssim_bwd(const float* im1, const float* im2, const float* mask, int MC, int B, int C, int H, int W, int md,
+                               float weight, const float* acc, const float* gscale, float* g1, float* g2, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = ssim_check(im1, im2, mask, MC, B, C, H, W, md)) return rc;
   SININN_CHECK(acc && (g1 || g2), "ssim_bwd: null pointer");
   const int Ho = H - 2 * md, Wo = W - 2 * md, TW = SS_T + 4 * md;
@@ -708,7 +719,8 @@ __global__ void brox_mask_kernel(const float* __restrict__ fw, const float* __re
   mask[idx] = sq_sum >= 0.01f * sum_sq + 0.5f ? 1 : 0;
 }
 
-int brox_mask_launch(const float* fw, const float* warped_bw, int B, int H, int W, uint8_t* mask, hipStream_t st) {
+extern "C" int sininn_occlusion_brox(const float* fw, const float* warped_bw, int B, int H, int W, uint8_t* mask, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(fw && warped_bw && mask && B > 0 && H > 0 && W > 0, "occlusion_brox: bad arguments");
   const int64_t total = (int64_t)B * H * W;
   hipLaunchKernelGGL(brox_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, fw, warped_bw, B, H, W, mask);

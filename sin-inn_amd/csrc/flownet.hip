@@ -1360,7 +1360,7 @@ int hidden_wgrad_launch(int ntiles, const float* dh, const float* in, float* par
 }
 
 // the support table; a refusal leaves its reason, with the table, as the library's last error
-int flownet_supported(const sininn_flownet_args* a, const char* who);
+static int flownet_supported(const sininn_flownet_args* a, const char* who);
 
 // two coordinates per point (domain_dim = 2): the encodings whose Enc<> row says PAIR, 512 wide, progressive 514
 static int flownet_supported_pair(const sininn_flownet_args* a, const char* who) {
@@ -1387,7 +1387,7 @@ static int flownet_supported_pair(const sininn_flownet_args* a, const char* who)
   return ok;
 }
 
-int flownet_supported_dim(const sininn_flownet_args* a, int dim, const char* who) {
+static int flownet_supported_dim(const sininn_flownet_args* a, int dim, const char* who) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
   if (dim == FN_DOM) return flownet_supported(a, who);
   if (dim == 2) return flownet_supported_pair(a, who);
@@ -1395,7 +1395,7 @@ int flownet_supported_dim(const sininn_flownet_args* a, int dim, const char* who
   return 0;
 }
 
-int flownet_supported(const sininn_flownet_args* a, const char* who) {
+static int flownet_supported(const sininn_flownet_args* a, const char* who) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
   const bool prog = a->progressive == 1;
   const bool ok = (a->progressive == 0 || prog) && a->hidden == FN_HID && a->layers == 3 && a->out_dim == FN_OUT &&
@@ -1419,23 +1419,28 @@ int flownet_supported(const sininn_flownet_args* a, const char* who) {
   return ok;
 }
 
-size_t flownet_forward_workspace_bytes(const sininn_flownet_args* a) {
+extern "C" int sininn_flownet_supported(const sininn_flownet_args* a) { return flownet_supported(a, "sininn_flownet_supported"); }
+extern "C" int sininn_flownet_supported_dim(const sininn_flownet_args* a, int dim) {
+  return flownet_supported_dim(a, dim, "sininn_flownet_supported_dim");
+}
+
+extern "C" size_t sininn_flownet_forward_workspace_bytes(const sininn_flownet_args* a) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args) || !a->progressive) return 0;   // plain PE reads W1 in place
   return for_kind(a->encoding, (size_t)0, [](auto k) { return Enc<decltype(k)::value>::PACK_FLOATS * sizeof(float); });
 }
 
-size_t flownet_saved_bytes(int64_t n) {
+extern "C" size_t sininn_flownet_saved_bytes(int64_t n) {
   if (n <= 0) return 0;
   return (size_t)3 * (size_t)((n + FN_P - 1) / FN_P) * FN_P * FN_HID * sizeof(float);
 }
 
-size_t flownet_workspace_bytes(int64_t n) {
+extern "C" size_t sininn_flownet_workspace_bytes(int64_t n) {
   if (n <= 0 || n > ((int64_t)1 << 22)) return 0;
   const int ntiles = (int)((n + FN_P - 1) / FN_P);
-  return flownet_saved_bytes(n) + ((size_t)2 * FN_HID * FN_HID + part_floats(ntiles)) * sizeof(float);
+  return sininn_flownet_saved_bytes(n) + ((size_t)2 * FN_HID * FN_HID + part_floats(ntiles)) * sizeof(float);
 }
 
-size_t flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
+extern "C" size_t sininn_flownet_encgrad_workspace_bytes(const sininn_flownet_args* a) {
   const bool has = a != nullptr && a->struct_bytes == sizeof(sininn_flownet_args) &&
                    for_kind(a->encoding, false, [](auto k) { return Enc<decltype(k)::value>::FREQ_GRAD; });
   return has ? FN_EG_FLOATS * sizeof(float) : 0;
@@ -1570,7 +1575,7 @@ static int backward_launch(const sininn_flownet_args* a, const Call& c, float* e
   const char* const who = c.has(SININN_FLOWNET_POSEGRAD) || (spatial && pl) ? c.who() : nullptr;
   FlowNetDev q;
   if (int rc = fill_args(a, who ? who : spatial ? "flownet_backward_spatial" : pl ? "flownet_backward_points" : "flownet_backward", q, spatial, pl, dim)) return rc;
-  if (int rc = check_backward_buffers<4>(a, who ? who : pl ? "flownet_backward_points" : "flownet_backward", flownet_saved_bytes(q.N), flownet_workspace_bytes(q.N), q))
+  if (int rc = check_backward_buffers<4>(a, who ? who : pl ? "flownet_backward_points" : "flownet_backward", sininn_flownet_saved_bytes(q.N), sininn_flownet_workspace_bytes(q.N), q))
     return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
@@ -1622,8 +1627,8 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
   using E = Enc<KIND>;
   constexpr const char* who = SPATIAL ? "flownet_forward_spatial" : "flownet_forward";
   if constexpr (PROG && !SPATIAL) {
-    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
-                 "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", flownet_forward_workspace_bytes(a),
+    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= sininn_flownet_forward_workspace_bytes(a),
+                 "flownet_forward: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", sininn_flownet_forward_workspace_bytes(a),
                  a->workspace ? a->workspace_bytes : (size_t)0);
     SININN_CHECK(aligned16(a->workspace), "flownet_forward: workspace must be 16-byte aligned");
     float* const w1p = static_cast<float*>(a->workspace);
@@ -1642,7 +1647,8 @@ static int forward_kind_launch(const sininn_flownet_args* a, FlowNetDev& q, hipS
   return 0;
 }
 
-int flownet_forward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, hipStream_t st) {
+extern "C" int sininn_flownet_forward(const sininn_flownet_args* a, const sininn_flownet_call* call, void* stream) {
+  hipStream_t st = ST(stream);
   Call c;
   if (int rc = check_call(call, "flownet", CALL_FORWARD, c)) return rc;
   const SpatialArgs* const spatial = c.spatial();
@@ -1652,7 +1658,7 @@ int flownet_forward_launch(const sininn_flownet_args* a, const sininn_flownet_ca
   FlowNetDev q;
   if (int rc = check_head(a, who, spatial, dim)) return rc;
   if (int rc = fill_args(a, who, q, spatial, pl, dim)) return rc;
-  if (int rc = check_forward_buffers(a, pl ? who : "flownet_forward", flownet_saved_bytes(q.N), q)) return rc;
+  if (int rc = check_forward_buffers(a, pl ? who : "flownet_forward", sininn_flownet_saved_bytes(q.N), q)) return rc;
   if (dim == 2)
     return for_pair(a, [&](auto k, auto prog) { return forward_kind_launch<decltype(k)::value, decltype(prog)::value, false, 2>(a, q, st); });
   return for_mode(a, spatial != nullptr, [&](auto k, auto prog, auto sp) {
@@ -1660,7 +1666,8 @@ int flownet_forward_launch(const sininn_flownet_args* a, const sininn_flownet_ca
   });
 }
 
-int flownet_sample_mask_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, float* out, hipStream_t st) {
+extern "C" int sininn_flownet_sample_mask(const sininn_flownet_args* a, const sininn_flownet_call* call, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   Call c;
   if (int rc = check_call(call, "flownet", CALL_SAMPLE_MASK, c)) return rc;
   const char* const who = c.who();
@@ -1680,12 +1687,12 @@ int flownet_sample_mask_launch(const sininn_flownet_args* a, const sininn_flowne
 static int backward_encgrad_launch(const sininn_flownet_args* a, const Call& c, hipStream_t st) {
   const char* const who = c.who();
   if (int rc = check_head(a, who, c.spatial())) return rc;
-  SININN_CHECK(flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
+  SININN_CHECK(sininn_flownet_encgrad_workspace_bytes(a) != 0, "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only", who,
                a->encoding);
   SININN_CHECK(c.c.g_enc_a != nullptr, "%s: null g_enc_a", who);
-  SININN_CHECK(c.c.enc_workspace != nullptr && c.c.enc_workspace_bytes >= flownet_encgrad_workspace_bytes(a),
+  SININN_CHECK(c.c.enc_workspace != nullptr && c.c.enc_workspace_bytes >= sininn_flownet_encgrad_workspace_bytes(a),
                "%s: enc_workspace holds %zu bytes, %zu needed", who, c.c.enc_workspace ? c.c.enc_workspace_bytes : (size_t)0,
-               flownet_encgrad_workspace_bytes(a));
+               sininn_flownet_encgrad_workspace_bytes(a));
   SININN_CHECK(aligned16(c.c.enc_workspace), "%s: enc_workspace must be 16-byte aligned", who);
   return backward_launch(a, c, static_cast<float*>(c.c.enc_workspace), st);
 }
@@ -1696,10 +1703,10 @@ static size_t posegrad_pack_bytes(const sininn_flownet_args* a) {
   return for_kind(a->encoding, (size_t)0, [](auto k) { return posegrad_pack_floats<decltype(k)::value>() * sizeof(float); });
 }
 
-size_t flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad) {
+extern "C" size_t sininn_flownet_posegrad_workspace_bytes(const sininn_flownet_args* a, int with_enc_grad) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
   const size_t pack = posegrad_pack_bytes(a);
-  return pack ? pack + (with_enc_grad ? flownet_encgrad_workspace_bytes(a) : 0) : 0;
+  return pack ? pack + (with_enc_grad ? sininn_flownet_encgrad_workspace_bytes(a) : 0) : 0;
 }
 
 // SPATIAL: the pack is unmasked and no global mask is read; the corner tile comes on top of posegrad_lds
@@ -1725,10 +1732,10 @@ static int backward_posegrad_launch(const sininn_flownet_args* a, const Call& c,
   const bool enc_grad = c.has(SININN_FLOWNET_ENCGRAD);
   if (int rc = check_head(a, who, c.spatial())) return rc;
   SININN_CHECK(c.c.g_poses != nullptr, "%s: null g_poses", who);
-  SININN_CHECK(!enc_grad || flownet_encgrad_workspace_bytes(a) != 0,
+  SININN_CHECK(!enc_grad || sininn_flownet_encgrad_workspace_bytes(a) != 0,
                "%s: encoding is %d; the gradient of enc_a exists for SININN_FLOWNET_FOURIER only (pass a null g_enc_a)", who, a->encoding);
   SININN_CHECK(!enc_grad || c.c.g_enc_a != nullptr, "%s: null g_enc_a", who);
-  const size_t need = flownet_posegrad_workspace_bytes(a, enc_grad);
+  const size_t need = sininn_flownet_posegrad_workspace_bytes(a, enc_grad);
   SININN_CHECK(c.c.extra_workspace != nullptr && c.c.extra_workspace_bytes >= need, "%s: extra_workspace holds %zu bytes, %zu needed", who,
                c.c.extra_workspace ? c.c.extra_workspace_bytes : (size_t)0, need);
   SININN_CHECK(aligned16(c.c.extra_workspace), "%s: extra_workspace must be 16-byte aligned", who);
@@ -1741,7 +1748,8 @@ static int backward_posegrad_launch(const sininn_flownet_args* a, const Call& c,
   });
 }
 
-int flownet_backward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, hipStream_t st) {
+extern "C" int sininn_flownet_backward(const sininn_flownet_args* a, const sininn_flownet_call* call, void* stream) {
+  hipStream_t st = ST(stream);
   Call c;
   if (int rc = check_call(call, "flownet", CALL_BACKWARD, c)) return rc;
   if (c.has(SININN_FLOWNET_POSEGRAD)) return backward_posegrad_launch(a, c, st);

@@ -320,17 +320,17 @@ int jac_ndirs(unsigned dirs) { return (int)((dirs & 1u) + ((dirs >> 1) & 1u) + (
 
 }  // namespace
 
-size_t flownet_jacobian_saved_bytes(int64_t n, int n_dirs) {
+extern "C" size_t sininn_flownet_jacobian_saved_bytes(int64_t n, int n_dirs) {
   if (n <= 0 || n_dirs < 1 || n_dirs > FN_DOM) return 0;
-  return (size_t)n_dirs * flownet_saved_bytes(n);
+  return (size_t)n_dirs * sininn_flownet_saved_bytes(n);
 }
 
 // dt [3][Npad][256], the partial sums of one launch, one scratch gradient per layer: the directions run one after the other
-size_t flownet_jacobian_workspace_bytes(const sininn_flownet_args* a, int64_t n, int n_dirs) {
+extern "C" size_t sininn_flownet_jacobian_workspace_bytes(const sininn_flownet_args* a, int64_t n, int n_dirs) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_flownet_args)) return 0;
   if (n <= 0 || n > ((int64_t)1 << 22) || n_dirs < 1 || n_dirs > FN_DOM) return 0;
   const int ntiles = (int)((n + FN_P - 1) / FN_P);
-  return flownet_saved_bytes(n) + (part_floats(ntiles) + JAC_SCRATCH) * sizeof(float);
+  return sininn_flownet_saved_bytes(n) + (part_floats(ntiles) + JAC_SCRATCH) * sizeof(float);
 }
 
 // the head of both entry points: the direction set, the call descriptor as this feature takes it, then the network.  Every refusal is one
@@ -368,23 +368,24 @@ static int for_jac(const sininn_flownet_args* a, F&& f) {
                         : f(std::integral_constant<int, SININN_FLOWNET_FOURIER>{}, std::false_type{});
 }
 
-int flownet_jacobian_forward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, unsigned dirs, float* jac, float* tsaved,
-                                    size_t tsaved_bytes, hipStream_t st) {
+extern "C" int sininn_flownet_jacobian_forward(const sininn_flownet_args* a, const sininn_flownet_call* call, unsigned dirs, float* jac,
+                                               float* tsaved, size_t tsaved_bytes, void* stream) {
+  hipStream_t st = ST(stream);
   const char* const who = "flownet_jacobian_forward";
   Call c;
   if (int rc = jac_check_head(a, call, dirs, who, CALL_FORWARD, c)) return rc;
   const int nd = jac_ndirs(dirs);
   SININN_CHECK(jac != nullptr && tsaved != nullptr, "%s: null jac / tsaved", who);
-  SININN_CHECK(tsaved_bytes >= flownet_jacobian_saved_bytes(c.points.n, nd), "%s: tsaved holds %zu bytes, %zu needed", who, tsaved_bytes,
-               flownet_jacobian_saved_bytes(c.points.n, nd));
+  SININN_CHECK(tsaved_bytes >= sininn_flownet_jacobian_saved_bytes(c.points.n, nd), "%s: tsaved holds %zu bytes, %zu needed", who, tsaved_bytes,
+               sininn_flownet_jacobian_saved_bytes(c.points.n, nd));
   SININN_CHECK(aligned16(tsaved) && ((uintptr_t)jac & 3u) == 0, "%s: tsaved must be 16-byte aligned, jac 4-byte aligned", who);
   SININN_CHECK(a->saved != nullptr, "%s: null saved: the tangent passes take their gates from the value pass's hidden layers", who);
   FlowNetDev q;
   if (int rc = fill_args(a, who, q, nullptr, c.pl())) return rc;
-  if (int rc = check_forward_buffers(a, "flownet_forward", flownet_saved_bytes(q.N), q)) return rc;
+  if (int rc = check_forward_buffers(a, "flownet_forward", sininn_flownet_saved_bytes(q.N), q)) return rc;
   if (a->progressive) {
-    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= flownet_forward_workspace_bytes(a),
-                 "%s: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", who, flownet_forward_workspace_bytes(a),
+    SININN_CHECK(a->workspace != nullptr && a->workspace_bytes >= sininn_flownet_forward_workspace_bytes(a),
+                 "%s: the progressive forward packs W1 into a workspace of %zu bytes, %zu given", who, sininn_flownet_forward_workspace_bytes(a),
                  a->workspace ? a->workspace_bytes : (size_t)0);
     SININN_CHECK(aligned16(a->workspace), "%s: workspace must be 16-byte aligned", who);
   }
@@ -392,7 +393,7 @@ int flownet_jacobian_forward_launch(const sininn_flownet_args* a, const sininn_f
   if (int rc = for_jac(a, [&](auto k, auto prog) { return raise_lds(flownet_jac_fwd_kernel<decltype(k)::value, decltype(prog)::value>, tile_lds(false), who); }))
     return rc;
   // the value pass: the plain training-mode call, with its own checks in front of its launches.  Nothing below it refuses
-  if (int rc = flownet_forward_launch(a, call, st)) return rc;
+  if (int rc = sininn_flownet_forward(a, call, st)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   return for_jac(a, [&](auto k, auto prog) {
     constexpr int KIND = decltype(k)::value;
@@ -418,24 +419,26 @@ int flownet_jacobian_forward_launch(const sininn_flownet_args* a, const sininn_f
   });
 }
 
-int flownet_jacobian_backward_launch(const sininn_flownet_args* a, const sininn_flownet_call* call, unsigned dirs, const float* djac,
-                                     const float* tsaved, size_t tsaved_bytes, void* jac_workspace, size_t jac_workspace_bytes, hipStream_t st) {
+extern "C" int sininn_flownet_jacobian_backward(const sininn_flownet_args* a, const sininn_flownet_call* call, unsigned dirs, const float* djac,
+                                                const float* tsaved, size_t tsaved_bytes, void* jac_workspace, size_t jac_workspace_bytes,
+                                                void* stream) {
+  hipStream_t st = ST(stream);
   const char* const who = "flownet_jacobian_backward";
   Call c;
   if (int rc = jac_check_head(a, call, dirs, who, CALL_BACKWARD, c)) return rc;
   const int nd = jac_ndirs(dirs);
   SININN_CHECK(djac != nullptr && tsaved != nullptr && jac_workspace != nullptr, "%s: null djac / tsaved / jac_workspace", who);
-  SININN_CHECK(tsaved_bytes >= flownet_jacobian_saved_bytes(c.points.n, nd), "%s: tsaved holds %zu bytes, %zu needed", who, tsaved_bytes,
-               flownet_jacobian_saved_bytes(c.points.n, nd));
-  SININN_CHECK(jac_workspace_bytes >= flownet_jacobian_workspace_bytes(a, c.points.n, nd), "%s: jac_workspace holds %zu bytes, %zu needed", who,
-               jac_workspace_bytes, flownet_jacobian_workspace_bytes(a, c.points.n, nd));
+  SININN_CHECK(tsaved_bytes >= sininn_flownet_jacobian_saved_bytes(c.points.n, nd), "%s: tsaved holds %zu bytes, %zu needed", who, tsaved_bytes,
+               sininn_flownet_jacobian_saved_bytes(c.points.n, nd));
+  SININN_CHECK(jac_workspace_bytes >= sininn_flownet_jacobian_workspace_bytes(a, c.points.n, nd), "%s: jac_workspace holds %zu bytes, %zu needed", who,
+               jac_workspace_bytes, sininn_flownet_jacobian_workspace_bytes(a, c.points.n, nd));
   SININN_CHECK(aligned16(tsaved) && aligned16(jac_workspace) && ((uintptr_t)djac & 3u) == 0,
                "%s: tsaved / jac_workspace must be 16-byte aligned, djac 4-byte aligned", who);
   SININN_CHECK(a->saved != nullptr, "%s: null saved: the gates are the value pass's hidden layers", who);
   {                                                    // the plain call's own host checks, ahead of the LDS limits: nothing is written before both
     FlowNetDev probe;
     if (int rc = fill_args(a, "flownet_backward_points", probe, nullptr, c.pl())) return rc;
-    if (int rc = check_backward_buffers<4>(a, "flownet_backward_points", flownet_saved_bytes(probe.N), flownet_workspace_bytes(probe.N), probe)) return rc;
+    if (int rc = check_backward_buffers<4>(a, "flownet_backward_points", sininn_flownet_saved_bytes(probe.N), sininn_flownet_workspace_bytes(probe.N), probe)) return rc;
   }
   if (raise_lds(flownet_jac_chain_kernel, tile_lds(false), who)) return 1;
   if (int rc = for_jac(a, [&](auto k, auto prog) { return raise_lds(flownet_jac_wgrad_kernel<decltype(k)::value, decltype(prog)::value>, FN_WG_LDS, who); }))

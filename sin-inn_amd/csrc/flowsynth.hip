@@ -142,18 +142,19 @@ __global__ void flowsynth_blend_kernel(const float* __restrict__ i0, const float
   }
 }
 
-int64_t flow_synth_workspace(int B, int K, int C, int H, int W) {
+extern "C" int64_t sininn_flow_synth_workspace(int B, int K, int C, int H, int W) {
   if (B <= 0 || K <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
   return (int64_t)B * K * 2 * (C + 1) * H * W;
 }
 
-int flow_synth_launch(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
-                      int H, int W, float* workspace, int64_t workspace_floats, float* out, uint8_t* out_u8, hipStream_t st) {
+extern "C" int sininn_flow_synth(const float* i0, const float* i1, const float* f01, const float* f10, const float* tau, int B, int K, int C,
+                                 int H, int W, float* workspace, int64_t workspace_floats, float* out, uint8_t* out_u8, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(i0 && i1 && f01 && f10 && tau && workspace && out, "flow_synth: null pointer");
   SININN_CHECK(B > 0 && K > 0 && C > 0 && H > 0 && W > 0, "flow_synth: bad shape (every size must be positive)");
   SININN_CHECK(K <= FS_MAX_K, "flow_synth: K = %d times in one call, at most %d", K, FS_MAX_K);
   SININN_CHECK(C == 1 || C == 3, "flow_synth: frames have 1 or 3 channels (got %d)", C);
-  const int64_t need = flow_synth_workspace(B, K, C, H, W);
+  const int64_t need = sininn_flow_synth_workspace(B, K, C, H, W);
   SININN_CHECK(workspace_floats >= need, "flow_synth: workspace of %lld floats, need %lld", (long long)workspace_floats,
                (long long)need);
   const int64_t total = (int64_t)B * K * H * W;

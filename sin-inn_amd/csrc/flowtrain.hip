@@ -325,19 +325,20 @@ static inline int64_t es_tiles(int w) { return ((int64_t)w + ES_TX - 1) / ES_TX;
 
 }  // namespace
 
-int64_t flow_epe_partials(int n, int h, int w) {
+extern "C" int64_t sininn_flow_epe_partials(int n, int h, int w) {
   if (!ft_dims_ok(n, h, w)) return 0;
   return ((int64_t)n * h * w + FT_THREADS - 1) / FT_THREADS;
 }
 
-int flow_epe_launch(const float* flow, int64_t flow_sample_stride, const float* gt, int n, int h, int w, double* partials,
-                    int64_t n_partials, float* out, hipStream_t st) {
+extern "C" int sininn_flow_epe(const float* flow, int64_t flow_sample_stride, const float* gt, int n, int h, int w, double* partials,
+                               int64_t n_partials, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(flow && gt && partials && out, "flow_epe: null pointer");
   SININN_CHECK(ft_dims_ok(n, h, w), "flow_epe: bad extents n=%d h=%d w=%d", n, h, w);
   const int64_t hw = (int64_t)h * w, total = (int64_t)n * hw;
   SININN_CHECK(flow_sample_stride >= 2 * hw, "flow_epe: sample stride %lld is smaller than two channel planes (%lld)",
                (long long)flow_sample_stride, (long long)(2 * hw));
-  const int64_t blocks = flow_epe_partials(n, h, w);
+  const int64_t blocks = sininn_flow_epe_partials(n, h, w);
   SININN_CHECK(blocks <= 0x7fffffff, "flow_epe: %lld pixels need more blocks than one launch has", (long long)total);
   SININN_CHECK(n_partials >= blocks, "flow_epe: the partial-sum buffer holds %lld doubles, needs %lld", (long long)n_partials,
                (long long)blocks);
@@ -350,7 +351,8 @@ int flow_epe_launch(const float* flow, int64_t flow_sample_stride, const float* 
   return 0;
 }
 
-int splat_mask_launch(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, hipStream_t st) {
+extern "C" int sininn_splat_mask(const float* mask, int mask_channels, const float* splat, int n, int c, int h, int w, float* out, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(mask && splat && out, "splat_mask: null pointer");
   SININN_CHECK(ft_dims_ok(n, h, w), "splat_mask: bad extents n=%d h=%d w=%d", n, h, w);
   SININN_CHECK(c == 3, "splat_mask: the splat has 3 channels (got %d)", c);
@@ -363,15 +365,18 @@ int splat_mask_launch(const float* mask, int mask_channels, const float* splat, 
   return 0;
 }
 
-int64_t flow_error_stash_workspace_floats(int B, int H, int W, int res) {
+extern "C" int64_t sininn_flow_error_stash_workspace_floats(int B, int H, int W, int res) {
   if (!ft_dims_ok(B, H, W) || res < 3 || res > ES_MAX_RES) return 0;
   return (int64_t)B * H * es_tiles(W) * res + (int64_t)B * res * res + 2 * (int64_t)res;   // R1, R2, Cy, Cx
 }
 
-int flow_error_stash_launch(const float* softmax1, const float* frame1, const float* mask1, const float* softmax2, const float* frame2,
-                            const float* mask2, int mask_channels, int B, int C, int H, int W, const float* times, const float* ys,
-                            const float* xs, int res, const float* centre, const float* scale, float* log_buffer, float* log_counter,
-                            float* e_out, float* workspace, int64_t workspace_floats, hipStream_t st) {
+extern "C" int sininn_flow_error_stash(const float* softmax1, const float* frame1, const float* mask1, const float* softmax2,
+                                       const float* frame2, const float* mask2, int mask_channels, int B, int C, int H, int W,
+                                       const float* times, const float* ys, const float* xs, int res, float centre_t, float centre_y,
+                                       float centre_x, float scale_t, float scale_y, float scale_x, float* log_buffer, float* log_counter,
+                                       float* e_out, float* workspace, int64_t workspace_floats, void* stream) {
+  hipStream_t st = ST(stream);
+  const float centre[3] = {centre_t, centre_y, centre_x}, scale[3] = {scale_t, scale_y, scale_x};
   SININN_CHECK(softmax1 && frame1 && mask1 && softmax2 && frame2 && mask2 && times && ys && xs && log_buffer && log_counter && workspace,
                "flow_error_stash: null pointer");
   SININN_CHECK(ft_dims_ok(B, H, W), "flow_error_stash: bad extents B=%d H=%d W=%d", B, H, W);
@@ -379,7 +384,7 @@ int flow_error_stash_launch(const float* softmax1, const float* frame1, const fl
   SININN_CHECK(C == 1 || C == 3, "flow_error_stash: the frames have 1 or 3 channels (got %d)", C);
   SININN_CHECK(mask_channels == 1 || mask_channels == C, "flow_error_stash: the masks have 1 or %d channels (got %d)", C, mask_channels);
   SININN_CHECK(H <= 65535 && B < 65535, "flow_error_stash: at most 65535 rows and 65534 frames per call (got H=%d B=%d)", H, B);
-  const int64_t need = flow_error_stash_workspace_floats(B, H, W, res);
+  const int64_t need = sininn_flow_error_stash_workspace_floats(B, H, W, res);
   SININN_CHECK(workspace_floats >= need, "flow_error_stash: workspace holds %lld floats, needs %lld", (long long)workspace_floats,
                (long long)need);
   const float* const ptrs[] = {softmax1, frame1, mask1, softmax2, frame2, mask2, times, ys, xs, log_buffer, log_counter, e_out, workspace};
@@ -403,14 +408,15 @@ int flow_error_stash_launch(const float* softmax1, const float* frame1, const fl
   return 0;
 }
 
-int64_t flow2img_workspace_floats(int n, int h, int w) {
+extern "C" int64_t sininn_flow2img_workspace_floats(int n, int h, int w) {
   if (!ft_dims_ok(n, h, w)) return 0;
   const int64_t bpf = ((int64_t)h * w + F2I_PIX - 1) / F2I_PIX;
   return (int64_t)n * bpf + n;                             // the partial maxima, then maxrad per frame
 }
 
-int flow2img_launch(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
-                    int64_t workspace_floats, uint8_t* img, hipStream_t st) {
+extern "C" int sininn_flow2img(const float* flow, int n, int h, int w, float clip, const double* wheel, int wheel_rows, float* workspace,
+                               int64_t workspace_floats, uint8_t* img, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(flow && wheel && workspace && img, "flow2img: null pointer");
   SININN_CHECK(ft_dims_ok(n, h, w), "flow2img: bad extents n=%d h=%d w=%d", n, h, w);
   SININN_CHECK(wheel_rows == F2I_NCOLS, "flow2img: the colour wheel has %d rows (got %d)", F2I_NCOLS, wheel_rows);
@@ -421,7 +427,7 @@ int flow2img_launch(const float* flow, int n, int h, int w, float clip, const do
   const int64_t bpf = (hw + F2I_PIX - 1) / F2I_PIX, cblocks = (hw + FT_THREADS - 1) / FT_THREADS;
   SININN_CHECK(n <= 65535, "flow2img: at most 65535 frames per call (got %d)", n);
   SININN_CHECK(cblocks <= 0x7fffffff, "flow2img: a frame of %lld pixels needs more blocks than one launch has", (long long)hw);
-  const int64_t need = flow2img_workspace_floats(n, h, w);
+  const int64_t need = sininn_flow2img_workspace_floats(n, h, w);
   SININN_CHECK(workspace_floats >= need, "flow2img: workspace holds %lld floats, needs %lld", (long long)workspace_floats, (long long)need);
   float* part = workspace;
   float* maxrad = workspace + (int64_t)n * bpf;

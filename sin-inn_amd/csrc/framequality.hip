@@ -175,19 +175,20 @@ static int64_t fq_blocks(int B, int C, int H, int W) {
   return (int64_t)B * C * tiles_y * tiles_x;
 }
 
-int64_t frame_quality_workspace_floats(int B, int C, int H, int W) {
+extern "C" int64_t sininn_frame_quality_workspace_floats(int B, int C, int H, int W) {
   if (!fq_shape_ok(B, C, H, W)) return 0;
   return 4 * fq_blocks(B, C, H, W);                     // two doubles per block
 }
 
-int frame_quality_launch(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
-                         float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, hipStream_t st) {
+extern "C" int sininn_frame_quality(const float* pred, const float* target, int B, int C, int H, int W, int quantize, const float* window,
+                                    float* workspace, int64_t workspace_floats, double* sqerr, float* out, float* ssim_map, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(pred && target && window && workspace && sqerr && out, "frame_quality: null pointer");
   SININN_CHECK(B > 0, "frame_quality: bad shape (B = %d must be positive)", B);
   SININN_CHECK(C == 1 || C == 3, "frame_quality: frames have 1 or 3 channels (got %d)", C);
   SININN_CHECK(H >= FQ_WIN && W >= FQ_WIN, "frame_quality: frames of %d x %d are smaller than the 11 x 11 window", H, W);
   SININN_CHECK(fq_shape_ok(B, C, H, W), "frame_quality: B * C * H * W = %lld is past an int index", (long long)B * C * H * W);
-  const int64_t need = frame_quality_workspace_floats(B, C, H, W);
+  const int64_t need = sininn_frame_quality_workspace_floats(B, C, H, W);
   SININN_CHECK(workspace_floats >= need, "frame_quality: workspace of %lld floats, need %lld", (long long)workspace_floats,
                (long long)need);
   SININN_CHECK((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sqerr) & 7u) == 0,

@@ -13,25 +13,6 @@
 
 namespace sininn {
 
-int conv_launch(const sininn_conv_args* a, hipStream_t st);
-int conv_pair_k1_supported(const sininn_conv_args* f, const sininn_conv_args* s);
-int conv_pair_k1_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
-int conv_pair_k1_preferred(const sininn_conv_args* f);
-int conv_sub3_bf16_supported(const sininn_conv_args* f, const sininn_conv_args* s);
-int conv_sub3_bf16_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
-bool sub3_fusion_enabled();
-size_t wgrad_workspace_bytes(int N, int Cin, int ksize, int B, int H, int W);
-int wgrad_launch(const float* in, int in_stride, int Cin, const float* dout, int dout_stride, int N, int B, int H, int W,
-                 int ksize, float* gw, float* gb, void* ws, size_t ws_bytes, hipStream_t st);
-size_t wgrad_group_workspace_bytes(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize);
-int wgrad_group_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
-                       hipStream_t st);
-bool wgrad_grouping_enabled();
-int wgrad_group_mode();
-int coupling_bwd_launch(const float* dy, int dy_stride, const int* dy_map, const float* vy, int vy_stride,
-                        const int* vy_map, const float* s, const float* gld, int B, int HW, int Co, float clamp,
-                        int inverse, float* dr, float* dv, int dv_stride, hipStream_t st);
-
 static inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }   // floats -> keeps 256-byte alignment
 static inline int pad16i(int n) { return (n + 15) / 16 * 16; }
 
@@ -40,27 +21,6 @@ static inline int pad16i(int n) { return (n + 15) / 16 * 16; }
 static std::mutex g_ev_mutex;
 struct EventRing { hipEvent_t ev[64]; bool ready = false; unsigned next = 0; };
 static EventRing g_rings[16];
-
-// conv_sub1.hip: the whole backward of a fp32 1x1 subnet in one persistent launch (h recomputed, dh on chip)
-int conv_sub1_bwd_shape_supported(int ksize, int dtype, int cond_cin, int co);
-size_t conv_sub1_bwd_workspace_bytes(int cond_cin, int co);
-int conv_sub1_bwd_launch(const sininn_conv_args* rc, const sininn_conv_args* d2, const sininn_conv_args* d1, int no_dx, void* ws,
-                         size_t ws_bytes, int* slabs_out, hipStream_t st);
-int conv_sub1_bwd_reduce(int cond_cin, int co, const void* ws, int slabs, float* gw2, float* gb2, float* gw1, float* gb1, hipStream_t st);
-int conv_sub1_fwd_supported(const sininn_conv_args* f, const sininn_conv_args* s);
-int conv_sub1_fwd_launch(const sininn_conv_args* f, const sininn_conv_args* s, hipStream_t st);
-// conv_sub1_bf16.hip: data gradients of a wide (level-1) 1x1 subnet + the weight gradient of its conv1 in one persistent launch
-size_t conv_sub1_bf16_wide_ws_bytes(int ksize, int dtype, int cond_cin, int co);
-int conv_sub1_bf16_wide_bwd_supported(const sininn_conv_args* d2, const sininn_conv_args* d1);
-int conv_sub1_bf16_wide_bwd_wg1_launch(const sininn_conv_args* d2, const sininn_conv_args* d1, const float* x, int x_stride, void* ws, size_t ws_bytes,
-                                       int* slabs_out, hipStream_t st);
-int conv_sub1_bf16_wide_reduce(const void* ws, int slabs, float* gw1, float* gb1, hipStream_t st);
-// conv3_smallk_bf16.hip: the small-K 3x3 convs of a level-0 subnet; `bits` = the ReLU gates as a bit mask [pixel][8] words
-int conv3_smallk_bf16_supported(const sininn_conv_args* a);
-int conv3_smallk_bf16_launch_bits(const sininn_conv_args* a, unsigned* bits, hipStream_t st);
-size_t conv_sub1_bf16_wide_wg2_ws_bytes(int ksize, int dtype, int cond_cin, int co);
-int conv_sub1_bf16_wide_wg2_launch(const float* dr, int dr_stride, const void* h, int h_stride, int B, int H, int W, void* ws, size_t ws_bytes,
-                                   float* gw2, float* gb2, hipStream_t st);
 
 int order_after(hipStream_t waiter, hipStream_t producer) {
   if (waiter == producer) return 0;
@@ -92,7 +52,7 @@ static int g_prof_max = 0;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_events;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_pool;
 
-void profile_begin(int h, unsigned long long* stamps, int max_launches) {
+extern "C" void sininn_profile_begin(int h, unsigned long long* stamps, int max_launches) {
   std::lock_guard<std::mutex> lock(g_ev_mutex);
   g_prof_stamps = stamps; g_prof_max = stamps ? max_launches : 0;
   for (auto& p : g_prof_events) g_prof_pool.push_back(p);
@@ -100,7 +60,7 @@ void profile_begin(int h, unsigned long long* stamps, int max_launches) {
   g_prof_h = h;
 }
 
-int profile_end(int* count, float* total_ms) {
+extern "C" int sininn_profile_end(int* count, float* total_ms) {
   std::lock_guard<std::mutex> lock(g_ev_mutex);
   g_prof_h = 0; g_prof_stamps = nullptr; g_prof_max = 0;
   float tot = 0.f;
@@ -143,14 +103,14 @@ static bool g_pc_on = false;
 static std::vector<ClassRec> g_pc_recs;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_pc_pool;
 
-void profile_classes_begin() {
+extern "C" void sininn_profile_classes_begin(void) {
   std::lock_guard<std::mutex> lock(g_ev_mutex);
   for (auto& r : g_pc_recs) g_pc_pool.push_back({r.a, r.b});
   g_pc_recs.clear();
   g_pc_on = true;
 }
 
-int profile_classes_end(int n, double* ms, double* flops, int* launches) {
+extern "C" int sininn_profile_classes_end(int n, double* ms, double* flops, int* launches) {
   std::lock_guard<std::mutex> lock(g_ev_mutex);
   g_pc_on = false;
   for (int i = 0; i < n; ++i) { ms[i] = 0.0; flops[i] = 0.0; launches[i] = 0; }
@@ -170,7 +130,7 @@ int profile_classes_end(int n, double* ms, double* flops, int* launches) {
 }
 
 // algorithmic HBM bytes per class summed over the launches of the last profile_classes_end (0 where a launch did not report them)
-int profile_classes_bytes(int n, double* bytes) {
+extern "C" int sininn_profile_classes_bytes(int n, double* bytes) {
   std::lock_guard<std::mutex> lock(g_ev_mutex);
   for (int i = 0; i < n; ++i) bytes[i] = i < PC_N ? g_pc_bytes[i] : 0.0;
   return 0;
@@ -205,10 +165,11 @@ static const bool g_group_major = getenv("SININN_GROUP_MAJOR") == nullptr || ato
 // 256 / 8 channel groups with a 32-bit byte offset (conv_prepare: (Cin / 8) * group stride * 4 < 2^32) and the weight-gradient
 // staging descriptors hold 32-bit byte offsets from a tile origin (wgrad_group_plan: the same product + a 64-row tile span).
 // Larger tensors (M = B*H*W >= ~2^22 pixels, e.g. 1024 x 1024 at batch 16, level 0) take the row-major hidden layout.
-bool group_major_fits(size_t M, int W) {
+static bool group_major_fits(size_t M, int W) {
   const unsigned long long gs = (unsigned long long)M * 8ull;                       // floats between channel groups
   return (SININN_HIDDEN / 8) * gs * 4ull + 64ull * (unsigned long long)W * 8ull * 4ull < (1ull << 32);
 }
+extern "C" int sininn_glow_group_major_fits(int B, int H, int W) { return group_major_fits((size_t)B * H * W, W) ? 1 : 0; }
 static bool group_major_hidden(const sininn_glow_args* a, const sininn_subnet* net) {
   const size_t M = (size_t)a->B * a->H * a->W;
   return g_group_major && a->dtype == 0 && a->ksize == 3 && (net->winograd & 15) == 15 && group_major_fits(M, a->W) && wgrad_grouping_enabled();
@@ -255,12 +216,14 @@ static Saved saved_layout(float* base, size_t M, int co_a, int co_b, bool bf16 =
   return s;
 }
 
-size_t glow_saved_floats(int B, int H, int W, int C, int dtype) {
+static size_t glow_saved_floats(int B, int H, int W, int C, int dtype) {
   const size_t M = (size_t)B * H * W;
   const int big = C - C / 2;
   const size_t hid = dtype == 1 ? M * SININN_HIDDEN / 2 : M * SININN_HIDDEN;
   return 2 * align64(hid) + 3 * align64(M * big) + (dtype == 1 ? 2 * align64(padded_pixels(B, H, W) * (SININN_HIDDEN / 32)) : 0) + 64;
 }
+extern "C" size_t sininn_glow_saved_floats(int B, int H, int W, int C) { return glow_saved_floats(B, H, W, C, 0); }
+extern "C" size_t sininn_glow_saved_floats_dtype(int B, int H, int W, int C, int dtype) { return glow_saved_floats(B, H, W, C, dtype); }
 
 struct Scratch { float *dr_b, *dh_b, *dy_first, *dr_a, *dh_a; void* ws; size_t ws_bytes; void* slab[2]; size_t slab_bytes[2]; void* slab2[2]; size_t slab2_bytes[2]; size_t total_bytes; };
 static Scratch scratch_layout(void* basep, int B, int H, int W, int C, int ksize, int co_a, int co_b, int dtype = 0) {
@@ -275,10 +238,10 @@ static Scratch scratch_layout(void* basep, int B, int H, int W, int C, int ksize
   s.dh_a = base + o; o += align64(M * SININN_HIDDEN);
   size_t w = 0;
   const int cond_a = C - co_a;
-  const size_t cands[4] = {wgrad_workspace_bytes(2 * co_b, SININN_HIDDEN, ksize, B, H, W),
-                           wgrad_workspace_bytes(SININN_HIDDEN, co_a, ksize, B, H, W),
-                           wgrad_workspace_bytes(2 * co_a, SININN_HIDDEN, ksize, B, H, W),
-                           wgrad_workspace_bytes(SININN_HIDDEN, cond_a, ksize, B, H, W)};
+  const size_t cands[4] = {sininn_wgrad_workspace_bytes(2 * co_b, SININN_HIDDEN, ksize, B, H, W),
+                           sininn_wgrad_workspace_bytes(SININN_HIDDEN, co_a, ksize, B, H, W),
+                           sininn_wgrad_workspace_bytes(2 * co_a, SININN_HIDDEN, ksize, B, H, W),
+                           sininn_wgrad_workspace_bytes(SININN_HIDDEN, cond_a, ksize, B, H, W)};
   for (size_t c : cands) w = c > w ? c : w;
   {  // grouped weight gradients: the four convs' slabs live side by side
     const int cond_b = co_a;
@@ -299,7 +262,7 @@ static Scratch scratch_layout(void* basep, int B, int H, int W, int C, int ksize
         int n = 0;
         for (int i = 0; i < 4; ++i)
           if (mask & (1 << i)) sub[n++] = it[i];
-        const size_t bytes = wgrad_group_workspace_bytes(sub, n, B, H, W, ksize);
+        const size_t bytes = sininn_wgrad_group_workspace_bytes(sub, n, B, H, W, ksize);
         w = bytes > w ? bytes : w;
       }
     }
@@ -311,7 +274,7 @@ static Scratch scratch_layout(void* basep, int B, int H, int W, int C, int ksize
   size_t so = (o * sizeof(float) + w + 255) / 256 * 256;
   const int cond_cin[2] = {C - co_a, co_a}, cos[2] = {co_a, co_b};
   for (int i = 0; i < 2; ++i) {
-    s.slab_bytes[i] = conv_sub1_bwd_shape_supported(ksize, dtype, cond_cin[i], cos[i]) ? conv_sub1_bwd_workspace_bytes(cond_cin[i], cos[i]) : 0;
+    s.slab_bytes[i] = conv_sub1_bwd_shape_supported(ksize, dtype, cond_cin[i], cos[i]) ? sininn_conv_sub1_bwd_workspace_bytes(cond_cin[i], cos[i]) : 0;
     const size_t wide = conv_sub1_bf16_wide_ws_bytes(ksize, dtype, cond_cin[i], cos[i]);
     if (wide > s.slab_bytes[i]) s.slab_bytes[i] = wide;
     s.slab[i] = reinterpret_cast<char*>(base) + so;
@@ -325,11 +288,15 @@ static Scratch scratch_layout(void* basep, int B, int H, int W, int C, int ksize
   return s;
 }
 
-size_t glow_scratch_bytes(int B, int H, int W, int C, int ksize, int dtype) {
+static size_t glow_scratch_bytes(int B, int H, int W, int C, int ksize, int dtype) {
   const int big = C - C / 2;
   // upper bound over both directions (co_a / co_b are C/2 and C - C/2 in some order)
   Scratch s = scratch_layout(nullptr, B, H, W, C, ksize, big, big, dtype);
   return s.total_bytes + 256;
+}
+extern "C" size_t sininn_glow_scratch_bytes(int B, int H, int W, int C, int ksize) { return glow_scratch_bytes(B, H, W, C, ksize, 0); }
+extern "C" size_t sininn_glow_scratch_bytes_dtype(int B, int H, int W, int C, int ksize, int dtype) {
+  return glow_scratch_bytes(B, H, W, C, ksize, dtype);
 }
 
 static int check_common(const sininn_glow_args* a, const char* who) {
@@ -360,7 +327,8 @@ __global__ void hidden_gates_kernel(const float* __restrict__ h, int64_t M, int 
   }
 }
 
-int glow_hidden_gates(const sininn_glow_args* a, int which, unsigned char* gates, hipStream_t st) {
+extern "C" int sininn_glow_hidden_gates(const sininn_glow_args* a, int which, unsigned char* gates, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(a && a->saved && gates && (which == 0 || which == 1), "glow_hidden_gates: bad arguments");
   SININN_CHECK(a->B > 0 && a->H > 0 && a->W > 0 && a->C >= 16, "glow_hidden_gates: bad shape");
   const size_t M = (size_t)a->B * a->H * a->W;
@@ -387,14 +355,14 @@ int glow_hidden_gates(const sininn_glow_args* a, int which, unsigned char* gates
         // mixed precision: h = bf16(relu(fp32 sum + b1)), the sum taken over two 16-channel steps of v_mfma_f32_32x32x16_bf16
         // from zero -- the stand-alone bf16 conv, the pair kernel and the persistent kernels all issue exactly that chain
         c1.w_bf16 = 1; c1.out_bf16 = 1;
-        if (int rc = conv_launch(&c1, st)) return rc;
+        if (int rc = sininn_conv(&c1, st)) return rc;
       } else {
       sininn_conv_args c2 = {};
       c2.in = h; c2.in_stride = SININN_HIDDEN; c2.Cin = SININN_HIDDEN; c2.w = hv[which].net->w2; c2.Np = 2 * hv[which].co;
       c2.B = a->B; c2.H = a->H; c2.W = a->W; c2.ksize = 1; c2.mode = SININN_CONV_LINEAR;
       c2.out = which == 0 ? sv.h_b : sv.h_a; c2.out_stride = 2 * hv[which].co; c2.N = 2 * hv[which].co;
-      SININN_CHECK(conv_pair_k1_supported(&c1, &c2), "glow_hidden_gates: the 1x1 pair kernel is switched off (needed to reproduce the recomputed h)");
-      if (int rc = conv_pair_k1_launch(&c1, &c2, st)) return rc;
+      SININN_CHECK(sininn_conv_pair_k1_supported(&c1, &c2), "glow_hidden_gates: the 1x1 pair kernel is switched off (needed to reproduce the recomputed h)");
+      if (int rc = sininn_conv_pair_k1(&c1, &c2, st)) return rc;
       }
     }
   }
@@ -405,7 +373,8 @@ int glow_hidden_gates(const sininn_glow_args* a, int which, unsigned char* gates
   return 0;
 }
 
-int glow_forward(const sininn_glow_args* a, hipStream_t st) {
+extern "C" int sininn_glow_forward(const sininn_glow_args* a, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = check_common(a, "glow_forward")) return rc;
   const size_t M = (size_t)a->B * a->H * a->W;
   const int C = a->C;
@@ -447,9 +416,9 @@ int glow_forward(const sininn_glow_args* a, hipStream_t st) {
     if (a->no_save && bf16 && a->ksize == 3 && sub3_fusion_enabled()) {
       sininn_conv_args f1 = c1;
       f1.out = nullptr;
-      if (conv_sub3_bf16_supported(&f1, &c2)) {
+      if (sininn_conv_sub3_supported(&f1, &c2)) {
         ClassScope sc(PC_COUPLE, a->ksize, conv_flops(M, a->ksize, c1.Cin, SININN_HIDDEN) + conv_flops(M, a->ksize, SININN_HIDDEN, 2 * h.co), st);
-        if (int rc = conv_sub3_bf16_launch(&f1, &c2, st)) return rc;
+        if (int rc = sininn_conv_sub3(&f1, &c2, st)) return rc;
         continue;
       }
     }
@@ -458,24 +427,24 @@ int glow_forward(const sininn_glow_args* a, hipStream_t st) {
     // algorithmic HBM bytes of a fused 1x1 forward: x, v in; y (+ its compact copy for the first half), s out; + the hidden tensor when stored
     const double fwd_bytes = 4.0 * (double)M * (c1.Cin + 2 * h.co + (a->no_save ? 0 : h.co) + (i == 0 ? h.co : 0)) +
                              ((a->no_save || recompute) ? 0.0 : (double)M * SININN_HIDDEN * (bf16 ? 2 : 4));
-    if (recompute && conv_sub1_fwd_supported(&c1, &c2)) {
+    if (recompute && sininn_conv_sub1_fwd_supported(&c1, &c2)) {
       // ... and the forward is the persistent twin of that kernel: conv1 -> conv2 -> coupling + log-det, weights resident on chip
       ClassScope sc(PC_COUPLE, a->ksize, conv_flops(M, a->ksize, c1.Cin, SININN_HIDDEN) + conv_flops(M, a->ksize, SININN_HIDDEN, 2 * h.co), st, fwd_bytes);
-      if (int rc = conv_sub1_fwd_launch(&c1, &c2, st)) return rc;
+      if (int rc = sininn_conv_sub1_fwd(&c1, &c2, st)) return rc;
       continue;
     }
-    if (conv_pair_k1_supported(&c1, &c2) && (a->no_save || recompute || conv_pair_k1_preferred(&c1))) {
+    if (sininn_conv_pair_k1_supported(&c1, &c2) && (a->no_save || recompute || conv_pair_k1_preferred(&c1))) {
       if (a->no_save || recompute) c1.out = nullptr; // ... and then the hidden tensor never reaches HBM
       ClassScope sc(PC_COUPLE, a->ksize, conv_flops(M, a->ksize, c1.Cin, SININN_HIDDEN) + conv_flops(M, a->ksize, SININN_HIDDEN, 2 * h.co), st, fwd_bytes);
-      if (int rc = conv_pair_k1_launch(&c1, &c2, st)) return rc;
+      if (int rc = sininn_conv_pair_k1(&c1, &c2, st)) return rc;
       continue;
     }
     {
       ClassScope sc(PC_CONV1, a->ksize, conv_flops(M, a->ksize, c1.Cin, SININN_HIDDEN), st);
-      if (bf16 && a->ksize == 3 && !a->no_save && conv3_smallk_bf16_supported(&c1)) {
+      if (bf16 && a->ksize == 3 && !a->no_save && sininn_conv3_smallk_bits_supported(&c1)) {
         // small-K conv1 of a training pass: the gates go out as a bit mask too (the backward's masked data gradient reads it)
         if (int rc = conv3_smallk_bf16_launch_bits(&c1, i == 0 ? sv.bits_a : sv.bits_b, st)) return rc;
-      } else if (int rc = conv_launch(&c1, st)) return rc;
+      } else if (int rc = sininn_conv(&c1, st)) return rc;
     }
     hipEvent_t e0, e1;
     unsigned long long* stamp = nullptr;
@@ -485,14 +454,15 @@ int glow_forward(const sininn_glow_args* a, hipStream_t st) {
     if (timed) (void)hipEventRecord(e0, st);
     {
       ClassScope sc(PC_COUPLE, a->ksize, conv_flops(M, a->ksize, SININN_HIDDEN, 2 * h.co), st);
-      if (int rc = conv_launch(&c2, st)) return rc;
+      if (int rc = sininn_conv(&c2, st)) return rc;
     }
     if (timed) (void)hipEventRecord(e1, st);
   }
   return 0;
 }
 
-int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
+extern "C" int sininn_glow_backward(const sininn_glow_args* a, void* stream, void* wgrad_stream) {
+  hipStream_t st = ST(stream), wst = ST(wgrad_stream);
   if (int rc = check_common(a, "glow_backward")) return rc;
   SININN_CHECK(a->dout && a->dx && a->scratch, "glow_backward: null tensor");
   SININN_CHECK(a->s1.w1_dgrad && a->s1.w2_dgrad && a->s2.w1_dgrad && a->s2.w2_dgrad, "glow_backward: missing dgrad weights");
@@ -539,7 +509,7 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
     const sininn_subnet* net = h.net;
     if (do_coupling) {
       ClassScope sc(PC_CBWD, 3, 0.0, st);
-      if (int rc = coupling_bwd_launch(dy, dy_stride, dy_map, vy, vy_stride, vy_map, sbuf, a->gld, B, HW, h.co, a->clamp, inv,
+      if (int rc = sininn_coupling_bwd(dy, dy_stride, dy_map, vy, vy_stride, vy_map, sbuf, a->gld, B, HW, h.co, a->clamp, inv,
                                        dr, a->dx + h.base, C, st)) return rc;
     }
     const bool gm = group_major_hidden(a, net);
@@ -559,7 +529,7 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
       else {
         if (int rc = order_after(wst, st)) return rc;
         ClassScope scp(PC_WGRAD, k, conv_flops(M, k, SININN_HIDDEN, 2 * h.co), wst);
-        if (int rc = wgrad_launch(hbuf, SININN_HIDDEN, SININN_HIDDEN, dr, 2 * h.co, 2 * h.co, B, H, W, k, net->gw2, net->gb2,
+        if (int rc = sininn_wgrad(hbuf, SININN_HIDDEN, SININN_HIDDEN, dr, 2 * h.co, 2 * h.co, B, H, W, k, net->gw2, net->gb2,
                                   sc.ws, sc.ws_bytes, wst)) return rc;
       }
     }
@@ -618,7 +588,7 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
       const size_t wide_ws = conv_sub1_bf16_wide_ws_bytes(k, a->dtype, cond_cin, h.co);
       sininn_conv_args d2w = d2;
       d2w.out = nullptr;
-      if (bf16 && !skip_d1 && net->gw1 && wide_ws > 0 && sc.slab_bytes[which] >= wide_ws && conv_pair_k1_supported(&d2, &d1) &&
+      if (bf16 && !skip_d1 && net->gw1 && wide_ws > 0 && sc.slab_bytes[which] >= wide_ws && sininn_conv_pair_k1_supported(&d2, &d1) &&
           conv_sub1_bf16_wide_bwd_supported(&d2w, &d1)) {
         int slabs = 0;
         {
@@ -632,10 +602,10 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
         return conv_sub1_bf16_wide_reduce(sc.slab[which], slabs, net->gw1, net->gb1, wst);
       }
     }
-    const bool pair = !skip_d1 && conv_pair_k1_supported(&d2, &d1);
+    const bool pair = !skip_d1 && sininn_conv_pair_k1_supported(&d2, &d1);
     if (pair) {
       ClassScope scp(PC_DGRAD2, k, conv_flops(M, k, 2 * h.co, SININN_HIDDEN) + conv_flops(M, k, SININN_HIDDEN, cond_cin), st);
-      if (int rc = conv_pair_k1_launch(&d2, &d1, st)) return rc;
+      if (int rc = sininn_conv_pair_k1(&d2, &d1, st)) return rc;
     } else {
       ClassScope scp(PC_DGRAD2, k, conv_flops(M, k, 2 * h.co, SININN_HIDDEN), st);
       // the forward pass wrote the gate bit mask iff its conv1 ran on the small-K kernel: the same predicate on the same descriptor
@@ -643,16 +613,16 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
       f1.in = cond; f1.in_stride = cond_stride; f1.Cin = cond_cin; f1.w = net->w1; f1.bias = net->b1; f1.Np = SININN_HIDDEN;
       f1.B = B; f1.H = H; f1.W = W; f1.ksize = k; f1.mode = SININN_CONV_RELU;
       f1.out = const_cast<float*>(hbuf); f1.out_stride = SININN_HIDDEN; f1.N = SININN_HIDDEN; f1.w_bf16 = 1; f1.out_bf16 = 1;
-      if (bf16 && k == 3 && conv3_smallk_bf16_supported(&f1) && conv3_smallk_bf16_supported(&d2)) {
+      if (bf16 && k == 3 && sininn_conv3_smallk_bits_supported(&f1) && sininn_conv3_smallk_bits_supported(&d2)) {
         if (int rc = conv3_smallk_bf16_launch_bits(&d2, which_half == 0 ? sv.bits_a : sv.bits_b, st)) return rc;
-      } else if (int rc = conv_launch(&d2, st)) return rc;
+      } else if (int rc = sininn_conv(&d2, st)) return rc;
     }
     if (net->gw1) {
       if (grouped) add_item(cond, cond_stride, cond_cin, dh, SININN_HIDDEN, SININN_HIDDEN, net->gw1, net->gb1, 0, bf16 ? 1 : 0, 0, gs);
       else {
         if (int rc = order_after(wst, st)) return rc;
         ClassScope scp(PC_WGRAD, k, conv_flops(M, k, cond_cin, SININN_HIDDEN), wst);
-        if (int rc = wgrad_launch(cond, cond_stride, cond_cin, dh, SININN_HIDDEN, SININN_HIDDEN, B, H, W, k, net->gw1, net->gb1,
+        if (int rc = sininn_wgrad(cond, cond_stride, cond_cin, dh, SININN_HIDDEN, SININN_HIDDEN, B, H, W, k, net->gw1, net->gb1,
                                   sc.ws, sc.ws_bytes, wst)) return rc;
       }
       if (grouped && (last_half || per_half) && n_items > 0) {     // every input of the group is queued on `st` now
@@ -660,13 +630,13 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
         double fl = 0.0;
         for (int i = 0; i < n_items; ++i) fl += conv_flops(M, k, items[i].Cin, items[i].N);
         ClassScope scp(PC_WGRAD, k, fl, wst);
-        if (int rc = wgrad_group_launch(items, n_items, B, H, W, k, sc.ws, sc.ws_bytes, wst)) return rc;
+        if (int rc = sininn_wgrad_group(items, n_items, B, H, W, k, sc.ws, sc.ws_bytes, wst)) return rc;
         n_items = 0;
       }
     }
     if (skip_d1 || pair) return 0;                   // the gradient w.r.t. this half's condition is not needed / already done
     ClassScope scp(PC_DGRAD1, k, conv_flops(M, k, SININN_HIDDEN, cond_cin), st);
-    return conv_launch(&d1, st);
+    return sininn_conv(&d1, st);
   };
 
   // ---- second half first: its condition is the first half's compact output -------------------------
@@ -699,7 +669,7 @@ int glow_backward(const sininn_glow_args* a, hipStream_t st, hipStream_t wst) {
     double fl = 0.0;
     for (int i = 0; i < n_items; ++i) fl += conv_flops(M, k, items[i].Cin, items[i].N);
     ClassScope scp(PC_WGRAD, k, fl, wst);
-    if (int rc = wgrad_group_launch(items, n_items, B, H, W, k, sc.ws, sc.ws_bytes, wst)) return rc;
+    if (int rc = sininn_wgrad_group(items, n_items, B, H, W, k, sc.ws, sc.ws_bytes, wst)) return rc;
   }
   return 0;
 }

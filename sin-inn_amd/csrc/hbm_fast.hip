@@ -54,8 +54,9 @@ __global__ void frames_to_u8_strided_kernel(const float* __restrict__ in, Str4 i
   }
 }
 
-int frames_to_u8_launch(const float* in, const int64_t is[4], uint8_t* out, int B, int C, int H, int W, int wrap,
-                        hipStream_t st) {
+extern "C" int sininn_frames_to_u8(const float* in, const int64_t is[4], uint8_t* out, int B, int C, int H, int W, int wrap,
+                                   void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && is && out && B > 0 && C > 0 && H > 0 && W > 0, "frames_to_u8: bad arguments");
   const int64_t n = (int64_t)B * C * H * W;
   const bool dense = is[1] == 1 && is[3] == C && is[2] == (int64_t)W * C && is[0] == (int64_t)H * W * C &&
@@ -133,8 +134,9 @@ __global__ void squeeze_rows_kernel(const float* __restrict__ in, float* __restr
   }
 }
 
-int squeeze_rows_launch(const float* in, float* out, int B, int C, int H, int W, int levels, int inverse, const int* map,
-                        hipStream_t st) {
+extern "C" int sininn_squeeze_rows(const float* in, float* out, int B, int C, int H, int W, int levels, int inverse, const int* map,
+                                   void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(in && out && B > 0 && C > 0 && H > 0 && W > 0 && levels >= 0 && levels <= 4, "squeeze_rows: bad arguments");
   SININN_CHECK((H % (1 << levels)) == 0 && (W % (1 << levels)) == 0, "squeeze_rows: H=%d W=%d not divisible by 2^%d", H, W, levels);
   const int64_t total = (int64_t)B * C * H * W;
@@ -243,8 +245,9 @@ __global__ void sample_pairs_planar_kernel(const uint8_t* __restrict__ clip, con
   }
 }
 
-int sample_pairs_planar_launch(const uint8_t* clip, const int* idx, int n, int T, int H, int W, int gap, void* out0, void* out1,
-                               int bf16, hipStream_t st) {
+extern "C" int sininn_sample_pairs(const uint8_t* clip, const int* idx, int n, int T, int H, int W, int gap, void* out0, void* out1,
+                                   int bf16, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(clip && idx && out0 && out1 && n > 0 && T > 0 && H > 0 && W > 0, "sample_pairs: bad arguments");
   const int64_t HW = (int64_t)H * W;
   SININN_CHECK(HW % 4 == 0 && aligned16(clip) && aligned16(out0) && aligned16(out1), "sample_pairs: H*W %% 4 == 0 and 16-byte aligned buffers");

@@ -9,8 +9,6 @@
 
 namespace sininn {
 
-size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors);
-
 namespace {
 
 constexpr int LAMB_THREADS = 256;
@@ -192,7 +190,7 @@ int lamb_check(const sininn_lamb_args* a, const char* who) {
   SININN_CHECK(a->step >= 1, "%s: step must be >= 1 (got %d)", who, a->step);
   SININN_CHECK(a->n_groups >= 1 && a->n_groups <= 4096 && a->group >= 0 && a->group < a->n_groups,
                "%s: group index %d outside 0..%d", who, a->group, a->n_groups - 1);
-  const size_t need = lamb_workspace_bytes(a->n_chunks, a->n_tensors);
+  const size_t need = sininn_lamb_workspace_bytes(a->n_chunks, a->n_tensors);
   SININN_CHECK(a->workspace_bytes >= need, "%s: workspace holds %zu bytes, needs %zu", who, a->workspace_bytes, need);
   return 0;
 }
@@ -201,12 +199,13 @@ static inline int lamb_grid(int64_t n_chunks) { return (int)(n_chunks < LAMB_MAX
 
 }  // namespace
 
-size_t lamb_workspace_bytes(int64_t n_chunks, int n_tensors) {
+extern "C" size_t sininn_lamb_workspace_bytes(int64_t n_chunks, int n_tensors) {
   if (n_chunks <= 0 || n_tensors <= 0) return 0;
   return pad4((size_t)n_tensors) * sizeof(float) + 3 * pad2((size_t)n_chunks) * sizeof(double);
 }
 
-int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st) {
+extern "C" int sininn_lamb_grad_norm(const sininn_lamb_args* a, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = lamb_check(a, "lamb_grad_norm")) return rc;
   const LambWs ws = lamb_ws(a->workspace, a->n_chunks, a->n_tensors);
   const LambChunk* chunks = reinterpret_cast<const LambChunk*>(a->chunks);
@@ -218,7 +217,8 @@ int lamb_grad_norm_launch(const sininn_lamb_args* a, hipStream_t st) {
   return 0;
 }
 
-int lamb_step_launch(const sininn_lamb_args* a, hipStream_t st) {
+extern "C" int sininn_lamb_step(const sininn_lamb_args* a, void* stream) {
+  hipStream_t st = ST(stream);
   if (int rc = lamb_check(a, "lamb_step")) return rc;
   const LambWs ws = lamb_ws(a->workspace, a->n_chunks, a->n_tensors);
   const LambChunk* chunks = reinterpret_cast<const LambChunk*>(a->chunks);

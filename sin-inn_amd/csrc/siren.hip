@@ -35,9 +35,6 @@
 
 namespace sininn {
 
-size_t hidden_wgrad_part_floats(int ntiles);           // flownet.hip
-int hidden_wgrad_launch(int ntiles, const float* dh, const float* in, float* part, float* gw, float* gb, hipStream_t st);
-
 namespace {
 
 constexpr int SR_IN = 3;
@@ -322,7 +319,7 @@ size_t part_floats(int ntiles) {
 }  // namespace
 
 // the support table; a refusal leaves its reason, with the table, as the library's last error
-int siren_supported(const sininn_siren_args* a, const char* who) {
+static int siren_supported(const sininn_siren_args* a, const char* who) {
   if (a == nullptr || a->struct_bytes != sizeof(sininn_siren_args)) return 0;
   const bool ok = a->in_dim == SR_IN && a->hidden == FN_HID && a->layers == SR_SINES - 1 && a->out_dim == FN_OUT && a->omega > 0.f &&
                   a->omega <= 3.4028234664e38f;   // finite and positive: a NaN fails both comparisons
@@ -331,13 +328,14 @@ int siren_supported(const sininn_siren_args* a, const char* who) {
               a->in_dim, a->hidden, a->layers, a->out_dim, (double)a->omega, SR_IN, FN_HID, SR_SINES - 1, FN_OUT);
   return ok;
 }
+extern "C" int sininn_siren_supported(const sininn_siren_args* a) { return siren_supported(a, "sininn_siren_supported"); }
 
-size_t siren_saved_bytes(int64_t n) {
+extern "C" size_t sininn_siren_saved_bytes(int64_t n) {
   if (n <= 0) return 0;
   return (size_t)SR_SINES * (size_t)((n + FN_P - 1) / FN_P) * FN_P * FN_HID * sizeof(float);
 }
 
-size_t siren_workspace_bytes(int64_t n) {
+extern "C" size_t sininn_siren_workspace_bytes(int64_t n) {
   if (n <= 0 || n > ((int64_t)1 << 22)) return 0;
   const int ntiles = (int)((n + FN_P - 1) / FN_P);
   const size_t lstride = (size_t)ntiles * FN_P * FN_HID;
@@ -358,13 +356,14 @@ static int check_args(const sininn_siren_args* a, const char* who, SirenDev& q, 
   return 0;
 }
 
-int siren_forward_launch(const sininn_siren_args* a, const sininn_flownet_call* call, hipStream_t st) {
+extern "C" int sininn_siren_forward(const sininn_siren_args* a, const sininn_flownet_call* call, void* stream) {
+  hipStream_t st = ST(stream);
   Call c;
   if (int rc = check_call(call, "siren", CALL_FORWARD, c)) return rc;
   SirenDev q;
   const char* const who = c.who();
   if (int rc = check_args(a, who, q, c.pl())) return rc;
-  if (int rc = check_forward_buffers(a, who, siren_saved_bytes(q.N), q)) return rc;
+  if (int rc = check_forward_buffers(a, who, sininn_siren_saved_bytes(q.N), q)) return rc;
   if (raise_lds(siren_fwd_kernel, SR_LDS, "siren_forward")) return 1;
   hipLaunchKernelGGL(siren_fwd_kernel, dim3(chain_blocks(q.ntiles)), dim3(FN_NTHR), SR_LDS, st, q);   // two resident blocks per CU
   SININN_LAUNCH_CHECK("siren_forward");
@@ -372,7 +371,8 @@ int siren_forward_launch(const sininn_siren_args* a, const sininn_flownet_call* 
 }
 
 // POSEGRAD (with a pose list): the chain kernel that also writes the gradient of the coordinates; everything else is the same
-int siren_backward_launch(const sininn_siren_args* a, const sininn_flownet_call* call, hipStream_t st) {
+extern "C" int sininn_siren_backward(const sininn_siren_args* a, const sininn_flownet_call* call, void* stream) {
+  hipStream_t st = ST(stream);
   Call c;
   if (int rc = check_call(call, "siren", CALL_BACKWARD, c)) return rc;
   SirenPoseDev q;
@@ -381,7 +381,7 @@ int siren_backward_launch(const sininn_siren_args* a, const sininn_flownet_call*
   SININN_CHECK(!c.has(SININN_FLOWNET_POSEGRAD) || g_poses != nullptr, "%s: null g_poses", who);
   if (int rc = check_args(a, who, q, c.pl())) return rc;
   q.g_poses = g_poses;
-  if (int rc = check_backward_buffers<SR_SINES + 1>(a, who, siren_saved_bytes(q.N), siren_workspace_bytes(q.N), q)) return rc;
+  if (int rc = check_backward_buffers<SR_SINES + 1>(a, who, sininn_siren_saved_bytes(q.N), sininn_siren_workspace_bytes(q.N), q)) return rc;
   const size_t lstride = (size_t)q.ntiles * FN_P * FN_HID;
   float* const ws = static_cast<float*>(a->workspace);
   float* const wt = ws + 2 * (SR_SINES - 1) * lstride;

@@ -755,16 +755,16 @@ __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(WgradGroup g) {
 
 struct WgradPlan { int RT, CT, Nr, Cc, nblk, cblk, S, tiles_per_split, ntiles, tiles_x, tiles_y; size_t bytes; bool use32; bool wino; int th; int kh; };
 
-void wgrad_set_bf16_mfma(int on);
+static void wgrad_set_bf16_mfma(int on);
 static bool g_wgrad_force16 = false;   // test hook
 static bool g_wgrad_wino = true;       // Winograd weight gradient for 3x3 (test hook bit 1 disables)
 static bool g_wgrad_wino_th8 = false;  // test hook bit 2: 8-row pixel tiles in the Winograd weight gradient
 static bool g_wgrad_wino_kh2 = false;  // test hook bit 3: 8-wave blocks with an in-block k split (half the slabs; same kernel
                                        // time, but 3 % slower end to end when other streams' kernels co-run) -- off
-void wgrad_set_wide_c(int on);
+static void wgrad_set_wide_c(int on);
 static int g_wgrad_group_mode = 1;     // 1: whole block (4 convs), 2: per half-coupling (2 convs); test hook bit 5 selects 2
 static bool g_wgrad_grouped = true;    // test hook bit 4 clears: the block executor issues one launch pair per conv (round-1 path)
-void wgrad_set_force16(int on) { g_wgrad_force16 = (on & 1) != 0; g_wgrad_wino = (on & 2) == 0; g_wgrad_wino_th8 = (on & 4) != 0; g_wgrad_wino_kh2 = (on & 8) != 0; g_wgrad_grouped = (on & 16) == 0; g_wgrad_group_mode = (on & 32) ? 2 : 1; wgrad_set_bf16_mfma((on & 64) == 0); wgrad_set_wide_c((on & 128) == 0); }
+extern "C" void sininn_wgrad_test_hooks(int on) { g_wgrad_force16 = (on & 1) != 0; g_wgrad_wino = (on & 2) == 0; g_wgrad_wino_th8 = (on & 4) != 0; g_wgrad_wino_kh2 = (on & 8) != 0; g_wgrad_grouped = (on & 16) == 0; g_wgrad_group_mode = (on & 32) ? 2 : 1; wgrad_set_bf16_mfma((on & 64) == 0); wgrad_set_wide_c((on & 128) == 0); }
 bool wgrad_grouping_enabled() { return g_wgrad_grouped && g_wgrad_wino && !g_wgrad_force16; }
 int wgrad_group_mode() { return g_wgrad_group_mode; }
 
@@ -799,7 +799,7 @@ static WgradPlan make_plan(int N, int Cin, int ksize, int B, int H, int W) {
   return pl;
 }
 
-size_t wgrad_workspace_bytes(int N, int Cin, int ksize, int B, int H, int W) {
+extern "C" size_t sininn_wgrad_workspace_bytes(int N, int Cin, int ksize, int B, int H, int W) {
   return make_plan(N, Cin, ksize, B, H, W).bytes;
 }
 
@@ -812,8 +812,9 @@ static void launch_wgrad(const WgradPlan& pl, const WgradDev& d, hipStream_t st)
   else hipLaunchKernelGGL((wgrad_mfma_kernel<KS, 4, 2, 2, 1>), grid, dim3(256), 0, st, d);
 }
 
-int wgrad_launch(const float* in, int in_stride, int Cin, const float* dout, int dout_stride, int N,
-                 int B, int H, int W, int ksize, float* gw, float* gb, void* ws, size_t ws_bytes, hipStream_t st) {
+extern "C" int sininn_wgrad(const float* in, int in_stride, int Cin, const float* dout, int dout_stride, int N,
+                            int B, int H, int W, int ksize, float* gw, float* gb, void* ws, size_t ws_bytes, void* stream) {
+  hipStream_t st = ST(stream);
   SININN_CHECK(ksize == 1 || ksize == 3, "wgrad: ksize %d not in {1,3}", ksize);
   SININN_CHECK(in && dout && gw && ws, "wgrad: null pointer");
   SININN_CHECK(Cin > 0 && Cin % 4 == 0 && N > 0 && N % 4 == 0, "wgrad: Cin=%d and N=%d must be multiples of 4", Cin, N);
@@ -1202,8 +1203,8 @@ struct WgradGroupPlan { WgradGroup g; int grad_blocks, red_blocks; size_t bytes;
 static bool g_wgrad_wide_c = true;      // test hook bit 7 clears: N <= 32 problems use the 64 x 32 block shape like everything else
                                         // (and Cin <= 32 problems of the bf16 kernel its 64 x 64 blocks instead of 128 x 32)
 static bool g_wgrad_bf16_mfma = true;   // test hook bit 6 clears: bf16-operand problems accumulate on the f32 pipe (Winograd)
-void wgrad_set_bf16_mfma(int on) { g_wgrad_bf16_mfma = on != 0; }
-void wgrad_set_wide_c(int on) { g_wgrad_wide_c = on != 0; }
+static void wgrad_set_bf16_mfma(int on) { g_wgrad_bf16_mfma = on != 0; }
+static void wgrad_set_wide_c(int on) { g_wgrad_wide_c = on != 0; }
 
 // f32_quads (the IRN bf16 DenseBlock executor only): an fp32 operand needs a channel count % 4, not % 8, on the bf16 matrix pipe --
 // its staging loads 4-channel quads (WgStage / load_d); the bf16 operand keeps % 8.  conv5's N = 84 / 108 / 12 / 180 are such.
@@ -1293,7 +1294,7 @@ static int plan_group(const sininn_wgrad_item* items, int n, int B, int H, int W
   return 0;
 }
 
-size_t wgrad_group_workspace_bytes(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize) {
+extern "C" size_t sininn_wgrad_group_workspace_bytes(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize) {
   WgradGroupPlan pl;
   if (plan_group(items, n, B, H, W, ksize, nullptr, pl)) return 0;
   return pl.bytes;
@@ -1309,9 +1310,9 @@ size_t wgrad_group_mixed_workspace_bytes(const sininn_wgrad_item* items, int n, 
 static int wgrad_group_run(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
                            hipStream_t st, bool f32_quads);
 
-int wgrad_group_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  return wgrad_group_run(items, n, B, H, W, ksize, ws, ws_bytes, st, false);
+extern "C" int sininn_wgrad_group(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return wgrad_group_run(items, n, B, H, W, ksize, ws, ws_bytes, ST(stream), false);
 }
 
 int wgrad_group_mixed_launch(const sininn_wgrad_item* items, int n, int B, int H, int W, int ksize, void* ws, size_t ws_bytes,

@@ -25,6 +25,69 @@ def test_abi_exports_every_declared_symbol():
     assert handle.sininn_version() == 4
 
 
+def _header_prototypes():
+    """{name: (return type, [parameter declarations])} of every sininn_* function include/sininn.h declares."""
+    text = open(os.path.join(ROOT, 'include', 'sininn.h')).read()
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    text = re.sub(r'^[ \t]*#[^\n]*(\\\n[^\n]*)*', ' ', text, flags=re.M)        # #define / #include / #ifdef lines
+    text = re.sub(r'(\btypedef\s+)?\b(struct|enum)\b[^;{}()]*\{[^{}]*\}[^;]*;', ' ', text)   # struct typedefs and enums
+    protos = {}
+    for ret, name, params in re.findall(r'([A-Za-z_][\w \t\n\*]*?)\b(sininn_\w+)\s*\(([^()]*)\)\s*;', text):
+        assert name not in protos, f'{name} is declared twice'
+        params = [p.strip() for p in params.split(',')]
+        protos[name] = (' '.join(ret.split()), [] if params == ['void'] else params)
+    return protos
+
+
+def _c_class(decl, is_return=False):
+    if '*' in decl or '[' in decl:
+        return 'pointer'
+    words = [w for w in decl.split() if w != 'const']
+    if not is_return:
+        words = words[:-1]                                   # the parameter's name
+    base = ' '.join(words)
+    return {'int': 'int', 'unsigned': 'int', 'unsigned int': 'int', 'int64_t': 'int64', 'size_t': 'size_t', 'float': 'float',
+            'double': 'double', 'void': 'void'}[base]
+
+
+def _ctypes_class(t):
+    import ctypes as C
+    from sin_inn_amd import _lib
+    if t is None:
+        return 'void'
+    if t in (C.c_void_p, C.c_char_p, _lib.I64x4) or issubclass(t, (C._Pointer, C.Array)):
+        return 'pointer'
+    return {C.c_int: 'int', C.c_uint: 'int', C.c_int64: 'int64', C.c_size_t: 'size_t', C.c_float: 'float', C.c_double: 'double'}[t]
+
+
+def test_sigs_agree_with_the_header():
+    # needs no built library: the prototypes of include/sininn.h against the ctypes signatures of _lib._SIGS, class by class
+    import sin_inn_amd
+    from sin_inn_amd import _lib
+    protos = _header_prototypes()
+    assert len(protos) > 100 and 'sininn_flow_error_stash' in protos and 'sininn_version' in protos
+    missing = sorted(set(_lib._SIGS) - set(protos))
+    assert not missing, f'_SIGS names that include/sininn.h does not declare: {missing}'
+    rowless = sorted(set(protos) - set(_lib._SIGS))
+    assert not rowless, f'prototypes of include/sininn.h without a row in _SIGS: {rowless}'
+    # the undeclared test hooks are the other table; one that the header comes to declare belongs in _SIGS, where it is checked
+    declared_hooks = sorted(set(_lib._TEST_HOOKS) & set(protos))
+    assert not declared_hooks, f'_TEST_HOOKS names that include/sininn.h declares (move them to _SIGS): {declared_hooks}'
+    assert not set(_lib._TEST_HOOKS) & set(_lib._SIGS) and set(_lib.EXPORTED) == set(_lib._SIGS) | set(_lib._TEST_HOOKS)
+    wrong = []
+    for name in sorted(set(protos) & set(_lib._SIGS)):
+        ret, params = protos[name]
+        res, args = _lib._SIGS[name]
+        want = [_c_class(ret, True)] + [_c_class(p) for p in params]
+        got = [_ctypes_class(res)] + [_ctypes_class(t) for t in args]
+        if want != got:
+            where = next((i for i, (a, b) in enumerate(zip(want, got)) if a != b), min(len(want), len(got)))
+            wrong.append(f'{name}: header {len(params)} parameters, _SIGS {len(args)}; first difference at position {where - 1} '
+                         f'(-1 = return): header {want[where:where + 1]}, _SIGS {got[where:where + 1]}')
+    assert not wrong, '\n'.join(wrong)
+
+
 def test_cpu_tensors_are_refused_loudly():
     import sin_inn_amd
     from sin_inn_amd import ops
